@@ -7,12 +7,16 @@ evaluation + accept/reject, and a residual/Jacobian/JtJ evaluation whenever the
 step is accepted) with all observations resident in HBM. The timed region runs
 whole solves from the perturbed initial guess (reference default tolerances)
 until exactly K iterations have been made; each solve's initial evaluation
-(iteration 0) is inside the timed region and not counted as a step.
+(iteration 0) is inside the timed region and not counted as a step. By default
+the timed region is one sample of K iterations (--repeats R: R samples of K,
+the median reported).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. --dump-outputs DIR writes what the last timed
+solve handed back (see dump_outputs) as DIR/<name>.npy: the inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import ctypes
@@ -27,6 +31,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def algorithmic_bytes_per_jacobian_launch(scene):
@@ -329,6 +334,34 @@ def roofline_object(scene, world, args, ms_per_step, iter_bytes, dense_ms, dense
     }
 
 
+def dump_outputs(path, built, scene, summary):
+    """Writes what a caller of the timed path holds after its last step, as float64 arrays path/<name>.npy: the solve's
+    summary (counts and costs, no timings) and iteration log, the estimates of the control points and of every sensor
+    block, and each sensor's residuals at those estimates with their validity flags (Sensor::UpdateResiduals)."""
+    from calico_amd import _capi, synthetic as syn
+    P = built.problem
+    fields = ("termination_type", "num_iterations", "num_successful_steps", "num_unsuccessful_steps",
+              "num_jacobian_evaluations", "num_cost_evaluations", "initial_cost", "final_cost")
+    log_fields = [f for f, _ in _capi.Iteration._fields_ if f != "reserved"]
+    sensors, ctrl = syn.read_back(built, scene)
+    out = {"summary": [getattr(summary, f) for f in fields],
+           "iterations": [[getattr(it, f) for f in log_fields] for it in P.iterations()],
+           "control_points": ctrl}
+    for i, (s, est, sid) in enumerate(zip(scene.sensors, sensors, built.sensor_ids)):
+        for k in ("intrinsics", "t", "q", "latency"):
+            out["sensor%d_%s" % (i, k)] = est[k]
+        if s.n:
+            r, valid = P.residuals(sid, s.n, s.dim, check=False)
+            out["sensor%d_residuals" % i], out["sensor%d_valid" % i] = r, valid
+    out = {k: np.asarray(v, np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -339,19 +372,25 @@ def main():
     ap.add_argument("--sync-every", type=int, default=8)
     ap.add_argument("--force-collective", action="store_true",
                     help="exercise the sharding + all-reduce path even with one rank (validation)")
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed samples of --steps iterations each (default: 25 when --steps <= 50, else 5); the median is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed samples of --steps iterations each, the median is reported (default 1: the timed region is "
+                         "exactly --steps iterations; 0: as many samples as --min-seconds asks for, at least 25 when "
+                         "--steps <= 50, else 5)")
     ap.add_argument("--min-seconds", type=float, default=10.5,
-                    help="without --repeats: as many samples as it takes to keep the GPU busy this long")
+                    help="with --repeats 0: as many samples as it takes to keep the GPU busy this long")
     ap.add_argument("--poor-start", type=float, default=0.0,
                     help="move the start away from the truth: focal lengths x (1 + F/100), translations + F cm, control "
                          "points + F mrad / F mm of noise (context runs: many rejected steps); 0 = the reference test's perturbation")
     ap.add_argument("--tagging-passes", type=int, default=0,
                     help="outlier tagging loop (configs[4]): solve, tag |r| > 3 on the device, re-solve, N times; reported, untimed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed region, write what its last solve handed back as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.repeats < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --repeats >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -552,10 +591,12 @@ def main():
     wu_ms, wu_n = read_phases()
     # timed region: only the Jacobian kernel (phase 0) and the reduced-system launch (phase 6: the longest kernel of an
     # iteration) carry events, and only every 64th of their launches (one launch of each per sample; round 4: every 16th,
-    # two per sample and 1.5 % of the sample's time) -- an event pair costs ~6 us of stream time on either side of the kernel. The K-step sample is a few milliseconds long, so it is
-    # repeated and the MEDIAN sample is the one reported (box-to-box and run-to-run spread is several per cent).
-    # By default the samples add up to >= 8 s of contiguous GPU work (9 s are aimed at: the first, estimating sample runs slower) (a 20-iteration sample is ~3 ms: the driver's 5-second utilisation
-    # sampler would otherwise never see the device busy); --repeats N fixes the count.
+    # two per sample and 1.5 % of the sample's time) -- an event pair costs ~6 us of stream time on either side of the kernel.
+    # By default the timed region is ONE sample of exactly --steps iterations: --steps sets the work timed, so a caller sizes
+    # the region (a 20-iteration sample is ~3 ms: long samples are the caller's to ask for). --repeats N runs N samples and
+    # reports the MEDIAN one (box-to-box and run-to-run spread is several per cent); --repeats 0 runs as many as add up to
+    # >= 8 s of contiguous GPU work (9 s are aimed at: the first, estimating sample runs slower; the driver's 5-second
+    # utilisation sampler would otherwise never see the device busy).
     if args.repeats > 0:
         repeats = args.repeats
     else:
@@ -583,6 +624,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         samples.append((elapsed / rec[0], elapsed, rec))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, built, scene, rec[4])       # (rec: the last sample; its last solve's summary)
     samples.sort(key=lambda z: z[0])
     _, elapsed, (done, jac, cost, solves, last, phase_ms, phase_n) = samples[len(samples) // 2]
 
@@ -627,6 +670,7 @@ def main():
             "dtype": "f64",
             "data": "synthetic",
             "repeats": repeats,
+            "timed_steps_total": sum(z[2][0] for z in samples),
             "timed_seconds_total": sum(z[1] for z in samples),
             # (sorted samples; the median is the one reported) quantiles of all of them + the 25 around the median
             "ms_per_step_quantiles": {q: round(1e3 * samples[min(len(samples) - 1, int(q * len(samples) / 100))][0], 5) for q in (0, 10, 25, 50, 75, 90, 99)},
