@@ -70,6 +70,11 @@ class Summary(C.Structure):
         return d
 
 
+class CovarianceOptions(C.Structure):
+    """calico_covariance_options."""
+    _fields_ = [("min_relative_pivot", C.c_double), ("reserved", C.c_int32 * 6)]
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -122,6 +127,7 @@ ABI_SYMBOLS = [
     "problem_set_stream", "get_phase_time", "set_phase_timing", "project",
     "problem_set_outlier_mask", "mark_outliers", "fit_spline", "residual_heatmap",
     "comm_get_unique_id", "comm_init_rccl", "comm_info", "problem_finalize", "plan_cache_stats", "plan_cache_clear",
+    "default_covariance_options", "covariance_compute", "covariance_info", "covariance_get_dense", "covariance_get_block",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table"]
@@ -180,6 +186,11 @@ class CApi:
             g("comm_info", C.c_int32, [P, I, I, C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
             g("plan_cache_stats", C.c_int32, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)])
             g("plan_cache_clear", C.c_int32, [])
+            g("default_covariance_options", None, [C.POINTER(CovarianceOptions)])
+            g("covariance_compute", C.c_int32, [P, C.POINTER(CovarianceOptions)])
+            g("covariance_info", C.c_int32, [P, I, I, D])
+            g("covariance_get_dense", C.c_int32, [P, D])
+            g("covariance_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
             g("debug_plan_info", C.c_int32, [P, I, C.c_int32])
@@ -228,6 +239,7 @@ class Problem:
             raise CalicoError(st, "calico_problem_create failed (no usable HIP device?)")
         self._keep = []
         self._sizes = {}      # block id -> ambient size, of the blocks added through this object
+        self._manifolds = {}  # block id -> manifold, of the same blocks
 
     def close(self):
         if self.h:
@@ -250,6 +262,7 @@ class Problem:
         self._check(self.api.problem_add_param_block(self.h, _dp(v), v.size, manifold, int(bool(constant)),
                                                      C.byref(out)))
         self._sizes[out.value] = v.size
+        self._manifolds[out.value] = manifold
         return out.value
 
     def add_param_blocks(self, values, manifold=MANIFOLD_EUCLIDEAN, constant=False):
@@ -266,6 +279,7 @@ class Problem:
         self._check(self.api.problem_add_param_blocks(self.h, n, size, manifold, const.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(v), _ip(ids)))
         for i in ids:
             self._sizes[int(i)] = size
+            self._manifolds[int(i)] = manifold
         return ids
 
     def get_param_block(self, block_id, size):
@@ -386,6 +400,49 @@ class Problem:
         H = np.zeros((n, n)) if want_jtj else None
         self._check(self.api.evaluate(self.h, C.byref(cost), _dp(g), _dp(H) if want_jtj else None))
         return cost.value, g, H
+
+    def covariance_compute(self, min_relative_pivot=None):
+        """calico_covariance_compute; returns (dim, n_unobserved, min_relative_pivot). Raises CalicoError on failure."""
+        o = CovarianceOptions()
+        self.api.default_covariance_options(C.byref(o))
+        if min_relative_pivot is not None:
+            o.min_relative_pivot = float(min_relative_pivot)
+        self._check(self.api.covariance_compute(self.h, C.byref(o)))
+        return self.covariance_info()
+
+    def covariance_info(self):
+        dim, nu, piv = C.c_int32(0), C.c_int32(0), C.c_double(0)
+        self._check(self.api.covariance_info(self.h, C.byref(dim), C.byref(nu), C.byref(piv)))
+        return dim.value, nu.value, piv.value
+
+    def covariance_dense(self):
+        """Σ of the dense border (dim x dim, border tangent order) of the last successful compute."""
+        dim = self.covariance_info()[0]
+        out = np.zeros((dim, dim))
+        self._check(self.api.covariance_get_dense(self.h, _dp(out)))
+        return out
+
+    def covariance(self, blocks, tangent=False, min_relative_pivot=None):
+        """Compute Σ and return {(a, b): block} for every pair of the given block ids (a <= b in the list's order), as
+        numpy arrays: ambient form (GetCovarianceBlock) or, with tangent=True, tangent form (3 rows per quaternion)."""
+        self.covariance_compute(min_relative_pivot)
+        res = {}
+        for i, a in enumerate(blocks):
+            for b in blocks[i:]:
+                res[(a, b)] = self.covariance_block(a, b, tangent)
+        return res
+
+    def covariance_block(self, block_a, block_b, tangent=False, sizes=None):
+        """Block (block_a, block_b) of the last computed Σ. `sizes`: (rows, cols) of the requested form; by default taken
+        from the blocks added through this object (ambient size, or 3 for a 4-vector in tangent form)."""
+        if sizes is None:
+            def sz(b):
+                n = self._sizes[b]
+                return 3 if (tangent and n == 4 and self._manifolds.get(b) == MANIFOLD_EIGEN_QUATERNION) else n
+            sizes = (sz(block_a), sz(block_b))
+        out = np.zeros(sizes)
+        self._check(self.api.covariance_get_block(self.h, int(block_a), int(block_b), int(bool(tangent)), _dp(out)))
+        return out
 
     def set_allreduce(self, pyfunc):
         cb = ALLREDUCE_FN(pyfunc)

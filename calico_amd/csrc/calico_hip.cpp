@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <array>
 #include <atomic>
 #include <map>
@@ -104,6 +105,14 @@ hipError_t configure_dense_back_bytes(size_t lds);
 void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
                        const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s);
 int reduced_schur_slices(const SolveArgs& a);
+void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const double* x, const BlockDev* blocks, int n_blocks, hipStream_t s,
+                           bool with_post_eval, IterLog* log, int log_cap, int jacobi);
+int covariance_max_dim();
+int covariance_ld(int n);
+bool covariance_in_lds(int n);
+void launch_covariance(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* out,
+                       double* info, hipStream_t s);
+hipError_t configure_covariance_kernel();
 
 }  // namespace cal
 
@@ -524,6 +533,20 @@ struct calico_problem : PlanHost, PlanDev, Workspace {
   struct ResCache { bool valid = false, predict = false; std::vector<double> x, r; std::vector<uint8_t> v; } res_cache;
   std::vector<calico_iteration> iterations;
   PhaseTimer timer;
+  // calico_covariance_compute: its own LM state, scale, damping and solution buffers (the pass never touches the LM's),
+  // the factorisation's workspace and the result -- owned by the handle, not by the workspace the plan cache recycles
+  struct Covariance {
+    DevBuf<LmState> st;
+    DevBuf<double> scale, dadd, y, zbuf, work, out, info;
+    bool valid = false;
+    int dim = 0, n_unobserved = 0;
+    double min_relative_pivot = 0.0;
+    std::vector<double> sigma;       // dim x dim, border tangent order
+    // per block id at the time of the compute: offset of its tangent rows in sigma (-1: not in Σ -- constant or unused --,
+    // -2: control point), ambient size, manifold, value (the quaternion lift is taken at the values Σ was computed at)
+    struct Blk { int off, size, manifold; std::vector<double> v; };
+    std::vector<Blk> blocks;
+  } cov;
 
   int set_error(int code, const std::string& msg) { error = msg; return code; }
   int hip_error(hipError_t e, const char* what) {
@@ -1655,6 +1678,7 @@ int configure_kernels(calico_problem* p) {
 int finalize(calico_problem* p) {
   if (!p->dirty) return CALICO_OK;
   p->res_cache.valid = false;
+  p->cov.valid = false;      // (a covariance of the structure before is gone: its layout is not this plan's)
   if (p->order <= 0) return p->set_error(CALICO_FAILED_PRECONDITION, "spline not set");
   if (p->order > 8) return p->set_error(CALICO_UNIMPLEMENTED, "spline order > 8 is not supported by the HIP kernels");
   HIP_TRY(p, hipSetDevice(p->device));
@@ -1839,9 +1863,14 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
 // One linear solve + update of the candidate point: tree solver or sequential banded factorisation.
 // with_post_eval: 0 none, 1 the bookkeeping of the step just accepted rides in the first launch, 2 the bookkeeping of the
 // solve's FIRST evaluation does (tree solver only: level 0 then forms the Jacobi scale of its diagonal entries itself)
-void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi) {
+// reduce_only (the covariance pass): stop once the reduced system is in sa.Spart -- no reduced solve, no back-substitution.
+void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only = false) {
   hipStream_t s = p->stream;
   const int n_blocks = int(p->h_blocks.size());
+  if (reduce_only && !p->use_bcr) {
+    launch_band_reduction(sa, o, p->d_x.p, p->d_blocks.p, n_blocks, s, with_post_eval == 1, p->d_log.p, kLogCap, jacobi);
+    return;
+  }
   if (!p->use_bcr) {
     launch_solve(sa, o, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, p->dense_in_lds, s, with_post_eval == 1, p->d_log.p, kLogCap, jacobi);
     return;
@@ -1868,6 +1897,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
                      p->d_log.p, kLogCap, jacobi, s, schur_rides && l == L - 1 ? ks : 0, schur_rides ? fan_word : nullptr, inl, lv.q_max);
   }
   if (!schur_rides) launch_bcr_schur(sa, b, ks, o, s);
+  if (reduce_only) return;
   // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
   // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
   // the ones it waits for anyway) instead of costing a launch of its own.
@@ -2802,6 +2832,170 @@ int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient, doubl
   if (jtj)
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j) jtj[size_t(i) * n + j] = H(p->eff_to_tan[size_t(i)], p->eff_to_tan[size_t(j)]);
+  return CALICO_OK;
+}
+
+void calico_default_covariance_options(calico_covariance_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->min_relative_pivot = 1e-12;
+}
+
+// Σ = (JᵀJ)⁻¹ of the calibration blocks at the current values: one evaluation (as the LM loop's, exchange included), the
+// linear solve's reduction WITHOUT damping and Jacobi scaling -- a state of its own with an infinite radius, a scale of
+// ones --, stopped once the reduced system is formed, then covariance_kernel (cov_kernels.hip). The LM state, the
+// parameter buffers, the iteration log and the plan / workspace sizes are left alone.
+int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_options* opt) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  calico_covariance_options def;
+  calico_default_covariance_options(&def);
+  if (!opt) opt = &def;
+  if (!(opt->min_relative_pivot >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "min_relative_pivot must be >= 0");
+  if (p->world > 1 && !p->has_exchange())
+    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
+  int rc = finalize(p);
+  if (rc != CALICO_OK) return rc;
+  HIP_TRY(p, hipSetDevice(p->device));
+  calico_problem::Covariance& cv = p->cov;
+  cv.valid = false;
+  SolveArgs sa = make_solve_args(p);
+  const int mc = p->m, m = sa.m;
+  if (m > covariance_max_dim())
+    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: reduced system of " + std::to_string(m) + " rows (at most " +
+                                                  std::to_string(covariance_max_dim()) + ")");
+  const int NT = sa.NT(), ny = NT + p->border_extra();
+  // (the same sizes as the workspace's buffers they stand in for: prepare_workspace)
+  HIP_TRY(p, cv.st.alloc(1)); HIP_TRY(p, cv.scale.alloc(2 * size_t(NT))); HIP_TRY(p, cv.dadd.alloc(size_t(NT)));
+  HIP_TRY(p, cv.y.alloc(size_t(ny) + 64)); HIP_TRY(p, cv.zbuf.alloc(size_t(sa.n_s()) + 64));
+  HIP_TRY(p, cv.out.alloc(size_t(mc) * mc)); HIP_TRY(p, cv.info.alloc(4));
+  if (!covariance_in_lds(m)) HIP_TRY(p, cv.work.alloc(size_t(m) * covariance_ld(m)));
+  HIP_TRY(p, configure_covariance_kernel());
+  hipStream_t s = p->stream;
+  {
+    const std::vector<double> ones(2 * size_t(NT), 1.0);      // [Jacobi scale s | 1 / s^2]: no scaling
+    HIP_TRY(p, hipMemcpyAsync(cv.scale.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(p, hipStreamSynchronize(s));      // (`ones` is a local)
+  }
+  rc = upload_x(p);
+  if (rc != CALICO_OK) return rc;
+  {
+    // (the phase timer measures the LM loop: the pass records nothing into it)
+    const int mask = p->timer.mask;
+    p->timer.mask = 0;
+    rc = enqueue_jacobian_eval(p, nullptr, 0);      // R(x) into reduce buffer 0, all ranks' sum
+    p->timer.mask = mask;
+  }
+  if (rc != CALICO_OK) return rc;
+  // damping = clamp(v s², min, max) / (radius s²) = 0 with s = 1 and an infinite radius (FromR::damping, prepare_kernel)
+  launch_init_state(cv.st.p, std::numeric_limits<double>::infinity(), 0.0, s);
+  sa.st = cv.st.p; sa.scale = cv.scale.p; sa.dadd = cv.dadd.p; sa.y = cv.y.p; sa.zbuf = cv.zbuf.p; sa.progress = nullptr;
+  LmOptionsDev o = {};
+  o.min_lm_diagonal = 1e-6; o.max_lm_diagonal = 1e32;
+  (void)hipGetLastError();
+  if (mc > 0) {
+    enqueue_linear_solve(p, sa, o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
+    HIP_TRY(p, hipGetLastError());
+    launch_covariance(sa.Spart, reduced_schur_slices(sa), m, mc, sa.R + sa.off_C(), cv.st.p, cv.work.p, cv.out.p, cv.info.p, s);
+    HIP_TRY(p, hipGetLastError());
+  }
+  double info[4] = {1.0, 0.0, 0.0, 0.0};
+  std::vector<double> R01(2);
+  HIP_TRY(p, hipMemcpyAsync(R01.data(), p->d_R.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  cv.sigma.assign(size_t(mc) * mc, 0.0);
+  if (mc > 0) {
+    HIP_TRY(p, hipMemcpyAsync(info, cv.info.p, sizeof(info), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(cv.sigma.data(), cv.out.p, cv.sigma.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(p, hipStreamSynchronize(s));
+  if (R01[1] > 0.0) return p->set_error(CALICO_FAILED_PRECONDITION, "covariance: the residual evaluation failed at the current parameter values");
+  cv.dim = mc; cv.min_relative_pivot = info[0]; cv.n_unobserved = int(info[2]);
+  const int flags = int(info[1]);
+  if (flags & (1 | 4 | 8))
+    return p->set_error(CALICO_FAILED_PRECONDITION, std::string("covariance: JᵀJ is rank deficient or not finite (") +
+                                                        ((flags & 4) ? "a block of the control points' elimination is not positive definite"
+                                                         : (flags & 1) ? "non-finite value in the reduced system" : "non-finite value in the result") + ")");
+  if ((flags & 2) || info[0] < opt->min_relative_pivot) {
+    char msg[256];
+    std::snprintf(msg, sizeof(msg), "covariance: JᵀJ is rank deficient (minimum relative pivot %.3e, threshold %.3e): a gauge freedom "
+                  "or a parameter the data do not determine", info[0], opt->min_relative_pivot);
+    return p->set_error(CALICO_FAILED_PRECONDITION, msg);
+  }
+  cv.blocks.resize(p->blocks.size());
+  for (size_t i = 0; i < p->blocks.size(); ++i) {
+    const HBlock& h = p->blocks[i];
+    const bool in = !h.constant && h.used;
+    cv.blocks[i] = {in ? (h.tan < 6 * p->n_cp ? -2 : h.tan - 6 * p->n_cp) : -1, h.size, h.manifold, h.v};
+  }
+  cv.valid = true;
+  return CALICO_OK;
+}
+
+int32_t calico_covariance_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, double* min_relative_pivot) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  if (!p->cov.valid || p->dirty) return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
+  if (dim) *dim = p->cov.dim;
+  if (n_unobserved) *n_unobserved = p->cov.n_unobserved;
+  if (min_relative_pivot) *min_relative_pivot = p->cov.min_relative_pivot;
+  return CALICO_OK;
+}
+
+int32_t calico_covariance_get_dense(calico_problem* p, double* out) {
+  if (!p || !out) return CALICO_INVALID_ARGUMENT;
+  if (!p->cov.valid || p->dirty) return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
+  std::copy(p->cov.sigma.begin(), p->cov.sigma.end(), out);
+  return CALICO_OK;
+}
+
+namespace {
+// EigenQuaternionManifold::PlusJacobian at x (storage x, y, z, w): 4x3 row-major
+void quat_plus_jacobian(const double* x, double J[12]) {
+  const double X = x[0], Y = x[1], Z = x[2], W = x[3];
+  const double j[12] = {W, Z, -Y, -Z, W, X, Y, -X, W, -X, -Y, -Z};
+  std::copy(j, j + 12, J);
+}
+}  // namespace
+
+int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t block_b, int32_t tangent, double* out) {
+  if (!p || !out) return CALICO_INVALID_ARGUMENT;
+  const int nb = int(p->blocks.size());
+  if (block_a < 0 || block_a >= nb || block_b < 0 || block_b >= nb) return p->set_error(CALICO_INVALID_ARGUMENT, "covariance: unknown parameter block id");
+  // (p->dirty: the structure changed since the compute -- blocks, sensors, observations --; the next finalisation drops Σ)
+  if (!p->cov.valid || p->dirty || size_t(nb) != p->cov.blocks.size())
+    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
+  const calico_problem::Covariance::Blk& A = p->cov.blocks[size_t(block_a)];
+  const calico_problem::Covariance::Blk& B = p->cov.blocks[size_t(block_b)];
+  if (A.off == -2 || B.off == -2)
+    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point blocks are not supported (their blocks need a selected inversion of the band)");
+  const bool qa = A.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION, qb = B.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION;
+  const int ta = qa ? 3 : A.size, tb = qb ? 3 : B.size;
+  const int ra = tangent ? ta : A.size, rb = tangent ? tb : B.size;
+  std::fill(out, out + size_t(ra) * rb, 0.0);
+  if (A.off < 0 || B.off < 0) return CALICO_OK;      // constant / unused blocks: zeros (Ceres: constant)
+  const int oa = A.off, ob = B.off, dim = p->cov.dim;
+  if (oa + ta > dim || ob + tb > dim) return p->set_error(CALICO_INTERNAL, "covariance: block layout out of range");
+  std::vector<double> t(size_t(ta) * tb);
+  for (int i = 0; i < ta; ++i)
+    for (int j = 0; j < tb; ++j) t[size_t(i) * tb + j] = p->cov.sigma[size_t(oa + i) * dim + (ob + j)];
+  if (tangent) { std::copy(t.begin(), t.end(), out); return CALICO_OK; }
+  // ambient: P_a Σ P_bᵀ, P the manifold's PlusJacobian at the value Σ was computed at (identity for Euclidean blocks)
+  double Pa[12], Pb[12];
+  if (qa) quat_plus_jacobian(A.v.data(), Pa);
+  if (qb) quat_plus_jacobian(B.v.data(), Pb);
+  std::vector<double> u(size_t(ra) * tb);       // P_a t
+  for (int i = 0; i < ra; ++i)
+    for (int j = 0; j < tb; ++j) {
+      double v = 0.0;
+      if (qa) { for (int k = 0; k < 3; ++k) v += Pa[i * 3 + k] * t[size_t(k) * tb + j]; }
+      else v = t[size_t(i) * tb + j];
+      u[size_t(i) * tb + j] = v;
+    }
+  for (int i = 0; i < ra; ++i)
+    for (int j = 0; j < rb; ++j) {
+      double v = 0.0;
+      if (qb) { for (int k = 0; k < 3; ++k) v += u[size_t(i) * tb + k] * Pb[j * 3 + k]; }
+      else v = u[size_t(i) * tb + j];
+      out[size_t(i) * rb + j] = v;
+    }
   return CALICO_OK;
 }
 

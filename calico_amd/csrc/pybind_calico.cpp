@@ -312,6 +312,30 @@ PYBIND11_MODULE(_calico, m) {
       .def_readwrite("max_trust_region_radius", &SolverOptions::max_trust_region_radius);
   m.def("DefaultSolverOptions", &DefaultSolverOptions);
 
+  // ceres::Covariance's result: per-sensor blocks as numpy arrays (tangent space: 6 x 6 extrinsics [rotation | translation])
+  py::class_<Covariance>(m, "Covariance")
+      .def("Dimension", &Covariance::Dimension)
+      .def("NumUnobserved", &Covariance::NumUnobserved)
+      .def("MinRelativePivot", &Covariance::MinRelativePivot)
+      .def("Intrinsics",
+           [](const Covariance& c, std::shared_ptr<Sensor> s) {
+             std::vector<double> v;
+             raise_if_error(SensorIntrinsicsCovariance(c, *s, &v));
+             const py::ssize_t n = py::ssize_t(s->GetIntrinsics().size());
+             return py::array_t<double>({n, n}, v.data());
+           })
+      .def("Extrinsics",
+           [](const Covariance& c, std::shared_ptr<Sensor> s) {
+             std::vector<double> v;
+             raise_if_error(SensorExtrinsicsCovariance(c, *s, &v));
+             return py::array_t<double>({py::ssize_t(6), py::ssize_t(6)}, v.data());
+           })
+      .def("Latency", [](const Covariance& c, std::shared_ptr<Sensor> s) {
+        double v = 0.0;
+        raise_if_error(SensorLatencyVariance(c, *s, &v));
+        return v;
+      });
+
   py::class_<BatchOptimizer>(m, "BatchOptimizer")
       .def(py::init<>())
       .def("AddSensor", [](BatchOptimizer& self, std::shared_ptr<Sensor> sensor) { self.AddSensor(sensor.get(), /*take_ownership=*/false); },
@@ -329,5 +353,15 @@ PYBIND11_MODULE(_calico, m) {
             raise_if_error(summary.status());
             return summary.value();
           },
-          py::arg("options") = DefaultSolverOptions(), py::arg("device") = 0);
+          py::arg("options") = DefaultSolverOptions(), py::arg("device") = 0)
+      .def(
+          "ComputeCovariance",
+          [](BatchOptimizer& self, double min_relative_pivot, int device) {
+            calico_covariance_options o = DefaultCovarianceOptions();
+            if (min_relative_pivot >= 0.0) o.min_relative_pivot = min_relative_pivot;
+            auto cov = self.ComputeCovariance(o, device);
+            raise_if_error(cov.status());
+            return cov.value();
+          },
+          py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0);
 }

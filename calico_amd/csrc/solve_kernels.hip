@@ -2087,8 +2087,10 @@ void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipSt
                        reduced_in_lds ? 1 : 0);
   }
 }
-void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
-                  int n_blocks, bool reduced_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi) {
+// The banded solver up to the reduced system: staging (+ damping), band factorisation with the border, Schur complement
+// into a.Spart in reduced_schur_slices(a) K-slices. Also the covariance pass's reduction (undamped: calico_hip.cpp).
+void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const double* x, const BlockDev* blocks, int n_blocks, hipStream_t s,
+                           bool with_post_eval, IterLog* log, int log_cap, int jacobi) {
   const int m1 = a.m + 1;
   const size_t total = size_t(a.n_cp) * a.W() * 6 + size_t(a.n_s()) * m1 + size_t(m1) * m1;
   const int pb = int((total + 255) / 256);
@@ -2099,6 +2101,11 @@ void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, do
   const int nt = (m1 + 15) / 16;
   const int ks = reduced_schur_slices(a);
   hipLaunchKernelGGL(schur_kernel, dim3(nt * (nt + 1) / 2 * ks), dim3(256), 0, s, a, ks);
+}
+void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
+                  int n_blocks, bool reduced_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi) {
+  launch_band_reduction(a, o, x, blocks, n_blocks, s, with_post_eval, log, log_cap, jacobi);
+  const int ks = reduced_schur_slices(a);
   launch_reduced_solve(a, reduced_in_lds, ks, s, nullptr);
   hipLaunchKernelGGL(border_matvec_kernel, dim3((a.n_s() + 3) / 4), dim3(256), 0, s, a);
   {

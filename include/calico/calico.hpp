@@ -182,6 +182,7 @@ inline SolverOptions DefaultSolverOptions() { SolverOptions o; calico_default_so
 // their address (Ceres semantics); Solve() flattens everything through the C
 // ABI, runs the device LM and writes the estimates back IN PLACE.
 // ---------------------------------------------------------------------------
+class Covariance;
 class Problem {
  public:
   Problem() = default;
@@ -219,6 +220,28 @@ class Problem {
 
   /// ceres::Solve(options, &problem, &summary)
   Status Solve(const SolverOptions& options, Summary* summary, int device = 0) {
+    if (Status b = Build(device); !b.ok()) return b;
+    if (int st = calico_solve(h_, &options, summary)) return Err(st);
+    for (size_t i = 0; i < blocks_.size(); ++i)  // in-place update, as Ceres does
+      if (int st = calico_get_param_block(h_, ids_[i], blocks_[i].ptr)) return Err(st);
+    return OkStatus();
+  }
+  /// ceres::Covariance::Compute over the problem as it stands (a fresh handle; the values are not changed): see Covariance
+  Status ComputeCovariance(const calico_covariance_options& options, Covariance* out, int device = 0);
+  /// problem.EvaluateResidualBlock(id, /*apply_loss_function=*/false, ...) for every block of a sensor.
+  Status EvaluateResiduals(int sensor, std::vector<double>* out, std::vector<uint8_t>* valid) {
+    if (!h_) return FailedPreconditionError("problem has not been solved");
+    const SensorRec& s = sensors_[size_t(sensor)];
+    const size_t n = s.stamps.size();
+    out->assign(n * (s.kind == CALICO_SENSOR_CAMERA ? 2 : 3), 0.0); valid->assign(n, 0);
+    const int st = calico_get_residuals(h_, sensor_ids_[size_t(sensor)], out->data(), valid->data());
+    return st == CALICO_OK ? OkStatus() : Err(st);
+  }
+  calico_problem* handle() { return h_; }
+
+ private:
+  // a new handle with every block, the spline, the sensors and their residuals
+  Status Build(int device) {
     if (h_) { calico_problem_destroy(h_); h_ = nullptr; }
     if (calico_problem_create(&h_, device) != CALICO_OK) return InternalError("calico_problem_create failed: no usable HIP device");
     ids_.assign(blocks_.size(), -1);
@@ -254,23 +277,8 @@ class Problem {
         if (int st = calico_problem_add_imu_residuals(h_, sid, n, s.meas.data(), s.stamps.data())) return Err(st);
       }
     }
-    if (int st = calico_solve(h_, &options, summary)) return Err(st);
-    for (size_t i = 0; i < blocks_.size(); ++i)  // in-place update, as Ceres does
-      if (int st = calico_get_param_block(h_, ids_[i], blocks_[i].ptr)) return Err(st);
     return OkStatus();
   }
-  /// problem.EvaluateResidualBlock(id, /*apply_loss_function=*/false, ...) for every block of a sensor.
-  Status EvaluateResiduals(int sensor, std::vector<double>* out, std::vector<uint8_t>* valid) {
-    if (!h_) return FailedPreconditionError("problem has not been solved");
-    const SensorRec& s = sensors_[size_t(sensor)];
-    const size_t n = s.stamps.size();
-    out->assign(n * (s.kind == CALICO_SENSOR_CAMERA ? 2 : 3), 0.0); valid->assign(n, 0);
-    const int st = calico_get_residuals(h_, sensor_ids_[size_t(sensor)], out->data(), valid->data());
-    return st == CALICO_OK ? OkStatus() : Err(st);
-  }
-  calico_problem* handle() { return h_; }
-
- private:
   struct BlockRec { double* ptr; int size; int manifold; bool constant; };
   struct SensorRec {
     int kind, model; double *intr, *q, *t, *latency, *gravity; double sigma; int loss; double loss_scale;
@@ -288,6 +296,43 @@ class Problem {
   std::vector<double*> ctrl_;
   calico_problem* h_ = nullptr;
 };
+
+/// ceres::Covariance's result (calico_covariance_* in include/calico_hip.h for the semantics): blocks keyed by the parameter
+/// pointers the Problem was given. It keeps the library handle it was computed on (and its device buffers) until destroyed.
+class Covariance {
+ public:
+  /// GetCovarianceBlock: ambient form (a quaternion block lifted as P Σ Pᵀ), row-major size_a x size_b
+  bool GetCovarianceBlock(const double* a, const double* b, double* out) const { return Get(a, b, 0, out).ok(); }
+  /// GetCovarianceBlockInTangentSpace: 3 rows / columns per quaternion block
+  bool GetCovarianceBlockInTangentSpace(const double* a, const double* b, double* out) const { return Get(a, b, 1, out).ok(); }
+  /// the same, with the library's status (UNIMPLEMENTED for control points, INVALID_ARGUMENT for an unknown pointer)
+  Status Get(const double* a, const double* b, int tangent, double* out) const {
+    if (!h_) return FailedPreconditionError("covariance has not been computed");
+    const auto ia = ids_.find(a), ib = ids_.find(b);
+    if (ia == ids_.end() || ib == ids_.end()) return InvalidArgumentError("covariance: parameter block not in the problem");
+    const int st = calico_covariance_get_block(h_.get(), ia->second, ib->second, tangent, out);
+    return st == CALICO_OK ? OkStatus() : Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+  }
+  int Dimension() const { int32_t d = 0; if (h_) calico_covariance_info(h_.get(), &d, nullptr, nullptr); return d; }
+  int NumUnobserved() const { int32_t n = 0; if (h_) calico_covariance_info(h_.get(), nullptr, &n, nullptr); return n; }
+  double MinRelativePivot() const { double v = 0.0; if (h_) calico_covariance_info(h_.get(), nullptr, nullptr, &v); return v; }
+
+ private:
+  friend class Problem;
+  std::shared_ptr<calico_problem> h_;
+  std::map<const double*, int32_t> ids_;
+};
+
+inline Status Problem::ComputeCovariance(const calico_covariance_options& options, Covariance* out, int device) {
+  if (Status b = Build(device); !b.ok()) return b;
+  if (int st = calico_covariance_compute(h_, &options)) return Err(st);
+  out->ids_.clear();
+  for (size_t i = 0; i < blocks_.size(); ++i) out->ids_[blocks_[i].ptr] = ids_[i];
+  out->h_ = std::shared_ptr<calico_problem>(h_, calico_problem_destroy);      // the result stays with its handle
+  h_ = nullptr;
+  return OkStatus();
+}
+inline calico_covariance_options DefaultCovarianceOptions() { calico_covariance_options o; calico_default_covariance_options(&o); return o; }
 
 namespace utils {
 /// optimization_utils.h:51-68
@@ -587,6 +632,7 @@ class SensorCommon : public Sensor {
   const VectorXd& GetIntrinsics() const final { return intrinsics_; }
   Status SetLatency(double latency) final { latency_ = latency; return OkStatus(); }
   double GetLatency() const final { return latency_; }
+  const double* LatencyData() const { return &latency_; }      // (the parameter block's address: Covariance's key)
   void EnableExtrinsicsEstimation(bool e) final { extrinsics_enabled_ = e; }
   void EnableIntrinsicsEstimation(bool e) final { intrinsics_enabled_ = e; }
   void EnableLatencyEstimation(bool e) final { latency_enabled_ = e; }
@@ -881,6 +927,32 @@ class Accelerometer : public ImuSensor<CALICO_SENSOR_ACCELEROMETER> {
 // ---------------------------------------------------------------------------
 // BatchOptimizer (batch_optimizer.{h,cpp})
 // ---------------------------------------------------------------------------
+/// Per-sensor blocks of a Covariance: intrinsics (n x n), extrinsics as 6 x 6 [rotation tangent | translation], latency.
+inline Status SensorIntrinsicsCovariance(const Covariance& c, const sensors::Sensor& s, std::vector<double>* out) {
+  const size_t n = size_t(s.GetIntrinsics().size());
+  out->assign(n * n, 0.0);
+  return c.Get(s.GetIntrinsics().data(), s.GetIntrinsics().data(), 1, out->data());
+}
+inline Status SensorExtrinsicsCovariance(const Covariance& c, const sensors::Sensor& s, std::vector<double>* out) {
+  const double* q = s.GetExtrinsics().rotation().data();
+  const double* t = s.GetExtrinsics().translation().data();
+  const double* blk[2] = {q, t};
+  out->assign(36, 0.0);
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) {
+      double tmp[9];
+      if (Status st = c.Get(blk[a], blk[b], 1, tmp); !st.ok()) return st;
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) (*out)[size_t(3 * a + i) * 6 + size_t(3 * b + j)] = tmp[3 * i + j];
+    }
+  return OkStatus();
+}
+inline Status SensorLatencyVariance(const Covariance& c, const sensors::Sensor& s, double* out) {
+  const auto* sc = dynamic_cast<const sensors::SensorCommon*>(&s);
+  if (!sc) return InvalidArgumentError("covariance: not a library sensor");
+  return c.Get(sc->LatencyData(), sc->LatencyData(), 1, out);
+}
+
 class BatchOptimizer {
  public:
   ~BatchOptimizer() {  // batch_optimizer.cpp:19-33: un-owned pointers are released, owned ones deleted
@@ -892,6 +964,24 @@ class BatchOptimizer {
   void AddWorldModel(WorldModel* world_model, bool take_ownership = true) { world_model_ = world_model; own_world_model_ = take_ownership; }
   void AddTrajectory(Trajectory* trajectory_world_sensorrig, bool take_ownership = true) { trajectory_ = trajectory_world_sensorrig; own_trajectory_ = take_ownership; }
   /// batch_optimizer.cpp:53-81
+  /// Covariance of the estimates at the current values (the problem is rebuilt, as Optimize does; the plan cache makes that
+  /// cheap). The sensors' residual information is left as it is.
+  StatusOr<Covariance> ComputeCovariance(const calico_covariance_options& options = DefaultCovarianceOptions(), int device = 0) {
+    if (!world_model_ || !trajectory_) return FailedPreconditionError("world model and trajectory must be added before ComputeCovariance()");
+    Problem problem;
+    world_model_->AddParametersToProblem(problem);
+    trajectory_->AddParametersToProblem(problem);
+    for (sensors::Sensor* sensor : sensors_) {
+      const auto np = sensor->AddParametersToProblem(problem);
+      if (!np.ok()) return np.status();
+      const auto nr = sensor->AddResidualsToProblem(problem, *trajectory_, *world_model_);
+      if (!nr.ok()) return nr.status();
+    }
+    Covariance cov;
+    const Status st = problem.ComputeCovariance(options, &cov, device);
+    if (!st.ok()) return st;
+    return cov;
+  }
   StatusOr<Summary> Optimize(const SolverOptions& options = DefaultSolverOptions(), int device = 0) {
     if (!world_model_ || !trajectory_) return FailedPreconditionError("world model and trajectory must be added before Optimize()");
     Problem problem;

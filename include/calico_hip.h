@@ -306,6 +306,58 @@ int32_t calico_num_effective_parameters(calico_problem* p, int32_t* n_out);
 int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient,
                         double* jtj_dense);
 
+/* ---- covariance of the estimates (ceres::Covariance) ------------------ */
+/* Σ = (JᵀJ)⁻¹ of the dense border -- every free, used block that is not a spline control point: intrinsics,
+ * extrinsics q / t, latencies, gravity, a free chart pose, free model points, rigid bodies -- with all cross-covariances,
+ * at the current parameter values. JᵀJ is the Gauss-Newton matrix exactly as the LM loop evaluates it: sigma-weighted
+ * residuals, the robust loss applied through the same corrector (Ceres' apply_loss_function = true), quaternion blocks
+ * in the EigenQuaternion tangent. No LM damping and no Jacobi scaling enter the result (an internal symmetric
+ * equilibration is undone).
+ *  - No a-posteriori variance factor is applied. To scale by the estimated residual variance, multiply Σ by
+ *    2·cost / (num_residuals - num_effective_parameters) (calico_summary) yourself.
+ *  - The control points are eliminated (Schur complement, as in the solver): Σ is their marginal over them. Their own
+ *    blocks are not available (calico_covariance_get_block returns CALICO_UNIMPLEMENTED).
+ *  - Constant (and unused) blocks read back as zeros, as in Ceres.
+ *  - Deviation from Ceres: a tangent column whose JᵀJ diagonal is exactly 0.0 -- no residual depends on it, e.g. the
+ *    gyroscope's translation block -- is left out of the inversion and its rows and columns of Σ are 0 (the
+ *    Moore-Penrose result for a zero column). Ceres' default would reject every IMU problem because of it.
+ *  - Any other rank deficiency (a gauge freedom, a non-finite value) makes calico_covariance_compute return
+ *    CALICO_FAILED_PRECONDITION with a message in calico_last_error. The test is a RELATIVE PIVOT threshold on the
+ *    equilibrated reduced system (unit diagonal: a pivot is the fraction of a column's JᵀJ diagonal the other columns do
+ *    not explain), not Ceres' min_reciprocal_condition_number on J -- formed from JᵀJ in double precision, a
+ *    reciprocal condition number of J below ~1e-8 is out of reach.
+ *    Default: see calico_default_covariance_options.
+ * The result lives in a buffer of the handle from the first compute to the next compute or calico_problem_destroy; a
+ * structural change of the problem (blocks, sensors, observations, shard) makes the readers return
+ * CALICO_FAILED_PRECONDITION until the next compute. Ambient blocks are lifted at the values Σ was computed at.
+ * calico_covariance_compute leaves the parameters, the LM state, the iteration log and the last summary alone (a solve
+ * after it is bit-identical to one without it). On a sharded handle it takes the same exchange as an evaluation (every
+ * rank calls it): every rank then holds the same Σ. */
+typedef struct calico_covariance_options {
+  double min_relative_pivot;   /* smallest relative pivot accepted (>= 0) */
+  int32_t reserved[6];
+} calico_covariance_options;
+/* Defaults. min_relative_pivot = 1e-12, in the gap measured on the test scenes (tests/test_gpu_covariance.py prints
+ * them): the well-posed scenes' minimum relative pivots lie between 3.7e-5 and 8.7e-3 (six camera models, the scale-only
+ * and scale-and-bias IMU models robust and not, free model points, spline orders 7 and 8, the banded solver, the configs[3]
+ * and configs[4] shapes), the gauge-deficient scene's
+ * (camera-only, free chart pose) is 6.4e-16 -- rounding noise of an exactly singular system; an exactly singular
+ * column gives a pivot <= 0, reported as 0. */
+void calico_default_covariance_options(calico_covariance_options* o);
+/* Compute Σ (finalises the problem if needed). o == NULL: the defaults. */
+int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_options* o);
+/* Size of Σ (the border's tangent dimension), the number of structurally unobserved columns left out, and the minimum
+ * relative pivot of the factorisation. CALICO_FAILED_PRECONDITION without a successful compute. */
+int32_t calico_covariance_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, double* min_relative_pivot);
+/* Σ as dim x dim row-major, border tangent order: the free, used non-control-point blocks in block-id order
+ * (the tail of calico_num_effective_parameters' order). */
+int32_t calico_covariance_get_dense(calico_problem* p, double* out);
+/* The (block_a, block_b) block of Σ, row-major. tangent != 0: tangent space (GetCovarianceBlockInTangentSpace, 3 rows per
+ * quaternion); tangent == 0: ambient (GetCovarianceBlock), a quaternion block lifted as P Σ Pᵀ with P the
+ * EigenQuaternionManifold PlusJacobian at the current value. CALICO_UNIMPLEMENTED for control-point blocks,
+ * CALICO_INVALID_ARGUMENT for an unknown id, CALICO_FAILED_PRECONDITION without a successful compute. */
+int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t block_b, int32_t tangent, double* out);
+
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
  * packed normal-equation buffer (and of the candidate cost).  The host owns
