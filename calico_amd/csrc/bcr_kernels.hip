@@ -9,7 +9,7 @@
 //     block TRIDIAGONAL in superblocks, bordered by the calibration columns and the right-hand side (F);
 //   * level 0 eliminates chains of q consecutive superblocks between kept separators, every further level every other
 //     surviving separator, all chains of a level side by side on different CUs (one launch per level); the last survivor
-//     (the root) joins the calibration blocks in the dense reduced system, which reduced_solve_panel_kernel factors;
+//     (the root) joins the calibration blocks in the dense reduced system, which dense_block_solve_body factors;
 //   * eliminating superblock e with neighbours a (left separator) and n (next of the chain / right separator):
 //       D_e = L Lᵀ,  [Z^A | Z^B | Z^F] = L⁻¹ [T(e,a) | T(n,e)ᵀ | F_e],
 //       D_n -= Z^BᵀZ^B, T(n,a) -= Z^BᵀZ^A, F_n -= Z^BᵀZ^F, D_a -= Z^AᵀZ^A, F_a -= Z^AᵀZ^F, C -= Z^FᵀZ^F (one SYRK at the end);
@@ -44,6 +44,9 @@ constexpr int DLD = 33;                 // row stride of the augmented diagonal 
 constexpr int XLD = 2 * BP + kBcrFS + 1;  // row stride of X = [A | B | F slice] (80 columns)
 constexpr int CA = 0, CB = BP, CF = 2 * BP;   // column offsets inside X / Z
 constexpr int kLevelThreads = 512;
+// Bytes of its own code, from s_getpc on, that the barrier form of the level kernel asks for as data (prefetch_code). They must
+// lie inside the code object's executable segment: tests/test_kernel_resources.py reads this constant and checks the placement.
+constexpr int kLevelCodePrefetchBytes = 40 * 1024;
 }  // namespace
 
 // acc (+/-)= Σ_k P[k][pc0 + i] · Q[k][qc0 + j], k in [k0, k1): one 16x16 tile of PᵀQ on the matrix cores; P, Q row-major in LDS.
@@ -326,23 +329,6 @@ struct BcrPre { double d[NU], bt[NU], at[NU], f[NF]; };
 // level 0: what a block's requests return, before selection and damping (fetch_request / fetch_finish)
 template <int NUD, int NU, int NF>
 struct BcrRaw { double vraw[NUD], svv[NUD], q2v[NUD], vraw1[NUD], graw[NU], garaw[NU], graw1[NU], garaw1[NU], fraw[NF], fraw1[NF]; unsigned flags; };
-#ifndef BCR_FIRST_BLOCK_ALL_WAVES
-#define BCR_FIRST_BLOCK_ALL_WAVES 1
-#endif
-// BCR_EARLY_REQUESTS=1 (compile time; round 5, measured and left OFF): the loaders issue the requests of block i + 2 in front of
-// step i's Schur phase and only finish (selection, damping, commit) at the top of step i + 1. Bit-identical; level 0 25.0 ->
-// 26.9 us (27.8 with the 18 registers it spills): the requests' address arithmetic (3-4k clocks on SIMDs shared with the chief
-// and the followers) then sits between the step's two barriers and holds the chief up by more than the earlier commit gains.
-#ifndef BCR_EARLY_REQUESTS
-#define BCR_EARLY_REQUESTS 0
-#endif
-
-// LA (look-ahead, round 5; ELIM only): between two blocks of a chain only what the NEXT block's chief waits for stays in
-// front of the step's second barrier -- the operands of every Schur product read into registers and the three tiles of
-// next.D -= Z^BᵀZ^B --; the chief then starts on the next block at once. The followers of the A and F tiles form the update
-// of their own input tiles (next.A -= Z^BᵀZ^A, next.F -= Z^BᵀZ^F) straight in the registers the elimination keeps them in
-// (elim_follow with use_pre: same layout), the loader waves file Z and carry the left separator's sums, and the next block's
-// requests go out right behind the barrier. Same products in the same order as without it: bit-identical.
 // Rolling chief (bcr_level_kernel<.., ROLL>): where a lane's tile entries sit in the band's storage, by spline order k = 1..6 --
 // the band is uniform in time, so the positions are those of superblock 0 (superblock I adds I·strideB) and depend on nothing
 // but k and the lane. Per lane 48 words: [0..11] byte offsets of the spine's entries (tiles (0,0), (0,1), (1,1), register 0..3 each:
@@ -415,7 +401,7 @@ static hipError_t upload_roll_table() {      // (called under configure_kernels'
 
 // ROLL (round 6; level 0 with the block elimination): the chain without a workgroup barrier between its blocks -- see the
 // "rolling chief" section in front of the step loop.
-template <bool FROM_R, bool ELIM, bool LA = false, bool ROLL = false>
+template <bool FROM_R, bool ELIM, bool ROLL = false>
 __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, BcrArgs b, int node0, int n_nodes, int nfs, int level,
                                                                    int keep0, int n_keep, LmOptionsDev o, int with_post,
                                                                    const double* __restrict__ x, const BlockDev* __restrict__ blocks,
@@ -433,7 +419,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
   // (~4k clocks behind a kernel boundary) then runs beside the state's and the set-up below instead of behind them. Every wave
   // asks for the same words, used or not: straight-line requests, nothing waits for them before they are used.
   uint4 tv[8], tva[4];
-  if constexpr (ROLL && FROM_R) {
+  if constexpr (ROLL) {
     const uint4* const tl = reinterpret_cast<const uint4*>(&g_roll_tab[min(max(a.k, 1), 6) - 1][threadIdx.x & 63][0]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) tv[i] = tl[i];
@@ -447,7 +433,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
   // misses per workgroup in front of them -- by all waves, or by waves 4..6 alone -- made level 0 1.0 / 1.35 us LONGER
   // (r06_code_prefetch_ab.txt); the barrier form waits for its first block at a barrier anyway: level 1 11.0 -> 10.5 us.
   int code_pf = 0;
-  if constexpr (!ROLL) code_pf = prefetch_code(threadIdx.x, kLevelThreads, 40 * 1024);
+  if constexpr (!ROLL) code_pf = prefetch_code(threadIdx.x, kLevelThreads, kLevelCodePrefetchBytes);
   // `pub` (the last level's launch when the Schur complement rides in it): this level's workgroups are the PRODUCERS of
   // an in-launch fan-in -- what the riders read (Y rows, the root's pending slots, separators updated in place) leaves
   // with write-through stores, and every producing workgroup arrives at `fan_word` once, terminated or not; the riders
@@ -626,12 +612,12 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
   extern __shared__ double lds[];
   double* const Daug = lds;                        // [2][64·DLD]
   double* const Xb = Daug + 2 * 64 * DLD;          // [2][32·XLD]
-  double* const Zb_base = Xb + 2 * BP * XLD;       // [32·XLD], LA: [2][32·XLD]
-  double* const dinv = Zb_base + (LA ? 2 : 1) * BP * XLD;    // [80]
+  double* const Zb = Xb + 2 * BP * XLD;            // [32·XLD]
+  double* const dinv = Zb + BP * XLD;              // [80]
   double* const bcast = dinv + 80;                 // [128]
   double* const dump = bcast + 128 + tid;          // [512]
   const ElimChannel ech = elim_channel(bcast + 128 + kLevelThreads);      // [kElimBufDoubles] (ELIM)
-  static_assert(!ROLL || (ELIM && !LA), "the rolling chief works on the block elimination");
+  static_assert(!ROLL || (FROM_R && ELIM), "the rolling chief works on level 0's chains with the block elimination");
   if (ELIM && !ROLL) elim_reset(ech, tid, kLevelThreads);   // (the barrier behind the first block's commit orders it)
   const int l16 = lane & 15, lk = lane >> 4;
   // ---- global -> registers -> LDS of one chain block. Loaders are waves 1-3 and 5-7 (384 threads: three entries each
@@ -676,11 +662,9 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
   };
   BcrLoadMap<NL, NU, NF> lmap;
   lmap.lt = lt;
-  constexpr bool kAllFetchFirst = ELIM && BCR_FIRST_BLOCK_ALL_WAVES;
-  if (!kAllFetchFirst) fill_map(lmap);       // (otherwise behind the first block's requests: the loaders' map is for the later blocks)
+  if (!ELIM) fill_map(lmap);       // (ELIM: behind the first block's requests -- the loaders' map is for the later blocks)
   // Level 0: a block's fetch in two halves -- `fetch_request` is the address arithmetic and the loads (nothing in it waits),
-  // `fetch_finish` the selection, the damping of the diagonal and what goes to `pr` -- so that the loaders can put a block's
-  // requests in FRONT of a step's Schur phase and only finish behind it (round 5; see the step loop).
+  // `fetch_finish` the selection, the damping of the diagonal and what goes to `pr`.
   auto fetch_request = [&](int i, auto& rw, auto both_tag, const auto& m) {
     typedef typename std::remove_reference<decltype(m)>::type M;
     constexpr int NL = M::NL, NU = M::NU, NF = M::NF, NUD = M::NUD;
@@ -912,9 +896,6 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
     // counter; a reader polls the counter, then reads). Z, L⁻ᵀ and the tile images are double-buffered by parity, the channel three deep.
     // Same products in the same order as the barrier form: bit-identical results (profiles/dev/bitwise.py).
     // Unobserved control points (b.all_active == 0) are padding rows / columns, by a five-bit mask per superblock asked for with its tiles.
-    // The levels above level 0 (FROM_R = false; single-block chains: the host sends longer ones to the barrier form): the same waves
-    // in the same roles, each taking its tiles straight from D / G / F and the pending slots -- no staging, no barrier but the
-    // first --, and the chain's results leave as the barrier form's do (write-through where the Schur complement's riders read them).
     // ================================================================================================================
     constexpr int kImg = 28 * 64;                         // a follower's inputs: spine (12 registers) + rows of Bᵀ (16), by lane
     double* const Zr = lds;                               // [2][32·XLD] Z = [Z^A | Z^B | Z^F] by block parity
@@ -953,9 +934,8 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
     const f64x4 zero4 = {0.0, 0.0, 0.0, 0.0};
     const bool has_left = left >= 0;
     const int n_s = a.n_s(), kk = a.k;
-    const bool tile_wave = wave < 2 || (FROM_R && wave == 7);         // the waves that load spines and rows of Bᵀ
-    const unsigned tmask = FROM_R ? tv[7].y : 0u;
-    auto leave_terminated = [&]() { if (pub) fanin_arrive(fan_word); };      // (every wave of the workgroup takes this exit or none does)
+    const bool tile_wave = wave < 2 || wave == 7;         // the waves that load spines and rows of Bᵀ
+    const unsigned tmask = tv[7].y;
     for (int e = tid; e < 3 * kElimBufDoubles; e += kLevelThreads) reinterpret_cast<unsigned long long*>(chb)[e] = kElimSentinel;
     if (tid < 16) ctr[tid] = 0;
     if (tdbg && tid < 64) tstamp[tid] = 0;
@@ -1004,60 +984,6 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
     auto act_mask = [&](int flag) { return all_act ? 31u : (unsigned(__builtin_amdgcn_ballot_w64(flag != 0 && (lane & 7) < kBcrCps)) & 31u); };
     auto act = [](unsigned am, int row) { return ((am >> (row / 6)) & 1u) != 0; };
     if (tile_wave) {
-      if constexpr (!FROM_R) {
-        // ---- an upper level's two chief-side waves: wave 0 factors the (single) block, wave 1 follows with the rows of Bᵀ and
-        //      leaves -Z^BᵀZ^B in the right separator's pending slot (elim_follow_d against a zero diagonal) ----
-        const int blk = blk0, mask = pend_mask;
-        const ElimChannel chk = elim_channel(chb);
-        auto summed = [&](const double* base, const double* p0, const double* p1, int o) {
-          const double v0 = base[o], v1 = p0[o], v2 = p1[o];
-          return (v0 + ((mask & 1) ? v1 : 0.0)) + ((mask & 2) ? v2 : 0.0);
-        };
-        if (wave == 0) {
-          const double* const Db = b.D + size_t(blk) * BB;
-          const double* const P0 = pendD_r + (size_t(blk) * 2 + 0) * BB;
-          const double* const P1 = pendD_r + (size_t(blk) * 2 + 1) * BB;
-          f64x4 t00, t01, t11;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int c = lk + 4 * r, hi = max(l16, c), lo = min(l16, c);
-            t00[r] = -summed(Db, P0, P1, hi * BP + lo);
-            t01[r] = -summed(Db, P0, P1, (16 + l16) * BP + c);
-            t11[r] = -summed(Db, P0, P1, (16 + hi) * BP + 16 + lo);
-          }
-          if (uniform(terminated_v)) { leave_terminated(); return; }
-          stamp(0, 0);
-          elim_chief_reg<0>(t00, t01, t11, nullptr, 0, chk, lane);
-          stamp(0, 1);
-        } else {
-          const bool has_next = right >= 0;
-          const double* const Gb = Gr + size_t(blk) * BB;      // G[next's dim][this block's dim]
-          f64x4 x0[2], x1[2], n00 = zero4, n01 = zero4, n11 = zero4;
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const double g0 = Gb[(16 * qt + l16) * BP + lk + 4 * r], g1 = Gb[(16 * qt + l16) * BP + 16 + lk + 4 * r];
-              x0[qt][r] = -(has_next ? g0 : 0.0); x1[qt][r] = -(has_next ? g1 : 0.0);
-            }
-          }
-          if (uniform(terminated_v)) { leave_terminated(); return; }
-          stamp(0, 0);
-          elim_follow_d(x0, x1, Zr + CB, Zr + CB + 16, 1, XLD, chk, lane, n00, n01, n11);
-          ctr_set(C_DONE_D1, 1);
-          stamp(0, 1);
-          if (right >= 0 && role == 0) {
-            double* dst = pendD_w + (size_t(right) * 2 + 0) * BB;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int c = lk + 4 * r;
-              put(dst + c * BP + l16, -n00[r]);
-              put(dst + (16 + l16) * BP + c, -n01[r]);
-              put(dst + (16 + c) * BP + 16 + l16, -n11[r]);
-            }
-          }
-        }
-      } else {
       // this lane's entries of a spine (tiles (0,0), (0,1), (1,1): elim_load_spine) and of the rows of Bᵀ (two row tiles of
       // sixteen dimensions of the next block against this block's 32 columns: elim_load_rows) in the band's storage
       unsigned oS[12], oB[16];
@@ -1161,7 +1087,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
             in.fa = req_act(blk0); in.fn = req_act(blk0 + 1);
           }
           hstamp(3);
-          if (uniform(terminated_v)) { leave_terminated(); return; }
+          if (uniform(terminated_v)) return;
           hstamp(4);
           const bool second = uniform(r_cur_v) != 0;
 #pragma unroll
@@ -1218,7 +1144,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
         if (want_fill && par == ((q - 1) & 1)) fill_half(1);      // (the last block's chief: see fill_half)
       } else {
         // ---- wave 7: stages the followers' inputs of blocks 1.. as tile images, a block ahead; files with waves 4..6 ----
-        if (uniform(terminated_v)) { leave_terminated(); return; }
+        if (uniform(terminated_v)) return;
         a.R = uniform(r_cur_v) ? R_buf1 : R_buf0;
         const double* const bandC = a.R + a.off_B();      // R(x)'s band
         const int lt2 = tid - 256;
@@ -1268,11 +1194,10 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
           ctr_set(C_FILED + 3, k + 1);
         }
       }
-      }
     } else if (wave == 2) {
       // ---- the rows of Aᵀ: Z^A. First block: T(block, left separator) from R(x); from the second on the fill -Z^BᵀZ^A ----
       f64x4 pre0[2] = {zero4, zero4}, pre1[2] = {zero4, zero4};
-      if constexpr (FROM_R) {
+      {
         // entry (this block's row rb, the left separator's column cs): tile qt holds cs = 16 qt + l16, register r rb = 16 h + lk + 4 r
         // (g_roll_tab words 32..47, counted from the left separator's superblock)
         double av[16], av1[16];
@@ -1286,7 +1211,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
           if (has_left) { av[e] = ldo(p, oA[e]); av1[e] = ldo(p + alt, oA[e]); }
         }
         const int f_this = req_act(blk0), f_left = req_act(blk0 - 1);
-        if (uniform(terminated_v)) { leave_terminated(); return; }
+        if (uniform(terminated_v)) return;
         const bool second = uniform(r_cur_v) != 0;
         const int nreal = n_s - RB * blk0;
         const unsigned m_this = act_mask(f_this), m_left = act_mask(f_left);
@@ -1302,18 +1227,6 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
             pre1[qt][r] = -(v1 ? (second ? av1[e1] : av[e1]) : 0.0);
           }
         }
-      } else {
-        // G[left separator][this block's dim][the separator's dim]
-        const double* const Ga = Gr + size_t(left > 0 ? left : 0) * BB;
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double g0 = Ga[(lk + 4 * r) * BP + 16 * qt + l16], g1 = Ga[(16 + lk + 4 * r) * BP + 16 * qt + l16];
-            pre0[qt][r] = -(has_left ? g0 : 0.0); pre1[qt][r] = -(has_left ? g1 : 0.0);
-          }
-        }
-        if (uniform(terminated_v)) { leave_terminated(); return; }
       }
       auto fill_pre = [&](const double* Zp) {      // pre = -(0 - Z^BᵀZ^A), in the elimination's (negated) tile layout
         double zb0[8], zb1[8], za[8];
@@ -1345,11 +1258,11 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
         ctr_set(C_DONE_A, k + 1);
         stamp(k, 1);
       }
-      if (want_fill) { fill_half(0); if (!FROM_R) fill_half(1); }
+      if (want_fill) fill_half(0);
     } else if (wave == 3) {
       if (role == 0) {
         // ---- the identity rows: L⁻ᵀ ----
-        if (uniform(terminated_v)) { leave_terminated(); return; }
+        if (uniform(terminated_v)) return;
         for (int k = 0; k < q; ++k) {
           const ElimChannel chk = elim_channel(chb + (k % 3) * kElimBufDoubles);
           double* const Mk = Mr + (k & 1) * BP * DLD;
@@ -1375,34 +1288,19 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
         };
         unsigned m_f = 31u;      // activity of the block whose F rows are in fv
         auto f_valid = [&](int k, int e) {
-          if (!FROM_R) return true;      // (D / F of a separator hold the padding's values themselves)
           const int r = 16 * (e >> 2) + lk + 4 * (e & 3);
           return r < RB && r < n_s - RB * (blk0 + k) && col <= a.mc && act(m_f, r);
         };
         double fv[8];
-        int f_flag = FROM_R ? req_act(blk0) : 1;
+        int f_flag = req_act(blk0);
         {
-          if constexpr (FROM_R) {
-            double fv1[8];
-            req_f(0, fv, R_buf0); req_f(0, fv1, R_buf1);
-            if (uniform(terminated_v)) { leave_terminated(); return; }
-            const bool second = uniform(r_cur_v) != 0;
-            a.R = second ? R_buf1 : R_buf0;
+          double fv1[8];
+          req_f(0, fv, R_buf0); req_f(0, fv1, R_buf1);
+          if (uniform(terminated_v)) return;
+          const bool second = uniform(r_cur_v) != 0;
+          a.R = second ? R_buf1 : R_buf0;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) fv[e] = second ? fv1[e] : fv[e];
-          } else {
-            // F + what the chains on either side left for this separator (the sum the barrier form's loaders take)
-            const double* const Fb = b.F + size_t(blk0) * fblk;
-            const double* const P0 = pendF_r + (size_t(blk0) * 2 + 0) * fblk;
-            const double* const P1 = pendF_r + (size_t(blk0) * 2 + 1) * fblk;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const size_t o2 = size_t(16 * (e >> 2) + lk + 4 * (e & 3)) * m1p + col;
-              const double v0 = Fb[o2], v1 = P0[o2], v2 = P1[o2];
-              fv[e] = (v0 + ((pend_mask & 1) ? v1 : 0.0)) + ((pend_mask & 2) ? v2 : 0.0);
-            }
-            if (uniform(terminated_v)) { leave_terminated(); return; }
-          }
+          for (int e = 0; e < 8; ++e) fv[e] = second ? fv1[e] : fv[e];
         }
         for (int k = 0; k < q; ++k) {
           const ElimChannel chk = elim_channel(chb + (k % 3) * kElimBufDoubles);
@@ -1412,7 +1310,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
           m_f = act_mask(f_flag);
 #pragma unroll
           for (int r = 0; r < 4; ++r) { pre0[0][r] = -(f_valid(k, r) ? fv[r] : 0.0); pre1[0][r] = -(f_valid(k, 4 + r) ? fv[4 + r] : 0.0); }
-          if (FROM_R && k + 1 < q) { req_f(k + 1, fv, a.R); f_flag = req_act(blk0 + k + 1); }
+          if (k + 1 < q) { req_f(k + 1, fv, a.R); f_flag = req_act(blk0 + k + 1); }
           if (k > 0) {
             const double* Zp = Zr + ((k - 1) & 1) * BP * XLD;
             double zb0[8], zb1[8], zf[8];
@@ -1449,7 +1347,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
       }
     } else {
       // ---- waves 4..6: filing, the left separator's sums, the channel ----
-      if (uniform(terminated_v)) { leave_terminated(); return; }
+      if (uniform(terminated_v)) return;
       const int w4 = wave - 4, lt2 = tid - 256;
       const bool acc_owner = wave == 5 || wave == 6, acc_owner2 = role == 0 && wave == 5;
       const int acc_p = role == 0 ? CA + (wave == 6 ? 16 : 0) : CA + 16 * (wave - 5);
@@ -1461,17 +1359,13 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
         const int blk = blk0 + k;
         const double* const Zk = Zr + (k & 1) * BP * XLD;
         if (role == 0) {
-          // (an upper level with riders behind it: what only the back-substitution reads is filed BEHIND the fan-in -- the
-          //  arrival drains every store of the wave, and these 24 KB are nobody's business in this launch)
-          if (!pub) {
-            const double* const Mk = Mr + (k & 1) * BP * DLD;
+          const double* const Mk = Mr + (k & 1) * BP * DLD;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int e = lt2 + 256 * u, r = e >> 5, c = e & 31;
-              b.M[size_t(blk) * BB + e] = Mk[r * DLD + c];
-              b.ZA[size_t(blk) * BB + e] = Zk[r * XLD + CA + c];
-              b.ZB[size_t(blk) * BB + e] = Zk[r * XLD + CB + c];
-            }
+          for (int u = 0; u < 4; ++u) {
+            const int e = lt2 + 256 * u, r = e >> 5, c = e & 31;
+            b.M[size_t(blk) * BB + e] = Mk[r * DLD + c];
+            b.ZA[size_t(blk) * BB + e] = Zk[r * XLD + CA + c];
+            b.ZB[size_t(blk) * BB + e] = Zk[r * XLD + CB + c];
           }
         } else {
 #pragma unroll
@@ -1517,31 +1411,18 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
                  tstamp[(w * 4 + 1) * 2], tstamp[(w * 4 + 1) * 2 + 1], tstamp[(w * 4 + 2) * 2], tstamp[(w * 4 + 2) * 2 + 1], tstamp[(w * 4 + 3) * 2], tstamp[(w * 4 + 3) * 2 + 1]);
       }
     }
-    if (pub) {
-      fanin_arrive(fan_word);
-      if (role == 0 && wave >= 4) {      // (single-block chains: q == 1)
-        const int lt2 = tid - 256;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int e = lt2 + 256 * u, r = e >> 5, c = e & 31;
-          b.M[size_t(blk0) * BB + e] = Mr[r * DLD + c];
-          b.ZA[size_t(blk0) * BB + e] = Zr[r * XLD + CA + c];
-          b.ZB[size_t(blk0) * BB + e] = Zr[r * XLD + CB + c];
-        }
-      }
-    }
     return;
   }
   {
     // ELIM: nobody has anything else to do before the first block is in LDS -- all eight waves fetch it, two entries of
     // D / B / A and one of the F slice each (half the instructions per thread of the loaders' share of a later block)
-    typedef typename std::conditional<kAllFetchFirst, BcrLoadMap<kLevelThreads, BB / kLevelThreads, 1>, BcrLoadMap<NL, NU, NF>>::type Map0;
+    typedef typename std::conditional<ELIM, BcrLoadMap<kLevelThreads, BB / kLevelThreads, 1>, BcrLoadMap<NL, NU, NF>>::type Map0;
     Map0 m0;
-    if constexpr (kAllFetchFirst) { m0.lt = tid; fill_map(m0); } else { m0 = lmap; }
+    if constexpr (ELIM) { m0.lt = tid; fill_map(m0); } else { m0 = lmap; }
     BcrPre<Map0::NU, Map0::NF> pr;
-    const bool load0 = kAllFetchFirst || loader;
+    const bool load0 = ELIM || loader;
     if (load0) fetch(0, pr, std::integral_constant<bool, FROM_R>(), m0);
-    if (kAllFetchFirst) fill_map(lmap);
+    if (ELIM) fill_map(lmap);
     if (FROM_R) a.R = uniform(r_cur_v) ? R_buf1 : R_buf0;        // (use_current_R; the later blocks' requests come behind the state anyway)
     if (uniform(terminated_v)) { if (pub) fanin_arrive(fan_word); return; }
     if (load0) commit(0, pr, m0);
@@ -1552,28 +1433,10 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
   if (CAL_DEV_TIMING(a.debug >= 4)) t_first = __builtin_readcyclecounter() - t_kernel;
   // (the barriers of the step loop order LDS traffic only: __syncthreads() would also drain the global loads of the
   //  next block, which are meant to stay in flight while this one is factored)
-  // LA: the left separator's sums live in loader waves 5 and 6 (wave 4 shares its SIMD with the chief, wave 7 with the
-  // follower the next block's diagonal waits for): role 0: wave 5 tiles (0,0) and (1,0) [acc_a, acc_a2], wave 6 tile (1,1);
-  // border roles: row tile 0 on wave 5, 1 on wave 6
-  const bool la_acc_owner = LA && (wave == 5 || wave == 6), la_acc_owner2 = LA && role == 0 && wave == 5;
-  const int la_acc_p = role == 0 ? CA + (wave == 6 ? 16 : 0) : CA + 16 * (wave - 5);
-  const int la_acc_q = role == 0 ? CA + (wave == 6 ? 16 : 0) : CF;
-  f64x4 acc_a2 = {0.0, 0.0, 0.0, 0.0};
-  constexpr bool kEarly = FROM_R && ELIM && !LA && BCR_EARLY_REQUESTS;
-  BcrRaw<BcrLoadMap<NL, NU, NF>::NUD, NU, NF> rw_early;
   Pre pr;
-  f64x4 pre0[2], pre1[2];       // LA: a follower's own input tiles of the next block, updated (wave 2: the two A tiles; wave 1 of a border role: the F tile)
-  if (LA && q > 1 && loader) fetch(1, pr, std::false_type(), lmap);
-  const int lane_outer = lane;
   for (int i = 0; i < q; ++i) {
-    // (the lane number made opaque once per step: every LDS / global address of a step is lane arithmetic, and kept across
-    //  the loop as loop invariants -- some hundred of them over all roles -- they were what the registers ran out on; a few
-    //  integer instructions per step form them again)
-    int lane_step = lane_outer;
-    if (LA) asm volatile("" : "+v"(lane_step));
-    const int lane = lane_step, l16 = lane & 15, lk = lane >> 4, tid = 64 * wave + lane;
+    const int tid = 64 * wave + lane;      // (the step's addresses from the scalar wave number, as before)
     const int p = i & 1;
-    double* const Zb = Zb_base + (LA ? p * BP * XLD : 0);      // LA: Z of step i is still read while the followers of step i + 1 write theirs
     double* Dp = Daug + p * 64 * DLD;
     double* Xp = Xb + p * BP * XLD;
     double* Dn = Daug + (p ^ 1) * 64 * DLD;
@@ -1585,16 +1448,9 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
 #pragma unroll
       for (int k = 0; k < 4; ++k) if (k == i) t_top[k] = t_step - t_kernel;
     }
-    if (CAL_DEV_TIMING(a.debug >= 4 && !LA && i == 1 && lane == 0 && wave >= 4)) bcast[16 + wave] = double(__builtin_readcyclecounter() - t_kernel);
-    if (!LA && !last && loader) {
-      // in flight while the block is factored (LA: requested behind the step before). EARLY (level 0, block elimination): the
-      // requests of block i + 1 went out in front of the LAST step's Schur phase -- only the selection, the damping and the
-      // commit are left, at once: the loaders' request -> commit time (address arithmetic 3-4k clocks on SIMDs they share with
-      // the chief and the followers, then the round trip) was the tail of every step, 1.5-2k clocks behind the followers.
-      if (kEarly && i > 0) fetch_finish(i + 1, rw_early, pr, std::false_type(), lmap);
-      else fetch(i + 1, pr, std::false_type(), lmap);
-    }
-    if (CAL_DEV_TIMING(a.debug >= 4 && !LA && i == 1 && lane == 0 && wave >= 4)) bcast[24 + wave] = double(__builtin_readcyclecounter() - t_kernel);
+    if (CAL_DEV_TIMING(a.debug >= 4 && i == 1 && lane == 0 && wave >= 4)) bcast[16 + wave] = double(__builtin_readcyclecounter() - t_kernel);
+    if (!last && loader) fetch(i + 1, pr, std::false_type(), lmap);      // (in flight while the block is factored)
+    if (CAL_DEV_TIMING(a.debug >= 4 && i == 1 && lane == 0 && wave >= 4)) bcast[24 + wave] = double(__builtin_readcyclecounter() - t_kernel);
     if (CAL_DEV_TIMING(a.debug == 2 && bid < 1 && lane == 0 && wave >= 4)) printf("level %d step %d wave %d: requests issued at %lld clocks of the step\n", level, i, wave, (long long)(__builtin_readcyclecounter() - t_step));
     if (ELIM) {
       // ---- D = L Lᵀ, Z = L⁻¹X and (role 0) L⁻ᵀ in one pass: wave 0 the spine, waves 1..3 two row tiles each ----
@@ -1605,12 +1461,12 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
           elim_follow<2>(t, ech, lane);
         } else {
           const ElimTile t[1] = {{Xp + CF, 1, XLD, Zb + CF, 1, XLD, 0, nullptr}};
-          elim_follow<1>(t, ech, lane, LA && i > 0, pre0, pre1);
+          elim_follow<1>(t, ech, lane);
         }
       } else if (wave == 2 || wave == 3) {
         const int c0 = wave == 2 ? CA : CB;
         const ElimTile t[2] = {{Xp + c0, 1, XLD, Zb + c0, 1, XLD, 0, nullptr}, {Xp + c0 + 16, 1, XLD, Zb + c0 + 16, 1, XLD, 0, nullptr}};
-        elim_follow<2>(t, ech, lane, LA && wave == 2 && i > 0, pre0, pre1);
+        elim_follow<2>(t, ech, lane);
       }
       if (CAL_DEV_TIMING(a.debug >= 4 && i == 1 && lane == 0)) bcast[8 + wave] = double(__builtin_readcyclecounter() - t_kernel);
       if (CAL_DEV_TIMING(a.debug == 2 && bid < 1 && lane == 0 && wave < 4)) printf("level %d step %d wave %d: elimination done at %lld clocks of the step\n", level, i, wave, (long long)(__builtin_readcyclecounter() - t_step));
@@ -1658,95 +1514,6 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
       for (int k = 0; k < 4; ++k) if (k == i) t_bara[k] = __builtin_readcyclecounter() - t_kernel;
     }
     if (ELIM && !last) elim_reset(ech, tid, kLevelThreads);      // (the followers are through; the barrier at the end of the step orders it)
-    if (kEarly && i + 2 < q && loader) fetch_request(i + 2, rw_early, std::false_type(), lmap);      // (nothing in it waits: see the top of the loop)
-    if (LA && !last) {
-      // ---- look-ahead: in front of the barrier only next.D -= Z^BᵀZ^B (and the next block's requests); behind it the other
-      //      Schur products, read from THIS step's Z buffer (the followers of the next block write the other one) ----
-      // operand of the 16x16x4 product for sixteen columns of Z: lane (l16, lk) holds Z[lk + 4u][col0 + l16]
-      auto ops = [&](int col0, double (&v)[8]) {
-        const double* pp = Zb + lk * XLD + col0 + l16;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = pp[4 * u * XLD];
-      };
-      if (wave == 0 || wave == 2 || wave == 3) {      // next.D -= Z^BᵀZ^B: tiles (0,0), (1,0), (1,1) -- the upper right one is read by nobody
-        const int it = (wave & 3) >> 1, jt = wave & 1;
-        const int row0 = 16 * it + lk, col0 = 16 * jt + l16;
-        const bool dbgw = CAL_DEV_TIMING(a.debug >= 4 && i == 1 && lane == 0 && wave == 0);
-        if (dbgw) bcast[16] = double(__builtin_readcyclecounter() - t_kernel);
-        double zp[8], zq[8];
-        ops(CB + 16 * it, zp);
-        if (it != jt) ops(CB + 16 * jt, zq);
-        f64x4 acc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = Dn[(row0 + 4 * r) * DLD + col0];
-        if (dbgw) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); bcast[17] = double(__builtin_readcyclecounter() - t_kernel); }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-zp[u], it != jt ? zq[u] : zp[u], acc, 0, 0, 0);
-        if (dbgw) { asm volatile("" :: "v"(acc[0])); bcast[18] = double(__builtin_readcyclecounter() - t_kernel); }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Dn[(row0 + 4 * r) * DLD + col0] = acc[r];
-      }
-      LTICK(5)
-      if (CAL_DEV_TIMING(a.debug >= 4 && i == 1 && lane == 0)) bcast[wave] = double(__builtin_readcyclecounter() - t_kernel);
-      lds_barrier();
-      LTICK(6)
-      // the next block but one: requested first thing behind the barrier, in flight while the next block is factored (in
-      // front of the barrier its address arithmetic -- 6k clocks at level 0 -- held the chief up)
-      if (i + 2 < q && loader) fetch(i + 2, pr, std::false_type(), lmap);
-      const bool wF = role > 0 && wave == 1;
-      if (wave == 2) {        // next.A -= Z^BᵀZ^A, in the (negated) form the elimination holds its tiles in
-        double zb0[8], zb1[8], za[8];
-        ops(CB, zb0); ops(CB + 16, zb1);
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt) {
-          ops(CA + 16 * jt, za);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            pre0[jt][r] = -Xn[(lk + 4 * r) * XLD + CA + 16 * jt + l16];
-            pre1[jt][r] = -Xn[(16 + lk + 4 * r) * XLD + CA + 16 * jt + l16];
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            pre0[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zb0[u], za[u], pre0[jt], 0, 0, 0);
-            pre1[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(zb1[u], za[u], pre1[jt], 0, 0, 0);
-          }
-        }
-      }
-      if (wF) {               // next.F -= Z^BᵀZ^F
-        double zb0[8], zb1[8], zf[8];
-        ops(CB, zb0); ops(CB + 16, zb1); ops(CF, zf);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          pre0[0][r] = -Xn[(lk + 4 * r) * XLD + CF + l16];
-          pre1[0][r] = -Xn[(16 + lk + 4 * r) * XLD + CF + l16];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          pre0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(zb0[u], zf[u], pre0[0], 0, 0, 0);
-          pre1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(zb1[u], zf[u], pre1[0], 0, 0, 0);
-        }
-      }
-      // what the back-substitution needs: filed by the loader waves
-      if (wave >= 4) {
-        const int lt2 = tid - 256;
-        if (role == 0) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int e = lt2 + 256 * u, r = e >> 5, c = e & 31;
-            b.M[size_t(blk) * BB + e] = Dp[(BP + r) * DLD + c];
-            b.ZA[size_t(blk) * BB + e] = Zb[r * XLD + CA + c];
-            b.ZB[size_t(blk) * BB + e] = Zb[r * XLD + CB + c];
-          }
-        } else {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) { const int e = lt2 + 256 * u; put(b.Y + size_t(blk) * fblk + size_t(e >> 4) * m1p + f0 + (e & 15), Zb[(e >> 4) * XLD + CF + (e & 15)]); }
-        }
-      }
-      // what the left separator collects over the chain (see la_acc_tile: on loader waves that do not share a SIMD with the chief)
-      if (left >= 0 && la_acc_owner) acc_a = atb_tile<true>(Zb, XLD, la_acc_p, Zb, XLD, la_acc_q, 0, BP, acc_a, lane);
-      if (left >= 0 && la_acc_owner2) acc_a2 = atb_tile<true>(Zb, XLD, CA + 16, Zb, XLD, CA, 0, BP, acc_a2, lane);
-      continue;
-    }
     // ---- file what the back-substitution needs ----
     if (role == 0) {
 #pragma unroll
@@ -1820,10 +1587,7 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
     }
     // ---- what the left separator collects over the chain ----
     if (left >= 0) {
-      if (LA) {       // (the owners of the sums are loader waves: see la_acc_owner)
-        if (la_acc_owner) acc_a = atb_tile<true>(Zb, XLD, la_acc_p, Zb, XLD, la_acc_q, 0, BP, acc_a, lane);
-        if (la_acc_owner2) acc_a2 = atb_tile<true>(Zb, XLD, CA + 16, Zb, XLD, CA, 0, BP, acc_a2, lane);
-      } else if (role == 0) {
+      if (role == 0) {
         if (wave < 4 && !sym_skip) acc_a = atb_tile<true>(Zb, XLD, CA + 16 * it, Zb, XLD, CA + 16 * jt, 0, BP, acc_a, lane);
       } else if (wave == 2 || wave == 3) {
         acc_a = atb_tile<true>(Zb, XLD, CA + 16 * (wave - 2), Zb, XLD, CF, 0, BP, acc_a, lane);
@@ -1839,26 +1603,21 @@ __global__ __launch_bounds__(kLevelThreads) void bcr_level_kernel(SolveArgs a, B
 #undef LTICK
   if (left >= 0) {
     if (role == 0) {
-      if (LA ? la_acc_owner : (wave < 4 && !(ELIM && wave == 1))) {
-        const int it = LA ? (wave == 6 ? 1 : 0) : wave >> 1, jt = LA ? (wave == 6 ? 1 : 0) : wave & 1;
+      if (wave < 4 && !(ELIM && wave == 1)) {
+        const int it = wave >> 1, jt = wave & 1;
         double* dst = pendD_w + (size_t(left) * 2 + 1) * BB;
 #pragma unroll
         for (int r = 0; r < 4; ++r) put(dst + (16 * it + lk + 4 * r) * BP + 16 * jt + l16, acc_a[r]);
-        if (la_acc_owner2) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) put(dst + (16 + lk + 4 * r) * BP + l16, acc_a2[r]);
-        }
       }
-    } else if (LA ? la_acc_owner : (wave == 2 || wave == 3)) {
-      const int h = LA ? wave - 5 : wave - 2;
+    } else if (wave == 2 || wave == 3) {
+      const int h = wave - 2;
       double* dst = pendF_w + (size_t(left) * 2 + 1) * fblk + f0 + l16;
 #pragma unroll
       for (int r = 0; r < 4; ++r) put(dst + size_t(16 * h + lk + 4 * r) * m1p, acc_a[r]);
     }
   }
-  if (CAL_DEV_TIMING(a.debug >= 4 && !LA && tid == 0 && bid < 4 && q > 1)) printf("bcr_level %d wg %d, step 1: loaders (waves 4..7) begin their requests at %.0f %.0f %.0f %.0f, have issued them at %.0f %.0f %.0f %.0f, have committed at %.0f %.0f %.0f %.0f | chief / followers through at %.0f %.0f %.0f %.0f\n", level, bid,
+  if (CAL_DEV_TIMING(a.debug >= 4 && tid == 0 && bid < 4 && q > 1)) printf("bcr_level %d wg %d, step 1: loaders (waves 4..7) begin their requests at %.0f %.0f %.0f %.0f, have issued them at %.0f %.0f %.0f %.0f, have committed at %.0f %.0f %.0f %.0f | chief / followers through at %.0f %.0f %.0f %.0f\n", level, bid,
       bcast[20], bcast[21], bcast[22], bcast[23], bcast[28], bcast[29], bcast[30], bcast[31], bcast[12], bcast[13], bcast[14], bcast[15], bcast[8], bcast[9], bcast[10], bcast[11]);
-  if (CAL_DEV_TIMING(a.debug >= 4 && LA && tid == 0 && bid < 4 && q > 1)) printf("bcr_level %d wg %d: arrival at the second barrier of step 1 by wave: %.0f %.0f %.0f %.0f %.0f %.0f %.0f %.0f | end of the elimination (commit for 4..7) of step 1 by wave: %.0f %.0f %.0f %.0f %.0f %.0f %.0f %.0f | wave 0, step 1: behind the first barrier %.0f, operands there %.0f, products done %.0f\n", level, bid, bcast[0], bcast[1], bcast[2], bcast[3], bcast[4], bcast[5], bcast[6], bcast[7], bcast[8], bcast[9], bcast[10], bcast[11], bcast[12], bcast[13], bcast[14], bcast[15], bcast[16], bcast[17], bcast[18]);
   if (CAL_DEV_TIMING(a.debug >= 4 && tid == 0 && (bid < 9 || bid % 7 == 0))) printf("bcr_level %d: chain workgroup %d (role %d) lived %lld clocks: set-up done at %lld, first block in LDS at %lld, chain done at %lld | steps begin %lld %lld %lld %lld | wave 0 through with its part %lld %lld %lld %lld | Z there %lld %lld %lld %lld\n", level, bid, role, (long long)(__builtin_readcyclecounter() - t_kernel), t_setup, t_first, t_loop, t_top[0], t_top[1], t_top[2], t_top[3], t_elim[0], t_elim[1], t_elim[2], t_elim[3], t_bara[0], t_bara[1], t_bara[2], t_bara[3]);
   if (role == 0 && wave == 0 && lane == 0 && !(pmin > 0.0)) st->chol_failed = 1;
   if (pub) fanin_arrive(fan_word);
@@ -2619,18 +2378,14 @@ static_assert(kDenseChan >= 64 * DLD, "the panel buffer must fit where the chann
 // (Taking the top level of the tree along in this workgroup -- back_calib + back_node for its one to three nodes -- was
 //  tried and lost: two nodes one after the other cost 12 us of dependent loads here against the 7 us of a launch that
 //  runs them side by side, and the levels below then sweep their own border rows.)
-// t0 > 0: the system is what the blocked multi-launch factorisation (reduced_block_step_kernel) left of a larger one --
+// t0 > 0: the system is what the blocked multi-launch factorisation (reduced_block_step_mfma_kernel) left of a larger one --
 // unknowns t0 .. a.m - 1, in place in slice 0 of a.Spart with the full system's row stride, right-hand side in its row a.m.
 // elim (round 4): every 32-column block is eliminated by block_elim.hpp in place -- wave 0 the chief on the diagonal block (L
 // into the lower triangle), waves 1..3 the followers: the identity rows (L⁻ᵀ: strict upper triangle + dinvm), the row tiles
 // below (Z = A_ij L⁻ᵀ comes out of the factorisation, in place) and the right-hand side as a single-row tile (z = g L⁻ᵀ) --,
 // waves 4..7 beside them the trailing tiles of the block before that the current block does not touch; between two
 // blocks one phase: right-hand side of the rows below, and the trailing update of the NEXT block's two column tiles.
-// COH (the body rides in reduced_fused_kernel behind the blocked steps of the same launch): what those steps wrote -- the
-// system that is left, the factor's panels, the forward-substituted right-hand side -- is read with L1-bypassing loads.
-template <bool COH = false>
-DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const Handoff& ho, int t0 = 0, int outer_back = 0, int elim = 0, int code_pf = 0) {
-  auto ldc = [](const double* p) { return COH ? load_sc1(p) : *p; };
+DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const Handoff& ho, int t0 = 0, int outer_back = 0, int elim = 0) {
   const long long t_entry = CAL_DEV_TIMING(a.debug != 0) ? __builtin_readcyclecounter() : 0;
   LmState* st = a.st;
   const int terminated = st->terminated;
@@ -2665,11 +2420,11 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
       const int c = min(tid, m - 1);
       // (one request per slice there is: these two waves carry the longest share of the load phase's instructions)
       const double* const rp = Sp + size_t(m) * M1 + c;
-      rhs_acc = 0.0 + ldc(rp);
-      if (nsl > 1) rhs_acc += ldc(rp + mm);
+      rhs_acc = 0.0 + *rp;
+      if (nsl > 1) rhs_acc += *(rp + mm);
       if (nsl > 2) {
 #pragma unroll
-        for (int k = 2; k < 8; ++k) rhs_acc += ldc(rp + size_t(min(k, nsl - 1)) * mm) * (k < nsl ? 1.0 : 0.0);
+        for (int k = 2; k < 8; ++k) rhs_acc += *(rp + size_t(min(k, nsl - 1)) * mm) * (k < nsl ? 1.0 : 0.0);
       }
     }
     // The lower triangle FOLDED into a rectangle of mp/2 rows of mp entries, dealt flat over the workgroup (sixteen entries per
@@ -2687,7 +2442,7 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
     double vdiag = 0.0;
     {
       const int rl = min(rd, m - 1), off = rl * M1 + rl;
-      vdiag = (0.0 + ldc(Sp + off) * 1.0) + ldc(Sp + off + slice1) * w1;
+      vdiag = (0.0 + *(Sp + off) * 1.0) + *(Sp + off + slice1) * w1;
     }
     // (the block count as a compile-time constant: thread tid's entries tid + 512 u then sit at folded row f0 + (16 / NB) u
     //  and a fixed position -- no division, and most of the index arithmetic folds)
@@ -2704,7 +2459,7 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
         const int r = low ? f : MP - 1 - f, c = low ? p : p - f - 1;
         rc[u] = r << 8 | c;
         const int rl = min(r, m - 1), cl = min(c, rl), off = rl * M1 + cl;
-        v[u] = TWO ? (0.0 + ldc(Sp + off) * 1.0) + ldc(Sp + off + slice1) * w1 : ldc(Sp + off);
+        v[u] = TWO ? (0.0 + *(Sp + off) * 1.0) + *(Sp + off + slice1) * w1 : *(Sp + off);
       }
       if (terminated) return;
 #pragma unroll
@@ -2757,7 +2512,6 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
   const bool dbg = CAL_DEV_TIMING(a.debug == 1 && (tid == 0 || tid == 64 * 5));
   long long tph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tk = dbg ? __builtin_readcyclecounter() : 0;
 #define DTICK(i) if (dbg) { const long long t_ = __builtin_readcyclecounter(); tph[i] += t_ - tk; tk = t_; }
-  asm volatile("" :: "v"(code_pf));      // (prefetch_code: the kernel's code, asked for at its first instructions)
   __syncthreads();
   DTICK(0)
   if (dbg) printf("dense_block_solve wave %d: %lld clocks from the kernel's first instruction to the loaded system\n", wave, (long long)(tk - t_entry));
@@ -3190,7 +2944,7 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
       for (int i0 = c0 + BP + g; i0 < mt; i0 += 64) {
         double lv[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) lv[u] = ldc(Lg + size_t(min(i0 + 16 * u, mt - 1)) * M1 + c0 + c);
+        for (int u = 0; u < 4; ++u) lv[u] = *(Lg + size_t(min(i0 + 16 * u, mt - 1)) * M1 + c0 + c);
 #pragma unroll
         for (int u = 0; u < 4; ++u) part += i0 + 16 * u < mt ? lv[u] * ybig[i0 + 16 * u] : 0.0;
       }
@@ -3198,10 +2952,10 @@ DEVI void dense_block_solve_body(const SolveArgs& a, int nsl, double* lds, const
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int e = tid + kDenseThreads * u, r = e >> 5, c2 = e & 31;
-        const double v = ldc(Lg + size_t(c0 + r) * M1 + c0 + c2);
+        const double v = *(Lg + size_t(c0 + r) * M1 + c0 + c2);
         Mt[r * 33 + c2] = c2 > r ? v : (c2 == r ? 1.0 / v : 0.0);
       }
-      const double zq = tid < BP ? ldc(Lg + size_t(mt) * M1 + c0 + tid) : 0.0;
+      const double zq = tid < BP ? *(Lg + size_t(mt) * M1 + c0 + tid) : 0.0;
       lds_barrier();
       if (tid < BP) {
         double pd = 0.0;
@@ -3244,16 +2998,14 @@ __global__ __launch_bounds__(kDenseThreads) void dense_back_kernel(SolveArgs a, 
   __shared__ double sh[64];
   const Handoff ho = {word, seq};
   const long long t_db = CAL_DEV_TIMING(a.debug == 4) ? __builtin_readcyclecounter() : 0;
-  const int code_pf = 0;
   if (blockIdx.x == 0) {
-    dense_block_solve_body(a, nsl, lds, ho, 0, 0, elim, code_pf);
+    dense_block_solve_body(a, nsl, lds, ho, 0, 0, elim);
     if (CAL_DEV_TIMING(a.debug == 4 && threadIdx.x == 0)) printf("dense_back: the solve's workgroup lived %lld clocks (terminated %d)\n", (long long)(__builtin_readcyclecounter() - t_db), a.st->terminated);
     return;
   }
   bcr_back_body<QM, MODE, true, PRE>(a, b, int(blockIdx.x) - 1, node0, n_nodes, 1, q_max, x, x_cand, blocks, n_blocks, ts, lds, sh, ho,
                                      node0 == 0 ? q_max : 0);      // (the nodes of this launch are level 0's: launch_dense_back)
   if (CAL_DEV_TIMING(a.debug == 4 && threadIdx.x == 0)) printf("dense_back: workgroup %d lived %lld clocks (terminated %d)\n", int(blockIdx.x), (long long)(__builtin_readcyclecounter() - t_db), a.st->terminated);
-  asm volatile("" :: "v"(code_pf));
 }
 size_t dense_block_solve_lds_bytes() { return size_t(128 * DNL + 128 + kDenseChan + 128 * 3 + 32 + 128 + kDenseThreads) * sizeof(double); }
 hipError_t configure_dense_block_solve() {
@@ -3271,21 +3023,14 @@ void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0,
 // every workgroup, no communication), forms Zᵀ = L⁻¹ Pᵀ for its two row blocks P_I, P_K of the panel on the matrix
 // cores and subtracts Z_I Z_Kᵀ from its tile in 16x16 MFMA tiles. The panel rows are read along the rows (a wave reads
 // two 256-byte row segments per instruction) and transposed through LDS; the tile itself travels through the MFMA
-// accumulators. Replaces reduced_block_step_kernel's 64-row in-wave column Cholesky (14k clocks per step) and its
-// one-row-per-lane loads (64 cache lines per instruction: 21k clocks for the first step, which also sums the K-slices
-// of the Schur complement). The first tile column files the panel into the factor L (Swork): L_jj by workgroup 0, the
+// accumulators. (Round 2's step, a 64-row in-wave column Cholesky with one-row-per-lane loads, took 14k clocks per step
+// and 21k for the first, which also sums the K-slices of the Schur complement.) The first tile column files the panel into the factor L (Swork): L_jj by workgroup 0, the
 // rows below by the workgroups with K = 0; the right-hand side rides as row m.
 // ---------------------------------------------------------------------------
 constexpr int kStepThreads = 512;
 constexpr int PTL = 65;       // row stride of the transposed panel blocks [32][64]
-// FUSED (reduced_fused_kernel: all steps and the in-LDS solve in one launch, step j + 1 behind a fan-in of step j's
-// workgroups): the trailing matrix and the factor's panels leave with write-through stores and are read with L1-bypassing
-// loads; `bid` is the workgroup's number within its step. Returns without a word on a terminated solve -- the caller arrives
-// at the fan-in either way.
-template <bool FUSED>
+// `bid`: the workgroup's number within the step.
 DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, double* lds) {
-  auto ldA = [](const double* p) { return FUSED ? load_sc1(p) : *p; };
-  auto stA = [](double* p, double v) { if (FUSED) store_sc1(p, v); else *p = v; };
   LmState* st = a.st;
   if (st->terminated) return;
   double* const Daug = lds;                        // [64][DLD]: rows 0..31 A_jj -> L_jj, rows 32..63 identity -> L⁻ᵀ
@@ -3312,8 +3057,8 @@ DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, d
   for (int u = 0; u < 2; ++u) {      // pivot block: the lower triangle is stored, the upper one mirrored
     const int e = tid + kStepThreads * u, r = e >> 5, c = e & 31;
     const size_t o = size_t(c0 + max(r, c)) * m1 + c0 + min(r, c);
-    double v = ldA(A + o);
-    for (int k = 1; k < nsl; ++k) v += ldA(A + size_t(k) * msq + o);
+    double v = *(A + o);
+    for (int k = 1; k < nsl; ++k) v += *(A + size_t(k) * msq + o);
     dv[u] = v;
   }
 #pragma unroll
@@ -3324,8 +3069,8 @@ DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, d
       const int e = tid + kStepThreads * u, r = e >> 5, c = e & 31;
       const int row = rb + r;
       const size_t o = size_t(min(row, m1 - 1)) * m1 + c0 + c;
-      double v = ldA(A + o);
-      for (int k = 1; k < nsl; ++k) v += ldA(A + size_t(k) * msq + o);
+      double v = *(A + o);
+      for (int k = 1; k < nsl; ++k) v += *(A + size_t(k) * msq + o);
       pv[h][u] = row < m1 ? v : 0.0;
     }
   }
@@ -3339,8 +3084,8 @@ DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, d
     for (int r = 0; r < 4; ++r) {
       const int ur = rI + 16 * ti + lk + 4 * r, uc = rK + 16 * tj + l16;
       const size_t o = size_t(min(ur, m1 - 1)) * m1 + min(uc, m1 - 1);
-      double v = ldA(A + o);
-      for (int k = 1; k < nsl; ++k) v += ldA(A + size_t(k) * msq + o);
+      double v = *(A + o);
+      for (int k = 1; k < nsl; ++k) v += *(A + size_t(k) * msq + o);
       tacc[q][r] = v;
     }
   }
@@ -3386,14 +3131,14 @@ DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, d
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int e = tid + kStepThreads * u, r = e >> 5, c = e & 31;
-      stA(L + size_t(c0 + r) * m1 + c0 + c, c <= r ? Daug[r * DLD + c] : Daug[(BP + r) * DLD + c]);
+      *(L + size_t(c0 + r) * m1 + c0 + c) = c <= r ? Daug[r * DLD + c] : Daug[(BP + r) * DLD + c];
     }
   }
   if (K == 0) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int e = tid + kStepThreads * u, r = e >> 5, c = e & 31;
-      if (rI + r < m1) stA(L + size_t(rI + r) * m1 + c0 + c, ZT[c * PTL + r]);
+      if (rI + r < m1) *(L + size_t(rI + r) * m1 + c0 + c) = ZT[c * PTL + r];
     }
   }
   // ---- tile update: A_IK -= Z_I Z_Kᵀ ----
@@ -3404,57 +3149,18 @@ DEVI void reduced_block_step_body(const SolveArgs& a, int j, int nsl, int bid, d
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int ur = rI + 16 * ti + lk + 4 * r, uc = rK + 16 * tj + l16;
-      if (ur < m1 && uc <= ur) stA(A + size_t(ur) * m1 + uc, tacc[q][r]);
+      if (ur < m1 && uc <= ur) *(A + size_t(ur) * m1 + uc) = tacc[q][r];
     }
   }
 }
 __global__ __launch_bounds__(kStepThreads) void reduced_block_step_mfma_kernel(SolveArgs a, int j, int nsl) {
   extern __shared__ double lds[];
-  reduced_block_step_body<false>(a, j, nsl, int(blockIdx.x), lds);
-}
-// Workgroups of step j of the blocked factorisation (T(T+1)/2 tiles of 64x64 below the panel, at least one)
-__host__ __device__ inline int reduced_step_workgroups(int m1, int j) {
-  const int rows = m1 - BP * (j + 1), T = rows > 0 ? (rows + 63) / 64 : 0;
-  return T > 0 ? T * (T + 1) / 2 : 1;
-}
-// The whole blocked factorisation of a reduced system of more than 128 columns in ONE launch: the workgroups of step j + 1
-// wait for those of step j at a fan-in word (words[j]; every workgroup arrives, terminated solve or not), the last
-// workgroup is the in-LDS solver of what the steps leave (dense_block_solve_body with the blocked backward sweep behind
-// it) and waits for the last step. All of them are resident at once (launch_reduced_fused checks the count), so nobody
-// waits for a workgroup that has no CU. The solver's workgroup clears the words behind its wait: every other waiter has
-// passed its own by then (it has arrived at a later word), and the next launch finds zeros.
-static_assert(kStepThreads == kDenseThreads, "one launch, one workgroup size");
-__global__ __launch_bounds__(kStepThreads) void reduced_fused_kernel(SolveArgs a, int nsteps, int nsl, int* words, int elim) {
-  extern __shared__ double lds[];
-  const int m1 = a.m + 1;
-  int bid = blockIdx.x, j = 0;
-  for (; j < nsteps; ++j) { const int nw = reduced_step_workgroups(m1, j); if (bid < nw) break; bid -= nw; }
-  if (j < nsteps) {
-    if (j > 0) fanin_wait(words + j - 1, reduced_step_workgroups(m1, j - 1));
-    reduced_block_step_body<true>(a, j, j == 0 ? nsl : 1, bid, lds);
-    fanin_arrive(words + j);
-    return;
-  }
-  fanin_wait(words + nsteps - 1, reduced_step_workgroups(m1, nsteps - 1));
-  if (int(threadIdx.x) < nsteps) __hip_atomic_store(words + threadIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  dense_block_solve_body<true>(a, 1, lds, Handoff{nullptr, 0}, BP * nsteps, 1, elim);
+  reduced_block_step_body(a, j, nsl, int(blockIdx.x), lds);
 }
 size_t reduced_block_step_lds_bytes() { return size_t(64 * DLD + 4 * BP * PTL + 80 + 128 + kStepThreads) * sizeof(double); }
 hipError_t configure_reduced_block_step() {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_block_step_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                              int(reduced_block_step_lds_bytes()));
-}
-size_t reduced_fused_lds_bytes() { return std::max(reduced_block_step_lds_bytes(), dense_block_solve_lds_bytes()); }
-hipError_t configure_reduced_fused() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(reduced_fused_lds_bytes()));
-}
-// false: too many workgroups to count on all of them being resident together (one per CU with the solver's LDS footprint)
-bool launch_reduced_fused(const SolveArgs& a, int nsteps, int nsl, int* words, hipStream_t s) {
-  int n_wg = 1;
-  for (int j = 0; j < nsteps; ++j) n_wg += reduced_step_workgroups(a.m + 1, j);
-  if (nsteps < 1 || nsteps > 8 || n_wg > 128) return false;
-  hipLaunchKernelGGL(reduced_fused_kernel, dim3(n_wg), dim3(kStepThreads), reduced_fused_lds_bytes(), s, a, nsteps, nsl, words, dense_elim_mode());
-  return true;
 }
 void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hipStream_t s) {
   hipLaunchKernelGGL(reduced_block_step_mfma_kernel, dim3(n_wg), dim3(kStepThreads), reduced_block_step_lds_bytes(), s, a, j, nsl);
@@ -3471,8 +3177,7 @@ bool schur_rides_in_last_level(int n_levels, int n_last_nodes, int root) {
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows) {
   const char* fe = std::getenv("CALICO_FUSE_BACK");       // (read per solve: an A/B switch, and what the tests toggle)
   const bool on = !fe || std::atoi(fe) != 0;
-  static const bool use_block = [] { const char* e = std::getenv("CALICO_DENSE"); return !(e && std::string(e) == "panel"); }();
-  return on && use_block && a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
+  return on && a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
 }
 // PRE: the nodes form their solution as an affine map of the reduced solve's output while they wait (back_node_pre);
 // needs mc + 33 <= 128 columns (one 16-column tile per wave) and a reduced solve long enough to hide the recursion behind:
@@ -3528,19 +3233,11 @@ static int dense_elim_mode() {
   const char* e = std::getenv("CALICO_DENSE_ROLL");
   return (!e || std::atoi(e) != 0) ? 2 : 1;
 }
-// CALICO_LOOKAHEAD=1: the tree levels' steps with look-ahead (bcr_level_kernel<.., LA>); read per solve (A/B switch). OFF by
-// default: bit-identical, but measured 1.2 us SLOWER per level-0 launch at configs[3] (26.2 against 25.0 us, same box,
-// profiles/r05_lookahead_ab.txt) -- the chief does start ~2.5k clocks earlier per step, but a step is then bounded by the
-// loader waves' commit of the next block (they lose the Schur phase as load time) and by the two barriers' own latency.
-static bool level_lookahead_enabled() { const char* e = std::getenv("CALICO_LOOKAHEAD"); return e && std::atoi(e) != 0; }
-// Level 0's chains with the rolling chief (bcr_level_kernel<true, true, false, true>: no workgroup barrier between the blocks of
+// Level 0's chains with the rolling chief (bcr_level_kernel<true, true, true>: no workgroup barrier between the blocks of
 // a chain), the default; CALICO_ROLL=0: the barrier form (A/B switch, read per solve)
 static bool level_roll_enabled() { const char* e = std::getenv("CALICO_ROLL"); return !e || std::atoi(e) != 0; }
-// the same form on the levels above level 0 (single-block chains): CALICO_ROLL_UPPER=1
-// (NOT the default: the chains of an upper level end 2-3k clocks earlier with it, the launch does not -- it ends with the Schur
-//  complement's riders behind the fan-in --, and the iteration rate is 0.7-1.5 % lower at every shape measured.)
-static bool level_roll_upper_enabled() { const char* e = std::getenv("CALICO_ROLL_UPPER"); return e && std::atoi(e) != 0; }
-size_t bcr_level_lds_bytes() { return size_t(2 * 64 * DLD + 4 * BP * XLD + 80 + 128 + kLevelThreads + kElimBufDoubles) * sizeof(double); }      // (4: X twice, Z twice with the look-ahead)
+// (4 · BP · XLD: the barrier form uses three -- X twice, Z --; the rolling form's layout needs the fourth, see its static_assert)
+size_t bcr_level_lds_bytes() { return size_t(2 * 64 * DLD + 4 * BP * XLD + 80 + 128 + kLevelThreads + kElimBufDoubles) * sizeof(double); }
 size_t bcr_back_lds_bytes(int q_max, int m1p) {
   return (size_t(2) * q_max * BP * DLD + kBcrMaxChain * BP + 3 * BP + m1p + size_t(q_max) * BP + 4 * BP) * sizeof(double);
 }
@@ -3548,9 +3245,8 @@ hipError_t configure_bcr_kernels(int q_max, int m1p) {
   hipError_t e = upload_roll_table();      // (per device: a __device__ symbol lives on each of them)
   if (e != hipSuccess) return e;
   for (const void* f : {reinterpret_cast<const void*>(&bcr_level_kernel<true, true>), reinterpret_cast<const void*>(&bcr_level_kernel<false, true>),
-                        reinterpret_cast<const void*>(&bcr_level_kernel<true, true, true>), reinterpret_cast<const void*>(&bcr_level_kernel<false, true, true>),
                         reinterpret_cast<const void*>(&bcr_level_kernel<true, false>), reinterpret_cast<const void*>(&bcr_level_kernel<false, false>),
-                        reinterpret_cast<const void*>(&bcr_level_kernel<true, true, false, true>), reinterpret_cast<const void*>(&bcr_level_kernel<false, true, false, true>)}) {
+                        reinterpret_cast<const void*>(&bcr_level_kernel<true, true, true>)}) {
     e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(bcr_level_lds_bytes()));
     if (e != hipSuccess) return e;
   }
@@ -3570,7 +3266,7 @@ hipError_t configure_bcr_kernels(int q_max, int m1p) {
 // this level's workgroups and take its results over the fan-in word; level 0 (`fan_word` given) resets the word.
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
-                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl, int q_max) {
+                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl) {
   const int nfs = (a.mc + 1 + kBcrFS - 1) / kBcrFS;
   int n_apply = n_keep > 0 ? std::min(64, std::max(1, n_keep * 4)) : 0;
   const int main_span = 8 * ((n_nodes + 7) / 8) * (1 + nfs);      // (node, role) workgroups laid out by XCD: see the kernel
@@ -3583,10 +3279,10 @@ void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nod
     const int room = kCUs - main_span - (level == 0 && with_post_eval ? 1 : 0);
     if (room >= 8 && n_apply > room) n_apply = room;
   }
-  const bool elim = block_elim_enabled(), la = level_lookahead_enabled();
+  const bool elim = block_elim_enabled();
   if (level == 0) {
-    const bool roll = elim && !la && a.k >= 1 && a.k <= 6 && level_roll_enabled();
-    hipLaunchKernelGGL((roll ? bcr_level_kernel<true, true, false, true> : elim ? (la ? bcr_level_kernel<true, true, true> : bcr_level_kernel<true, true>) : bcr_level_kernel<true, false>), dim3(main_span + n_apply + (with_post_eval ? 1 : 0)), dim3(kLevelThreads),
+    const bool roll = elim && a.k >= 1 && a.k <= 6 && level_roll_enabled();
+    hipLaunchKernelGGL((roll ? bcr_level_kernel<true, true, true> : elim ? bcr_level_kernel<true, true> : bcr_level_kernel<true, false>), dim3(main_span + n_apply + (with_post_eval ? 1 : 0)), dim3(kLevelThreads),
                        bcr_level_lds_bytes(), s, a, b, node0, n_nodes, nfs, level, keep0, n_keep, o, with_post_eval, x, blocks, n_blocks,
                        log, log_cap, jacobi, 0, 0, 1, fan_word, 0, inl);
   } else {
@@ -3596,8 +3292,7 @@ void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nod
     const int n_schur_wg = schur_ks > 0 ? nt * (nt + 1) / 2 * schur_ks : 0;
     const int n_root_wg = schur_ks > 0 ? std::max(1, (br * (a.mc + 1 + br) + kLevelThreads - 1) / kLevelThreads) : 0;
     const int n_prod = n_nodes * (1 + nfs) + n_apply;        // the workgroups of this level that really exist
-    const bool roll = elim && !la && q_max == 1 && level_roll_enabled() && level_roll_upper_enabled();      // (single-block chains: see the kernel)
-    hipLaunchKernelGGL((roll ? bcr_level_kernel<false, true, false, true> : elim ? (la ? bcr_level_kernel<false, true, true> : bcr_level_kernel<false, true>) : bcr_level_kernel<false, false>), dim3(main_span + n_apply + n_schur_wg + n_root_wg), dim3(kLevelThreads), bcr_level_lds_bytes(), s, a, b,
+    hipLaunchKernelGGL((elim ? bcr_level_kernel<false, true> : bcr_level_kernel<false, false>), dim3(main_span + n_apply + n_schur_wg + n_root_wg), dim3(kLevelThreads), bcr_level_lds_bytes(), s, a, b,
                        node0, n_nodes, nfs, level, keep0, n_keep, o, 0, x, blocks, n_blocks, log, log_cap, jacobi, n_schur_wg, n_root_wg,
                        std::max(1, schur_ks), schur_ks > 0 ? fan_word : nullptr, n_prod, inl);
   }

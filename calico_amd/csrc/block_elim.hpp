@@ -224,8 +224,8 @@ struct ElimTile {
 // A follower with NT row tiles (compile-time unrolled; the descriptors are wave-uniform).
 // use_pre: the tiles come in registers -- pre0[q] / pre1[q] = the NEGATED entries of tile q against the block's columns 0..15 /
 // 16..31 in the accumulator layout (register r of lane (l16, lk): row l16 of the tile, column lk + 4r) -- instead of being
-// loaded from t[q].in: the tree levels' followers form the Schur update of their own input tiles in exactly that layout
-// (bcr_level_kernel, look-ahead), so the updated tiles never go through LDS.
+// loaded from t[q].in: the rolling chief's followers form the Schur update of their own input tiles in exactly that layout
+// (bcr_level_kernel, ROLL), so the updated tiles never go through LDS.
 // (`use_pre` is a run-time, wave-uniform flag and not a template parameter: a second instantiation of the eight steps
 //  doubled the loop-invariant output addresses the compiler keeps across the caller's loop -- into scratch.)
 template <int NT, bool CC = false>

@@ -88,17 +88,16 @@ hipError_t configure_bcr_kernels(int q_max, int m1p);
 void roll_table_row(int k, int lane, unsigned* out);      // (host only: test hook)
 hipError_t configure_dense_block_solve();
 hipError_t configure_reduced_block_step();
-hipError_t configure_reduced_fused();
 size_t dense_block_solve_lds_bytes();
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
-                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl, int q_max);
+                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl);
 bool schur_rides_in_last_level(int n_levels, int n_last_nodes, int root);
 void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
 void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
 
-void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s, int* fan_words);
+void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
 size_t dense_back_lds_bytes(int q_max, int m1p);
 hipError_t configure_dense_back_bytes(size_t lds);
@@ -1575,7 +1574,7 @@ int prepare_workspace(calico_problem* p) {
     HIP_TRY(p, hipMemsetAsync(p->d_bG.p, 0, 2 * N * bb * sizeof(double), s));
     HIP_TRY(p, hipMemsetAsync(p->d_bpD.p, 0, 4 * N * bb * sizeof(double), s)); HIP_TRY(p, hipMemsetAsync(p->d_bpF.p, 0, 4 * N * fb * sizeof(double), s));
     HIP_TRY(p, hipMemsetAsync(p->d_bupd.p, 0, size_t(p->bcr_slots) * 4 * sizeof(double), s));
-    HIP_TRY(p, p->d_handoff.alloc(16)); HIP_TRY(p, hipMemsetAsync(p->d_handoff.p, 0, 16 * sizeof(int), s));
+    HIP_TRY(p, p->d_handoff.alloc(8)); HIP_TRY(p, hipMemsetAsync(p->d_handoff.p, 0, 8 * sizeof(int), s));
     p->handoff_seq = 0;
   }
   p->ws_ready = true;
@@ -1667,7 +1666,6 @@ int configure_kernels(calico_problem* p) {
   HIP_TRY(p, configure_solve_kernels(nw[1], nw[2], nw[3]));
   HIP_TRY(p, configure_dense_block_solve());
   HIP_TRY(p, configure_reduced_block_step());
-  HIP_TRY(p, configure_reduced_fused());
   if (nw[4]) HIP_TRY(p, configure_bcr_kernels(int(nw[5]), int(nw[6])));
   if (nw[7]) HIP_TRY(p, configure_dense_back_bytes(nw[7]));
   cur = nw;
@@ -1894,7 +1892,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
       else if (lv.n_nodes <= 4) { inl.n = lv.n_nodes; for (int i = 0; i < lv.n_nodes; ++i) inl.nd[i] = p->h_bcr_nodes[size_t(lv.node0 + i)]; }
     }
     launch_bcr_level(sa, b, lv.node0, lv.n_nodes, l, lv.keep0, lv.n_keep, o, p->d_x.p, p->d_blocks.p, n_blocks, l == 0 ? with_post_eval : 0,
-                     p->d_log.p, kLogCap, jacobi, s, schur_rides && l == L - 1 ? ks : 0, schur_rides ? fan_word : nullptr, inl, lv.q_max);
+                     p->d_log.p, kLogCap, jacobi, s, schur_rides && l == L - 1 ? ks : 0, schur_rides ? fan_word : nullptr, inl);
   }
   if (!schur_rides) launch_bcr_schur(sa, b, ks, o, s);
   if (reduce_only) return;
@@ -1923,7 +1921,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
     p->handoff_seq = p->handoff_seq % 0x3fffffff + 1;
     launch_dense_back(sa, b, ks, lf.node0, lf.n_nodes, lf.q_max, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, ts, p->d_handoff.p, p->handoff_seq, s);
   } else {
-    launch_reduced_solve(sa, p->dense_in_lds, ks, s, p->d_handoff.p + 8);      // (words 8..15: the fan-ins of a blocked factorisation in one launch)
+    launch_reduced_solve(sa, p->dense_in_lds, ks, s);
   }
   p->timer.end(s);
   for (int l = L - 1; l >= 0; --l) {

@@ -538,11 +538,7 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // A cell's block leaves with write-through stores: 6 MB of blocks written at the very end of the launch's workgroups would
 // otherwise sit dirty in the XCDs' L2s and be written back behind the last wave, inside the launch's duration.
 DEV void block_store(double* p, double v) {
-#ifdef CALICO_BLOCK_STORE_PLAIN
-  *p = v;
-#else
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 template <int NT> struct StageBTiles {      // tile t of the row-major upper triangle -> (row[t], col[t]), at compile time
   int row[NT * (NT + 1) / 2], col[NT * (NT + 1) / 2];
@@ -639,11 +635,7 @@ DEV void stage_b_mfma(LdsRows lds, int pad, int nrows, int n1, double* out) {
       const bool keep = (I < J || gi <= gj) && gj < n1;
       if (keep) {
         const unsigned off = rs[4 * I + r] + unsigned(gj);      // (unsigned: one base in scalar registers + a 32-bit offset per store)
-#ifdef CALICO_BLOCK_STORE_PLAIN
-        og[off] = acc[t][r];
-#else
         __hip_atomic_store(og + off, acc[t][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       }
     }
   }

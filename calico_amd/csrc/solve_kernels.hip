@@ -849,7 +849,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void b
 }
 
 // Sred = S - YᵀY, one 16×16 lower tile per workgroup, 64-row chunks staged in LDS with register prefetch.
-constexpr int kSchurSlices = 2;   // K-slices when the in-LDS panel solver consumes the result (it sums them on load)
+constexpr int kSchurSlices = 2;   // K-slices where reduced_schur_slices picks no other count (the consumers sum them on load)
 // `ks` workgroups share the rows (K dimension) of every tile: slice k writes its partial S/ks-th into
 // Spart + k·(m+1)² (slice 0 carries S itself), and the consumer adds the slices up when it loads the matrix.
 __global__ __launch_bounds__(256) void schur_kernel(SolveArgs a, int ks) {
@@ -957,121 +957,6 @@ __global__ __launch_bounds__(256) void reduced_solve_kernel(SolveArgs a, int use
   if (tid == 0 && s_fail) st->chol_failed = 1;
 }
 
-// Register-resident variant: thread (ti, tj) of a 16×16 grid owns the entries
-// (ti + 16a, tj + 16b) of the reduced matrix for the whole factorisation; per
-// column only the pivot column is broadcast through a double-buffered LDS
-// vector, so a step costs one barrier, 2·NT LDS reads and ~NT²/2 register FMAs.
-// The factor is kept row-major in Lrow (LDS or global); the backward substitution runs on one
-// wave in axpy form: y_i = (b_i - acc_i)/L_ii, then acc_j += L_ij y_i for j < i, the pivot value
-// travelling by v_readlane — no reduction on the dependency chain. Valid for m+1 <= 16·NT.
-template <int NT, bool L_IN_LDS>
-__global__ __launch_bounds__(256) void reduced_solve_reg_kernel(SolveArgs a) {
-  LmState* st = a.st;
-  if (st->terminated) return;
-  extern __shared__ double lds[];
-  const int m = a.m, m1 = a.m + 1, n = a.n_s();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ti = tid >> 4, tj = tid & 15;
-  constexpr int NP = 16 * NT;
-  double* colbuf = lds;                 // [2][NP]
-  double* dinv = lds + 2 * NP;          // [NP] reciprocal diagonal of the factor
-  // row-major factor Lrow[i*NP + j], rows 0..m; the address space is a template parameter so that the
-  // LDS variant compiles to ds_* instructions instead of flat ones
-  double* Lrow;
-  if constexpr (L_IN_LDS) Lrow = lds + 3 * NP; else Lrow = a.Swork;
-  __shared__ int s_fail;
-  if (tid == 0) s_fail = 0;
-  double A[NT][NT];
-#pragma unroll
-  for (int aa = 0; aa < NT; ++aa)
-#pragma unroll
-    for (int bb = 0; bb < NT; ++bb) {
-      const int i = ti + 16 * aa, c = tj + 16 * bb;
-      A[aa][bb] = (i <= m && c <= i && c < m1) ? a.Spart[size_t(i) * m1 + c] : 0.0;
-    }
-  const double dflag = (ti >= tj) ? 1.0 : 0.0;   // diagonal tiles: only c <= i
-  const bool dbg = CAL_DEV_TIMING(a.debug && tid == 0);
-  const long long t_begin = dbg ? __builtin_readcyclecounter() : 0;
-  long long tph[4] = {0, 0, 0, 0}, tk = t_begin;
-#define RTICK(i) if (dbg) { const long long t_ = __builtin_readcyclecounter(); tph[i] += t_ - tk; tk = t_; }
-  for (int j = 0; j < m; ++j) {
-    double* cb = colbuf + (j & 1) * NP;
-    const int bj = j >> 4;   // wave-uniform
-    if (tj == (j & 15)) {
-#pragma unroll
-      for (int bb = 0; bb < NT; ++bb)
-        if (bb == bj) {
-#pragma unroll
-          for (int aa = 0; aa < NT; ++aa) cb[ti + 16 * aa] = A[aa][bb];
-        }
-    }
-    RTICK(0)
-    __syncthreads();
-    RTICK(1)
-    double p = cb[j];
-    if (!(p > 0.0) || !isfinite(p)) { if (tid == 0) s_fail = 1; p = 1.0; }
-    const double rs = rsqrt_nr(p);
-    double ri[NT], cj[NT];
-#pragma unroll
-    for (int aa = 0; aa < NT; ++aa) ri[aa] = cb[ti + 16 * aa] * rs;                                   // L(i, j)
-#pragma unroll
-    for (int bb = 0; bb < NT; ++bb) cj[bb] = (tj + 16 * bb > j) ? cb[tj + 16 * bb] * rs : 0.0;        // L(c, j), c > j
-#pragma unroll
-    for (int aa = 0; aa < NT; ++aa) {
-#pragma unroll
-      for (int bb = 0; bb < aa; ++bb) A[aa][bb] -= ri[aa] * cj[bb];
-      A[aa][aa] -= ri[aa] * cj[aa] * dflag;
-    }
-    RTICK(2)
-    if (tj == (j & 15)) {   // stream the finished column out (row-major store)
-#pragma unroll
-      for (int aa = 0; aa < NT; ++aa) {
-        const int i = ti + 16 * aa;
-        if (i >= j && i <= m) Lrow[size_t(i) * NP + j] = ri[aa];
-      }
-      if (ti == 0) dinv[j] = rs;
-    }
-    RTICK(3)
-  }
-  __syncthreads();
-  if constexpr (!L_IN_LDS) __threadfence();
-  __syncthreads();
-  const long long t_fact = dbg ? __builtin_readcyclecounter() : 0;
-  if (wave == 0) {
-    constexpr int NV = (NP + 63) / 64;
-    double acc[NV], bq[NV], dv[NV], cur[NV], nxt[NV];
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int j = lane + 64 * u;
-      acc[u] = 0.0;
-      bq[u] = j < m ? Lrow[size_t(m) * NP + j] : 0.0;
-      dv[u] = j < m ? dinv[j] : 0.0;
-    }
-    auto fetch = [&](int i, double v[NV]) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u) { const int j = lane + 64 * u; v[u] = (i >= 0 && j < i) ? Lrow[size_t(i) * NP + j] : 0.0; }
-    };
-    fetch(m - 1, nxt);
-    for (int i = m - 1; i >= 0; --i) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u) cur[u] = nxt[u];
-      fetch(i - 1, nxt);
-      double cand = 0.0;
-#pragma unroll
-      for (int u = 0; u < NV; ++u) if ((i >> 6) == u) cand = (bq[u] - acc[u]) * dv[u];
-      const double yi = readlane_f64(cand, i & 63);
-#pragma unroll
-      for (int u = 0; u < NV; ++u) acc[u] += cur[u] * yi;
-      if (lane == 0) a.y[n + i] = yi;
-    }
-  }
-  __syncthreads();
-  if (dbg) printf("reduced_solve cycles/col: bcast-write %lld  barrier %lld  update %lld  store %lld | backward total %lld\n",
-                  tph[0] / (m > 0 ? m : 1), tph[1] / (m > 0 ? m : 1), tph[2] / (m > 0 ? m : 1), tph[3] / (m > 0 ? m : 1),
-                  (long long)__builtin_readcyclecounter() - t_fact);
-  if (tid == 0 && s_fail) st->chol_failed = 1;
-}
-
 // Panel variant for m+1 <= 64·RPL: the augmented reduced matrix lives in LDS (row-major, odd stride) and is
 // factored 16 columns at a time with look-ahead:
 //   [block column p+1 receives the contribution of panel p, all waves] | barrier |
@@ -1082,8 +967,8 @@ __global__ __launch_bounds__(256) void reduced_solve_reg_kernel(SolveArgs a) {
 // (left-looking) instead of once per panel. Row m is the right-hand side, so the forward substitution comes for free.
 // Backward substitution by blocks of 16: an in-wave chain for the diagonal block, a parallel matrix-vector product
 // for the rest (see below).
-// `t0`, `nsl`: the kernel factors the trailing matrix from row/column t0 on (the blocked path hands over the last
-// <= 128 rows once its panels have been eliminated; t0 = 0 otherwise) and adds up `nsl` K-slices on load.
+// `t0`, `nsl`: the kernel factors the trailing matrix from row/column t0 on and adds up `nsl` K-slices on load.
+// (launch_reduced_solve sends only a.m == 0 here; the systems with calibration blocks go to dense_block_solve_body.)
 template <int RPL>
 __global__ __launch_bounds__(256) void reduced_solve_panel_kernel(SolveArgs a, int t0, int nsl) {
   LmState* st = a.st;
@@ -1213,251 +1098,11 @@ __global__ __launch_bounds__(256) void reduced_solve_panel_kernel(SolveArgs a, i
   if (tid == 0 && s_fail) st->chol_failed = 1;
 }
 
-// ---------------------------------------------------------------------------
-// Large reduced systems (m + 1 > 128: many cameras, free chart points): blocked right-looking Cholesky over all CUs,
-// one launch per 32-column panel j. Workgroup (I, K), I >= K, owns the 64×64 tile of the trailing matrix at rows
-// t0 + 64·I, columns t0 + 64·K (t0 = first row under the panel). Each of its four waves takes the pivot block A_jj
-// in lanes 0-31 (one row per lane, 32 registers) and 32 rows of the panel under it in lanes 32-63, and runs the
-// column Cholesky on the 64 rows at once, pivots and multipliers travelling by v_readlane: lanes 0-31 end up with
-// L_jj (recomputed by every wave, which costs no time), lanes 32-63 with their rows of A_ij·L_jj⁻ᵀ. The four row
-// blocks are those of tile rows I (waves 0, 1) and tile rows K (waves 2, 3); they meet in LDS and wave (a, b)
-// subtracts P_{I,a}·P_{K,b}ᵀ from its 32×32 quarter of the tile, in place. The first tile column also files the
-// panel into the factor L (Swork). The right-hand side rides as row m, so L(m, :) is the forward-substituted vector.
-// `nsl`: K-slices of the Schur complement to add up on the first touch (panel 0 touches every entry).
+// Large reduced systems (m + 1 > 128: many cameras, free chart points): blocked right-looking Cholesky over all CUs, one
+// launch per kRB-column panel (reduced_block_step_mfma_kernel, bcr_kernels.hip), until what is left fits the in-LDS solver,
+// which finishes the factorisation and runs the backward sweep over the panels too. That sweep holds the solution in LDS.
 constexpr int kRB = 32;
-__global__ __launch_bounds__(256) void reduced_block_step_kernel(SolveArgs a, int j, int nsl) {
-  LmState* st = a.st;
-  if (st->terminated) return;
-  __shared__ double sP[4][kRB][kRB + 1];
-  __shared__ __attribute__((aligned(16))) double sCol[4][2][64];
-  const int m = a.m, m1 = a.m + 1;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c0 = kRB * j, t0 = c0 + kRB;
-  int I = 0, rem = blockIdx.x;
-  while (rem > I) { rem -= I + 1; ++I; }
-  const int K = rem;
-  const int rI = t0 + 64 * I, rK = t0 + 64 * K;
-  double* A = a.Spart;
-  const size_t msq = size_t(m1) * m1;
-  double* L = a.Swork;
-  const bool dbg = CAL_DEV_TIMING(a.debug && blockIdx.x == 0 && j <= 1);
-  long long tph[6] = {}, tk = dbg ? __builtin_readcyclecounter() : 0;
-#define BTICK(i) if (dbg) { const long long t_ = __builtin_readcyclecounter(); tph[i] += t_ - tk; tk = t_; }
-  // ---- loads: this wave's 64 rows of panel j, and this lane's 4×4 piece of the tile ----
-  const int rb = (wave < 2 ? rI : rK) + kRB * (wave & 1);
-  const int myrow = lane < kRB ? c0 + lane : rb + (lane - kRB);
-  const bool row_ok = myrow < m1;
-  const double* src = A + size_t(min(myrow, m1 - 1)) * m1;
-  double G[kRB];
-#pragma unroll
-  for (int c = 0; c < kRB; ++c) {
-    const int col = c0 + c;                // may run past the row end: masked below, and Spart has slack behind it
-    double v = src[col];
-    for (int k = 1; k < nsl; ++k) v += src[size_t(k) * msq + col];
-    const bool ok = row_ok && c0 + c < m1 && (lane >= kRB || c <= lane);
-    G[c] = ok ? v : 0.0;
-  }
-  const int qa = wave >> 1, qb = wave & 1, r4 = lane >> 3, c4 = lane & 7;
-  const int ur0 = rI + kRB * qa + 4 * r4, uc0 = rK + kRB * qb + 4 * c4;
-  double pre[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const size_t o = size_t(min(ur0 + i, m1 - 1)) * m1 + uc0 + jj;
-      double v = A[o];
-      for (int k = 1; k < nsl; ++k) v += A[size_t(k) * msq + o];
-      pre[i][jj] = v;
-    }
-  if (dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  BTICK(0)
-  // ---- column Cholesky of the 64 rows ----
-  // Column c: the unscaled column goes to a wave-private LDS vector; the pivot and the multiplier of column c+1 (the
-  // latency chain) travel by v_readlane, the other multipliers come back as broadcast ds_read_b128 — one VALU
-  // instruction per update instead of three.
-  double (*cb)[64] = sCol[wave];
-  double pmin = 1.0, psum = 0.0;
-  // pivot path of column 0; inside the loop the one of column c+1 is started before the bulk of column c's updates,
-  // so that the rsqrt chain runs under them
-  double rs, t;
-  {
-    double p = readlane_f64(G[0], 0);
-    p = c0 < m ? p : 1.0;                  // column m is the right-hand side, beyond it padding
-    pmin = fmin(pmin, p); psum += p;       // a NaN pivot poisons psum, a non-positive one shows in pmin
-    rs = rsqrt_nr(p);
-    t = G[0] * (rs * rs);
-  }
-#pragma unroll
-  for (int c = 0; c < kRB; ++c) {
-    double* buf = cb[c & 1];
-    buf[lane] = G[c];
-    __builtin_amdgcn_wave_barrier();
-    double rs_n = 1.0, t_n = 0.0;
-    if (c + 1 < kRB) {
-      G[c + 1] -= t * readlane_f64(G[c], c + 1);
-      double p = readlane_f64(G[c + 1], c + 1);
-      p = c0 + c + 1 < m ? p : 1.0;
-      pmin = fmin(pmin, p); psum += p;
-      rs_n = rsqrt_nr(p);
-      t_n = G[c + 1] * (rs_n * rs_n);
-    }
-    // Multipliers of rows e, e+1 (constant bounds: everything unrolls). The four waves of the workgroup share one
-    // LDS pipe, whose return path takes 4 clocks per broadcast double and wave; a v_readlane pair takes 8 clocks of
-    // the wave's own SIMD. Alternating between the two balances the pipes.
-    // The pins (empty asm over the updated columns and the pivot column) come after every group of 8 rows: without
-    // them the compiler sinks every update to the column's first use (a left-looking schedule that keeps all 496
-    // multipliers alive: 512 VGPRs and spills) or hoists all readlanes (SGPR spills through v_writelane).
-    double gc = G[c];
-    double2 U[kRB / 4];                     // all LDS reads of the column are issued before the first pin
-#pragma unroll
-    for (int e = 0; e < kRB; e += 4)
-      if (e >= c + 2) U[e / 4] = *reinterpret_cast<const double2*>(buf + e);
-#pragma unroll
-    for (int e8 = 0; e8 < kRB; e8 += 8) {
-      if (e8 + 7 < c + 2) continue;
-#pragma unroll
-      for (int e = e8; e < e8 + 8; e += 2) {
-        if (e >= c + 2) {
-          if ((e >> 1) & 1) {
-            G[e] -= t * readlane_f64(gc, e);
-            G[e + 1] -= t * readlane_f64(gc, e + 1);
-          } else {
-            G[e] -= t * U[e / 4].x;
-            G[e + 1] -= t * U[e / 4].y;
-          }
-        } else if (e + 1 >= c + 2) {
-          G[e + 1] -= t * readlane_f64(gc, e + 1);
-        }
-      }
-      asm volatile("" : "+v"(gc), "+v"(G[e8]), "+v"(G[e8 + 1]), "+v"(G[e8 + 2]), "+v"(G[e8 + 3]), "+v"(G[e8 + 4]), "+v"(G[e8 + 5]), "+v"(G[e8 + 6]), "+v"(G[e8 + 7]));
-    }
-    G[c] = gc * rs;
-    rs = rs_n; t = t_n;
-  }
-  BTICK(1)
-  // ---- file the panel, exchange the row blocks ----
-  if (lane >= kRB) {
-#pragma unroll
-    for (int c = 0; c < kRB; ++c) sP[wave][lane - kRB][c] = G[c];
-    if (K == 0 && wave < 2 && row_ok) {   // masked entries go to a dump word past the factor: no branch per store
-#pragma unroll
-      for (int c = 0; c < kRB; ++c) L[c0 + c < m1 ? size_t(myrow) * m1 + c0 + c : msq + lane] = G[c];
-    }
-  } else if (blockIdx.x == 0 && wave == 0 && row_ok) {
-#pragma unroll
-    for (int c = 0; c < kRB; ++c) L[c <= lane ? size_t(myrow) * m1 + c0 + c : msq + lane] = G[c];
-  }
-  if (blockIdx.x == 0 && tid == 0 && (!(pmin > 0.0) || !isfinite(psum))) st->chol_failed = 1;
-  __syncthreads();
-  BTICK(2)
-  // ---- tile update ----
-  double acc[4][4] = {};
-  const double (*PI)[kRB + 1] = sP[qa];
-  const double (*PK)[kRB + 1] = sP[2 + qb];
-#pragma unroll 8
-  for (int k = 0; k < kRB; ++k) {
-    double ra[4], rc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { ra[i] = PI[4 * r4 + i][k]; rc[i] = PK[4 * c4 + i][k]; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[i][jj] += ra[i] * rc[jj];
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int ur = ur0 + i, uc = uc0 + jj;
-      double* dst = (ur < m1 && uc <= ur) ? A + size_t(ur) * m1 + uc : L + msq + lane;
-      *dst = pre[i][jj] - acc[i][jj];
-    }
-  BTICK(3)
-  if (dbg && lane == 0) printf("reduced_block_step %d cycles (wave %d): loads %lld  factor %lld  file+barrier %lld  update+store %lld\n", j, wave, tph[0], tph[1], tph[2], tph[3]);
-#undef BTICK
-}
-
-// Backward substitution Lᵀ y_c = L(m, :) for the blocked factor, one workgroup, panel by panel from the end:
-// the half-wave whose threads own the panel's columns solves the 32×32 triangle in axpy form (one column of L_jj per
-// lane, the solved unknown travelling by v_readlane), then every thread adds the panel's contribution to the
-// pending sums of the columns it owns (column c belongs to thread c mod 256).
-constexpr int kRBCols = 4;   // columns per thread: m <= 1024
-// `np`: panels eliminated by the step kernels; the unknowns from kRB·np on were solved by the in-LDS kernel and enter
-// the pending sums first.
-__global__ __launch_bounds__(256) void reduced_block_back_kernel(SolveArgs a, int np) {
-  LmState* st = a.st;
-  if (st->terminated) return;
-  __shared__ double sy[2][kRB];
-  const int m = a.m, m1 = a.m + 1, n = a.n_s();
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double* L = a.Swork;
-  double acc[kRBCols] = {};
-  for (int i0 = kRB * np; i0 < m; i0 += kRB) {
-    __syncthreads();
-    if (tid < kRB) sy[0][tid] = i0 + tid < m ? a.y[n + i0 + tid] : 0.0;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kRBCols; ++u) {
-      const int col = tid + 256 * u;
-      if (col < kRB * np) {
-        double t[kRB];
-#pragma unroll
-        for (int i = 0; i < kRB; ++i) t[i] = L[size_t(min(i0 + i, m - 1)) * m1 + col];
-        double sacc = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRB; ++i) sacc += t[i] * sy[0][i];
-        acc[u] += sacc;
-      }
-    }
-  }
-  __syncthreads();
-  for (int jb = np - 1; jb >= 0; --jb) {
-    const int c0 = kRB * jb;
-    double* ybuf = sy[jb & 1];
-    if (wave == ((c0 & 255) >> 6)) {
-      const int l0 = c0 & 63, ci = lane - l0;       // this lane's column inside the panel (valid when 0 <= ci < 32)
-      const int col = min(c0 + min(max(ci, 0), kRB - 1), m - 1);
-      double Lc[kRB];
-#pragma unroll
-      for (int i = 0; i < kRB; ++i) Lc[i] = L[size_t(min(c0 + i, m - 1)) * m1 + col];
-      const double zq = L[size_t(m) * m1 + col];
-      double pend = 0.0;
-#pragma unroll
-      for (int u = 0; u < kRBCols; ++u) pend = (col >> 8) == u ? acc[u] : pend;
-      double dj = 1.0;
-#pragma unroll
-      for (int i = 0; i < kRB; ++i) dj = ci == i ? Lc[i] : dj;
-      dj = 1.0 / dj;
-      double yk = 0.0;
-#pragma unroll
-      for (int i = kRB - 1; i >= 0; --i) {
-        const double cand = (zq - pend) * dj;
-        double yi = readlane_f64(cand, l0 + i);
-        yi = c0 + i < m ? yi : 0.0;
-        yk = ci == i ? yi : yk;
-        pend += (ci >= 0 && ci < i) ? Lc[i] * yi : 0.0;
-      }
-      if (ci >= 0 && ci < kRB) {
-        ybuf[ci] = yk;
-        if (c0 + ci < m) a.y[n + c0 + ci] = yk;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kRBCols; ++u) {
-      const int col = tid + 256 * u;
-      if (col < c0) {
-        double t[kRB];
-#pragma unroll
-        for (int i = 0; i < kRB; ++i) t[i] = L[size_t(min(c0 + i, m - 1)) * m1 + col];
-        double sacc = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRB; ++i) sacc += t[i] * ybuf[i];
-        acc[u] += sacc;
-      }
-    }
-  }
-}
+constexpr int kBlockedMaxM = 1024;
 
 // z = L⁻¹g_s - Y·y_c : one wave per band row, all CUs.  (y[0..n) used as z storage)
 __global__ __launch_bounds__(256) void border_matvec_kernel(SolveArgs a) {
@@ -1979,12 +1624,7 @@ hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t b
                             hipFuncAttributeMaxDynamicSharedMemorySize, int(reduced_lds));
     if (e != hipSuccess) return e;
   }
-  const int big = 150 * 1024;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_solve_panel_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_solve_panel_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, big);
-  for (const void* f : {reinterpret_cast<const void*>(&reduced_solve_reg_kernel<4, true>), reinterpret_cast<const void*>(&reduced_solve_reg_kernel<7, true>),
-                        reinterpret_cast<const void*>(&reduced_solve_reg_kernel<10, true>), reinterpret_cast<const void*>(&reduced_solve_reg_kernel<13, true>)})
-    (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_solve_panel_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
   for (const void* f : {reinterpret_cast<const void*>(&band_backsolve_kernel<2>), reinterpret_cast<const void*>(&band_backsolve_kernel<3>),
                         reinterpret_cast<const void*>(&band_backsolve_kernel<4>), reinterpret_cast<const void*>(&band_backsolve_kernel<5>),
                         reinterpret_cast<const void*>(&band_backsolve_kernel<6>), reinterpret_cast<const void*>(&band_backsolve_kernel<7>),
@@ -1994,25 +1634,16 @@ hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t b
   }
   return hipSuccess;
 }
-static int reduced_blocked_from() {
-  static const int v = [] { const char* e = std::getenv("CALICO_REDUCED_BLOCKED_FROM"); return e ? std::atoi(e) : 129; }();
-  return v;
-}
-static bool reduced_is_blocked(const SolveArgs& a) {
-  const int m1 = a.m + 1;
-  return m1 >= reduced_blocked_from() && m1 > 128 && a.m <= 256 * kRBCols;
-}
+static bool reduced_is_blocked(const SolveArgs& a) { return a.m + 1 > 128 && a.m <= kBlockedMaxM; }
 // K-slices of the Schur complement the reduced solve adds up on load
 int reduced_schur_slices(const SolveArgs& a) {
   if (!(a.m + 1 <= 128 || reduced_is_blocked(a))) return 1;
   // Long trajectories: the Schur complement's tiles walk all eliminated rows (6 n_cp · 32/30), a few tiles x K-slices
   // workgroups in all -- at 1453 control points two slices meant 4.7k rows per workgroup, 12 us beside the last level.
-  // More slices there; the in-LDS 32-column-block solver adds up to eight on load (the 16-column panel solver two).
-  const char* e = std::getenv("CALICO_DENSE");
-  const bool panel = e && std::string(e) == "panel";
+  // More slices there; the in-LDS 32-column-block solver adds up to eight on load.
   // (CALICO_SCHUR_SLICES=1 / 2: A/B switch, read per solve)
   if (const char* se = std::getenv("CALICO_SCHUR_SLICES")) return std::max(1, std::min(kSchurSlices, std::atoi(se)));
-  if (a.m + 1 <= 128 && !panel) {
+  if (a.m + 1 <= 128) {
     if (a.n_cp >= 1280) return 8;
     if (a.n_cp >= 640) return 4;
     // Short trajectories: ONE slice. The tiles' workgroups ride beside the last level's chains and have time to spare
@@ -2029,59 +1660,23 @@ int reduced_schur_slices(const SolveArgs& a) {
 // Dense solve of the (m+1)x(m+1) augmented reduced system in a.Spart (ks K-slices) -> a.y[n_s ...]
 void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0 = 0, int outer_back = 0);     // bcr_kernels.hip
 void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hipStream_t s);     // bcr_kernels.hip
-bool launch_reduced_fused(const SolveArgs& a, int nsteps, int nsl, int* words, hipStream_t s);     // bcr_kernels.hip
-void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s, int* fan_words) {
+void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s) {
   const int m1 = a.m + 1;
-  const bool blocked = reduced_is_blocked(a);
-  // CALICO_DENSE=panel keeps the 16-column panel kernel for the in-LDS case (A/B switch)
-  const bool use_block = [] { const char* e = std::getenv("CALICO_DENSE"); return !(e && std::string(e) == "panel"); }();      // (read per solve: A/B switches)
-  if (m1 <= 128 && a.m >= 1 && use_block && ks <= 8) { launch_dense_block_solve(a, ks, s); return; }
-  if (m1 <= 128) {
+  if (m1 <= 128 && a.m >= 1) {
+    launch_dense_block_solve(a, ks, s);      // (ks <= 8, what the solver adds up on load: see reduced_schur_slices)
+  } else if (m1 <= 128) {
+    // a.m == 0 (nothing to calibrate): only the right-hand side's row, which the panel kernel takes
     const size_t lds = (size_t(m1) * ((16 * ((m1 + 15) / 16)) | 1) + m1 + 32 + 128 + 256) * sizeof(double);
-    if (m1 <= 64) hipLaunchKernelGGL(reduced_solve_panel_kernel<1>, dim3(1), dim3(256), lds, s, a, 0, ks);
-    else hipLaunchKernelGGL(reduced_solve_panel_kernel<2>, dim3(1), dim3(256), lds, s, a, 0, ks);
-  } else if (blocked) {
-    // panels are eliminated over all CUs until what is left fits the in-LDS solver, which finishes the factorisation
-    // and solves for its unknowns; the blocked backward sweep takes it from there
-    const int steps = (m1 - 128 + kRB - 1) / kRB, t0 = kRB * steps, mt1 = m1 - t0;
-    // CALICO_BLOCK_STEP=valu: round 2's step kernel (in-wave column Cholesky on 64 rows, VALU tile update) and backward
-    // sweep in a launch of its own -- A/B switch
-    const bool step_mfma = [] { const char* e = std::getenv("CALICO_BLOCK_STEP"); return !(e && std::string(e) == "valu"); }();
-    const bool fused_back = step_mfma && use_block && mt1 >= 2 && a.m <= 1024;     // (the dense solver goes on with the panels' backward sweep)
-    // CALICO_REDUCED_FUSED=1: all of it in ONE launch (reduced_fused_kernel: the steps behind fan-ins of one another, the
-    // in-LDS solver last). Off by default: a step has nothing to do before the step in front of it is through, so a fan-in
-    // only replaces the boundary -- by L1-bypassing loads and write-through stores of everything that crosses it: configs[4]
-    // 3545 -> 3520 it/s (read per solve).
-    const bool one_launch = fused_back && fan_words && [] { const char* e = std::getenv("CALICO_REDUCED_FUSED"); return e && std::atoi(e) != 0; }();
-    if (one_launch && launch_reduced_fused(a, steps, ks, fan_words, s)) return;
+    hipLaunchKernelGGL(reduced_solve_panel_kernel<1>, dim3(1), dim3(256), lds, s, a, 0, ks);
+  } else if (reduced_is_blocked(a)) {
+    // panels are eliminated over all CUs until what is left (97..128 unknowns) fits the in-LDS solver, which finishes the
+    // factorisation, solves for its unknowns and runs the backward sweep over the panels
+    const int steps = (m1 - 128 + kRB - 1) / kRB, t0 = kRB * steps;
     for (int j = 0; j < steps; ++j) {
       const int rows = m1 - kRB * (j + 1), T = rows > 0 ? (rows + 63) / 64 : 0;
-      if (step_mfma) launch_reduced_block_step(a, j, j == 0 ? ks : 1, T > 0 ? T * (T + 1) / 2 : 1, s);
-      else hipLaunchKernelGGL(reduced_block_step_kernel, dim3(T > 0 ? T * (T + 1) / 2 : 1), dim3(256), 0, s, a, j, j == 0 ? ks : 1);
+      launch_reduced_block_step(a, j, j == 0 ? ks : 1, T > 0 ? T * (T + 1) / 2 : 1, s);
     }
-    if (use_block && mt1 >= 2) launch_dense_block_solve(a, 1, s, t0, fused_back ? 1 : 0);     // (the 32-column-block solver of the small systems)
-    else {
-      const size_t lds = (size_t(mt1) * ((16 * ((mt1 + 15) / 16)) | 1) + mt1 + 32 + 128 + 256) * sizeof(double);
-      if (mt1 <= 64) hipLaunchKernelGGL(reduced_solve_panel_kernel<1>, dim3(1), dim3(256), lds, s, a, t0, 1);
-      else hipLaunchKernelGGL(reduced_solve_panel_kernel<2>, dim3(1), dim3(256), lds, s, a, t0, 1);
-    }
-    if (!fused_back) hipLaunchKernelGGL(reduced_block_back_kernel, dim3(1), dim3(256), 0, s, a, steps);
-  } else if (m1 <= 16 * 13) {
-    const int NT = m1 <= 64 ? 4 : (m1 <= 112 ? 7 : (m1 <= 160 ? 10 : 13));
-    const int NP = 16 * NT;
-    const size_t full = size_t(3 * NP + size_t(a.m + 1) * NP) * sizeof(double);
-    const bool l_in_lds = full <= 150 * 1024;
-    const size_t lds = l_in_lds ? full : size_t(3 * NP) * sizeof(double);
-#define LAUNCH_RS(N) \
-    if (l_in_lds) hipLaunchKernelGGL((reduced_solve_reg_kernel<N, true>), dim3(1), dim3(256), lds, s, a); \
-    else hipLaunchKernelGGL((reduced_solve_reg_kernel<N, false>), dim3(1), dim3(256), lds, s, a)
-    switch (NT) {
-      case 4: LAUNCH_RS(4); break;
-      case 7: LAUNCH_RS(7); break;
-      case 10: LAUNCH_RS(10); break;
-      default: LAUNCH_RS(13); break;
-    }
-#undef LAUNCH_RS
+    launch_dense_block_solve(a, 1, s, t0, 1);
   } else {
     hipLaunchKernelGGL(reduced_solve_kernel, dim3(1), dim3(256), reduced_in_lds ? reduced_solve_lds_bytes(a) : 0, s, a,
                        reduced_in_lds ? 1 : 0);
@@ -2106,7 +1701,7 @@ void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, do
                   int n_blocks, bool reduced_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi) {
   launch_band_reduction(a, o, x, blocks, n_blocks, s, with_post_eval, log, log_cap, jacobi);
   const int ks = reduced_schur_slices(a);
-  launch_reduced_solve(a, reduced_in_lds, ks, s, nullptr);
+  launch_reduced_solve(a, reduced_in_lds, ks, s);
   hipLaunchKernelGGL(border_matvec_kernel, dim3((a.n_s() + 3) / 4), dim3(256), 0, s, a);
   {
     const size_t bl = band_backsolve_lds_bytes(a);

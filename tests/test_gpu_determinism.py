@@ -194,43 +194,19 @@ def test_back_to_back_solves_behind_leftover_kernels():
 
 
 @pytest.mark.gpu
-def test_large_reduced_system_kernels_agree(monkeypatch):
+def test_large_reduced_system_kernels_agree():
     """Rigs of many sensors have a reduced system of more than 128 columns (eight cameras + two IMUs: 220): it is factored
     panel by panel over several workgroups (reduced_block_step_mfma_kernel: the tree nodes' parts on the matrix cores),
-    the remainder and the panels' backward sweep by the in-LDS 32-column-block solver. Round 2's kernels (64-row in-wave
-    column Cholesky, VALU tile update, backward sweep in a launch of its own) stay behind CALICO_BLOCK_STEP=valu, the
-    16-column panel solver for the remainder behind CALICO_DENSE=panel: the same algorithm in another order -- same
-    iterations, estimates equal to rounding; and the default path is reproducible bit for bit."""
+    the remainder and the panels' backward sweep by the in-LDS 32-column-block solver. Two runs must agree bit for bit
+    (a step that read a tile of the panel before it was written shows as a run-to-run difference). The estimates are
+    compared with the oracle at this size by test_gpu_full_size.py (configs[4])."""
     api = helpers.hip_api()
     scene = syn.make_scene(8, 1, True, 3, cam_rate=5.0, imu_rate=50.0, duration=4.0, chart="april", seed=31,
                            pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=True, segment_duration=4.0 / 23.9,
                            max_cam_obs=20000, n_imus=2)
-    runs = {}
-    for step, dense, fused in (("", "", ""), ("valu", "", ""), ("", "panel", ""), ("", "", "1")):
-        # (fused = "1": all steps and the in-LDS solver in ONE launch behind in-launch fan-ins, reduced_fused_kernel --
-        #  measured 0.7 % slower than a launch per step at configs[4], hence off by default)
-        if fused:
-            monkeypatch.setenv("CALICO_REDUCED_FUSED", fused)
-        else:
-            monkeypatch.delenv("CALICO_REDUCED_FUSED", raising=False)
-        if step:
-            monkeypatch.setenv("CALICO_BLOCK_STEP", step)
-        else:
-            monkeypatch.delenv("CALICO_BLOCK_STEP", raising=False)
-        if dense:
-            monkeypatch.setenv("CALICO_DENSE", dense)
-        else:
-            monkeypatch.delenv("CALICO_DENSE", raising=False)
-        runs[(step, dense, fused)] = _solve_repeatedly(api, scene, repeats=2, max_iter=20)
-    monkeypatch.delenv("CALICO_REDUCED_FUSED", raising=False)
-    ref = runs[("", "", "")]
+    ref = _solve_repeatedly(api, scene, repeats=2, max_iter=20)
     assert ref[0][0] > 3
-    assert ref[0][2] == ref[1][2] and np.array_equal(ref[0][3], ref[1][3]), "the default path is not reproducible"
-    for key, rr in runs.items():
-        for r in rr:
-            assert r[0] == ref[0][0] and r[1] == ref[0][1], key
-            np.testing.assert_allclose(r[2], ref[0][2], rtol=1e-9, err_msg=str(key))
-            np.testing.assert_allclose(r[3], ref[0][3], rtol=1e-7, atol=1e-9, err_msg=str(key))
+    assert ref[0][:3] == ref[1][:3] and np.array_equal(ref[0][3], ref[1][3]), "the default path is not reproducible"
 
 
 @pytest.mark.gpu
@@ -338,41 +314,6 @@ def test_cell_workgroups_equal_the_expansion_launch(monkeypatch):
 
 
 @pytest.mark.gpu
-def test_chain_look_ahead_is_bit_identical(monkeypatch):
-    """Round 5: the tree levels' chain steps with look-ahead (bcr_level_kernel<.., LA>, CALICO_LOOKAHEAD=1: the chief starts on
-    the next block of a chain behind the diagonal's Schur update alone, the followers form the update of their own input
-    tiles in registers, Z is double-buffered, the loader waves carry the left separator's sums) reorder WHO computes a
-    product and WHEN, never the products or the order of a sum: every iteration, cost and estimate must equal the default
-    path's bit for bit -- chains of 4 (configs[3]'s shape), of 8 (long trajectory, several levels) and of 2 / 3 (leaf
-    override), border roles and role 0 alike; three repeats each (a hazard between a step's LDS buffers would show as a
-    run-to-run difference)."""
-    api = helpers.hip_api()
-    common = dict(chart="april", pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=True, max_cam_obs=6000)
-    scenes = [
-        (syn.make_scene(4, 1, True, 3, cam_rate=10.0, imu_rate=100.0, duration=8.7, seed=41, segment_duration=8.7 / 23.9, **common), None),
-        (syn.make_scene(2, 1, True, 2, seed=4), None),        # 185 control points: several tree levels
-        (syn.make_scene(2, 3, True, 2, cam_rate=10.0, imu_rate=100.0, duration=6.0, seed=42, segment_duration=6.0 / 23.9, **common), "2"),
-        (syn.make_scene(2, 3, True, 2, cam_rate=10.0, imu_rate=100.0, duration=6.0, seed=42, segment_duration=6.0 / 23.9, **common), "3"),
-    ]
-    for sc, leaf in scenes:
-        if leaf:
-            monkeypatch.setenv("CALICO_BCR_LEAF", leaf)
-        runs = {}
-        for la in ("0", "1"):
-            monkeypatch.setenv("CALICO_LOOKAHEAD", la)
-            runs[la] = _solve_repeatedly(api, sc, repeats=3, max_iter=20)
-        monkeypatch.delenv("CALICO_LOOKAHEAD")
-        if leaf:
-            monkeypatch.delenv("CALICO_BCR_LEAF")
-        ref = runs["0"][0]
-        assert ref[0] > 3
-        for la in ("0", "1"):
-            for r in runs[la]:
-                assert r[0] == ref[0] and r[1] == ref[1] and r[2] == ref[2], (la, leaf)
-                assert np.array_equal(r[3], ref[3]), (la, leaf)
-
-
-@pytest.mark.gpu
 def test_rolling_chief_equals_the_barrier_form_bit_for_bit(monkeypatch):
     """Round 6: level 0 of the tree solver eliminates its chains with a ROLLING CHIEF (bcr_level_kernel<.., ROLL>): waves 0 and 1
     take turns as the chief, the follower forms the next block's diagonal D_{k+1} - Z^BᵀZ^B step by step in the chief's own
@@ -380,15 +321,17 @@ def test_rolling_chief_equals_the_barrier_form_bit_for_bit(monkeypatch):
     staged as tile images a block ahead, and nothing waits at a workgroup barrier -- order is kept by single-writer counters
     and write-once channels in LDS. The products and their order are those of the barrier form (CALICO_ROLL=0), so every
     iterate must come out BIT FOR BIT the same -- for chains of 1, 2, 3, 4 and 8 blocks (odd / even hand-overs, the channel
-    ring of three wrapping, the image ring of two wrapping), a trajectory whose last superblock is partly padding, spline orders
-    4 and 5 (other band structure in the offset table), a trajectory with unobserved control points, with and without the same form on the upper levels
-    (CALICO_ROLL_UPPER=1) -- and repeat itself run to run (a follower that read a tile image, a channel entry or a Z row too
-    early, or a buffer reused too soon, shows as a run-to-run difference or a difference to the barrier form)."""
+    ring of three wrapping, the image ring of two wrapping), a stereo rig with three IMUs (border roles) on chains of 2 and 3,
+    a trajectory whose last superblock is partly padding, spline orders 4 and 5 (other band structure in the offset table),
+    a trajectory with unobserved control points -- and repeat itself run to run, three repeats (a follower that read a tile
+    image, a channel entry or a Z row too early, or a buffer reused too soon, shows as a run-to-run difference or a
+    difference to the barrier form)."""
     api = helpers.hip_api()
     common = dict(chart="april", pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=True, max_cam_obs=6000)
     scenes = [
         ("92 control points", syn.make_scene(4, 1, True, 3, cam_rate=10.0, imu_rate=100.0, duration=8.7, seed=41, segment_duration=8.7 / 23.9, **common), ("", "1", "2", "3", "8")),
         ("185 control points", syn.make_scene(2, 1, True, 2, seed=4), ("", "3")),
+        ("stereo, three IMUs", syn.make_scene(2, 3, True, 2, cam_rate=10.0, imu_rate=100.0, duration=6.0, seed=42, segment_duration=6.0 / 23.9, **common), ("2", "3")),
         ("ragged end", syn.make_scene(2, 1, True, 3, cam_rate=10.0, imu_rate=100.0, duration=7.3, seed=43, segment_duration=7.3 / 23.9, **common), ("", "2")),
     ]
     # data over the first 5 s of a trajectory of 8.7 s: the control points behind it are unobserved -- padding rows in the tiles (a
@@ -406,13 +349,11 @@ def test_rolling_chief_equals_the_barrier_form_bit_for_bit(monkeypatch):
             else:
                 monkeypatch.delenv("CALICO_BCR_LEAF", raising=False)
             runs = {}
-            for roll, upper in (("0", "0"), ("1", "0"), ("1", "1")):
+            for roll in ("0", "1"):
                 monkeypatch.setenv("CALICO_ROLL", roll)
-                monkeypatch.setenv("CALICO_ROLL_UPPER", upper)
-                runs[(roll, upper)] = _solve_repeatedly(api, sc, repeats=3 if roll == "1" else 1, max_iter=12)
+                runs[roll] = _solve_repeatedly(api, sc, repeats=3 if roll == "1" else 1, max_iter=12)
             monkeypatch.delenv("CALICO_ROLL")
-            monkeypatch.delenv("CALICO_ROLL_UPPER")
-            ref = runs[("0", "0")][0]
+            ref = runs["0"][0]
             assert ref[0] >= 3, (name, leaf)
             for key, reps in runs.items():
                 for r in reps:

@@ -42,3 +42,64 @@ def test_evaluation_kernel_scratch_budget():
     for k, v in res.items():
         if "eval_frames_kernel" in k or "eval_jacobian_kernel" in k:
             assert v["ScratchSize"] == 0, (k, v)
+
+
+def _llvm_tool(name):
+    for d in (os.path.join(os.path.dirname(os.path.realpath(entry.HIPCC)), "..", "llvm", "bin"), "/opt/rocm/llvm/bin"):
+        p = os.path.join(d, name)
+        if os.path.exists(p):
+            return p
+    return shutil.which(name)
+
+
+@pytest.mark.skipif(shutil.which(entry.HIPCC) is None and not os.path.exists(entry.HIPCC), reason="no hipcc")
+@pytest.mark.skipif(not all(_llvm_tool(t) for t in ("clang-offload-bundler", "llvm-readelf", "llvm-objdump", "llvm-objcopy")),
+                    reason="no LLVM binary tools")
+def test_level_kernels_code_prefetch_stays_in_the_code_object(tmp_path):
+    """The barrier form of bcr_level_kernel asks for its own code as data at its first instructions (prefetch_code): it reads
+    kLevelCodePrefetchBytes from s_getpc on. Those reads must stay inside the code object's executable segment, which
+    depends on where the kernels land in .text: every instantiation without the rolling form is checked."""
+    src = os.path.join(entry.CSRC, "bcr_kernels.hip")
+    text = open(src).read()
+    m = re.search(r"constexpr int kLevelCodePrefetchBytes = ([0-9 *]+);", text)
+    assert m, "kLevelCodePrefetchBytes not found"
+    nbytes = 1
+    for f in m.group(1).split("*"):
+        nbytes *= int(f)
+    assert "prefetch_code(threadIdx.x, kLevelThreads, kLevelCodePrefetchBytes)" in text
+    # the build's object when it is up to date, a fresh compile with the build's flags otherwise
+    obj = os.path.join(entry.CSRC, "build", "bcr_kernels.hip.o")
+    deps = [src] + [os.path.join(entry.CSRC, f) for f in os.listdir(entry.CSRC) if f.endswith((".hpp", ".h"))]
+    if not entry._newer(obj, deps):
+        obj = str(tmp_path / "bcr_kernels.o")
+        subprocess.run([entry.HIPCC] + entry.HIP_FLAGS + entry.HIP_FILE_FLAGS.get("bcr_kernels.hip", []) + ["-c", src, "-o", obj],
+                       check=True, capture_output=True, timeout=900)
+    fat, co = str(tmp_path / "fatbin"), str(tmp_path / "bcr.co")
+    subprocess.run([_llvm_tool("llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, obj, str(tmp_path / "host.o")],
+                   check=True, capture_output=True)
+    subprocess.run([_llvm_tool("clang-offload-bundler"), "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    "--output=" + co, "--unbundle"], check=True, capture_output=True)
+    elf = subprocess.run([_llvm_tool("llvm-readelf"), "--wide", "--segments", "--symbols", co], check=True, capture_output=True,
+                         text=True).stdout
+    seg_end = None
+    for line in elf.splitlines():
+        f = line.split()
+        if f[:1] == ["LOAD"] and "E" in f[6:-1]:
+            seg_end = int(f[2], 16) + int(f[5], 16)      # VirtAddr + MemSiz
+    assert seg_end is not None, elf[:2000]
+    kernels = {}
+    for line in elf.splitlines():
+        f = line.split()
+        if len(f) == 8 and f[3] == "FUNC":
+            k = re.search(r"bcr_level_kernelILb([01])ELb([01])ELb([01])E", f[7])
+            if k:
+                kernels[k.groups()] = (int(f[1], 16), int(f[2]))
+    barrier = {args: v for args, v in kernels.items() if args[2] == "0"}
+    assert len(barrier) == 4 and len(kernels) == 5, sorted(kernels)
+    for args, (addr, size) in barrier.items():
+        dis = subprocess.run([_llvm_tool("llvm-objdump"), "-d", "--start-address=%#x" % addr, "--stop-address=%#x" % (addr + 1024), co],
+                             check=True, capture_output=True, text=True).stdout
+        g = re.search(r"s_getpc_b64 .*// ([0-9A-Fa-f]+):", dis)
+        assert g, ("no s_getpc_b64 at the head of", args)
+        pc = int(g.group(1), 16) + 4         # (s_getpc_b64 returns the address of the next instruction)
+        assert pc + nbytes <= seg_end, (args, hex(addr), hex(pc), hex(seg_end))
