@@ -23,9 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
-#include <string>
 #include <type_traits>
 
 #include "problem_dev.hpp"
@@ -3166,18 +3164,11 @@ void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hip
   hipLaunchKernelGGL(reduced_block_step_mfma_kernel, dim3(n_wg), dim3(kStepThreads), reduced_block_step_lds_bytes(), s, a, j, nsl);
 }
 size_t bcr_back_lds_bytes(int q_max, int m1p);
-// Does the Schur complement ride in the last level's launch? Trees of at least two levels whose last level has one or two
-// single-superblock nodes (it always has, by construction of the plan); CALICO_FUSE_SCHUR=0: a launch of its own (A/B).
-bool schur_rides_in_last_level(int n_levels, int n_last_nodes, int root) {
-  const char* e = std::getenv("CALICO_FUSE_SCHUR");
-  return (!e || std::atoi(e) != 0) && n_levels >= 2 && n_last_nodes >= 1 && n_last_nodes <= 2 && root >= 0;
-}
 // Can the first back-substitution launch ride in the dense solve's launch? Only the shapes the in-LDS solve takes, no
 // border-row sweep workgroups (those would sit on every CU with the dense solve's LDS footprint), chains of at most four.
+// CALICO_FUSE_BACK=0: two launches (read per solve; the tests' reference for the hand-off).
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows) {
-  const char* fe = std::getenv("CALICO_FUSE_BACK");       // (read per solve: an A/B switch, and what the tests toggle)
-  const bool on = !fe || std::atoi(fe) != 0;
-  return on && a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
+  return env_flag("CALICO_FUSE_BACK", true) && a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
 }
 // PRE: the nodes form their solution as an affine map of the reduced solve's output while they wait (back_node_pre);
 // needs mc + 33 <= 128 columns (one 16-column tile per wave) and a reduced solve long enough to hide the recursion behind:
@@ -3185,10 +3176,8 @@ bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows)
 // 32-column block -- four blocks (m + 1 > 96: configs[3]) cover it, two (configs[1]: 9450 with, 10200 it/s without) do
 // not. CALICO_BACK_PRE=0 / 1: never / whenever the columns fit (A/B switch).
 static bool dense_back_pre(const SolveArgs& a) {
-  const char* e = std::getenv("CALICO_BACK_PRE");
   if (a.mc + BP + 1 > 128) return false;
-  if (e) return std::atoi(e) != 0;
-  return a.m + 1 > 96;
+  return env_flag("CALICO_BACK_PRE", a.m + 1 > 96);
 }
 static size_t dense_back_lds(int q_max, int m1p) {
   const int qm = q_max <= 1 ? 1 : (q_max <= 2 ? 2 : 4);
@@ -3225,17 +3214,16 @@ void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, 
 
 // ---- launch helpers ---------------------------------------------------------
 // CALICO_ELIM=panel: the block factorisation of rounds 1-3 (two in-wave panels + tile update + Z phase); read per solve (A/B switch)
-bool block_elim_enabled() { const char* e = std::getenv("CALICO_ELIM"); return !(e && std::string(e) == "panel"); }
+bool block_elim_enabled() { return !env_is("CALICO_ELIM", "panel"); }
 // The dense reduced solve with rolling owners (dense_block_solve_body, elim == 2), the default; CALICO_DENSE_ROLL=0: the barrier
 // form (A/B switch, read per solve)
 static int dense_elim_mode() {
   if (!block_elim_enabled()) return 0;
-  const char* e = std::getenv("CALICO_DENSE_ROLL");
-  return (!e || std::atoi(e) != 0) ? 2 : 1;
+  return env_flag("CALICO_DENSE_ROLL", true) ? 2 : 1;
 }
 // Level 0's chains with the rolling chief (bcr_level_kernel<true, true, true>: no workgroup barrier between the blocks of
 // a chain), the default; CALICO_ROLL=0: the barrier form (A/B switch, read per solve)
-static bool level_roll_enabled() { const char* e = std::getenv("CALICO_ROLL"); return !e || std::atoi(e) != 0; }
+static bool level_roll_enabled() { return env_flag("CALICO_ROLL", true); }
 // (4 · BP · XLD: the barrier form uses three -- X twice, Z --; the rolling form's layout needs the fourth, see its static_assert)
 size_t bcr_level_lds_bytes() { return size_t(2 * 64 * DLD + 4 * BP * XLD + 80 + 128 + kLevelThreads + kElimBufDoubles) * sizeof(double); }
 size_t bcr_back_lds_bytes(int q_max, int m1p) {

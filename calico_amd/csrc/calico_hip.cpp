@@ -73,7 +73,7 @@ void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, do
 void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s);
 void launch_control(LmState* st, const LmOptionsDev& o, double* R2, double* x, const double* x_cand, int n_amb,
                     IterLog* log, int log_cap, const double* item_cost, int n_items, const double* Rbase, size_t r_stride,
-                    hipStream_t s, bool commit_by_copy = false, int* progress = nullptr, int seq = 0);
+                    hipStream_t s, bool commit_by_copy = false);
 void launch_init_state(LmState* st, double radius, double x_norm, hipStream_t s, const double* upd_ext = nullptr, int upd_ext_n = 0);
 void launch_begin_solve(LmState* st, double radius, double x_norm, const double* upd_ext, int upd_ext_n, const ResultSink& sink, double* x,
                         double* x_cand, const double* h_x, int n_amb, hipStream_t s);
@@ -92,7 +92,6 @@ size_t dense_block_solve_lds_bytes();
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
                       hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl);
-bool schur_rides_in_last_level(int n_levels, int n_last_nodes, int root);
 void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
 void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
@@ -306,7 +305,7 @@ class DeviceArena {
  private:
   static constexpr size_t kAlign = 4096, kSlab = size_t(64) << 20;
   struct Slab { char* base = nullptr; size_t size = 0; int device = 0; std::map<size_t, size_t> free; };
-  DeviceArena() { const char* e = std::getenv("CALICO_ARENA"); enabled_ = !e || std::atoi(e) != 0; }
+  DeviceArena() { enabled_ = env_flag("CALICO_ARENA", true); }
   static int& batch_device() { static thread_local int d = -1; return d; }
   static void sync_device(int device) {
     int cur = device;
@@ -407,7 +406,6 @@ struct PlanHost {
   std::vector<BcrLevel> bcr_levels;
   std::vector<BcrNodeDev> h_bcr_nodes;
   std::vector<int> h_bcr_keep, h_cp_block;
-  bool bcr_merge_top = true;      // the top level's back-substitution rides in the launch below it
   int border_extra() const { return use_bcr ? bcr_br : 6 * sep_n; }   // rows the band hands to the dense reduced solve
   int n_cp = 0, m = 0, n_amb = 0, n_eff = 0, n_items = 0, n_items_all = 0, lds_cols = 0, row_pad = kRowPad;
   int64_t n_obs = 0;
@@ -583,13 +581,24 @@ int camera_num_params(int model) {
 }
 int imu_num_params(int model) { return model == 1 ? 1 : (model == 2 ? 4 : (model == 3 ? 12 : -1)); }
 
+// The switches that shape a plan, read when one is constructed -- once per finalize: build_plan takes them from
+// here and the plan cache's key hashes them, so a plan built under other settings is never adopted.
+struct PlanSwitches {
+  bool band_solver = env_is("CALICO_SOLVER", "band");            // the sequential banded factorisation for every spline order
+  bool speculative = env_flag("CALICO_SPECULATIVE", true);
+  bool band_split = env_flag("CALICO_BAND_SPLIT", true);          // the banded factorisation's separator
+  bool fuse_expand = env_flag("CALICO_FUSE_EXPAND", true);        // cell workgroups
+  bool gather_struct = env_flag("CALICO_GATHER_STRUCT", true);    // the gather's lists built on the device
+  int bcr_leaf = env_int("CALICO_BCR_LEAF", 0, 1, kBcrMaxChain);  // level 0's chain length (0: chosen by the plan)
+};
+
 SolveArgs make_solve_args(calico_problem* p) {
   SolveArgs a;
   a.R = p->d_R.p; a.r_stride = p->speculative ? p->r_size : 0; a.Lb = p->d_Lb.p; a.Linv = p->d_Linv.p; a.Y = p->d_Y.p; a.S = p->d_S.p; a.Spart = p->d_Spart.p;
   a.Swork = p->d_Swork.p; a.y = p->d_y.p; a.zbuf = p->d_zbuf.p; a.dadd = p->d_dadd.p;
   a.scale = p->d_scale.p; a.cp_active = p->d_cp_active.p; a.st = p->d_state.p; a.n_cp = p->n_cp; a.k = p->order; a.mc = p->m; a.sep_s = p->sep_s; a.sep_n = p->sep_n; a.m = p->m + p->border_extra();
   static const int dbg = [] {
-    const int v = std::getenv("CALICO_KERNEL_TIMING") ? std::atoi(std::getenv("CALICO_KERNEL_TIMING")) : 0;
+    const int v = env_int("CALICO_KERNEL_TIMING", 0, 0);
 #ifndef CALICO_DEV_TIMING
     if (v) std::fprintf(stderr, "[calico] CALICO_KERNEL_TIMING is set, but this library was built without the kernels' development "
                                 "instrumentation (rebuild with CALICO_DEV_TIMING=1 in the environment of __graft_entry__.build())\n");
@@ -613,7 +622,7 @@ BcrArgs make_bcr_args(calico_problem* p) {
 // Elimination plan of the tree solver: level 0 eliminates chains of q consecutive superblocks between kept
 // separators, every further level every other survivor; the last survivor is the root (joins the dense solve).
 // q minimises (levels · launch + chain steps · factorisation) for the trajectory length at hand.
-void build_bcr_plan(calico_problem* p) {
+void build_bcr_plan(calico_problem* p, const PlanSwitches& sw) {
   const int N = (p->n_cp + kBcrCps - 1) / kBcrCps;
   p->bcr_N = N;
   auto levels_after = [](int n_sep) { int l = 0; while (n_sep > 1) { n_sep /= 2; ++l; } return l; };
@@ -631,7 +640,7 @@ void build_bcr_plan(calico_problem* p) {
       if (8 * ((nodes + 7) / 8) * per + 9 > 256) cost += 5.0;
       if (cost < best) { best = cost; q = c; }
     }
-    if (const char* e = std::getenv("CALICO_BCR_LEAF")) q = std::max(1, std::min(kBcrMaxChain, std::atoi(e)));
+    if (sw.bcr_leaf > 0) q = sw.bcr_leaf;
   }
   p->bcr_levels.clear(); p->h_bcr_nodes.clear(); p->h_bcr_keep.clear();
   std::vector<int> alive(static_cast<size_t>(N), 0), mask(static_cast<size_t>(N), 0);
@@ -676,12 +685,11 @@ void build_bcr_plan(calico_problem* p) {
   p->bcr_q_max = q_max_all;
   p->bcr_q0 = q;       // level 0's chain length: its node table is arithmetic on the node's number (BcrInlineNodes)
   p->bcr_slots = int(p->h_bcr_nodes.size()) + 1;
-  { const char* e = std::getenv("CALICO_BCR_MERGE_TOP"); p->bcr_merge_top = !e || std::atoi(e) != 0; }   // (A/B switch, see enqueue_linear_solve)
 }
 
 EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res) {
   EvalArgs a;
-  static const int dbg = std::getenv("CALICO_KERNEL_TIMING") ? std::atoi(std::getenv("CALICO_KERNEL_TIMING")) : 0;
+  static const int dbg = env_int("CALICO_KERNEL_TIMING", 0, 0);
   a.debug = dbg;
   a.x = x; a.sensors = p->d_sensors.p; a.layouts = p->d_layouts.p; a.items = p->d_items.p;
   a.knots = p->d_knots.p; a.basis = p->d_basis.p; a.ctrl_off = p->d_ctrl_off.p;
@@ -692,26 +700,31 @@ EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool
   a.cell_chunk = p->cell_chunk; a.cell_rec_max = p->cell_rec_max; a.project = 0; a.row_cell_chunk = p->row_cell_chunk; a.frame_lds_doubles = p->frame_lds_doubles; a.pad5 = 0; a.wave_log = p->d_wave_log.p; a.active = p->any_tagged ? p->d_active.p : nullptr; a.apply_loss = apply_loss;
   a.st = nullptr; a.need_flag = 0; a.cost_index_base = 0;
   a.fitems = p->d_fitems.p; a.n_fitems = p->n_fitems;
-  a.hint_progress = nullptr; a.hint_seq = 0; a.hint_first = 0; a.hint_ftol = a.hint_ptol = 0.0;
+  a.hint_progress = nullptr; a.hint_seq = 0; a.hint_ftol = a.hint_ptol = 0.0;
   a.pair_mode = 0; a.wave_lds_doubles = 0;
   return a;
 }
 
+constexpr int kImuChunkItems = 21;     // IMU blocks per work item (the Jacobian kernel gives an IMU block three lanes)
+
+// CALICO_SETUP_TIMING=1: wall time of the sections of finalize, plan building included (development aid)
+struct SetupTimer {
+  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  void section(const char* name) {
+    static const bool on = env_flag("CALICO_SETUP_TIMING", false);
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[calico] finalize %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - t).count());
+    t = now;
+  }
+};
+
 // Flatten the host tables into cells / work items / gather lists, plan the elimination, upload the STRUCTURE (everything
 // here depends on what the problem looks like, nothing on a value: the result is what the plan cache shares).
-int build_plan(calico_problem* p) {
+int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
   const int k = p->order;
   const int n_cp = int(p->ctrl.size());
   p->n_cp = n_cp;
-  // CALICO_SETUP_TIMING=1: wall time of the sections of this function (development aid)
-  static const bool setup_timing = std::getenv("CALICO_SETUP_TIMING") != nullptr;
-  auto t_sec = std::chrono::steady_clock::now();
-  auto section = [&](const char* name) {
-    if (!setup_timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[calico] finalize %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_sec).count());
-    t_sec = t;
-  };
   // ---- ambient offsets, used flags ----
   int off = 0;
   for (HBlock& b : p->blocks) { b.amb_off = off; off += b.size; b.used = false; b.tan = -1; b.eff = -1; }
@@ -764,9 +777,7 @@ int build_plan(calico_problem* p) {
   {
     bool all_active = true;
     for (int i = 0; i < n_cp; ++i) all_active = all_active && cp_active[size_t(i)] != 0;
-    const char* env = std::getenv("CALICO_BAND_SPLIT");
-    const bool allowed = !env || std::atoi(env) != 0;
-    if (allowed && all_active && n_cp >= 6 * k && m + 6 * (k - 1) + 1 <= 1024) {
+    if (sw.band_split && all_active && n_cp >= 6 * k && m + 6 * (k - 1) + 1 <= 1024) {
       p->sep_n = k - 1;
       p->sep_s = (n_cp - p->sep_n) / 2;
     }
@@ -775,18 +786,17 @@ int build_plan(calico_problem* p) {
   // over the split of the band, so the single-separator variant above is switched off. CALICO_SOLVER=band keeps the
   // sequential banded factorisation (A/B switch, and the path of higher spline orders).
   {
-    const char* env = std::getenv("CALICO_SOLVER");
-    p->use_bcr = k <= 6 && !(env && std::string(env) == "band");
+    p->use_bcr = k <= 6 && !sw.band_solver;
     if (p->use_bcr) {
       p->sep_s = 0; p->sep_n = 0;
       p->bcr_all_active = true;
       for (int i = 0; i < n_cp; ++i) p->bcr_all_active = p->bcr_all_active && cp_active[size_t(i)] != 0;
       p->bcr_m1p = 16 * ((m + 1 + 15) / 16);
-      build_bcr_plan(p);
+      build_bcr_plan(p, sw);
     }
   }
   const int NS = 6 * n_cp;
-  section("blocks / tangent order");
+  setup.section("blocks / tangent order");
   // ---- layouts ----
   std::vector<SensorDev> sd(p->sensors.size());
   std::vector<LayoutDev> layouts;
@@ -837,7 +847,7 @@ int build_plan(calico_problem* p) {
       layouts.push_back(L); layout_gmap.push_back(gmap);
     }
   }
-  section("layouts");
+  setup.section("layouts");
   // ---- sort observations by (layout, segment) and cut work items ----
   struct Key { int layout, seg, sensor; int64_t idx; double stamp; };
   std::vector<Key> keys;
@@ -883,7 +893,6 @@ int build_plan(calico_problem* p) {
   std::vector<double> st(n_obs);
   std::vector<int> point_off(n_obs, 0);
   p->h_items.clear(); p->h_items_all.clear();
-  const int imu_chunk_items = [] { const char* e = std::getenv("CALICO_IMU_CHUNK"); return e ? std::max(1, std::min(21, std::atoi(e))) : 21; }();   // (the Jacobian kernel gives an IMU block three lanes)
   int max_cols = 0;
   for (int64_t q = 0; q < n_obs;) {
     int64_t e = q;
@@ -892,7 +901,7 @@ int build_plan(calico_problem* p) {
     const int dim = p->sensors[L.sensor].dim();
     // cameras fill the 128 staged rows; an IMU block is a long single-lane computation and there are few of them, so
     // they are cut finer: more waves in flight, shorter JᵀJ stage, smaller LDS footprint next to the camera frames
-    const int chunk = dim == 2 ? kRowsPerItem / 2 : imu_chunk_items;
+    const int chunk = dim == 2 ? kRowsPerItem / 2 : kImuChunkItems;
     max_cols = std::max(max_cols, L.ncols + 1);
     for (int64_t b = q; b < e; b += chunk) {
       ItemDev it;
@@ -967,8 +976,8 @@ int build_plan(calico_problem* p) {
     // fuse_expand (CALICO_FUSE_EXPAND=0: off): no launch for the cell expansion -- a camera cell is expanded by the last of its
     // frames inside the Jacobian launch (eval_kernels.hip), and the other work items form their blocks themselves, each
     // registered as a cell of its own so that the gather's device-built lists see it. Needs every such (layout, segment) to
-    // be ONE work item (an IMU cell of at most imu_chunk_items blocks: the usual case).
-    bool fuse = !p->h_fitems.empty() && [] { const char* e = std::getenv("CALICO_FUSE_EXPAND"); return !e || std::atoi(e) != 0; }();
+    // be ONE work item (an IMU cell of at most kImuChunkItems blocks: the usual case).
+    bool fuse = !p->h_fitems.empty() && sw.fuse_expand;
     for (const CellDev& c : p->h_cells) if (c.frame_count > 2) fuse = false;       // (a workgroup is two waves: one frame each)
     {
       // ... and two waves' staging areas must fit the CU's LDS
@@ -981,7 +990,7 @@ int build_plan(calico_problem* p) {
           const int Ps = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_bq >= 0);
           need = std::max(need, frame_lds_doubles(Ps, P1, L.ncols + 1));
         } else {
-          need = std::max(need, size_t((L.ncols + 1 + 15) & ~15) * size_t((((3 * imu_chunk_items + 3) & ~3) + 1) | 1));      // (as lds_cols x row_pad below)
+          need = std::max(need, size_t((L.ncols + 1 + 15) & ~15) * size_t((((3 * kImuChunkItems + 3) & ~3) + 1) | 1));      // (as lds_cols x row_pad below)
         }
       }
       need = (need + 1) & ~size_t(1);
@@ -1025,7 +1034,6 @@ int build_plan(calico_problem* p) {
       p->h_fitems.swap(packed);
       for (CellDev& c : p->h_cells) c.frame_begin = -1;      // (the frames are no longer contiguous by cell: FrameItemDev.cell says whose they are)
     }
-    const bool row_cells_ok = !fuse && [] { const char* e = std::getenv("CALICO_ROW_CELLS"); return !e || std::atoi(e) != 0; }();
     for (ItemDev it : p->h_items) {
       if (layout_uses_frames[size_t(it.layout)]) continue;
       const LayoutDev& L = layouts[size_t(it.layout)];
@@ -1040,13 +1048,13 @@ int build_plan(calico_problem* p) {
         it.rows_off = -2;            // (< 0: the item forms its own block; -2: that block is listed as a cell's)
         it.partial_off = int64_t(poff);
         poff += size_t(tri_size(n1));
-      } else if (row_cells_ok && hs.kind != CALICO_SENSOR_CAMERA && n1 <= 112) {
+      } else if (hs.kind != CALICO_SENSOR_CAMERA && n1 <= 112) {
         it.partial_off = 0; it.rows_off = 0;   // row store offset assigned below, once the staging dimensions are known
         if (p->h_cells.empty() || p->h_cells.back().prim_off >= 0 || p->h_cells.back().layout != it.layout ||
             p->h_cells.back().seg != it.seg) {
           CellDev c;
           c.layout = it.layout; c.seg = it.seg; c.frame_begin = int(p->h_jac_items.size()); c.frame_count = 0;
-          c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = hs.dim() * imu_chunk_items; c.prim_off = -1; c.pad0 = 0;
+          c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = hs.dim() * kImuChunkItems; c.prim_off = -1; c.pad0 = 0;
           poff += size_t(tri_size(n1));
           p->h_cells.push_back(c);
         }
@@ -1177,7 +1185,7 @@ int build_plan(calico_problem* p) {
     for (const CellDev& c : p->h_cells) if (c.prim_off == -1) most = std::max(most, c.frame_count);
     p->row_cell_chunk = std::min(p->row_cell_chunk, most);
   }
-  section("sort + work items");
+  setup.section("sort + work items");
   // ---- gather lists ----
   SolveArgs sa; sa.n_cp = n_cp; sa.k = k; sa.mc = m; sa.sep_s = p->sep_s; sa.sep_n = p->sep_n; sa.m = m + p->border_extra(); sa.debug = 0; sa.progress = nullptr;
   const size_t r_size = sa.r_size();
@@ -1193,8 +1201,7 @@ int build_plan(calico_problem* p) {
   // calibration part of the right-hand side (2 % of the outputs, sources in every segment) are listed here.
   // CALICO_GATHER_STRUCT=0: everything listed by the host (A/B switch, and the path of problems with free model points or
   // other spline orders' generic items).
-  bool gs_ok = [] { const char* e = std::getenv("CALICO_GATHER_STRUCT"); return !e || std::atoi(e) != 0; }();
-  gs_ok = gs_ok && int(layouts.size()) * k <= 96 && int(layouts.size()) >= 1 && m >= 1 && n_cells > 0;
+  bool gs_ok = sw.gather_struct && int(layouts.size()) * k <= 96 && int(layouts.size()) >= 1 && m >= 1 && n_cells > 0;
   for (int itn = n_cells; gs_ok && itn < n_part; ++itn) {   // no block of its own, or one that is listed as a cell's (fuse_expand)
     const int64_t ro = p->h_jac_items[size_t(itn - n_cells)].rows_off;
     gs_ok = ro >= 0 || ro == -2;
@@ -1299,7 +1306,7 @@ int build_plan(calico_problem* p) {
   p->n_thin = int(out_thin.size()); p->n_fat = int(out_fat.size());
   p->n_thin8 = p->n_thin; p->n_thin4 = p->n_thin;
   p->gather_owner_block = 0;
-  section("gather lists");
+  setup.section("gather lists");
   // ---- upload of the structure ----
   hipStream_t s = p->stream;
   std::vector<int> ctrl_off(n_cp);
@@ -1347,12 +1354,11 @@ int build_plan(calico_problem* p) {
       for (int l = 0; l < gsd.n_lay; ++l) holders += gs_tab[size_t(gsd.n_lay) * gsd.nseg + size_t(l) * m + size_t(tc)] >= 0 ? 1 : 0;
       one_layout = holders <= 1;
     }
-    const bool tiny_env = [] { const char* e = std::getenv("CALICO_GATHER_TINY"); return !e || std::atoi(e) != 0; }();      // (per plan, like the key that hashes it)
     const int n_border0 = NS + n_cp * k * 36;          // first border output
-    p->n_thin4 = (one_layout && tiny_env) ? n_border0 : p->n_thin;
+    p->n_thin4 = one_layout ? n_border0 : p->n_thin;
     // band blocks at distance d from the diagonal have (k - d) segments per layout: four lanes where that is <= 24 sources
     const int d4 = gsd.d_split;
-    p->n_thin8 = (one_layout && tiny_env) ? std::min(n_border0, NS + d4 * n_cp * 36) : p->n_thin;     // (the classes are ranges: [8 | 4 | 1])
+    p->n_thin8 = one_layout ? std::min(n_border0, NS + d4 * n_cp * 36) : p->n_thin;     // (the classes are ranges: [8 | 4 | 1])
   } else {
     HIP_TRY(p, p->d_out_thin.upload(out_thin, s)); HIP_TRY(p, p->d_idx_thin.upload(idx_thin, s));
     HIP_TRY(p, p->d_ptr_thin.upload(ptr_thin, s));
@@ -1360,11 +1366,11 @@ int build_plan(calico_problem* p) {
   HIP_TRY(p, p->d_out_fat.upload(out_fat, s)); HIP_TRY(p, p->d_idx_fat.upload(idx_fat, s));
   HIP_TRY(p, p->d_ptr_fat.upload(ptr_fat, s));
   // the thin outputs' lists at a fixed stride per lane class: the gather then needs no pointer load in front of its index
-  // loads (CALICO_GATHER_FIXED=0: the CSR form; read per plan and part of its key)
+  // loads
   // Only for the device-built lists: their lengths are bounded by the structure (layouts x k <= thin_per_lane x 8 per output),
   // which is what the fixed stride relies on; host-built lists (plans the table cannot describe) keep the CSR form -- padding
   // each of their short lists to 48 / 96 slots would multiply the index memory, and nothing bounds their length.
-  p->gather_fixed = [] { const char* e = std::getenv("CALICO_GATHER_FIXED"); return !e || std::atoi(e) != 0; }() && p->n_thin > 0 && gs_ok;
+  p->gather_fixed = p->n_thin > 0 && gs_ok;
   if (p->gather_fixed) {
     HIP_TRY(p, p->d_idx_fixed.alloc(gather_fixed_entries(p->n_thin, p->n_thin8, p->n_thin4, p->thin_per_lane) + 8));
     launch_gather_pack_fixed(p->d_ptr_thin.p, p->d_idx_thin.p, p->n_thin, p->n_thin8, p->n_thin4, p->thin_per_lane, zero_slot, p->d_idx_fixed.p, s);
@@ -1372,10 +1378,7 @@ int build_plan(calico_problem* p) {
   HIP_TRY(p, p->d_cells.upload(p->h_cells, s)); HIP_TRY(p, p->d_prim_tab.upload(prim_tab, s));
   p->partials_alloc = comp_base + comp_off + row_store + 2;      // (+ the word that is always zero, see zero_slot)
   p->r_size = r_size;
-  {
-    const char* env = std::getenv("CALICO_SPECULATIVE");
-    p->speculative = !env || std::atoi(env) != 0;
-  }
+  p->speculative = sw.speculative;
   {
     sa = make_solve_args(p);
     if (band_cholesky_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "spline order too high for the banded factorisation window");
@@ -1393,7 +1396,7 @@ int build_plan(calico_problem* p) {
       return p->set_error(CALICO_UNIMPLEMENTED, "tree solver workspace exceeds the LDS");
   }
   HIP_TRY(p, hipStreamSynchronize(s));      // the uploads read locals of this function
-  section("structure uploads");
+  setup.section("structure uploads");
   return CALICO_OK;
 }
 
@@ -1434,7 +1437,7 @@ struct PlanCache {
 // (never destroyed, like the stream and pinned pools: its buffers would be freed after the HIP runtime is gone)
 PlanCache& plan_cache() { static PlanCache* c = new PlanCache; return *c; }
 bool plan_cache_enabled() {
-  static const bool on = [] { const char* e = std::getenv("CALICO_PLAN_CACHE"); return !e || std::atoi(e) != 0; }();
+  static const bool on = env_flag("CALICO_PLAN_CACHE", true);
   return on;
 }
 struct Hasher {
@@ -1466,7 +1469,7 @@ struct Hasher {
   template <class T> void vec(const std::vector<T>& v) { word(v.size()); bytes(v.data(), v.size() * sizeof(T)); }
   void dbl(double d) { uint64_t w; std::memcpy(&w, &d, 8); word(w); }
 };
-PlanKey structure_key(const calico_problem* p) {
+PlanKey structure_key(const calico_problem* p, const PlanSwitches& sw) {
   Hasher h;
   h.word(uint64_t(p->order)); h.vec(p->knots); h.vec(p->basis); h.vec(p->ctrl);
   h.word(uint64_t(p->rank)); h.word(uint64_t(p->world));
@@ -1484,13 +1487,8 @@ PlanKey structure_key(const calico_problem* p) {
     h.vec(s.stamps); h.vec(s.body); h.vec(s.point);
     n_obs += s.stamps.size();
   }
-  // the switches finalize reads from the environment
-  for (const char* name : {"CALICO_SOLVER", "CALICO_SPECULATIVE", "CALICO_BAND_SPLIT", "CALICO_BCR_LEAF", "CALICO_BCR_MERGE_TOP", "CALICO_IMU_CHUNK",
-                           "CALICO_ROW_CELLS", "CALICO_FUSE_EXPAND", "CALICO_GATHER_STRUCT", "CALICO_GATHER_TINY", "CALICO_GATHER_FIXED"}) {
-    const char* e = std::getenv(name);
-    h.word(e ? 1 : 0);
-    if (e) h.bytes(e, std::strlen(e));
-  }
+  h.word(uint64_t(sw.band_solver) | (uint64_t(sw.speculative) << 1) | (uint64_t(sw.band_split) << 2) | (uint64_t(sw.fuse_expand) << 3) |
+         (uint64_t(sw.gather_struct) << 4) | (uint64_t(sw.bcr_leaf) << 8));
   PlanKey k; k.h1 = h.a; k.h2 = h.b; k.n_blocks = p->blocks.size(); k.n_obs = n_obs; k.device = p->device;
   return k;
 }
@@ -1529,7 +1527,7 @@ int prepare_workspace(calico_problem* p) {
   HIP_TRY(p, p->d_m0.alloc(size_t(n_obs))); HIP_TRY(p, p->d_m1.alloc(size_t(n_obs))); HIP_TRY(p, p->d_m2.alloc(size_t(n_obs)));
   HIP_TRY(p, p->d_partials.alloc(p->partials_alloc));
   HIP_TRY(p, hipMemsetAsync(p->d_partials.p + (p->partials_alloc - 2), 0, 2 * sizeof(double), s));      // the word the lists point to for "nothing"
-  if (std::getenv("CALICO_KERNEL_TIMING") && std::atoi(std::getenv("CALICO_KERNEL_TIMING")) >= 3) HIP_TRY(p, p->d_wave_log.alloc(2 * size_t(p->n_jac_items + p->n_fitems) + 8));
+  if (env_int("CALICO_KERNEL_TIMING", 0, 0) >= 3) HIP_TRY(p, p->d_wave_log.alloc(2 * size_t(p->n_jac_items + p->n_fitems) + 8));
   HIP_TRY(p, p->d_R.alloc(2 * r_size)); HIP_TRY(p, hipMemsetAsync(p->d_R.p, 0, 2 * r_size * sizeof(double), s));
   HIP_TRY(p, p->d_R2.alloc(2));
   const int NT = 6 * n_cp + m;
@@ -1680,26 +1678,20 @@ int finalize(calico_problem* p) {
   if (p->order <= 0) return p->set_error(CALICO_FAILED_PRECONDITION, "spline not set");
   if (p->order > 8) return p->set_error(CALICO_UNIMPLEMENTED, "spline order > 8 is not supported by the HIP kernels");
   HIP_TRY(p, hipSetDevice(p->device));
-  static const bool setup_timing = std::getenv("CALICO_SETUP_TIMING") != nullptr;
-  auto t_sec = std::chrono::steady_clock::now();
-  auto section = [&](const char* name) {
-    if (!setup_timing) return;
-    const auto t = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[calico] finalize %-28s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(t - t_sec).count());
-    t_sec = t;
-  };
+  const PlanSwitches sw{};
+  SetupTimer setup;
   // a workspace that belongs to the plan the handle is leaving goes back to that plan's pool
   const bool use_cache = plan_cache_enabled();
   PlanKey key;
   std::shared_ptr<PlanEntry> hit;
   if (use_cache) {
-    key = structure_key(p);
+    key = structure_key(p, sw);
     PlanCache& c = plan_cache();
     std::lock_guard<std::mutex> lock(c.mu);
     for (const std::shared_ptr<PlanEntry>& e : c.entries) if (e->key == key) { hit = e; break; }
     if (hit) { hit->last_use = ++c.tick; ++c.hits; } else ++c.misses;
   }
-  section("structure key + look-up");
+  setup.section("structure key + look-up");
   if (hit && p->plan == hit && p->ws_ready) {
     // same structure as before on the same handle (values re-registered): nothing to rebuild
   } else {
@@ -1714,7 +1706,7 @@ int finalize(calico_problem* p) {
     p->ws_ready = false;
     if (hit) adopt_plan(p, hit);
     else {
-      const int rc = build_plan(p);
+      const int rc = build_plan(p, sw, setup);
       if (rc != CALICO_OK) return rc;
       if (use_cache) {
         auto e = std::make_shared<PlanEntry>();
@@ -1747,10 +1739,10 @@ int finalize(calico_problem* p) {
         }
       }
     }
-    section(hit ? "plan adopted" : "plan built");
+    setup.section(hit ? "plan adopted" : "plan cached");
     const int rc = prepare_workspace(p);
     if (rc != CALICO_OK) return rc;
-    section("workspace");
+    setup.section("workspace");
   }
   int rc = upload_values(p);
   if (rc != CALICO_OK) return rc;
@@ -1758,7 +1750,7 @@ int finalize(calico_problem* p) {
   if (rc != CALICO_OK) return rc;
   HIP_TRY(p, hipStreamSynchronize(p->stream));
   pinned_pool().release(p->h_mpin, p->h_mpin_n); p->h_mpin = nullptr; p->h_mpin_n = 0;     // (the uploads are through)
-  section("values + kernel attributes");
+  setup.section("values + kernel attributes");
   p->dirty = false;
   return CALICO_OK;
 }
@@ -1817,9 +1809,6 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
   ea.st = st; ea.need_flag = need_flag;
   if (end_hint && tail && st && end_hint_available(p)) {
     ea.hint_progress = tail->progress; ea.hint_seq = tail->seq;
-    // (the hint's workgroup first in the grid: it is dispatched with the launch, not behind the first workgroups that end
-    //  -- the host has the whole evaluation to enqueue the next iteration. CALICO_HINT_FIRST=0: last, A/B switch read per solve)
-    ea.hint_first = [] { const char* e = std::getenv("CALICO_HINT_FIRST"); return !e || std::atoi(e) != 0; }() ? 1 : 0;
     ea.hint_ftol = tail->o.function_tolerance; ea.hint_ptol = tail->o.parameter_tolerance;
   }
   ea.items = p->d_jac_items.p; ea.n_items = p->n_jac_items; ea.cost_index_base = p->n_fitems;
@@ -1877,13 +1866,15 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   const int L = int(p->bcr_levels.size());
   const int ks = reduced_schur_slices(sa);
   // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
-  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less.
-  bool schur_rides = schur_rides_in_last_level(L, p->bcr_levels[size_t(L - 1)].n_nodes, p->bcr_root);
-  for (int i = 0; schur_rides && i < p->bcr_levels[size_t(L - 1)].n_nodes; ++i)
-    schur_rides = p->h_bcr_nodes[size_t(p->bcr_levels[size_t(L - 1)].node0 + i)].q == 1;
+  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
+  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
+  // launch bcr_schur_kernel on its own.
+  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
+  bool schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
+  for (int i = 0; schur_rides && i < last.n_nodes; ++i) schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
   int* const fan_word = p->d_handoff.p + 4;
   // (A/B switch, read per solve: 0 = every level reads its node descriptors from the table)
-  const bool inline_nodes = [] { const char* e = std::getenv("CALICO_INLINE_NODES"); return !e || std::atoi(e) != 0; }();
+  const bool inline_nodes = env_flag("CALICO_INLINE_NODES", true);
   for (int l = 0; l < L; ++l) {
     const BcrLevel& lv = p->bcr_levels[size_t(l)];
     BcrInlineNodes inl = {};
@@ -1900,7 +1891,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
   // the ones it waits for anyway) instead of costing a launch of its own.
   BcrTopSeps ts = {};
-  if (p->bcr_merge_top && L >= 2) {
+  if (L >= 2) {
     const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
     bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
     for (int i = 0; ok && i < tl.n_nodes; ++i) {
@@ -1934,7 +1925,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
                     first ? ts : none, s);
   }
   // development aid (CALICO_CHECK_FINITE=1): where does the first non-finite value of a solve sit?
-  static const bool check = std::getenv("CALICO_CHECK_FINITE") != nullptr;
+  static const bool check = env_flag("CALICO_CHECK_FINITE", false);
   if (check) {
     (void)hipStreamSynchronize(s);
     const hipError_t le = hipGetLastError();
@@ -2063,7 +2054,7 @@ void calico_problem_destroy(calico_problem* p) {
   // Idle slabs beyond a few go back to the driver -- lazily: hipFree waits for the whole device (other handles' streams,
   // PyTorch's), and a create / solve / destroy loop over a problem of several slabs would hipMalloc them again every cycle.
   // CALICO_ARENA_KEEP_SLABS (default 4 = 256 MB per device) idle slabs stay; calico_plan_cache_clear() frees them all.
-  static const int keep_slabs = [] { const char* e = std::getenv("CALICO_ARENA_KEEP_SLABS"); return e ? std::max(0, std::atoi(e)) : 4; }();
+  static const int keep_slabs = env_int("CALICO_ARENA_KEEP_SLABS", 4, 0);
   DeviceArena::get().trim(keep_slabs);
 }
 
@@ -2289,7 +2280,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   if (!p || !opt || !sm) return CALICO_INVALID_ARGUMENT;
   const auto t_start = std::chrono::steady_clock::now();
   // CALICO_SOLVE_TIMING=1: host time of the sections of this call and since the previous call returned (development aid)
-  static const bool solve_timing = std::getenv("CALICO_SOLVE_TIMING") != nullptr;
+  static const bool solve_timing = env_flag("CALICO_SOLVE_TIMING", false);
   static std::chrono::steady_clock::time_point t_last_return = t_start;
   double t_mark[6] = {0, 0, 0, 0, 0, 0};
   auto mark = [&](int i) { if (solve_timing) t_mark[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(); };
@@ -2324,7 +2315,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   // stream and leaves at most `depth` iterations of early-exit kernels behind a terminated solve. The stage that
   // terminates the solve writes the results (state, log, parameters) into pinned host memory itself, so the call
   // returns as soon as the flag is up: the early-exit kernels drain while the caller prepares its next call.
-  const int stream_depth = [] { const char* e = std::getenv("CALICO_STREAM_DEPTH"); return e ? std::atoi(e) : 2; }();
+  const int stream_depth = env_int("CALICO_STREAM_DEPTH", 2, 0);
   // (the progress word carries the iteration count in 20 bits: budgets beyond that take the batched loop)
   const bool streaming = p->speculative && !p->has_exchange() && stream_depth > 0 && p->h_progress != nullptr &&
                          opt->max_num_iterations <= 0xfffff;
@@ -2357,22 +2348,19 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   rc = enqueue_jacobian_eval(p, nullptr, 0);
   if (rc != CALICO_OK) return rc;
   // The bookkeeping of the first evaluation (initial cost, gradient norms, Jacobi scaling, log row 0) rides in the first
-  // linear solve's level-0 launch where the streaming loop and the tree solver run (CALICO_FOLD_FIRST=0: its own launch)
-  const bool fold_first = streaming && p->use_bcr && !p->has_exchange() && opt->max_num_iterations > 0 &&
-                          [] { const char* e = std::getenv("CALICO_FOLD_FIRST"); return !e || std::atoi(e) != 0; }();
+  // linear solve's level-0 launch where the streaming loop and the tree solver run
+  const bool fold_first = streaming && p->use_bcr && !p->has_exchange() && opt->max_num_iterations > 0;
   if (!fold_first) {
     p->timer.begin(4, s);
     launch_post_eval(sa, p->d_x.p, p->d_blocks.p, int(p->h_blocks.size()), o, p->d_log.p, kLogCap, 1, opt->jacobi_scaling, s);
     p->timer.end(s);
   }
-  const bool fused_control = [] { const char* e = std::getenv("CALICO_FUSED_CONTROL"); return !e || std::atoi(e) != 0; }();
   // The iteration enqueued ahead of the device is wasted when the one in front of it ends the solve (six early-exit kernels,
   // 40 us at configs[3], in front of the caller's next solve). With the end hint the Jacobian launch of iteration i says, from
   // what the linear solve left, whether iteration i's control stage will end the solve; iteration i + 1 is enqueued on its
   // "go" (progress word 2) -- the evaluation chain is still running then, so the device does not wait -- or, without one,
   // once iteration i has ended without terminating (CALICO_PREDICT_END=0: always one iteration ahead, rounds 2-3).
-  const bool predict_end = streaming && fused_control && end_hint_available(p) &&
-                           [] { const char* e = std::getenv("CALICO_PREDICT_END"); return !e || std::atoi(e) != 0; }();
+  const bool predict_end = streaming && end_hint_available(p) && env_flag("CALICO_PREDICT_END", true);
   mark(2);
   int dbg_enq = 0, dbg_go = 0, dbg_wait = 0;      // CALICO_SOLVE_TIMING: iterations enqueued, on a go word, behind a finished iteration
   if (streaming) {
@@ -2425,14 +2413,8 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
       tail.enabled = 1; tail.n_amb = p->n_amb; tail.log_cap = kLogCap; tail.seq = ++enq; tail.o = o; tail.x = p->d_x.p;
       tail.x_cand = p->d_xc.p; tail.log = p->d_log.p; tail.Rbase = p->d_R.p; tail.r_stride = p->r_size;
       tail.progress = p->d_progress; tail.owner_block = p->gather_owner_block;
-      rc = enqueue_jacobian_eval(p, p->d_state.p, 0, p->d_xc.p, true, fused_control ? &tail : nullptr, predict_end);
+      rc = enqueue_jacobian_eval(p, p->d_state.p, 0, p->d_xc.p, true, &tail, predict_end);
       if (rc != CALICO_OK) return rc;
-      if (!fused_control) {
-        p->timer.begin(4, s);
-        launch_control(p->d_state.p, o, p->d_R2.p, p->d_x.p, p->d_xc.p, p->n_amb, p->d_log.p, kLogCap, nullptr, 0, p->d_R.p,
-                       p->r_size, s, false, p->d_progress, enq);
-        p->timer.end(s);
-      }
     }
   } else {
     rc = read_state(p);
@@ -2447,8 +2429,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   // a multi-rank run needs the host between the phases (the all-reduce must not run when the evaluation was skipped).
   const bool spec = p->speculative;
   const bool multi = p->has_exchange();
-  const bool multi_async_ok = [] { const char* e = std::getenv("CALICO_MULTIRANK_ASYNC"); return !e || std::atoi(e) != 0; }();
-  const bool async = !multi || (spec && multi_async_ok);
+  const bool async = !multi || (spec && env_flag("CALICO_MULTIRANK_ASYNC", true));
   const int batch = async ? std::max(1, opt->sync_every) : 1;
   int batch_now = batch;
   while (!streaming && !p->h_state->terminated) {

@@ -1248,13 +1248,14 @@ __global__ __launch_bounds__(64) void eval_jacobian_kernel(EvalArgs a) {
 }
 
 // Cell workgroups (EvalArgs.pair_mode): the Jacobian pass in workgroups of TWO waves, one per SIMD pair of a CU.
+//   with the end hint (EvalArgs.hint_progress) workgroup 0 is the hint's -- dispatched with the launch, not behind the first
+//     workgroups that end: the host has the whole evaluation to enqueue the next iteration --; the others, g = 0, 1, ..., follow:
 //   workgroups [0, n_item_wg): two work items (IMU cells), each wave its own -- they form their blocks themselves;
 //   workgroups behind them: wave w evaluates frame 2 g + w (a.fitems holds two entries per workgroup). The two frames of ONE
 //     cell: M_ext and the expansion coefficients stay in the waves' LDS areas, and behind ONE workgroup barrier both waves expand
 //     the cell's block, pair by pair, frame 0 then frame 1 -- the sums of expand_cells_kernel in the same order (bit-identical)
 //     without the compact record's trip through memory, without that kernel's launch and without its dependent loads (cell
-//     descriptor -> records). Or two one-frame cells ("solo"): each wave expands its own block out of its own LDS area;
-//   one more workgroup for the end hint.
+//     descriptor -> records). Or two one-frame cells ("solo"): each wave expands its own block out of its own LDS area.
 // 2 x (cells + item pairs) waves: what the one-wave launch had, in the same single round of one wave per SIMD.
 DEV void eval_cells_body(const EvalArgs& a, double* lds);
 __global__ __launch_bounds__(128) void eval_cells_kernel(EvalArgs a) {
@@ -1271,7 +1272,7 @@ DEV void eval_cells_body(const EvalArgs& a, double* lds) {
   const int tid = threadIdx.x, wave = tid >> 6;
   double* const lds_w = lds + size_t(wave) * a.wave_lds_doubles;
   const int n_item_wg = (a.n_items + 1) >> 1, n_cell_wg = a.n_fitems >> 1;
-  const int hint_wg = a.hint_progress && a.st && a.hint_first ? 1 : 0;       // (launch_eval_jacobian: one more workgroup)
+  const int hint_wg = a.hint_progress && a.st ? 1 : 0;       // (launch_eval_jacobian: one more workgroup)
   if (hint_wg && blockIdx.x == 0) { if (wave == 0) end_hint_body(a); return; }
   const int g = int(blockIdx.x) - hint_wg;
   if (g < n_item_wg) {
@@ -1322,7 +1323,6 @@ DEV void eval_cells_body(const EvalArgs& a, double* lds) {
     if (dbg) printf("item pair wave %d (late %d): rows staged after %lld clocks, own tiles %lld, barrier %lld, shared tiles %lld\n", wave, int(late_m), tq1 - tq0, tq2 - tq1, tq3 - tq2, (long long)__builtin_readcyclecounter() - tq3);
     return;
   }
-  if (g >= n_item_wg + n_cell_wg) { if (wave == 0 && a.hint_progress) end_hint_body(a); return; }
   if (a.st && (a.st->terminated || (a.need_flag && !a.st->need_jacobian))) return;      // (both waves alike: nobody is left at the barrier)
   const int fidx = 2 * (g - n_item_wg) + wave;
   const FrameItemDev* ip = a.fitems + fidx;

@@ -13,6 +13,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <climits>
+#include <cstdlib>
+#include <cstring>
 
 // Development instrumentation of the kernels (cycle counts printed by one wave per kernel, life span of every wave of the
 // Jacobian launch: CALICO_KERNEL_TIMING). Compiled in only with -DCALICO_DEV_TIMING (CALICO_DEV_TIMING=1 in the
@@ -25,6 +28,25 @@
 #endif
 
 namespace cal {
+
+// The library's CALICO_* switches, host side. Unset: the default; a value that reads as the integer 0: off;
+// any other value: on.
+inline bool env_flag(const char* name, bool def) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) != 0 : def;
+}
+// An integer switch: unset gives the default, a set value is clamped to [lo, hi].
+inline int env_int(const char* name, int def, int lo, int hi = INT_MAX) {
+  const char* e = std::getenv(name);
+  if (!e) return def;
+  const int v = std::atoi(e);
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+// A switch that names a variant (CALICO_SOLVER=band, CALICO_ELIM=panel).
+inline bool env_is(const char* name, const char* value) {
+  const char* e = std::getenv(name);
+  return e && std::strcmp(e, value) == 0;
+}
 
 constexpr int kRowsPerItem = 128;   // LDS rows staged per work item (64 camera obs × 2)
 constexpr int kRowPad = 129;        // largest row stride (doubles) of a staged Jacobian column
@@ -124,7 +146,7 @@ struct EvalArgs {
   // the host enqueues the next iteration only on "go" (progress word 2), so that a solve that ends leaves no iteration of
   // early-exit kernels behind on the stream. nullptr: no hint.
   int* hint_progress;
-  int hint_seq, hint_first;       // hint_first: the hint's workgroup is block 0 of eval_cells_kernel (else the last one)
+  int hint_seq;              // (the hint's workgroup: block 0 of eval_cells_kernel, the last one of eval_jacobian_kernel)
   double hint_ftol, hint_ptol;
   // Cell workgroups (plans with `fuse_expand`; eval_cells_kernel): the Jacobian launch runs workgroups of TWO waves -- the
   // (at most two) frames of one camera cell, which then expand the cell's block together out of LDS: no compact record

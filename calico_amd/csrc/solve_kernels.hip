@@ -14,8 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
-#include <string>
 
 #include "problem_dev.hpp"
 #include "solve_dev.hpp"
@@ -216,19 +214,19 @@ __global__ __launch_bounds__(256) void gather_kernel(double* __restrict__ R, con
                                                      const int* __restrict__ out_fat, const int64_t* __restrict__ ptr_fat,
                                                      const int* __restrict__ idx_fat, int n_fat, int nb_fat,
                                                      const double* __restrict__ cost_src, int n_cost,
-                                                     const LmState* st, int need_flag, size_t other_stride, ControlTail tail, int xcd_map) {
+                                                     const LmState* st, int need_flag, size_t other_stride, ControlTail tail) {
   // (the list pointers of this thread's output do not depend on the state: requested before the flags are looked at)
   int64_t pre_q0 = 0, pre_q1 = 0;
   const int nb_thin8 = (n_thin8 + 31) / 32, nb_thin4 = (n_thin4 - n_thin8 + 63) / 64;
   int o_thin = 0;
   int cls = 8;       // lanes per output of this workgroup's thin outputs
-  // xcd_map: workgroup p runs on XCD p % 8, each XCD has an L2 of its own, and the outputs are numbered in time inside a lane
+  // Workgroup p runs on XCD p % 8, each XCD has an L2 of its own, and the outputs are numbered in time inside a lane
   // class -- so every class is cut into eight contiguous pieces, one per XCD (the class's workgroups, padded to a multiple of
   // eight and starting at a multiple of eight, are dealt piece x = p % 8, position p / 8): the cells' blocks of one stretch of
   // the trajectory are then fetched by one L2 instead of by all eight.
-  int tb_map = int(blockIdx.x) - 1 - nb_fat;
+  int tb_map = 0;
   bool idle = false;
-  if (xcd_map && int(blockIdx.x) - 1 >= nb_fat) {
+  if (int(blockIdx.x) - 1 >= nb_fat) {
     const int pb = int(blockIdx.x) - ((1 + nb_fat + 7) & ~7);
     const int nb_thin1 = (n_thin - n_thin4 + 255) / 256;
     const int nbp8 = (nb_thin8 + 7) & ~7, nbp4 = (nb_thin4 + 7) & ~7;
@@ -1570,15 +1568,13 @@ void launch_gather(double* R, const double* src, const int* out_idx_thin, const 
                    const LmState* st, int need_flag, size_t other_stride, hipStream_t s, const ControlTail* tail) {
   const int nb_fat = (n_fat + 3) / 4;
   const int nb8 = (n_thin8 + 31) / 32, nb4 = (n_thin4 - n_thin8 + 63) / 64, nb1 = (n_thin - n_thin4 + 255) / 256;
-  // (A/B switch, read per launch: CALICO_GATHER_XCD=0 = the thin workgroups in output order, rounds 1-4)
-  const int xcd_map = [] { const char* e = std::getenv("CALICO_GATHER_XCD"); return !e || std::atoi(e) != 0; }() ? 1 : 0;
-  const int n_blocks = xcd_map ? ((1 + nb_fat + 7) & ~7) + ((nb8 + 7) & ~7) + ((nb4 + 7) & ~7) + ((nb1 + 7) & ~7) : 1 + nb_fat + nb8 + nb4 + nb1;
+  const int n_blocks = ((1 + nb_fat + 7) & ~7) + ((nb8 + 7) & ~7) + ((nb4 + 7) & ~7) + ((nb1 + 7) & ~7);     // (each class dealt to the XCDs)
   ControlTail t;
   if (tail) t = *tail; else { t = ControlTail(); t.enabled = 0; }
   // workgroup 0: cost / invalid count (+ control stage), then the fat outputs, then the thin ones
   // ptr_thin == nullptr: idx_thin is the fixed-stride table (gather_pack_fixed)
 #define LAUNCH_GATHER(UU, FX) hipLaunchKernelGGL((gather_kernel<UU, FX>), dim3(n_blocks), dim3(256), 0, s, R, src, out_idx_thin, ptr_thin, idx_thin, n_thin, n_thin8, n_thin4, \
-                       out_idx_fat, ptr_fat, idx_fat, n_fat, nb_fat, cost_src, n_cost, st, need_flag, other_stride, t, xcd_map)
+                       out_idx_fat, ptr_fat, idx_fat, n_fat, nb_fat, cost_src, n_cost, st, need_flag, other_stride, t)
   if (thin_per_lane <= 6) { if (ptr_thin) LAUNCH_GATHER(6, false); else LAUNCH_GATHER(6, true); }
   else { if (ptr_thin) LAUNCH_GATHER(12, false); else LAUNCH_GATHER(12, true); }
 #undef LAUNCH_GATHER
@@ -1641,8 +1637,6 @@ int reduced_schur_slices(const SolveArgs& a) {
   // Long trajectories: the Schur complement's tiles walk all eliminated rows (6 n_cp · 32/30), a few tiles x K-slices
   // workgroups in all -- at 1453 control points two slices meant 4.7k rows per workgroup, 12 us beside the last level.
   // More slices there; the in-LDS 32-column-block solver adds up to eight on load.
-  // (CALICO_SCHUR_SLICES=1 / 2: A/B switch, read per solve)
-  if (const char* se = std::getenv("CALICO_SCHUR_SLICES")) return std::max(1, std::min(kSchurSlices, std::atoi(se)));
   if (a.m + 1 <= 128) {
     if (a.n_cp >= 1280) return 8;
     if (a.n_cp >= 640) return 4;
@@ -1721,9 +1715,10 @@ void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const 
 }
 void launch_control(LmState* st, const LmOptionsDev& o, double* R2, double* x, const double* x_cand, int n_amb,
                     IterLog* log, int log_cap, const double* item_cost, int n_items, const double* Rbase, size_t r_stride,
-                    hipStream_t s, bool commit_by_copy, int* progress, int seq) {
+                    hipStream_t s, bool commit_by_copy) {
+  // (no progress word: the streaming loop's control stage rides in the gather kernel)
   hipLaunchKernelGGL(lm_control_kernel, dim3(1), dim3(256), 0, s, st, o, R2, x, x_cand, n_amb, log, log_cap, item_cost, n_items,
-                     Rbase, r_stride, commit_by_copy ? 1 : 0, progress, seq);
+                     Rbase, r_stride, commit_by_copy ? 1 : 0, nullptr, 0);
   if (commit_by_copy && r_stride)
     hipLaunchKernelGGL(commit_kernel, dim3(unsigned(std::min<size_t>(512, (r_stride + 255) / 256))), dim3(256), 0, s, st,
                        const_cast<double*>(Rbase), r_stride);

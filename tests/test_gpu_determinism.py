@@ -67,21 +67,18 @@ def test_solver_variants_agree(monkeypatch):
         monkeypatch.setenv("CALICO_BAND_SPLIT", split)
         monkeypatch.setenv("CALICO_SPECULATIVE", spec)
         results[(solver, leaf, split, spec)] = _solve_repeatedly(api, scene, repeats=1, max_iter=50)[0]
-    # the other development toggles (read per solve / per finalisation): blocking batches instead of the polled loop,
-    # stand-alone control kernel, IMU items forming their own blocks, smaller IMU work items, the tree's top level
-    # back-substituted in a launch of its own, the Schur complement / the first back-substitution in launches of their own,
-    # the gather's source lists built on the host instead of by the device from the cell structure
+    # the other switches (read per solve / per finalisation): blocking batches instead of the polled loop, the first
+    # back-substitution in a launch of its own, the gather's source lists built on the host instead of by the device from
+    # the cell structure
     monkeypatch.delenv("CALICO_SOLVER")
     monkeypatch.delenv("CALICO_BCR_LEAF", raising=False)
     monkeypatch.setenv("CALICO_BAND_SPLIT", "1")
     monkeypatch.setenv("CALICO_SPECULATIVE", "1")
-    for name, value in [("CALICO_STREAM_DEPTH", "0"), ("CALICO_FUSED_CONTROL", "0"), ("CALICO_ROW_CELLS", "0"),
-                        ("CALICO_IMU_CHUNK", "7"), ("CALICO_STREAM_DEPTH", "1"), ("CALICO_BCR_MERGE_TOP", "0"),
-                        ("CALICO_FUSE_SCHUR", "0"), ("CALICO_FUSE_BACK", "0"), ("CALICO_GATHER_STRUCT", "0"), ("CALICO_GATHER_TINY", "0"), ("CALICO_FOLD_FIRST", "0"),
-                        ("CALICO_GATHER_FIXED", "0"), ("CALICO_ELIM", "panel"),       # round 4: the block factorisation of rounds 1-3 instead of block_elim.hpp
+    for name, value in [("CALICO_STREAM_DEPTH", "0"), ("CALICO_STREAM_DEPTH", "1"),
+                        ("CALICO_FUSE_BACK", "0"), ("CALICO_GATHER_STRUCT", "0"),
+                        ("CALICO_ELIM", "panel"),       # round 4: the block factorisation of rounds 1-3 instead of block_elim.hpp
                         ("CALICO_PREDICT_END", "0"), ("CALICO_INLINE_NODES", "0"),
-                        ("CALICO_FUSE_EXPAND", "0"),        # the cell expansion in a launch of its own, IMU cells as row cells
-                        ("CALICO_GATHER_XCD", "0"), ("CALICO_SCHUR_SLICES", "2"), ("CALICO_HINT_FIRST", "0")]:        # the gather's workgroups in output order instead of dealt to the XCDs by stretches of time
+                        ("CALICO_FUSE_EXPAND", "0")]:        # the cell expansion in a launch of its own, IMU cells as row cells
         monkeypatch.setenv(name, value)
         results[(name, value)] = _solve_repeatedly(api, scene, repeats=1, max_iter=50)[0]
         monkeypatch.delenv(name)
