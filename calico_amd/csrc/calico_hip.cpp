@@ -41,7 +41,6 @@ namespace cal {
 
 // ---- kernels (eval_kernels.hip / solve_kernels.hip) -------------------------
 void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream);
-void launch_eval_frames(const EvalArgs& a, hipStream_t stream);
 void launch_eval_jacobian(const EvalArgs& a, hipStream_t stream);
 void launch_expand_cells(const EvalArgs& a, hipStream_t stream);
 void launch_residual_heatmap(const double* res, const uint8_t* valid, const uint8_t* active, const double* px, const double* py,
@@ -405,19 +404,16 @@ struct PlanHost {
   int bcr_N = 0, bcr_m1p = 16, bcr_root = -1, bcr_root_pend = 0, bcr_root_par = 0, bcr_br = 0, bcr_q_max = 1, bcr_slots = 1, bcr_q0 = 1;
   std::vector<BcrLevel> bcr_levels;
   std::vector<BcrNodeDev> h_bcr_nodes;
-  std::vector<int> h_bcr_keep, h_cp_block;
   int border_extra() const { return use_bcr ? bcr_br : 6 * sep_n; }   // rows the band hands to the dense reduced solve
   int n_cp = 0, m = 0, n_amb = 0, n_eff = 0, n_items = 0, n_items_all = 0, lds_cols = 0, row_pad = kRowPad;
-  int64_t n_obs = 0;
+  int64_t n_obs = 0, n_obs_local = 0;   // residual blocks: all, this rank's shard (calico_comm_info)
   size_t partial_doubles = 0, partials_alloc = 0;
   std::vector<int> eff_to_tan;
   std::vector<BlockDev> h_blocks;
-  std::vector<ItemDev> h_items, h_items_all, h_jac_items;
-  std::vector<FrameItemDev> h_fitems;
-  std::vector<CellDev> h_cells;
-  int cell_chunk = 1, cell_rec_max = 1, row_cell_chunk = 1;
+  int n_cells = 0, cell_chunk = 1, cell_rec_max = 1, row_cell_chunk = 1;
   int frame_lds_doubles = 0;
   int n_fitems = 0, n_jac_items = 0;
+  int max_cell_frames = 0, max_item_run = 0;   // frames of the fullest camera cell, longest run of one cell's work items (calico_debug_plan_info)
   bool fuse_expand = false;    // cell workgroups (EvalArgs.pair_mode): camera cells expanded inside the Jacobian launch, IMU items form their own blocks
   int pair_wave_lds_doubles = 0;
   int n_thin = 0, n_fat = 0;
@@ -425,8 +421,6 @@ struct PlanHost {
   int thin_per_lane = 6;       // sources per lane of a thin output's eight lanes (6: up to 48 sources, 12: up to 96)
   bool gather_fixed = false;   // the thin lists at a fixed stride (d_idx_fixed) instead of CSR
   bool dense_in_lds = true;
-  int gather_owner_block = 0;
-  bool gs_lists_on_device = false;   // the band / border / spline right-hand side lists were built by the device (launch_gather_lists)
 };
 struct PlanDev {      // structure on the device: immutable once uploaded
   DevBuf<double> d_knots, d_basis, d_stamp;
@@ -622,7 +616,7 @@ BcrArgs make_bcr_args(calico_problem* p) {
 // Elimination plan of the tree solver: level 0 eliminates chains of q consecutive superblocks between kept
 // separators, every further level every other survivor; the last survivor is the root (joins the dense solve).
 // q minimises (levels · launch + chain steps · factorisation) for the trajectory length at hand.
-void build_bcr_plan(calico_problem* p, const PlanSwitches& sw) {
+void build_bcr_plan(calico_problem* p, const PlanSwitches& sw, std::vector<int>& keep) {
   const int N = (p->n_cp + kBcrCps - 1) / kBcrCps;
   p->bcr_N = N;
   auto levels_after = [](int n_sep) { int l = 0; while (n_sep > 1) { n_sep /= 2; ++l; } return l; };
@@ -642,14 +636,14 @@ void build_bcr_plan(calico_problem* p, const PlanSwitches& sw) {
     }
     if (sw.bcr_leaf > 0) q = sw.bcr_leaf;
   }
-  p->bcr_levels.clear(); p->h_bcr_nodes.clear(); p->h_bcr_keep.clear();
+  p->bcr_levels.clear(); p->h_bcr_nodes.clear(); keep.clear();
   std::vector<int> alive(static_cast<size_t>(N), 0), mask(static_cast<size_t>(N), 0);
   for (int i = 0; i < N; ++i) alive[size_t(i)] = i;
   int level = 0, q_max_all = 1;
   while (!alive.empty() && (level == 0 || alive.size() > 1)) {
     const int chain = level == 0 ? q : 1;
     BcrLevel L;
-    L.node0 = int(p->h_bcr_nodes.size()); L.keep0 = int(p->h_bcr_keep.size() / 2); L.q_max = 1;
+    L.node0 = int(p->h_bcr_nodes.size()); L.keep0 = int(keep.size() / 2); L.q_max = 1;
     std::vector<int> kept, new_mask(size_t(N), 0);
     const size_t n = alive.size();
     size_t pos = 0;
@@ -670,9 +664,9 @@ void build_bcr_plan(calico_problem* p, const PlanSwitches& sw) {
     }
     // separators that survive this level: level 0 initialises them from R(x), later levels add last level's pending updates
     for (int kb : kept)
-      if (level == 0 || mask[size_t(kb)]) { p->h_bcr_keep.push_back(kb); p->h_bcr_keep.push_back(mask[size_t(kb)]); }
+      if (level == 0 || mask[size_t(kb)]) { keep.push_back(kb); keep.push_back(mask[size_t(kb)]); }
     L.n_nodes = int(p->h_bcr_nodes.size()) - L.node0;
-    L.n_keep = int(p->h_bcr_keep.size() / 2) - L.keep0;
+    L.n_keep = int(keep.size() / 2) - L.keep0;
     q_max_all = std::max(q_max_all, L.q_max);
     p->bcr_levels.push_back(L);
     alive = kept; mask = new_mask;
@@ -696,7 +690,7 @@ EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool
   a.m0 = p->d_m0.p; a.m1 = p->d_m1.p; a.m2 = p->d_m2.p; a.stamp = p->d_stamp.p; a.point_off = p->d_point_off.p;
   a.partials = p->d_partials.p; a.item_cost = p->d_partials.p + p->partial_doubles;
   a.res_out = want_res ? p->d_res.p : nullptr; a.valid_out = want_res ? p->d_valid.p : nullptr;
-  a.order = p->order; a.n_items = p->n_items; a.lds_cols = p->lds_cols; a.row_pad = p->row_pad; a.n_cells = int(p->h_cells.size()); a.cells = p->d_cells.p; a.prim_tab = p->d_prim_tab.p;
+  a.order = p->order; a.n_items = p->n_items; a.lds_cols = p->lds_cols; a.row_pad = p->row_pad; a.n_cells = p->n_cells; a.cells = p->d_cells.p; a.prim_tab = p->d_prim_tab.p;
   a.cell_chunk = p->cell_chunk; a.cell_rec_max = p->cell_rec_max; a.project = 0; a.row_cell_chunk = p->row_cell_chunk; a.frame_lds_doubles = p->frame_lds_doubles; a.pad5 = 0; a.wave_log = p->d_wave_log.p; a.active = p->any_tagged ? p->d_active.p : nullptr; a.apply_loss = apply_loss;
   a.st = nullptr; a.need_flag = 0; a.cost_index_base = 0;
   a.fitems = p->d_fitems.p; a.n_fitems = p->n_fitems;
@@ -721,17 +715,51 @@ struct SetupTimer {
 
 // Flatten the host tables into cells / work items / gather lists, plan the elimination, upload the STRUCTURE (everything
 // here depends on what the problem looks like, nothing on a value: the result is what the plan cache shares).
-int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
+// The stages below hand their tables on in PlanTables; only the last one, upload_plan, talks to the device.
+struct ObsKey { int layout, seg, sensor; int64_t idx; double stamp; };
+struct PlanTables {
+  std::vector<uint8_t> cp_active;               // per control point: observed
+  std::vector<int> ctrl_off;                    // per control point: ambient offset
+  std::vector<int> bcr_keep, cp_block;          // tree solver: kept separators (build_bcr_plan), block of every control point
+  std::vector<SensorDev> sd;
+  std::vector<LayoutDev> layouts;
+  std::vector<std::vector<int>> layout_gmap;    // local calibration column -> solver tangent index
+  std::map<std::array<int, 3>, int> layout_of;  // layout_key -> layout id
+  std::vector<ObsKey> keys;                     // the observations in device order
+  std::vector<double> st; std::vector<int> point_off;   // ... their stamps, their model points' ambient offsets
+  int seg_lo = 0, seg_hi = 0;                   // this rank's shard: spline segments [seg_lo, seg_hi)
+  std::vector<ItemDev> items, items_all, jac_items;
+  std::vector<FrameItemDev> fitems;
+  std::vector<CellDev> cells;
+  std::vector<int> prim_tab;
+  size_t partials_end = 0;                      // end of [expanded blocks | item costs | compact frame records | row store]
+  // gather lists: host-built CSR (thin / fat), or the table the device builds the thin ones from (gs_ok)
+  bool gs_ok = false; int64_t gs_n_out = 0;
+  std::vector<int> gs_tab;
+  GatherStruct gsd = {};
+  std::vector<int> out_thin, idx_thin, out_fat, idx_fat;
+  std::vector<int64_t> ptr_thin{0}, ptr_fat{0};
+};
+
+// (sensor, body, free model point or -1) of observation i: what its layout is per. A free model point is one more
+// calibration block of the residual blocks that observe it, so those blocks get a layout (and cells) of their own per point.
+std::array<int, 3> layout_key(const calico_problem* p, size_t si, const HSensor& s, int64_t i) {
+  if (s.kind != CALICO_SENSOR_CAMERA) return {int(si), -1, -1};
+  return {int(si), s.body[i], p->blocks[s.point[i]].constant ? -1 : s.point[i]};
+}
+
+// ---- ambient offsets, used flags, tangent order, the band's separator / the tree solver's plan ----
+int plan_blocks(calico_problem* p, const PlanSwitches& sw, PlanTables& t) {
   const int k = p->order;
   const int n_cp = int(p->ctrl.size());
   p->n_cp = n_cp;
-  // ---- ambient offsets, used flags ----
+  p->speculative = sw.speculative;
   int off = 0;
   for (HBlock& b : p->blocks) { b.amb_off = off; off += b.size; b.used = false; b.tan = -1; b.eff = -1; }
   p->n_amb = off;
   std::vector<char> is_ctrl(p->blocks.size(), 0);
   for (int id : p->ctrl) is_ctrl[id] = 1;
-  std::vector<uint8_t> cp_active(n_cp, 0);
+  std::vector<uint8_t>& cp_active = t.cp_active = std::vector<uint8_t>(size_t(n_cp), 0);
   for (HSensor& s : p->sensors) {
     if (s.n() == 0) continue;
     p->blocks[s.intr].used = p->blocks[s.q].used = p->blocks[s.t].used = p->blocks[s.lat].used = true;
@@ -749,6 +777,7 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     b.used = cp_active[i] != 0;
     if (b.constant && b.used) return p->set_error(CALICO_UNIMPLEMENTED, "constant control points are not supported");
     b.tan = 6 * i;
+    t.ctrl_off.push_back(b.amb_off);
   }
   // ---- tangent order ----
   p->h_blocks.clear(); p->eff_to_tan.clear();
@@ -770,48 +799,40 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     m += b.tangent_size(); eff += b.tangent_size();
   }
   p->m = m; p->n_eff = eff;
+  bool all_active = true;
+  for (int i = 0; i < n_cp; ++i) all_active = all_active && cp_active[size_t(i)] != 0;
   // Nested dissection with one separator (k-1 control points in the middle of the trajectory): the two halves of
   // the band are then factored and back-substituted side by side, the separator joins the dense border. Used when
   // the enlarged border still fits the in-LDS reduced solve and every control point is observed.
   p->sep_s = 0; p->sep_n = 0;
-  {
-    bool all_active = true;
-    for (int i = 0; i < n_cp; ++i) all_active = all_active && cp_active[size_t(i)] != 0;
-    if (sw.band_split && all_active && n_cp >= 6 * k && m + 6 * (k - 1) + 1 <= 1024) {
-      p->sep_n = k - 1;
-      p->sep_s = (n_cp - p->sep_n) / 2;
-    }
+  if (sw.band_split && all_active && n_cp >= 6 * k && m + 6 * (k - 1) + 1 <= 1024) {
+    p->sep_n = k - 1;
+    p->sep_s = (n_cp - p->sep_n) / 2;
   }
   // Tree solver for spline orders up to 6 (superblocks of five control points are then block tridiagonal); it takes
   // over the split of the band, so the single-separator variant above is switched off. CALICO_SOLVER=band keeps the
   // sequential banded factorisation (A/B switch, and the path of higher spline orders).
-  {
-    p->use_bcr = k <= 6 && !sw.band_solver;
-    if (p->use_bcr) {
-      p->sep_s = 0; p->sep_n = 0;
-      p->bcr_all_active = true;
-      for (int i = 0; i < n_cp; ++i) p->bcr_all_active = p->bcr_all_active && cp_active[size_t(i)] != 0;
-      p->bcr_m1p = 16 * ((m + 1 + 15) / 16);
-      build_bcr_plan(p, sw);
-    }
+  p->use_bcr = k <= 6 && !sw.band_solver;
+  if (p->use_bcr) {
+    p->sep_s = 0; p->sep_n = 0;
+    p->bcr_all_active = all_active;
+    p->bcr_m1p = 16 * ((m + 1 + 15) / 16);
+    build_bcr_plan(p, sw, t.bcr_keep);
+    t.cp_block.assign(size_t(n_cp), -1);
+    for (size_t bi = 0; bi < p->h_blocks.size(); ++bi)
+      if (p->h_blocks[bi].tan_off < 6 * n_cp) t.cp_block[size_t(p->h_blocks[bi].tan_off / 6)] = int(bi);
   }
-  const int NS = 6 * n_cp;
-  setup.section("blocks / tangent order");
-  // ---- layouts ----
-  std::vector<SensorDev> sd(p->sensors.size());
-  std::vector<LayoutDev> layouts;
-  std::vector<std::vector<int>> layout_gmap;             // local calibration column -> solver tangent index
-  // (sensor, body, free model point or -1) -> layout id. A free model point is one more calibration block of the
-  // residual blocks that observe it, so those blocks get a layout (and cells) of their own per point.
-  std::map<std::array<int, 3>, int> layout_of;
-  auto layout_key = [&](size_t si, const HSensor& s, int64_t i) -> std::array<int, 3> {
-    if (s.kind != CALICO_SENSOR_CAMERA) return {int(si), -1, -1};
-    return {int(si), s.body[i], p->blocks[s.point[i]].constant ? -1 : s.point[i]};
-  };
+  return CALICO_OK;
+}
+
+// ---- layouts ----
+void plan_layouts(calico_problem* p, PlanTables& t) {
+  const int k = p->order;
+  t.sd.resize(p->sensors.size());
   auto is_free = [&](int id) { return id >= 0 && !p->blocks[id].constant; };
   for (size_t si = 0; si < p->sensors.size(); ++si) {
     const HSensor& s = p->sensors[si];
-    SensorDev& d = sd[si];
+    SensorDev& d = t.sd[si];
     d.kind = s.kind; d.model = s.model; d.K = s.K; d.loss = s.loss;
     d.intr_off = p->blocks[s.intr].amb_off; d.q_off = p->blocks[s.q].amb_off; d.t_off = p->blocks[s.t].amb_off;
     d.lat_off = p->blocks[s.lat].amb_off; d.grav_off = s.grav >= 0 ? p->blocks[s.grav].amb_off : 0; d.pad0 = 0;
@@ -819,10 +840,10 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     std::array<int, 3> seen = {-2, -2, -2};       // (consecutive observations mostly share their layout: one compare instead of a map look-up)
     for (int64_t i = 0; i < s.n(); ++i) {
       const int body = s.kind == CALICO_SENSOR_CAMERA ? s.body[i] : -1;
-      const std::array<int, 3> lkey = layout_key(si, s, i);
+      const std::array<int, 3> lkey = layout_key(p, si, s, i);
       if (lkey == seen) continue;
       seen = lkey;
-      if (layout_of.count(lkey)) continue;
+      if (t.layout_of.count(lkey)) continue;
       LayoutDev L;
       L.sensor = int(si); L.c_pt = -1;
       std::vector<int> gmap;
@@ -843,14 +864,15 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
         add(s.grav, &L.c_grav);
       }
       L.ncols = c;
-      layout_of[lkey] = int(layouts.size());
-      layouts.push_back(L); layout_gmap.push_back(gmap);
+      t.layout_of[lkey] = int(t.layouts.size());
+      t.layouts.push_back(L); t.layout_gmap.push_back(gmap);
     }
   }
-  setup.section("layouts");
-  // ---- sort observations by (layout, segment) and cut work items ----
-  struct Key { int layout, seg, sensor; int64_t idx; double stamp; };
-  std::vector<Key> keys;
+}
+
+// ---- sort observations by (layout, segment), cut work items, this rank's shard ----
+void plan_items(calico_problem* p, PlanTables& t) {
+  std::vector<ObsKey>& keys = t.keys;
   int64_t n_obs = 0;
   for (const HSensor& s : p->sensors) n_obs += s.n();
   keys.reserve(size_t(n_obs));
@@ -860,8 +882,8 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     std::array<int, 3> seen = {-2, -2, -2};
     int seen_layout = -1;
     for (int64_t i = 0; i < s.n(); ++i) {
-      const std::array<int, 3> lkey = layout_key(si, s, i);
-      if (!(lkey == seen)) { seen = lkey; seen_layout = layout_of[lkey]; }
+      const std::array<int, 3> lkey = layout_key(p, si, s, i);
+      if (!(lkey == seen)) { seen = lkey; seen_layout = t.layout_of[lkey]; }
       keys.push_back({seen_layout, s.seg[i], int(si), i, s.stamps[size_t(i)]});
     }
   }
@@ -870,296 +892,272 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     // does almost all of it -- measurements arrive in time order, sensor by sensor --; a cell whose stamps are not in
     // order gets a stable comparison sort of its own. (One comparison sort over all keys was 1.5 ms of the set-up.)
     const int nseg_all = std::max(1, int(p->valid_knots.size()) - 1);
-    const size_t n_cell_ids = layouts.size() * size_t(nseg_all);
+    const size_t n_cell_ids = t.layouts.size() * size_t(nseg_all);
     std::vector<int64_t> cstart(n_cell_ids + 1, 0);
-    auto cell_of = [&](const Key& kq) { return size_t(kq.layout) * size_t(nseg_all) + size_t(std::max(0, std::min(nseg_all - 1, kq.seg))); };
-    for (const Key& kq : keys) ++cstart[cell_of(kq) + 1];
+    auto cell_of = [&](const ObsKey& kq) { return size_t(kq.layout) * size_t(nseg_all) + size_t(std::max(0, std::min(nseg_all - 1, kq.seg))); };
+    for (const ObsKey& kq : keys) ++cstart[cell_of(kq) + 1];
     for (size_t c = 0; c < n_cell_ids; ++c) cstart[c + 1] += cstart[c];
-    std::vector<Key> sorted(keys.size());
+    std::vector<ObsKey> sorted(keys.size());
     {
       std::vector<int64_t> fill(cstart.begin(), cstart.end() - 1);
-      for (const Key& kq : keys) sorted[size_t(fill[cell_of(kq)]++)] = kq;
+      for (const ObsKey& kq : keys) sorted[size_t(fill[cell_of(kq)]++)] = kq;
     }
     for (size_t c = 0; c < n_cell_ids; ++c) {
       const int64_t q0 = cstart[c], q1 = cstart[c + 1];
       bool ordered = true;
       for (int64_t q = q0 + 1; q < q1 && ordered; ++q) ordered = !(sorted[size_t(q)].stamp < sorted[size_t(q - 1)].stamp);
       if (!ordered)
-        std::stable_sort(sorted.begin() + q0, sorted.begin() + q1, [](const Key& a, const Key& b) { return a.stamp < b.stamp; });
+        std::stable_sort(sorted.begin() + q0, sorted.begin() + q1, [](const ObsKey& a, const ObsKey& b) { return a.stamp < b.stamp; });
     }
     keys.swap(sorted);
   }
   p->n_obs = n_obs;
-  std::vector<double> st(n_obs);
-  std::vector<int> point_off(n_obs, 0);
-  p->h_items.clear(); p->h_items_all.clear();
-  int max_cols = 0;
-  for (int64_t q = 0; q < n_obs;) {
-    int64_t e = q;
-    while (e < n_obs && keys[e].layout == keys[q].layout && keys[e].seg == keys[q].seg) ++e;
-    const LayoutDev& L = layouts[keys[q].layout];
-    const int dim = p->sensors[L.sensor].dim();
-    // cameras fill the 128 staged rows; an IMU block is a long single-lane computation and there are few of them, so
-    // they are cut finer: more waves in flight, shorter JᵀJ stage, smaller LDS footprint next to the camera frames
-    const int chunk = dim == 2 ? kRowsPerItem / 2 : kImuChunkItems;
-    max_cols = std::max(max_cols, L.ncols + 1);
-    for (int64_t b = q; b < e; b += chunk) {
-      ItemDev it;
-      it.layout = keys[q].layout; it.seg = keys[q].seg; it.obs_begin = int(b); it.obs_count = int(std::min<int64_t>(chunk, e - b));
-      it.partial_off = 0; it.rows_off = -1;
-      p->h_items_all.push_back(it);
-    }
-    q = e;
-  }
-  // this rank's shard: a contiguous window of spline segments (shard.hpp)
-  const int nseg = int(p->valid_knots.size()) - 1;
-  std::vector<int64_t> per_seg(size_t(nseg), 0);
-  for (const ItemDev& it : p->h_items_all) per_seg[size_t(it.seg)] += it.obs_count;
-  const std::vector<int> win = shard_windows(per_seg, p->world);
-  const int seg_lo = win[size_t(p->rank)], seg_hi = win[size_t(p->rank) + 1];
-  for (const ItemDev& it : p->h_items_all)
-    if (it.seg >= seg_lo && it.seg < seg_hi) p->h_items.push_back(it);
-  // Jacobian pass: camera cells are cut into FRAMES (blocks sharing the stamp) for the frame kernel
-  // when the spline order is 6 and frames are reasonably full; everything else goes to the generic kernel.
-  p->h_fitems.clear(); p->h_jac_items.clear(); p->h_cells.clear();
-  size_t poff = 0, comp_off = 0;
-  // compact record of a camera frame: M_ext (PE×PE) + expansion coefficients (ncols + 1); see eval_kernels.hip
-  auto frame_rec = [&](const LayoutDev& L) -> size_t {
-    const HSensor& hs = p->sensors[size_t(L.sensor)];
-    const int P1 = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_q >= 0) + 3 * (L.c_t >= 0) + 3 * (L.c_bq >= 0) + 3 * (L.c_bt >= 0);
-    const int PE = P1 + 1;     // prim columns + the latency row / column
-    return size_t(PE) * PE + size_t(L.ncols + 1);
-  };
-  {
-    std::vector<char> layout_uses_frames(layouts.size(), 0);
-    if (k == 6) {
-      std::vector<int64_t> n_obs_l(layouts.size(), 0), n_frames_l(layouts.size(), 0);
-      for (int64_t q = 0; q < n_obs;) {
-        int64_t e = q;
-        while (e < n_obs && keys[e].layout == keys[q].layout && keys[e].seg == keys[q].seg && keys[e].stamp == keys[q].stamp) ++e;
-        n_obs_l[size_t(keys[q].layout)] += e - q; n_frames_l[size_t(keys[q].layout)] += 1;
-        q = e;
-      }
-      for (size_t l = 0; l < layouts.size(); ++l)
-        layout_uses_frames[l] = p->sensors[size_t(layouts[l].sensor)].kind == CALICO_SENSOR_CAMERA && n_frames_l[l] > 0 &&
-                                n_obs_l[l] >= 16 * n_frames_l[l] && layouts[l].ncols + 1 - 36 + 6 <= 30 && layouts[l].c_pt < 0;
-    }
-    for (int64_t q = 0; q < n_obs;) {
-      const Key& kq = keys[q];
-      int64_t e = q;
-      if (layout_uses_frames[size_t(kq.layout)]) {
-        while (e < n_obs && keys[e].layout == kq.layout && keys[e].seg == kq.seg && keys[e].stamp == kq.stamp) ++e;
-        if (kq.seg >= seg_lo && kq.seg < seg_hi) {
-          FrameItemDev f;
-          f.layout = kq.layout; f.seg = kq.seg; f.obs_begin = int(q); f.obs_count = int(e - q); f.stamp = kq.stamp;
-          f.partial_off = int64_t(comp_off);                  // compact record, rebased below
-          comp_off += frame_rec(layouts[size_t(kq.layout)]);
-          // frames arrive sorted by (layout, segment, stamp): consecutive frames of one cell share one expanded block
-          if (p->h_cells.empty() || p->h_cells.back().layout != kq.layout || p->h_cells.back().seg != kq.seg) {
-            CellDev c;
-            c.layout = kq.layout; c.seg = kq.seg; c.frame_begin = int(p->h_fitems.size()); c.frame_count = 0;
-            c.partial_off = int64_t(poff); c.prim_off = 0;
-            poff += size_t(tri_size(layouts[size_t(kq.layout)].ncols + 1));      // (the block's upper triangle, packed: problem_dev.hpp)
-            p->h_cells.push_back(c);
-          }
-          p->h_cells.back().frame_count += 1;
-          f.cell = int(p->h_cells.size()) - 1; f.cell_frames = 0; f.cell_prim_off = 0; f.cell_pad = 0; f.cell_partial_off = 0; f.cell_src_off = 0;   // (filled below)
-          p->h_fitems.push_back(f);
-        }
-      } else {
-        while (e < n_obs && keys[e].layout == kq.layout) ++e;
-      }
-      q = e;
-    }
-    // IMU work items hand their staged rows to the cell kernel ("row cells": one expanded block per (layout, segment)
-    // instead of one per item); everything else forms its own block
-    // fuse_expand (CALICO_FUSE_EXPAND=0: off): no launch for the cell expansion -- a camera cell is expanded by the last of its
-    // frames inside the Jacobian launch (eval_kernels.hip), and the other work items form their blocks themselves, each
-    // registered as a cell of its own so that the gather's device-built lists see it. Needs every such (layout, segment) to
-    // be ONE work item (an IMU cell of at most kImuChunkItems blocks: the usual case).
-    bool fuse = !p->h_fitems.empty() && sw.fuse_expand;
-    for (const CellDev& c : p->h_cells) if (c.frame_count > 2) fuse = false;       // (a workgroup is two waves: one frame each)
-    {
-      // ... and two waves' staging areas must fit the CU's LDS
-      size_t need = 0;
-      for (size_t l = 0; l < layouts.size(); ++l) {
-        const LayoutDev& L = layouts[l];
-        const HSensor& hs = p->sensors[size_t(L.sensor)];
-        if (layout_uses_frames[l]) {
-          const int P1 = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_q >= 0) + 3 * (L.c_t >= 0) + 3 * (L.c_bq >= 0) + 3 * (L.c_bt >= 0);
-          const int Ps = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_bq >= 0);
-          need = std::max(need, frame_lds_doubles(Ps, P1, L.ncols + 1));
-        } else {
-          need = std::max(need, size_t((L.ncols + 1 + 15) & ~15) * size_t((((3 * kImuChunkItems + 3) & ~3) + 1) | 1));      // (as lds_cols x row_pad below)
-        }
-      }
-      need = (need + 1) & ~size_t(1);
-      if (cells_launch_lds_bytes(need) > kCellsMaxLds) fuse = false;     // (the same bound the kernel's attribute is set to)
-      p->pair_wave_lds_doubles = int(need);
-    }
-    {
-      int prev_layout = -1, prev_seg = -1;
-      for (const ItemDev& it : p->h_items) {
-        if (layout_uses_frames[size_t(it.layout)]) continue;
-        if (it.layout == prev_layout && it.seg == prev_seg) fuse = false;
-        if (p->sensors[size_t(layouts[size_t(it.layout)].sensor)].kind == CALICO_SENSOR_CAMERA) fuse = false;     // (camera blocks outside the frame path)
-        prev_layout = it.layout; prev_seg = it.seg;
-      }
-    }
-    p->fuse_expand = fuse;
-    if (fuse) {
-      // two frame entries per workgroup, so that wave w of workgroup g finds its frame at 2 g + w without reading a descriptor
-      // first: the two frames of a cell (they expand the cell's block together), or two one-frame cells (`cell_pad` = 1, "solo":
-      // each wave expands its own cell alone, no barrier), or a solo frame and an empty entry (obs_count = 0)
-      std::vector<FrameItemDev> packed;
-      packed.reserve(2 * p->h_cells.size());
-      std::vector<FrameItemDev> solos;
-      for (CellDev& c : p->h_cells) {
-        if (c.frame_count > 1) {
-          FrameItemDev f0 = p->h_fitems[size_t(c.frame_begin)], f1 = p->h_fitems[size_t(c.frame_begin) + 1];
-          f0.cell_pad = f1.cell_pad = 0;
-          packed.push_back(f0); packed.push_back(f1);
-        } else {
-          FrameItemDev f0 = p->h_fitems[size_t(c.frame_begin)];
-          f0.cell_pad = 1;
-          solos.push_back(f0);
-        }
-      }
-      for (size_t i = 0; i < solos.size(); i += 2) {
-        packed.push_back(solos[i]);
-        FrameItemDev f1 = solos[i];
-        if (i + 1 < solos.size()) f1 = solos[i + 1]; else f1.obs_count = 0;
-        packed.push_back(f1);
-      }
-      p->h_fitems.swap(packed);
-      for (CellDev& c : p->h_cells) c.frame_begin = -1;      // (the frames are no longer contiguous by cell: FrameItemDev.cell says whose they are)
-    }
-    for (ItemDev it : p->h_items) {
-      if (layout_uses_frames[size_t(it.layout)]) continue;
-      const LayoutDev& L = layouts[size_t(it.layout)];
-      const HSensor& hs = p->sensors[size_t(L.sensor)];
-      const int n1 = L.ncols + 1;
-      if (fuse) {
-        // a cell of one work item that writes the cell's block itself (prim_off = -2: nothing for expand_cells_kernel to do)
-        CellDev c;
-        c.layout = it.layout; c.seg = it.seg; c.frame_begin = int(p->h_jac_items.size()); c.frame_count = 1;
-        c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = 0; c.prim_off = -2; c.pad0 = 0;
-        p->h_cells.push_back(c);
-        it.rows_off = -2;            // (< 0: the item forms its own block; -2: that block is listed as a cell's)
-        it.partial_off = int64_t(poff);
-        poff += size_t(tri_size(n1));
-      } else if (hs.kind != CALICO_SENSOR_CAMERA && n1 <= 112) {
-        it.partial_off = 0; it.rows_off = 0;   // row store offset assigned below, once the staging dimensions are known
-        if (p->h_cells.empty() || p->h_cells.back().prim_off >= 0 || p->h_cells.back().layout != it.layout ||
-            p->h_cells.back().seg != it.seg) {
-          CellDev c;
-          c.layout = it.layout; c.seg = it.seg; c.frame_begin = int(p->h_jac_items.size()); c.frame_count = 0;
-          c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = hs.dim() * kImuChunkItems; c.prim_off = -1; c.pad0 = 0;
-          poff += size_t(tri_size(n1));
-          p->h_cells.push_back(c);
-        }
-        p->h_cells.back().frame_count += 1;
-        p->h_cells.back().pad0 += hs.dim() * it.obs_count;
-      } else {
-        it.rows_off = -1;
-        it.partial_off = int64_t(poff);
-        poff += size_t(tri_size(n1));
-      }
-      p->h_jac_items.push_back(it);
-    }
-  }
-  p->n_fitems = int(p->h_fitems.size());
-  p->n_jac_items = int(p->h_jac_items.size());
-  // buffer layout: [expanded partial blocks: cells, generic items | item costs (2 per item) | compact frame records]
-  const size_t n_cost_slots = 2 * size_t(std::max(std::max(int(p->h_items.size()), int(p->h_items_all.size())), p->n_fitems + p->n_jac_items));
-  const size_t comp_base = poff + n_cost_slots;
-  p->cell_rec_max = 1;
-  p->frame_lds_doubles = 0;
-  for (FrameItemDev& f : p->h_fitems) {
-    {
-      const LayoutDev& L = layouts[size_t(f.layout)];
-      const HSensor& hs = p->sensors[size_t(L.sensor)];
-      const int P1 = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_q >= 0) + 3 * (L.c_t >= 0) + 3 * (L.c_bq >= 0) + 3 * (L.c_bt >= 0);
-      const int Ps = 7 + (L.c_intr >= 0 ? hs.K : 0) + 3 * (L.c_bq >= 0);     // staged (small) prim columns: eval_kernels.hip
-      p->frame_lds_doubles = std::max(p->frame_lds_doubles, int(frame_lds_doubles(Ps, P1, L.ncols + 1)));
-    }
-    f.partial_off += int64_t(comp_base);
-    p->cell_rec_max = std::max(p->cell_rec_max, int(frame_rec(layouts[size_t(f.layout)])));
-  }
-  p->cell_chunk = std::max(1, int((56 * 1024 / sizeof(double)) / size_t(p->cell_rec_max)));
-  {
-    // no more LDS than the fullest cell needs: the cell kernel's workgroups should all be resident at once
-    int most = 1;
-    for (const CellDev& c : p->h_cells) if (c.prim_off >= 0) most = std::max(most, c.frame_count);
-    p->cell_chunk = std::min(p->cell_chunk, most);
-  }
-  // per-layout prim-column table of the cell kernel (mirror of prim_map / the frame kernel's column order)
-  std::vector<int> prim_tab;
-  {
-    std::vector<int> tab_off(layouts.size(), -1);
-    for (CellDev& c : p->h_cells) {
-      if (c.prim_off < 0) continue;   // row cell
-      const LayoutDev& L = layouts[size_t(c.layout)];
-      const HSensor& hs = p->sensors[size_t(L.sensor)];
-      int pc = 6;
-      const int p_intr = pc; if (L.c_intr >= 0) pc += hs.K;
-      const int p_q = pc; if (L.c_q >= 0) pc += 3;
-      const int p_t = pc; if (L.c_t >= 0) pc += 3;
-      const int p_bq = pc; if (L.c_bq >= 0) pc += 3;
-      const int p_bt = pc; if (L.c_bt >= 0) pc += 3;
-      const int p_r = pc, PT = pc + 1;     // latency row / column right behind the prim columns
-      if (tab_off[size_t(c.layout)] < 0) {
-        tab_off[size_t(c.layout)] = int(prim_tab.size());
-        std::vector<int> prim;
-        for (int lc = 0; lc <= L.ncols; ++lc) {
-          int pr;
-          if (lc < 36) pr = lc % 6;
-          else if (lc == L.c_lat) pr = PT;
-          else if (lc == L.ncols) pr = p_r;
-          else if (L.c_intr >= 0 && lc >= L.c_intr && lc < L.c_intr + hs.K) pr = p_intr + (lc - L.c_intr);
-          else if (L.c_q >= 0 && lc >= L.c_q && lc < L.c_q + 3) pr = p_q + (lc - L.c_q);
-          else if (L.c_t >= 0 && lc >= L.c_t && lc < L.c_t + 3) pr = p_t + (lc - L.c_t);
-          else if (L.c_bq >= 0 && lc >= L.c_bq && lc < L.c_bq + 3) pr = p_bq + (lc - L.c_bq);
-          else pr = p_bt + (lc - L.c_bt);
-          prim.push_back(pr);
-        }
-        // pair table of the cell kernel: row-major upper triangle of the (c+1)×(c+1) block
-        const int n1 = L.ncols + 1, PEc = PT + 1;
-        for (int i = 0; i < n1; ++i)
-          for (int j = i; j < n1; ++j) prim_tab.push_back(i | (j << 8) | ((prim[size_t(i)] * PEc + prim[size_t(j)]) << 16));
-      }
-      c.prim_off = tab_off[size_t(c.layout)]; c.pad0 = 0;
-      c.n1 = L.ncols + 1; c.PE = PT + 1;
-      c.src_off = c.frame_begin >= 0 ? p->h_fitems[size_t(c.frame_begin)].partial_off : 0;      // (no compact records with cell workgroups)
-    }
-    for (FrameItemDev& fi : p->h_fitems) {      // (copies of the cell's fields for the cell's workgroup: fuse_expand)
-      const CellDev& c = p->h_cells[size_t(fi.cell)];
-      fi.cell_frames = c.frame_count; fi.cell_prim_off = c.prim_off; fi.cell_partial_off = c.partial_off; fi.cell_src_off = c.src_off;
-    }
-  }
+  t.st.assign(size_t(n_obs), 0.0);
+  t.point_off.assign(size_t(n_obs), 0);
   for (HSensor& s : p->sensors) { s.sorted_begin = n_obs; s.sorted_end = 0; }
   for (int64_t q = 0; q < n_obs; ++q) {
     HSensor& s = p->sensors[keys[q].sensor];
     const int64_t i = keys[q].idx;
     s.sorted_pos[size_t(i)] = q;
     s.sorted_begin = std::min(s.sorted_begin, q); s.sorted_end = std::max(s.sorted_end, q + 1);   // layouts are per sensor: contiguous
-    st[q] = s.stamps[i];
-    if (s.kind == CALICO_SENSOR_CAMERA) point_off[q] = p->blocks[s.point[i]].amb_off;
+    t.st[q] = s.stamps[i];
+    if (s.kind == CALICO_SENSOR_CAMERA) t.point_off[q] = p->blocks[s.point[i]].amb_off;
   }
-  p->n_items = int(p->h_items.size());
-  p->n_items_all = int(p->h_items_all.size());
+  for (int64_t q = 0; q < n_obs;) {
+    int64_t e = q;
+    while (e < n_obs && keys[e].layout == keys[q].layout && keys[e].seg == keys[q].seg) ++e;
+    const LayoutDev& L = t.layouts[keys[q].layout];
+    const int dim = p->sensors[L.sensor].dim();
+    // cameras fill the 128 staged rows; an IMU block is a long single-lane computation and there are few of them, so
+    // they are cut finer: more waves in flight, shorter JᵀJ stage, smaller LDS footprint next to the camera frames
+    const int chunk = dim == 2 ? kRowsPerItem / 2 : kImuChunkItems;
+    for (int64_t b = q; b < e; b += chunk) {
+      ItemDev it;
+      it.layout = keys[q].layout; it.seg = keys[q].seg; it.obs_begin = int(b); it.obs_count = int(std::min<int64_t>(chunk, e - b));
+      it.partial_off = 0; it.rows_off = -1;
+      t.items_all.push_back(it);
+    }
+    q = e;
+  }
+  // this rank's shard: a contiguous window of spline segments (shard.hpp)
+  const int nseg = int(p->valid_knots.size()) - 1;
+  std::vector<int64_t> per_seg(size_t(nseg), 0);
+  for (const ItemDev& it : t.items_all) per_seg[size_t(it.seg)] += it.obs_count;
+  const std::vector<int> win = shard_windows(per_seg, p->world);
+  t.seg_lo = win[size_t(p->rank)]; t.seg_hi = win[size_t(p->rank) + 1];
+  p->n_obs_local = 0;
+  for (const ItemDev& it : t.items_all)
+    if (it.seg >= t.seg_lo && it.seg < t.seg_hi) { t.items.push_back(it); p->n_obs_local += it.obs_count; }
+  p->n_items = int(t.items.size());
+  p->n_items_all = int(t.items_all.size());
+}
+
+// ---- the evaluation route: frames, cells, cell workgroups, generic and IMU items, the row store ----
+int plan_route(calico_problem* p, const PlanSwitches& sw, PlanTables& t) {
+  const int k = p->order;
+  const int64_t n_obs = p->n_obs;
+  const std::vector<ObsKey>& keys = t.keys; const std::vector<LayoutDev>& layouts = t.layouts;
+  std::vector<FrameItemDev>& fitems = t.fitems; std::vector<ItemDev>& jac_items = t.jac_items; std::vector<CellDev>& cells = t.cells;
+  // Jacobian pass: camera cells are cut into FRAMES (blocks sharing the stamp) for the frame path (eval_frames_body)
+  // when the spline order is 6 and frames are reasonably full; everything else goes to the generic kernel.
+  size_t poff = 0, comp_off = 0;
+  // compact record of a camera frame: M_ext (PE×PE) + expansion coefficients (ncols + 1); see eval_kernels.hip
+  auto frame_rec = [&](const LayoutDev& L) -> size_t {
+    const int PE = prim_map(L, t.sd[size_t(L.sensor)]).PE;
+    return size_t(PE) * PE + size_t(L.ncols + 1);
+  };
+  // LDS of a frame workgroup of the layout (eval_kernels.hip, frame_lds_doubles)
+  auto frame_lds = [&](const LayoutDev& L) -> size_t {
+    const SensorDev& S = t.sd[size_t(L.sensor)];
+    return frame_lds_doubles(small_map(L, S).P, prim_map(L, S).P1, L.ncols + 1);
+  };
+  std::vector<char> layout_uses_frames(layouts.size(), 0);
+  if (k == 6) {
+    std::vector<int64_t> n_obs_l(layouts.size(), 0), n_frames_l(layouts.size(), 0);
+    for (int64_t q = 0; q < n_obs;) {
+      int64_t e = q;
+      while (e < n_obs && keys[e].layout == keys[q].layout && keys[e].seg == keys[q].seg && keys[e].stamp == keys[q].stamp) ++e;
+      n_obs_l[size_t(keys[q].layout)] += e - q; n_frames_l[size_t(keys[q].layout)] += 1;
+      q = e;
+    }
+    for (size_t l = 0; l < layouts.size(); ++l)
+      layout_uses_frames[l] = p->sensors[size_t(layouts[l].sensor)].kind == CALICO_SENSOR_CAMERA && n_frames_l[l] > 0 &&
+                              n_obs_l[l] >= 16 * n_frames_l[l] && layouts[l].ncols + 1 - 36 + 6 <= 30 && layouts[l].c_pt < 0;
+  }
+  for (int64_t q = 0; q < n_obs;) {
+    const ObsKey& kq = keys[q];
+    int64_t e = q;
+    if (layout_uses_frames[size_t(kq.layout)]) {
+      while (e < n_obs && keys[e].layout == kq.layout && keys[e].seg == kq.seg && keys[e].stamp == kq.stamp) ++e;
+      if (kq.seg >= t.seg_lo && kq.seg < t.seg_hi) {
+        FrameItemDev f;
+        f.layout = kq.layout; f.seg = kq.seg; f.obs_begin = int(q); f.obs_count = int(e - q); f.stamp = kq.stamp;
+        f.partial_off = int64_t(comp_off);                  // compact record, rebased below
+        comp_off += frame_rec(layouts[size_t(kq.layout)]);
+        // frames arrive sorted by (layout, segment, stamp): consecutive frames of one cell share one expanded block
+        if (cells.empty() || cells.back().layout != kq.layout || cells.back().seg != kq.seg) {
+          CellDev c;
+          c.layout = kq.layout; c.seg = kq.seg; c.frame_begin = int(fitems.size()); c.frame_count = 0;
+          c.partial_off = int64_t(poff); c.prim_off = 0;
+          poff += size_t(tri_size(layouts[size_t(kq.layout)].ncols + 1));      // (the block's upper triangle, packed: problem_dev.hpp)
+          cells.push_back(c);
+        }
+        cells.back().frame_count += 1;
+        f.cell = int(cells.size()) - 1; f.cell_frames = 0; f.cell_prim_off = 0; f.cell_pad = 0; f.cell_partial_off = 0; f.cell_src_off = 0;   // (filled below)
+        fitems.push_back(f);
+      }
+    } else {
+      while (e < n_obs && keys[e].layout == kq.layout) ++e;
+    }
+    q = e;
+  }
+  // IMU work items hand their staged rows to the cell kernel ("row cells": one expanded block per (layout, segment)
+  // instead of one per item); everything else forms its own block
+  // fuse_expand (CALICO_FUSE_EXPAND=0: off): no launch for the cell expansion -- a camera cell is expanded by the last of its
+  // frames inside the Jacobian launch (eval_kernels.hip), and the other work items form their blocks themselves, each
+  // registered as a cell of its own so that the gather's device-built lists see it. Needs every such (layout, segment) to
+  // be ONE work item (an IMU cell of at most kImuChunkItems blocks: the usual case).
+  bool fuse = !fitems.empty() && sw.fuse_expand;
+  for (const CellDev& c : cells) if (c.frame_count > 2) fuse = false;       // (a workgroup is two waves: one frame each)
+  {
+    // ... and two waves' staging areas must fit the CU's LDS
+    size_t need = 0;
+    for (size_t l = 0; l < layouts.size(); ++l) {
+      const LayoutDev& L = layouts[l];
+      if (layout_uses_frames[l]) need = std::max(need, frame_lds(L));
+      else need = std::max(need, size_t((L.ncols + 1 + 15) & ~15) * size_t((((3 * kImuChunkItems + 3) & ~3) + 1) | 1));      // (as lds_cols x row_pad below)
+    }
+    need = (need + 1) & ~size_t(1);
+    if (cells_launch_lds_bytes(need) > kCellsMaxLds) fuse = false;     // (the same bound the kernel's attribute is set to)
+    p->pair_wave_lds_doubles = int(need);
+  }
+  {
+    int prev_layout = -1, prev_seg = -1;
+    for (const ItemDev& it : t.items) {
+      if (layout_uses_frames[size_t(it.layout)]) continue;
+      if (it.layout == prev_layout && it.seg == prev_seg) fuse = false;
+      if (p->sensors[size_t(layouts[size_t(it.layout)].sensor)].kind == CALICO_SENSOR_CAMERA) fuse = false;     // (camera blocks outside the frame path)
+      prev_layout = it.layout; prev_seg = it.seg;
+    }
+  }
+  p->fuse_expand = fuse;
+  if (fuse) {
+    // two frame entries per workgroup, so that wave w of workgroup g finds its frame at 2 g + w without reading a descriptor
+    // first: the two frames of a cell (they expand the cell's block together), or two one-frame cells (`cell_pad` = 1, "solo":
+    // each wave expands its own cell alone, no barrier), or a solo frame and an empty entry (obs_count = 0)
+    std::vector<FrameItemDev> packed;
+    packed.reserve(2 * cells.size());
+    std::vector<FrameItemDev> solos;
+    for (CellDev& c : cells) {
+      if (c.frame_count > 1) {
+        FrameItemDev f0 = fitems[size_t(c.frame_begin)], f1 = fitems[size_t(c.frame_begin) + 1];
+        f0.cell_pad = f1.cell_pad = 0;
+        packed.push_back(f0); packed.push_back(f1);
+      } else {
+        FrameItemDev f0 = fitems[size_t(c.frame_begin)];
+        f0.cell_pad = 1;
+        solos.push_back(f0);
+      }
+    }
+    for (size_t i = 0; i < solos.size(); i += 2) {
+      packed.push_back(solos[i]);
+      FrameItemDev f1 = solos[i];
+      if (i + 1 < solos.size()) f1 = solos[i + 1]; else f1.obs_count = 0;
+      packed.push_back(f1);
+    }
+    fitems.swap(packed);
+    for (CellDev& c : cells) c.frame_begin = -1;      // (the frames are no longer contiguous by cell: FrameItemDev.cell says whose they are)
+  }
+  int run = 0;      // (consecutive work items of one cell; the longest run: calico_debug_plan_info)
+  p->max_item_run = 0;
+  for (ItemDev it : t.items) {
+    if (layout_uses_frames[size_t(it.layout)]) continue;
+    const LayoutDev& L = layouts[size_t(it.layout)];
+    const HSensor& hs = p->sensors[size_t(L.sensor)];
+    const int n1 = L.ncols + 1;
+    if (fuse) {
+      // a cell of one work item that writes the cell's block itself (prim_off = -2: nothing for expand_cells_kernel to do)
+      CellDev c;
+      c.layout = it.layout; c.seg = it.seg; c.frame_begin = int(jac_items.size()); c.frame_count = 1;
+      c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = 0; c.prim_off = -2; c.pad0 = 0;
+      cells.push_back(c);
+      it.rows_off = -2;            // (< 0: the item forms its own block; -2: that block is listed as a cell's)
+      it.partial_off = int64_t(poff);
+      poff += size_t(tri_size(n1));
+    } else if (hs.kind != CALICO_SENSOR_CAMERA && n1 <= 112) {
+      it.partial_off = 0; it.rows_off = 0;   // row store offset assigned below, once the staging dimensions are known
+      if (cells.empty() || cells.back().prim_off >= 0 || cells.back().layout != it.layout || cells.back().seg != it.seg) {
+        CellDev c;
+        c.layout = it.layout; c.seg = it.seg; c.frame_begin = int(jac_items.size()); c.frame_count = 0;
+        c.partial_off = int64_t(poff); c.src_off = 0; c.n1 = n1; c.PE = hs.dim() * kImuChunkItems; c.prim_off = -1; c.pad0 = 0;
+        poff += size_t(tri_size(n1));
+        cells.push_back(c);
+      }
+      cells.back().frame_count += 1;
+      cells.back().pad0 += hs.dim() * it.obs_count;
+    } else {
+      it.rows_off = -1;
+      it.partial_off = int64_t(poff);
+      poff += size_t(tri_size(n1));
+    }
+    run = !jac_items.empty() && jac_items.back().layout == it.layout && jac_items.back().seg == it.seg ? run + 1 : 1;
+    p->max_item_run = std::max(p->max_item_run, run);
+    jac_items.push_back(it);
+  }
+  p->n_fitems = int(fitems.size());
+  p->n_jac_items = int(jac_items.size());
+  p->n_cells = int(cells.size());
+  // buffer layout: [expanded partial blocks: cells, generic items | item costs (2 per item) | compact frame records]
+  const size_t n_cost_slots = 2 * size_t(std::max(std::max(p->n_items, p->n_items_all), p->n_fitems + p->n_jac_items));
+  const size_t comp_base = poff + n_cost_slots;
+  p->cell_rec_max = 1;
+  p->frame_lds_doubles = 0;
+  for (FrameItemDev& f : fitems) {
+    p->frame_lds_doubles = std::max(p->frame_lds_doubles, int(frame_lds(layouts[size_t(f.layout)])));
+    f.partial_off += int64_t(comp_base);
+    p->cell_rec_max = std::max(p->cell_rec_max, int(frame_rec(layouts[size_t(f.layout)])));
+  }
+  p->cell_chunk = std::max(1, int((56 * 1024 / sizeof(double)) / size_t(p->cell_rec_max)));
+  // no more LDS than the fullest cell needs: the cell kernel's workgroups should all be resident at once
+  p->max_cell_frames = 0;
+  for (const CellDev& c : cells) if (c.prim_off >= 0) p->max_cell_frames = std::max(p->max_cell_frames, c.frame_count);   // (camera cells; < 0: IMU cells)
+  p->cell_chunk = std::min(p->cell_chunk, std::max(1, p->max_cell_frames));
+  // per-layout pair table of the cell kernel: row-major upper triangle of the (c+1)×(c+1) block, each entry with the
+  // M_ext element it expands from (prim_of_col: the frame's column order)
+  {
+    std::vector<int> tab_off(layouts.size(), -1);
+    for (CellDev& c : cells) {
+      if (c.prim_off < 0) continue;   // row cell
+      const LayoutDev& L = layouts[size_t(c.layout)];
+      const SensorDev& S = t.sd[size_t(L.sensor)];
+      const PrimMap pm = prim_map(L, S);
+      const int n1 = L.ncols + 1;
+      if (tab_off[size_t(c.layout)] < 0) {
+        tab_off[size_t(c.layout)] = int(t.prim_tab.size());
+        for (int i = 0; i < n1; ++i)
+          for (int j = i; j < n1; ++j)
+            t.prim_tab.push_back(i | (j << 8) | ((prim_of_col(L, S, pm, i) * pm.PE + prim_of_col(L, S, pm, j)) << 16));
+      }
+      c.prim_off = tab_off[size_t(c.layout)]; c.pad0 = 0;
+      c.n1 = n1; c.PE = pm.PE;
+      c.src_off = c.frame_begin >= 0 ? fitems[size_t(c.frame_begin)].partial_off : 0;      // (no compact records with cell workgroups)
+    }
+    for (FrameItemDev& fi : fitems) {      // (copies of the cell's fields for the cell's workgroup: fuse_expand)
+      const CellDev& c = cells[size_t(fi.cell)];
+      fi.cell_frames = c.frame_count; fi.cell_prim_off = c.prim_off; fi.cell_partial_off = c.partial_off; fi.cell_src_off = c.src_off;
+    }
+  }
   p->partial_doubles = poff;
   if (poff + 2 * size_t(std::max(p->n_items, p->n_fitems + p->n_jac_items)) >= size_t(0x7fffffff))
     return p->set_error(CALICO_UNIMPLEMENTED, "problem too large for 32-bit gather indices");
   {
     // LDS staging of the generic Jacobian kernel: sized by the items that actually go through it
     int jc = 4, jr = 2;
-    for (const ItemDev& it : p->h_jac_items) {
+    for (const ItemDev& it : jac_items) {
       const LayoutDev& L = layouts[size_t(it.layout)];
       jc = std::max(jc, L.ncols + 1);
       jr = std::max(jr, p->sensors[size_t(L.sensor)].dim() * it.obs_count);
     }
-    (void)max_cols;
     // whole groups of sixteen columns and of four rows: stage B reads them without masks (eval_kernels.hip, stage_b_mfma;
     // the padding is cleared by the work item)
     p->lds_cols = (jc + 15) & ~15;
@@ -1172,27 +1170,43 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
   {
     const size_t stride = (size_t(p->lds_cols) * p->row_pad + 1) & ~size_t(1);   // even: the rows travel as 16-byte words
     row_store = (comp_base + comp_off) & 1;                                      // ... from an even offset
-    for (size_t i = 0; i < p->h_jac_items.size(); ++i) {
-      ItemDev& it = p->h_jac_items[i];
+    for (ItemDev& it : jac_items) {
       if (it.rows_off < 0) continue;
       it.rows_off = int64_t(comp_base + comp_off + row_store);
       row_store += stride;
     }
-    for (CellDev& c : p->h_cells)
-      if (c.prim_off == -1) c.src_off = p->h_jac_items[size_t(c.frame_begin)].rows_off;
+    for (CellDev& c : cells)
+      if (c.prim_off == -1) c.src_off = jac_items[size_t(c.frame_begin)].rows_off;
     p->row_cell_chunk = std::max(1, int((56 * 1024 / sizeof(double)) / std::max<size_t>(1, stride)));
     int most = 1;
-    for (const CellDev& c : p->h_cells) if (c.prim_off == -1) most = std::max(most, c.frame_count);
+    for (const CellDev& c : cells) if (c.prim_off == -1) most = std::max(most, c.frame_count);
     p->row_cell_chunk = std::min(p->row_cell_chunk, most);
   }
-  setup.section("sort + work items");
-  // ---- gather lists ----
+  t.partials_end = comp_base + comp_off + row_store;
+  // every work item / frame carries copies of its layout, its sensor and the offsets of its control points
+  auto fill = [&](auto& it) {
+    it.L = layouts[size_t(it.layout)];
+    it.S = t.sd[size_t(it.L.sensor)];
+    for (int i = 0; i < 8; ++i) it.ctrl_off[i] = (i < k && it.seg + i < p->n_cp) ? t.ctrl_off[size_t(it.seg + i)] : 0;
+  };
+  for (ItemDev& it : t.items) fill(it);
+  for (ItemDev& it : t.items_all) fill(it);
+  for (ItemDev& it : jac_items) fill(it);
+  for (FrameItemDev& it : fitems) fill(it);
+  return CALICO_OK;
+}
+
+// ---- gather lists ----
+int plan_gather(calico_problem* p, const PlanSwitches& sw, PlanTables& t) {
+  const int k = p->order, n_cp = p->n_cp, m = p->m, NS = 6 * n_cp;
+  const std::vector<CellDev>& cells = t.cells; const std::vector<ItemDev>& jac_items = t.jac_items;
   SolveArgs sa; sa.n_cp = n_cp; sa.k = k; sa.mc = m; sa.sep_s = p->sep_s; sa.sep_n = p->sep_n; sa.m = m + p->border_extra(); sa.debug = 0; sa.progress = nullptr;
   const size_t r_size = sa.r_size();
   if (r_size >= size_t(0x7fffffff)) return p->set_error(CALICO_UNIMPLEMENTED, "normal-equation buffer too large");
+  p->r_size = r_size;
   struct Pair { int dst, src; };
   std::vector<Pair> pairs;
-  const int n_cells = int(p->h_cells.size());
+  const int n_cells = int(cells.size());
   const int n_part = n_cells + p->n_jac_items;     // producers of expanded partial blocks
   // Lists built on the device: when every producer is a cell (camera frames' cells, IMU row cells) and the layouts are
   // few, the sources of the band, the border and the spline part of the right-hand side follow from the outputs' indices
@@ -1201,24 +1215,23 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
   // calibration part of the right-hand side (2 % of the outputs, sources in every segment) are listed here.
   // CALICO_GATHER_STRUCT=0: everything listed by the host (A/B switch, and the path of problems with free model points or
   // other spline orders' generic items).
-  bool gs_ok = sw.gather_struct && int(layouts.size()) * k <= 96 && int(layouts.size()) >= 1 && m >= 1 && n_cells > 0;
+  bool gs_ok = sw.gather_struct && int(t.layouts.size()) * k <= 96 && int(t.layouts.size()) >= 1 && m >= 1 && n_cells > 0;
   for (int itn = n_cells; gs_ok && itn < n_part; ++itn) {   // no block of its own, or one that is listed as a cell's (fuse_expand)
-    const int64_t ro = p->h_jac_items[size_t(itn - n_cells)].rows_off;
+    const int64_t ro = jac_items[size_t(itn - n_cells)].rows_off;
     gs_ok = ro >= 0 || ro == -2;
   }
   const int64_t gs_n_out = int64_t(NS) * m + int64_t(n_cp) * k * 36 + NS;
   gs_ok = gs_ok && gs_n_out * 96 < int64_t(0x7fffffff);
-  p->gs_lists_on_device = gs_ok;
-  std::vector<int> gs_tab;
-  GatherStruct gsd = {};
+  t.gs_ok = gs_ok; t.gs_n_out = gs_n_out;
+  std::vector<int>& gs_tab = t.gs_tab; GatherStruct& gsd = t.gsd;
   if (gs_ok) {
-    const int n_lay = int(layouts.size()), nsg = int(p->valid_knots.size()) - 1;
+    const int n_lay = int(t.layouts.size()), nsg = int(p->valid_knots.size()) - 1;
     gs_tab.assign(size_t(n_lay) * nsg + size_t(n_lay) * m + size_t(n_lay), -1);
-    for (const CellDev& c : p->h_cells) gs_tab[size_t(c.layout) * nsg + size_t(c.seg)] = int(c.partial_off);
+    for (const CellDev& c : cells) gs_tab[size_t(c.layout) * nsg + size_t(c.seg)] = int(c.partial_off);
     for (int l = 0; l < n_lay; ++l) {
-      const std::vector<int>& gmap = layout_gmap[size_t(l)];
+      const std::vector<int>& gmap = t.layout_gmap[size_t(l)];
       for (size_t q = 0; q < gmap.size(); ++q) gs_tab[size_t(n_lay) * nsg + size_t(l) * m + size_t(gmap[q] - NS)] = 6 * k + int(q);
-      gs_tab[size_t(n_lay) * nsg + size_t(n_lay) * m + size_t(l)] = layouts[size_t(l)].ncols + 1;
+      gs_tab[size_t(n_lay) * nsg + size_t(n_lay) * m + size_t(l)] = t.layouts[size_t(l)].ncols + 1;
     }
     gsd.n_lay = n_lay; gsd.nseg = nsg; gsd.n_cp = n_cp; gsd.k = k; gsd.m = m;
     {   // band blocks at distance d from the diagonal have (k - d) segments per layout: four lanes in the gather where that is <= 24 sources
@@ -1228,15 +1241,15 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     }
     gsd.off_g = sa.off_g(); gsd.off_B = sa.off_B(); gsd.off_E = sa.off_E();
   }
-  pairs.reserve(gs_ok ? size_t(n_part) * 256 : poff / 2 + 4 * size_t(p->n_items));
+  pairs.reserve(gs_ok ? size_t(n_part) * 256 : p->partial_doubles / 2 + 4 * size_t(p->n_items));
   for (int itn = 0; itn < n_part; ++itn) {
     const bool is_cell = itn < n_cells;
-    if (!is_cell && (p->h_jac_items[size_t(itn - n_cells)].rows_off >= 0 || p->h_jac_items[size_t(itn - n_cells)].rows_off == -2)) continue;   // its block is a cell's
-    const int it_layout = is_cell ? p->h_cells[size_t(itn)].layout : p->h_jac_items[size_t(itn - n_cells)].layout;
-    const int it_seg = is_cell ? p->h_cells[size_t(itn)].seg : p->h_jac_items[size_t(itn - n_cells)].seg;
-    const int64_t it_poff = is_cell ? p->h_cells[size_t(itn)].partial_off : p->h_jac_items[size_t(itn - n_cells)].partial_off;
-    const LayoutDev& L = layouts[size_t(it_layout)];
-    const std::vector<int>& gmap = layout_gmap[size_t(it_layout)];
+    if (!is_cell && (jac_items[size_t(itn - n_cells)].rows_off >= 0 || jac_items[size_t(itn - n_cells)].rows_off == -2)) continue;   // its block is a cell's
+    const int it_layout = is_cell ? cells[size_t(itn)].layout : jac_items[size_t(itn - n_cells)].layout;
+    const int it_seg = is_cell ? cells[size_t(itn)].seg : jac_items[size_t(itn - n_cells)].seg;
+    const int64_t it_poff = is_cell ? cells[size_t(itn)].partial_off : jac_items[size_t(itn - n_cells)].partial_off;
+    const LayoutDev& L = t.layouts[size_t(it_layout)];
+    const std::vector<int>& gmap = t.layout_gmap[size_t(it_layout)];
     const int nc = L.ncols, n1 = nc + 1;
     auto tan_of = [&](int c) { return c < 6 * k ? 6 * (it_seg + c / 6) + c % 6 : gmap[size_t(c - 6 * k)]; };
     for (int i = gs_ok ? 6 * k : 0; i < nc; ++i) {      // (structured gather: the spline rows have no lists)
@@ -1264,8 +1277,6 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
   // Group the pairs by output, keeping the order in which they were generated inside every group (the summation
   // order of the device's gather, hence its rounding): a counting sort over the outputs -- linear, where a comparison
   // sort of the ~10^6 pairs took most of the set-up time.
-  std::vector<int> out_thin, idx_thin, out_fat, idx_fat;
-  std::vector<int64_t> ptr_thin(1, 0), ptr_fat(1, 0);
   {
     std::vector<int64_t> start(r_size + 1, 0);
     for (const Pair& pr : pairs) ++start[size_t(pr.dst) + 1];
@@ -1278,7 +1289,7 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     // thin outputs: eight lanes, 6 sources per lane -- or 12 when the problem has outputs of 49..96 sources (many
     // layouts: their band and right-hand-side entries would each take a whole wave otherwise)
     int thin_cap = 48;
-    if (gs_ok) thin_cap = int(layouts.size()) * k <= 48 ? 48 : 96;
+    if (gs_ok) thin_cap = int(t.layouts.size()) * k <= 48 ? 48 : 96;
     else {
       size_t n_mid = 0;
       for (size_t d = 0; d < r_size; ++d) { const int64_t c = start[d + 1] - start[d]; if (c > 48 && c <= 96) ++n_mid; }
@@ -1290,62 +1301,23 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
       const int64_t c = start[d + 1] - start[d];
       if (gs_ok || c > thin_cap) n_fat_src += size_t(c); else n_thin_src += size_t(c);
     }
-    idx_thin.reserve(n_thin_src); idx_fat.reserve(n_fat_src);
+    t.idx_thin.reserve(n_thin_src); t.idx_fat.reserve(n_fat_src);
     for (size_t d = 0; d < r_size; ++d) {
       const int64_t q0 = start[d], q1 = start[d + 1];
       if (q1 == q0) continue;
       const bool fat = gs_ok || (q1 - q0) > thin_cap;        // (the device's lists are the thin ones: what the host lists goes to the waves)
-      std::vector<int>& out = fat ? out_fat : out_thin;
-      std::vector<int>& idx = fat ? idx_fat : idx_thin;
-      std::vector<int64_t>& ptr = fat ? ptr_fat : ptr_thin;
+      std::vector<int>& out = fat ? t.out_fat : t.out_thin;
+      std::vector<int>& idx = fat ? t.idx_fat : t.idx_thin;
+      std::vector<int64_t>& ptr = fat ? t.ptr_fat : t.ptr_thin;
       out.push_back(int(d));
       idx.insert(idx.end(), sorted_src.begin() + q0, sorted_src.begin() + q1);
       ptr.push_back(int64_t(idx.size()));
     }
   }
-  p->n_thin = int(out_thin.size()); p->n_fat = int(out_fat.size());
+  p->n_thin = int(t.out_thin.size()); p->n_fat = int(t.out_fat.size());
   p->n_thin8 = p->n_thin; p->n_thin4 = p->n_thin;
-  p->gather_owner_block = 0;
-  setup.section("gather lists");
-  // ---- upload of the structure ----
-  hipStream_t s = p->stream;
-  std::vector<int> ctrl_off(n_cp);
-  for (int i = 0; i < n_cp; ++i) ctrl_off[i] = p->blocks[p->ctrl[i]].amb_off;
-  {
-    // every work item / frame carries copies of its layout, its sensor and the offsets of its control points
-    auto fill = [&](auto& it) {
-      it.L = layouts[size_t(it.layout)];
-      it.S = sd[size_t(it.L.sensor)];
-      for (int i = 0; i < 8; ++i) it.ctrl_off[i] = (i < k && it.seg + i < n_cp) ? ctrl_off[size_t(it.seg + i)] : 0;
-    };
-    for (ItemDev& it : p->h_items) fill(it);
-    for (ItemDev& it : p->h_items_all) fill(it);
-    for (ItemDev& it : p->h_jac_items) fill(it);
-    for (FrameItemDev& it : p->h_fitems) fill(it);
-  }
-  HIP_TRY(p, p->d_knots.upload(p->knots, s)); HIP_TRY(p, p->d_basis.upload(p->basis, s));
-  HIP_TRY(p, p->d_ctrl_off.upload(ctrl_off, s));
-  HIP_TRY(p, p->d_stamp.upload(st, s)); HIP_TRY(p, p->d_point_off.upload(point_off, s));
-  HIP_TRY(p, p->d_sensors.upload(sd, s)); HIP_TRY(p, p->d_layouts.upload(layouts, s));
-  HIP_TRY(p, p->d_items.upload(p->h_items, s)); HIP_TRY(p, p->d_items_all.upload(p->h_items_all, s));
-  HIP_TRY(p, p->d_jac_items.upload(p->h_jac_items, s)); HIP_TRY(p, p->d_fitems.upload(p->h_fitems, s));
-  HIP_TRY(p, p->d_blocks.upload(p->h_blocks, s));
-  HIP_TRY(p, p->d_cp_active.upload(cp_active, s));
-  DevBuf<int> d_cnt;                    // (scratch of the device's list build; freed behind the synchronisation below)
-  DevBuf<long long> d_scan;
-  // a word of the partials nobody writes (allocated and cleared with them): what padded list entries point to. The lists
-  // hold 32-bit positions, so the whole partials buffer must be addressable by one -- checked for every kind of list
-  if (comp_base + comp_off + row_store + 2 >= size_t(0x7fffffff)) return p->set_error(CALICO_UNIMPLEMENTED, "problem too large for 32-bit gather indices");
-  const int zero_slot = int(comp_base + comp_off + row_store);
   if (gs_ok) {
-    HIP_TRY(p, p->d_gs_tab.upload(gs_tab, s));
-    gsd.tab = p->d_gs_tab.p;
-    const int per_out = int(layouts.size()) * k;      // (<= 96)
-    HIP_TRY(p, p->d_out_thin.alloc(size_t(gs_n_out))); HIP_TRY(p, p->d_ptr_thin.alloc(size_t(gs_n_out) + 1));
-    HIP_TRY(p, p->d_idx_thin.alloc(size_t(gs_n_out) * per_out)); HIP_TRY(p, d_cnt.alloc(size_t(gs_n_out)));
-    HIP_TRY(p, d_scan.alloc(size_t(gs_n_out) / 1024 + 2));      // block sums of the lists' prefix scan
-    launch_gather_lists(gsd, int(gs_n_out), d_cnt.p, p->d_out_thin.p, p->d_ptr_thin.p, p->d_idx_thin.p, zero_slot, d_scan.p, s);
-    p->n_thin = int(gs_n_out);
+    p->n_thin = int(gs_n_out);      // (the device's lists: one per output of the band, the border and the spline right-hand side)
     // the border's outputs (behind the right-hand side and the band) have one source per segment and layout that holds
     // their calibration column: at most k where every column belongs to ONE layout -- one lane each in the gather
     bool one_layout = k <= 8;
@@ -1359,43 +1331,84 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
     // band blocks at distance d from the diagonal have (k - d) segments per layout: four lanes where that is <= 24 sources
     const int d4 = gsd.d_split;
     p->n_thin8 = one_layout ? std::min(n_border0, NS + d4 * n_cp * 36) : p->n_thin;     // (the classes are ranges: [8 | 4 | 1])
-  } else {
-    HIP_TRY(p, p->d_out_thin.upload(out_thin, s)); HIP_TRY(p, p->d_idx_thin.upload(idx_thin, s));
-    HIP_TRY(p, p->d_ptr_thin.upload(ptr_thin, s));
   }
-  HIP_TRY(p, p->d_out_fat.upload(out_fat, s)); HIP_TRY(p, p->d_idx_fat.upload(idx_fat, s));
-  HIP_TRY(p, p->d_ptr_fat.upload(ptr_fat, s));
   // the thin outputs' lists at a fixed stride per lane class: the gather then needs no pointer load in front of its index
   // loads
   // Only for the device-built lists: their lengths are bounded by the structure (layouts x k <= thin_per_lane x 8 per output),
   // which is what the fixed stride relies on; host-built lists (plans the table cannot describe) keep the CSR form -- padding
   // each of their short lists to 48 / 96 slots would multiply the index memory, and nothing bounds their length.
   p->gather_fixed = p->n_thin > 0 && gs_ok;
+  // a word of the partials nobody writes (allocated and cleared with them): what padded list entries point to. The lists
+  // hold 32-bit positions, so the whole partials buffer must be addressable by one -- checked for every kind of list
+  if (t.partials_end + 2 >= size_t(0x7fffffff)) return p->set_error(CALICO_UNIMPLEMENTED, "problem too large for 32-bit gather indices");
+  p->partials_alloc = t.partials_end + 2;      // (+ the word that is always zero: the lists' zero_slot)
+  return CALICO_OK;
+}
+
+// ---- upload of the structure: the only stage that talks to the device ----
+int upload_plan(calico_problem* p, PlanTables& t) {
+  hipStream_t s = p->stream;
+  HIP_TRY(p, p->d_knots.upload(p->knots, s)); HIP_TRY(p, p->d_basis.upload(p->basis, s));
+  HIP_TRY(p, p->d_ctrl_off.upload(t.ctrl_off, s));
+  HIP_TRY(p, p->d_stamp.upload(t.st, s)); HIP_TRY(p, p->d_point_off.upload(t.point_off, s));
+  HIP_TRY(p, p->d_sensors.upload(t.sd, s)); HIP_TRY(p, p->d_layouts.upload(t.layouts, s));
+  HIP_TRY(p, p->d_items.upload(t.items, s)); HIP_TRY(p, p->d_items_all.upload(t.items_all, s));
+  HIP_TRY(p, p->d_jac_items.upload(t.jac_items, s)); HIP_TRY(p, p->d_fitems.upload(t.fitems, s));
+  HIP_TRY(p, p->d_blocks.upload(p->h_blocks, s));
+  HIP_TRY(p, p->d_cp_active.upload(t.cp_active, s));
+  DevBuf<int> d_cnt;                    // (scratch of the device's list build; freed behind the synchronisation below)
+  DevBuf<long long> d_scan;
+  const int zero_slot = int(t.partials_end);
+  if (t.gs_ok) {
+    HIP_TRY(p, p->d_gs_tab.upload(t.gs_tab, s));
+    t.gsd.tab = p->d_gs_tab.p;
+    const size_t n_out = size_t(t.gs_n_out), per_out = t.layouts.size() * size_t(p->order);      // (<= 96)
+    HIP_TRY(p, p->d_out_thin.alloc(n_out)); HIP_TRY(p, p->d_ptr_thin.alloc(n_out + 1));
+    HIP_TRY(p, p->d_idx_thin.alloc(n_out * per_out)); HIP_TRY(p, d_cnt.alloc(n_out));
+    HIP_TRY(p, d_scan.alloc(n_out / 1024 + 2));      // block sums of the lists' prefix scan
+    launch_gather_lists(t.gsd, int(n_out), d_cnt.p, p->d_out_thin.p, p->d_ptr_thin.p, p->d_idx_thin.p, zero_slot, d_scan.p, s);
+  } else {
+    HIP_TRY(p, p->d_out_thin.upload(t.out_thin, s)); HIP_TRY(p, p->d_idx_thin.upload(t.idx_thin, s));
+    HIP_TRY(p, p->d_ptr_thin.upload(t.ptr_thin, s));
+  }
+  HIP_TRY(p, p->d_out_fat.upload(t.out_fat, s)); HIP_TRY(p, p->d_idx_fat.upload(t.idx_fat, s));
+  HIP_TRY(p, p->d_ptr_fat.upload(t.ptr_fat, s));
   if (p->gather_fixed) {
     HIP_TRY(p, p->d_idx_fixed.alloc(gather_fixed_entries(p->n_thin, p->n_thin8, p->n_thin4, p->thin_per_lane) + 8));
     launch_gather_pack_fixed(p->d_ptr_thin.p, p->d_idx_thin.p, p->n_thin, p->n_thin8, p->n_thin4, p->thin_per_lane, zero_slot, p->d_idx_fixed.p, s);
   }
-  HIP_TRY(p, p->d_cells.upload(p->h_cells, s)); HIP_TRY(p, p->d_prim_tab.upload(prim_tab, s));
-  p->partials_alloc = comp_base + comp_off + row_store + 2;      // (+ the word that is always zero, see zero_slot)
-  p->r_size = r_size;
-  p->speculative = sw.speculative;
-  {
-    sa = make_solve_args(p);
-    if (band_cholesky_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "spline order too high for the banded factorisation window");
-    p->dense_in_lds = reduced_solve_lds_bytes(sa) <= kMaxLds - 1024;
-    if (band_backsolve_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "trajectory too long for the back-substitution window");
-  }
+  HIP_TRY(p, p->d_cells.upload(t.cells, s)); HIP_TRY(p, p->d_prim_tab.upload(t.prim_tab, s));
   if (p->use_bcr) {
-    HIP_TRY(p, p->d_bnodes.upload(p->h_bcr_nodes, s)); HIP_TRY(p, p->d_bkeep.upload(p->h_bcr_keep, s));
-    // (a member, not a local: the asynchronous upload reads it until the synchronisation below)
-    p->h_cp_block.assign(size_t(n_cp), -1);
-    for (size_t bi = 0; bi < p->h_blocks.size(); ++bi)
-      if (p->h_blocks[bi].tan_off < NS) p->h_cp_block[size_t(p->h_blocks[bi].tan_off / 6)] = int(bi);
-    HIP_TRY(p, p->d_cp_block.upload(p->h_cp_block, s));
-    if (bcr_level_lds_bytes() > kMaxLds || bcr_back_lds_bytes(p->bcr_q_max, p->bcr_m1p) > kMaxLds)
-      return p->set_error(CALICO_UNIMPLEMENTED, "tree solver workspace exceeds the LDS");
+    HIP_TRY(p, p->d_bnodes.upload(p->h_bcr_nodes, s)); HIP_TRY(p, p->d_bkeep.upload(t.bcr_keep, s));
+    HIP_TRY(p, p->d_cp_block.upload(t.cp_block, s));
   }
-  HIP_TRY(p, hipStreamSynchronize(s));      // the uploads read locals of this function
+  HIP_TRY(p, hipStreamSynchronize(s));      // the uploads read the caller's PlanTables
+  return CALICO_OK;
+}
+
+int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
+  PlanTables t;
+  int rc = plan_blocks(p, sw, t);
+  if (rc != CALICO_OK) return rc;
+  setup.section("blocks / tangent order");
+  plan_layouts(p, t);
+  setup.section("layouts");
+  plan_items(p, t);
+  setup.section("sort + work items");
+  rc = plan_route(p, sw, t);
+  if (rc != CALICO_OK) return rc;
+  setup.section("evaluation route");
+  rc = plan_gather(p, sw, t);
+  if (rc != CALICO_OK) return rc;
+  setup.section("gather lists");
+  const SolveArgs sa = make_solve_args(p);       // (the solvers' LDS windows)
+  if (band_cholesky_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "spline order too high for the banded factorisation window");
+  p->dense_in_lds = reduced_solve_lds_bytes(sa) <= kMaxLds - 1024;
+  if (band_backsolve_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "trajectory too long for the back-substitution window");
+  if (p->use_bcr && (bcr_level_lds_bytes() > kMaxLds || bcr_back_lds_bytes(p->bcr_q_max, p->bcr_m1p) > kMaxLds))
+    return p->set_error(CALICO_UNIMPLEMENTED, "tree solver workspace exceeds the LDS");
+  rc = upload_plan(p, t);
+  if (rc != CALICO_OK) return rc;
   setup.section("structure uploads");
   return CALICO_OK;
 }
@@ -1819,15 +1832,9 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
   // (a PyTorch probe, a hipMalloc fallback) is not this solve's --, and asked per launch: hipGetLastError() reports the last
   // call only on some runtimes, so a refused first launch must not hide behind a second one that went through.
   (void)hipGetLastError();
-  if (p->order == 6 && p->n_fitems > 0) {
-    launch_eval_jacobian(ea, p->stream);                  // camera frames (item-cost slots [0, n_fitems)) + everything else
-    HIP_TRY(p, hipGetLastError());
-  } else {
-    launch_eval_frames(ea, p->stream);
-    HIP_TRY(p, hipGetLastError());
-    launch_eval(ea, true, p->stream);
-    HIP_TRY(p, hipGetLastError());
-  }
+  if (end_hint_available(p)) launch_eval_jacobian(ea, p->stream);   // camera frames (item-cost slots [0, n_fitems)) + everything else
+  else launch_eval(ea, true, p->stream);                             // (no frames: they exist for spline order 6 only)
+  HIP_TRY(p, hipGetLastError());
   p->timer.end(p->stream);
   p->timer.begin(1, p->stream);
   // the host knows which buffer is filled: multi-rank runs either read the state back every iteration or (batched)
@@ -2412,7 +2419,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
       ControlTail tail;
       tail.enabled = 1; tail.n_amb = p->n_amb; tail.log_cap = kLogCap; tail.seq = ++enq; tail.o = o; tail.x = p->d_x.p;
       tail.x_cand = p->d_xc.p; tail.log = p->d_log.p; tail.Rbase = p->d_R.p; tail.r_stride = p->r_size;
-      tail.progress = p->d_progress; tail.owner_block = p->gather_owner_block;
+      tail.progress = p->d_progress;
       rc = enqueue_jacobian_eval(p, p->d_state.p, 0, p->d_xc.p, true, &tail, predict_end);
       if (rc != CALICO_OK) return rc;
     }
@@ -2595,14 +2602,7 @@ int32_t calico_debug_plan_info(calico_problem* p, int32_t* out, int32_t n) {
   if (!p || !out || n < 0 || n > 9) return CALICO_INVALID_ARGUMENT;
   int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
-  int max_frames = 0, max_items = 0, run = 0, prev_layout = -1, prev_seg = -1;
-  for (const CellDev& c : p->h_cells) if (c.prim_off >= 0) max_frames = std::max(max_frames, c.frame_count);   // (camera cells; < 0: IMU cells)
-  for (const ItemDev& it : p->h_jac_items) {
-    run = (it.layout == prev_layout && it.seg == prev_seg) ? run + 1 : 1;
-    prev_layout = it.layout; prev_seg = it.seg;
-    max_items = std::max(max_items, run);
-  }
-  const int v[9] = {p->fuse_expand ? 1 : 0, p->n_fitems, p->n_jac_items, int(p->h_cells.size()), max_frames, max_items,
+  const int v[9] = {p->fuse_expand ? 1 : 0, p->n_fitems, p->n_jac_items, p->n_cells, p->max_cell_frames, p->max_item_run,
                     p->use_bcr ? 1 : 0, p->m, p->bcr_all_active ? 1 : 0};
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return CALICO_OK;
@@ -3045,13 +3045,10 @@ int32_t calico_comm_info(calico_problem* p, int32_t* rank_out, int32_t* world_ou
   }
   const int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
-  int64_t local = 0, total = 0;
-  for (const ItemDev& it : p->h_items) local += it.obs_count;
-  for (const ItemDev& it : p->h_items_all) total += it.obs_count;
   if (rank_out) *rank_out = p->rank;
   if (world_out) *world_out = world;
-  if (local_blocks_out) *local_blocks_out = local;
-  if (total_blocks_out) *total_blocks_out = total;
+  if (local_blocks_out) *local_blocks_out = p->n_obs_local;
+  if (total_blocks_out) *total_blocks_out = p->n_obs;       // (the work items of all ranks cover every residual block once)
   return CALICO_OK;
 }
 

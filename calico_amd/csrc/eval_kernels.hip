@@ -812,47 +812,7 @@ DEV void eval_items_body(const EvalArgs& a, const int item_id, double* lds, Item
 constexpr int kMaxPrim = 32;   // 6 + 11 + 3 + 3 + 3 + 3 + r = 30, padded to two 16-wide MFMA tiles
 constexpr int kFramePad = 132; // row stride of a staged prim column: ≡ 4 (mod 32) spreads the MFMA operand read over all banks
 constexpr int kMaxLocalCols = 96;
-
-// Prim columns of a camera layout: [pose 6 | intrinsics | q | t | body q | body t | residual]; the latency column is
-// the extra row/column PT of M_ext.
-struct PrimMap { int intr, q, t, bq, bt, r, P1, PT, PE; };
-DEV PrimMap prim_map(const LayoutDev& L, const SensorDev& S) {
-  PrimMap m;
-  int pc = 6;
-  m.intr = L.c_intr >= 0 ? pc : -1; if (L.c_intr >= 0) pc += S.K;
-  m.q = L.c_q >= 0 ? pc : -1; if (L.c_q >= 0) pc += 3;
-  m.t = L.c_t >= 0 ? pc : -1; if (L.c_t >= 0) pc += 3;
-  m.bq = L.c_bq >= 0 ? pc : -1; if (L.c_bq >= 0) pc += 3;
-  m.bt = L.c_bt >= 0 ? pc : -1; if (L.c_bt >= 0) pc += 3;
-  m.r = pc;
-  m.P1 = pc + 1;                 // prim columns incl. residual
-  m.PT = m.P1;                   // index of the latency row / column of M_ext (right behind the prim columns)
-  m.PE = m.PT + 1;               // M_ext = [[M, Qᵀ], [Q, qq]]
-  return m;
-}
-// Small prim columns (what is staged): [Y 3 | T 3 | Z 3 (body rotation free) | intrinsics | residual]
-struct SmallMap { int z, k, r, P, PT; };
-DEV SmallMap small_map(const LayoutDev& L, const SensorDev& S) {
-  SmallMap m;
-  int pc = 6;
-  m.z = L.c_bq >= 0 ? pc : -1; if (L.c_bq >= 0) pc += 3;
-  m.k = L.c_intr >= 0 ? pc : -1; if (L.c_intr >= 0) pc += S.K;
-  m.r = pc;
-  m.P = pc + 1;
-  m.PT = (m.P + 15) & ~15;
-  return m;
-}
-// prim column of local column lc of the layout (spline columns: the pose component)
-DEV int prim_of_col(const LayoutDev& L, const SensorDev& S, const PrimMap& pm, int lc) {
-  if (lc < 36) return lc % 6;
-  if (lc == L.c_lat) return pm.PT;
-  if (lc == L.ncols) return pm.r;
-  if (L.c_intr >= 0 && lc >= L.c_intr && lc < L.c_intr + S.K) return pm.intr + (lc - L.c_intr);
-  if (L.c_q >= 0 && lc >= L.c_q && lc < L.c_q + 3) return pm.q + (lc - L.c_q);
-  if (L.c_t >= 0 && lc >= L.c_t && lc < L.c_t + 3) return pm.t + (lc - L.c_t);
-  if (L.c_bq >= 0 && lc >= L.c_bq && lc < L.c_bq + 3) return pm.bq + (lc - L.c_bq);
-  return pm.bt + (lc - L.c_bt);
-}
+// (the prim and small prim columns of a layout: prim_map / small_map, problem_dev.hpp -- the planner shares them)
 
 template <int MODEL>
 DEV bool frame_camera_block(const SensorDev& S, const double* intr, const M3& R_rc, const M3& R_rw, const M3& R_wm, V3 t_rc, V3 t_wm,
@@ -1197,11 +1157,6 @@ template <bool JAC, int KT>
 __global__ __launch_bounds__(64) void eval_items_kernel(EvalArgs a) {
   extern __shared__ double lds[];
   eval_items_body<JAC, KT>(a, blockIdx.x, lds);
-}
-
-__global__ __launch_bounds__(64) void eval_frames_kernel(EvalArgs a) {
-  extern __shared__ double lds[];
-  eval_frames_body(a, blockIdx.x, lds);
 }
 
 // Whole Jacobian pass in one launch (spline order 6): the generic items (IMU cells; they are few and each is a long
@@ -1625,11 +1580,6 @@ size_t frame_lds_bytes() { return frame_lds_doubles(25, 31, kMaxLocalCols) * siz
 static size_t frame_launch_bytes(const EvalArgs& a) {
   return a.frame_lds_doubles > 0 ? size_t(a.frame_lds_doubles) * sizeof(double) : frame_lds_bytes();
 }
-void launch_eval_frames(const EvalArgs& a, hipStream_t stream) {
-  if (a.n_fitems == 0) return;
-  hipLaunchKernelGGL(eval_frames_kernel, dim3(a.n_fitems), dim3(64), frame_launch_bytes(a), stream, a);
-}
-
 // items (a.items / a.n_items, cost slots from a.cost_index_base) and frames (a.fitems / a.n_fitems) together
 void launch_eval_jacobian(const EvalArgs& a, hipStream_t stream) {
   if (a.n_items + a.n_fitems == 0) return;
@@ -1658,10 +1608,7 @@ void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream) {
 }
 
 hipError_t configure_eval_kernels(size_t max_lds_bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_frames_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(frame_lds_bytes()));
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&expand_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&expand_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(kCellsMaxLds));
   if (e != hipSuccess) return e;

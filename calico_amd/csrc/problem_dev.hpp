@@ -237,13 +237,14 @@ struct ControlTail {
   const double* Rbase;
   size_t r_stride;
   int* progress;
-  int owner_block;   // workgroup that produces outputs 0 and 1
 };
 
 #if defined(__HIPCC__)
 #define CAL_HD __host__ __device__
+#define CAL_HDI __host__ __device__ __forceinline__
 #else
 #define CAL_HD
+#define CAL_HDI inline
 #endif
 // A cell's / work item's partial block [J r]^T[J r] is its UPPER TRIANGLE, packed row-major (round 5; a full n1 x n1 square
 // with only the upper triangle written before): entry (i, j), i <= j, at tri_off(i, j, n1); tri_size(n1) entries per block.
@@ -251,6 +252,48 @@ struct ControlTail {
 // the trajectory (59 MB over all XCDs as squares) no longer fitted its L2.
 CAL_HD inline int tri_off(int i, int j, int n1) { return i * n1 - ((i * (i - 1)) >> 1) + (j - i); }
 CAL_HD inline int tri_size(int n1) { return (n1 * (n1 + 1)) >> 1; }
+
+// Prim columns of a camera frame (eval_kernels.hip, eval_frames_body): [pose 6 | intrinsics | q | t | body q | body t |
+// residual]; the latency column is the extra row/column PT of M_ext. The planner sizes the frames' records and LDS and
+// builds the cell kernel's pair table from these same maps.
+struct PrimMap { int intr, q, t, bq, bt, r, P1, PT, PE; };
+CAL_HDI PrimMap prim_map(const LayoutDev& L, const SensorDev& S) {
+  PrimMap m;
+  int pc = 6;
+  m.intr = L.c_intr >= 0 ? pc : -1; if (L.c_intr >= 0) pc += S.K;
+  m.q = L.c_q >= 0 ? pc : -1; if (L.c_q >= 0) pc += 3;
+  m.t = L.c_t >= 0 ? pc : -1; if (L.c_t >= 0) pc += 3;
+  m.bq = L.c_bq >= 0 ? pc : -1; if (L.c_bq >= 0) pc += 3;
+  m.bt = L.c_bt >= 0 ? pc : -1; if (L.c_bt >= 0) pc += 3;
+  m.r = pc;
+  m.P1 = pc + 1;                 // prim columns incl. residual
+  m.PT = m.P1;                   // index of the latency row / column of M_ext (right behind the prim columns)
+  m.PE = m.PT + 1;               // M_ext = [[M, Qᵀ], [Q, qq]]
+  return m;
+}
+// Small prim columns (what is staged): [Y 3 | T 3 | Z 3 (body rotation free) | intrinsics | residual]
+struct SmallMap { int z, k, r, P, PT; };
+CAL_HDI SmallMap small_map(const LayoutDev& L, const SensorDev& S) {
+  SmallMap m;
+  int pc = 6;
+  m.z = L.c_bq >= 0 ? pc : -1; if (L.c_bq >= 0) pc += 3;
+  m.k = L.c_intr >= 0 ? pc : -1; if (L.c_intr >= 0) pc += S.K;
+  m.r = pc;
+  m.P = pc + 1;
+  m.PT = (m.P + 15) & ~15;
+  return m;
+}
+// prim column of local column lc of the layout (spline columns: the pose component)
+CAL_HDI int prim_of_col(const LayoutDev& L, const SensorDev& S, const PrimMap& pm, int lc) {
+  if (lc < 36) return lc % 6;
+  if (lc == L.c_lat) return pm.PT;
+  if (lc == L.ncols) return pm.r;
+  if (L.c_intr >= 0 && lc >= L.c_intr && lc < L.c_intr + S.K) return pm.intr + (lc - L.c_intr);
+  if (L.c_q >= 0 && lc >= L.c_q && lc < L.c_q + 3) return pm.q + (lc - L.c_q);
+  if (L.c_t >= 0 && lc >= L.c_t && lc < L.c_t + 3) return pm.t + (lc - L.c_t);
+  if (L.c_bq >= 0 && lc >= L.c_bq && lc < L.c_bq + 3) return pm.bq + (lc - L.c_bq);
+  return pm.bt + (lc - L.c_bt);
+}
 
 // Arguments of the linear-solve kernels. The reduce buffer R is laid out as
 // [cost | invalid | g(NT) | band blocks B(n_cp,k,6,6) | border E(6n_cp,m) | corner C(m,m)].
