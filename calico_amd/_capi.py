@@ -72,7 +72,7 @@ class Summary(C.Structure):
 
 class CovarianceOptions(C.Structure):
     """calico_covariance_options."""
-    _fields_ = [("min_relative_pivot", C.c_double), ("reserved", C.c_int32 * 6)]
+    _fields_ = [("min_relative_pivot", C.c_double), ("control_points", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class Iteration(C.Structure):
@@ -128,6 +128,7 @@ ABI_SYMBOLS = [
     "problem_set_outlier_mask", "mark_outliers", "fit_spline", "residual_heatmap",
     "comm_get_unique_id", "comm_init_rccl", "comm_info", "problem_finalize", "plan_cache_stats", "plan_cache_clear",
     "default_covariance_options", "covariance_compute", "covariance_info", "covariance_get_dense", "covariance_get_block",
+    "covariance_trajectory", "covariance_trajectory_info",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table"]
@@ -191,6 +192,8 @@ class CApi:
             g("covariance_info", C.c_int32, [P, I, I, D])
             g("covariance_get_dense", C.c_int32, [P, D])
             g("covariance_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
+            g("covariance_trajectory", C.c_int32, [P, C.c_int64, D, D])
+            g("covariance_trajectory_info", C.c_int32, [P, I, I, D])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
             g("debug_plan_info", C.c_int32, [P, I, C.c_int32])
@@ -401,12 +404,14 @@ class Problem:
         self._check(self.api.evaluate(self.h, C.byref(cost), _dp(g), _dp(H) if want_jtj else None))
         return cost.value, g, H
 
-    def covariance_compute(self, min_relative_pivot=None):
-        """calico_covariance_compute; returns (dim, n_unobserved, min_relative_pivot). Raises CalicoError on failure."""
+    def covariance_compute(self, min_relative_pivot=None, control_points=False):
+        """calico_covariance_compute; returns (dim, n_unobserved, min_relative_pivot). Raises CalicoError on failure.
+        control_points=True: also the trajectory's blocks (covariance_block of control points, covariance_trajectory)."""
         o = CovarianceOptions()
         self.api.default_covariance_options(C.byref(o))
         if min_relative_pivot is not None:
             o.min_relative_pivot = float(min_relative_pivot)
+        o.control_points = int(bool(control_points))
         self._check(self.api.covariance_compute(self.h, C.byref(o)))
         return self.covariance_info()
 
@@ -432,9 +437,23 @@ class Problem:
                 res[(a, b)] = self.covariance_block(a, b, tangent)
         return res
 
+    def covariance_trajectory_info(self):
+        """(n_cp, order, min_relative_pivot_band) of the last compute with control_points=True."""
+        n, k, piv = C.c_int32(0), C.c_int32(0), C.c_double(0)
+        self._check(self.api.covariance_trajectory_info(self.h, C.byref(n), C.byref(k), C.byref(piv)))
+        return n.value, k.value, piv.value
+
+    def covariance_trajectory(self, stamps):
+        """Covariance of the spline's 6-vector at each stamp: (n, 6, 6)."""
+        t = _f64(np.atleast_1d(stamps)).ravel()
+        out = np.zeros((len(t), 6, 6))
+        self._check(self.api.covariance_trajectory(self.h, len(t), _dp(t), _dp(out)))
+        return out
+
     def covariance_block(self, block_a, block_b, tangent=False, sizes=None):
         """Block (block_a, block_b) of the last computed Σ. `sizes`: (rows, cols) of the requested form; by default taken
-        from the blocks added through this object (ambient size, or 3 for a 4-vector in tangent form)."""
+        from the blocks added through this object (ambient size, or 3 for a 4-vector in tangent form; 6 for a control
+        point)."""
         if sizes is None:
             def sz(b):
                 n = self._sizes[b]

@@ -110,6 +110,11 @@ bool covariance_in_lds(int n);
 void launch_covariance(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* out,
                        double* info, hipStream_t s);
 hipError_t configure_covariance_kernel();
+int cp_covariance_max_order();
+void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s);
+void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s);
+void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
+                      double* out, hipStream_t s);
 
 }  // namespace cal
 
@@ -534,9 +539,17 @@ struct calico_problem : PlanHost, PlanDev, Workspace {
     double min_relative_pivot = 0.0;
     std::vector<double> sigma;       // dim x dim, border tangent order
     // per block id at the time of the compute: offset of its tangent rows in sigma (-1: not in Σ -- constant or unused --,
-    // -2: control point), ambient size, manifold, value (the quaternion lift is taken at the values Σ was computed at)
-    struct Blk { int off, size, manifold; std::vector<double> v; };
+    // -2: control point), ambient size, manifold, value (the quaternion lift is taken at the values Σ was computed at), the
+    // control point's index (-1: not one)
+    struct Blk { int off, size, manifold; std::vector<double> v; int cp; };
     std::vector<Blk> blocks;
+    // control_points: the control points' blocks (cov_kernels.hip, CpCovArgs), their host copies and the stamp buffers
+    DevBuf<double> cp_dq, cp_L, cp_Li, cp_M, cp_X, cp_W, cp_Z, cp_sae, cp_band, cp_info, st_t, st_out;
+    DevBuf<int> st_seg;
+    bool has_cp = false, cp_requested = false;     // (requested: control_points = 1, whether or not the problem has a spline)
+    int n_cp = 0, order = 0;
+    double min_relative_pivot_band = 0.0;
+    std::vector<double> sae, band;     // Σ_AE (6 n_cp x dim), Σ_AA's band ([n_cp][order][36], block (J + d, J) row-major)
   } cov;
 
   int set_error(int code, const std::string& msg) { error = msg; return code; }
@@ -2837,11 +2850,28 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
   HIP_TRY(p, hipSetDevice(p->device));
   calico_problem::Covariance& cv = p->cov;
   cv.valid = false;
+  cv.has_cp = false;
+  cv.cp_requested = opt->control_points != 0;
   SolveArgs sa = make_solve_args(p);
   const int mc = p->m, m = sa.m;
   if (m > covariance_max_dim())
     return p->set_error(CALICO_UNIMPLEMENTED, "covariance: reduced system of " + std::to_string(m) + " rows (at most " +
                                                   std::to_string(covariance_max_dim()) + ")");
+  const bool want_cp = opt->control_points != 0 && p->n_cp > 0;
+  if (want_cp && p->order > cp_covariance_max_order())
+    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: the trajectory's control-point blocks are computed for spline orders up to " +
+                                                  std::to_string(cp_covariance_max_order()));
+  CpCovArgs ca = {};
+  if (want_cp) {
+    const int n_cp = p->n_cp, k = p->order;
+    const size_t nb = size_t(n_cp) * k * 36, ne = size_t(6) * n_cp * mc;
+    HIP_TRY(p, cv.cp_dq.alloc(6 * size_t(n_cp))); HIP_TRY(p, cv.cp_L.alloc(nb)); HIP_TRY(p, cv.cp_Li.alloc(size_t(n_cp) * 36));
+    HIP_TRY(p, cv.cp_M.alloc(nb)); HIP_TRY(p, cv.cp_X.alloc(ne)); HIP_TRY(p, cv.cp_W.alloc(ne)); HIP_TRY(p, cv.cp_Z.alloc(nb));
+    HIP_TRY(p, cv.cp_sae.alloc(ne)); HIP_TRY(p, cv.cp_band.alloc(nb)); HIP_TRY(p, cv.cp_info.alloc(2));
+    ca.R = sa.R; ca.off_B = sa.off_B(); ca.off_E = sa.off_E(); ca.n_cp = n_cp; ca.k = k; ca.mc = mc;
+    ca.dq = cv.cp_dq.p; ca.L = cv.cp_L.p; ca.Li = cv.cp_Li.p; ca.M = cv.cp_M.p; ca.X = cv.cp_X.p; ca.W = cv.cp_W.p; ca.Z = cv.cp_Z.p;
+    ca.sae = cv.cp_sae.p; ca.band = cv.cp_band.p; ca.info = cv.cp_info.p;
+  }
   const int NT = sa.NT(), ny = NT + p->border_extra();
   // (the same sizes as the workspace's buffers they stand in for: prepare_workspace)
   HIP_TRY(p, cv.st.alloc(1)); HIP_TRY(p, cv.scale.alloc(2 * size_t(NT))); HIP_TRY(p, cv.dadd.alloc(size_t(NT)));
@@ -2871,10 +2901,19 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
   LmOptionsDev o = {};
   o.min_lm_diagonal = 1e-6; o.max_lm_diagonal = 1e32;
   (void)hipGetLastError();
+  if (want_cp) {      // (reads the band and E of R as the evaluation left them: ahead of the reduction)
+    launch_cp_covariance_band(ca, s);
+    HIP_TRY(p, hipGetLastError());
+  }
   if (mc > 0) {
     enqueue_linear_solve(p, sa, o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
     HIP_TRY(p, hipGetLastError());
     launch_covariance(sa.Spart, reduced_schur_slices(sa), m, mc, sa.R + sa.off_C(), cv.st.p, cv.work.p, cv.out.p, cv.info.p, s);
+    HIP_TRY(p, hipGetLastError());
+  }
+  if (want_cp) {
+    ca.sigma = cv.out.p;
+    launch_cp_covariance_finish(ca, s);
     HIP_TRY(p, hipGetLastError());
   }
   double info[4] = {1.0, 0.0, 0.0, 0.0};
@@ -2884,6 +2923,14 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
   if (mc > 0) {
     HIP_TRY(p, hipMemcpyAsync(info, cv.info.p, sizeof(info), hipMemcpyDeviceToHost, s));
     HIP_TRY(p, hipMemcpyAsync(cv.sigma.data(), cv.out.p, cv.sigma.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  double cp_info[2] = {1.0, 0.0};
+  cv.sae.clear(); cv.band.clear();
+  if (want_cp) {
+    cv.sae.resize(size_t(6) * p->n_cp * mc); cv.band.resize(size_t(p->n_cp) * p->order * 36);
+    HIP_TRY(p, hipMemcpyAsync(cp_info, cv.cp_info.p, sizeof(cp_info), hipMemcpyDeviceToHost, s));
+    if (!cv.sae.empty()) HIP_TRY(p, hipMemcpyAsync(cv.sae.data(), cv.cp_sae.p, cv.sae.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(cv.band.data(), cv.cp_band.p, cv.band.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(p, hipStreamSynchronize(s));
   if (R01[1] > 0.0) return p->set_error(CALICO_FAILED_PRECONDITION, "covariance: the residual evaluation failed at the current parameter values");
@@ -2899,12 +2946,29 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
                   "or a parameter the data do not determine", info[0], opt->min_relative_pivot);
     return p->set_error(CALICO_FAILED_PRECONDITION, msg);
   }
+  if (want_cp) {
+    const int cpf = int(cp_info[1]);
+    bool finite = true;
+    for (double v : cv.sae) finite = finite && std::isfinite(v);
+    for (double v : cv.band) finite = finite && std::isfinite(v);
+    if ((cpf & 1) || !finite)
+      return p->set_error(CALICO_FAILED_PRECONDITION, "covariance: the trajectory's control-point block of JᵀJ is not finite");
+    if ((cpf & 2) || cp_info[0] < opt->min_relative_pivot) {
+      char msg[256];
+      std::snprintf(msg, sizeof(msg), "covariance: the trajectory's control-point band of JᵀJ is rank deficient (minimum relative pivot %.3e, "
+                    "threshold %.3e): the data do not determine the trajectory", cp_info[0], opt->min_relative_pivot);
+      return p->set_error(CALICO_FAILED_PRECONDITION, msg);
+    }
+    cv.n_cp = p->n_cp; cv.order = p->order; cv.min_relative_pivot_band = cp_info[0];
+  }
   cv.blocks.resize(p->blocks.size());
   for (size_t i = 0; i < p->blocks.size(); ++i) {
     const HBlock& h = p->blocks[i];
     const bool in = !h.constant && h.used;
-    cv.blocks[i] = {in ? (h.tan < 6 * p->n_cp ? -2 : h.tan - 6 * p->n_cp) : -1, h.size, h.manifold, h.v};
+    const bool is_cp = h.tan >= 0 && h.tan < 6 * p->n_cp;
+    cv.blocks[i] = {in ? (is_cp ? -2 : h.tan - 6 * p->n_cp) : -1, h.size, h.manifold, h.v, is_cp ? h.tan / 6 : -1};
   }
+  cv.has_cp = want_cp;
   cv.valid = true;
   return CALICO_OK;
 }
@@ -2943,18 +3007,37 @@ int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t 
     return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
   const calico_problem::Covariance::Blk& A = p->cov.blocks[size_t(block_a)];
   const calico_problem::Covariance::Blk& B = p->cov.blocks[size_t(block_b)];
-  if (A.off == -2 || B.off == -2)
-    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point blocks are not supported (their blocks need a selected inversion of the band)");
+  const calico_problem::Covariance& cv = p->cov;
+  if ((A.off == -2 || B.off == -2) && !cv.has_cp)
+    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point blocks are not computed (calico_covariance_options.control_points = 0)");
+  if (A.off == -2 && B.off == -2 && std::abs(A.cp - B.cp) >= cv.order)
+    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point pairs are computed only within the spline's support (control "
+                                              "points less than the spline order apart)");
   const bool qa = A.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION, qb = B.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION;
   const int ta = qa ? 3 : A.size, tb = qb ? 3 : B.size;
   const int ra = tangent ? ta : A.size, rb = tangent ? tb : B.size;
   std::fill(out, out + size_t(ra) * rb, 0.0);
-  if (A.off < 0 || B.off < 0) return CALICO_OK;      // constant / unused blocks: zeros (Ceres: constant)
-  const int oa = A.off, ob = B.off, dim = p->cov.dim;
-  if (oa + ta > dim || ob + tb > dim) return p->set_error(CALICO_INTERNAL, "covariance: block layout out of range");
+  if (A.off == -1 || B.off == -1) return CALICO_OK;      // constant / unused blocks: zeros (Ceres: constant)
+  const int oa = A.off, ob = B.off, dim = cv.dim;
+  // (a border offset must leave room for its block; a control point (offset -2) must be one of the computed ones)
+  const auto in_range = [&](const calico_problem::Covariance::Blk& X, int tx) {
+    return X.off >= 0 ? X.off + tx <= dim : X.cp >= 0 && X.cp < cv.n_cp && tx == 6;
+  };
+  if (!in_range(A, ta) || !in_range(B, tb)) return p->set_error(CALICO_INTERNAL, "covariance: block layout out of range");
   std::vector<double> t(size_t(ta) * tb);
   for (int i = 0; i < ta; ++i)
-    for (int j = 0; j < tb; ++j) t[size_t(i) * tb + j] = p->cov.sigma[size_t(oa + i) * dim + (ob + j)];
+    for (int j = 0; j < tb; ++j) {
+      double v;
+      if (oa >= 0 && ob >= 0) v = cv.sigma[size_t(oa + i) * dim + (ob + j)];
+      else if (oa == -2 && ob >= 0) v = cv.sae[size_t(6 * A.cp + i) * dim + (ob + j)];       // Σ_AE
+      else if (ob == -2 && oa >= 0) v = cv.sae[size_t(6 * B.cp + j) * dim + (oa + i)];
+      else {                                                                                  // Σ_AA's band
+        const int hi = std::max(A.cp, B.cp), lo = std::min(A.cp, B.cp);
+        const double* b = cv.band.data() + (size_t(lo) * cv.order + (hi - lo)) * 36;
+        v = A.cp >= B.cp ? b[i * 6 + j] : b[j * 6 + i];
+      }
+      t[size_t(i) * tb + j] = v;
+    }
   if (tangent) { std::copy(t.begin(), t.end(), out); return CALICO_OK; }
   // ambient: P_a Σ P_bᵀ, P the manifold's PlusJacobian at the value Σ was computed at (identity for Euclidean blocks)
   double Pa[12], Pb[12];
@@ -2975,6 +3058,60 @@ int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t 
       else v = u[size_t(i) * tb + j];
       out[size_t(i) * rb + j] = v;
     }
+  return CALICO_OK;
+}
+
+namespace {
+// the readers of the trajectory's blocks: CALICO_OK when the last compute produced them for the problem as it stands
+int trajectory_result_ready(calico_problem* p) {
+  const calico_problem::Covariance& cv = p->cov;
+  if (cv.valid && !p->dirty && !cv.has_cp && cv.cp_requested)
+    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of the trajectory: the problem has no spline control points "
+                                                    "(calico_problem_set_spline)");
+  if (!cv.valid || p->dirty || !cv.has_cp)
+    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of the trajectory: call calico_covariance_compute with control_points = 1 "
+                                                    "(again, if the problem changed) and check its status");
+  return CALICO_OK;
+}
+}  // namespace
+
+int32_t calico_covariance_trajectory_info(calico_problem* p, int32_t* n_cp, int32_t* order, double* min_relative_pivot_band) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  if (int rc = trajectory_result_ready(p)) return rc;
+  if (n_cp) *n_cp = p->cov.n_cp;
+  if (order) *order = p->cov.order;
+  if (min_relative_pivot_band) *min_relative_pivot_band = p->cov.min_relative_pivot_band;
+  return CALICO_OK;
+}
+
+// Σ_v(t) at each stamp from Σ_AA's band on the device (cp_stamp_kernel); the segment of a stamp is Interpolate's
+int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double* stamps, double* out) {
+  if (!p || n < 0 || (n > 0 && (!stamps || !out))) return CALICO_INVALID_ARGUMENT;
+  if (int rc = trajectory_result_ready(p)) return rc;
+  if (n == 0) return CALICO_OK;
+  if (n > int64_t((INT32_MAX - 255) / 36)) return p->set_error(CALICO_INVALID_ARGUMENT, "covariance: too many stamps in one call");
+  calico_problem::Covariance& cv = p->cov;
+  std::vector<int> seg(static_cast<size_t>(n));
+  std::vector<double> t(stamps, stamps + n);
+  for (int64_t i = 0; i < n; ++i) {
+    seg[size_t(i)] = spline_index(p, stamps[i]);
+    if (seg[size_t(i)] < 0) {
+      char msg[160];
+      std::snprintf(msg, sizeof(msg), "covariance: stamp %lld (%.17g) is outside the trajectory's valid knots [%.17g, %.17g]", (long long)i,
+                    stamps[i], p->valid_knots.front(), p->valid_knots.back());
+      return p->set_error(CALICO_INVALID_ARGUMENT, msg);
+    }
+  }
+  HIP_TRY(p, hipSetDevice(p->device));
+  hipStream_t s = p->stream;
+  HIP_TRY(p, cv.st_t.upload(t, s));
+  HIP_TRY(p, cv.st_seg.upload(seg, s));
+  HIP_TRY(p, cv.st_out.alloc(size_t(n) * 36));
+  (void)hipGetLastError();
+  launch_cp_stamps(int(n), cv.order, cv.st_t.p, cv.st_seg.p, p->d_knots.p, p->d_basis.p, cv.cp_band.p, cv.st_out.p, s);
+  HIP_TRY(p, hipGetLastError());
+  HIP_TRY(p, hipMemcpyAsync(out, cv.st_out.p, size_t(n) * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(p, hipStreamSynchronize(s));
   return CALICO_OK;
 }
 

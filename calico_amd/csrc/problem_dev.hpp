@@ -341,6 +341,24 @@ struct SolveArgs {
   CAL_HD int y_index(int j) const { return in_sep(j) ? n_s() + mc + (j - 6 * sep_s) : j; }
 };
 
+// Arguments of the control-point covariance kernels (cov_kernels.hip). Block storage [n_cp][k][36]: block (J + d, J) row-major.
+struct CpCovArgs {
+  const double* R;      // reduce buffer 0: band at off_B, E (6 n_cp x mc, row-major) at off_E
+  size_t off_B, off_E;
+  int n_cp, k, mc;
+  double* dq;           // [6 n_cp] equilibration D
+  double* L;            // [n_cp][k][36] block band factor of D A D
+  double* Li;           // [n_cp][36] L_JJ⁻¹ (lower triangular)
+  double* M;            // [n_cp][k][36] d = 0: L_JJ⁻ᵀ L_JJ⁻¹, d >= 1: L_{J+d,J} L_JJ⁻¹
+  double* X;            // [6 n_cp][mc] forward substitution L⁻¹ D E
+  double* W;            // [6 n_cp][mc] A⁻¹ E
+  double* Z;            // [n_cp][k][36] band of (D A D)⁻¹
+  double* sae;          // [6 n_cp][mc] Σ_AE
+  double* band;         // [n_cp][k][36] band of Σ_AA
+  const double* sigma;  // [mc][mc] Σ_EE
+  double* info;         // [0] minimum relative pivot of the band, [1] flags (1 non-finite or negative diagonal, 2 pivot not positive)
+};
+
 // ---------------------------------------------------------------------------
 // Tree solver ("BCR": block cyclic reduction / nested dissection of the band, bcr_kernels.hip).
 // The control points are grouped into superblocks of kBcrCps = 5 (30 rows, padded to 32): with spline order k <= 6 a

@@ -334,6 +334,19 @@ PYBIND11_MODULE(_calico, m) {
         double v = 0.0;
         raise_if_error(SensorLatencyVariance(c, *s, &v));
         return v;
+      })
+      // the trajectory's blocks (ComputeCovariance(control_points=True)): control points i and j by their index in the spline,
+      // and the spline's 6-vector at each stamp as an (n, 6, 6) array
+      .def("ControlPoints",
+           [](const Covariance& c, int i, int j) {
+             std::vector<double> v(36);
+             raise_if_error(c.ControlPoints(i, j, v.data()));
+             return py::array_t<double>({py::ssize_t(6), py::ssize_t(6)}, v.data());
+           })
+      .def("Trajectory", [](const Covariance& c, const std::vector<double>& stamps) {
+        std::vector<double> v;
+        raise_if_error(c.TrajectoryCovariance(stamps, &v));
+        return py::array_t<double>({py::ssize_t(stamps.size()), py::ssize_t(6), py::ssize_t(6)}, v.data());
       });
 
   py::class_<BatchOptimizer>(m, "BatchOptimizer")
@@ -356,12 +369,13 @@ PYBIND11_MODULE(_calico, m) {
           py::arg("options") = DefaultSolverOptions(), py::arg("device") = 0)
       .def(
           "ComputeCovariance",
-          [](BatchOptimizer& self, double min_relative_pivot, int device) {
+          [](BatchOptimizer& self, double min_relative_pivot, int device, bool control_points) {
             calico_covariance_options o = DefaultCovarianceOptions();
             if (min_relative_pivot >= 0.0) o.min_relative_pivot = min_relative_pivot;
+            o.control_points = control_points ? 1 : 0;
             auto cov = self.ComputeCovariance(o, device);
             raise_if_error(cov.status());
             return cov.value();
           },
-          py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0);
+          py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0, py::arg("control_points") = false);
 }

@@ -305,7 +305,8 @@ class Covariance {
   bool GetCovarianceBlock(const double* a, const double* b, double* out) const { return Get(a, b, 0, out).ok(); }
   /// GetCovarianceBlockInTangentSpace: 3 rows / columns per quaternion block
   bool GetCovarianceBlockInTangentSpace(const double* a, const double* b, double* out) const { return Get(a, b, 1, out).ok(); }
-  /// the same, with the library's status (UNIMPLEMENTED for control points, INVALID_ARGUMENT for an unknown pointer)
+  /// the same, with the library's status (control points: after a compute with control_points = 1, with border blocks and
+  /// with control points less than the spline order apart, else UNIMPLEMENTED; INVALID_ARGUMENT for an unknown pointer)
   Status Get(const double* a, const double* b, int tangent, double* out) const {
     if (!h_) return FailedPreconditionError("covariance has not been computed");
     const auto ia = ids_.find(a), ib = ids_.find(b);
@@ -316,11 +317,27 @@ class Covariance {
   int Dimension() const { int32_t d = 0; if (h_) calico_covariance_info(h_.get(), &d, nullptr, nullptr); return d; }
   int NumUnobserved() const { int32_t n = 0; if (h_) calico_covariance_info(h_.get(), nullptr, &n, nullptr); return n; }
   double MinRelativePivot() const { double v = 0.0; if (h_) calico_covariance_info(h_.get(), nullptr, nullptr, &v); return v; }
+  /// 6 x 6 block of control points i and j (by their index in the spline), row-major (control_points = 1)
+  Status ControlPoints(int i, int j, double* out) const {
+    if (!h_) return FailedPreconditionError("covariance has not been computed");
+    if (i < 0 || j < 0 || size_t(i) >= ctrl_ids_.size() || size_t(j) >= ctrl_ids_.size())
+      return InvalidArgumentError("covariance: control point index out of range");
+    const int st = calico_covariance_get_block(h_.get(), ctrl_ids_[size_t(i)], ctrl_ids_[size_t(j)], 1, out);
+    return st == CALICO_OK ? OkStatus() : Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+  }
+  /// Covariance of the spline's 6-vector at each stamp (calico_covariance_trajectory): stamps.size() row-major 6 x 6 blocks
+  Status TrajectoryCovariance(const std::vector<double>& stamps, std::vector<double>* out) const {
+    if (!h_) return FailedPreconditionError("covariance has not been computed");
+    out->assign(stamps.size() * 36, 0.0);
+    const int st = calico_covariance_trajectory(h_.get(), int64_t(stamps.size()), stamps.data(), out->data());
+    return st == CALICO_OK ? OkStatus() : Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+  }
 
  private:
   friend class Problem;
   std::shared_ptr<calico_problem> h_;
   std::map<const double*, int32_t> ids_;
+  std::vector<int32_t> ctrl_ids_;      // block ids of the control points, in spline order
 };
 
 inline Status Problem::ComputeCovariance(const calico_covariance_options& options, Covariance* out, int device) {
@@ -328,6 +345,11 @@ inline Status Problem::ComputeCovariance(const calico_covariance_options& option
   if (int st = calico_covariance_compute(h_, &options)) return Err(st);
   out->ids_.clear();
   for (size_t i = 0; i < blocks_.size(); ++i) out->ids_[blocks_[i].ptr] = ids_[i];
+  out->ctrl_ids_.clear();
+  for (double* c : ctrl_) {
+    const auto it = out->ids_.find(c);
+    out->ctrl_ids_.push_back(it == out->ids_.end() ? -1 : it->second);
+  }
   out->h_ = std::shared_ptr<calico_problem>(h_, calico_problem_destroy);      // the result stays with its handle
   h_ = nullptr;
   return OkStatus();

@@ -316,7 +316,8 @@ int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient,
  *  - No a-posteriori variance factor is applied. To scale by the estimated residual variance, multiply Σ by
  *    2·cost / (num_residuals - num_effective_parameters) (calico_summary) yourself.
  *  - The control points are eliminated (Schur complement, as in the solver): Σ is their marginal over them. Their own
- *    blocks are not available (calico_covariance_get_block returns CALICO_UNIMPLEMENTED).
+ *    blocks are computed only on request (control_points = 1, below); otherwise calico_covariance_get_block returns
+ *    CALICO_UNIMPLEMENTED for them.
  *  - Constant (and unused) blocks read back as zeros, as in Ceres.
  *  - Deviation from Ceres: a tangent column whose JᵀJ diagonal is exactly 0.0 -- no residual depends on it, e.g. the
  *    gyroscope's translation block -- is left out of the inversion and its rows and columns of Σ are 0 (the
@@ -335,15 +336,30 @@ int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient,
  * rank calls it): every rank then holds the same Σ. */
 typedef struct calico_covariance_options {
   double min_relative_pivot;   /* smallest relative pivot accepted (>= 0) */
-  int32_t reserved[6];
+  int32_t control_points;      /* 0 or 1: also compute the trajectory's blocks (below) */
+  int32_t reserved[5];
 } calico_covariance_options;
-/* Defaults. min_relative_pivot = 1e-12, in the gap measured on the test scenes (tests/test_gpu_covariance.py prints
+/* Defaults. control_points = 0. min_relative_pivot = 1e-12, in the gap measured on the test scenes (tests/test_gpu_covariance.py prints
  * them): the well-posed scenes' minimum relative pivots lie between 3.7e-5 and 8.7e-3 (six camera models, the scale-only
  * and scale-and-bias IMU models robust and not, free model points, spline orders 7 and 8, the banded solver, the configs[3]
  * and configs[4] shapes), the gauge-deficient scene's
  * (camera-only, free chart pose) is 6.4e-16 -- rounding noise of an exactly singular system; an exactly singular
  * column gives a pivot <= 0, reported as 0. */
 void calico_default_covariance_options(calico_covariance_options* o);
+/* The trajectory's part of Σ (control_points = 1). Tangent order as calico_num_effective_parameters: control points first
+ * (6 each, Euclidean: ambient = tangent), then the border. With H = JᵀJ = [[A, E], [Eᵀ, C]], A the control points' block band
+ * (block bandwidth order - 1), the compute adds
+ *  - every cross block control point x border block, Σ_AE = -A⁻¹ E Σ_EE (exact, dense);
+ *  - the control-point pairs (i, j) with |i - j| < order (the spline's support), Σ_AA(i, j) = [A⁻¹]_ij - [Σ_AE (A⁻¹ E)ᵀ]_ij,
+ *    from a selected inversion of the band (block band Cholesky of the equilibrated A, Takahashi recurrence), all on the device.
+ *    Pairs farther apart are not computed: calico_covariance_get_block returns CALICO_UNIMPLEMENTED for them.
+ * An unobserved control point (no residual reaches it) reads back as zeros, as a constant block. A pivot of the equilibrated
+ * band below min_relative_pivot fails the whole compute with CALICO_FAILED_PRECONDITION. Spline orders up to 8 (beyond:
+ * CALICO_UNIMPLEMENTED). With control_points = 0 nothing of this runs and the compute is the border's alone; on a problem
+ * without a spline (no control points) the flag has nothing to compute and is ignored, and the trajectory readers return
+ * CALICO_FAILED_PRECONDITION saying so. A border of any width works, none (every calibration block constant) included.
+ * On a sharded handle every rank computes the same blocks from the all-reduced normal equations (no further exchange). The control
+ * points' blocks are bit-identical from compute to compute; the border's Σ does not depend on control_points. */
 /* Compute Σ (finalises the problem if needed). o == NULL: the defaults. */
 int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_options* o);
 /* Size of Σ (the border's tangent dimension), the number of structurally unobserved columns left out, and the minimum
@@ -354,9 +370,20 @@ int32_t calico_covariance_info(calico_problem* p, int32_t* dim, int32_t* n_unobs
 int32_t calico_covariance_get_dense(calico_problem* p, double* out);
 /* The (block_a, block_b) block of Σ, row-major. tangent != 0: tangent space (GetCovarianceBlockInTangentSpace, 3 rows per
  * quaternion); tangent == 0: ambient (GetCovarianceBlock), a quaternion block lifted as P Σ Pᵀ with P the
- * EigenQuaternionManifold PlusJacobian at the current value. CALICO_UNIMPLEMENTED for control-point blocks,
- * CALICO_INVALID_ARGUMENT for an unknown id, CALICO_FAILED_PRECONDITION without a successful compute. */
+ * EigenQuaternionManifold PlusJacobian at the current value. Control-point blocks (6 rows) after a compute with
+ * control_points = 1: with any border block, and with control points less than the spline order apart; CALICO_UNIMPLEMENTED
+ * for other control-point pairs and for every control-point block after a compute without it; CALICO_INVALID_ARGUMENT
+ * for an unknown id, CALICO_FAILED_PRECONDITION without a successful compute. */
 int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t block_b, int32_t tangent, double* out);
+/* Covariance of the spline's 6-vector (what Interpolate converts to a pose) at each of n stamps, out = n x 36 (row-major
+ * 6x6 each): Σ_v(t) = Σ_ij w_i(t) w_j(t) Σ_AA(s + i, s + j) over the order control points of t's segment s, w the spline's
+ * weights at t. Symmetric. CALICO_INVALID_ARGUMENT for a stamp outside the valid knots (the rule of Interpolate: the last
+ * valid knot belongs to the last segment), CALICO_FAILED_PRECONDITION without a successful compute with control_points = 1
+ * or after a structural change. */
+int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double* stamps, double* out);
+/* Number of control points and spline order of the trajectory's blocks, and the minimum relative pivot of the band's
+ * factorisation. CALICO_FAILED_PRECONDITION as calico_covariance_trajectory. */
+int32_t calico_covariance_trajectory_info(calico_problem* p, int32_t* n_cp, int32_t* order, double* min_relative_pivot_band);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
