@@ -131,7 +131,7 @@ ABI_SYMBOLS = [
     "covariance_trajectory", "covariance_trajectory_info",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
-TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table"]
+TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step"]
 
 
 class CApi:
@@ -199,6 +199,8 @@ class CApi:
             g("debug_plan_info", C.c_int32, [P, I, C.c_int32])
             if hasattr(self.lib, self.prefix + "debug_roll_table"):      # (a library of an older round, loaded for a same-box A/B, has none)
                 g("debug_roll_table", C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_uint32)])
+            if hasattr(self.lib, self.prefix + "debug_last_step"):
+                g("debug_last_step", C.c_int32, [P, C.c_int32, D, D, D])
 
     def _get(self, name, restype, argtypes):
         fn = getattr(self.lib, self.prefix + name)
@@ -471,13 +473,27 @@ class Problem:
     def finalize(self):
         self._check(self.api.problem_finalize(self.h))
 
+    PLAN_INFO_KEYS = ("fuse_expand", "frames", "items", "cells", "max_frames_per_cell", "max_items_per_cell", "tree_solver", "m",
+                      "all_control_points_observed",
+                      # what a linear solve does (calico_hip_testing.h): tree shape, launch fusions, reduced-solve route
+                      "superblocks", "chain", "levels", "root", "schur_rides", "top_seps", "fused_back", "reduced_route",
+                      "reduced_in_lds", "schur_slices", "reduced_m", "sep_n")
+    REDUCED_ROUTES = ("panel", "block", "blocked", "kernel")     # plan_info()["reduced_route"] indexes this
+
     def plan_info(self):
         """Test hook (calico_hip_testing.h): which evaluation route / solver the plan of this handle takes."""
-        out = np.zeros(9, np.int32)
-        self._check(self.api.debug_plan_info(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), 9))
-        keys = ("fuse_expand", "frames", "items", "cells", "max_frames_per_cell", "max_items_per_cell", "tree_solver", "m",
-                "all_control_points_observed")
-        return dict(zip(keys, (int(v) for v in out)))
+        n = len(self.PLAN_INFO_KEYS)
+        out = np.zeros(n, np.int32)
+        self._check(self.api.debug_plan_info(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        return dict(zip(self.PLAN_INFO_KEYS, (int(v) for v in out)))
+
+    def last_step(self, n=None):
+        """Test hook (calico_hip_testing.h): (step, damping, scale) of the last linear solve of the last solve(), in
+        calico_evaluate's column order (n=None), or in tangent order over every control point (n = 6 n_cp + m)."""
+        n = self.num_effective_parameters() if n is None else int(n)
+        step, damping, scale = np.zeros(n), np.zeros(n), np.zeros(n)
+        self._check(self.api.debug_last_step(self.h, n, _dp(step), _dp(damping), _dp(scale)))
+        return step, damping, scale
 
     def comm_init_rccl(self, unique_id, rank, world_size):
         """Native exchange: the handle creates its own RCCL communicator from the 128-byte id (see comm_unique_id)."""

@@ -96,6 +96,7 @@ void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_node
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
 
 void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
+int reduced_solve_route(const SolveArgs& a);
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
 size_t dense_back_lds_bytes(int q_max, int m1p);
 hipError_t configure_dense_back_bytes(size_t lds);
@@ -124,6 +125,7 @@ namespace {
 
 constexpr size_t kMaxLds = 160 * 1024;
 constexpr int kLogCap = 4096;
+constexpr int kPlanInfoWords = 21;    // words calico_debug_plan_info reports (calico_hip_testing.h)
 constexpr int kNumPhases = 7;   // 5 = calibration: the same event bracket around a trivial kernel; 6 = the reduced-system launch inside phase 2
 
 // RCCL is loaded when the first communicator is asked for (calico_comm_get_unique_id / calico_comm_init_rccl), not at
@@ -524,6 +526,7 @@ struct calico_problem : PlanHost, PlanDev, Workspace {
   bool active_dirty = true;
   bool any_tagged = false;       // some observation is tagged as an outlier: the kernels look at the tags only then
   bool xc_stale = true;       // the candidate buffer must be re-seeded with the constant blocks' values
+  bool step_ready = false;    // d_y / d_dadd / d_scale hold a linear solve of the current plan and values (calico_debug_last_step)
   // residuals of ALL sensors at the parameter values `x` (calico_get_residuals / calico_project are per sensor, as
   // Sensor::UpdateResiduals is: the second to last sensor of a write-back are served from here)
   struct ResCache { bool valid = false, predict = false; std::vector<double> x, r; std::vector<uint8_t> v; } res_cache;
@@ -1554,7 +1557,13 @@ int prepare_workspace(calico_problem* p) {
   HIP_TRY(p, p->d_partials.alloc(p->partials_alloc));
   HIP_TRY(p, hipMemsetAsync(p->d_partials.p + (p->partials_alloc - 2), 0, 2 * sizeof(double), s));      // the word the lists point to for "nothing"
   if (env_int("CALICO_KERNEL_TIMING", 0, 0) >= 3) HIP_TRY(p, p->d_wave_log.alloc(2 * size_t(p->n_jac_items + p->n_fitems) + 8));
-  HIP_TRY(p, p->d_R.alloc(2 * r_size)); HIP_TRY(p, hipMemsetAsync(p->d_R.p, 0, 2 * r_size * sizeof(double), s));
+  // Behind the second reduce buffer: what the tree solver's rolling chief (bcr_level_kernel, ROLL) reads and masks past the
+  // band of the last superblock I = N - 1. Its lanes load at I·strideB + (g_roll_tab offset) and select afterwards; the offsets
+  // reach (6k - 1)·36 + 11 doubles into a superblock's storage (rows 30 and 31 of the 32-row tiles count as control point 5,
+  // the Bᵀ rows' column at most 31), i.e. (5N + 1 - n_cp)·k·36 - 24 <= 5·k·36 - 24 doubles past the band's end (5N - n_cp
+  // <= 4). In buffer 0 that lands in E / C / buffer 1; in buffer 1 it lands here when E and C are short (mc == 0).
+  const size_t r_pad = p->use_bcr ? size_t(kBcrCps) * size_t(k) * 36 : 0;
+  HIP_TRY(p, p->d_R.alloc(2 * r_size + r_pad)); HIP_TRY(p, hipMemsetAsync(p->d_R.p, 0, (2 * r_size + r_pad) * sizeof(double), s));
   HIP_TRY(p, p->d_R2.alloc(2));
   const int NT = 6 * n_cp + m;
   const int mw = m + p->border_extra();     // border width the solver kernels work with
@@ -1700,6 +1709,7 @@ int configure_kernels(calico_problem* p) {
 int finalize(calico_problem* p) {
   if (!p->dirty) return CALICO_OK;
   p->res_cache.valid = false;
+  p->step_ready = false;
   p->cov.valid = false;      // (a covariance of the structure before is gone: its layout is not this plan's)
   if (p->order <= 0) return p->set_error(CALICO_FAILED_PRECONDITION, "spline not set");
   if (p->order > 8) return p->set_error(CALICO_UNIMPLEMENTED, "spline order > 8 is not supported by the HIP kernels");
@@ -1867,6 +1877,54 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
   return do_allreduce(p, target, int64_t(p->r_size));
 }
 
+// What one linear solve does, from the plan and the switches read per solve: enqueue_linear_solve follows it,
+// calico_debug_plan_info reports it (one decision, so the hook cannot drift from what runs).
+struct LinearRoute {
+  int ks = 1;                 // K-slices of the Schur complement (reduced_schur_slices)
+  int reduced = 0;            // ReducedRoute of the reduced solve
+  bool reduced_in_lds = true; // kReducedKernel: works in LDS (else in Swork)
+  // tree solver only:
+  bool schur_rides = false;   // the Schur complement rides in the last level's launch
+  BcrTopSeps ts = {};         // top separators back-substituted in the launch of the level below (ts.n of them)
+  int l_first = 0;            // level of the first back-substitution launch behind the reduced solve
+  bool fused = false;         // the dense solve and that back-substitution share one launch (dense_back_kernel)
+};
+LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa) {
+  LinearRoute r;
+  r.ks = reduced_schur_slices(sa);
+  r.reduced = reduced_solve_route(sa);
+  r.reduced_in_lds = p->dense_in_lds;
+  if (!p->use_bcr || p->bcr_levels.empty()) return r;
+  const int L = int(p->bcr_levels.size());
+  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
+  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
+  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
+  // launch bcr_schur_kernel on its own.
+  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
+  r.schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
+  for (int i = 0; r.schur_rides && i < last.n_nodes; ++i) r.schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
+  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
+  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
+  // the ones it waits for anyway) instead of costing a launch of its own.
+  if (L >= 2) {
+    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
+    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
+    for (int i = 0; ok && i < tl.n_nodes; ++i) {
+      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
+      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
+      r.ts.blk[i] = nd.blk0; r.ts.left[i] = nd.left; r.ts.right[i] = nd.right;
+    }
+    r.ts.n = ok ? tl.n_nodes : 0;
+  }
+  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
+  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
+  r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
+  const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
+  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) &&
+            std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(lf.q_max, p->bcr_m1p)) + 1024 <= kMaxLds;
+  return r;
+}
+
 // One linear solve + update of the candidate point: tree solver or sequential banded factorisation.
 // with_post_eval: 0 none, 1 the bookkeeping of the step just accepted rides in the first launch, 2 the bookkeeping of the
 // solve's FIRST evaluation does (tree solver only: level 0 then forms the Jacobi scale of its diagonal entries itself)
@@ -1884,14 +1942,9 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   }
   const BcrArgs b = make_bcr_args(p);
   const int L = int(p->bcr_levels.size());
-  const int ks = reduced_schur_slices(sa);
-  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
-  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
-  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
-  // launch bcr_schur_kernel on its own.
-  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
-  bool schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
-  for (int i = 0; schur_rides && i < last.n_nodes; ++i) schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
+  const LinearRoute rt = linear_route(p, sa);
+  const int ks = rt.ks;
+  const bool schur_rides = rt.schur_rides;
   int* const fan_word = p->d_handoff.p + 4;
   // (A/B switch, read per solve: 0 = every level reads its node descriptors from the table)
   const bool inline_nodes = env_flag("CALICO_INLINE_NODES", true);
@@ -1907,26 +1960,9 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   }
   if (!schur_rides) launch_bcr_schur(sa, b, ks, o, s);
   if (reduce_only) return;
-  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
-  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
-  // the ones it waits for anyway) instead of costing a launch of its own.
-  BcrTopSeps ts = {};
-  if (L >= 2) {
-    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
-    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
-    for (int i = 0; ok && i < tl.n_nodes; ++i) {
-      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
-      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
-      ts.blk[i] = nd.blk0; ts.left[i] = nd.left; ts.right[i] = nd.right;
-    }
-    ts.n = ok ? tl.n_nodes : 0;
-  }
-  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
-  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
-  const int l_first = ts.n > 0 ? L - 2 : L - 1;
-  const BcrLevel& lf = p->bcr_levels[size_t(l_first)];
-  const bool fused = l_first == 0 && dense_back_fusable(sa, ks, lf.q_max, /*border_rows=*/l_first > 0) &&
-                     std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(lf.q_max, p->bcr_m1p)) + 1024 <= kMaxLds;
+  const BcrTopSeps& ts = rt.ts;
+  const BcrLevel& lf = p->bcr_levels[size_t(rt.l_first)];
+  const bool fused = rt.fused;
   p->timer.begin(6, s);       // the launch that solves the reduced system: the longest kernel of an iteration at configs[3]
   if (fused) {
     p->handoff_seq = p->handoff_seq % 0x3fffffff + 1;
@@ -2161,6 +2197,7 @@ int32_t calico_set_param_block(calico_problem* p, int32_t id, const double* v) {
   if (!p || id < 0 || id >= int(p->blocks.size()) || !v) return p ? p->set_error(CALICO_INVALID_ARGUMENT, "bad block id") : CALICO_INVALID_ARGUMENT;
   std::copy(v, v + p->blocks[id].size, p->blocks[id].v.begin());
   if (p->blocks[id].constant || !p->blocks[id].used) p->xc_stale = true;   // the update kernel never rewrites these
+  p->step_ready = false;
   return CALICO_OK;
 }
 
@@ -2187,6 +2224,7 @@ int32_t calico_set_param_blocks(calico_problem* p, int32_t n, const int32_t* ids
     v += b.size;
     if (b.constant || !b.used) p->xc_stale = true;
   }
+  if (n > 0) p->step_ready = false;
   return CALICO_OK;
 }
 
@@ -2314,6 +2352,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   if (rc != CALICO_OK) return rc;
   fill_counts(p, sm);
   p->iterations.clear();
+  p->step_ready = false;
   // event brackets nobody has asked about yet: resolved here once they pile up (a solve returns without draining them)
   if (p->timer.pending.size() > 8192) { HIP_TRY(p, hipStreamSynchronize(p->stream)); p->timer.resolve(); }
   LmOptionsDev o;
@@ -2558,6 +2597,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   sm->termination_type = st.termination_type;
   sm->num_successful_steps = st.num_successful; sm->num_unsuccessful_steps = st.num_unsuccessful;
   sm->num_iterations = st.last_logged_iteration;      // Summary::iterations.size() - 1; not read from the log buffer, which is capped at kLogCap rows
+  p->step_ready = st.last_logged_iteration >= 1;      // (every logged iteration after the 0th ran a linear solve)
   sm->initial_cost = st.initial_cost;
   sm->final_cost = st.termination_type == CALICO_FAILURE ? 0.0 : std::min(st.initial_cost, st.min_cost);
   std::snprintf(sm->message, sizeof(sm->message), "%s", reason_message(st.termination_reason));
@@ -2612,12 +2652,48 @@ int32_t calico_debug_roll_table(int32_t spline_order, int32_t lane, uint32_t* ou
 }
 
 int32_t calico_debug_plan_info(calico_problem* p, int32_t* out, int32_t n) {
-  if (!p || !out || n < 0 || n > 9) return CALICO_INVALID_ARGUMENT;
+  if (!p || !out || n < 0 || n > kPlanInfoWords) return CALICO_INVALID_ARGUMENT;
   int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
-  const int v[9] = {p->fuse_expand ? 1 : 0, p->n_fitems, p->n_jac_items, p->n_cells, p->max_cell_frames, p->max_item_run,
-                    p->use_bcr ? 1 : 0, p->m, p->bcr_all_active ? 1 : 0};
+  const SolveArgs sa = make_solve_args(p);
+  const LinearRoute rt = linear_route(p, sa);
+  const bool tree = p->use_bcr;
+  const int v[kPlanInfoWords] = {p->fuse_expand ? 1 : 0, p->n_fitems, p->n_jac_items, p->n_cells, p->max_cell_frames, p->max_item_run,
+                                 tree ? 1 : 0, p->m, p->bcr_all_active ? 1 : 0,
+                                 tree ? p->bcr_N : 0, tree ? p->bcr_q0 : 0, tree ? int(p->bcr_levels.size()) : 0,
+                                 tree && p->bcr_root >= 0 ? 1 : 0, rt.schur_rides ? 1 : 0, rt.ts.n, rt.fused ? 1 : 0,
+                                 rt.reduced, rt.reduced_in_lds ? 1 : 0, rt.ks, sa.m, p->sep_n};
   for (int i = 0; i < n; ++i) out[i] = v[i];
+  return CALICO_OK;
+}
+
+int32_t calico_debug_last_step(calico_problem* p, int32_t n, double* step, double* damping, double* scale) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  if (p->dirty || !p->step_ready)
+    return p->set_error(CALICO_FAILED_PRECONDITION, "no linear solve since the plan or the parameters last changed");
+  const int NS = 6 * p->n_cp, NT = NS + p->m;
+  if (n != p->n_eff && n != NT) return p->set_error(CALICO_INVALID_ARGUMENT, "n must be the effective parameter count or 6 n_cp + m");
+  HIP_TRY(p, hipSetDevice(p->device));
+  HIP_TRY(p, hipStreamSynchronize(p->stream));
+  const SolveArgs sa = make_solve_args(p);
+  std::vector<double> y(size_t(NT) + size_t(p->border_extra())), d(static_cast<size_t>(NT)), sc(static_cast<size_t>(NT));
+  HIP_TRY(p, hipMemcpy(y.data(), p->d_y.p, y.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(p, hipMemcpy(d.data(), p->d_dadd.p, d.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(p, hipMemcpy(sc.data(), p->d_scale.p, sc.size() * sizeof(double), hipMemcpyDeviceToHost));
+  // where the candidate update reads the solution of tangent row t (delta = -y): banded solver, y_index (the separator's rows
+  // behind the calibration part); tree solver, the root's rows behind the calibration part, every other row at its own index
+  constexpr int RB = 6 * kBcrCps;
+  auto y_of = [&](int t) -> double {
+    if (!p->use_bcr) return y[size_t(sa.y_index(t))];
+    if (t < NS && p->bcr_root >= 0 && t / RB == p->bcr_root) return y[size_t(NS + p->m + (t - RB * p->bcr_root))];
+    return y[size_t(t)];
+  };
+  for (int i = 0; i < n; ++i) {
+    const int t = n == NT ? i : p->eff_to_tan[size_t(i)];
+    if (step) step[i] = -y_of(t);
+    if (damping) damping[i] = d[size_t(t)];
+    if (scale) scale[i] = sc[size_t(t)];
+  }
   return CALICO_OK;
 }
 

@@ -341,6 +341,11 @@ struct SolveArgs {
   CAL_HD int y_index(int j) const { return in_sep(j) ? n_s() + mc + (j - 6 * sep_s) : j; }
 };
 
+// Which kernel solves the reduced system (reduced_solve_route, solve_kernels.hip): the 16-column panel kernel (a.m == 0: only
+// the right-hand side's row), the in-LDS 32-column-block solve (up to 128 unknowns), blocked panels down to that solve (up to
+// kBlockedMaxM), reduced_solve_kernel beyond.
+enum ReducedRoute { kReducedPanel = 0, kReducedBlock = 1, kReducedBlocked = 2, kReducedKernel = 3 };
+
 // Arguments of the control-point covariance kernels (cov_kernels.hip). Block storage [n_cp][k][36]: block (J + d, J) row-major.
 struct CpCovArgs {
   const double* R;      // reduce buffer 0: band at off_B, E (6 n_cp x mc, row-major) at off_E

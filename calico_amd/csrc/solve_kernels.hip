@@ -1654,15 +1654,21 @@ int reduced_schur_slices(const SolveArgs& a) {
 // Dense solve of the (m+1)x(m+1) augmented reduced system in a.Spart (ks K-slices) -> a.y[n_s ...]
 void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0 = 0, int outer_back = 0);     // bcr_kernels.hip
 void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hipStream_t s);     // bcr_kernels.hip
+// Which kernel solves the reduced system (launch_reduced_solve; calico_debug_plan_info reports it)
+int reduced_solve_route(const SolveArgs& a) {
+  if (a.m + 1 <= 128) return a.m >= 1 ? kReducedBlock : kReducedPanel;
+  return reduced_is_blocked(a) ? kReducedBlocked : kReducedKernel;
+}
 void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s) {
   const int m1 = a.m + 1;
-  if (m1 <= 128 && a.m >= 1) {
+  const int route = reduced_solve_route(a);
+  if (route == kReducedBlock) {
     launch_dense_block_solve(a, ks, s);      // (ks <= 8, what the solver adds up on load: see reduced_schur_slices)
-  } else if (m1 <= 128) {
+  } else if (route == kReducedPanel) {
     // a.m == 0 (nothing to calibrate): only the right-hand side's row, which the panel kernel takes
     const size_t lds = (size_t(m1) * ((16 * ((m1 + 15) / 16)) | 1) + m1 + 32 + 128 + 256) * sizeof(double);
     hipLaunchKernelGGL(reduced_solve_panel_kernel<1>, dim3(1), dim3(256), lds, s, a, 0, ks);
-  } else if (reduced_is_blocked(a)) {
+  } else if (route == kReducedBlocked) {
     // panels are eliminated over all CUs until what is left (97..128 unknowns) fits the in-LDS solver, which finishes the
     // factorisation, solves for its unknowns and runs the backward sweep over the panels
     const int steps = (m1 - 128 + kRB - 1) / kRB, t0 = kRB * steps;
