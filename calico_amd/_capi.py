@@ -75,6 +75,11 @@ class CovarianceOptions(C.Structure):
     _fields_ = [("min_relative_pivot", C.c_double), ("control_points", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class ObservabilityOptions(C.Structure):
+    """calico_observability_options."""
+    _fields_ = [("weak_threshold", C.c_double), ("min_relative_pivot", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -129,9 +134,11 @@ ABI_SYMBOLS = [
     "comm_get_unique_id", "comm_init_rccl", "comm_info", "problem_finalize", "plan_cache_stats", "plan_cache_clear",
     "default_covariance_options", "covariance_compute", "covariance_info", "covariance_get_dense", "covariance_get_block",
     "covariance_trajectory", "covariance_trajectory_info",
+    "default_observability_options", "observability_compute", "observability_info", "observability_get_spectrum",
+    "observability_get_directions", "observability_get_block", "observability_get_matrix",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
-TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step"]
+TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info"]
 
 
 class CApi:
@@ -194,6 +201,14 @@ class CApi:
             g("covariance_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
             g("covariance_trajectory", C.c_int32, [P, C.c_int64, D, D])
             g("covariance_trajectory_info", C.c_int32, [P, I, I, D])
+            g("default_observability_options", None, [C.POINTER(ObservabilityOptions)])
+            g("observability_compute", C.c_int32, [P, C.POINTER(ObservabilityOptions)])
+            g("observability_info", C.c_int32, [P, I, I, I, D, D, I])
+            g("observability_get_spectrum", C.c_int32, [P, D])
+            g("observability_get_directions", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
+            g("observability_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D, D])
+            g("observability_get_matrix", C.c_int32, [P, D])
+            g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
             g("debug_plan_info", C.c_int32, [P, I, C.c_int32])
@@ -464,6 +479,67 @@ class Problem:
         out = np.zeros(sizes)
         self._check(self.api.covariance_get_block(self.h, int(block_a), int(block_b), int(bool(tangent)), _dp(out)))
         return out
+
+    def observability_compute(self, weak_threshold=None, min_relative_pivot=None):
+        """calico_observability_compute; returns observability_info(). Raises CalicoError on failure (a trajectory the data
+        do not determine); a rank-deficient border is not one: n_weak > 0."""
+        o = ObservabilityOptions()
+        self.api.default_observability_options(C.byref(o))
+        if weak_threshold is not None:
+            o.weak_threshold = float(weak_threshold)
+        if min_relative_pivot is not None:
+            o.min_relative_pivot = float(min_relative_pivot)
+        self._check(self.api.observability_compute(self.h, C.byref(o)))
+        return self.observability_info()
+
+    def observability_info(self):
+        """dict: dim, n_unobserved, n_weak, lambda_min, lambda_max, sweeps of the last successful compute."""
+        dim, nu, nw, sw = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        lo, hi = C.c_double(0), C.c_double(0)
+        self._check(self.api.observability_info(self.h, C.byref(dim), C.byref(nu), C.byref(nw), C.byref(lo), C.byref(hi), C.byref(sw)))
+        return dict(dim=dim.value, n_unobserved=nu.value, n_weak=nw.value, lambda_min=lo.value, lambda_max=hi.value, sweeps=sw.value)
+
+    def observability_spectrum(self):
+        """Eigenvalues of S̃, ascending (dim - n_unobserved of them)."""
+        i = self.observability_info()
+        out = np.zeros(i["dim"] - i["n_unobserved"])
+        self._check(self.api.observability_get_spectrum(self.h, _dp(out) if out.size else _dp(np.zeros(1))))
+        return out
+
+    def observability_directions(self, first=0, count=None, tangent_units=False):
+        """Rows [first, first + count) of the ascending list, (count, dim): unit eigenvectors v_i, or with tangent_units the
+        directions δ_i in the parameters' own units."""
+        i = self.observability_info()
+        if count is None:
+            count = i["dim"] - i["n_unobserved"] - first
+        out = np.zeros((max(int(count), 0), i["dim"]))
+        self._check(self.api.observability_get_directions(self.h, int(first), int(count), int(bool(tangent_units)),
+                                                          _dp(out) if out.size else _dp(np.zeros(1))))
+        return out
+
+    def observability_block(self, index, block_id, tangent_units=False, size=None):
+        """(entries of direction `index` in the block's tangent rows, the block's share of the unit eigenvector)."""
+        if size is None:
+            n = self._sizes[block_id]
+            size = 3 if (n == 4 and self._manifolds.get(block_id) == MANIFOLD_EIGEN_QUATERNION) else n
+        out = np.zeros(size)
+        share = C.c_double(0)
+        self._check(self.api.observability_get_block(self.h, int(index), int(block_id), int(bool(tangent_units)), _dp(out), C.byref(share)))
+        return out, share.value
+
+    def observability_matrix(self):
+        """S̃ (dim x dim, zeros in dropped rows and columns)."""
+        dim = self.observability_info()["dim"]
+        out = np.zeros((dim, dim))
+        self._check(self.api.observability_get_matrix(self.h, _dp(out) if out.size else _dp(np.zeros(1))))
+        return out
+
+    def observability_debug(self):
+        """Test hook (calico_hip_testing.h): what the last observability compute did."""
+        out = np.zeros(6)
+        self._check(self.api.debug_observability_info(self.h, _dp(out), 6))
+        return dict(in_lds=int(out[0]), kept=int(out[1]), reduced_rows=int(out[2]), rotations=int(out[3]),
+                    min_relative_pivot_band=out[4], min_relative_pivot_root=out[5])
 
     def set_allreduce(self, pyfunc):
         cb = ALLREDUCE_FN(pyfunc)

@@ -114,6 +114,14 @@ hipError_t configure_covariance_kernel();
 int cp_covariance_max_order();
 void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s);
 void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s);
+void launch_cp_band_factor(const CpCovArgs& a, hipStream_t s);
+int observability_max_border();
+int observability_max_dim();
+bool observability_in_lds(int m, int mc);
+size_t observability_work_doubles(int m, int mc);
+void launch_observability(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* lam,
+                          double* vec, double* mat, double* d, double* info, hipStream_t s);
+hipError_t configure_observability_kernel();
 void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
                       double* out, hipStream_t s);
 
@@ -554,6 +562,21 @@ struct calico_problem : PlanHost, PlanDev, Workspace {
     double min_relative_pivot_band = 0.0;
     std::vector<double> sae, band;     // Σ_AE (6 n_cp x dim), Σ_AA's band ([n_cp][order][36], block (J + d, J) row-major)
   } cov;
+  // calico_observability_compute: the same kind of private state as the covariance pass, the eigensolver's workspace and
+  // the report (obs_kernels.hip)
+  struct Observability {
+    DevBuf<LmState> st;
+    DevBuf<double> scale, dadd, y, zbuf, work, lam, vec, mat, dvec, info, cp_dq, cp_L, cp_Li, cp_info;
+    bool valid = false;
+    int dim = 0, kept = 0, n_unobserved = 0, n_weak = 0, sweeps = 0, rotations = 0, in_lds = 0, reduced_rows = 0;
+    double min_relative_pivot_root = 0.0, min_relative_pivot_band = 0.0;
+    std::vector<double> eigenvalues;     // kept, ascending
+    std::vector<double> vectors;         // kept x dim: row i the unit eigenvector v_i, border tangent order, zeros in dropped columns
+    std::vector<double> d;               // dim: D = sqrt(diag C), 0 in dropped columns
+    std::vector<double> matrix;          // dim x dim: S̃, zeros in dropped rows and columns
+    struct Blk { int off, tsize; };      // per block id at the time of the compute: offset of its tangent rows (-1: not in the border, -2: control point)
+    std::vector<Blk> blocks;
+  } obs;
 
   int set_error(int code, const std::string& msg) { error = msg; return code; }
   int hip_error(hipError_t e, const char* what) {
@@ -1711,6 +1734,7 @@ int finalize(calico_problem* p) {
   p->res_cache.valid = false;
   p->step_ready = false;
   p->cov.valid = false;      // (a covariance of the structure before is gone: its layout is not this plan's)
+  p->obs.valid = false;      // (and so is an observability report)
   if (p->order <= 0) return p->set_error(CALICO_FAILED_PRECONDITION, "spline not set");
   if (p->order > 8) return p->set_error(CALICO_UNIMPLEMENTED, "spline order > 8 is not supported by the HIP kernels");
   HIP_TRY(p, hipSetDevice(p->device));
@@ -2909,6 +2933,44 @@ void calico_default_covariance_options(calico_covariance_options* o) {
   o->min_relative_pivot = 1e-12;
 }
 
+namespace {
+// What the covariance and the observability passes share up to the reduction: the pass's own LM state (an infinite radius),
+// a Jacobi scale of ones, damping and solution buffers -- nothing of the LM's is touched --, the parameter upload and one
+// evaluation (as the LM loop's, exchange included; the phase timer records nothing of it). On return `sa` points at the
+// pass's buffers and `o` holds the damping bounds: enqueue_linear_solve(p, sa, o, 0, 0, reduce_only) then leaves the undamped,
+// unscaled reduced system in sa.Spart.
+struct UndampedPass { DevBuf<LmState>& st; DevBuf<double>& scale; DevBuf<double>& dadd; DevBuf<double>& y; DevBuf<double>& zbuf; };
+int begin_undamped_pass(calico_problem* p, UndampedPass b, SolveArgs& sa, LmOptionsDev& o) {
+  const int NT = sa.NT(), ny = NT + p->border_extra();
+  // (the same sizes as the workspace's buffers they stand in for: prepare_workspace)
+  HIP_TRY(p, b.st.alloc(1)); HIP_TRY(p, b.scale.alloc(2 * size_t(NT))); HIP_TRY(p, b.dadd.alloc(size_t(NT)));
+  HIP_TRY(p, b.y.alloc(size_t(ny) + 64)); HIP_TRY(p, b.zbuf.alloc(size_t(sa.n_s()) + 64));
+  hipStream_t s = p->stream;
+  {
+    const std::vector<double> ones(2 * size_t(NT), 1.0);      // [Jacobi scale s | 1 / s^2]: no scaling
+    HIP_TRY(p, hipMemcpyAsync(b.scale.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(p, hipStreamSynchronize(s));      // (`ones` is a local)
+  }
+  int rc = upload_x(p);
+  if (rc != CALICO_OK) return rc;
+  {
+    // (the phase timer measures the LM loop: the pass records nothing into it)
+    const int mask = p->timer.mask;
+    p->timer.mask = 0;
+    rc = enqueue_jacobian_eval(p, nullptr, 0);      // R(x) into reduce buffer 0, all ranks' sum
+    p->timer.mask = mask;
+  }
+  if (rc != CALICO_OK) return rc;
+  // damping = clamp(v s², min, max) / (radius s²) = 0 with s = 1 and an infinite radius (FromR::damping, prepare_kernel)
+  launch_init_state(b.st.p, std::numeric_limits<double>::infinity(), 0.0, s);
+  sa.st = b.st.p; sa.scale = b.scale.p; sa.dadd = b.dadd.p; sa.y = b.y.p; sa.zbuf = b.zbuf.p; sa.progress = nullptr;
+  o = {};
+  o.min_lm_diagonal = 1e-6; o.max_lm_diagonal = 1e32;
+  (void)hipGetLastError();
+  return CALICO_OK;
+}
+}  // namespace
+
 // Σ = (JᵀJ)⁻¹ of the calibration blocks at the current values: one evaluation (as the LM loop's, exchange included), the
 // linear solve's reduction WITHOUT damping and Jacobi scaling -- a state of its own with an infinite radius, a scale of
 // ones --, stopped once the reduced system is formed, then covariance_kernel (cov_kernels.hip). The LM state, the
@@ -2948,35 +3010,13 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
     ca.dq = cv.cp_dq.p; ca.L = cv.cp_L.p; ca.Li = cv.cp_Li.p; ca.M = cv.cp_M.p; ca.X = cv.cp_X.p; ca.W = cv.cp_W.p; ca.Z = cv.cp_Z.p;
     ca.sae = cv.cp_sae.p; ca.band = cv.cp_band.p; ca.info = cv.cp_info.p;
   }
-  const int NT = sa.NT(), ny = NT + p->border_extra();
-  // (the same sizes as the workspace's buffers they stand in for: prepare_workspace)
-  HIP_TRY(p, cv.st.alloc(1)); HIP_TRY(p, cv.scale.alloc(2 * size_t(NT))); HIP_TRY(p, cv.dadd.alloc(size_t(NT)));
-  HIP_TRY(p, cv.y.alloc(size_t(ny) + 64)); HIP_TRY(p, cv.zbuf.alloc(size_t(sa.n_s()) + 64));
   HIP_TRY(p, cv.out.alloc(size_t(mc) * mc)); HIP_TRY(p, cv.info.alloc(4));
   if (!covariance_in_lds(m)) HIP_TRY(p, cv.work.alloc(size_t(m) * covariance_ld(m)));
   HIP_TRY(p, configure_covariance_kernel());
   hipStream_t s = p->stream;
-  {
-    const std::vector<double> ones(2 * size_t(NT), 1.0);      // [Jacobi scale s | 1 / s^2]: no scaling
-    HIP_TRY(p, hipMemcpyAsync(cv.scale.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(p, hipStreamSynchronize(s));      // (`ones` is a local)
-  }
-  rc = upload_x(p);
-  if (rc != CALICO_OK) return rc;
-  {
-    // (the phase timer measures the LM loop: the pass records nothing into it)
-    const int mask = p->timer.mask;
-    p->timer.mask = 0;
-    rc = enqueue_jacobian_eval(p, nullptr, 0);      // R(x) into reduce buffer 0, all ranks' sum
-    p->timer.mask = mask;
-  }
-  if (rc != CALICO_OK) return rc;
-  // damping = clamp(v s², min, max) / (radius s²) = 0 with s = 1 and an infinite radius (FromR::damping, prepare_kernel)
-  launch_init_state(cv.st.p, std::numeric_limits<double>::infinity(), 0.0, s);
-  sa.st = cv.st.p; sa.scale = cv.scale.p; sa.dadd = cv.dadd.p; sa.y = cv.y.p; sa.zbuf = cv.zbuf.p; sa.progress = nullptr;
   LmOptionsDev o = {};
-  o.min_lm_diagonal = 1e-6; o.max_lm_diagonal = 1e32;
-  (void)hipGetLastError();
+  rc = begin_undamped_pass(p, {cv.st, cv.scale, cv.dadd, cv.y, cv.zbuf}, sa, o);
+  if (rc != CALICO_OK) return rc;
   if (want_cp) {      // (reads the band and E of R as the evaluation left them: ahead of the reduction)
     launch_cp_covariance_band(ca, s);
     HIP_TRY(p, hipGetLastError());
@@ -3188,6 +3228,212 @@ int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double*
   HIP_TRY(p, hipGetLastError());
   HIP_TRY(p, hipMemcpyAsync(out, cv.st_out.p, size_t(n) * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(p, hipStreamSynchronize(s));
+  return CALICO_OK;
+}
+
+void calico_default_observability_options(calico_observability_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->weak_threshold = 1e-10;
+  o->min_relative_pivot = 1e-12;
+}
+
+// The spectrum of S̃ = D⁻¹ (C - Eᵀ A⁻¹ E) D⁻¹ at the current values: the covariance pass's evaluation and undamped reduction
+// (begin_undamped_pass), the band's own factorisation for its minimum relative pivot (cp_band_factor_kernel, natural order:
+// is A invertible at all?), then observability_kernel (obs_kernels.hip). Leaves alone what the covariance pass leaves alone,
+// and the stored covariance.
+int32_t calico_observability_compute(calico_problem* p, const calico_observability_options* opt) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  calico_observability_options def;
+  calico_default_observability_options(&def);
+  if (!opt) opt = &def;
+  if (!(opt->min_relative_pivot >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "min_relative_pivot must be >= 0");
+  if (!(opt->weak_threshold >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "weak_threshold must be >= 0");
+  if (p->world > 1 && !p->has_exchange())
+    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
+  int rc = finalize(p);
+  if (rc != CALICO_OK) return rc;
+  HIP_TRY(p, hipSetDevice(p->device));
+  calico_problem::Observability& ob = p->obs;
+  ob.valid = false;
+  SolveArgs sa = make_solve_args(p);
+  const int mc = p->m, m = sa.m;
+  if (mc > observability_max_border())
+    return p->set_error(CALICO_UNIMPLEMENTED, "observability: border of " + std::to_string(mc) + " columns (at most " +
+                                                  std::to_string(observability_max_border()) + ")");
+  if (m > observability_max_dim())
+    return p->set_error(CALICO_UNIMPLEMENTED, "observability: reduced system of " + std::to_string(m) + " rows (at most " +
+                                                  std::to_string(observability_max_dim()) + ")");
+  const bool have_band = p->n_cp > 0 && p->order <= cp_covariance_max_order();
+  CpCovArgs ca = {};
+  if (have_band) {
+    const int n_cp = p->n_cp, k = p->order;
+    HIP_TRY(p, ob.cp_dq.alloc(6 * size_t(n_cp))); HIP_TRY(p, ob.cp_L.alloc(size_t(n_cp) * k * 36)); HIP_TRY(p, ob.cp_Li.alloc(size_t(n_cp) * 36));
+    HIP_TRY(p, ob.cp_info.alloc(2));
+    ca.R = sa.R; ca.off_B = sa.off_B(); ca.off_E = sa.off_E(); ca.n_cp = n_cp; ca.k = k; ca.mc = mc;
+    ca.dq = ob.cp_dq.p; ca.L = ob.cp_L.p; ca.Li = ob.cp_Li.p; ca.info = ob.cp_info.p;
+  }
+  const bool in_lds = observability_in_lds(m, mc);
+  const size_t n2 = size_t(mc) * mc;
+  HIP_TRY(p, ob.lam.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.vec.alloc(n2 + 1)); HIP_TRY(p, ob.mat.alloc(n2 + 1));
+  HIP_TRY(p, ob.dvec.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.info.alloc(8));
+  if (!in_lds) HIP_TRY(p, ob.work.alloc(observability_work_doubles(m, mc)));
+  HIP_TRY(p, configure_observability_kernel());
+  hipStream_t s = p->stream;
+  LmOptionsDev o = {};
+  rc = begin_undamped_pass(p, {ob.st, ob.scale, ob.dadd, ob.y, ob.zbuf}, sa, o);
+  if (rc != CALICO_OK) return rc;
+  if (have_band) {      // (reads the band of R as the evaluation left it: ahead of the reduction)
+    launch_cp_band_factor(ca, s);
+    HIP_TRY(p, hipGetLastError());
+  }
+  if (mc > 0) {
+    enqueue_linear_solve(p, sa, o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
+    HIP_TRY(p, hipGetLastError());
+    launch_observability(sa.Spart, reduced_schur_slices(sa), m, mc, sa.R + sa.off_C(), ob.st.p, ob.work.p, ob.lam.p, ob.vec.p, ob.mat.p,
+                         ob.dvec.p, ob.info.p, s);
+    HIP_TRY(p, hipGetLastError());
+  }
+  double info[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, in_lds ? 1.0 : 0.0, 0.0};
+  double cp_info[2] = {1.0, 0.0};
+  std::vector<double> R01(2), lam(size_t(mc), 0.0);
+  HIP_TRY(p, hipMemcpyAsync(R01.data(), p->d_R.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  ob.vectors.assign(n2, 0.0); ob.matrix.assign(n2, 0.0); ob.d.assign(size_t(mc), 0.0);
+  if (have_band) HIP_TRY(p, hipMemcpyAsync(cp_info, ob.cp_info.p, sizeof(cp_info), hipMemcpyDeviceToHost, s));
+  if (mc > 0) {
+    HIP_TRY(p, hipMemcpyAsync(info, ob.info.p, sizeof(info), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(lam.data(), ob.lam.p, lam.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(ob.vectors.data(), ob.vec.p, n2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(ob.matrix.data(), ob.mat.p, n2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(p, hipMemcpyAsync(ob.d.data(), ob.dvec.p, size_t(mc) * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(p, hipStreamSynchronize(s));
+  if (R01[1] > 0.0) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: the residual evaluation failed at the current parameter values");
+  const int flags = int(info[1]), cpf = int(cp_info[1]);
+  ob.min_relative_pivot_band = cp_info[0]; ob.min_relative_pivot_root = info[0];
+  if (cpf & 1) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: the trajectory's control-point block of JᵀJ is not finite");
+  // A itself is singular: S does not exist. The band's own pivot (natural order), the tree levels' flag, the root rows' pivot
+  // (checked ahead of the reduced system's values: an elimination that failed leaves non-finite ones behind).
+  if ((cpf & 2) || cp_info[0] < opt->min_relative_pivot || (flags & (2 | 4)) || info[0] < opt->min_relative_pivot) {
+    char msg[512];
+    std::snprintf(msg, sizeof(msg), "observability: the trajectory's control-point band of JᵀJ is rank deficient (minimum relative pivot %.3e of "
+                  "the band, %.3e of the root rows, threshold %.3e%s): the data do not determine the trajectory, so the calibration's Schur "
+                  "complement does not exist", cp_info[0], info[0], opt->min_relative_pivot,
+                  (flags & 4) ? "; a block of the control points' elimination is not positive definite" : "");
+    return p->set_error(CALICO_FAILED_PRECONDITION, msg);
+  }
+  if (flags & 1) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: non-finite value in the reduced system");
+  if (flags & 16)
+    return p->set_error(CALICO_INTERNAL, "observability: the Jacobi eigensolver did not converge in " + std::to_string(int(info[4])) + " sweeps");
+  if (flags & 8) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: non-finite value in the result");
+  ob.dim = mc; ob.n_unobserved = int(info[2]); ob.kept = mc > 0 ? int(info[3]) : 0; ob.sweeps = int(info[4]); ob.rotations = int(info[5]);
+  ob.in_lds = int(info[6]); ob.reduced_rows = int(info[7]);
+  if (ob.kept < 0 || ob.kept > mc) return p->set_error(CALICO_INTERNAL, "observability: kept columns out of range");
+  ob.eigenvalues.assign(lam.begin(), lam.begin() + ob.kept);
+  ob.n_weak = 0;
+  for (double v : ob.eigenvalues) ob.n_weak += v < opt->weak_threshold ? 1 : 0;
+  ob.blocks.resize(p->blocks.size());
+  for (size_t i = 0; i < p->blocks.size(); ++i) {
+    const HBlock& h = p->blocks[i];
+    const bool in = !h.constant && h.used;
+    const bool is_cp = h.tan >= 0 && h.tan < 6 * p->n_cp;
+    const int tsize = h.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION ? 3 : h.size;
+    ob.blocks[i] = {in ? (is_cp ? -2 : h.tan - 6 * p->n_cp) : -1, tsize};
+  }
+  ob.valid = true;
+  return CALICO_OK;
+}
+
+namespace {
+const char* const kNoObservability = "no observability report of this problem: call calico_observability_compute (again, if the problem "
+                                     "changed) and check its status";
+bool observability_ready(const calico_problem* p) { return p->obs.valid && !p->dirty; }
+// row i of the report in the requested units: v_i, or δ_i = D⁻¹ v_i / |D⁻¹ v_i|
+void observability_direction(const calico_problem::Observability& ob, int i, int tangent_units, double* out) {
+  const double* v = ob.vectors.data() + size_t(i) * ob.dim;
+  if (!tangent_units) { std::copy(v, v + ob.dim, out); return; }
+  double nrm = 0.0;
+  for (int j = 0; j < ob.dim; ++j) { out[j] = ob.d[size_t(j)] > 0.0 ? v[j] / ob.d[size_t(j)] : 0.0; nrm += out[j] * out[j]; }
+  nrm = std::sqrt(nrm);
+  if (nrm > 0.0) for (int j = 0; j < ob.dim; ++j) out[j] /= nrm;
+}
+}  // namespace
+
+int32_t calico_observability_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, int32_t* n_weak, double* lambda_min,
+                                  double* lambda_max, int32_t* sweeps) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  const calico_problem::Observability& ob = p->obs;
+  if (dim) *dim = ob.dim;
+  if (n_unobserved) *n_unobserved = ob.n_unobserved;
+  if (n_weak) *n_weak = ob.n_weak;
+  if (lambda_min) *lambda_min = ob.eigenvalues.empty() ? 0.0 : ob.eigenvalues.front();
+  if (lambda_max) *lambda_max = ob.eigenvalues.empty() ? 0.0 : ob.eigenvalues.back();
+  if (sweeps) *sweeps = ob.sweeps;
+  return CALICO_OK;
+}
+
+int32_t calico_observability_get_spectrum(calico_problem* p, double* eigenvalues) {
+  if (!p || !eigenvalues) return CALICO_INVALID_ARGUMENT;
+  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  std::copy(p->obs.eigenvalues.begin(), p->obs.eigenvalues.end(), eigenvalues);
+  return CALICO_OK;
+}
+
+int32_t calico_observability_get_directions(calico_problem* p, int32_t first, int32_t count, int32_t tangent_units, double* out) {
+  if (!p || !out) return CALICO_INVALID_ARGUMENT;
+  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  const calico_problem::Observability& ob = p->obs;
+  if (first < 0 || count < 0 || first > ob.kept || count > ob.kept - first)
+    return p->set_error(CALICO_INVALID_ARGUMENT, "observability: directions [" + std::to_string(first) + ", " + std::to_string(int64_t(first) + count) +
+                                                     ") out of range (" + std::to_string(ob.kept) + " directions)");
+  for (int i = 0; i < count; ++i) observability_direction(ob, first + i, tangent_units, out + size_t(i) * ob.dim);
+  return CALICO_OK;
+}
+
+int32_t calico_observability_get_block(calico_problem* p, int32_t index, int32_t block_id, int32_t tangent_units, double* out, double* share) {
+  if (!p || (!out && !share)) return CALICO_INVALID_ARGUMENT;
+  const int nb = int(p->blocks.size());
+  if (block_id < 0 || block_id >= nb) return p->set_error(CALICO_INVALID_ARGUMENT, "observability: unknown parameter block id");
+  if (!observability_ready(p) || size_t(nb) != p->obs.blocks.size()) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  const calico_problem::Observability& ob = p->obs;
+  if (index < 0 || index >= ob.kept) return p->set_error(CALICO_INVALID_ARGUMENT, "observability: direction index out of range");
+  const calico_problem::Observability::Blk& B = ob.blocks[size_t(block_id)];
+  if (B.off == -2)
+    return p->set_error(CALICO_INVALID_ARGUMENT, "observability: a control point is not part of the report (the trajectory is eliminated)");
+  if (out) std::fill(out, out + B.tsize, 0.0);
+  if (share) *share = 0.0;
+  if (B.off == -1) return CALICO_OK;      // constant / unused blocks: zeros
+  if (B.off < 0 || B.off + B.tsize > ob.dim) return p->set_error(CALICO_INTERNAL, "observability: block layout out of range");
+  if (out) {
+    std::vector<double> dir(size_t(ob.dim));
+    observability_direction(ob, index, tangent_units, dir.data());
+    std::copy(dir.begin() + B.off, dir.begin() + B.off + B.tsize, out);
+  }
+  if (share) {
+    const double* v = ob.vectors.data() + size_t(index) * ob.dim + B.off;
+    double sh = 0.0;
+    for (int j = 0; j < B.tsize; ++j) sh += v[j] * v[j];
+    *share = sh;
+  }
+  return CALICO_OK;
+}
+
+int32_t calico_observability_get_matrix(calico_problem* p, double* out) {
+  if (!p || !out) return CALICO_INVALID_ARGUMENT;
+  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  std::copy(p->obs.matrix.begin(), p->obs.matrix.end(), out);
+  return CALICO_OK;
+}
+
+// test hook (calico_hip_testing.h)
+int32_t calico_debug_observability_info(calico_problem* p, double* out, int32_t n) {
+  if (!p || !out || n < 0) return CALICO_INVALID_ARGUMENT;
+  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
+  const calico_problem::Observability& ob = p->obs;
+  const double v[6] = {double(ob.in_lds), double(ob.kept), double(ob.reduced_rows), double(ob.rotations), ob.min_relative_pivot_band,
+                       ob.min_relative_pivot_root};
+  for (int i = 0; i < n && i < 6; ++i) out[i] = v[i];
   return CALICO_OK;
 }
 

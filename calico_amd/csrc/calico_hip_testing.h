@@ -50,6 +50,12 @@ int32_t calico_debug_last_step(calico_problem* problem, int32_t n, double* step,
  * order 1..6 and a lane 0..63 -- byte offsets of the lane's tile entries in the band's storage and which of them exist. */
 int32_t calico_debug_roll_table(int32_t spline_order, int32_t lane, uint32_t* out48);
 
+/* What the last calico_observability_compute did. out[0..n) (n <= 6) receives: [0] 1: the eigensolver's matrices lived in
+ * LDS, 0: in the global workspace, [1] kept columns, [2] rows of the compact reduced system (root / separator rows + kept
+ * columns), [3] rotations applied, [4] minimum relative pivot of the trajectory's band, [5] of the root rows.
+ * CALICO_FAILED_PRECONDITION without a successful compute. */
+int32_t calico_debug_observability_info(calico_problem* problem, double* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -543,6 +543,8 @@ void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s) {      // read
   if (a.mc > 0) hipLaunchKernelGGL(cp_solve_kernel, dim3((a.mc + kCpCols - 1) / kCpCols), dim3(6 * kCpCols), 0, s, a);
   hipLaunchKernelGGL(cp_takahashi_kernel, dim3(1), dim3(kCpThreads), 0, s, a);
 }
+// the band's factorisation alone (dq, L, Li, info of `a`): the observability pass wants its minimum relative pivot
+void launch_cp_band_factor(const CpCovArgs& a, hipStream_t s) { hipLaunchKernelGGL(cp_band_factor_kernel, dim3(1), dim3(kCpThreads), 0, s, a); }
 void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s) {    // behind covariance_kernel (Σ_EE)
   const size_t ne = size_t(6) * a.n_cp * a.mc;
   if (ne > 0) hipLaunchKernelGGL(cp_cross_kernel, dim3(unsigned((ne + 255) / 256)), dim3(256), 0, s, a);

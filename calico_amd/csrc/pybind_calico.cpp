@@ -312,6 +312,37 @@ PYBIND11_MODULE(_calico, m) {
       .def_readwrite("max_trust_region_radius", &SolverOptions::max_trust_region_radius);
   m.def("DefaultSolverOptions", &DefaultSolverOptions);
 
+  // the observability report: spectrum, directions and where they live, as numpy arrays / lists of (name, part, share)
+  py::class_<Observability>(m, "Observability")
+      .def("Dimension", &Observability::Dimension)
+      .def("NumUnobserved", &Observability::NumUnobserved)
+      .def("NumWeak", &Observability::NumWeak)
+      .def("Sweeps", &Observability::Sweeps)
+      .def("Eigenvalues",
+           [](const Observability& o) {
+             const std::vector<double> v = o.Eigenvalues();
+             return py::array_t<double>(py::ssize_t(v.size()), v.data());
+           })
+      .def("Direction",
+           [](const Observability& o, int i, bool tangent_units) {
+             const std::vector<double> v = o.Direction(i, tangent_units);
+             if (v.empty() && o.Dimension() > 0) throw std::out_of_range("observability: direction index out of range");
+             return py::array_t<double>(py::ssize_t(v.size()), v.data());
+           },
+           py::arg("index"), py::arg("tangent_units") = false)
+      .def("IntrinsicsShare",
+           [](const Observability& o, int i, std::shared_ptr<Sensor> s) {
+             auto sh = o.BlockShare(i, s->GetIntrinsics().data());
+             raise_if_error(sh.status());
+             return sh.value();
+           })
+      .def("Describe",
+           [](const Observability& o, int i) {
+             py::list out;
+             for (const Observability::Entry& e : o.Describe(i)) out.append(py::make_tuple(e.name, e.part, e.share));
+             return out;
+           });
+
   // ceres::Covariance's result: per-sensor blocks as numpy arrays (tangent space: 6 x 6 extrinsics [rotation | translation])
   py::class_<Covariance>(m, "Covariance")
       .def("Dimension", &Covariance::Dimension)
@@ -377,5 +408,16 @@ PYBIND11_MODULE(_calico, m) {
             raise_if_error(cov.status());
             return cov.value();
           },
-          py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0, py::arg("control_points") = false);
+          py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0, py::arg("control_points") = false)
+      .def(
+          "AnalyzeObservability",
+          [](BatchOptimizer& self, double weak_threshold, double min_relative_pivot, int device) {
+            calico_observability_options o = DefaultObservabilityOptions();
+            if (weak_threshold >= 0.0) o.weak_threshold = weak_threshold;
+            if (min_relative_pivot >= 0.0) o.min_relative_pivot = min_relative_pivot;
+            auto obs = self.AnalyzeObservability(o, device);
+            raise_if_error(obs.status());
+            return obs.value();
+          },
+          py::arg("weak_threshold") = -1.0, py::arg("min_relative_pivot") = -1.0, py::arg("device") = 0);
 }

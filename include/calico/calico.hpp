@@ -183,6 +183,7 @@ inline SolverOptions DefaultSolverOptions() { SolverOptions o; calico_default_so
 // ABI, runs the device LM and writes the estimates back IN PLACE.
 // ---------------------------------------------------------------------------
 class Covariance;
+class Observability;
 class Problem {
  public:
   Problem() = default;
@@ -228,6 +229,8 @@ class Problem {
   }
   /// ceres::Covariance::Compute over the problem as it stands (a fresh handle; the values are not changed): see Covariance
   Status ComputeCovariance(const calico_covariance_options& options, Covariance* out, int device = 0);
+  /// calico_observability_compute over the problem as it stands (a fresh handle; the values are not changed): see Observability
+  Status AnalyzeObservability(const calico_observability_options& options, Observability* out, int device = 0);
   /// problem.EvaluateResidualBlock(id, /*apply_loss_function=*/false, ...) for every block of a sensor.
   Status EvaluateResiduals(int sensor, std::vector<double>* out, std::vector<uint8_t>* valid) {
     if (!h_) return FailedPreconditionError("problem has not been solved");
@@ -355,6 +358,80 @@ inline Status Problem::ComputeCovariance(const calico_covariance_options& option
   return OkStatus();
 }
 inline calico_covariance_options DefaultCovarianceOptions() { calico_covariance_options o; calico_default_covariance_options(&o); return o; }
+
+/// The observability report (calico_observability_* in include/calico_hip.h for the definition): the spectrum of the
+/// calibration's equilibrated Schur complement, ascending, and its directions; blocks keyed by the parameter pointers the
+/// Problem was given. A rank-deficient calibration is not an error: NumWeak() > 0 and Describe() says where the weak
+/// directions live. It keeps the library handle it was computed on until destroyed.
+class Observability {
+ public:
+  struct Entry { std::string name, part; double share; };      // e.g. {"gyroscope", "intrinsics", 0.52}
+  int Dimension() const { int32_t v = 0; if (h_) calico_observability_info(h_.get(), &v, nullptr, nullptr, nullptr, nullptr, nullptr); return v; }
+  int NumUnobserved() const { int32_t v = 0; if (h_) calico_observability_info(h_.get(), nullptr, &v, nullptr, nullptr, nullptr, nullptr); return v; }
+  int NumWeak() const { int32_t v = 0; if (h_) calico_observability_info(h_.get(), nullptr, nullptr, &v, nullptr, nullptr, nullptr); return v; }
+  int Sweeps() const { int32_t v = 0; if (h_) calico_observability_info(h_.get(), nullptr, nullptr, nullptr, nullptr, nullptr, &v); return v; }
+  /// the eigenvalues, ascending (Dimension() - NumUnobserved() of them)
+  std::vector<double> Eigenvalues() const {
+    std::vector<double> v(static_cast<size_t>(std::max(0, Dimension() - NumUnobserved())), 0.0);
+    if (h_ && !v.empty()) calico_observability_get_spectrum(h_.get(), v.data());
+    return v;
+  }
+  /// direction i of the ascending list over the border's tangent rows: the unit eigenvector, or (tangent_units) δ_i in the
+  /// parameters' own units; empty on error
+  std::vector<double> Direction(int i, bool tangent_units = false) const {
+    std::vector<double> v(static_cast<size_t>(Dimension()), 0.0);
+    if (!h_ || v.empty() || calico_observability_get_directions(h_.get(), i, 1, tangent_units ? 1 : 0, v.data()) != CALICO_OK) v.clear();
+    return v;
+  }
+  /// the share of direction i's unit eigenvector that lies in one parameter block (0 for a constant block)
+  StatusOr<double> BlockShare(int i, const double* parameter) const {
+    if (!h_) return FailedPreconditionError("observability has not been computed");
+    const auto it = ids_.find(parameter);
+    if (it == ids_.end()) return InvalidArgumentError("observability: parameter block not in the problem");
+    double share = 0.0;
+    const int st = calico_observability_get_block(h_.get(), i, it->second, 0, nullptr, &share);
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+    return share;
+  }
+  /// the entries of direction i in one parameter block (tangent size: 3 for a quaternion)
+  Status Block(int i, const double* parameter, bool tangent_units, double* out) const {
+    if (!h_) return FailedPreconditionError("observability has not been computed");
+    const auto it = ids_.find(parameter);
+    if (it == ids_.end()) return InvalidArgumentError("observability: parameter block not in the problem");
+    const int st = calico_observability_get_block(h_.get(), i, it->second, tangent_units ? 1 : 0, out, nullptr);
+    return st == CALICO_OK ? OkStatus() : Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+  }
+  /// a name for a block in Describe(): BatchOptimizer::AnalyzeObservability labels every sensor's blocks
+  void Label(const double* parameter, const std::string& name, const std::string& part) { labels_.push_back({parameter, name, part}); }
+  /// where direction i lives: the labelled blocks with a share above min_share, largest share first
+  std::vector<Entry> Describe(int i, double min_share = 1e-12) const {
+    std::vector<Entry> out;
+    for (const LabelRec& l : labels_) {
+      const auto sh = BlockShare(i, l.ptr);
+      if (sh.ok() && sh.value() > min_share) out.push_back({l.name, l.part, sh.value()});
+    }
+    std::stable_sort(out.begin(), out.end(), [](const Entry& a, const Entry& b) { return a.share > b.share; });
+    return out;
+  }
+
+ private:
+  friend class Problem;
+  struct LabelRec { const double* ptr; std::string name, part; };
+  std::shared_ptr<calico_problem> h_;
+  std::map<const double*, int32_t> ids_;
+  std::vector<LabelRec> labels_;
+};
+
+inline Status Problem::AnalyzeObservability(const calico_observability_options& options, Observability* out, int device) {
+  if (Status b = Build(device); !b.ok()) return b;
+  if (int st = calico_observability_compute(h_, &options)) return Err(st);
+  out->ids_.clear();
+  for (size_t i = 0; i < blocks_.size(); ++i) out->ids_[blocks_[i].ptr] = ids_[i];
+  out->h_ = std::shared_ptr<calico_problem>(h_, calico_problem_destroy);      // the result stays with its handle
+  h_ = nullptr;
+  return OkStatus();
+}
+inline calico_observability_options DefaultObservabilityOptions() { calico_observability_options o; calico_default_observability_options(&o); return o; }
 
 namespace utils {
 /// optimization_utils.h:51-68
@@ -1003,6 +1080,32 @@ class BatchOptimizer {
     const Status st = problem.ComputeCovariance(options, &cov, device);
     if (!st.ok()) return st;
     return cov;
+  }
+  /// Which directions of the calibration the data determine, at the current values (the problem is rebuilt, as
+  /// ComputeCovariance does). Every sensor's blocks are labelled with its name: Describe(i) reads "gyroscope intrinsics 0.52, ...".
+  StatusOr<Observability> AnalyzeObservability(const calico_observability_options& options = DefaultObservabilityOptions(), int device = 0) {
+    if (!world_model_ || !trajectory_) return FailedPreconditionError("world model and trajectory must be added before AnalyzeObservability()");
+    Problem problem;
+    world_model_->AddParametersToProblem(problem);
+    trajectory_->AddParametersToProblem(problem);
+    for (sensors::Sensor* sensor : sensors_) {
+      const auto np = sensor->AddParametersToProblem(problem);
+      if (!np.ok()) return np.status();
+      const auto nr = sensor->AddResidualsToProblem(problem, *trajectory_, *world_model_);
+      if (!nr.ok()) return nr.status();
+    }
+    Observability obs;
+    const Status st = problem.AnalyzeObservability(options, &obs, device);
+    if (!st.ok()) return st;
+    for (size_t i = 0; i < sensors_.size(); ++i) {
+      const sensors::Sensor* s = sensors_[i];
+      const std::string name = s->GetName().empty() ? "sensor " + std::to_string(i) : s->GetName();
+      obs.Label(s->GetIntrinsics().data(), name, "intrinsics");
+      obs.Label(s->GetExtrinsics().rotation().data(), name, "rotation");
+      obs.Label(s->GetExtrinsics().translation().data(), name, "translation");
+      if (const auto* sc = dynamic_cast<const sensors::SensorCommon*>(s)) obs.Label(sc->LatencyData(), name, "latency");
+    }
+    return obs;
   }
   StatusOr<Summary> Optimize(const SolverOptions& options = DefaultSolverOptions(), int device = 0) {
     if (!world_model_ || !trajectory_) return FailedPreconditionError("world model and trajectory must be added before Optimize()");

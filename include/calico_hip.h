@@ -360,7 +360,8 @@ void calico_default_covariance_options(calico_covariance_options* o);
  * CALICO_FAILED_PRECONDITION saying so. A border of any width works, none (every calibration block constant) included.
  * On a sharded handle every rank computes the same blocks from the all-reduced normal equations (no further exchange). The control
  * points' blocks are bit-identical from compute to compute; the border's Σ does not depend on control_points. */
-/* Compute Σ (finalises the problem if needed). o == NULL: the defaults. */
+/* Compute Σ (finalises the problem if needed). o == NULL: the defaults. A problem refused as rank deficient can be taken to
+ * calico_observability_compute (below), which reports which directions of the border are undetermined. */
 int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_options* o);
 /* Size of Σ (the border's tangent dimension), the number of structurally unobserved columns left out, and the minimum
  * relative pivot of the factorisation. CALICO_FAILED_PRECONDITION without a successful compute. */
@@ -384,6 +385,70 @@ int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double*
 /* Number of control points and spline order of the trajectory's blocks, and the minimum relative pivot of the band's
  * factorisation. CALICO_FAILED_PRECONDITION as calico_covariance_trajectory. */
 int32_t calico_covariance_trajectory_info(calico_problem* p, int32_t* n_cp, int32_t* order, double* min_relative_pivot_band);
+
+/* ---- observability of the calibration ---------------------------------- */
+/* Which directions of the dense border the data determine, and how well: the answer calico_covariance_compute cannot give
+ * when it refuses a problem as rank deficient (it works on the well-posed ones too). Definition, at the current values,
+ * with H = JᵀJ = [[A, E], [Eᵀ, C]] (A: control points, C: the dense border in the tangent order of
+ * calico_num_effective_parameters; the Gauss-Newton matrix exactly as the covariance pass evaluates it: sigma-weighted,
+ * robust loss through the corrector, quaternion tangent, no LM damping, no Jacobi scaling):
+ *  - S = C - Eᵀ A⁻¹ E, the Schur complement onto the border (dim x dim): the information on the calibration that is left
+ *    when the trajectory is free to follow.
+ *  - Border columns whose C diagonal is exactly 0.0 (no residual depends on them) are left out, as in the covariance:
+ *    n_unobserved of them, dim_kept = dim - n_unobserved.
+ *  - S̃ = D⁻¹ S D⁻¹ on the kept columns, D = sqrt(diag C): the column norms of J, NOT diag S (a column the trajectory
+ *    explains entirely has diag S ~ 0). Eigenvalues of S̃ lie in [0, dim_kept]; an eigenvalue is the share of a
+ *    direction's information that neither the trajectory nor the other directions explain.
+ *  - The report is S̃ = V Λ Vᵀ, eigenvalues ascending, each eigenvector's largest-magnitude entry positive (lowest index on
+ *    a tie), computed on the device by a cyclic Jacobi method with a fixed order of operations: repeated computes, and the
+ *    ranks of a sharded handle, hold bit-identical reports.
+ *  - Direction i in TANGENT UNITS: δ_i = D⁻¹ v_i / |D⁻¹ v_i|, zero in the dropped columns. For a null direction S δ_i = 0:
+ *    moving the calibration along δ_i (the trajectory following by -A⁻¹ E δ_i) leaves the cost unchanged to second order.
+ *  - n_weak = number of eigenvalues below weak_threshold.
+ * A rank-deficient border is NOT an error: the compute returns CALICO_OK and n_weak > 0. A itself must be invertible for S
+ * to exist: a pivot of the trajectory's equilibrated block band (natural order), or of the root / separator rows of the
+ * elimination, that is not positive or below min_relative_pivot makes the compute return CALICO_FAILED_PRECONDITION with a
+ * message that names the trajectory as the deficient part (the covariance's border message does not) and both pivots.
+ * Borders of up to 256 columns (beyond: CALICO_UNIMPLEMENTED with the two numbers); CALICO_INTERNAL if the eigensolver
+ * does not converge in 30 sweeps.
+ * Contracts as the covariance's: the result lives on the handle until the next calico_observability_compute or
+ * calico_problem_destroy; a structural change (blocks, sensors, observations, shard) makes the readers return
+ * CALICO_FAILED_PRECONDITION until the next compute, a change of values does not; the compute leaves the parameters, the LM
+ * state, the iteration log, the last summary and a stored covariance alone (a solve after it is bit-identical to one
+ * without it); on a sharded handle it takes the same exchange as an evaluation (every rank calls it) and every rank holds
+ * the same report. */
+typedef struct calico_observability_options {
+  double weak_threshold;        /* eigenvalues of S̃ below this count as weak (>= 0) */
+  double min_relative_pivot;    /* for the trajectory's band and the root rows (>= 0) */
+  int32_t reserved[4];
+} calico_observability_options;
+/* Defaults. min_relative_pivot = 1e-12 (as calico_default_covariance_options). weak_threshold = 1e-10, inside the gap the test
+ * scenes show (tests/test_gpu_observability.py prints the spectra): exact deficiencies -- OpenCV8 at zero distortion, VectorNav
+ * IMUs with a free rotation, a free chart pose, configs[3] and configs[4] of BASELINE.json as they are -- come out of the device
+ * at |λ| <= 7.3e-16 (the CPU reference built from the oracle: <= 5.8e-15), the smallest eigenvalue of a well-posed or merely weak
+ * direction is 8.1e-7 (the free-chart-pose scene): four decades on either side. That scene's three directions near 1e-6 are
+ * deliberately NOT counted by the default: at the start values they are weak, not null, and the spectrum shows them. */
+void calico_default_observability_options(calico_observability_options* o);
+/* Compute the report (finalises the problem if needed). o == NULL: the defaults. */
+int32_t calico_observability_compute(calico_problem* p, const calico_observability_options* o);
+/* dim (the border's tangent dimension), the structurally unobserved columns left out, the eigenvalues below weak_threshold,
+ * the smallest and the largest eigenvalue, the Jacobi sweeps taken. Any output pointer may be NULL.
+ * CALICO_FAILED_PRECONDITION without a successful compute. */
+int32_t calico_observability_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, int32_t* n_weak, double* lambda_min,
+                                  double* lambda_max, int32_t* sweeps);
+/* The dim_kept = dim - n_unobserved eigenvalues of S̃, ascending. */
+int32_t calico_observability_get_spectrum(calico_problem* p, double* eigenvalues /* dim_kept */);
+/* Rows [first, first + count) of the ascending list; out = count x dim (border tangent order, zeros in dropped columns);
+ * tangent_units = 0: v_i (orthonormal), 1: δ_i. CALICO_INVALID_ARGUMENT for a range outside [0, dim_kept]. */
+int32_t calico_observability_get_directions(calico_problem* p, int32_t first, int32_t count, int32_t tangent_units, double* out);
+/* The entries of direction `index` that belong to one parameter block (tangent size: 3 for a quaternion), and the block's
+ * share Σ v_i[rows of block]² of the unit eigenvector (the shares of all blocks add up to 1). out or share may be NULL (not
+ * both). A constant or unused block reads back zeros; CALICO_INVALID_ARGUMENT for an unknown id, a control point (the
+ * trajectory is eliminated: not part of the report) or an index outside [0, dim_kept). */
+int32_t calico_observability_get_block(calico_problem* p, int32_t index, int32_t block_id, int32_t tangent_units, double* out,
+                                       double* share);
+/* S̃ itself, dim x dim row-major, zeros in dropped rows / columns. */
+int32_t calico_observability_get_matrix(calico_problem* p, double* out);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
