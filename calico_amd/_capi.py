@@ -80,6 +80,11 @@ class ObservabilityOptions(C.Structure):
     _fields_ = [("weak_threshold", C.c_double), ("min_relative_pivot", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
+class PredictionOptions(C.Structure):
+    """calico_prediction_options."""
+    _fields_ = [("apply_loss", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -134,6 +139,7 @@ ABI_SYMBOLS = [
     "comm_get_unique_id", "comm_init_rccl", "comm_info", "problem_finalize", "plan_cache_stats", "plan_cache_clear",
     "default_covariance_options", "covariance_compute", "covariance_info", "covariance_get_dense", "covariance_get_block",
     "covariance_trajectory", "covariance_trajectory_info",
+    "default_prediction_options", "prediction_covariance",
     "default_observability_options", "observability_compute", "observability_info", "observability_get_spectrum",
     "observability_get_directions", "observability_get_block", "observability_get_matrix",
 ]
@@ -201,6 +207,8 @@ class CApi:
             g("covariance_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
             g("covariance_trajectory", C.c_int32, [P, C.c_int64, D, D])
             g("covariance_trajectory_info", C.c_int32, [P, I, I, D])
+            g("default_prediction_options", None, [C.POINTER(PredictionOptions)])
+            g("prediction_covariance", C.c_int32, [P, C.c_int32, C.POINTER(PredictionOptions), D, D, C.POINTER(C.c_uint8)])
             g("default_observability_options", None, [C.POINTER(ObservabilityOptions)])
             g("observability_compute", C.c_int32, [P, C.POINTER(ObservabilityOptions)])
             g("observability_info", C.c_int32, [P, I, I, I, D, D, I])
@@ -260,6 +268,8 @@ class Problem:
         self._keep = []
         self._sizes = {}      # block id -> ambient size, of the blocks added through this object
         self._manifolds = {}  # block id -> manifold, of the same blocks
+        self._sensor_dim = {}  # sensor id -> residual dimension, of the sensors added through this object
+        self._sensor_n = {}    # sensor id -> registered observations
 
     def close(self):
         if self.h:
@@ -343,15 +353,19 @@ class Problem:
         out = C.c_int32(-1)
         self._check(self.api.problem_add_sensor(self.h, kind, model, intr, q, t, lat, grav, float(sigma), loss,
                                                 float(loss_scale), C.byref(out)))
+        self._sensor_dim[out.value] = 2 if kind == SENSOR_CAMERA else 3
+        self._sensor_n[out.value] = 0
         return out.value
 
     def add_camera_residuals(self, sensor, pixels, stamps, body_ids, point_blocks):
         px, st, b, p = _f64(pixels), _f64(stamps), _i32(body_ids), _i32(point_blocks)
         self._check(self.api.problem_add_camera_residuals(self.h, sensor, st.size, _dp(px), _dp(st), _ip(b), _ip(p)))
+        self._sensor_n[sensor] = self._sensor_n.get(sensor, 0) + st.size
 
     def add_imu_residuals(self, sensor, meas, stamps):
         m, st = _f64(meas), _f64(stamps)
         self._check(self.api.problem_add_imu_residuals(self.h, sensor, st.size, _dp(m), _dp(st)))
+        self._sensor_n[sensor] = self._sensor_n.get(sensor, 0) + st.size
 
     def solve(self, options=None):
         o = options if options is not None else self.api.default_options()
@@ -466,6 +480,20 @@ class Problem:
         out = np.zeros((len(t), 6, 6))
         self._check(self.api.covariance_trajectory(self.h, len(t), _dp(t), _dp(out)))
         return out
+
+    def prediction_covariance(self, sensor, apply_loss=True):
+        """calico_prediction_covariance for every registered observation of `sensor`, in insertion order: P_i = J_i Σ J_iᵀ
+        (n, d, d), the leverages trace(P_i) (n,) and the valid flags (n,) bool. Needs covariance_compute(control_points=True).
+        apply_loss=True: diagonal blocks of the hat matrix; False: prediction covariance of the whitened model output."""
+        n, d = self._sensor_n.get(sensor, 0), self._sensor_dim.get(sensor, 3)
+        o = PredictionOptions()
+        self.api.default_prediction_options(C.byref(o))
+        o.apply_loss = int(apply_loss)
+        cov, lev = np.zeros((n, d, d)), np.zeros(n)
+        valid = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.api.prediction_covariance(self.h, int(sensor), C.byref(o), _dp(cov), _dp(lev),
+                                                   valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return cov, lev, valid[:n].astype(bool)
 
     def covariance_block(self, block_a, block_b, tangent=False, sizes=None):
         """Block (block_a, block_b) of the last computed Σ. `sizes`: (rows, cols) of the requested form; by default taken

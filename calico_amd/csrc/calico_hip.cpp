@@ -51,6 +51,7 @@ void launch_inlier_mask(const double* res, uint8_t* valid_then_mask, const uint8
 void launch_mark_outliers(const double* res, const uint8_t* valid, uint8_t* active, int begin, int end, int dim,
                           double threshold, int* n_marked, hipStream_t s);
 hipError_t configure_eval_kernels(size_t max_lds_bytes);
+hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream);
 
 void launch_gather(double* R, const double* src, const int* out_idx_thin, const int64_t* ptr_thin, const int* idx_thin,
                    int n_thin, int n_thin8, int n_thin4, int thin_per_lane, const int* out_idx_fat, const int64_t* ptr_fat, const int* idx_fat, int n_fat,
@@ -436,10 +437,13 @@ struct PlanHost {
   int thin_per_lane = 6;       // sources per lane of a thin output's eight lanes (6: up to 48 sources, 12: up to 96)
   bool gather_fixed = false;   // the thin lists at a fixed stride (d_idx_fixed) instead of CSR
   bool dense_in_lds = true;
+  // calico_prediction_covariance: widest layout (columns) and longest work item (row stride) of the list of ALL work items,
+  // row length of the column map (d_pred_map)
+  int pred_cols = 0, pred_row_pad = 3, pred_map_stride = 1;
 };
 struct PlanDev {      // structure on the device: immutable once uploaded
   DevBuf<double> d_knots, d_basis, d_stamp;
-  DevBuf<int> d_ctrl_off, d_point_off, d_out_thin, d_idx_thin, d_idx_fixed, d_out_fat, d_idx_fat, d_prim_tab, d_bkeep, d_cp_block, d_gs_tab;
+  DevBuf<int> d_ctrl_off, d_point_off, d_out_thin, d_idx_thin, d_idx_fixed, d_out_fat, d_idx_fat, d_prim_tab, d_bkeep, d_cp_block, d_gs_tab, d_pred_map;
   DevBuf<int64_t> d_ptr_thin, d_ptr_fat;
   DevBuf<uint8_t> d_cp_active;
   DevBuf<SensorDev> d_sensors;
@@ -451,7 +455,7 @@ struct PlanDev {      // structure on the device: immutable once uploaded
   DevBuf<BcrNodeDev> d_bnodes;
 #define PLAN_DEV_BUFS(X) X(d_knots) X(d_basis) X(d_stamp) X(d_ctrl_off) X(d_point_off) X(d_out_thin) X(d_idx_thin) X(d_idx_fixed) X(d_out_fat) X(d_idx_fat) \
   X(d_prim_tab) X(d_bkeep) X(d_cp_block) X(d_gs_tab) X(d_ptr_thin) X(d_ptr_fat) X(d_cp_active) X(d_sensors) X(d_layouts) X(d_items) X(d_items_all)     \
-  X(d_jac_items) X(d_fitems) X(d_cells) X(d_blocks) X(d_bnodes)
+  X(d_jac_items) X(d_fitems) X(d_cells) X(d_blocks) X(d_bnodes) X(d_pred_map)
   void take_from(PlanDev& o) {
 #define X(n) n.take(o.n);
     PLAN_DEV_BUFS(X)
@@ -771,6 +775,7 @@ struct PlanTables {
   std::vector<FrameItemDev> fitems;
   std::vector<CellDev> cells;
   std::vector<int> prim_tab;
+  std::vector<int> pred_map;                    // [layout][pred_map_stride]: border offset of every calibration column (prediction covariance)
   size_t partials_end = 0;                      // end of [expanded blocks | item costs | compact frame records | row store]
   // gather lists: host-built CSR (thin / fat), or the table the device builds the thin ones from (gs_ok)
   bool gs_ok = false; int64_t gs_n_out = 0;
@@ -989,6 +994,21 @@ void plan_items(calico_problem* p, PlanTables& t) {
     if (it.seg >= t.seg_lo && it.seg < t.seg_hi) { t.items.push_back(it); p->n_obs_local += it.obs_count; }
   p->n_items = int(t.items.size());
   p->n_items_all = int(t.items_all.size());
+  // prediction covariance (prediction_items_kernel walks items_all): its staging area's sizes, and per layout the border
+  // offset -- row of Σ_EE, column of Σ_AE -- of every calibration column
+  {
+    int pc = 4, pr = 2, stride = 1;
+    for (const ItemDev& it : t.items_all) {
+      const LayoutDev& L = t.layouts[size_t(it.layout)];
+      pc = std::max(pc, L.ncols);
+      pr = std::max(pr, p->sensors[size_t(L.sensor)].dim() * it.obs_count);
+    }
+    for (const std::vector<int>& g : t.layout_gmap) stride = std::max(stride, int(g.size()));
+    p->pred_cols = pc; p->pred_row_pad = (((pr + 3) & ~3) + 1) | 1; p->pred_map_stride = stride;
+    t.pred_map.assign(std::max<size_t>(1, t.layouts.size()) * size_t(stride), 0);
+    for (size_t l = 0; l < t.layouts.size(); ++l)
+      for (size_t j = 0; j < t.layout_gmap[l].size(); ++j) t.pred_map[l * size_t(stride) + j] = t.layout_gmap[l][j] - 6 * p->n_cp;
+  }
 }
 
 // ---- the evaluation route: frames, cells, cell workgroups, generic and IMU items, the row store ----
@@ -1417,6 +1437,7 @@ int upload_plan(calico_problem* p, PlanTables& t) {
     launch_gather_pack_fixed(p->d_ptr_thin.p, p->d_idx_thin.p, p->n_thin, p->n_thin8, p->n_thin4, p->thin_per_lane, zero_slot, p->d_idx_fixed.p, s);
   }
   HIP_TRY(p, p->d_cells.upload(t.cells, s)); HIP_TRY(p, p->d_prim_tab.upload(t.prim_tab, s));
+  HIP_TRY(p, p->d_pred_map.upload(t.pred_map, s));
   if (p->use_bcr) {
     HIP_TRY(p, p->d_bnodes.upload(p->h_bcr_nodes, s)); HIP_TRY(p, p->d_bkeep.upload(t.bcr_keep, s));
     HIP_TRY(p, p->d_cp_block.upload(t.cp_block, s));
@@ -3228,6 +3249,73 @@ int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double*
   HIP_TRY(p, hipGetLastError());
   HIP_TRY(p, hipMemcpyAsync(out, cv.st_out.p, size_t(n) * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(p, hipStreamSynchronize(s));
+  return CALICO_OK;
+}
+
+void calico_default_prediction_options(calico_prediction_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->apply_loss = 1;
+}
+
+// P_i = J_i Σ J_iᵀ of every registered observation of a sensor (prediction_items_kernel): J_i at the current values, Σ the
+// device copies the last compute with control_points = 1 left (Σ_EE in cov.out, Σ_AE in cov.cp_sae, Σ_AA's band in
+// cov.cp_band). Output buffers of its own; nothing of the LM's, of the residual cache or of the stored reports is touched.
+int32_t calico_prediction_covariance(calico_problem* p, int32_t sid, const calico_prediction_options* opt, double* cov_out,
+                                     double* leverage_out, uint8_t* valid) {
+  if (!p) return CALICO_INVALID_ARGUMENT;
+  calico_prediction_options def;
+  calico_default_prediction_options(&def);
+  if (!opt) opt = &def;
+  if (sid < 0 || sid >= int(p->sensors.size())) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: unknown sensor id");
+  if (opt->apply_loss != 0 && opt->apply_loss != 1) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: apply_loss must be 0 or 1");
+  if (!cov_out && !leverage_out && !valid) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: no output buffer");
+  if (int rc = trajectory_result_ready(p)) return rc;
+  calico_problem::Covariance& cv = p->cov;
+  if (cv.n_cp != p->n_cp || cv.order != p->order || cv.dim != p->m) return p->set_error(CALICO_INTERNAL, "prediction covariance: stored covariance does not match the plan");
+  const HSensor& hs = p->sensors[size_t(sid)];
+  const int64_t n = hs.n();
+  if (n == 0) return CALICO_OK;
+  const size_t lds_bytes = pred_lds_doubles(p->pred_cols, p->pred_row_pad) * sizeof(double);
+  if (lds_bytes > kMaxLds) {
+    char msg[200];
+    std::snprintf(msg, sizeof(msg), "prediction covariance: a residual block of %d Jacobian columns needs %zu bytes of LDS staging (at most %zu)",
+                  p->pred_cols, lds_bytes, kMaxLds);
+    return p->set_error(CALICO_UNIMPLEMENTED, msg);
+  }
+  HIP_TRY(p, hipSetDevice(p->device));
+  int rc = upload_x(p);
+  if (rc != CALICO_OK) return rc;
+  const int dim = hs.dim(), dd = dim * dim;
+  const int64_t nrange = hs.sorted_end - hs.sorted_begin;      // (layouts are per sensor: the sensor's observations are contiguous)
+  if (nrange != n) return p->set_error(CALICO_INTERNAL, "prediction covariance: the sensor's observations are not contiguous");
+  hipStream_t s = p->stream;
+  DevBuf<double> d_cov, d_lev;
+  DevBuf<uint8_t> d_val;
+  HIP_TRY(p, d_cov.alloc(size_t(n) * dd)); HIP_TRY(p, d_lev.alloc(size_t(n))); HIP_TRY(p, d_val.alloc(size_t(n)));
+  PredArgs pa = {};
+  pa.e = make_eval_args(p, p->d_x.p, opt->apply_loss, false);
+  pa.e.items = p->d_items_all.p; pa.e.n_items = p->n_items_all;      // every rank evaluates all blocks
+  pa.e.active = nullptr;                                             // tagged observations included
+  pa.e.row_pad = p->pred_row_pad; pa.e.lds_cols = (p->pred_cols + 15) & ~15;
+  pa.sensor = sid; pa.obs_begin = int(hs.sorted_begin); pa.n_cp = p->n_cp; pa.mc = p->m;
+  pa.colmap = p->d_pred_map.p; pa.map_stride = p->pred_map_stride;
+  pa.sigma = cv.out.p; pa.sae = cv.cp_sae.p; pa.band = cv.cp_band.p;
+  pa.cov = d_cov.p; pa.leverage = d_lev.p; pa.valid = d_val.p;
+  (void)hipGetLastError();
+  HIP_TRY(p, launch_prediction(pa, lds_bytes, s));
+  std::vector<double> hc(size_t(n) * dd), hl(static_cast<size_t>(n));
+  std::vector<uint8_t> hv(static_cast<size_t>(n));
+  HIP_TRY(p, hipMemcpyAsync(hc.data(), d_cov.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(p, hipMemcpyAsync(hl.data(), d_lev.p, hl.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(p, hipMemcpyAsync(hv.data(), d_val.p, hv.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(p, hipStreamSynchronize(s));
+  for (int64_t i = 0; i < n; ++i) {
+    const size_t q = size_t(hs.sorted_pos[size_t(i)] - hs.sorted_begin);
+    if (cov_out) std::copy(hc.begin() + q * dd, hc.begin() + (q + 1) * dd, cov_out + i * dd);
+    if (leverage_out) leverage_out[i] = hl[q];
+    if (valid) valid[i] = hv[q];
+  }
   return CALICO_OK;
 }
 

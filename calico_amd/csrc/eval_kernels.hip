@@ -17,6 +17,8 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
+#include <set>
 
 #include "device_math.hpp"
 #include "problem_dev.hpp"
@@ -1159,6 +1161,150 @@ __global__ __launch_bounds__(64) void eval_items_kernel(EvalArgs a) {
   eval_items_body<JAC, KT>(a, blockIdx.x, lds);
 }
 
+// ---------------------------------------------------------------------------
+// Prediction covariance / leverage: P_i = J_i Σ J_iᵀ of every residual block of one sensor (calico_prediction_covariance).
+// One wave per work item of the list that covers ALL observations. Stage A as eval_items_body: the item's rows [J] column-
+// major in LDS -- tagged observations included (no tags are read), the loss through the corrector or not as asked. Then
+// Σ_cc, Σ restricted to the item's columns, is staged next to them: control-point pairs from the band of Σ_AA (block (J + d,
+// J), transposed above the diagonal), control point x border from Σ_AE, border x border from Σ_EE; a residual block only
+// touches the `order` control points of its segment, i.e. exactly the pairs the covariance pass computed. T = J Σ_cc runs on
+// the matrix cores, sixteen rows by sixteen columns at a time, k-steps in ascending order; a tile's entries are multiplied
+// with the block's own rows at once and summed over the sixteen lanes of a row (DPP, fixed order) and over the column
+// groups in ascending order, so T never leaves the registers and the result is the same bits on every call and rank.
+// P_i leaves as ½ (P + Pᵀ) of the raw products (bitwise symmetric), the leverage as its trace summed from the left.
+// The staging area is cleared first: the k-steps and column groups read whole groups of four / sixteen without masks.
+// ---------------------------------------------------------------------------
+DEV double pred_sigma_entry(const PredArgs& a, const int* map, int kk, int k, int seg, int i, int j) {
+  const bool si = i < kk, sj = j < kk;
+  if (si && sj) {
+    const int Ji = seg + i / 6, ci = i % 6, Jj = seg + j / 6, cj = j % 6;
+    return Ji >= Jj ? a.band[(size_t(Jj) * k + (Ji - Jj)) * 36 + ci * 6 + cj] : a.band[(size_t(Ji) * k + (Jj - Ji)) * 36 + cj * 6 + ci];
+  }
+  if (si) return a.sae[size_t(6 * (seg + i / 6) + i % 6) * a.mc + map[j - kk]];
+  if (sj) return a.sae[size_t(6 * (seg + j / 6) + j % 6) * a.mc + map[i - kk]];
+  return a.sigma[size_t(map[i - kk]) * a.mc + map[j - kk]];
+}
+
+template <int KT>
+__global__ __launch_bounds__(64) void prediction_items_kernel(PredArgs pa) {
+  extern __shared__ double lds[];
+  const EvalArgs& a = pa.e;
+  const int lane = threadIdx.x & 63;
+  const ItemDev* ip = a.items + blockIdx.x;
+  if (ip->L.sensor != pa.sensor) return;
+  const ItemDev it = *ip;
+  const LayoutDev& L = ip->L;
+  const SensorDev& S = ip->S;
+  ItemCtx c;
+  c.s = &S; c.L = &L; c.k = a.order; c.x = a.x; c.info = wave_uniform(S.info);
+  const int ki = it.seg + a.order - 1;
+  c.knot0 = a.knots[ki]; c.knot1 = a.knots[ki + 1];
+  c.M = a.basis + size_t(it.seg) * a.order * a.order;
+  c.ctrl_off = ip->ctrl_off;
+  const int dim = (S.kind == 0) ? 2 : 3;
+  const int row_pad = a.row_pad, ncols = L.ncols;
+  const int c4 = (ncols + 3) & ~3, c16 = (ncols + 15) & ~15, sld = pred_sigma_ld(ncols);
+  const int nrows = dim * it.obs_count;
+  double* Jl = lds;                                           // [c16][row_pad] (+ slack)
+  double* Sg = lds + pred_rows_doubles(ncols, row_pad);       // [c4][sld]
+  double* Praw = Sg + c4 * sld;                               // [rows][3]
+  double* vflag = Praw + 3 * row_pad;                         // [64]
+  const int total = int(pred_lds_doubles(ncols, row_pad));
+  for (int e = lane; e < total; e += 64) lds[e] = 0.0;
+  wave_lds_sync();
+  // ---- stage A: the rows ----
+  const bool triple = S.kind != 0;
+  const int ol = triple ? lane / 3 : lane, jl = triple ? lane - 3 * ol : 0;
+  const bool active = ol < it.obs_count;
+  const int o = it.obs_begin + ol;
+  double res[3] = {0.0, 0.0, 0.0};
+  double cost = 0.0;
+  bool ok = true;
+  RowSink sink; sink.J = Jl; sink.row0 = dim * ol; sink.pad = row_pad;
+  if (active) {
+    const double st = a.stamp[o];
+    const double z0 = a.m0[o], z1 = a.m1[o], z2 = a.m2[o];
+    if (S.kind == 0) ok = camera_dispatch<true, KT>(c, z0, z1, st, a.x + a.point_off[o], res, sink, &cost, a.apply_loss);
+    else if (S.kind == 1) ok = gyro_block<true, KT>(c, mk(z0, z1, z2), st, res, sink, &cost, a.apply_loss, jl);
+    else ok = accel_block<true, KT>(c, mk(z0, z1, z2), st, res, sink, &cost, a.apply_loss, jl);
+    if (jl == 0) {
+      if (!ok) {      // no prediction: zero rows, P = 0
+        for (int col = 0; col < ncols; ++col)
+          for (int r = 0; r < dim; ++r) sink.put(col, r, 0.0);
+      }
+      vflag[ol] = ok ? 1.0 : 0.0;
+    }
+  }
+  // ---- Σ_cc ----
+  {
+    const int* map = pa.colmap + size_t(it.layout) * pa.map_stride;
+    const int kk = 6 * a.order;
+    for (int e = lane; e < ncols * ncols; e += 64) {
+      const int i = e / ncols, j = e - i * ncols;
+      Sg[i * sld + j] = pred_sigma_entry(pa, map, kk, a.order, it.seg, i, j);
+    }
+  }
+  wave_lds_sync();
+  // ---- T = J Σ_cc, P = T Jᵀ restricted to the blocks' own rows ----
+  const int lc16 = lane & 15, lk = lane >> 4;
+  const int ksteps = c4 >> 2, ntile_r = (nrows + 15) >> 4, ntile_c = c16 >> 4;
+  for (int I = 0; I < ntile_r; ++I) {
+    double part[4][3];
+    int rbase[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * I + lk + 4 * r;
+      rbase[r] = row - row % dim;      // first row of the block this row belongs to
+      part[r][0] = part[r][1] = part[r][2] = 0.0;
+    }
+    for (int Jt = 0; Jt < ntile_c; ++Jt) {
+      f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+      const double* ap = Jl + lk * row_pad + 16 * I + lc16;
+      const double* bp = Sg + lk * sld + 16 * Jt + lc16;
+      for (int s = 0; s < ksteps; ++s) {
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[0], bp[0], acc, 0, 0, 0);
+        ap += 4 * row_pad; bp += 4 * sld;
+      }
+      const double* jc = Jl + (16 * Jt + lc16) * row_pad;
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+          if (b < dim) part[r][b] += acc[r] * jc[rbase[r] + b];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * I + lk + 4 * r;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const double v = row16_sum(part[r][b]);
+        if (lc16 == 0 && row < nrows && b < dim) Praw[3 * row + b] = v;
+      }
+    }
+  }
+  wave_lds_sync();
+  for (int q = lane; q < it.obs_count; q += 64) {
+    const size_t dst = size_t(it.obs_begin + q - pa.obs_begin);
+    const bool good = vflag[q] != 0.0;
+    double P[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) P[r][b] = (r < dim && b < dim && good) ? Praw[3 * (dim * q + r) + b] : 0.0;
+    double tr = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      if (r >= dim) continue;
+      tr += P[r][r];
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+        if (b < dim && pa.cov) pa.cov[dst * (dim * dim) + r * dim + b] = 0.5 * (P[r][b] + P[b][r]);
+    }
+    if (pa.leverage) pa.leverage[dst] = tr;
+    pa.valid[dst] = good ? 1 : 0;
+  }
+}
+
 // Whole Jacobian pass in one launch (spline order 6): the generic items (IMU cells; they are few and each is a long
 // single-wave computation, so they go first) and the camera frames run side by side instead of back to back.
 // The extra workgroup of the Jacobian launch in the streaming solve loop (EvalArgs.hint_progress): will the control stage
@@ -1605,6 +1751,30 @@ void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream) {
     if (a.order == 6) hipLaunchKernelGGL((eval_items_kernel<false, 6>), dim3(a.n_items), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((eval_items_kernel<false, 0>), dim3(a.n_items), dim3(64), 0, stream, a);
   }
+}
+
+// One wave per work item of pa.e.items; `lds_bytes`: pred_lds_doubles of the problem's widest layout. The kernel's dynamic-LDS
+// limit is raised to the device's on a device's first call (it runs on a user's request: no handle's limit is ever lowered).
+hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream) {
+  if (pa.e.n_items == 0) return hipSuccess;
+  {
+    static std::mutex mu;
+    static std::set<int> done;      // devices whose limit is raised
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!done.count(dev)) {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prediction_items_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) return e;
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prediction_items_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) return e;
+      done.insert(dev);
+    }
+  }
+  if (pa.e.order == 6) hipLaunchKernelGGL((prediction_items_kernel<6>), dim3(pa.e.n_items), dim3(64), lds_bytes, stream, pa);
+  else hipLaunchKernelGGL((prediction_items_kernel<0>), dim3(pa.e.n_items), dim3(64), lds_bytes, stream, pa);
+  return hipGetLastError();
 }
 
 hipError_t configure_eval_kernels(size_t max_lds_bytes) {

@@ -253,6 +253,30 @@ struct ControlTail {
 CAL_HD inline int tri_off(int i, int j, int n1) { return i * n1 - ((i * (i - 1)) >> 1) + (j - i); }
 CAL_HD inline int tri_size(int n1) { return (n1 * (n1 + 1)) >> 1; }
 
+// Arguments of prediction_items_kernel (eval_kernels.hip): P_i = J_i Σ J_iᵀ of every residual block of one sensor.
+// `e` describes the evaluation as for the Jacobian launch of the generic work items (items: all of them, active: nullptr --
+// tagged observations are evaluated --, apply_loss as asked, row_pad / lds_cols sized for every layout of the problem).
+struct PredArgs {
+  EvalArgs e;
+  int sensor, obs_begin;   // only the work items of this sensor; its first observation in sorted order
+  int n_cp, mc;
+  const int* colmap;       // [n_layouts][map_stride]: border tangent offset (row of sigma, column of sae) of local column 6k + j
+  int map_stride, pad0;
+  const double* sigma;     // [mc][mc] Σ_EE
+  const double* sae;       // [6 n_cp][mc] Σ_AE
+  const double* band;      // [n_cp][k][36] band of Σ_AA, block (J + d, J) row-major
+  double* cov;             // [n][d][d] by sorted position less obs_begin, or nullptr
+  double* leverage;        // [n], or nullptr
+  uint8_t* valid;          // [n]
+};
+// LDS of one work item of that kernel (doubles): the staged rows [16 ceil(c / 16)][row_pad] (+ slack for the reads of a
+// row group's padding), Σ_cc [4 ceil(c / 4)][16 ceil(c / 16) + 4], the raw products [rows][3] and the valid flags [64]
+CAL_HD inline int pred_sigma_ld(int ncols) { return ((ncols + 15) & ~15) + 4; }
+CAL_HD inline size_t pred_rows_doubles(int ncols, int row_pad) { return size_t((ncols + 15) & ~15) * size_t(row_pad) + 32; }
+CAL_HD inline size_t pred_lds_doubles(int ncols, int row_pad) {
+  return pred_rows_doubles(ncols, row_pad) + size_t((ncols + 3) & ~3) * size_t(pred_sigma_ld(ncols)) + 3 * size_t(row_pad) + 64;
+}
+
 // Prim columns of a camera frame (eval_kernels.hip, eval_frames_body): [pose 6 | intrinsics | q | t | body q | body t |
 // residual]; the latency column is the extra row/column PT of M_ext. The planner sizes the frames' records and LDS and
 // builds the cell kernel's pair table from these same maps.

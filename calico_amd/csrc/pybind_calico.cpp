@@ -378,7 +378,22 @@ PYBIND11_MODULE(_calico, m) {
         std::vector<double> v;
         raise_if_error(c.TrajectoryCovariance(stamps, &v));
         return py::array_t<double>({py::ssize_t(stamps.size()), py::ssize_t(6), py::ssize_t(6)}, v.data());
-      });
+      })
+      // prediction covariance of a sensor's residual blocks (ComputeCovariance(control_points=True)): (cov (n, d, d),
+      // leverage (n,), valid (n,) bool), in the order of the sensor's residual write-back
+      .def("Predictions",
+           [](const Covariance& c, std::shared_ptr<Sensor> s, bool apply_loss) {
+             std::vector<double> cov, lev;
+             std::vector<uint8_t> valid;
+             raise_if_error(SensorPredictions(c, *s, apply_loss, &cov, &lev, &valid));
+             const py::ssize_t n = py::ssize_t(lev.size());
+             const py::ssize_t d = n > 0 ? py::ssize_t(std::lround(std::sqrt(double(cov.size() / lev.size())))) :
+                                           (dynamic_cast<const sensors::Camera*>(s.get()) ? 2 : 3);
+             py::array_t<bool> ok(n);
+             for (py::ssize_t i = 0; i < n; ++i) ok.mutable_at(i) = valid[size_t(i)] != 0;
+             return py::make_tuple(py::array_t<double>({n, d, d}, cov.data()), py::array_t<double>(n, lev.data()), ok);
+           },
+           py::arg("sensor"), py::arg("apply_loss") = true);
 
   py::class_<BatchOptimizer>(m, "BatchOptimizer")
       .def(py::init<>())

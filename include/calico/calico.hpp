@@ -335,12 +335,40 @@ class Covariance {
     const int st = calico_covariance_trajectory(h_.get(), int64_t(stamps.size()), stamps.data(), out->data());
     return st == CALICO_OK ? OkStatus() : Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
   }
+  /// Prediction covariance and leverage of every residual block of a sensor (calico_prediction_covariance; control_points =
+  /// 1): `sensor` is the index Problem::AddSensor returned (sensors::SensorCommon::ProblemSensor() for a sensor of the
+  /// optimizer the covariance came from; SensorPredictions below). cov: n row-major d x d blocks, leverage: n traces, valid:
+  /// n flags, in the order the residuals were added -- the order and selection of the facade's residual write-back.
+  calico_problem* handle() const { return h_.get(); }      // the library handle the result lives on (C ABI readers)
+  int NumSensors() const { return int(sensor_ids_.size()); }
+  int SensorDimension(int sensor) const { return sensor >= 0 && sensor < NumSensors() ? sensor_dim_[size_t(sensor)] : 0; }
+  int64_t NumObservations(int sensor) const { return sensor >= 0 && sensor < NumSensors() ? sensor_n_[size_t(sensor)] : 0; }
+  Status Predictions(int sensor, bool apply_loss, std::vector<double>* cov, std::vector<double>* leverage,
+                     std::vector<uint8_t>* valid) const {
+    if (!h_) return FailedPreconditionError("covariance has not been computed");
+    if (sensor < 0 || sensor >= NumSensors()) return InvalidArgumentError("covariance: sensor not in the problem");
+    const size_t n = size_t(sensor_n_[size_t(sensor)]), d = size_t(sensor_dim_[size_t(sensor)]);
+    std::vector<double> c(n * d * d, 0.0), l(n, 0.0);
+    std::vector<uint8_t> v(n, 0);
+    calico_prediction_options o;
+    calico_default_prediction_options(&o);
+    o.apply_loss = apply_loss ? 1 : 0;
+    const int st = calico_prediction_covariance(h_.get(), sensor_ids_[size_t(sensor)], &o, c.data(), l.data(), v.data());
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+    if (cov) cov->swap(c);
+    if (leverage) leverage->swap(l);
+    if (valid) valid->swap(v);
+    return OkStatus();
+  }
 
  private:
   friend class Problem;
   std::shared_ptr<calico_problem> h_;
   std::map<const double*, int32_t> ids_;
   std::vector<int32_t> ctrl_ids_;      // block ids of the control points, in spline order
+  std::vector<int32_t> sensor_ids_;    // library ids of the problem's sensors, their residual dimensions and block counts
+  std::vector<int> sensor_dim_;
+  std::vector<int64_t> sensor_n_;
 };
 
 inline Status Problem::ComputeCovariance(const calico_covariance_options& options, Covariance* out, int device) {
@@ -352,6 +380,12 @@ inline Status Problem::ComputeCovariance(const calico_covariance_options& option
   for (double* c : ctrl_) {
     const auto it = out->ids_.find(c);
     out->ctrl_ids_.push_back(it == out->ids_.end() ? -1 : it->second);
+  }
+  out->sensor_ids_.assign(sensor_ids_.begin(), sensor_ids_.end());
+  out->sensor_dim_.clear(); out->sensor_n_.clear();
+  for (const SensorRec& s : sensors_) {
+    out->sensor_dim_.push_back(s.kind == CALICO_SENSOR_CAMERA ? 2 : 3);
+    out->sensor_n_.push_back(int64_t(s.stamps.size()));
   }
   out->h_ = std::shared_ptr<calico_problem>(h_, calico_problem_destroy);      // the result stays with its handle
   h_ = nullptr;
@@ -740,6 +774,8 @@ class SensorCommon : public Sensor {
     if (sigma <= 0.0) return InvalidArgumentError("Sigma must be greater than 0.");
     sigma_ = sigma; return OkStatus();
   }
+  /// index of this sensor in the Problem it last added its residuals to (-1: none yet): Covariance::Predictions
+  int ProblemSensor() const { return problem_sensor_; }
  protected:
   // camera.cpp:92-113 / gyroscope.cpp:10-31 / accelerometer.cpp:10-33
   StatusOr<int> AddCommonParameters(Problem& problem, bool model_set, const char* what) {
@@ -1050,6 +1086,14 @@ inline Status SensorLatencyVariance(const Covariance& c, const sensors::Sensor& 
   const auto* sc = dynamic_cast<const sensors::SensorCommon*>(&s);
   if (!sc) return InvalidArgumentError("covariance: not a library sensor");
   return c.Get(sc->LatencyData(), sc->LatencyData(), 1, out);
+}
+
+/// Covariance::Predictions for a sensor of the optimizer the covariance came from.
+inline Status SensorPredictions(const Covariance& c, const sensors::Sensor& s, bool apply_loss, std::vector<double>* cov,
+                                std::vector<double>* leverage, std::vector<uint8_t>* valid) {
+  const auto* sc = dynamic_cast<const sensors::SensorCommon*>(&s);
+  if (!sc) return InvalidArgumentError("covariance: not a library sensor");
+  return c.Predictions(sc->ProblemSensor(), apply_loss, cov, leverage, valid);
 }
 
 class BatchOptimizer {

@@ -386,6 +386,42 @@ int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double*
  * factorisation. CALICO_FAILED_PRECONDITION as calico_covariance_trajectory. */
 int32_t calico_covariance_trajectory_info(calico_problem* p, int32_t* n_cp, int32_t* order, double* min_relative_pivot_band);
 
+/* ---- prediction covariance and leverage of the observations ------------ */
+/* How well the fit determines what the model predicts for each registered observation, and how much each observation
+ * carries the fit. For residual block i of a sensor (dimension d = 2 camera, 3 gyroscope / accelerometer), at the CURRENT
+ * parameter values:
+ *   J_i (d x n_eff): its Jacobian rows exactly as the LM loop and the covariance pass evaluate them -- sigma-weighted,
+ *     quaternion blocks in the tangent, tangent order of calico_num_effective_parameters. apply_loss = 1 (default): the
+ *     robust loss goes through the corrector as in the solve, so J_i are rows of the very J whose (JᵀJ)⁻¹ Σ is;
+ *     apply_loss = 0: the Jacobian of the plain whitened residual (z − f(θ)) / sigma.
+ *   P_i = J_i Σ J_iᵀ (d x d, symmetric, row-major), Σ the full covariance [control points | border] of the last successful
+ *     calico_covariance_compute with control_points = 1 (structurally unobserved columns are zero in Σ, as there). A
+ *     residual block touches the `order` control points of its segment and a few border blocks: exactly the part of Σ that
+ *     compute produced. leverage_i = trace(P_i).
+ *       apply_loss = 1: P_i is the i-th diagonal block of the hat matrix J (JᵀJ)⁻¹ Jᵀ: 0 <= P_i <= I, and the leverages of all
+ *         blocks of all sensors that are in the fit add up to 6 n_cp + dim − n_unobserved (observed control points).
+ *       apply_loss = 0: sigma² P_i is the covariance of the model's prediction for observation i in measurement units.
+ * Every registered observation of the sensor is evaluated, observations tagged as outliers included (the residual of a
+ * held-out point has variance I + P_i, of one in the fit I − P_i; the caller has the mask). An observation that does not
+ * evaluate (the projection fails) gets valid = 0 and zeros. Order: insertion order, as calico_get_residuals.
+ * J_i is taken at the current values and Σ at the values of its compute: a caller who moved the parameters (a solve, a
+ * set_param_block) calls calico_covariance_compute again first. The call leaves the parameters, the LM state, the iteration
+ * log, the last summary, the stored covariance and observability report and the phase timers alone. On a sharded handle it
+ * evaluates all blocks on every rank without an exchange (every rank holds the same Σ); results are bit-identical from
+ * call to call and between ranks. */
+typedef struct calico_prediction_options {
+  int32_t apply_loss;   /* default 1 */
+  int32_t reserved[7];
+} calico_prediction_options;
+void calico_default_prediction_options(calico_prediction_options* o);
+/* cov_out: n x d x d, leverage_out: n, valid: n (n = the sensor's registered observations); any of them may be NULL, not
+ * all three (CALICO_INVALID_ARGUMENT). o == NULL: the defaults. CALICO_FAILED_PRECONDITION without a successful
+ * calico_covariance_compute with control_points = 1, after a structural change, or on a problem without a spline;
+ * CALICO_INVALID_ARGUMENT for an unknown sensor or apply_loss outside {0, 1}; CALICO_UNIMPLEMENTED for a layout whose
+ * columns do not fit the kernel's staging area. */
+int32_t calico_prediction_covariance(calico_problem* p, int32_t sensor, const calico_prediction_options* o, double* cov_out,
+                                     double* leverage_out, uint8_t* valid);
+
 /* ---- observability of the calibration ---------------------------------- */
 /* Which directions of the dense border the data determine, and how well: the answer calico_covariance_compute cannot give
  * when it refuses a problem as rank deficient (it works on the well-posed ones too). Definition, at the current values,
