@@ -26,6 +26,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "kernels.hpp"
 #include "problem_dev.hpp"
 #include "solve_dev.hpp"
 #include "block_elim.hpp"

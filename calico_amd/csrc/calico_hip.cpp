@@ -10,6 +10,8 @@
 //                   solve_kernels.hip; this file only enqueues them and reads
 //                   back one small state struct per iteration),
 //   calico_get_residuals -> cost-only kernel without the loss function.
+// What is read from a solved problem (covariance, prediction covariance, observability) is analysis.cpp; the handle and
+// what the two files share is problem_host.hpp.
 // There is no CPU compute path in this library.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>     // types only: the library itself is loaded on first use (RcclApi below)
@@ -34,108 +36,12 @@
 
 #include "../../include/calico_hip.h"
 #include "calico_hip_testing.h"
+#include "kernels.hpp"
 #include "problem_dev.hpp"
+#include "problem_host.hpp"
 #include "shard.hpp"
 
-namespace cal {
-
-// ---- kernels (eval_kernels.hip / solve_kernels.hip) -------------------------
-void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream);
-void launch_eval_jacobian(const EvalArgs& a, hipStream_t stream);
-void launch_expand_cells(const EvalArgs& a, hipStream_t stream);
-void launch_residual_heatmap(const double* res, const uint8_t* valid, const uint8_t* active, const double* px, const double* py,
-                             int begin, int end, int width, int height, int num_rows, int num_cols, double* rmse, long long* count,
-                             hipStream_t s);
-void launch_inlier_mask(const double* res, uint8_t* valid_then_mask, const uint8_t* active, int begin, int end, int dim, double threshold,
-                        hipStream_t s);
-void launch_mark_outliers(const double* res, const uint8_t* valid, uint8_t* active, int begin, int end, int dim,
-                          double threshold, int* n_marked, hipStream_t s);
-hipError_t configure_eval_kernels(size_t max_lds_bytes);
-hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream);
-
-void launch_gather(double* R, const double* src, const int* out_idx_thin, const int64_t* ptr_thin, const int* idx_thin,
-                   int n_thin, int n_thin8, int n_thin4, int thin_per_lane, const int* out_idx_fat, const int64_t* ptr_fat, const int* idx_fat, int n_fat,
-                   const double* cost_src, int n_cost, const LmState* st, int need_flag, size_t other_stride, hipStream_t s, const ControlTail* tail = nullptr);
-void launch_gather_lists(const GatherStruct& gs, int n_out, int* cnt, int* out_idx, int64_t* ptr, int* idx, int zero_slot, long long* scratch,
-                         hipStream_t s);
-size_t gather_fixed_entries(int n_thin, int n_thin8, int n_thin4, int thin_per_lane);
-void launch_gather_pack_fixed(const int64_t* ptr, const int* idx, int n_thin, int n_thin8, int n_thin4, int thin_per_lane, int zero_slot, int* out,
-                              hipStream_t s);
-void launch_post_eval(const SolveArgs& a, const double* x, const BlockDev* blocks, int n_blocks, const LmOptionsDev& o,
-                      IterLog* log, int log_cap, int first, int jacobi, hipStream_t s);
-size_t band_cholesky_lds_bytes(const SolveArgs& a);
-size_t reduced_solve_lds_bytes(const SolveArgs& a);
-size_t frame_lds_doubles(int Ps, int P1e, int n1);
-size_t band_backsolve_lds_bytes(const SolveArgs& a);
-hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t back_lds);
-void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
-                  int n_blocks, bool dense_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi);
-void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s);
-void launch_control(LmState* st, const LmOptionsDev& o, double* R2, double* x, const double* x_cand, int n_amb,
-                    IterLog* log, int log_cap, const double* item_cost, int n_items, const double* Rbase, size_t r_stride,
-                    hipStream_t s, bool commit_by_copy = false);
-void launch_init_state(LmState* st, double radius, double x_norm, hipStream_t s, const double* upd_ext = nullptr, int upd_ext_n = 0);
-void launch_begin_solve(LmState* st, double radius, double x_norm, const double* upd_ext, int upd_ext_n, const ResultSink& sink, double* x,
-                        double* x_cand, const double* h_x, int n_amb, hipStream_t s);
-void launch_publish_results(const LmState* st, const IterLog* log, int log_rows, const double* x, int n_amb, LmState* h_state,
-                            IterLog* h_log, double* h_x, hipStream_t s);
-void launch_seed_x(double* x, const double* h_x, int n_amb, hipStream_t s);
-void launch_debug_control_replay(LmState* st, const LmOptionsDev& o, const double* rho, const int* infinite, int n, double* R2,
-                                 double* radius_out, int* accepted_out, double* cost_out, IterLog* log, int log_cap, hipStream_t s);
-size_t bcr_level_lds_bytes();
-size_t bcr_back_lds_bytes(int q_max, int m1p);
-hipError_t configure_bcr_kernels(int q_max, int m1p);
-void roll_table_row(int k, int lane, unsigned* out);      // (host only: test hook)
-hipError_t configure_dense_block_solve();
-hipError_t configure_reduced_block_step();
-size_t dense_block_solve_lds_bytes();
-void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
-                      const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
-                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl);
-void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
-void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
-                     const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
-
-void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
-int reduced_solve_route(const SolveArgs& a);
-bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
-size_t dense_back_lds_bytes(int q_max, int m1p);
-hipError_t configure_dense_back_bytes(size_t lds);
-void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
-                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s);
-int reduced_schur_slices(const SolveArgs& a);
-void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const double* x, const BlockDev* blocks, int n_blocks, hipStream_t s,
-                           bool with_post_eval, IterLog* log, int log_cap, int jacobi);
-int covariance_max_dim();
-int covariance_ld(int n);
-bool covariance_in_lds(int n);
-void launch_covariance(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* out,
-                       double* info, hipStream_t s);
-hipError_t configure_covariance_kernel();
-int cp_covariance_max_order();
-void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s);
-void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s);
-void launch_cp_band_factor(const CpCovArgs& a, hipStream_t s);
-int observability_max_border();
-int observability_max_dim();
-bool observability_in_lds(int m, int mc);
-size_t observability_work_doubles(int m, int mc);
-void launch_observability(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* lam,
-                          double* vec, double* mat, double* d, double* info, hipStream_t s);
-hipError_t configure_observability_kernel();
-void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
-                      double* out, hipStream_t s);
-
-}  // namespace cal
-
-using namespace cal;
-
 namespace {
-
-constexpr size_t kMaxLds = 160 * 1024;
-constexpr int kLogCap = 4096;
-constexpr int kPlanInfoWords = 21;    // words calico_debug_plan_info reports (calico_hip_testing.h)
-constexpr int kNumPhases = 7;   // 5 = calibration: the same event bracket around a trivial kernel; 6 = the reduced-system launch inside phase 2
 
 // RCCL is loaded when the first communicator is asked for (calico_comm_get_unique_id / calico_comm_init_rccl), not at
 // link time: a single-GPU user needs no librccl on the machine. An already loaded librccl (e.g. the one torch ships) is
@@ -192,426 +98,6 @@ RcclApi& rccl() {
   return api;
 }
 
-struct HBlock {
-  std::vector<double> v;
-  int size = 0, manifold = 0;
-  bool constant = false, used = false;
-  int amb_off = 0;
-  int tan = -1;      // solver tangent index (6·cp for control points, 6·n_cp + c for calibration blocks)
-  int eff = -1;      // tangent index in the reduced-problem order exported by calico_evaluate
-  int tangent_size() const { return manifold == CALICO_MANIFOLD_EIGEN_QUATERNION ? 3 : size; }
-};
-struct HBody { int q, t; };
-struct HSensor {
-  int kind, model, K;
-  int intr, q, t, lat, grav;
-  double sigma, info;
-  int loss; double loss_scale;
-  std::vector<double> meas, stamps;
-  std::vector<int> body, point, seg;
-  std::vector<int64_t> sorted_pos;  // original observation -> position in the sorted device arrays
-  std::vector<uint8_t> active;      // 0 = tagged as outlier (outlier_ids_, camera.h:185): left out of the problem
-  int64_t n_active = -1;            // cached count of the blocks that are in the problem (-1: recount)
-  int64_t sorted_begin = 0, sorted_end = 0;   // this sensor's contiguous range in the sorted arrays
-  int dim() const { return kind == CALICO_SENSOR_CAMERA ? 2 : 3; }
-  int64_t n() const { return int64_t(stamps.size()); }
-};
-
-// Device memory of plans and workspaces comes out of a few large slabs instead of one hipMalloc per buffer: a handle
-// has some forty buffers, most of them a few KB, and a buffer of its own sits on pages of its own -- every kernel's
-// first touch of each (state, descriptors, index lists, ...) then costs an address translation of its own behind the
-// kernel boundary. One slab is one allocation of 64 MB: contiguous, mapped with the largest fragments the driver
-// has. First fit over a free list ordered by address, neighbours merged on release; a request no slab can serve opens
-// a new slab, and if that fails the request goes to hipMalloc as before. A request larger than a slab is an allocation
-// of its own (hipMalloc / hipFree: it has large fragments anyway and must not pin memory for good).
-// Slabs go back to the driver: trim() frees every slab that is one free extent -- calico_plan_cache_clear() frees all of
-// them, calico_problem_destroy() all but CALICO_ARENA_KEEP_SLABS idle ones per device (default 4) -- so a process that once solved a large
-// problem, or that shares the GPU with PyTorch / RCCL, does not keep that memory. (No HIP calls during static
-// destruction: what is still held at exit is the driver's to reclaim.) CALICO_ARENA=0: hipMalloc per buffer (rounds 1-4).
-class DeviceArena {
- public:
-  static DeviceArena& get() { static DeviceArena* a = new DeviceArena; return *a; }
-  hipError_t alloc(void** out, size_t bytes) {
-    if (!enabled_ || bytes > kSlab) return hipMalloc(out, bytes);
-    bytes = (bytes + kAlign - 1) / kAlign * kAlign;
-    std::lock_guard<std::mutex> g(mu_);
-    int dev = 0; (void)hipGetDevice(&dev);
-    for (int pass = 0; pass < 2; ++pass) {
-      for (Slab& sl : slabs_) {
-        if (sl.device != dev) continue;
-        for (auto it = sl.free.begin(); it != sl.free.end(); ++it) {
-          if (it->second < bytes) continue;
-          const size_t off = it->first, len = it->second;
-          sl.free.erase(it);
-          if (len > bytes) sl.free.emplace(off + bytes, len - bytes);
-          *out = sl.base + off;
-          used_[*out] = bytes;
-          return hipSuccess;
-        }
-      }
-      if (pass == 1) break;
-      void* base = nullptr;
-      if (hipMalloc(&base, kSlab) != hipSuccess) { (void)hipGetLastError(); break; }
-      Slab sl; sl.base = static_cast<char*>(base); sl.size = kSlab; sl.device = dev; sl.free.emplace(0, kSlab);
-      slabs_.push_back(std::move(sl));
-    }
-    return hipMalloc(out, bytes);      // (not in used_: release() hands it to hipFree)
-  }
-  void release(void* p) {
-    if (!p) return;
-    int owner = -1;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      if (used_.count(p))
-        for (const Slab& sl : slabs_)
-          if (static_cast<char*>(p) >= sl.base && static_cast<char*>(p) < sl.base + sl.size) { owner = sl.device; break; }
-    }
-    if (owner < 0) { (void)hipFree(p); return; }
-    // hipFree waits for the device; a block that goes back to the free list must do the same (a solve returns while the
-    // early-exit kernels of the iterations enqueued ahead are still on its stream) -- for the device that OWNS the slab,
-    // and once per batch of releases (Batch below), not once per buffer
-    if (batch_device() != owner) sync_device(owner);
-    std::lock_guard<std::mutex> g(mu_);
-    auto u = used_.find(p);
-    if (u == used_.end()) return;
-    const size_t bytes = u->second;
-    used_.erase(u);
-    for (Slab& sl : slabs_) {
-      char* c = static_cast<char*>(p);
-      if (c < sl.base || c >= sl.base + sl.size) continue;
-      size_t off = size_t(c - sl.base), len = bytes;
-      auto next = sl.free.lower_bound(off);
-      if (next != sl.free.end() && next->first == off + len) { len += next->second; next = sl.free.erase(next); }
-      if (next != sl.free.begin()) {
-        auto prev = std::prev(next);
-        if (prev->first + prev->second == off) { off = prev->first; len += prev->second; sl.free.erase(prev); }
-      }
-      sl.free.emplace(off, len);
-      return;
-    }
-  }
-  // Everything a handle or a plan gives back at once (some forty buffers): ONE wait for the owning device, up front.
-  struct Batch {
-    explicit Batch(int device) : prev_(batch_device()) { if (DeviceArena::get().enabled_) { sync_device(device); batch_device() = device; } }
-    ~Batch() { batch_device() = prev_; }
-    Batch(const Batch&) = delete;
-    Batch& operator=(const Batch&) = delete;
-   private:
-    int prev_;
-  };
-  // Frees the slabs nothing lives in; `keep_per_device` of them stay per device for the next handle. Returns the bytes freed.
-  size_t trim(int keep_per_device) {
-    std::vector<Slab> drop;
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      std::map<int, int> kept;
-      for (size_t i = 0; i < slabs_.size();) {
-        Slab& sl = slabs_[i];
-        const bool idle = sl.free.size() == 1 && sl.free.begin()->first == 0 && sl.free.begin()->second == sl.size;
-        if (idle && kept[sl.device]++ >= keep_per_device) { drop.push_back(std::move(sl)); slabs_.erase(slabs_.begin() + long(i)); }
-        else ++i;
-      }
-    }
-    size_t bytes = 0;
-    for (Slab& sl : drop) { (void)hipFree(sl.base); bytes += sl.size; }     // (hipFree waits for the device itself)
-    return bytes;
-  }
-  size_t slab_bytes() { std::lock_guard<std::mutex> g(mu_); size_t b = 0; for (const Slab& sl : slabs_) b += sl.size; return b; }
- private:
-  static constexpr size_t kAlign = 4096, kSlab = size_t(64) << 20;
-  struct Slab { char* base = nullptr; size_t size = 0; int device = 0; std::map<size_t, size_t> free; };
-  DeviceArena() { enabled_ = env_flag("CALICO_ARENA", true); }
-  static int& batch_device() { static thread_local int d = -1; return d; }
-  static void sync_device(int device) {
-    int cur = device;
-    (void)hipGetDevice(&cur);
-    if (cur != device) (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    if (cur != device) (void)hipSetDevice(cur);
-  }
-  std::mutex mu_;
-  std::vector<Slab> slabs_;
-  std::unordered_map<void*, size_t> used_;
-  bool enabled_ = true;
-};
-
-template <class T> struct DevBuf {
-  T* p = nullptr; size_t n = 0;
-  bool owner = true;        // false: a view of a buffer the plan cache owns (structure shared between handles)
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void release() { if (p && owner) DeviceArena::get().release(p); p = nullptr; n = 0; owner = true; }
-  void alias(const DevBuf& o) { release(); p = o.p; n = o.n; owner = false; }
-  void take(DevBuf& o) { release(); p = o.p; n = o.n; owner = o.owner; o.p = nullptr; o.n = 0; o.owner = true; }
-  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(owner, o.owner); }
-  hipError_t alloc(size_t count) {
-    if (count == 0) count = 1;
-    if (count == n && p && owner) return hipSuccess;
-    release();        // (a view is dropped, never written through)
-    hipError_t e = DeviceArena::get().alloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  hipError_t upload(const std::vector<T>& h, hipStream_t s) {
-    hipError_t e = alloc(h.size());
-    if (e != hipSuccess || h.empty()) return e;
-    return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
-  }
-};
-
-struct PhaseTimer {
-  std::vector<hipEvent_t> pool;
-  struct Rec { int phase; hipEvent_t a, b; };
-  std::vector<Rec> pending;
-  size_t next = 0;
-  double ms[kNumPhases] = {0, 0, 0, 0, 0, 0};
-  int64_t count[kNumPhases] = {0, 0, 0, 0, 0, 0};
-  // the same restricted to "working" launches: kernels of iterations enqueued ahead return at once when the solve has
-  // terminated (or the step was rejected), and such brackets (shorter than a quarter of the phase's longest) are left out
-  double ms_working[kNumPhases] = {0, 0, 0, 0, 0, 0};
-  int64_t count_working[kNumPhases] = {0, 0, 0, 0, 0, 0};
-  std::vector<float> samples[kNumPhases];
-  hipEvent_t get() {
-    if (next == pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); pool.push_back(e); }
-    return pool[next++];
-  }
-  int mask = 0;              // no event brackets unless asked for (calico_set_phase_timing): each pair costs ~6 us of stream time
-  int every = 1;            // bracket only every `every`-th launch of a phase (an event pair costs ~6 us of stream time)
-  int64_t seen[kNumPhases] = {0, 0, 0, 0, 0, 0};
-  bool open_rec = false;
-  int nested = 0;           // phase 6 sits inside phase 2: a bracket inside an open bracket is not recorded
-  void begin(int phase, hipStream_t s) {
-    if (open_rec) { ++nested; return; }
-    open_rec = (mask >> phase) & 1;
-    if (open_rec && phase != 5 && every > 1) open_rec = (seen[phase]++ % every) == 0;
-    if (!open_rec) return;
-    Rec r; r.phase = phase; r.a = get(); r.b = nullptr; (void)hipEventRecord(r.a, s); pending.push_back(r);
-  }
-  void end(hipStream_t s) { if (nested) { --nested; return; } if (!open_rec) return; Rec& r = pending.back(); r.b = get(); (void)hipEventRecord(r.b, s); open_rec = false; }
-  void resolve() {  // call after a stream sync
-    for (const Rec& r : pending) {
-      float t = 0;
-      if (r.b && hipEventElapsedTime(&t, r.a, r.b) == hipSuccess) { ms[r.phase] += t; count[r.phase]++; samples[r.phase].push_back(t); }
-    }
-    pending.clear(); next = 0;
-    for (int ph = 0; ph < kNumPhases; ++ph) {
-      float mx = 0; for (float t : samples[ph]) mx = std::max(mx, t);
-      ms_working[ph] = 0; count_working[ph] = 0;
-      for (float t : samples[ph]) if (t >= 0.25f * mx) { ms_working[ph] += t; count_working[ph]++; }
-    }
-  }
-  void reset() { for (int i = 0; i < kNumPhases; ++i) { ms[i] = 0; count[i] = 0; seen[i] = 0; ms_working[i] = 0; count_working[i] = 0; samples[i].clear(); } }
-  ~PhaseTimer() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
-};
-
-}  // namespace
-
-// ---- what calico_problem_finalize derives from the STRUCTURE of a problem (not from any value): shared between handles
-//      of identical structure through the plan cache -------------------------------------------------------------------
-struct BcrLevel { int node0, n_nodes, keep0, n_keep, q_max; };
-struct PlanHost {
-  bool speculative = true;    // evaluate cost AND Jacobian at the candidate point in one pass (two reduce buffers)
-  size_t r_size = 0;
-  int sep_s = 0, sep_n = 0;   // separator control points of the nested-dissection split (sep_n = 0: none)
-  // tree solver (bcr_kernels.hip): elimination plan, level after level
-  bool use_bcr = false, bcr_all_active = false;
-  int bcr_N = 0, bcr_m1p = 16, bcr_root = -1, bcr_root_pend = 0, bcr_root_par = 0, bcr_br = 0, bcr_q_max = 1, bcr_slots = 1, bcr_q0 = 1;
-  std::vector<BcrLevel> bcr_levels;
-  std::vector<BcrNodeDev> h_bcr_nodes;
-  int border_extra() const { return use_bcr ? bcr_br : 6 * sep_n; }   // rows the band hands to the dense reduced solve
-  int n_cp = 0, m = 0, n_amb = 0, n_eff = 0, n_items = 0, n_items_all = 0, lds_cols = 0, row_pad = kRowPad;
-  int64_t n_obs = 0, n_obs_local = 0;   // residual blocks: all, this rank's shard (calico_comm_info)
-  size_t partial_doubles = 0, partials_alloc = 0;
-  std::vector<int> eff_to_tan;
-  std::vector<BlockDev> h_blocks;
-  int n_cells = 0, cell_chunk = 1, cell_rec_max = 1, row_cell_chunk = 1;
-  int frame_lds_doubles = 0;
-  int n_fitems = 0, n_jac_items = 0;
-  int max_cell_frames = 0, max_item_run = 0;   // frames of the fullest camera cell, longest run of one cell's work items (calico_debug_plan_info)
-  bool fuse_expand = false;    // cell workgroups (EvalArgs.pair_mode): camera cells expanded inside the Jacobian launch, IMU items form their own blocks
-  int pair_wave_lds_doubles = 0;
-  int n_thin = 0, n_fat = 0;
-  int n_thin8 = 0, n_thin4 = 0;  // thin outputs [0, n_thin8) take eight lanes, [n_thin8, n_thin4) four (<= 24 sources), [n_thin4, n_thin) one (<= 8)
-  int thin_per_lane = 6;       // sources per lane of a thin output's eight lanes (6: up to 48 sources, 12: up to 96)
-  bool gather_fixed = false;   // the thin lists at a fixed stride (d_idx_fixed) instead of CSR
-  bool dense_in_lds = true;
-  // calico_prediction_covariance: widest layout (columns) and longest work item (row stride) of the list of ALL work items,
-  // row length of the column map (d_pred_map)
-  int pred_cols = 0, pred_row_pad = 3, pred_map_stride = 1;
-};
-struct PlanDev {      // structure on the device: immutable once uploaded
-  DevBuf<double> d_knots, d_basis, d_stamp;
-  DevBuf<int> d_ctrl_off, d_point_off, d_out_thin, d_idx_thin, d_idx_fixed, d_out_fat, d_idx_fat, d_prim_tab, d_bkeep, d_cp_block, d_gs_tab, d_pred_map;
-  DevBuf<int64_t> d_ptr_thin, d_ptr_fat;
-  DevBuf<uint8_t> d_cp_active;
-  DevBuf<SensorDev> d_sensors;
-  DevBuf<LayoutDev> d_layouts;
-  DevBuf<ItemDev> d_items, d_items_all, d_jac_items;
-  DevBuf<FrameItemDev> d_fitems;
-  DevBuf<CellDev> d_cells;
-  DevBuf<BlockDev> d_blocks;
-  DevBuf<BcrNodeDev> d_bnodes;
-#define PLAN_DEV_BUFS(X) X(d_knots) X(d_basis) X(d_stamp) X(d_ctrl_off) X(d_point_off) X(d_out_thin) X(d_idx_thin) X(d_idx_fixed) X(d_out_fat) X(d_idx_fat) \
-  X(d_prim_tab) X(d_bkeep) X(d_cp_block) X(d_gs_tab) X(d_ptr_thin) X(d_ptr_fat) X(d_cp_active) X(d_sensors) X(d_layouts) X(d_items) X(d_items_all)     \
-  X(d_jac_items) X(d_fitems) X(d_cells) X(d_blocks) X(d_bnodes) X(d_pred_map)
-  void take_from(PlanDev& o) {
-#define X(n) n.take(o.n);
-    PLAN_DEV_BUFS(X)
-#undef X
-  }
-  void alias_from(const PlanDev& o) {
-#define X(n) n.alias(o.n);
-    PLAN_DEV_BUFS(X)
-#undef X
-  }
-};
-// ---- what a handle works in: values, normal equations, solver workspaces, result staging. Recycled between handles of
-//      identical structure (a destroyed handle leaves its workspace with the cached plan) ----------------------------------
-struct Workspace {
-  DevBuf<unsigned long long> d_wave_log;   // CALICO_KERNEL_TIMING=3
-  DevBuf<double> d_x, d_xc, d_m0, d_m1, d_m2, d_partials, d_R, d_R2, d_Lb, d_Linv, d_Y, d_S, d_Spart, d_Swork, d_zbuf, d_y, d_dadd, d_scale, d_res;
-  DevBuf<double> d_bD, d_bG, d_bF, d_bpD, d_bpF, d_bM, d_bZA, d_bZB, d_bY, d_bysol, d_bzb, d_bupd;
-  DevBuf<uint8_t> d_valid, d_active;
-  DevBuf<int> d_counter;
-  DevBuf<int> d_handoff;         // hand-off word of the fused dense-solve + back-substitution launch
-  DevBuf<LmState> d_state;
-  DevBuf<IterLog> d_log;
-  int handoff_seq = 0;           // number of the last such launch (the word carries it when the solve part is through)
-  LmState* h_state = nullptr;  // pinned
-  int* h_progress = nullptr;   // pinned, device-visible: [epoch << 20 | iterations the control kernel is through with, epoch of the terminated solve]
-  int solve_epoch = 0;         // number of the streaming solve under way (1 .. 2047, wraps)
-  int* d_progress = nullptr;
-  double* h_xpin = nullptr;    // pinned staging for the parameter vector (upload at the start of a call, download at its end)
-  size_t h_xpin_n = 0;
-  IterLog* h_log = nullptr;    // pinned
-  bool ws_ready = false;       // allocated and initialised for the plan at hand
-#define WS_BUFS(X) X(d_wave_log) X(d_x) X(d_xc) X(d_m0) X(d_m1) X(d_m2) X(d_partials) X(d_R) X(d_R2) X(d_Lb) X(d_Linv) X(d_Y) X(d_S) X(d_Spart)      \
-  X(d_Swork) X(d_zbuf) X(d_y) X(d_dadd) X(d_scale) X(d_res) X(d_bD) X(d_bG) X(d_bF) X(d_bpD) X(d_bpF) X(d_bM) X(d_bZA) X(d_bZB) X(d_bY) X(d_bysol) \
-  X(d_bzb) X(d_bupd) X(d_valid) X(d_active) X(d_counter) X(d_handoff) X(d_state) X(d_log)
-  void swap_ws(Workspace& o) {
-#define X(n) n.swap(o.n);
-    WS_BUFS(X)
-#undef X
-    std::swap(handoff_seq, o.handoff_seq); std::swap(h_state, o.h_state); std::swap(h_progress, o.h_progress);
-    std::swap(solve_epoch, o.solve_epoch); std::swap(d_progress, o.d_progress); std::swap(h_xpin, o.h_xpin);
-    std::swap(h_xpin_n, o.h_xpin_n); std::swap(h_log, o.h_log); std::swap(ws_ready, o.ws_ready);
-  }
-  void free_pinned() {
-    if (h_state) (void)hipHostFree(h_state);
-    if (h_progress) (void)hipHostFree(h_progress);
-    if (h_xpin) (void)hipHostFree(h_xpin);
-    if (h_log) (void)hipHostFree(h_log);
-    h_state = nullptr; h_progress = nullptr; d_progress = nullptr; h_xpin = nullptr; h_xpin_n = 0; h_log = nullptr;
-  }
-  Workspace() = default;
-  Workspace(const Workspace&) = delete;
-  Workspace& operator=(const Workspace&) = delete;
-  ~Workspace() { free_pinned(); }
-};
-
-struct PlanEntry;      // plan cache entry (below)
-
-struct calico_problem : PlanHost, PlanDev, Workspace {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::string error;
-  std::vector<HBlock> blocks;
-  std::vector<HBody> bodies;
-  std::vector<HSensor> sensors;
-  int order = 0;
-  std::vector<double> knots, valid_knots, basis;
-  std::vector<int> ctrl;
-  bool dirty = true;
-  calico_allreduce_fn allreduce = nullptr;
-  void* allreduce_ctx = nullptr;
-  ncclComm_t comm = nullptr;      // native exchange: RCCL communicator owned by the handle (calico_comm_init_rccl)
-  bool has_exchange() const { return allreduce != nullptr || comm != nullptr; }
-  int rank = 0, world = 1;
-  std::shared_ptr<PlanEntry> plan;    // the cached plan this handle's structure buffers are views of (null: it owns them)
-
-  std::vector<double> h_x;     // staging of the parameter values (alive until the upload is through)
-  double* h_mpin = nullptr;    // pinned staging of the measurements in device order [m0 | m1 | m2], borrowed from the process-wide pool for the duration of finalize
-  size_t h_mpin_n = 0;
-  bool active_dirty = true;
-  bool any_tagged = false;       // some observation is tagged as an outlier: the kernels look at the tags only then
-  bool xc_stale = true;       // the candidate buffer must be re-seeded with the constant blocks' values
-  bool step_ready = false;    // d_y / d_dadd / d_scale hold a linear solve of the current plan and values (calico_debug_last_step)
-  // residuals of ALL sensors at the parameter values `x` (calico_get_residuals / calico_project are per sensor, as
-  // Sensor::UpdateResiduals is: the second to last sensor of a write-back are served from here)
-  struct ResCache { bool valid = false, predict = false; std::vector<double> x, r; std::vector<uint8_t> v; } res_cache;
-  std::vector<calico_iteration> iterations;
-  PhaseTimer timer;
-  // calico_covariance_compute: its own LM state, scale, damping and solution buffers (the pass never touches the LM's),
-  // the factorisation's workspace and the result -- owned by the handle, not by the workspace the plan cache recycles
-  struct Covariance {
-    DevBuf<LmState> st;
-    DevBuf<double> scale, dadd, y, zbuf, work, out, info;
-    bool valid = false;
-    int dim = 0, n_unobserved = 0;
-    double min_relative_pivot = 0.0;
-    std::vector<double> sigma;       // dim x dim, border tangent order
-    // per block id at the time of the compute: offset of its tangent rows in sigma (-1: not in Σ -- constant or unused --,
-    // -2: control point), ambient size, manifold, value (the quaternion lift is taken at the values Σ was computed at), the
-    // control point's index (-1: not one)
-    struct Blk { int off, size, manifold; std::vector<double> v; int cp; };
-    std::vector<Blk> blocks;
-    // control_points: the control points' blocks (cov_kernels.hip, CpCovArgs), their host copies and the stamp buffers
-    DevBuf<double> cp_dq, cp_L, cp_Li, cp_M, cp_X, cp_W, cp_Z, cp_sae, cp_band, cp_info, st_t, st_out;
-    DevBuf<int> st_seg;
-    bool has_cp = false, cp_requested = false;     // (requested: control_points = 1, whether or not the problem has a spline)
-    int n_cp = 0, order = 0;
-    double min_relative_pivot_band = 0.0;
-    std::vector<double> sae, band;     // Σ_AE (6 n_cp x dim), Σ_AA's band ([n_cp][order][36], block (J + d, J) row-major)
-  } cov;
-  // calico_observability_compute: the same kind of private state as the covariance pass, the eigensolver's workspace and
-  // the report (obs_kernels.hip)
-  struct Observability {
-    DevBuf<LmState> st;
-    DevBuf<double> scale, dadd, y, zbuf, work, lam, vec, mat, dvec, info, cp_dq, cp_L, cp_Li, cp_info;
-    bool valid = false;
-    int dim = 0, kept = 0, n_unobserved = 0, n_weak = 0, sweeps = 0, rotations = 0, in_lds = 0, reduced_rows = 0;
-    double min_relative_pivot_root = 0.0, min_relative_pivot_band = 0.0;
-    std::vector<double> eigenvalues;     // kept, ascending
-    std::vector<double> vectors;         // kept x dim: row i the unit eigenvector v_i, border tangent order, zeros in dropped columns
-    std::vector<double> d;               // dim: D = sqrt(diag C), 0 in dropped columns
-    std::vector<double> matrix;          // dim x dim: S̃, zeros in dropped rows and columns
-    struct Blk { int off, tsize; };      // per block id at the time of the compute: offset of its tangent rows (-1: not in the border, -2: control point)
-    std::vector<Blk> blocks;
-  } obs;
-
-  int set_error(int code, const std::string& msg) { error = msg; return code; }
-  int hip_error(hipError_t e, const char* what) {
-    return set_error(CALICO_INTERNAL, std::string(what) + ": " + hipGetErrorString(e));
-  }
-};
-
-#define HIP_TRY(p, expr)                                    \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return (p)->hip_error(_e, #expr); \
-  } while (0)
-
-namespace {
-
-// bspline.hpp:138-150
-int spline_index(const calico_problem* p, double t) {
-  const std::vector<double>& vk = p->valid_knots;
-  if (t == vk.back()) return int(vk.size()) - 2;
-  if (!(t < vk.back())) return -1;
-  // upper_bound(vk, t) - 1, found from a guess on the (uniform) knot spacing and corrected by comparisons with the knots
-  // themselves, so the result is the binary search's for any knot vector
-  const int n = int(vk.size());
-  if (t < vk.front()) return -1;
-  const double dt = (vk.back() - vk.front()) / double(n - 1);
-  int i = dt > 0.0 ? int((t - vk.front()) / dt) : 0;
-  i = std::max(0, std::min(n - 2, i));
-  while (i > 0 && t < vk[size_t(i)]) --i;
-  while (i + 1 < n && !(t < vk[size_t(i) + 1])) ++i;
-  return i;
-}
 int camera_num_params(int model) {
   switch (model) { case 1: return 8; case 2: return 11; case 3: return 7; case 4: return 5; case 5: return 4; case 6: return 4;
     case 7: return 5; default: return -1; }
@@ -628,24 +114,6 @@ struct PlanSwitches {
   bool gather_struct = env_flag("CALICO_GATHER_STRUCT", true);    // the gather's lists built on the device
   int bcr_leaf = env_int("CALICO_BCR_LEAF", 0, 1, kBcrMaxChain);  // level 0's chain length (0: chosen by the plan)
 };
-
-SolveArgs make_solve_args(calico_problem* p) {
-  SolveArgs a;
-  a.R = p->d_R.p; a.r_stride = p->speculative ? p->r_size : 0; a.Lb = p->d_Lb.p; a.Linv = p->d_Linv.p; a.Y = p->d_Y.p; a.S = p->d_S.p; a.Spart = p->d_Spart.p;
-  a.Swork = p->d_Swork.p; a.y = p->d_y.p; a.zbuf = p->d_zbuf.p; a.dadd = p->d_dadd.p;
-  a.scale = p->d_scale.p; a.cp_active = p->d_cp_active.p; a.st = p->d_state.p; a.n_cp = p->n_cp; a.k = p->order; a.mc = p->m; a.sep_s = p->sep_s; a.sep_n = p->sep_n; a.m = p->m + p->border_extra();
-  static const int dbg = [] {
-    const int v = env_int("CALICO_KERNEL_TIMING", 0, 0);
-#ifndef CALICO_DEV_TIMING
-    if (v) std::fprintf(stderr, "[calico] CALICO_KERNEL_TIMING is set, but this library was built without the kernels' development "
-                                "instrumentation (rebuild with CALICO_DEV_TIMING=1 in the environment of __graft_entry__.build())\n");
-#endif
-    return v;
-  }();
-  a.debug = dbg;
-  a.progress = nullptr;
-  return a;
-}
 
 BcrArgs make_bcr_args(calico_problem* p) {
   BcrArgs b;
@@ -722,24 +190,6 @@ void build_bcr_plan(calico_problem* p, const PlanSwitches& sw, std::vector<int>&
   p->bcr_q_max = q_max_all;
   p->bcr_q0 = q;       // level 0's chain length: its node table is arithmetic on the node's number (BcrInlineNodes)
   p->bcr_slots = int(p->h_bcr_nodes.size()) + 1;
-}
-
-EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res) {
-  EvalArgs a;
-  static const int dbg = env_int("CALICO_KERNEL_TIMING", 0, 0);
-  a.debug = dbg;
-  a.x = x; a.sensors = p->d_sensors.p; a.layouts = p->d_layouts.p; a.items = p->d_items.p;
-  a.knots = p->d_knots.p; a.basis = p->d_basis.p; a.ctrl_off = p->d_ctrl_off.p;
-  a.m0 = p->d_m0.p; a.m1 = p->d_m1.p; a.m2 = p->d_m2.p; a.stamp = p->d_stamp.p; a.point_off = p->d_point_off.p;
-  a.partials = p->d_partials.p; a.item_cost = p->d_partials.p + p->partial_doubles;
-  a.res_out = want_res ? p->d_res.p : nullptr; a.valid_out = want_res ? p->d_valid.p : nullptr;
-  a.order = p->order; a.n_items = p->n_items; a.lds_cols = p->lds_cols; a.row_pad = p->row_pad; a.n_cells = p->n_cells; a.cells = p->d_cells.p; a.prim_tab = p->d_prim_tab.p;
-  a.cell_chunk = p->cell_chunk; a.cell_rec_max = p->cell_rec_max; a.project = 0; a.row_cell_chunk = p->row_cell_chunk; a.frame_lds_doubles = p->frame_lds_doubles; a.pad5 = 0; a.wave_log = p->d_wave_log.p; a.active = p->any_tagged ? p->d_active.p : nullptr; a.apply_loss = apply_loss;
-  a.st = nullptr; a.need_flag = 0; a.cost_index_base = 0;
-  a.fitems = p->d_fitems.p; a.n_fitems = p->n_fitems;
-  a.hint_progress = nullptr; a.hint_seq = 0; a.hint_ftol = a.hint_ptol = 0.0;
-  a.pair_mode = 0; a.wave_lds_doubles = 0;
-  return a;
 }
 
 constexpr int kImuChunkItems = 21;     // IMU blocks per work item (the Jacobian kernel gives an IMU block three lanes)
@@ -1749,6 +1199,172 @@ int configure_kernels(calico_problem* p) {
   return CALICO_OK;
 }
 
+int do_allreduce(calico_problem* p, double* buf, int64_t n) {
+  if (p->comm) {     // native: one in-place RCCL all-reduce on the handle's stream, no host code in between
+    const ncclResult_t r = rccl().AllReduce(buf, buf, size_t(n), ncclDouble, ncclSum, p->comm, p->stream);
+    if (r != ncclSuccess) return p->set_error(CALICO_INTERNAL, std::string("ncclAllReduce: ") + rccl().GetErrorString(r));
+    return CALICO_OK;
+  }
+  if (!p->allreduce) return CALICO_OK;
+  const int st = p->allreduce(p->allreduce_ctx, buf, n, p->stream);
+  if (st != 0) return p->set_error(CALICO_INTERNAL, "all-reduce callback failed");
+  return CALICO_OK;
+}
+
+static bool end_hint_available(const calico_problem* p) { return p->order == 6 && p->n_fitems > 0; }
+
+// What one linear solve does, from the plan and the switches read per solve: enqueue_linear_solve follows it,
+// calico_debug_plan_info reports it (one decision, so the hook cannot drift from what runs).
+struct LinearRoute {
+  int ks = 1;                 // K-slices of the Schur complement (reduced_schur_slices)
+  int reduced = 0;            // ReducedRoute of the reduced solve
+  bool reduced_in_lds = true; // kReducedKernel: works in LDS (else in Swork)
+  // tree solver only:
+  bool schur_rides = false;   // the Schur complement rides in the last level's launch
+  BcrTopSeps ts = {};         // top separators back-substituted in the launch of the level below (ts.n of them)
+  int l_first = 0;            // level of the first back-substitution launch behind the reduced solve
+  bool fused = false;         // the dense solve and that back-substitution share one launch (dense_back_kernel)
+};
+LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa) {
+  LinearRoute r;
+  r.ks = reduced_schur_slices(sa);
+  r.reduced = reduced_solve_route(sa);
+  r.reduced_in_lds = p->dense_in_lds;
+  if (!p->use_bcr || p->bcr_levels.empty()) return r;
+  const int L = int(p->bcr_levels.size());
+  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
+  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
+  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
+  // launch bcr_schur_kernel on its own.
+  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
+  r.schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
+  for (int i = 0; r.schur_rides && i < last.n_nodes; ++i) r.schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
+  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
+  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
+  // the ones it waits for anyway) instead of costing a launch of its own.
+  if (L >= 2) {
+    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
+    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
+    for (int i = 0; ok && i < tl.n_nodes; ++i) {
+      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
+      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
+      r.ts.blk[i] = nd.blk0; r.ts.left[i] = nd.left; r.ts.right[i] = nd.right;
+    }
+    r.ts.n = ok ? tl.n_nodes : 0;
+  }
+  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
+  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
+  r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
+  const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
+  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) &&
+            std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(lf.q_max, p->bcr_m1p)) + 1024 <= kMaxLds;
+  return r;
+}
+
+int read_state(calico_problem* p) {
+  HIP_TRY(p, hipMemcpyAsync(p->h_state, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(p, hipStreamSynchronize(p->stream));
+  p->timer.resolve();
+  return CALICO_OK;
+}
+
+void fill_counts(calico_problem* p, calico_summary* sm) {
+  int nrb = 0, nr = 0;
+  for (HSensor& s : p->sensors) {   // tagged outliers are not part of the problem (camera.cpp:121-124)
+    if (s.n_active < 0) { int64_t c = 0; for (uint8_t a : s.active) c += a ? 1 : 0; s.n_active = c; }   // per solve otherwise: 100k bytes
+    const int64_t na = s.n_active;
+    nrb += int(na); nr += int(na) * s.dim();
+  }
+  sm->num_residual_blocks = nrb; sm->num_residuals = nr;
+  sm->num_residual_blocks_reduced = nrb; sm->num_residuals_reduced = nr;
+  sm->num_parameter_blocks = int(p->blocks.size());
+  int np = 0, ne = 0, npr = 0;
+  for (const HBlock& b : p->blocks) { np += b.size; ne += b.tangent_size(); }
+  sm->num_parameters = np; sm->num_effective_parameters = ne;
+  sm->num_parameter_blocks_reduced = int(p->h_blocks.size());
+  for (const BlockDev& b : p->h_blocks) npr += b.size;
+  sm->num_parameters_reduced = npr;
+  sm->num_effective_parameters_reduced = p->n_eff;
+}
+
+const char* reason_message(int reason) {
+  switch (reason) {
+    case 1: return "Maximum number of iterations reached.";
+    case 2: return "Gradient tolerance reached.";
+    case 3: return "Minimum trust region radius reached.";
+    case 4: return "Parameter tolerance reached.";
+    case 5: return "Function tolerance reached.";
+    case 10: return "Initial residual and Jacobian evaluation failed.";
+    case 11: return "Residual and Jacobian evaluation failed.";
+    case 12: return "Number of consecutive invalid steps more than Solver::Options::max_num_consecutive_invalid_steps.";
+    default: return "";
+  }
+}
+
+}  // namespace
+
+// ---- what analysis.cpp calls as well (declared in problem_host.hpp) ----
+namespace cal {
+
+int require_exchange(calico_problem* p) {
+  if (p->world > 1 && !p->has_exchange())
+    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
+  return CALICO_OK;
+}
+
+// bspline.hpp:138-150
+int spline_index(const calico_problem* p, double t) {
+  const std::vector<double>& vk = p->valid_knots;
+  if (t == vk.back()) return int(vk.size()) - 2;
+  if (!(t < vk.back())) return -1;
+  // upper_bound(vk, t) - 1, found from a guess on the (uniform) knot spacing and corrected by comparisons with the knots
+  // themselves, so the result is the binary search's for any knot vector
+  const int n = int(vk.size());
+  if (t < vk.front()) return -1;
+  const double dt = (vk.back() - vk.front()) / double(n - 1);
+  int i = dt > 0.0 ? int((t - vk.front()) / dt) : 0;
+  i = std::max(0, std::min(n - 2, i));
+  while (i > 0 && t < vk[size_t(i)]) --i;
+  while (i + 1 < n && !(t < vk[size_t(i) + 1])) ++i;
+  return i;
+}
+
+SolveArgs make_solve_args(calico_problem* p) {
+  SolveArgs a;
+  a.R = p->d_R.p; a.r_stride = p->speculative ? p->r_size : 0; a.Lb = p->d_Lb.p; a.Linv = p->d_Linv.p; a.Y = p->d_Y.p; a.S = p->d_S.p; a.Spart = p->d_Spart.p;
+  a.Swork = p->d_Swork.p; a.y = p->d_y.p; a.zbuf = p->d_zbuf.p; a.dadd = p->d_dadd.p;
+  a.scale = p->d_scale.p; a.cp_active = p->d_cp_active.p; a.st = p->d_state.p; a.n_cp = p->n_cp; a.k = p->order; a.mc = p->m; a.sep_s = p->sep_s; a.sep_n = p->sep_n; a.m = p->m + p->border_extra();
+  static const int dbg = [] {
+    const int v = env_int("CALICO_KERNEL_TIMING", 0, 0);
+#ifndef CALICO_DEV_TIMING
+    if (v) std::fprintf(stderr, "[calico] CALICO_KERNEL_TIMING is set, but this library was built without the kernels' development "
+                                "instrumentation (rebuild with CALICO_DEV_TIMING=1 in the environment of __graft_entry__.build())\n");
+#endif
+    return v;
+  }();
+  a.debug = dbg;
+  a.progress = nullptr;
+  return a;
+}
+
+EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res) {
+  EvalArgs a;
+  static const int dbg = env_int("CALICO_KERNEL_TIMING", 0, 0);
+  a.debug = dbg;
+  a.x = x; a.sensors = p->d_sensors.p; a.layouts = p->d_layouts.p; a.items = p->d_items.p;
+  a.knots = p->d_knots.p; a.basis = p->d_basis.p; a.ctrl_off = p->d_ctrl_off.p;
+  a.m0 = p->d_m0.p; a.m1 = p->d_m1.p; a.m2 = p->d_m2.p; a.stamp = p->d_stamp.p; a.point_off = p->d_point_off.p;
+  a.partials = p->d_partials.p; a.item_cost = p->d_partials.p + p->partial_doubles;
+  a.res_out = want_res ? p->d_res.p : nullptr; a.valid_out = want_res ? p->d_valid.p : nullptr;
+  a.order = p->order; a.n_items = p->n_items; a.lds_cols = p->lds_cols; a.row_pad = p->row_pad; a.n_cells = p->n_cells; a.cells = p->d_cells.p; a.prim_tab = p->d_prim_tab.p;
+  a.cell_chunk = p->cell_chunk; a.cell_rec_max = p->cell_rec_max; a.project = 0; a.row_cell_chunk = p->row_cell_chunk; a.frame_lds_doubles = p->frame_lds_doubles; a.pad5 = 0; a.wave_log = p->d_wave_log.p; a.active = p->any_tagged ? p->d_active.p : nullptr; a.apply_loss = apply_loss;
+  a.st = nullptr; a.need_flag = 0; a.cost_index_base = 0;
+  a.fitems = p->d_fitems.p; a.n_fitems = p->n_fitems;
+  a.hint_progress = nullptr; a.hint_seq = 0; a.hint_ftol = a.hint_ptol = 0.0;
+  a.pair_mode = 0; a.wave_lds_doubles = 0;
+  return a;
+}
+
 // Plan (cached or built), workspace (pooled or allocated), values.
 int finalize(calico_problem* p) {
   if (!p->dirty) return CALICO_OK;
@@ -1836,7 +1452,7 @@ int finalize(calico_problem* p) {
   return CALICO_OK;
 }
 
-int upload_x(calico_problem* p, bool seed = true) {
+int upload_x(calico_problem* p, bool seed) {
   if (p->active_dirty) {   // outlier tags, in the sorted order of the device arrays
     std::vector<uint8_t> act(size_t(std::max<int64_t>(p->n_obs, 1)), 1);
     bool tagged = false;
@@ -1863,18 +1479,6 @@ int upload_x(calico_problem* p, bool seed = true) {
   return CALICO_OK;
 }
 
-int do_allreduce(calico_problem* p, double* buf, int64_t n) {
-  if (p->comm) {     // native: one in-place RCCL all-reduce on the handle's stream, no host code in between
-    const ncclResult_t r = rccl().AllReduce(buf, buf, size_t(n), ncclDouble, ncclSum, p->comm, p->stream);
-    if (r != ncclSuccess) return p->set_error(CALICO_INTERNAL, std::string("ncclAllReduce: ") + rccl().GetErrorString(r));
-    return CALICO_OK;
-  }
-  if (!p->allreduce) return CALICO_OK;
-  const int st = p->allreduce(p->allreduce_ctx, buf, n, p->stream);
-  if (st != 0) return p->set_error(CALICO_INTERNAL, "all-reduce callback failed");
-  return CALICO_OK;
-}
-
 // residual + Jacobian evaluation at d_x into the reduce buffer R. With st != nullptr the
 // kernels skip themselves on the device when the solve has terminated or (need_flag) when
 // the last step was rejected, so whole iterations can be enqueued without a host round trip.
@@ -1882,9 +1486,8 @@ int do_allreduce(calico_problem* p, double* buf, int64_t n) {
 // the device from LmState.rcur); otherwise evaluation at x into buffer 0.
 // `end_hint` (streaming solve loop, fused Jacobian launch only: end_hint_available): the launch tells the host whether the
 // control stage behind it is about to end the solve (eval_kernels.hip, end_hint_body).
-static bool end_hint_available(const calico_problem* p) { return p->order == 6 && p->n_fitems > 0; }
-int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, const double* x_at = nullptr, bool spec = false,
-                          const ControlTail* tail = nullptr, bool end_hint = false) {
+int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, const double* x_at, bool spec, const ControlTail* tail,
+                          bool end_hint) {
   p->timer.begin(0, p->stream);
   EvalArgs ea = make_eval_args(p, x_at ? x_at : p->d_x.p, 1, false);
   ea.st = st; ea.need_flag = need_flag;
@@ -1922,59 +1525,11 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
   return do_allreduce(p, target, int64_t(p->r_size));
 }
 
-// What one linear solve does, from the plan and the switches read per solve: enqueue_linear_solve follows it,
-// calico_debug_plan_info reports it (one decision, so the hook cannot drift from what runs).
-struct LinearRoute {
-  int ks = 1;                 // K-slices of the Schur complement (reduced_schur_slices)
-  int reduced = 0;            // ReducedRoute of the reduced solve
-  bool reduced_in_lds = true; // kReducedKernel: works in LDS (else in Swork)
-  // tree solver only:
-  bool schur_rides = false;   // the Schur complement rides in the last level's launch
-  BcrTopSeps ts = {};         // top separators back-substituted in the launch of the level below (ts.n of them)
-  int l_first = 0;            // level of the first back-substitution launch behind the reduced solve
-  bool fused = false;         // the dense solve and that back-substitution share one launch (dense_back_kernel)
-};
-LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa) {
-  LinearRoute r;
-  r.ks = reduced_schur_slices(sa);
-  r.reduced = reduced_solve_route(sa);
-  r.reduced_in_lds = p->dense_in_lds;
-  if (!p->use_bcr || p->bcr_levels.empty()) return r;
-  const int L = int(p->bcr_levels.size());
-  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
-  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
-  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
-  // launch bcr_schur_kernel on its own.
-  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
-  r.schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
-  for (int i = 0; r.schur_rides && i < last.n_nodes; ++i) r.schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
-  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
-  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
-  // the ones it waits for anyway) instead of costing a launch of its own.
-  if (L >= 2) {
-    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
-    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
-    for (int i = 0; ok && i < tl.n_nodes; ++i) {
-      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
-      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
-      r.ts.blk[i] = nd.blk0; r.ts.left[i] = nd.left; r.ts.right[i] = nd.right;
-    }
-    r.ts.n = ok ? tl.n_nodes : 0;
-  }
-  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
-  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
-  r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
-  const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
-  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) &&
-            std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(lf.q_max, p->bcr_m1p)) + 1024 <= kMaxLds;
-  return r;
-}
-
 // One linear solve + update of the candidate point: tree solver or sequential banded factorisation.
 // with_post_eval: 0 none, 1 the bookkeeping of the step just accepted rides in the first launch, 2 the bookkeeping of the
 // solve's FIRST evaluation does (tree solver only: level 0 then forms the Jacobi scale of its diagonal entries itself)
 // reduce_only (the covariance pass): stop once the reduced system is in sa.Spart -- no reduced solve, no back-substitution.
-void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only = false) {
+void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only) {
   hipStream_t s = p->stream;
   const int n_blocks = int(p->h_blocks.size());
   if (reduce_only && !p->use_bcr) {
@@ -2053,47 +1608,7 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   }
 }
 
-int read_state(calico_problem* p) {
-  HIP_TRY(p, hipMemcpyAsync(p->h_state, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(p, hipStreamSynchronize(p->stream));
-  p->timer.resolve();
-  return CALICO_OK;
-}
-
-void fill_counts(calico_problem* p, calico_summary* sm) {
-  int nrb = 0, nr = 0;
-  for (HSensor& s : p->sensors) {   // tagged outliers are not part of the problem (camera.cpp:121-124)
-    if (s.n_active < 0) { int64_t c = 0; for (uint8_t a : s.active) c += a ? 1 : 0; s.n_active = c; }   // per solve otherwise: 100k bytes
-    const int64_t na = s.n_active;
-    nrb += int(na); nr += int(na) * s.dim();
-  }
-  sm->num_residual_blocks = nrb; sm->num_residuals = nr;
-  sm->num_residual_blocks_reduced = nrb; sm->num_residuals_reduced = nr;
-  sm->num_parameter_blocks = int(p->blocks.size());
-  int np = 0, ne = 0, npr = 0;
-  for (const HBlock& b : p->blocks) { np += b.size; ne += b.tangent_size(); }
-  sm->num_parameters = np; sm->num_effective_parameters = ne;
-  sm->num_parameter_blocks_reduced = int(p->h_blocks.size());
-  for (const BlockDev& b : p->h_blocks) npr += b.size;
-  sm->num_parameters_reduced = npr;
-  sm->num_effective_parameters_reduced = p->n_eff;
-}
-
-const char* reason_message(int reason) {
-  switch (reason) {
-    case 1: return "Maximum number of iterations reached.";
-    case 2: return "Gradient tolerance reached.";
-    case 3: return "Minimum trust region radius reached.";
-    case 4: return "Parameter tolerance reached.";
-    case 5: return "Function tolerance reached.";
-    case 10: return "Initial residual and Jacobian evaluation failed.";
-    case 11: return "Residual and Jacobian evaluation failed.";
-    case 12: return "Number of consecutive invalid steps more than Solver::Options::max_num_consecutive_invalid_steps.";
-    default: return "";
-  }
-}
-
-}  // namespace
+}  // namespace cal
 
 namespace {
 struct StreamPool {
@@ -2388,8 +1903,7 @@ int32_t calico_solve(calico_problem* p, const calico_solver_options* opt, calico
   double t_mark[6] = {0, 0, 0, 0, 0, 0};
   auto mark = [&](int i) { if (solve_timing) t_mark[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count(); };
   std::memset(sm, 0, sizeof(*sm));
-  if (p->world > 1 && !p->has_exchange())
-    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
+  if (int rc = require_exchange(p)) return rc;
   int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
   HIP_TRY(p, hipSetDevice(p->device));
@@ -2914,8 +2428,7 @@ int32_t calico_num_effective_parameters(calico_problem* p, int32_t* n_out) {
 
 int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient, double* jtj) {
   if (!p) return CALICO_INVALID_ARGUMENT;
-  if (p->world > 1 && !p->has_exchange())
-    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
+  if (int rc = require_exchange(p)) return rc;
   int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
   HIP_TRY(p, hipSetDevice(p->device));
@@ -2945,583 +2458,6 @@ int32_t calico_evaluate(calico_problem* p, double* cost, double* gradient, doubl
   if (jtj)
     for (int i = 0; i < n; ++i)
       for (int j = 0; j < n; ++j) jtj[size_t(i) * n + j] = H(p->eff_to_tan[size_t(i)], p->eff_to_tan[size_t(j)]);
-  return CALICO_OK;
-}
-
-void calico_default_covariance_options(calico_covariance_options* o) {
-  if (!o) return;
-  std::memset(o, 0, sizeof(*o));
-  o->min_relative_pivot = 1e-12;
-}
-
-namespace {
-// What the covariance and the observability passes share up to the reduction: the pass's own LM state (an infinite radius),
-// a Jacobi scale of ones, damping and solution buffers -- nothing of the LM's is touched --, the parameter upload and one
-// evaluation (as the LM loop's, exchange included; the phase timer records nothing of it). On return `sa` points at the
-// pass's buffers and `o` holds the damping bounds: enqueue_linear_solve(p, sa, o, 0, 0, reduce_only) then leaves the undamped,
-// unscaled reduced system in sa.Spart.
-struct UndampedPass { DevBuf<LmState>& st; DevBuf<double>& scale; DevBuf<double>& dadd; DevBuf<double>& y; DevBuf<double>& zbuf; };
-int begin_undamped_pass(calico_problem* p, UndampedPass b, SolveArgs& sa, LmOptionsDev& o) {
-  const int NT = sa.NT(), ny = NT + p->border_extra();
-  // (the same sizes as the workspace's buffers they stand in for: prepare_workspace)
-  HIP_TRY(p, b.st.alloc(1)); HIP_TRY(p, b.scale.alloc(2 * size_t(NT))); HIP_TRY(p, b.dadd.alloc(size_t(NT)));
-  HIP_TRY(p, b.y.alloc(size_t(ny) + 64)); HIP_TRY(p, b.zbuf.alloc(size_t(sa.n_s()) + 64));
-  hipStream_t s = p->stream;
-  {
-    const std::vector<double> ones(2 * size_t(NT), 1.0);      // [Jacobi scale s | 1 / s^2]: no scaling
-    HIP_TRY(p, hipMemcpyAsync(b.scale.p, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(p, hipStreamSynchronize(s));      // (`ones` is a local)
-  }
-  int rc = upload_x(p);
-  if (rc != CALICO_OK) return rc;
-  {
-    // (the phase timer measures the LM loop: the pass records nothing into it)
-    const int mask = p->timer.mask;
-    p->timer.mask = 0;
-    rc = enqueue_jacobian_eval(p, nullptr, 0);      // R(x) into reduce buffer 0, all ranks' sum
-    p->timer.mask = mask;
-  }
-  if (rc != CALICO_OK) return rc;
-  // damping = clamp(v s², min, max) / (radius s²) = 0 with s = 1 and an infinite radius (FromR::damping, prepare_kernel)
-  launch_init_state(b.st.p, std::numeric_limits<double>::infinity(), 0.0, s);
-  sa.st = b.st.p; sa.scale = b.scale.p; sa.dadd = b.dadd.p; sa.y = b.y.p; sa.zbuf = b.zbuf.p; sa.progress = nullptr;
-  o = {};
-  o.min_lm_diagonal = 1e-6; o.max_lm_diagonal = 1e32;
-  (void)hipGetLastError();
-  return CALICO_OK;
-}
-}  // namespace
-
-// Σ = (JᵀJ)⁻¹ of the calibration blocks at the current values: one evaluation (as the LM loop's, exchange included), the
-// linear solve's reduction WITHOUT damping and Jacobi scaling -- a state of its own with an infinite radius, a scale of
-// ones --, stopped once the reduced system is formed, then covariance_kernel (cov_kernels.hip). The LM state, the
-// parameter buffers, the iteration log and the plan / workspace sizes are left alone.
-int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_options* opt) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  calico_covariance_options def;
-  calico_default_covariance_options(&def);
-  if (!opt) opt = &def;
-  if (!(opt->min_relative_pivot >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "min_relative_pivot must be >= 0");
-  if (p->world > 1 && !p->has_exchange())
-    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
-  int rc = finalize(p);
-  if (rc != CALICO_OK) return rc;
-  HIP_TRY(p, hipSetDevice(p->device));
-  calico_problem::Covariance& cv = p->cov;
-  cv.valid = false;
-  cv.has_cp = false;
-  cv.cp_requested = opt->control_points != 0;
-  SolveArgs sa = make_solve_args(p);
-  const int mc = p->m, m = sa.m;
-  if (m > covariance_max_dim())
-    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: reduced system of " + std::to_string(m) + " rows (at most " +
-                                                  std::to_string(covariance_max_dim()) + ")");
-  const bool want_cp = opt->control_points != 0 && p->n_cp > 0;
-  if (want_cp && p->order > cp_covariance_max_order())
-    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: the trajectory's control-point blocks are computed for spline orders up to " +
-                                                  std::to_string(cp_covariance_max_order()));
-  CpCovArgs ca = {};
-  if (want_cp) {
-    const int n_cp = p->n_cp, k = p->order;
-    const size_t nb = size_t(n_cp) * k * 36, ne = size_t(6) * n_cp * mc;
-    HIP_TRY(p, cv.cp_dq.alloc(6 * size_t(n_cp))); HIP_TRY(p, cv.cp_L.alloc(nb)); HIP_TRY(p, cv.cp_Li.alloc(size_t(n_cp) * 36));
-    HIP_TRY(p, cv.cp_M.alloc(nb)); HIP_TRY(p, cv.cp_X.alloc(ne)); HIP_TRY(p, cv.cp_W.alloc(ne)); HIP_TRY(p, cv.cp_Z.alloc(nb));
-    HIP_TRY(p, cv.cp_sae.alloc(ne)); HIP_TRY(p, cv.cp_band.alloc(nb)); HIP_TRY(p, cv.cp_info.alloc(2));
-    ca.R = sa.R; ca.off_B = sa.off_B(); ca.off_E = sa.off_E(); ca.n_cp = n_cp; ca.k = k; ca.mc = mc;
-    ca.dq = cv.cp_dq.p; ca.L = cv.cp_L.p; ca.Li = cv.cp_Li.p; ca.M = cv.cp_M.p; ca.X = cv.cp_X.p; ca.W = cv.cp_W.p; ca.Z = cv.cp_Z.p;
-    ca.sae = cv.cp_sae.p; ca.band = cv.cp_band.p; ca.info = cv.cp_info.p;
-  }
-  HIP_TRY(p, cv.out.alloc(size_t(mc) * mc)); HIP_TRY(p, cv.info.alloc(4));
-  if (!covariance_in_lds(m)) HIP_TRY(p, cv.work.alloc(size_t(m) * covariance_ld(m)));
-  HIP_TRY(p, configure_covariance_kernel());
-  hipStream_t s = p->stream;
-  LmOptionsDev o = {};
-  rc = begin_undamped_pass(p, {cv.st, cv.scale, cv.dadd, cv.y, cv.zbuf}, sa, o);
-  if (rc != CALICO_OK) return rc;
-  if (want_cp) {      // (reads the band and E of R as the evaluation left them: ahead of the reduction)
-    launch_cp_covariance_band(ca, s);
-    HIP_TRY(p, hipGetLastError());
-  }
-  if (mc > 0) {
-    enqueue_linear_solve(p, sa, o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
-    HIP_TRY(p, hipGetLastError());
-    launch_covariance(sa.Spart, reduced_schur_slices(sa), m, mc, sa.R + sa.off_C(), cv.st.p, cv.work.p, cv.out.p, cv.info.p, s);
-    HIP_TRY(p, hipGetLastError());
-  }
-  if (want_cp) {
-    ca.sigma = cv.out.p;
-    launch_cp_covariance_finish(ca, s);
-    HIP_TRY(p, hipGetLastError());
-  }
-  double info[4] = {1.0, 0.0, 0.0, 0.0};
-  std::vector<double> R01(2);
-  HIP_TRY(p, hipMemcpyAsync(R01.data(), p->d_R.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  cv.sigma.assign(size_t(mc) * mc, 0.0);
-  if (mc > 0) {
-    HIP_TRY(p, hipMemcpyAsync(info, cv.info.p, sizeof(info), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(cv.sigma.data(), cv.out.p, cv.sigma.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  double cp_info[2] = {1.0, 0.0};
-  cv.sae.clear(); cv.band.clear();
-  if (want_cp) {
-    cv.sae.resize(size_t(6) * p->n_cp * mc); cv.band.resize(size_t(p->n_cp) * p->order * 36);
-    HIP_TRY(p, hipMemcpyAsync(cp_info, cv.cp_info.p, sizeof(cp_info), hipMemcpyDeviceToHost, s));
-    if (!cv.sae.empty()) HIP_TRY(p, hipMemcpyAsync(cv.sae.data(), cv.cp_sae.p, cv.sae.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(cv.band.data(), cv.cp_band.p, cv.band.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(p, hipStreamSynchronize(s));
-  if (R01[1] > 0.0) return p->set_error(CALICO_FAILED_PRECONDITION, "covariance: the residual evaluation failed at the current parameter values");
-  cv.dim = mc; cv.min_relative_pivot = info[0]; cv.n_unobserved = int(info[2]);
-  const int flags = int(info[1]);
-  if (flags & (1 | 4 | 8))
-    return p->set_error(CALICO_FAILED_PRECONDITION, std::string("covariance: JᵀJ is rank deficient or not finite (") +
-                                                        ((flags & 4) ? "a block of the control points' elimination is not positive definite"
-                                                         : (flags & 1) ? "non-finite value in the reduced system" : "non-finite value in the result") + ")");
-  if ((flags & 2) || info[0] < opt->min_relative_pivot) {
-    char msg[256];
-    std::snprintf(msg, sizeof(msg), "covariance: JᵀJ is rank deficient (minimum relative pivot %.3e, threshold %.3e): a gauge freedom "
-                  "or a parameter the data do not determine", info[0], opt->min_relative_pivot);
-    return p->set_error(CALICO_FAILED_PRECONDITION, msg);
-  }
-  if (want_cp) {
-    const int cpf = int(cp_info[1]);
-    bool finite = true;
-    for (double v : cv.sae) finite = finite && std::isfinite(v);
-    for (double v : cv.band) finite = finite && std::isfinite(v);
-    if ((cpf & 1) || !finite)
-      return p->set_error(CALICO_FAILED_PRECONDITION, "covariance: the trajectory's control-point block of JᵀJ is not finite");
-    if ((cpf & 2) || cp_info[0] < opt->min_relative_pivot) {
-      char msg[256];
-      std::snprintf(msg, sizeof(msg), "covariance: the trajectory's control-point band of JᵀJ is rank deficient (minimum relative pivot %.3e, "
-                    "threshold %.3e): the data do not determine the trajectory", cp_info[0], opt->min_relative_pivot);
-      return p->set_error(CALICO_FAILED_PRECONDITION, msg);
-    }
-    cv.n_cp = p->n_cp; cv.order = p->order; cv.min_relative_pivot_band = cp_info[0];
-  }
-  cv.blocks.resize(p->blocks.size());
-  for (size_t i = 0; i < p->blocks.size(); ++i) {
-    const HBlock& h = p->blocks[i];
-    const bool in = !h.constant && h.used;
-    const bool is_cp = h.tan >= 0 && h.tan < 6 * p->n_cp;
-    cv.blocks[i] = {in ? (is_cp ? -2 : h.tan - 6 * p->n_cp) : -1, h.size, h.manifold, h.v, is_cp ? h.tan / 6 : -1};
-  }
-  cv.has_cp = want_cp;
-  cv.valid = true;
-  return CALICO_OK;
-}
-
-int32_t calico_covariance_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, double* min_relative_pivot) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  if (!p->cov.valid || p->dirty) return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
-  if (dim) *dim = p->cov.dim;
-  if (n_unobserved) *n_unobserved = p->cov.n_unobserved;
-  if (min_relative_pivot) *min_relative_pivot = p->cov.min_relative_pivot;
-  return CALICO_OK;
-}
-
-int32_t calico_covariance_get_dense(calico_problem* p, double* out) {
-  if (!p || !out) return CALICO_INVALID_ARGUMENT;
-  if (!p->cov.valid || p->dirty) return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
-  std::copy(p->cov.sigma.begin(), p->cov.sigma.end(), out);
-  return CALICO_OK;
-}
-
-namespace {
-// EigenQuaternionManifold::PlusJacobian at x (storage x, y, z, w): 4x3 row-major
-void quat_plus_jacobian(const double* x, double J[12]) {
-  const double X = x[0], Y = x[1], Z = x[2], W = x[3];
-  const double j[12] = {W, Z, -Y, -Z, W, X, Y, -X, W, -X, -Y, -Z};
-  std::copy(j, j + 12, J);
-}
-}  // namespace
-
-int32_t calico_covariance_get_block(calico_problem* p, int32_t block_a, int32_t block_b, int32_t tangent, double* out) {
-  if (!p || !out) return CALICO_INVALID_ARGUMENT;
-  const int nb = int(p->blocks.size());
-  if (block_a < 0 || block_a >= nb || block_b < 0 || block_b >= nb) return p->set_error(CALICO_INVALID_ARGUMENT, "covariance: unknown parameter block id");
-  // (p->dirty: the structure changed since the compute -- blocks, sensors, observations --; the next finalisation drops Σ)
-  if (!p->cov.valid || p->dirty || size_t(nb) != p->cov.blocks.size())
-    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of this problem: call calico_covariance_compute (again, if the problem changed) and check its status");
-  const calico_problem::Covariance::Blk& A = p->cov.blocks[size_t(block_a)];
-  const calico_problem::Covariance::Blk& B = p->cov.blocks[size_t(block_b)];
-  const calico_problem::Covariance& cv = p->cov;
-  if ((A.off == -2 || B.off == -2) && !cv.has_cp)
-    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point blocks are not computed (calico_covariance_options.control_points = 0)");
-  if (A.off == -2 && B.off == -2 && std::abs(A.cp - B.cp) >= cv.order)
-    return p->set_error(CALICO_UNIMPLEMENTED, "covariance: control-point pairs are computed only within the spline's support (control "
-                                              "points less than the spline order apart)");
-  const bool qa = A.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION, qb = B.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION;
-  const int ta = qa ? 3 : A.size, tb = qb ? 3 : B.size;
-  const int ra = tangent ? ta : A.size, rb = tangent ? tb : B.size;
-  std::fill(out, out + size_t(ra) * rb, 0.0);
-  if (A.off == -1 || B.off == -1) return CALICO_OK;      // constant / unused blocks: zeros (Ceres: constant)
-  const int oa = A.off, ob = B.off, dim = cv.dim;
-  // (a border offset must leave room for its block; a control point (offset -2) must be one of the computed ones)
-  const auto in_range = [&](const calico_problem::Covariance::Blk& X, int tx) {
-    return X.off >= 0 ? X.off + tx <= dim : X.cp >= 0 && X.cp < cv.n_cp && tx == 6;
-  };
-  if (!in_range(A, ta) || !in_range(B, tb)) return p->set_error(CALICO_INTERNAL, "covariance: block layout out of range");
-  std::vector<double> t(size_t(ta) * tb);
-  for (int i = 0; i < ta; ++i)
-    for (int j = 0; j < tb; ++j) {
-      double v;
-      if (oa >= 0 && ob >= 0) v = cv.sigma[size_t(oa + i) * dim + (ob + j)];
-      else if (oa == -2 && ob >= 0) v = cv.sae[size_t(6 * A.cp + i) * dim + (ob + j)];       // Σ_AE
-      else if (ob == -2 && oa >= 0) v = cv.sae[size_t(6 * B.cp + j) * dim + (oa + i)];
-      else {                                                                                  // Σ_AA's band
-        const int hi = std::max(A.cp, B.cp), lo = std::min(A.cp, B.cp);
-        const double* b = cv.band.data() + (size_t(lo) * cv.order + (hi - lo)) * 36;
-        v = A.cp >= B.cp ? b[i * 6 + j] : b[j * 6 + i];
-      }
-      t[size_t(i) * tb + j] = v;
-    }
-  if (tangent) { std::copy(t.begin(), t.end(), out); return CALICO_OK; }
-  // ambient: P_a Σ P_bᵀ, P the manifold's PlusJacobian at the value Σ was computed at (identity for Euclidean blocks)
-  double Pa[12], Pb[12];
-  if (qa) quat_plus_jacobian(A.v.data(), Pa);
-  if (qb) quat_plus_jacobian(B.v.data(), Pb);
-  std::vector<double> u(size_t(ra) * tb);       // P_a t
-  for (int i = 0; i < ra; ++i)
-    for (int j = 0; j < tb; ++j) {
-      double v = 0.0;
-      if (qa) { for (int k = 0; k < 3; ++k) v += Pa[i * 3 + k] * t[size_t(k) * tb + j]; }
-      else v = t[size_t(i) * tb + j];
-      u[size_t(i) * tb + j] = v;
-    }
-  for (int i = 0; i < ra; ++i)
-    for (int j = 0; j < rb; ++j) {
-      double v = 0.0;
-      if (qb) { for (int k = 0; k < 3; ++k) v += u[size_t(i) * tb + k] * Pb[j * 3 + k]; }
-      else v = u[size_t(i) * tb + j];
-      out[size_t(i) * rb + j] = v;
-    }
-  return CALICO_OK;
-}
-
-namespace {
-// the readers of the trajectory's blocks: CALICO_OK when the last compute produced them for the problem as it stands
-int trajectory_result_ready(calico_problem* p) {
-  const calico_problem::Covariance& cv = p->cov;
-  if (cv.valid && !p->dirty && !cv.has_cp && cv.cp_requested)
-    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of the trajectory: the problem has no spline control points "
-                                                    "(calico_problem_set_spline)");
-  if (!cv.valid || p->dirty || !cv.has_cp)
-    return p->set_error(CALICO_FAILED_PRECONDITION, "no covariance of the trajectory: call calico_covariance_compute with control_points = 1 "
-                                                    "(again, if the problem changed) and check its status");
-  return CALICO_OK;
-}
-}  // namespace
-
-int32_t calico_covariance_trajectory_info(calico_problem* p, int32_t* n_cp, int32_t* order, double* min_relative_pivot_band) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  if (int rc = trajectory_result_ready(p)) return rc;
-  if (n_cp) *n_cp = p->cov.n_cp;
-  if (order) *order = p->cov.order;
-  if (min_relative_pivot_band) *min_relative_pivot_band = p->cov.min_relative_pivot_band;
-  return CALICO_OK;
-}
-
-// Σ_v(t) at each stamp from Σ_AA's band on the device (cp_stamp_kernel); the segment of a stamp is Interpolate's
-int32_t calico_covariance_trajectory(calico_problem* p, int64_t n, const double* stamps, double* out) {
-  if (!p || n < 0 || (n > 0 && (!stamps || !out))) return CALICO_INVALID_ARGUMENT;
-  if (int rc = trajectory_result_ready(p)) return rc;
-  if (n == 0) return CALICO_OK;
-  if (n > int64_t((INT32_MAX - 255) / 36)) return p->set_error(CALICO_INVALID_ARGUMENT, "covariance: too many stamps in one call");
-  calico_problem::Covariance& cv = p->cov;
-  std::vector<int> seg(static_cast<size_t>(n));
-  std::vector<double> t(stamps, stamps + n);
-  for (int64_t i = 0; i < n; ++i) {
-    seg[size_t(i)] = spline_index(p, stamps[i]);
-    if (seg[size_t(i)] < 0) {
-      char msg[160];
-      std::snprintf(msg, sizeof(msg), "covariance: stamp %lld (%.17g) is outside the trajectory's valid knots [%.17g, %.17g]", (long long)i,
-                    stamps[i], p->valid_knots.front(), p->valid_knots.back());
-      return p->set_error(CALICO_INVALID_ARGUMENT, msg);
-    }
-  }
-  HIP_TRY(p, hipSetDevice(p->device));
-  hipStream_t s = p->stream;
-  HIP_TRY(p, cv.st_t.upload(t, s));
-  HIP_TRY(p, cv.st_seg.upload(seg, s));
-  HIP_TRY(p, cv.st_out.alloc(size_t(n) * 36));
-  (void)hipGetLastError();
-  launch_cp_stamps(int(n), cv.order, cv.st_t.p, cv.st_seg.p, p->d_knots.p, p->d_basis.p, cv.cp_band.p, cv.st_out.p, s);
-  HIP_TRY(p, hipGetLastError());
-  HIP_TRY(p, hipMemcpyAsync(out, cv.st_out.p, size_t(n) * 36 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(p, hipStreamSynchronize(s));
-  return CALICO_OK;
-}
-
-void calico_default_prediction_options(calico_prediction_options* o) {
-  if (!o) return;
-  std::memset(o, 0, sizeof(*o));
-  o->apply_loss = 1;
-}
-
-// P_i = J_i Σ J_iᵀ of every registered observation of a sensor (prediction_items_kernel): J_i at the current values, Σ the
-// device copies the last compute with control_points = 1 left (Σ_EE in cov.out, Σ_AE in cov.cp_sae, Σ_AA's band in
-// cov.cp_band). Output buffers of its own; nothing of the LM's, of the residual cache or of the stored reports is touched.
-int32_t calico_prediction_covariance(calico_problem* p, int32_t sid, const calico_prediction_options* opt, double* cov_out,
-                                     double* leverage_out, uint8_t* valid) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  calico_prediction_options def;
-  calico_default_prediction_options(&def);
-  if (!opt) opt = &def;
-  if (sid < 0 || sid >= int(p->sensors.size())) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: unknown sensor id");
-  if (opt->apply_loss != 0 && opt->apply_loss != 1) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: apply_loss must be 0 or 1");
-  if (!cov_out && !leverage_out && !valid) return p->set_error(CALICO_INVALID_ARGUMENT, "prediction covariance: no output buffer");
-  if (int rc = trajectory_result_ready(p)) return rc;
-  calico_problem::Covariance& cv = p->cov;
-  if (cv.n_cp != p->n_cp || cv.order != p->order || cv.dim != p->m) return p->set_error(CALICO_INTERNAL, "prediction covariance: stored covariance does not match the plan");
-  const HSensor& hs = p->sensors[size_t(sid)];
-  const int64_t n = hs.n();
-  if (n == 0) return CALICO_OK;
-  const size_t lds_bytes = pred_lds_doubles(p->pred_cols, p->pred_row_pad) * sizeof(double);
-  if (lds_bytes > kMaxLds) {
-    char msg[200];
-    std::snprintf(msg, sizeof(msg), "prediction covariance: a residual block of %d Jacobian columns needs %zu bytes of LDS staging (at most %zu)",
-                  p->pred_cols, lds_bytes, kMaxLds);
-    return p->set_error(CALICO_UNIMPLEMENTED, msg);
-  }
-  HIP_TRY(p, hipSetDevice(p->device));
-  int rc = upload_x(p);
-  if (rc != CALICO_OK) return rc;
-  const int dim = hs.dim(), dd = dim * dim;
-  const int64_t nrange = hs.sorted_end - hs.sorted_begin;      // (layouts are per sensor: the sensor's observations are contiguous)
-  if (nrange != n) return p->set_error(CALICO_INTERNAL, "prediction covariance: the sensor's observations are not contiguous");
-  hipStream_t s = p->stream;
-  DevBuf<double> d_cov, d_lev;
-  DevBuf<uint8_t> d_val;
-  HIP_TRY(p, d_cov.alloc(size_t(n) * dd)); HIP_TRY(p, d_lev.alloc(size_t(n))); HIP_TRY(p, d_val.alloc(size_t(n)));
-  PredArgs pa = {};
-  pa.e = make_eval_args(p, p->d_x.p, opt->apply_loss, false);
-  pa.e.items = p->d_items_all.p; pa.e.n_items = p->n_items_all;      // every rank evaluates all blocks
-  pa.e.active = nullptr;                                             // tagged observations included
-  pa.e.row_pad = p->pred_row_pad; pa.e.lds_cols = (p->pred_cols + 15) & ~15;
-  pa.sensor = sid; pa.obs_begin = int(hs.sorted_begin); pa.n_cp = p->n_cp; pa.mc = p->m;
-  pa.colmap = p->d_pred_map.p; pa.map_stride = p->pred_map_stride;
-  pa.sigma = cv.out.p; pa.sae = cv.cp_sae.p; pa.band = cv.cp_band.p;
-  pa.cov = d_cov.p; pa.leverage = d_lev.p; pa.valid = d_val.p;
-  (void)hipGetLastError();
-  HIP_TRY(p, launch_prediction(pa, lds_bytes, s));
-  std::vector<double> hc(size_t(n) * dd), hl(static_cast<size_t>(n));
-  std::vector<uint8_t> hv(static_cast<size_t>(n));
-  HIP_TRY(p, hipMemcpyAsync(hc.data(), d_cov.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(p, hipMemcpyAsync(hl.data(), d_lev.p, hl.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(p, hipMemcpyAsync(hv.data(), d_val.p, hv.size(), hipMemcpyDeviceToHost, s));
-  HIP_TRY(p, hipStreamSynchronize(s));
-  for (int64_t i = 0; i < n; ++i) {
-    const size_t q = size_t(hs.sorted_pos[size_t(i)] - hs.sorted_begin);
-    if (cov_out) std::copy(hc.begin() + q * dd, hc.begin() + (q + 1) * dd, cov_out + i * dd);
-    if (leverage_out) leverage_out[i] = hl[q];
-    if (valid) valid[i] = hv[q];
-  }
-  return CALICO_OK;
-}
-
-void calico_default_observability_options(calico_observability_options* o) {
-  if (!o) return;
-  std::memset(o, 0, sizeof(*o));
-  o->weak_threshold = 1e-10;
-  o->min_relative_pivot = 1e-12;
-}
-
-// The spectrum of S̃ = D⁻¹ (C - Eᵀ A⁻¹ E) D⁻¹ at the current values: the covariance pass's evaluation and undamped reduction
-// (begin_undamped_pass), the band's own factorisation for its minimum relative pivot (cp_band_factor_kernel, natural order:
-// is A invertible at all?), then observability_kernel (obs_kernels.hip). Leaves alone what the covariance pass leaves alone,
-// and the stored covariance.
-int32_t calico_observability_compute(calico_problem* p, const calico_observability_options* opt) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  calico_observability_options def;
-  calico_default_observability_options(&def);
-  if (!opt) opt = &def;
-  if (!(opt->min_relative_pivot >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "min_relative_pivot must be >= 0");
-  if (!(opt->weak_threshold >= 0.0)) return p->set_error(CALICO_INVALID_ARGUMENT, "weak_threshold must be >= 0");
-  if (p->world > 1 && !p->has_exchange())
-    return p->set_error(CALICO_FAILED_PRECONDITION, "calico_problem_set_shard(world > 1) needs an exchange: calico_comm_init_rccl or calico_problem_set_allreduce");
-  int rc = finalize(p);
-  if (rc != CALICO_OK) return rc;
-  HIP_TRY(p, hipSetDevice(p->device));
-  calico_problem::Observability& ob = p->obs;
-  ob.valid = false;
-  SolveArgs sa = make_solve_args(p);
-  const int mc = p->m, m = sa.m;
-  if (mc > observability_max_border())
-    return p->set_error(CALICO_UNIMPLEMENTED, "observability: border of " + std::to_string(mc) + " columns (at most " +
-                                                  std::to_string(observability_max_border()) + ")");
-  if (m > observability_max_dim())
-    return p->set_error(CALICO_UNIMPLEMENTED, "observability: reduced system of " + std::to_string(m) + " rows (at most " +
-                                                  std::to_string(observability_max_dim()) + ")");
-  const bool have_band = p->n_cp > 0 && p->order <= cp_covariance_max_order();
-  CpCovArgs ca = {};
-  if (have_band) {
-    const int n_cp = p->n_cp, k = p->order;
-    HIP_TRY(p, ob.cp_dq.alloc(6 * size_t(n_cp))); HIP_TRY(p, ob.cp_L.alloc(size_t(n_cp) * k * 36)); HIP_TRY(p, ob.cp_Li.alloc(size_t(n_cp) * 36));
-    HIP_TRY(p, ob.cp_info.alloc(2));
-    ca.R = sa.R; ca.off_B = sa.off_B(); ca.off_E = sa.off_E(); ca.n_cp = n_cp; ca.k = k; ca.mc = mc;
-    ca.dq = ob.cp_dq.p; ca.L = ob.cp_L.p; ca.Li = ob.cp_Li.p; ca.info = ob.cp_info.p;
-  }
-  const bool in_lds = observability_in_lds(m, mc);
-  const size_t n2 = size_t(mc) * mc;
-  HIP_TRY(p, ob.lam.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.vec.alloc(n2 + 1)); HIP_TRY(p, ob.mat.alloc(n2 + 1));
-  HIP_TRY(p, ob.dvec.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.info.alloc(8));
-  if (!in_lds) HIP_TRY(p, ob.work.alloc(observability_work_doubles(m, mc)));
-  HIP_TRY(p, configure_observability_kernel());
-  hipStream_t s = p->stream;
-  LmOptionsDev o = {};
-  rc = begin_undamped_pass(p, {ob.st, ob.scale, ob.dadd, ob.y, ob.zbuf}, sa, o);
-  if (rc != CALICO_OK) return rc;
-  if (have_band) {      // (reads the band of R as the evaluation left it: ahead of the reduction)
-    launch_cp_band_factor(ca, s);
-    HIP_TRY(p, hipGetLastError());
-  }
-  if (mc > 0) {
-    enqueue_linear_solve(p, sa, o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
-    HIP_TRY(p, hipGetLastError());
-    launch_observability(sa.Spart, reduced_schur_slices(sa), m, mc, sa.R + sa.off_C(), ob.st.p, ob.work.p, ob.lam.p, ob.vec.p, ob.mat.p,
-                         ob.dvec.p, ob.info.p, s);
-    HIP_TRY(p, hipGetLastError());
-  }
-  double info[8] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, in_lds ? 1.0 : 0.0, 0.0};
-  double cp_info[2] = {1.0, 0.0};
-  std::vector<double> R01(2), lam(size_t(mc), 0.0);
-  HIP_TRY(p, hipMemcpyAsync(R01.data(), p->d_R.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  ob.vectors.assign(n2, 0.0); ob.matrix.assign(n2, 0.0); ob.d.assign(size_t(mc), 0.0);
-  if (have_band) HIP_TRY(p, hipMemcpyAsync(cp_info, ob.cp_info.p, sizeof(cp_info), hipMemcpyDeviceToHost, s));
-  if (mc > 0) {
-    HIP_TRY(p, hipMemcpyAsync(info, ob.info.p, sizeof(info), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(lam.data(), ob.lam.p, lam.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(ob.vectors.data(), ob.vec.p, n2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(ob.matrix.data(), ob.mat.p, n2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(p, hipMemcpyAsync(ob.d.data(), ob.dvec.p, size_t(mc) * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(p, hipStreamSynchronize(s));
-  if (R01[1] > 0.0) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: the residual evaluation failed at the current parameter values");
-  const int flags = int(info[1]), cpf = int(cp_info[1]);
-  ob.min_relative_pivot_band = cp_info[0]; ob.min_relative_pivot_root = info[0];
-  if (cpf & 1) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: the trajectory's control-point block of JᵀJ is not finite");
-  // A itself is singular: S does not exist. The band's own pivot (natural order), the tree levels' flag, the root rows' pivot
-  // (checked ahead of the reduced system's values: an elimination that failed leaves non-finite ones behind).
-  if ((cpf & 2) || cp_info[0] < opt->min_relative_pivot || (flags & (2 | 4)) || info[0] < opt->min_relative_pivot) {
-    char msg[512];
-    std::snprintf(msg, sizeof(msg), "observability: the trajectory's control-point band of JᵀJ is rank deficient (minimum relative pivot %.3e of "
-                  "the band, %.3e of the root rows, threshold %.3e%s): the data do not determine the trajectory, so the calibration's Schur "
-                  "complement does not exist", cp_info[0], info[0], opt->min_relative_pivot,
-                  (flags & 4) ? "; a block of the control points' elimination is not positive definite" : "");
-    return p->set_error(CALICO_FAILED_PRECONDITION, msg);
-  }
-  if (flags & 1) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: non-finite value in the reduced system");
-  if (flags & 16)
-    return p->set_error(CALICO_INTERNAL, "observability: the Jacobi eigensolver did not converge in " + std::to_string(int(info[4])) + " sweeps");
-  if (flags & 8) return p->set_error(CALICO_FAILED_PRECONDITION, "observability: non-finite value in the result");
-  ob.dim = mc; ob.n_unobserved = int(info[2]); ob.kept = mc > 0 ? int(info[3]) : 0; ob.sweeps = int(info[4]); ob.rotations = int(info[5]);
-  ob.in_lds = int(info[6]); ob.reduced_rows = int(info[7]);
-  if (ob.kept < 0 || ob.kept > mc) return p->set_error(CALICO_INTERNAL, "observability: kept columns out of range");
-  ob.eigenvalues.assign(lam.begin(), lam.begin() + ob.kept);
-  ob.n_weak = 0;
-  for (double v : ob.eigenvalues) ob.n_weak += v < opt->weak_threshold ? 1 : 0;
-  ob.blocks.resize(p->blocks.size());
-  for (size_t i = 0; i < p->blocks.size(); ++i) {
-    const HBlock& h = p->blocks[i];
-    const bool in = !h.constant && h.used;
-    const bool is_cp = h.tan >= 0 && h.tan < 6 * p->n_cp;
-    const int tsize = h.manifold == CALICO_MANIFOLD_EIGEN_QUATERNION ? 3 : h.size;
-    ob.blocks[i] = {in ? (is_cp ? -2 : h.tan - 6 * p->n_cp) : -1, tsize};
-  }
-  ob.valid = true;
-  return CALICO_OK;
-}
-
-namespace {
-const char* const kNoObservability = "no observability report of this problem: call calico_observability_compute (again, if the problem "
-                                     "changed) and check its status";
-bool observability_ready(const calico_problem* p) { return p->obs.valid && !p->dirty; }
-// row i of the report in the requested units: v_i, or δ_i = D⁻¹ v_i / |D⁻¹ v_i|
-void observability_direction(const calico_problem::Observability& ob, int i, int tangent_units, double* out) {
-  const double* v = ob.vectors.data() + size_t(i) * ob.dim;
-  if (!tangent_units) { std::copy(v, v + ob.dim, out); return; }
-  double nrm = 0.0;
-  for (int j = 0; j < ob.dim; ++j) { out[j] = ob.d[size_t(j)] > 0.0 ? v[j] / ob.d[size_t(j)] : 0.0; nrm += out[j] * out[j]; }
-  nrm = std::sqrt(nrm);
-  if (nrm > 0.0) for (int j = 0; j < ob.dim; ++j) out[j] /= nrm;
-}
-}  // namespace
-
-int32_t calico_observability_info(calico_problem* p, int32_t* dim, int32_t* n_unobserved, int32_t* n_weak, double* lambda_min,
-                                  double* lambda_max, int32_t* sweeps) {
-  if (!p) return CALICO_INVALID_ARGUMENT;
-  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  const calico_problem::Observability& ob = p->obs;
-  if (dim) *dim = ob.dim;
-  if (n_unobserved) *n_unobserved = ob.n_unobserved;
-  if (n_weak) *n_weak = ob.n_weak;
-  if (lambda_min) *lambda_min = ob.eigenvalues.empty() ? 0.0 : ob.eigenvalues.front();
-  if (lambda_max) *lambda_max = ob.eigenvalues.empty() ? 0.0 : ob.eigenvalues.back();
-  if (sweeps) *sweeps = ob.sweeps;
-  return CALICO_OK;
-}
-
-int32_t calico_observability_get_spectrum(calico_problem* p, double* eigenvalues) {
-  if (!p || !eigenvalues) return CALICO_INVALID_ARGUMENT;
-  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  std::copy(p->obs.eigenvalues.begin(), p->obs.eigenvalues.end(), eigenvalues);
-  return CALICO_OK;
-}
-
-int32_t calico_observability_get_directions(calico_problem* p, int32_t first, int32_t count, int32_t tangent_units, double* out) {
-  if (!p || !out) return CALICO_INVALID_ARGUMENT;
-  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  const calico_problem::Observability& ob = p->obs;
-  if (first < 0 || count < 0 || first > ob.kept || count > ob.kept - first)
-    return p->set_error(CALICO_INVALID_ARGUMENT, "observability: directions [" + std::to_string(first) + ", " + std::to_string(int64_t(first) + count) +
-                                                     ") out of range (" + std::to_string(ob.kept) + " directions)");
-  for (int i = 0; i < count; ++i) observability_direction(ob, first + i, tangent_units, out + size_t(i) * ob.dim);
-  return CALICO_OK;
-}
-
-int32_t calico_observability_get_block(calico_problem* p, int32_t index, int32_t block_id, int32_t tangent_units, double* out, double* share) {
-  if (!p || (!out && !share)) return CALICO_INVALID_ARGUMENT;
-  const int nb = int(p->blocks.size());
-  if (block_id < 0 || block_id >= nb) return p->set_error(CALICO_INVALID_ARGUMENT, "observability: unknown parameter block id");
-  if (!observability_ready(p) || size_t(nb) != p->obs.blocks.size()) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  const calico_problem::Observability& ob = p->obs;
-  if (index < 0 || index >= ob.kept) return p->set_error(CALICO_INVALID_ARGUMENT, "observability: direction index out of range");
-  const calico_problem::Observability::Blk& B = ob.blocks[size_t(block_id)];
-  if (B.off == -2)
-    return p->set_error(CALICO_INVALID_ARGUMENT, "observability: a control point is not part of the report (the trajectory is eliminated)");
-  if (out) std::fill(out, out + B.tsize, 0.0);
-  if (share) *share = 0.0;
-  if (B.off == -1) return CALICO_OK;      // constant / unused blocks: zeros
-  if (B.off < 0 || B.off + B.tsize > ob.dim) return p->set_error(CALICO_INTERNAL, "observability: block layout out of range");
-  if (out) {
-    std::vector<double> dir(size_t(ob.dim));
-    observability_direction(ob, index, tangent_units, dir.data());
-    std::copy(dir.begin() + B.off, dir.begin() + B.off + B.tsize, out);
-  }
-  if (share) {
-    const double* v = ob.vectors.data() + size_t(index) * ob.dim + B.off;
-    double sh = 0.0;
-    for (int j = 0; j < B.tsize; ++j) sh += v[j] * v[j];
-    *share = sh;
-  }
-  return CALICO_OK;
-}
-
-int32_t calico_observability_get_matrix(calico_problem* p, double* out) {
-  if (!p || !out) return CALICO_INVALID_ARGUMENT;
-  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  std::copy(p->obs.matrix.begin(), p->obs.matrix.end(), out);
-  return CALICO_OK;
-}
-
-// test hook (calico_hip_testing.h)
-int32_t calico_debug_observability_info(calico_problem* p, double* out, int32_t n) {
-  if (!p || !out || n < 0) return CALICO_INVALID_ARGUMENT;
-  if (!observability_ready(p)) return p->set_error(CALICO_FAILED_PRECONDITION, kNoObservability);
-  const calico_problem::Observability& ob = p->obs;
-  const double v[6] = {double(ob.in_lds), double(ob.kept), double(ob.reduced_rows), double(ob.rotations), ob.min_relative_pivot_band,
-                       ob.min_relative_pivot_root};
-  for (int i = 0; i < n && i < 6; ++i) out[i] = v[i];
   return CALICO_OK;
 }
 

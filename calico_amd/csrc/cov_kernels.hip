@@ -24,7 +24,9 @@
 #include <cmath>
 
 #include "device_math.hpp"
+#include "kernels.hpp"
 #include "problem_dev.hpp"
+#include "reduced_system.hpp"
 #include "solve_dev.hpp"
 
 namespace cal {
@@ -40,8 +42,7 @@ int covariance_max_dim() { return kCovMaxDim; }
 int covariance_ld(int n) { return n | 1; }       // odd row stride: the column walks of LDS hit distinct banks
 bool covariance_in_lds(int n) { return size_t(n) * covariance_ld(n) * sizeof(double) + kCovStaticLds + 1024 <= kCovLdsBudget; }
 
-// info[0]: minimum relative pivot, info[1]: flags (1 non-finite input, 2 pivot not positive, 4 the reduction's own factorisation
-// failed, 8 non-finite result), info[2]: dropped
+// info[0]: minimum relative pivot, info[1]: flags (ReducedInfoFlag, problem_dev.hpp), info[2]: dropped
 // (structurally unobserved) calibration columns, info[3]: rows factored
 template <bool IN_LDS>
 __global__ __launch_bounds__(kCovThreads) void covariance_kernel(const double* __restrict__ Spart, int ks, int m, int mc,
@@ -56,43 +57,22 @@ __global__ __launch_bounds__(kCovThreads) void covariance_kernel(const double* _
   __shared__ double s_minpiv;
   double* const A = IN_LDS ? lds_dyn : work;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nr = m - mc, m1 = m + 1;
-  const size_t msq = size_t(m1) * m1;
-  // ---- 1. compact order: extra rows, then the observed calibration columns (a ballot per 64 columns) ----
+  const int nr = m - mc;
+  // ---- 1. compact order: extra rows, then the observed calibration columns (reduced_system.hpp) ----
   if (wave == 0) {
-    int cnt = 0;
-    for (int b0 = 0; b0 < mc; b0 += 64) {
-      const int j = b0 + lane;
-      const bool keep = j < mc && Cdiag[size_t(min(j, mc - 1)) * (mc + 1)] != 0.0;
-      const unsigned long long bal = __ballot(keep);
-      const int pos = cnt + __popcll(bal & ((1ull << lane) - 1ull));
-      if (keep) s_idx[nr + pos] = j;
-      cnt += __popcll(bal);
-    }
-    for (int r = lane; r < nr; r += 64) s_idx[r] = mc + r;
-    if (lane == 0) { s_nkeep = cnt; s_flags = (st->chol_failed ? 4 : 0); s_minpiv = 1.0; }
+    const int cnt = reduced_compact_order(s_idx, Cdiag, m, mc, lane);
+    if (lane == 0) { s_nkeep = cnt; s_flags = (st->chol_failed ? kInfoEliminationFailed : 0); s_minpiv = 1.0; }
   }
   for (size_t e = tid; e < size_t(mc) * mc; e += kCovThreads) out[e] = 0.0;
   __syncthreads();
   const int nc = s_nkeep, n = nr + nc, LD = n | 1;
   // ---- 2. load (slices added in order), equilibrate ----
-  int bad = 0;
-  for (int e = tid; e < n * n; e += kCovThreads) {
-    const int p = e / n, q = e - p * n;
-    if (q > p) continue;
-    const int oi = s_idx[p], oj = s_idx[q];
-    const size_t o = size_t(max(oi, oj)) * m1 + min(oi, oj);
-    double v = Spart[o];
-    for (int k = 1; k < ks; ++k) v += Spart[size_t(k) * msq + o];
-    bad |= !isfinite(v);
-    A[p * LD + q] = v;
-  }
-  if (bad) atomicOr(&s_flags, 1);
+  if (reduced_load_lower<kCovThreads>(A, LD, n, s_idx, Spart, ks, m, tid)) atomicOr(&s_flags, kInfoNonFiniteInput);
   __syncthreads();
   for (int p = tid; p < n; p += kCovThreads) {
     const double v = A[p * LD + p];
     const bool ok = v > 0.0 && isfinite(v);
-    if (!ok) atomicOr(&s_flags, 2);
+    if (!ok) atomicOr(&s_flags, kInfoPivotNotPositive);
     s_d[p] = ok ? 1.0 / sqrt(v) : 1.0;
   }
   __syncthreads();
@@ -109,7 +89,7 @@ __global__ __launch_bounds__(kCovThreads) void covariance_kernel(const double* _
   for (int j = 0; j < n; ++j) {
     const double piv = A[j * LD + j];
     if (!(piv > 0.0) || !isfinite(piv)) {       // (uniform: every thread reads the same entry)
-      if (tid == 0) { s_flags |= 2; s_minpiv = fmin(s_minpiv, piv > 0.0 ? piv : 0.0); }
+      if (tid == 0) { s_flags |= kInfoPivotNotPositive; s_minpiv = fmin(s_minpiv, piv > 0.0 ? piv : 0.0); }
       break;
     }
     const double rs = 1.0 / sqrt(piv);
@@ -156,7 +136,7 @@ __global__ __launch_bounds__(kCovThreads) void covariance_kernel(const double* _
       const int ia = s_idx[nr + a], ib = s_idx[nr + b];
       out[size_t(ia) * mc + ib] = v;
       out[size_t(ib) * mc + ia] = v;
-      if (!isfinite(v)) atomicOr(&s_flags, 8);
+      if (!isfinite(v)) atomicOr(&s_flags, kInfoNonFiniteResult);
     }
   }
   __syncthreads();

@@ -21,6 +21,7 @@
 #include <set>
 
 #include "device_math.hpp"
+#include "kernels.hpp"
 #include "problem_dev.hpp"
 
 namespace cal {

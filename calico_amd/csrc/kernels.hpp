@@ -1,0 +1,101 @@
+// kernels.hpp — host interfaces of the kernels: every launch_*, configure_* and size query a .hip file defines, declared once.
+// Included by the host translation units that call them and by the .hip file that defines each: callers and definitions are
+// compiled against the same declarations (and the same default arguments).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "problem_dev.hpp"
+
+namespace cal {
+
+// ---- kernels (eval_kernels.hip / solve_kernels.hip) -------------------------
+void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream);
+void launch_eval_jacobian(const EvalArgs& a, hipStream_t stream);
+void launch_expand_cells(const EvalArgs& a, hipStream_t stream);
+void launch_residual_heatmap(const double* res, const uint8_t* valid, const uint8_t* active, const double* px, const double* py,
+                             int begin, int end, int width, int height, int num_rows, int num_cols, double* rmse, long long* count,
+                             hipStream_t s);
+void launch_inlier_mask(const double* res, uint8_t* valid_then_mask, const uint8_t* active, int begin, int end, int dim, double threshold,
+                        hipStream_t s);
+void launch_mark_outliers(const double* res, const uint8_t* valid, uint8_t* active, int begin, int end, int dim,
+                          double threshold, int* n_marked, hipStream_t s);
+hipError_t configure_eval_kernels(size_t max_lds_bytes);
+hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream);
+
+void launch_gather(double* R, const double* src, const int* out_idx_thin, const int64_t* ptr_thin, const int* idx_thin,
+                   int n_thin, int n_thin8, int n_thin4, int thin_per_lane, const int* out_idx_fat, const int64_t* ptr_fat, const int* idx_fat, int n_fat,
+                   const double* cost_src, int n_cost, const LmState* st, int need_flag, size_t other_stride, hipStream_t s, const ControlTail* tail = nullptr);
+void launch_gather_lists(const GatherStruct& gs, int n_out, int* cnt, int* out_idx, int64_t* ptr, int* idx, int zero_slot, long long* scratch,
+                         hipStream_t s);
+size_t gather_fixed_entries(int n_thin, int n_thin8, int n_thin4, int thin_per_lane);
+void launch_gather_pack_fixed(const int64_t* ptr, const int* idx, int n_thin, int n_thin8, int n_thin4, int thin_per_lane, int zero_slot, int* out,
+                              hipStream_t s);
+void launch_post_eval(const SolveArgs& a, const double* x, const BlockDev* blocks, int n_blocks, const LmOptionsDev& o,
+                      IterLog* log, int log_cap, int first, int jacobi, hipStream_t s);
+size_t band_cholesky_lds_bytes(const SolveArgs& a);
+size_t reduced_solve_lds_bytes(const SolveArgs& a);
+size_t frame_lds_doubles(int Ps, int P1e, int n1);
+size_t band_backsolve_lds_bytes(const SolveArgs& a);
+hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t back_lds);
+void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
+                  int n_blocks, bool dense_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi);
+void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s);
+void launch_control(LmState* st, const LmOptionsDev& o, double* R2, double* x, const double* x_cand, int n_amb,
+                    IterLog* log, int log_cap, const double* item_cost, int n_items, const double* Rbase, size_t r_stride,
+                    hipStream_t s, bool commit_by_copy = false);
+void launch_init_state(LmState* st, double radius, double x_norm, hipStream_t s, const double* upd_ext = nullptr, int upd_ext_n = 0);
+void launch_begin_solve(LmState* st, double radius, double x_norm, const double* upd_ext, int upd_ext_n, const ResultSink& sink, double* x,
+                        double* x_cand, const double* h_x, int n_amb, hipStream_t s);
+void launch_publish_results(const LmState* st, const IterLog* log, int log_rows, const double* x, int n_amb, LmState* h_state,
+                            IterLog* h_log, double* h_x, hipStream_t s);
+void launch_seed_x(double* x, const double* h_x, int n_amb, hipStream_t s);
+void launch_debug_control_replay(LmState* st, const LmOptionsDev& o, const double* rho, const int* infinite, int n, double* R2,
+                                 double* radius_out, int* accepted_out, double* cost_out, IterLog* log, int log_cap, hipStream_t s);
+size_t bcr_level_lds_bytes();
+size_t bcr_back_lds_bytes(int q_max, int m1p);
+hipError_t configure_bcr_kernels(int q_max, int m1p);
+void roll_table_row(int k, int lane, unsigned* out);      // (host only: test hook)
+hipError_t configure_dense_block_solve();
+hipError_t configure_reduced_block_step();
+size_t dense_block_solve_lds_bytes();
+void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
+                      const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
+                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl);
+void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
+void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
+                     const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
+
+void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
+int reduced_solve_route(const SolveArgs& a);
+bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
+size_t dense_back_lds_bytes(int q_max, int m1p);
+hipError_t configure_dense_back_bytes(size_t lds);
+void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
+                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s);
+int reduced_schur_slices(const SolveArgs& a);
+void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const double* x, const BlockDev* blocks, int n_blocks, hipStream_t s,
+                           bool with_post_eval, IterLog* log, int log_cap, int jacobi);
+int covariance_max_dim();
+int covariance_ld(int n);
+bool covariance_in_lds(int n);
+void launch_covariance(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* out,
+                       double* info, hipStream_t s);
+hipError_t configure_covariance_kernel();
+int cp_covariance_max_order();
+void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s);
+void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s);
+void launch_cp_band_factor(const CpCovArgs& a, hipStream_t s);
+int observability_max_border();
+int observability_max_dim();
+bool observability_in_lds(int m, int mc);
+size_t observability_work_doubles(int m, int mc);
+void launch_observability(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* lam,
+                          double* vec, double* mat, double* d, double* info, hipStream_t s);
+hipError_t configure_observability_kernel();
+void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
+                      double* out, hipStream_t s);
+
+}  // namespace cal

@@ -7,8 +7,8 @@
 //   S̃ = D⁻¹ (C - Eᵀ A⁻¹ E) D⁻¹,  D = sqrt(diag C)  (the column norms of J, not diag S: a column the trajectory explains
 //                                                   entirely has diag S ~ 0)
 // on the calibration columns whose C diagonal is not exactly 0.0, and its eigendecomposition S̃ = V Λ Vᵀ. One workgroup:
-//   1. compact order as in covariance_kernel: the extra rows FIRST, then the kept calibration columns;
-//   2. the K-slices are added up in slice order; calibration rows are scaled by 1 / sqrt(C_ii), extra rows by their own
+//   1. the compact order covariance_kernel uses (reduced_system.hpp): the extra rows FIRST, then the kept calibration columns;
+//   2. the K-slices are added up in slice order (the same load); calibration rows are scaled by 1 / sqrt(C_ii), extra rows by their own
 //      diagonal (unit diagonal: their pivots are relative pivots);
 //   3. right-looking FP64 Cholesky over the extra rows only; what is left in the trailing block is S̃ (lower triangle). It
 //      is compacted to the front of the matrix area row by row (a row's target never reaches a row not yet read), mirrored
@@ -21,7 +21,7 @@
 //      A pair is rotated when |a_pq| > eps · max(sqrt|a_pp a_qq|, d_max / (4 nn)), d_max the largest diagonal entry of S̃:
 //      the first term is the relative criterion, the second stops the method from chasing entries of the exactly
 //      deficient directions that are rounding noise of S̃ itself (leaving them moves an eigenvalue by at most
-//      eps d_max / 4). A sweep without a rotation ends the method; kObsMaxSweeps sweeps that did not are reported (flag 16);
+//      eps d_max / 4). A sweep without a rotation ends the method; kObsMaxSweeps sweeps that did not are reported (kInfoSweepLimit);
 //   5. eigenvalues sorted ascending by rank counting (ties: lower index first), each eigenvector's sign fixed (its
 //      largest-magnitude entry positive, the lowest index on a tie), scattered to the border's tangent order.
 // Every sum and every rotation runs in a fixed order and nothing is accumulated atomically: repeated computes are
@@ -33,7 +33,9 @@
 #include <cmath>
 
 #include "device_math.hpp"
+#include "kernels.hpp"
 #include "problem_dev.hpp"
+#include "reduced_system.hpp"
 #include "solve_dev.hpp"
 
 namespace cal {
@@ -83,8 +85,8 @@ __device__ __forceinline__ int obs_block_any(int v, int* s_w) {
 }
 }  // namespace
 
-// info[0]: minimum relative pivot of the extra rows, info[1]: flags (1 non-finite input, 2 pivot of an extra row not
-// positive, 4 the reduction's own factorisation failed, 8 non-finite result, 16 sweep limit), info[2]: dropped
+// info[0]: minimum relative pivot of the extra rows, info[1]: flags (ReducedInfoFlag, problem_dev.hpp; the pivots are the
+// extra rows'), info[2]: dropped
 // (structurally unobserved) calibration columns, info[3]: kept columns, info[4]: sweeps, info[5]: rotations applied,
 // info[6]: 1 in LDS / 0 global workspace, info[7]: rows of the compact reduced system
 template <bool IN_LDS>
@@ -105,21 +107,11 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
   double* const mat = s_col + m;                // the shared matrix area (LDS class)
   int* const s_idx = reinterpret_cast<int*>(mat + (IN_LDS ? obs_shared_doubles(m, mc) : 0));      // compact row -> row of Spart
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nr = m - mc, m1 = m + 1;
-  const size_t msq = size_t(m1) * m1;
-  // ---- 1. compact order: extra rows, then the observed calibration columns (a ballot per 64 columns) ----
+  const int nr = m - mc;
+  // ---- 1. compact order: extra rows, then the observed calibration columns (reduced_system.hpp) ----
   if (wave == 0) {
-    int cnt = 0;
-    for (int b0 = 0; b0 < mc; b0 += 64) {
-      const int j = b0 + lane;
-      const bool keep = j < mc && Cdiag[size_t(min(j, mc - 1)) * (mc + 1)] != 0.0;
-      const unsigned long long bal = __ballot(keep);
-      const int pos = cnt + __popcll(bal & ((1ull << lane) - 1ull));
-      if (keep) s_idx[nr + pos] = j;
-      cnt += __popcll(bal);
-    }
-    for (int r = lane; r < nr; r += 64) s_idx[r] = mc + r;
-    if (lane == 0) { s_nkeep = cnt; s_flags = (st->chol_failed ? 4 : 0); s_minpiv = 1.0; s_dmax = 0.0; }
+    const int cnt = reduced_compact_order(s_idx, Cdiag, m, mc, lane);
+    if (lane == 0) { s_nkeep = cnt; s_flags = (st->chol_failed ? kInfoEliminationFailed : 0); s_minpiv = 1.0; s_dmax = 0.0; }
   }
   for (size_t e = tid; e < size_t(mc) * mc; e += kObsThreads) { vec_out[e] = 0.0; mat_out[e] = 0.0; }
   for (int e = tid; e < mc; e += kObsThreads) { lam_out[e] = 0.0; d_out[e] = 0.0; }
@@ -130,17 +122,7 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
   double* const S = IN_LDS ? mat : work + size_t(m) * obs_ld_reduced(m);            // S̃, full symmetric nn x nn
   double* const V = S + size_t(nn) * LDn;
   // ---- 2. load (slices added in order), scale ----
-  int bad = 0;
-  for (int e = tid; e < n * n; e += kObsThreads) {
-    const int p = e / n, q = e - p * n;
-    if (q > p) continue;
-    const int oi = s_idx[p], oj = s_idx[q];
-    const size_t o = size_t(max(oi, oj)) * m1 + min(oi, oj);
-    double v = Spart[o];
-    for (int k = 1; k < ks; ++k) v += Spart[size_t(k) * msq + o];
-    bad |= !isfinite(v);
-    A[p * LD + q] = v;
-  }
+  int bad = reduced_load_lower<kObsThreads>(A, LD, n, s_idx, Spart, ks, m, tid);
   __syncthreads();
   int badpiv = 0;
   for (int p = tid; p < n; p += kObsThreads) {
@@ -151,7 +133,7 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
   }
   bad = obs_block_any(bad, s_w);
   badpiv = obs_block_any(badpiv, s_w);
-  if (tid == 0) s_flags |= (bad ? 1 : 0) | (badpiv ? 2 : 0);
+  if (tid == 0) s_flags |= (bad ? kInfoNonFiniteInput : 0) | (badpiv ? kInfoPivotNotPositive : 0);
   for (int e = tid; e < n * n; e += kObsThreads) {
     const int p = e / n, q = e - p * n;
     if (q <= p) A[p * LD + q] *= s_d[p] * s_d[q];
@@ -163,7 +145,7 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
     for (int j = 0; j < nr; ++j) {
       const double piv = A[j * LD + j];
       if (!(piv > 0.0) || !isfinite(piv)) {       // (uniform: every thread reads the same entry)
-        if (tid == 0) { s_flags |= 2; s_minpiv = fmin(s_minpiv, piv > 0.0 ? piv : 0.0); }
+        if (tid == 0) { s_flags |= kInfoPivotNotPositive; s_minpiv = fmin(s_minpiv, piv > 0.0 ? piv : 0.0); }
         break;
       }
       const double rs = 1.0 / sqrt(piv);
@@ -276,7 +258,7 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
       __syncthreads();
       rotations += total;
       if (total == 0) break;
-      if (sweeps == kObsMaxSweeps && tid == 0) s_flags |= 16;
+      if (sweeps == kObsMaxSweeps && tid == 0) s_flags |= kInfoSweepLimit;
     }
     // ---- 5. sort ascending, fix the signs, scatter ----
     if (tid < nc) {
@@ -305,7 +287,7 @@ __global__ __launch_bounds__(kObsThreads) void observability_kernel(const double
       d_out[s_idx[nr + tid]] = 1.0 / s_d[nr + tid];
     }
     nonfinite = obs_block_any(nonfinite, s_w);
-    if (tid == 0 && nonfinite) s_flags |= 8;
+    if (tid == 0 && nonfinite) s_flags |= kInfoNonFiniteResult;
   }
   __syncthreads();
   if (tid == 0) {

@@ -370,6 +370,16 @@ struct SolveArgs {
 // kBlockedMaxM), reduced_solve_kernel beyond.
 enum ReducedRoute { kReducedPanel = 0, kReducedBlock = 1, kReducedBlocked = 2, kReducedKernel = 3 };
 
+// Flag bits of info[1] of covariance_kernel and observability_kernel (cov_kernels.hip, obs_kernels.hip), decoded by the host
+// (analysis.cpp)
+enum ReducedInfoFlag : int {
+  kInfoNonFiniteInput = 1,        // non-finite value in the reduced system
+  kInfoPivotNotPositive = 2,      // a pivot of the kernel's own factorisation is not positive
+  kInfoEliminationFailed = 4,     // the reduction's own factorisation failed (LmState.chol_failed)
+  kInfoNonFiniteResult = 8,       // non-finite value in the result
+  kInfoSweepLimit = 16,           // observability_kernel: the Jacobi eigensolver hit its sweep limit
+};
+
 // Arguments of the control-point covariance kernels (cov_kernels.hip). Block storage [n_cp][k][36]: block (J + d, J) row-major.
 struct CpCovArgs {
   const double* R;      // reduce buffer 0: band at off_B, E (6 n_cp x mc, row-major) at off_E

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 
+#include "kernels.hpp"
 #include "problem_dev.hpp"
 #include "solve_dev.hpp"
 

@@ -43,3 +43,164 @@ def has_gpu():
         return torch.cuda.is_available()
     except Exception:
         return False
+
+
+# ---- what the test files share: scenes, solving, reading a problem's state, the two-rank harness, the compiler's remarks ----
+
+def small_scene(camera_model=1, n_cameras=2, imu=True, imu_model=2, robust=False, seed=7, noise=True, **kw):
+    """The small seeded scene of the parity, covariance, observability and prediction tests. noise=False: exact measurements."""
+    from calico_amd import synthetic as syn
+    return syn.make_scene(n_cameras, camera_model, imu, imu_model, cam_rate=10.0, imu_rate=50.0, duration=3.0,
+                          segment_duration=3.0 / 23.9, pixel_noise=0.1 if noise else 0.0,
+                          gyro_noise=1e-3 if noise else 0.0, accel_noise=1e-2 if noise else 0.0, robust=robust,
+                          seed=seed, **kw)
+
+
+def full_size_scene(index):
+    """The shape of configs[3] / configs[4] with scale-and-bias IMUs: the VectorNav model of the configs themselves is
+    singular with a free IMU rotation (see test_imu_models_parity_and_unobserved_columns of test_gpu_covariance.py)."""
+    import numpy as np
+    from calico_amd import synthetic as syn
+    if index == 3:
+        return syn.make_scene(4, 1, True, 2, cam_rate=20.0, imu_rate=200.0, duration=8.7, chart="april", seed=0xCA11C0 + 3,
+                              pixel_noise=0.1, gyro_noise=1.7e-4 * np.sqrt(200.0), accel_noise=2e-3 * np.sqrt(200.0),
+                              robust=True, segment_duration=8.7 / 23.9)
+    return syn.make_scene(8, 1, True, 2, cam_rate=20.0, imu_rate=200.0, duration=21.7, chart="april", seed=0xCA11C0 + 4,
+                          pixel_noise=0.1, gyro_noise=1.7e-4 * np.sqrt(200.0), accel_noise=2e-3 * np.sqrt(200.0),
+                          robust=True, outlier_fraction=0.02, repeats=2, segment_duration=21.7 / 47.9, n_imus=2)
+
+
+def solve(P, api, iters=50):
+    o = api.default_options()
+    o.minimizer_progress_to_stdout = 0
+    o.max_num_iterations = iters
+    return P.solve(o)
+
+
+def copy_values(src, dst):
+    """Parameter values of one built problem into another built from the same scene."""
+    for b, n in dict(src.problem._sizes).items():
+        dst.problem.set_param_block(b, src.problem.get_param_block(b, n))
+
+
+def _state(built, scene):
+    """({block id: values}, [every sensor's (residuals, valid flags)]) of a built problem."""
+    P = built.problem
+    vals = {b: P.get_param_block(b, n) for b, n in dict(P._sizes).items()}
+    res = [P.residuals(sid, s.n, 2 if s.kind == _capi.SENSOR_CAMERA else 3) for sid, s in zip(built.sensor_ids, scene.sensors)]
+    return vals, res
+
+
+def border_layout(built, scene):
+    """{block id: (offset, tangent size)} of the dense border and its dimension, derived from the scene's structure alone: the
+    free blocks a residual uses, control points excluded, in block-id order (the order calico_num_effective_parameters
+    documents)."""
+    import numpy as np
+    free, used = {}, set()
+    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (len(scene.points),))
+    for b, c in zip(built.point_blocks, pc):
+        free[int(b)] = (not c, 3)
+    free[built.body_t_block] = (not scene.body_pose_constant, 3)
+    free[built.body_q_block] = (not scene.body_pose_constant, 3)
+    free[built.gravity_block] = (False, 3)
+    for s, b in zip(scene.sensors, built.sensor_blocks):
+        free[b["intrinsics"]] = (s.enable_intrinsics, len(s.intrinsics))
+        free[b["t"]] = (s.enable_extrinsics, 3)
+        free[b["q"]] = (s.enable_extrinsics, 3)
+        free[b["latency"]] = (s.enable_latency, 1)
+        if s.n:
+            used.update([b["intrinsics"], b["t"], b["q"], b["latency"]])
+            if s.kind == _capi.SENSOR_CAMERA:
+                used.update(int(built.point_blocks[i]) for i in np.unique(s.point_idx))
+                used.update([built.body_t_block, built.body_q_block])
+    out, off = {}, 0
+    for b in sorted(free):
+        if free[b][0] and b in used:
+            out[b] = (off, free[b][1])
+            off += free[b][1]
+    return out, off
+
+
+class _DevArray:
+    """A device buffer of n doubles at `ptr` for torch.as_tensor."""
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+
+def run_two_ranks(api, scene, values, per_rank, world=2):
+    """Two ranks on one device: each a handle built from `scene` with the parameter values `values` ({block id: values})
+    installed, sharded to its time window (calico_problem_set_shard) with a host exchange (sum in rank order).
+    per_rank(built) runs in a thread per rank; returns the list of its results, rank by rank. Fails with the errors
+    collected from the exchange and the threads."""
+    import threading
+    import torch
+    from calico_amd import synthetic as syn
+    ranks = []
+    for r in range(world):
+        b = syn.build_problem(api, scene)
+        for blk, v in values.items():
+            b.problem.set_param_block(blk, v)
+        b.problem.set_shard(r, world)
+        ranks.append(b)
+    meet = threading.Barrier(world, timeout=120)
+    staged = [None] * world
+    results, errors = [None] * world, []
+
+    def make_allreduce(rank):
+        def allreduce(ctx, buf, n, strm):
+            try:
+                torch.cuda.ExternalStream(strm).synchronize()
+                t = torch.as_tensor(_DevArray(buf, n), device="cuda")
+                staged[rank] = t.cpu().numpy().copy()
+                meet.wait()
+                total = staged[0].copy()
+                for k in range(1, world):
+                    total += staged[k]
+                meet.wait()
+                t.copy_(torch.from_numpy(total).cuda())
+                torch.cuda.synchronize()
+                return 0
+            except Exception as e:      # noqa: BLE001
+                errors.append(repr(e))
+                meet.abort()
+                return 1
+        return allreduce
+
+    for r, b in enumerate(ranks):
+        b.problem.set_allreduce(make_allreduce(r))
+
+    def run(r):
+        try:
+            results[r] = per_rank(ranks[r])
+        except Exception as e:      # noqa: BLE001
+            errors.append(repr(e))
+    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=180)
+    assert not errors, errors
+    return results
+
+
+def kernel_resources(source):
+    """{kernel's mangled name: {remark: value}} of one file of calico_amd/csrc, from the compiler's own remarks
+    (-Rpass-analysis=kernel-resource-usage) of a device-only compile with the build's flags."""
+    import re
+    import __graft_entry__ as entry
+    src = os.path.join(entry.CSRC, source)
+    flags = [f for f in entry.HIP_FLAGS if f != "-fPIC"] + entry.HIP_FILE_FLAGS.get(source, [])
+    r = subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            res[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
+        if m and name:
+            res[name][m.group(1).strip()] = int(m.group(2))
+    return res

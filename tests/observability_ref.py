@@ -3,14 +3,8 @@ test_gpu_observability.py: the scenes, and the numpy recipe that turns the oracl
 S̃ = D⁻¹ (C - Eᵀ A⁻¹ E) D⁻¹ (include/calico_hip.h, "observability of the calibration")."""
 import numpy as np
 
-from calico_amd import _capi, synthetic as syn
-
-
-def small_scene(camera_model=1, n_cameras=2, imu=True, imu_model=2, robust=False, seed=7, **kw):
-    """The small scene of the covariance tests (same seeds, same rates)."""
-    return syn.make_scene(n_cameras, camera_model, imu, imu_model, cam_rate=10.0, imu_rate=50.0, duration=3.0,
-                          segment_duration=3.0 / 23.9, pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=robust,
-                          seed=seed, **kw)
+from calico_amd import _capi
+from helpers import border_layout, copy_values, small_scene  # noqa: F401  (the tests reach them through this module)
 
 
 # name -> (scene factory, solver iterations before the pass (0: at the start values), n_weak with the default options)
@@ -36,12 +30,6 @@ MORE_SCENES = {
 SINGULAR_SCENES = [k for k, v in TABLE_SCENES.items() if v[2] > 0]
 WEAK_THRESHOLD = 1e-10       # calico_default_observability_options
 GAP = 1e6                    # the subspace comparison needs λ_ref[n_weak] / max|λ_ref[:n_weak]| at least this
-
-
-def copy_values(src, dst):
-    """Parameter values of one built problem into another built from the same scene."""
-    for b, n in dict(src.problem._sizes).items():
-        dst.problem.set_param_block(b, src.problem.get_param_block(b, n))
 
 
 def band_min_pivot(A, bandwidth):
@@ -93,34 +81,6 @@ def weak_count(lam):
 
 def projector(V, k):
     return V[:, :k] @ V[:, :k].T
-
-
-def border_layout(built, scene):
-    """{block id: (offset, tangent size)} of the dense border and its dimension, from the scene's structure alone: the free
-    blocks a residual uses, control points excluded, in block-id order."""
-    free, used = {}, set()
-    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (len(scene.points),))
-    for b, c in zip(built.point_blocks, pc):
-        free[int(b)] = (not c, 3)
-    free[built.body_t_block] = (not scene.body_pose_constant, 3)
-    free[built.body_q_block] = (not scene.body_pose_constant, 3)
-    free[built.gravity_block] = (False, 3)
-    for s, b in zip(scene.sensors, built.sensor_blocks):
-        free[b["intrinsics"]] = (s.enable_intrinsics, len(s.intrinsics))
-        free[b["t"]] = (s.enable_extrinsics, 3)
-        free[b["q"]] = (s.enable_extrinsics, 3)
-        free[b["latency"]] = (s.enable_latency, 1)
-        if s.n:
-            used.update([b["intrinsics"], b["t"], b["q"], b["latency"]])
-            if s.kind == _capi.SENSOR_CAMERA:
-                used.update(int(built.point_blocks[i]) for i in np.unique(s.point_idx))
-                used.update([built.body_t_block, built.body_q_block])
-    out, off = {}, 0
-    for b in sorted(free):
-        if free[b][0] and b in used:
-            out[b] = (off, free[b][1])
-            off += free[b][1]
-    return out, off
 
 
 def null_space_blocks(name, built, scene):

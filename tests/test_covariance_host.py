@@ -4,7 +4,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import pytest
@@ -12,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
+import helpers  # noqa: E402
 from calico_amd import _capi  # noqa: E402
 
 NAMES = ["default_covariance_options", "covariance_compute", "covariance_info", "covariance_get_dense", "covariance_get_block"]
@@ -33,21 +33,7 @@ def test_covariance_entries_declared_and_exported():
 
 @pytest.mark.skipif(shutil.which(entry.HIPCC) is None and not os.path.exists(entry.HIPCC), reason="no hipcc")
 def test_covariance_kernel_scratch_free():
-    src = os.path.join(entry.CSRC, "cov_kernels.hip")
-    flags = [f for f in entry.HIP_FLAGS if f != "-fPIC"] + entry.HIP_FILE_FLAGS.get("cov_kernels.hip", [])
-    r = subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
+    res = helpers.kernel_resources("cov_kernels.hip")
     ks = {k: v for k, v in res.items() if "covariance_kernel" in k}
     assert len(ks) == 2, sorted(res)      # the in-LDS and the global-memory variant
     for k, v in ks.items():

@@ -9,14 +9,9 @@ import numpy as np
 import pytest
 
 from calico_amd import _capi, synthetic as syn
+from helpers import _state, border_layout, full_size_scene, run_two_ranks, small_scene, solve
 
 pytestmark = pytest.mark.gpu
-
-
-def small_scene(camera_model=1, n_cameras=2, imu=True, imu_model=2, robust=False, seed=7, **kw):
-    return syn.make_scene(n_cameras, camera_model, imu, imu_model, cam_rate=10.0, imu_rate=50.0, duration=3.0,
-                          segment_duration=3.0 / 23.9, pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=robust,
-                          seed=seed, **kw)
 
 
 def _sizes(P):
@@ -74,13 +69,6 @@ def check_parity(gpu, ref, tol, what="", singular=False):
     return Sg, Sr, piv
 
 
-def solve(P, api, iters=50):
-    o = api.default_options()
-    o.minimizer_progress_to_stdout = 0
-    o.max_num_iterations = iters
-    return P.solve(o)
-
-
 # OpenCV8 (model 2) at the synthetic start values is exactly singular: its distortion starts at 0 (synthetic.py,
 # _initial_intrinsics), where the numerator and denominator terms of the same radial power have opposite Jacobian columns
 # (d/dk4 = -d/dk1, d/dk5 = -d/dk2, d/dk6 = -d/dk3 at k = 0; the oracle's equilibrated JᵀJ has eigenvalues ~1e-16).
@@ -128,34 +116,6 @@ def test_imu_models_parity_and_unobserved_columns(imu_model, singular, robust, h
     gyro = [b for s, b in zip(scene.sensors, gpu.sensor_blocks) if s.kind == _capi.SENSOR_GYROSCOPE][0]
     assert np.all(gpu.problem.covariance_block(gyro["t"], gyro["t"]) == 0.0)
     assert np.all(gpu.problem.covariance_block(gyro["intrinsics"], gyro["intrinsics"]).diagonal() > 0.0)
-
-
-def border_layout(built, scene):
-    """{block id: (offset, tangent size)} of the dense border, derived from the scene's structure alone: the free blocks a
-    residual uses, control points excluded, in block-id order (the order calico_num_effective_parameters documents)."""
-    free, used = {}, set()
-    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (len(scene.points),))
-    for b, c in zip(built.point_blocks, pc):
-        free[int(b)] = (not c, 3)
-    free[built.body_t_block] = (not scene.body_pose_constant, 3)
-    free[built.body_q_block] = (not scene.body_pose_constant, 3)
-    free[built.gravity_block] = (False, 3)
-    for s, b in zip(scene.sensors, built.sensor_blocks):
-        free[b["intrinsics"]] = (s.enable_intrinsics, len(s.intrinsics))
-        free[b["t"]] = (s.enable_extrinsics, 3)
-        free[b["q"]] = (s.enable_extrinsics, 3)
-        free[b["latency"]] = (s.enable_latency, 1)
-        if s.n:
-            used.update([b["intrinsics"], b["t"], b["q"], b["latency"]])
-            if s.kind == _capi.SENSOR_CAMERA:
-                used.update(int(built.point_blocks[i]) for i in np.unique(s.point_idx))
-                used.update([built.body_t_block, built.body_q_block])
-    out, off = {}, 0
-    for b in sorted(free):
-        if free[b][0] and b in used:
-            out[b] = (off, free[b][1])
-            off += free[b][1]
-    return out, off
 
 
 def test_quaternion_block_tangent_and_ambient(hip, oracle):
@@ -220,13 +180,6 @@ def test_gauge_deficiency_is_refused(hip, oracle):
     assert e.value.code == _capi.FAILED_PRECONDITION
     s = solve(gpu.problem, hip, 20)
     assert s.final_cost < s.initial_cost
-
-
-def _state(built, scene):
-    P = built.problem
-    vals = {b: P.get_param_block(b, n) for b, n in _sizes(P).items()}
-    res = [P.residuals(sid, s.n, 2 if s.kind == _capi.SENSOR_CAMERA else 3) for sid, s in zip(built.sensor_ids, scene.sensors)]
-    return vals, res
 
 
 def test_no_side_effects(hip):
@@ -320,18 +273,6 @@ def test_stale_result_is_refused_after_the_problem_changes(hip):
     assert P.covariance_block(intr, intr).shape == before.shape
 
 
-def full_size_scene(index):
-    """The shape of configs[3] / configs[4] with scale-and-bias IMUs: the VectorNav model of the configs themselves is
-    singular with a free IMU rotation (see test_imu_models_parity_and_unobserved_columns)."""
-    if index == 3:
-        return syn.make_scene(4, 1, True, 2, cam_rate=20.0, imu_rate=200.0, duration=8.7, chart="april", seed=0xCA11C0 + 3,
-                              pixel_noise=0.1, gyro_noise=1.7e-4 * np.sqrt(200.0), accel_noise=2e-3 * np.sqrt(200.0),
-                              robust=True, segment_duration=8.7 / 23.9)
-    return syn.make_scene(8, 1, True, 2, cam_rate=20.0, imu_rate=200.0, duration=21.7, chart="april", seed=0xCA11C0 + 4,
-                          pixel_noise=0.1, gyro_noise=1.7e-4 * np.sqrt(200.0), accel_noise=2e-3 * np.sqrt(200.0),
-                          robust=True, outlier_fraction=0.02, repeats=2, segment_duration=21.7 / 47.9, n_imus=2)
-
-
 @pytest.mark.parametrize("index", [3, 4])
 def test_full_size_parity_and_wall_time(index, hip, oracle):
     import time
@@ -353,62 +294,17 @@ def test_multirank_two_handles_agree(hip):
     """Two ranks on one device, each a handle sharded to its time window (calico_problem_set_shard) with a host exchange
     (sum in rank order): both
     hold the same Σ bit for bit, equal to the single-rank Σ to rounding."""
-    import threading
-    import torch
-    from test_gpu_multirank import _DevArray
     scene = small_scene(camera_model=1, imu=True, robust=True, seed=3)
     single = syn.build_problem(hip, scene)
     solve(single.problem, hip)
     vals = {b: single.problem.get_param_block(b, n) for b, n in _sizes(single.problem).items()}
     single.problem.covariance_compute()
     S1 = single.problem.covariance_dense()
-    world = 2
-    ranks = []
-    for r in range(world):
-        b = syn.build_problem(hip, scene)
-        for blk, v in vals.items():
-            b.problem.set_param_block(blk, v)
-        b.problem.set_shard(r, world)
-        ranks.append(b)
-    meet = threading.Barrier(world, timeout=120)
-    staged = [None] * world
-    results, errors = [None] * world, []
 
-    def make_allreduce(rank):
-        def allreduce(ctx, buf, n, strm):
-            try:
-                torch.cuda.ExternalStream(strm).synchronize()
-                t = torch.as_tensor(_DevArray(buf, n), device="cuda")
-                staged[rank] = t.cpu().numpy().copy()
-                meet.wait()
-                total = staged[0].copy()
-                for k in range(1, world):
-                    total += staged[k]
-                meet.wait()
-                t.copy_(torch.from_numpy(total).cuda())
-                torch.cuda.synchronize()
-                return 0
-            except Exception as e:      # noqa: BLE001
-                errors.append(repr(e))
-                meet.abort()
-                return 1
-        return allreduce
-
-    for r, b in enumerate(ranks):
-        b.problem.set_allreduce(make_allreduce(r))
-
-    def run(r):
-        try:
-            ranks[r].problem.covariance_compute()
-            results[r] = ranks[r].problem.covariance_dense()
-        except Exception as e:      # noqa: BLE001
-            errors.append(repr(e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=180)
-    assert not errors, errors
+    def per_rank(b):
+        b.problem.covariance_compute()
+        return b.problem.covariance_dense()
+    results = run_two_ranks(hip, scene, vals, per_rank)
     assert np.array_equal(results[0], results[1])
     assert rel_err(results[0], S1) <= 1e-9, rel_err(results[0], S1)
 

@@ -17,6 +17,7 @@ import pytest
 
 import observability_ref as R
 from calico_amd import _capi, synthetic as syn
+from helpers import _state, run_two_ranks, solve
 
 pytestmark = pytest.mark.gpu
 
@@ -36,13 +37,6 @@ TOL_DECOMP = 1e-11
 ALL_SCENES = dict(R.TABLE_SCENES)
 ALL_SCENES.update(R.MORE_SCENES)
 _cache = {}
-
-
-def solve(P, api, iters=50):
-    o = api.default_options()
-    o.minimizer_progress_to_stdout = 0
-    o.max_num_iterations = iters
-    return P.solve(o)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -186,13 +180,6 @@ def test_trajectory_deficiency(hip, oracle):
     assert "trajectory" not in e.value.message
 
 
-def _state(built, scene):
-    P = built.problem
-    vals = {b: P.get_param_block(b, n) for b, n in dict(P._sizes).items()}
-    res = [P.residuals(sid, s.n, 2 if s.kind == _capi.SENSOR_CAMERA else 3) for sid, s in zip(built.sensor_ids, scene.sensors)]
-    return vals, res
-
-
 def test_no_side_effects(hip):
     scene = R.small_scene(camera_model=1, imu=True)
     a, b = syn.build_problem(hip, scene), syn.build_problem(hip, scene)
@@ -320,63 +307,17 @@ def test_border_above_256_columns_is_unimplemented(hip):
 def test_multirank_two_handles_agree(hip):
     """Two ranks on one device, each a handle sharded to its time window with a host exchange (sum in rank order): both
     hold the same report bit for bit, equal to the single-rank one to rounding."""
-    import threading
-    import torch
-    from test_gpu_multirank import _DevArray
     scene = R.small_scene(camera_model=1, imu=True, imu_model=3, robust=True, seed=3)
     single = syn.build_problem(hip, scene)
     solve(single.problem, hip)
     vals = {b: single.problem.get_param_block(b, n) for b, n in dict(single.problem._sizes).items()}
     i1 = single.problem.observability_compute()
     l1 = single.problem.observability_spectrum()
-    world = 2
-    ranks = []
-    for r in range(world):
-        b = syn.build_problem(hip, scene)
-        for blk, v in vals.items():
-            b.problem.set_param_block(blk, v)
-        b.problem.set_shard(r, world)
-        ranks.append(b)
-    meet = threading.Barrier(world, timeout=120)
-    staged = [None] * world
-    results, errors = [None] * world, []
 
-    def make_allreduce(rank):
-        def allreduce(ctx, buf, n, strm):
-            try:
-                torch.cuda.ExternalStream(strm).synchronize()
-                t = torch.as_tensor(_DevArray(buf, n), device="cuda")
-                staged[rank] = t.cpu().numpy().copy()
-                meet.wait()
-                total = staged[0].copy()
-                for k in range(1, world):
-                    total += staged[k]
-                meet.wait()
-                t.copy_(torch.from_numpy(total).cuda())
-                torch.cuda.synchronize()
-                return 0
-            except Exception as e:      # noqa: BLE001
-                errors.append(repr(e))
-                meet.abort()
-                return 1
-        return allreduce
-
-    for r, b in enumerate(ranks):
-        b.problem.set_allreduce(make_allreduce(r))
-
-    def run(r):
-        try:
-            info = ranks[r].problem.observability_compute()
-            results[r] = (info, ranks[r].problem.observability_spectrum(), ranks[r].problem.observability_directions(),
-                          ranks[r].problem.observability_matrix())
-        except Exception as e:      # noqa: BLE001
-            errors.append(repr(e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=180)
-    assert not errors, errors
+    def per_rank(b):
+        info = b.problem.observability_compute()
+        return info, b.problem.observability_spectrum(), b.problem.observability_directions(), b.problem.observability_matrix()
+    results = run_two_ranks(hip, scene, vals, per_rank)
     assert results[0][0] == results[1][0]
     for x, y in zip(results[0][1:], results[1][1:]):
         assert np.array_equal(x, y)

@@ -7,15 +7,9 @@ import pytest
 
 import helpers
 from calico_amd import _capi, synthetic as syn
+from helpers import small_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def small_scene(camera_model=1, n_cameras=2, imu=True, imu_model=2, robust=False, noise=True, seed=7, **kw):
-    return syn.make_scene(n_cameras, camera_model, imu, imu_model, cam_rate=10.0, imu_rate=50.0, duration=3.0,
-                          segment_duration=3.0 / 23.9, pixel_noise=0.1 if noise else 0.0,
-                          gyro_noise=1e-3 if noise else 0.0, accel_noise=1e-2 if noise else 0.0, robust=robust,
-                          seed=seed, **kw)
 
 
 def both(scene, hip, oracle):

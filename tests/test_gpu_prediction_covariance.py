@@ -14,7 +14,7 @@ import pytest
 
 import prediction_ref as pr
 from calico_amd import _capi, synthetic as syn
-from test_gpu_covariance import full_size_scene, small_scene, solve
+from helpers import full_size_scene, run_two_ranks, small_scene, solve
 
 pytestmark = pytest.mark.gpu
 
@@ -280,61 +280,15 @@ def test_contracts(hip):
 def test_multirank_two_handles_agree(hip, oracle):
     """Two ranks on one device with a host exchange: both ranks' outputs are bit-identical and within the parity bound of
     the single rank's with 1e-9 in place of 1e-7."""
-    import threading
-    import torch
-    from test_gpu_multirank import _DevArray
     scene = small_scene(camera_model=1, imu=True, robust=True, seed=3)
     single, R, Js = prepared(hip, oracle, scene, 50)
     vals = {b: single.problem.get_param_block(b, n) for b, n in dict(single.problem._sizes).items()}
     one = {(s, a): single.problem.prediction_covariance(s, apply_loss=a) for s in single.sensor_ids for a in (True, False)}
-    world = 2
-    ranks = []
-    for r in range(world):
-        b = syn.build_problem(hip, scene)
-        for blk, v in vals.items():
-            b.problem.set_param_block(blk, v)
-        b.problem.set_shard(r, world)
-        ranks.append(b)
-    meet = threading.Barrier(world, timeout=120)
-    staged = [None] * world
-    results, errors = [None] * world, []
 
-    def make_allreduce(rank):
-        def allreduce(ctx, buf, n, strm):
-            try:
-                torch.cuda.ExternalStream(strm).synchronize()
-                x = torch.as_tensor(_DevArray(buf, n), device="cuda")
-                staged[rank] = x.cpu().numpy().copy()
-                meet.wait()
-                total = staged[0].copy()
-                for k in range(1, world):
-                    total += staged[k]
-                meet.wait()
-                x.copy_(torch.from_numpy(total).cuda())
-                torch.cuda.synchronize()
-                return 0
-            except Exception as e:      # noqa: BLE001
-                errors.append(repr(e))
-                meet.abort()
-                return 1
-        return allreduce
-
-    for r, b in enumerate(ranks):
-        b.problem.set_allreduce(make_allreduce(r))
-
-    def run(r):
-        try:
-            ranks[r].problem.covariance_compute(control_points=True)
-            results[r] = {(s, a): ranks[r].problem.prediction_covariance(s, apply_loss=a)
-                          for s in ranks[r].sensor_ids for a in (True, False)}
-        except Exception as e:      # noqa: BLE001
-            errors.append(repr(e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for x in th:
-        x.start()
-    for x in th:
-        x.join(timeout=180)
-    assert not errors, errors
+    def per_rank(b):
+        b.problem.covariance_compute(control_points=True)
+        return {(s, a): b.problem.prediction_covariance(s, apply_loss=a) for s in b.sensor_ids for a in (True, False)}
+    results = run_two_ranks(hip, scene, vals, per_rank)
     rows = dict(zip(single.sensor_ids, pr.sensor_rows(scene)))
     worst = 0.0
     for key, (cov, lev, valid) in results[0].items():

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from calico_amd import _capi, synthetic as syn
-from test_gpu_covariance import border_layout, full_size_scene, small_scene, solve
+from helpers import border_layout, full_size_scene, run_two_ranks, small_scene, solve
 
 pytestmark = pytest.mark.gpu
 
@@ -299,9 +299,6 @@ def test_determinism(hip):
 def test_multirank_two_handles_agree(hip):
     """Two ranks on one device with a host exchange (the pattern of test_gpu_covariance): the trajectory blocks of both
     ranks are bit-identical and within 1e-9 of the single rank's."""
-    import threading
-    import torch
-    from test_gpu_multirank import _DevArray
     scene = small_scene(camera_model=1, imu=True, robust=True, seed=3)
     single = syn.build_problem(hip, scene)
     solve(single.problem, hip)
@@ -310,53 +307,12 @@ def test_multirank_two_handles_agree(hip):
     G1, mask = gpu_blocks(single, scene)
     t = stamp_grid(scene)
     V1 = single.problem.covariance_trajectory(t)
-    world = 2
-    ranks = []
-    for r in range(world):
-        b = syn.build_problem(hip, scene)
-        for blk, v in vals.items():
-            b.problem.set_param_block(blk, v)
-        b.problem.set_shard(r, world)
-        ranks.append(b)
-    meet = threading.Barrier(world, timeout=120)
-    staged = [None] * world
-    results, errors = [None] * world, []
 
-    def make_allreduce(rank):
-        def allreduce(ctx, buf, n, strm):
-            try:
-                torch.cuda.ExternalStream(strm).synchronize()
-                x = torch.as_tensor(_DevArray(buf, n), device="cuda")
-                staged[rank] = x.cpu().numpy().copy()
-                meet.wait()
-                total = staged[0].copy()
-                for k in range(1, world):
-                    total += staged[k]
-                meet.wait()
-                x.copy_(torch.from_numpy(total).cuda())
-                torch.cuda.synchronize()
-                return 0
-            except Exception as e:      # noqa: BLE001
-                errors.append(repr(e))
-                meet.abort()
-                return 1
-        return allreduce
-
-    for r, b in enumerate(ranks):
-        b.problem.set_allreduce(make_allreduce(r))
-
-    def run(r):
-        try:
-            ranks[r].problem.covariance_compute(control_points=True)
-            results[r] = ranks[r].problem.covariance_trajectory(t)
-        except Exception as e:      # noqa: BLE001
-            errors.append(repr(e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for x in th:
-        x.start()
-    for x in th:
-        x.join(timeout=180)
-    assert not errors, errors
+    def per_rank(b):
+        b.problem.covariance_compute(control_points=True)
+        return b, b.problem.covariance_trajectory(t)
+    both = run_two_ranks(hip, scene, vals, per_rank)
+    ranks, results = [x[0] for x in both], [x[1] for x in both]
     Gs = [gpu_blocks(b, scene)[0] for b in ranks]
     assert np.array_equal(Gs[0], Gs[1]) and np.array_equal(results[0], results[1])
     err = masked_err(Gs[0], G1, mask)

@@ -13,25 +13,12 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
+import helpers  # noqa: E402
 
 
 @pytest.mark.skipif(shutil.which(entry.HIPCC) is None and not os.path.exists(entry.HIPCC), reason="no hipcc")
 def test_evaluation_kernel_scratch_budget():
-    src = os.path.join(entry.CSRC, "eval_kernels.hip")
-    flags = [f for f in entry.HIP_FLAGS if f != "-fPIC"] + entry.HIP_FILE_FLAGS.get("eval_kernels.hip", [])
-    r = subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
+    res = helpers.kernel_resources("eval_kernels.hip")
     cells = [v for k, v in res.items() if "eval_cells_kernel" in k]
     assert len(cells) == 1, sorted(res)
     c = cells[0]

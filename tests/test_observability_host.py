@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as entry  # noqa: E402
+import helpers  # noqa: E402
 import observability_ref as R  # noqa: E402
 from calico_amd import _capi, synthetic as syn  # noqa: E402
 
@@ -46,21 +46,7 @@ def test_observability_entries_declared_and_exported():
 
 @pytest.mark.skipif(shutil.which(entry.HIPCC) is None and not os.path.exists(entry.HIPCC), reason="no hipcc")
 def test_observability_kernel_scratch_free():
-    src = os.path.join(entry.CSRC, "obs_kernels.hip")
-    flags = [f for f in entry.HIP_FLAGS if f != "-fPIC"] + entry.HIP_FILE_FLAGS.get("obs_kernels.hip", [])
-    r = subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
+    res = helpers.kernel_resources("obs_kernels.hip")
     ks = {k: v for k, v in res.items() if "observability_kernel" in k}
     assert len(ks) == 2, sorted(res)      # the in-LDS and the global-workspace class
     for k, v in ks.items():
@@ -71,16 +57,16 @@ def test_observability_kernel_scratch_free():
 
 
 def test_no_atomics_in_the_kernel_source():
-    src = open(os.path.join(entry.CSRC, "obs_kernels.hip")).read()
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())
-    assert not re.search(r"\batomic\w*\s*\(", code)
+    for name in ("obs_kernels.hip", "reduced_system.hpp"):      # the kernel and the prologue it shares with covariance_kernel
+        src = open(os.path.join(entry.CSRC, name)).read()
+        code = "\n".join(line.split("//")[0] for line in src.splitlines())
+        assert not re.search(r"\batomic\w*\s*\(", code), name
 
 
 @pytest.mark.parametrize("name", list(R.TABLE_SCENES))
 def test_reference_recipe_reproduces_the_table(name):
     """The scenes of the GPU tests satisfy their own gap condition, from the oracle alone (solved scenes: the oracle's own
     solve; the GPU tests use the device's values, which agree to the solver's tolerance)."""
-    import helpers
     oracle = helpers.oracle_api()
     mk, iters, n_weak = R.TABLE_SCENES[name]
     scene = mk()
@@ -120,7 +106,6 @@ def test_reference_recipe_reproduces_the_table(name):
 
 
 def test_reference_finds_the_solved_camera_scene_trajectory_deficient():
-    import helpers
     oracle = helpers.oracle_api()
     scene = R.small_scene(camera_model=1, imu=False)
     ref = syn.build_problem(oracle, scene)

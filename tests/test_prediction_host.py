@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -14,7 +13,7 @@ import pytest
 import helpers
 import prediction_ref as pr
 from calico_amd import _capi, synthetic as syn
-from observability_ref import small_scene
+from helpers import small_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -84,21 +83,7 @@ def test_default_options_and_host_side_argument_checks():
 def test_prediction_kernel_scratch_budget():
     """ScratchSize / VGPRs Spill of prediction_items_kernel stay within what eval_items_kernel<true, 6> has, both read from
     one compile."""
-    src = os.path.join(entry.CSRC, "eval_kernels.hip")
-    flags = [f for f in entry.HIP_FLAGS if f != "-fPIC"] + entry.HIP_FILE_FLAGS.get("eval_kernels.hip", [])
-    r = subprocess.run([entry.HIPCC] + flags + ["--cuda-device-only", "-c", src, "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[a-zA-Z/]+\])?: (\d+)", line)
-        if m and name:
-            res[name][m.group(1).strip()] = int(m.group(2))
+    res = helpers.kernel_resources("eval_kernels.hip")
     base = [v for k, v in res.items() if "eval_items_kernelILb1ELi6E" in k]
     pred = {k: v for k, v in res.items() if "prediction_items_kernel" in k}
     assert len(base) == 1 and len(pred) == 2, sorted(res)
