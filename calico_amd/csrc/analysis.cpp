@@ -1,7 +1,8 @@
 // analysis.cpp — what is read from a solved problem: the covariance of the calibration estimates and of the trajectory, the
 // prediction covariance with leverage, and the observability report (this part of the C ABI of include/calico_hip.h).
-// Building, planning and solving a problem is calico_hip.cpp; the kernels are cov_kernels.hip, obs_kernels.hip and
-// prediction_items_kernel (eval_kernels.hip). The covariance and the observability pass open the same way (ReducedPass).
+// Describing a problem is calico_hip.cpp, planning it plan.cpp, solving it solve.cpp; the kernels are cov_kernels.hip,
+// obs_kernels.hip and prediction_items_kernel (eval_kernels.hip). The covariance and the observability pass open the same way
+// (ReducedPass).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,9 +1,10 @@
 // problem_host.hpp — what the host translation units of libcalico_hip.so share: the handle (calico_problem) with its plan,
-// device structure and workspace, the device-memory arena, and the few functions of calico_hip.cpp that analysis.cpp calls.
+// device structure and workspace, the device-memory arena, and the functions calico_hip.cpp, plan.cpp, solve.cpp and
+// analysis.cpp call of one another (declared once, at the end).
 // Internal: nothing declared here is part of the C ABI (include/calico_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>     // types only: the library itself is loaded on first use (RcclApi, calico_hip.cpp)
+#include <rccl/rccl.h>     // types only: the library itself is loaded on first use (rccl(), calico_hip.cpp)
 
 #include <algorithm>
 #include <cstdint>
@@ -348,7 +349,7 @@ struct Workspace {
   ~Workspace() { free_pinned(); }
 };
 
-struct PlanEntry;      // plan cache entry (calico_hip.cpp)
+struct PlanEntry;      // plan cache entry (plan.cpp)
 
 struct calico_problem : PlanHost, PlanDev, Workspace {
   int device = 0;
@@ -436,18 +437,37 @@ struct calico_problem : PlanHost, PlanDev, Workspace {
   } while (0)
 
 
-// ---- what analysis.cpp calls of calico_hip.cpp ------------------------------------------------------------------------------
+// ---- what the host files call of one another --------------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
 namespace cal {
+// calico_hip.cpp
+struct RcclApi {
+  void* lib = nullptr;
+  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+  ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
+  ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+  const char* (*GetErrorString)(ncclResult_t) = nullptr;
+  std::string error;
+  bool ok() const { return lib != nullptr; }
+};
+RcclApi& rccl();
 int spline_index(const calico_problem* p, double t);
+// a sharded handle (calico_problem_set_shard, world > 1) evaluates only with an exchange: CALICO_OK, or the error set
+int require_exchange(calico_problem* p);
+// plan.cpp
+int finalize(calico_problem* p);
+void return_workspace(calico_problem* p);
+void release_measurement_staging(calico_problem* p);
+void plan_cache_stats(int64_t* hits, int64_t* misses, int64_t* entries);
+void plan_cache_clear();
+// solve.cpp
 SolveArgs make_solve_args(calico_problem* p);
 EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res);
-int finalize(calico_problem* p);
 int upload_x(calico_problem* p, bool seed = true);
 int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, const double* x_at = nullptr, bool spec = false,
                           const ControlTail* tail = nullptr, bool end_hint = false);
 void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only = false);
-// a sharded handle (calico_problem_set_shard, world > 1) evaluates only with an exchange: CALICO_OK, or the error set
-int require_exchange(calico_problem* p);
 }  // namespace cal
 #pragma GCC visibility pop
