@@ -144,7 +144,8 @@ ABI_SYMBOLS = [
     "observability_get_directions", "observability_get_block", "observability_get_matrix",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
-TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info"]
+TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
+                "debug_lds_attribute_calls"]
 
 
 class CApi:
@@ -224,6 +225,8 @@ class CApi:
                 g("debug_roll_table", C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_uint32)])
             if hasattr(self.lib, self.prefix + "debug_last_step"):
                 g("debug_last_step", C.c_int32, [P, C.c_int32, D, D, D])
+            if hasattr(self.lib, self.prefix + "debug_lds_attribute_calls"):
+                g("debug_lds_attribute_calls", C.c_int64, [])
 
     def _get(self, name, restype, argtypes):
         fn = getattr(self.lib, self.prefix + name)

@@ -164,7 +164,7 @@ int32_t calico_covariance_compute(calico_problem* p, const calico_covariance_opt
   }
   HIP_TRY(p, cv.out.alloc(size_t(mc) * mc)); HIP_TRY(p, cv.info.alloc(4));
   if (!covariance_in_lds(m)) HIP_TRY(p, cv.work.alloc(size_t(m) * covariance_ld(m)));
-  HIP_TRY(p, configure_covariance_kernel());
+  HIP_TRY(p, configure_covariance_kernel(p->device));
   hipStream_t s = p->stream;
   rc = begin_reduced_pass(p, rp, want_cp);
   if (rc != CALICO_OK) return rc;
@@ -401,10 +401,10 @@ int32_t calico_prediction_covariance(calico_problem* p, int32_t sid, const calic
   const int64_t n = hs.n();
   if (n == 0) return CALICO_OK;
   const size_t lds_bytes = pred_lds_doubles(p->pred_cols, p->pred_row_pad) * sizeof(double);
-  if (lds_bytes > kMaxLds) {
+  if (lds_bytes > kLdsBudget) {
     char msg[200];
     std::snprintf(msg, sizeof(msg), "prediction covariance: a residual block of %d Jacobian columns needs %zu bytes of LDS staging (at most %zu)",
-                  p->pred_cols, lds_bytes, kMaxLds);
+                  p->pred_cols, lds_bytes, kLdsBudget);
     return p->set_error(CALICO_UNIMPLEMENTED, msg);
   }
   HIP_TRY(p, hipSetDevice(p->device));
@@ -427,6 +427,7 @@ int32_t calico_prediction_covariance(calico_problem* p, int32_t sid, const calic
   pa.sigma = cv.out.p; pa.sae = cv.cp_sae.p; pa.band = cv.cp_band.p;
   pa.cov = d_cov.p; pa.leverage = d_lev.p; pa.valid = d_val.p;
   (void)hipGetLastError();
+  HIP_TRY(p, configure_prediction_kernels(p->device));
   HIP_TRY(p, launch_prediction(pa, lds_bytes, s));
   std::vector<double> hc(size_t(n) * dd), hl(static_cast<size_t>(n));
   std::vector<uint8_t> hv(static_cast<size_t>(n));
@@ -480,7 +481,7 @@ int32_t calico_observability_compute(calico_problem* p, const calico_observabili
   HIP_TRY(p, ob.lam.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.vec.alloc(n2 + 1)); HIP_TRY(p, ob.mat.alloc(n2 + 1));
   HIP_TRY(p, ob.dvec.alloc(size_t(mc) + 1)); HIP_TRY(p, ob.info.alloc(8));
   if (!in_lds) HIP_TRY(p, ob.work.alloc(observability_work_doubles(m, mc)));
-  HIP_TRY(p, configure_observability_kernel());
+  HIP_TRY(p, configure_observability_kernel(p->device));
   hipStream_t s = p->stream;
   rc = begin_reduced_pass(p, rp, have_band);
   if (rc != CALICO_OK) return rc;

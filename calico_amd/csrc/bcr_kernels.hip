@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <mutex>
 #include <type_traits>
 
@@ -385,17 +386,12 @@ void roll_table_row(int k, int lane, unsigned* out) {
   std::call_once(once, [] { fill_roll_table(tab); });
   for (int i = 0; i < kRollTabWords; ++i) out[i] = tab[k - 1][lane][i];
 }
-static hipError_t upload_roll_table() {      // (called under configure_kernels' lock)
+// (to the current device's copy of the symbol; once per device -- the copy waits for the device --: ensure_roll_table)
+hipError_t upload_roll_table() {
   static unsigned host_tab[6][64][kRollTabWords];
   static std::once_flag once;
   std::call_once(once, [] { fill_roll_table(host_tab); });
-  static bool done[64] = {};       // once per device: the symbol lives on each of them, and the copy waits for the device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 64 && done[dev]) return hipSuccess;
-  const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_roll_tab), host_tab, sizeof(host_tab));
-  if (e == hipSuccess && dev >= 0 && dev < 64) done[dev] = true;
-  return e;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_roll_tab), host_tab, sizeof(host_tab));
 }
 
 // ROLL (round 6; level 0 with the block elimination): the chain without a workgroup barrier between its blocks -- see the
@@ -3007,10 +3003,7 @@ __global__ __launch_bounds__(kDenseThreads) void dense_back_kernel(SolveArgs a, 
   if (CAL_DEV_TIMING(a.debug == 4 && threadIdx.x == 0)) printf("dense_back: workgroup %d lived %lld clocks (terminated %d)\n", int(blockIdx.x), (long long)(__builtin_readcyclecounter() - t_db), a.st->terminated);
 }
 size_t dense_block_solve_lds_bytes() { return size_t(128 * DNL + 128 + kDenseChan + 128 * 3 + 32 + 128 + kDenseThreads) * sizeof(double); }
-hipError_t configure_dense_block_solve() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_block_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             int(dense_block_solve_lds_bytes()));
-}
+hipError_t configure_dense_block_solve(int device) { return raise_lds_limit(device, dense_block_solve_kernel, dense_block_solve_lds_bytes()); }
 void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0, int outer_back) {
   hipLaunchKernelGGL(dense_block_solve_kernel, dim3(1), dim3(kDenseThreads), dense_block_solve_lds_bytes(), s, a, ks, t0, outer_back, dense_elim_mode());
 }
@@ -3157,10 +3150,7 @@ __global__ __launch_bounds__(kStepThreads) void reduced_block_step_mfma_kernel(S
   reduced_block_step_body(a, j, nsl, int(blockIdx.x), lds);
 }
 size_t reduced_block_step_lds_bytes() { return size_t(64 * DLD + 4 * BP * PTL + 80 + 128 + kStepThreads) * sizeof(double); }
-hipError_t configure_reduced_block_step() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_block_step_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             int(reduced_block_step_lds_bytes()));
-}
+hipError_t configure_reduced_block_step(int device) { return raise_lds_limit(device, reduced_block_step_mfma_kernel, reduced_block_step_lds_bytes()); }
 void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hipStream_t s) {
   hipLaunchKernelGGL(reduced_block_step_mfma_kernel, dim3(n_wg), dim3(kStepThreads), reduced_block_step_lds_bytes(), s, a, j, nsl);
 }
@@ -3180,37 +3170,46 @@ static bool dense_back_pre(const SolveArgs& a) {
   if (a.mc + BP + 1 > 128) return false;
   return env_flag("CALICO_BACK_PRE", a.m + 1 > 96);
 }
+// chains share instantiations by length: QM is the next of 1, 2, 4, 8
+static int chain_variant(int q_max) { return q_max <= 1 ? 1 : (q_max <= 2 ? 2 : (q_max <= 4 ? 4 : 8)); }
+// (the solve's own LDS exceeds back_node_pre's at every QM of this launch, so the third term never decides the maximum)
 static size_t dense_back_lds(int q_max, int m1p) {
-  const int qm = q_max <= 1 ? 1 : (q_max <= 2 ? 2 : 4);
+  const int qm = std::min(chain_variant(q_max), 4);
   return std::max(std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(q_max, m1p)), bcr_back_pre_lds_doubles(qm) * sizeof(double));
 }
-size_t dense_back_lds_bytes(int q_max, int m1p) { return dense_back_lds(q_max, m1p); }
-hipError_t configure_dense_back_bytes(size_t lds) {
-  for (const void* f : {reinterpret_cast<const void*>(&dense_back_kernel<1, 1, false>), reinterpret_cast<const void*>(&dense_back_kernel<2, 1, false>),
-                        reinterpret_cast<const void*>(&dense_back_kernel<4, 1, false>), reinterpret_cast<const void*>(&dense_back_kernel<1, 2, false>),
-                        reinterpret_cast<const void*>(&dense_back_kernel<2, 2, false>), reinterpret_cast<const void*>(&dense_back_kernel<4, 2, false>),
-                        reinterpret_cast<const void*>(&dense_back_kernel<1, 1, true>), reinterpret_cast<const void*>(&dense_back_kernel<2, 1, true>),
-                        reinterpret_cast<const void*>(&dense_back_kernel<4, 1, true>), reinterpret_cast<const void*>(&dense_back_kernel<1, 2, true>),
-                        reinterpret_cast<const void*>(&dense_back_kernel<2, 2, true>), reinterpret_cast<const void*>(&dense_back_kernel<4, 2, true>)}) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+// Does the fused launch fit a CU at chains of up to q_max and a border of m1p columns? THE rule: the plan's attribute
+// (configure_dense_back) and the solve's route (linear_route) both ask here.
+bool dense_back_fits(int q_max, int m1p) { return dense_back_lds(q_max, m1p) + kLdsSlack <= kLdsBudget; }
+
+// dense_back_kernel<QM, MODE, PRE>: MODE 1: the top of the tree, 2: with top separators beside the nodes
+using DenseBackFn = decltype(&dense_back_kernel<1, 1, false>);
+struct DenseBackVariant { int qm, mode; bool pre; DenseBackFn fn; };
+template <int QM, int MODE, bool PRE>
+constexpr DenseBackVariant dense_back_variant = {QM, MODE, PRE, dense_back_kernel<QM, MODE, PRE>};
+constexpr DenseBackVariant kDenseBackVariants[] = {
+    dense_back_variant<1, 1, false>, dense_back_variant<2, 1, false>, dense_back_variant<4, 1, false>,
+    dense_back_variant<1, 2, false>, dense_back_variant<2, 2, false>, dense_back_variant<4, 2, false>,
+    dense_back_variant<1, 1, true>, dense_back_variant<2, 1, true>, dense_back_variant<4, 1, true>,
+    dense_back_variant<1, 2, true>, dense_back_variant<2, 2, true>, dense_back_variant<4, 2, true>};
+static const DenseBackVariant* select_dense_back(int q_max, bool top_seps, bool pre) {
+  for (const DenseBackVariant& v : kDenseBackVariants)
+    if (v.qm == chain_variant(q_max) && v.mode == (top_seps ? 2 : 1) && v.pre == pre) return &v;
+  return nullptr;
+}
+hipError_t configure_dense_back(int device, int q_max, int m1p) {
+  for (const DenseBackVariant& v : kDenseBackVariants) {
+    const hipError_t e = raise_lds_limit(device, v.fn, dense_back_lds(q_max, m1p));
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
                        const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s) {
-  const size_t lds = dense_back_lds(q_max, b.m1p);
+  const DenseBackVariant* v = select_dense_back(q_max, ts.n > 0, dense_back_pre(a));
+  assert(v && "dense_back_fusable keeps chains longer than four out of the fused launch");
   const dim3 grid(1 + n_nodes + 1), block(kDenseThreads);       // dense solve, the nodes, the calibration / root update
-  const int elim = dense_elim_mode();
-#define LAUNCH_DB(QM, SD, PR) hipLaunchKernelGGL(HIP_KERNEL_NAME(dense_back_kernel<QM, SD, PR>), grid, block, lds, s, a, b, ks, node0, n_nodes, q_max, x, x_cand, blocks, n_blocks, ts, word, seq, elim)
-  if (dense_back_pre(a)) {
-    if (ts.n > 0) { if (q_max <= 1) LAUNCH_DB(1, 2, true); else if (q_max <= 2) LAUNCH_DB(2, 2, true); else LAUNCH_DB(4, 2, true); }
-    else { if (q_max <= 1) LAUNCH_DB(1, 1, true); else if (q_max <= 2) LAUNCH_DB(2, 1, true); else LAUNCH_DB(4, 1, true); }
-  } else {
-    if (ts.n > 0) { if (q_max <= 1) LAUNCH_DB(1, 2, false); else if (q_max <= 2) LAUNCH_DB(2, 2, false); else LAUNCH_DB(4, 2, false); }
-    else { if (q_max <= 1) LAUNCH_DB(1, 1, false); else if (q_max <= 2) LAUNCH_DB(2, 1, false); else LAUNCH_DB(4, 1, false); }
-  }
-#undef LAUNCH_DB
+  hipLaunchKernelGGL(v->fn, grid, block, dense_back_lds(q_max, b.m1p), s, a, b, ks, node0, n_nodes, q_max, x, x_cand, blocks, n_blocks, ts,
+                     word, seq, dense_elim_mode());
 }
 
 // ---- launch helpers ---------------------------------------------------------
@@ -3230,25 +3229,32 @@ size_t bcr_level_lds_bytes() { return size_t(2 * 64 * DLD + 4 * BP * XLD + 80 + 
 size_t bcr_back_lds_bytes(int q_max, int m1p) {
   return (size_t(2) * q_max * BP * DLD + kBcrMaxChain * BP + 3 * BP + m1p + size_t(q_max) * BP + 4 * BP) * sizeof(double);
 }
-hipError_t configure_bcr_kernels(int q_max, int m1p) {
-  hipError_t e = upload_roll_table();      // (per device: a __device__ symbol lives on each of them)
-  if (e != hipSuccess) return e;
-  for (const void* f : {reinterpret_cast<const void*>(&bcr_level_kernel<true, true>), reinterpret_cast<const void*>(&bcr_level_kernel<false, true>),
-                        reinterpret_cast<const void*>(&bcr_level_kernel<true, false>), reinterpret_cast<const void*>(&bcr_level_kernel<false, false>),
-                        reinterpret_cast<const void*>(&bcr_level_kernel<true, true, true>)}) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(bcr_level_lds_bytes()));
-    if (e != hipSuccess) return e;
-  }
-  for (const void* f : {reinterpret_cast<const void*>(&bcr_back_kernel<1, 0>), reinterpret_cast<const void*>(&bcr_back_kernel<2, 0>),
-                        reinterpret_cast<const void*>(&bcr_back_kernel<4, 0>), reinterpret_cast<const void*>(&bcr_back_kernel<8, 0>),
-                        reinterpret_cast<const void*>(&bcr_back_kernel<1, 1>), reinterpret_cast<const void*>(&bcr_back_kernel<2, 1>),
-                        reinterpret_cast<const void*>(&bcr_back_kernel<4, 1>), reinterpret_cast<const void*>(&bcr_back_kernel<8, 1>),
-                        reinterpret_cast<const void*>(&bcr_back_kernel<1, 2>), reinterpret_cast<const void*>(&bcr_back_kernel<2, 2>),
-                        reinterpret_cast<const void*>(&bcr_back_kernel<4, 2>)}) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(bcr_back_lds_bytes(q_max, m1p)));
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// bcr_level_kernel<FROM_R, ELIM, ROLL>: five instantiations, picked by the two ternaries of launch_bcr_level (as a table with
+// its selection function they were four times these lines)
+constexpr decltype(&bcr_level_kernel<true, true>) kLevelKernels[] = {bcr_level_kernel<true, true>, bcr_level_kernel<false, true>, bcr_level_kernel<true, false>,
+                                                                    bcr_level_kernel<false, false>, bcr_level_kernel<true, true, true>};
+// bcr_back_kernel<QM, MODE>: MODE 0: a level below the top, 1: the top of the tree, 2: with top separators beside the nodes
+// (no <8, 2>: the registers do not hold a chain of eight and the separators -- linear_route folds the top separators into
+// the level below only where its chains are at most four long)
+using BackFn = decltype(&bcr_back_kernel<1, 0>);
+struct BackVariant { int qm, mode; BackFn fn; };
+template <int QM, int MODE>
+constexpr BackVariant back_variant = {QM, MODE, bcr_back_kernel<QM, MODE>};
+constexpr BackVariant kBackVariants[] = {back_variant<1, 0>, back_variant<2, 0>, back_variant<4, 0>, back_variant<8, 0>,
+                                         back_variant<1, 1>, back_variant<2, 1>, back_variant<4, 1>, back_variant<8, 1>,
+                                         back_variant<1, 2>, back_variant<2, 2>, back_variant<4, 2>};
+static const BackVariant* select_back(int q_max, bool top, bool top_seps) {
+  for (const BackVariant& v : kBackVariants)
+    if (v.qm == chain_variant(q_max) && v.mode == (top_seps ? 2 : (top ? 1 : 0))) return &v;
+  return nullptr;
+}
+hipError_t configure_bcr_kernels(int device, int q_max, int m1p) {
+  hipError_t e = ensure_roll_table(device);      // (per device: a __device__ symbol lives on each of them)
+  for (auto fn : kLevelKernels)
+    if (e == hipSuccess) e = raise_lds_limit(device, fn, bcr_level_lds_bytes());
+  for (const BackVariant& v : kBackVariants)
+    if (e == hipSuccess) e = raise_lds_limit(device, v.fn, bcr_back_lds_bytes(q_max, m1p));
+  return e;
 }
 
 // `schur_ks` > 0 (the LAST level of a tree of at least two): the Schur complement's tiles and the root's rows ride behind
@@ -3258,16 +3264,13 @@ void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nod
                       hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl) {
   const int nfs = (a.mc + 1 + kBcrFS - 1) / kBcrFS;
   int n_apply = n_keep > 0 ? std::min(64, std::max(1, n_keep * 4)) : 0;
-  const int main_span = 8 * ((n_nodes + 7) / 8) * (1 + nfs);      // (node, role) workgroups laid out by XCD: see the kernel
+  const int main_span = bcr_level_main_span(n_nodes, 1 + nfs);
   // One workgroup of this kernel fills a CU (its LDS), and the part has 256 of them: where the chains leave room, the separators'
   // workgroups (and level 0's bookkeeping workgroup, the last of the grid) are kept inside that room -- a workgroup that is only
   // dispatched when another has ended starts ~15k clocks late, and the bookkeeping one then ends the launch (440 control points:
   // 224 + 64 + 1 workgroups, level 0 21.5 us with the chains done at 13 us).
-  {
-    constexpr int kCUs = 256;
-    const int room = kCUs - main_span - (level == 0 && with_post_eval ? 1 : 0);
-    if (room >= 8 && n_apply > room) n_apply = room;
-  }
+  const int room = kNumCUs - main_span - (level == 0 && with_post_eval ? 1 : 0);
+  if (room >= 8 && n_apply > room) n_apply = room;
   const bool elim = block_elim_enabled();
   if (level == 0) {
     const bool roll = elim && a.k >= 1 && a.k <= 6 && level_roll_enabled();
@@ -3295,19 +3298,10 @@ void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_node
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s) {
   const int n_mv = border_rows ? (b.N * BP + kBackThreads / 64 - 1) / (kBackThreads / 64) : 0;   // (nobody below reads b.zb: no sweep)
   const dim3 grid(n_nodes + (extras ? 1 + n_mv : 0)), block(kBackThreads);
-  const size_t lds = bcr_back_lds_bytes(q_max, b.m1p);
-#define LAUNCH_BACK(QM) hipLaunchKernelGGL(HIP_KERNEL_NAME(bcr_back_kernel<QM, SD>), grid, block, lds, s, a, b, node0, n_nodes, top ? 1 : 0, extras ? 1 : 0, q_max, x, x_cand, blocks, n_blocks, ts)
-  if (ts.n > 0) {      // (the caller keeps chains longer than four out of this mode: the registers do not hold both)
-    constexpr int SD = 2;
-    if (q_max <= 1) LAUNCH_BACK(1); else if (q_max <= 2) LAUNCH_BACK(2); else LAUNCH_BACK(4);
-  } else if (top) {
-    constexpr int SD = 1;
-    if (q_max <= 1) LAUNCH_BACK(1); else if (q_max <= 2) LAUNCH_BACK(2); else if (q_max <= 4) LAUNCH_BACK(4); else LAUNCH_BACK(8);
-  } else {
-    constexpr int SD = 0;
-    if (q_max <= 1) LAUNCH_BACK(1); else if (q_max <= 2) LAUNCH_BACK(2); else if (q_max <= 4) LAUNCH_BACK(4); else LAUNCH_BACK(8);
-  }
-#undef LAUNCH_BACK
+  const BackVariant* v = select_back(q_max, top, ts.n > 0);
+  assert(v && "top separators ride only below chains of at most four (linear_route)");
+  hipLaunchKernelGGL(v->fn, grid, block, bcr_back_lds_bytes(q_max, b.m1p), s, a, b, node0, n_nodes, top ? 1 : 0, extras ? 1 : 0, q_max, x, x_cand,
+                     blocks, n_blocks, ts);
 }
 
 }  // namespace cal

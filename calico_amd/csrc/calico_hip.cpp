@@ -392,6 +392,8 @@ int32_t calico_debug_roll_table(int32_t spline_order, int32_t lane, uint32_t* ou
   return CALICO_OK;
 }
 
+int64_t calico_debug_lds_attribute_calls(void) { return cal::lds_attribute_calls(); }
+
 int32_t calico_get_iterations(calico_problem* p, calico_iteration* out, int32_t max_rows, int32_t* n_out) {
   if (!p || !out || !n_out) return CALICO_INVALID_ARGUMENT;
   const int n = std::min<int>(max_rows, int(p->iterations.size()));

@@ -56,6 +56,10 @@ int32_t calico_debug_roll_table(int32_t spline_order, int32_t lane, uint32_t* ou
  * CALICO_FAILED_PRECONDITION without a successful compute. */
 int32_t calico_debug_observability_info(calico_problem* problem, double* out, int32_t n);
 
+/* hipFuncSetAttribute calls the library's registry of dynamic-LDS limits has made in this process (raise_lds_limit, plan.cpp):
+ * grows only when a handle or an analysis needs more than its device already allows some kernel. */
+int64_t calico_debug_lds_attribute_calls(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,13 +34,12 @@ namespace cal {
 namespace {
 constexpr int kCovThreads = 1024;
 constexpr int kCovMaxDim = 1024;        // rows of the reduced system the kernel takes (static LDS below: 28 KB)
-constexpr size_t kCovLdsBudget = 160 * 1024;
 constexpr size_t kCovStaticLds = kCovMaxDim * (sizeof(int) + 3 * sizeof(double)) + 64;
 }  // namespace
 
 int covariance_max_dim() { return kCovMaxDim; }
 int covariance_ld(int n) { return n | 1; }       // odd row stride: the column walks of LDS hit distinct banks
-bool covariance_in_lds(int n) { return size_t(n) * covariance_ld(n) * sizeof(double) + kCovStaticLds + 1024 <= kCovLdsBudget; }
+bool covariance_in_lds(int n) { return size_t(n) * covariance_ld(n) * sizeof(double) + kCovStaticLds + kLdsSlack <= kLdsBudget; }
 
 // info[0]: minimum relative pivot, info[1]: flags (ReducedInfoFlag, problem_dev.hpp), info[2]: dropped
 // (structurally unobserved) calibration columns, info[3]: rows factored
@@ -153,10 +152,8 @@ void launch_covariance(const double* Spart, int ks, int m, int mc, const double*
     hipLaunchKernelGGL(covariance_kernel<false>, dim3(1), dim3(kCovThreads), 0, s, Spart, ks, m, mc, Cdiag, st, work, out, info);
 }
 
-hipError_t configure_covariance_kernel() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(covariance_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             int(kCovLdsBudget - kCovStaticLds - 1024));
-}
+// (the largest size covariance_in_lds admits)
+hipError_t configure_covariance_kernel(int device) { return raise_lds_limit(device, covariance_kernel<true>, kLdsBudget - kCovStaticLds - kLdsSlack); }
 
 // ---------------------------------------------------------------------------
 // Control-point blocks (calico_covariance_options.control_points). With H = JᵀJ = [[A, E], [Eᵀ, C]], A the block band of the

@@ -17,8 +17,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 
 #include "device_math.hpp"
 #include "kernels.hpp"
@@ -1754,43 +1752,28 @@ void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream) {
   }
 }
 
-// One wave per work item of pa.e.items; `lds_bytes`: pred_lds_doubles of the problem's widest layout. The kernel's dynamic-LDS
-// limit is raised to the device's on a device's first call (it runs on a user's request: no handle's limit is ever lowered).
+// One wave per work item of pa.e.items; `lds_bytes`: pred_lds_doubles of the problem's widest layout, at most the budget (the
+// caller checks). The kernels' limit is raised to the whole budget on a device's first request (it runs on a user's request,
+// outside the LM loop: configure_prediction_kernels in front of the launch).
+hipError_t configure_prediction_kernels(int device) {
+  const hipError_t e = raise_lds_limit(device, prediction_items_kernel<6>, kLdsBudget);
+  return e != hipSuccess ? e : raise_lds_limit(device, prediction_items_kernel<0>, kLdsBudget);
+}
 hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream) {
   if (pa.e.n_items == 0) return hipSuccess;
-  {
-    static std::mutex mu;
-    static std::set<int> done;      // devices whose limit is raised
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!done.count(dev)) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prediction_items_kernel<6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&prediction_items_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      done.insert(dev);
-    }
-  }
   if (pa.e.order == 6) hipLaunchKernelGGL((prediction_items_kernel<6>), dim3(pa.e.n_items), dim3(64), lds_bytes, stream, pa);
   else hipLaunchKernelGGL((prediction_items_kernel<0>), dim3(pa.e.n_items), dim3(64), lds_bytes, stream, pa);
   return hipGetLastError();
 }
 
-hipError_t configure_eval_kernels(size_t max_lds_bytes) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&expand_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_cells_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(kCellsMaxLds));
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_jacobian_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          int(std::max<size_t>(std::max(max_lds_bytes, frame_lds_bytes()), 80 * 1024)));
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_items_kernel<true, 6>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, int(max_lds_bytes));
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&eval_items_kernel<true, 0>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, int(max_lds_bytes));
+// (the forms of eval_items_kernel without the Jacobian stage nothing in dynamic LDS)
+hipError_t configure_eval_kernels(int device, size_t max_lds_bytes) {
+  hipError_t e = raise_lds_limit(device, expand_cells_kernel, 64 * 1024);
+  if (e == hipSuccess) e = raise_lds_limit(device, eval_cells_kernel, kCellsMaxLds);
+  if (e == hipSuccess) e = raise_lds_limit(device, eval_jacobian_kernel, std::max<size_t>(std::max(max_lds_bytes, frame_lds_bytes()), 80 * 1024));
+  if (e == hipSuccess) e = raise_lds_limit(device, eval_items_kernel<true, 6>, max_lds_bytes);
+  if (e == hipSuccess) e = raise_lds_limit(device, eval_items_kernel<true, 0>, max_lds_bytes);
+  return e;
 }
 
 }  // namespace cal

@@ -11,6 +11,21 @@
 
 namespace cal {
 
+// ---- launch contract ---------------------------------------------------------
+// A kernel family whose instantiation is picked from sizes (bcr_back_kernel, dense_back_kernel, band_backsolve_kernel) keeps
+// ONE variant table next to its kernels ({template parameters, function}): its configure_* walks the table, its launch_* picks
+// the entry through the family's selection function, so a variant that is launched is one that is configured, and a combination
+// without an entry is an assert. The dynamic-LDS limits live in one registry (plan.cpp): `device` allows `fn` at least `bytes` afterwards.
+// Limits are only ever raised (handles of different shapes share a device), hipFuncSetAttribute is called only when `bytes`
+// exceeds what the registry has set for `fn` there; `device` is the calling thread's current device.
+hipError_t raise_lds_limit(int device, const void* fn, size_t bytes);
+template <class... A>
+hipError_t raise_lds_limit(int device, void (*kernel)(A...), size_t bytes) {
+  return raise_lds_limit(device, reinterpret_cast<const void*>(kernel), bytes);
+}
+hipError_t ensure_roll_table(int device);     // upload_roll_table() once per device (the same per-device record)
+long long lds_attribute_calls();              // hipFuncSetAttribute calls of the registry in this process (test hook)
+
 // ---- kernels (eval_kernels.hip / solve_kernels.hip) -------------------------
 void launch_eval(const EvalArgs& a, bool jac, hipStream_t stream);
 void launch_eval_jacobian(const EvalArgs& a, hipStream_t stream);
@@ -22,7 +37,8 @@ void launch_inlier_mask(const double* res, uint8_t* valid_then_mask, const uint8
                         hipStream_t s);
 void launch_mark_outliers(const double* res, const uint8_t* valid, uint8_t* active, int begin, int end, int dim,
                           double threshold, int* n_marked, hipStream_t s);
-hipError_t configure_eval_kernels(size_t max_lds_bytes);
+hipError_t configure_eval_kernels(int device, size_t max_lds_bytes);
+hipError_t configure_prediction_kernels(int device);
 hipError_t launch_prediction(const PredArgs& pa, size_t lds_bytes, hipStream_t stream);
 
 void launch_gather(double* R, const double* src, const int* out_idx_thin, const int64_t* ptr_thin, const int* idx_thin,
@@ -39,7 +55,7 @@ size_t band_cholesky_lds_bytes(const SolveArgs& a);
 size_t reduced_solve_lds_bytes(const SolveArgs& a);
 size_t frame_lds_doubles(int Ps, int P1e, int n1);
 size_t band_backsolve_lds_bytes(const SolveArgs& a);
-hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t back_lds);
+hipError_t configure_solve_kernels(int device, size_t band_lds, size_t reduced_lds, size_t back_lds);
 void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
                   int n_blocks, bool dense_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi);
 void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s);
@@ -56,10 +72,11 @@ void launch_debug_control_replay(LmState* st, const LmOptionsDev& o, const doubl
                                  double* radius_out, int* accepted_out, double* cost_out, IterLog* log, int log_cap, hipStream_t s);
 size_t bcr_level_lds_bytes();
 size_t bcr_back_lds_bytes(int q_max, int m1p);
-hipError_t configure_bcr_kernels(int q_max, int m1p);
+hipError_t configure_bcr_kernels(int device, int q_max, int m1p);
+hipError_t upload_roll_table();                            // (ensure_roll_table calls it, under the registry's lock)
 void roll_table_row(int k, int lane, unsigned* out);      // (host only: test hook)
-hipError_t configure_dense_block_solve();
-hipError_t configure_reduced_block_step();
+hipError_t configure_dense_block_solve(int device);
+hipError_t configure_reduced_block_step(int device);
 size_t dense_block_solve_lds_bytes();
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
@@ -71,8 +88,8 @@ void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_node
 void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
 int reduced_solve_route(const SolveArgs& a);
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
-size_t dense_back_lds_bytes(int q_max, int m1p);
-hipError_t configure_dense_back_bytes(size_t lds);
+bool dense_back_fits(int q_max, int m1p);
+hipError_t configure_dense_back(int device, int q_max, int m1p);
 void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
                        const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s);
 int reduced_schur_slices(const SolveArgs& a);
@@ -83,7 +100,7 @@ int covariance_ld(int n);
 bool covariance_in_lds(int n);
 void launch_covariance(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* out,
                        double* info, hipStream_t s);
-hipError_t configure_covariance_kernel();
+hipError_t configure_covariance_kernel(int device);
 int cp_covariance_max_order();
 void launch_cp_covariance_band(const CpCovArgs& a, hipStream_t s);
 void launch_cp_covariance_finish(const CpCovArgs& a, hipStream_t s);
@@ -94,7 +111,7 @@ bool observability_in_lds(int m, int mc);
 size_t observability_work_doubles(int m, int mc);
 void launch_observability(const double* Spart, int ks, int m, int mc, const double* Cdiag, const LmState* st, double* work, double* lam,
                           double* vec, double* mat, double* d, double* info, hipStream_t s);
-hipError_t configure_observability_kernel();
+hipError_t configure_observability_kernel(int device);
 void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
                       double* out, hipStream_t s);
 

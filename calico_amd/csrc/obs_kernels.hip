@@ -47,7 +47,6 @@ constexpr int kObsMaxBorder = 256;      // calibration columns (mc) the eigensol
 constexpr int kObsMaxDim = 1024;        // rows of the reduced system (as covariance_kernel)
 constexpr int kObsMaxPairs = kObsMaxBorder / 2;
 constexpr int kObsMaxSweeps = 30;
-constexpr size_t kObsLdsBudget = 160 * 1024;
 // static LDS: six arrays per pair slot, the sort's order, the wave flags, scalars
 constexpr size_t kObsStaticLds = kObsMaxPairs * (4 * sizeof(double) + 3 * sizeof(int)) + kObsMaxBorder * sizeof(int) + kObsWaves * sizeof(int) + 64;
 
@@ -65,7 +64,7 @@ inline size_t obs_small_bytes(int m) { return size_t(m) * (2 * sizeof(double) + 
 int observability_max_border() { return kObsMaxBorder; }
 int observability_max_dim() { return kObsMaxDim; }
 bool observability_in_lds(int m, int mc) {
-  return obs_shared_doubles(m, mc) * sizeof(double) + obs_small_bytes(m) + kObsStaticLds + 1024 <= kObsLdsBudget;
+  return obs_shared_doubles(m, mc) * sizeof(double) + obs_small_bytes(m) + kObsStaticLds + kLdsSlack <= kLdsBudget;
 }
 // doubles of the global workspace (the other size class): the reduced system, S̃ and V apart
 size_t observability_work_doubles(int m, int mc) {
@@ -307,9 +306,9 @@ void launch_observability(const double* Spart, int ks, int m, int mc, const doub
                        vec, mat, d, info);
 }
 
-hipError_t configure_observability_kernel() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(observability_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             int(kObsLdsBudget - kObsStaticLds - 1024));
+// (the largest size observability_in_lds admits)
+hipError_t configure_observability_kernel(int device) {
+  return raise_lds_limit(device, observability_kernel<true>, kLdsBudget - kObsStaticLds - kLdsSlack);
 }
 
 }  // namespace cal

@@ -53,7 +53,7 @@ void build_bcr_plan(calico_problem* p, const PlanSwitches& sw, std::vector<int>&
       // nodes padded to a multiple of eight), eight separators' workgroups and the bookkeeping one do not fit runs its tail in a
       // second dispatch round (1453 control points, chains of four: 256 + 64 + 1 workgroups, level 0 34.7 us; chains of five: +2.9 % it/s)
       const int per = 1 + p->bcr_m1p / 16, nodes = n_sep + 1;
-      if (8 * ((nodes + 7) / 8) * per + 9 > 256) cost += 5.0;
+      if (bcr_level_main_span(nodes, per) + 9 > kNumCUs) cost += 5.0;
       if (cost < best) { best = cost; q = c; }
     }
     if (sw.bcr_leaf > 0) q = sw.bcr_leaf;
@@ -583,7 +583,7 @@ int plan_route(calico_problem* p, const PlanSwitches& sw, PlanTables& t) {
     p->lds_cols = (jc + 15) & ~15;
     p->row_pad = (((jr + 3) & ~3) + 1) | 1;
   }
-  if (size_t(p->lds_cols) * p->row_pad * sizeof(double) > kMaxLds)
+  if (size_t(p->lds_cols) * p->row_pad * sizeof(double) > kLdsBudget)
     return p->set_error(CALICO_UNIMPLEMENTED, "too many Jacobian columns per residual block for the LDS staging area");
   // row store of the items that leave [J r]ᵀ[J r] to the cell kernel: behind the compact frame records
   size_t row_store = 0;
@@ -823,10 +823,10 @@ int build_plan(calico_problem* p, const PlanSwitches& sw, SetupTimer& setup) {
   if (rc != CALICO_OK) return rc;
   setup.section("gather lists");
   const SolveArgs sa = make_solve_args(p);       // (the solvers' LDS windows)
-  if (band_cholesky_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "spline order too high for the banded factorisation window");
-  p->dense_in_lds = reduced_solve_lds_bytes(sa) <= kMaxLds - 1024;
-  if (band_backsolve_lds_bytes(sa) > kMaxLds) return p->set_error(CALICO_UNIMPLEMENTED, "trajectory too long for the back-substitution window");
-  if (p->use_bcr && (bcr_level_lds_bytes() > kMaxLds || bcr_back_lds_bytes(p->bcr_q_max, p->bcr_m1p) > kMaxLds))
+  if (band_cholesky_lds_bytes(sa) > kLdsBudget) return p->set_error(CALICO_UNIMPLEMENTED, "spline order too high for the banded factorisation window");
+  p->dense_in_lds = reduced_solve_lds_bytes(sa) <= kLdsBudget - kLdsSlack;
+  if (band_backsolve_lds_bytes(sa) > kLdsBudget) return p->set_error(CALICO_UNIMPLEMENTED, "trajectory too long for the back-substitution window");
+  if (p->use_bcr && (bcr_level_lds_bytes() > kLdsBudget || bcr_back_lds_bytes(p->bcr_q_max, p->bcr_m1p) > kLdsBudget))
     return p->set_error(CALICO_UNIMPLEMENTED, "tree solver workspace exceeds the LDS");
   rc = upload_plan(p, t);
   if (rc != CALICO_OK) return rc;
@@ -1124,31 +1124,19 @@ int upload_values(calico_problem* p) {
   return CALICO_OK;
 }
 
+// The dynamic-LDS limits this handle's launches need, raised at finalize (raise_lds_limit: a device that already allows them
+// -- every handle of a known structure, and most others -- costs a few dozen look-ups and no hipFuncSetAttribute call).
 int configure_kernels(calico_problem* p) {
   const SolveArgs sa = make_solve_args(p);
-  const size_t reduced_lds = reduced_solve_lds_bytes(sa);
-  // The kernels' dynamic-LDS limits depend on a handful of sizes. They are only ever RAISED on a device (two live handles
-  // of different shapes must not lower each other's limits), and the forty-odd hipFuncSetAttribute calls (0.3 ms) are
-  // skipped when the device already allows what this handle needs -- every handle of a known structure, and most others.
-  const bool db_fits = p->use_bcr && std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(std::min(p->bcr_q_max, 4), p->bcr_m1p)) + 1024 <= kMaxLds;
-  const std::array<size_t, 8> want = {size_t(p->lds_cols) * p->row_pad * sizeof(double), band_cholesky_lds_bytes(sa),
-                                      p->dense_in_lds ? reduced_lds : 0, band_backsolve_lds_bytes(sa), size_t(p->use_bcr ? 1 : 0),
-                                      size_t(p->use_bcr ? p->bcr_q_max : 0), size_t(p->use_bcr ? p->bcr_m1p : 0),
-                                      db_fits ? dense_back_lds_bytes(std::min(p->bcr_q_max, 4), p->bcr_m1p) : 0};
-  static std::mutex mu;
-  static std::map<int, std::array<size_t, 8>> allowed;
-  std::lock_guard<std::mutex> lock(mu);
-  std::array<size_t, 8>& cur = allowed[p->device];       // (zeros for a device seen for the first time)
-  std::array<size_t, 8> nw;
-  for (size_t i = 0; i < nw.size(); ++i) nw[i] = std::max(cur[i], want[i]);
-  if (nw == cur) return CALICO_OK;
-  HIP_TRY(p, configure_eval_kernels(nw[0]));
-  HIP_TRY(p, configure_solve_kernels(nw[1], nw[2], nw[3]));
-  HIP_TRY(p, configure_dense_block_solve());
-  HIP_TRY(p, configure_reduced_block_step());
-  if (nw[4]) HIP_TRY(p, configure_bcr_kernels(int(nw[5]), int(nw[6])));
-  if (nw[7]) HIP_TRY(p, configure_dense_back_bytes(nw[7]));
-  cur = nw;
+  const int dev = p->device;
+  HIP_TRY(p, configure_eval_kernels(dev, size_t(p->lds_cols) * p->row_pad * sizeof(double)));
+  HIP_TRY(p, configure_solve_kernels(dev, band_cholesky_lds_bytes(sa), p->dense_in_lds ? reduced_solve_lds_bytes(sa) : 0, band_backsolve_lds_bytes(sa)));
+  HIP_TRY(p, configure_dense_block_solve(dev));
+  HIP_TRY(p, configure_reduced_block_step(dev));
+  if (!p->use_bcr) return CALICO_OK;
+  HIP_TRY(p, configure_bcr_kernels(dev, p->bcr_q_max, p->bcr_m1p));
+  const int q_fused = std::min(p->bcr_q_max, 4);      // (longer chains never take the fused launch: dense_back_fusable)
+  if (dense_back_fits(q_fused, p->bcr_m1p)) HIP_TRY(p, configure_dense_back(dev, q_fused, p->bcr_m1p));
   return CALICO_OK;
 }
 
@@ -1156,6 +1144,38 @@ int configure_kernels(calico_problem* p) {
 
 // ---- what the other host files call (declared in problem_host.hpp) ----
 namespace cal {
+
+// ---- the launch registry (declared in kernels.hpp): what is done once per device and process ----
+namespace {
+struct DeviceLaunchState {
+  std::map<const void*, size_t> lds_limit;      // dynamic LDS each kernel may ask for here (absent: nothing set yet)
+  bool roll_table = false;                      // g_roll_tab (bcr_kernels.hip) is uploaded
+};
+std::mutex g_launch_mu;
+std::map<int, DeviceLaunchState> g_launch_state;
+long long g_attribute_calls = 0;
+}  // namespace
+
+hipError_t raise_lds_limit(int device, const void* fn, size_t bytes) {
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  size_t& cur = g_launch_state[device].lds_limit[fn];
+  if (bytes <= cur) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+  if (e == hipSuccess) { cur = bytes; ++g_attribute_calls; }
+  return e;
+}
+hipError_t ensure_roll_table(int device) {
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  DeviceLaunchState& d = g_launch_state[device];
+  if (d.roll_table) return hipSuccess;
+  const hipError_t e = upload_roll_table();
+  d.roll_table = e == hipSuccess;
+  return e;
+}
+long long lds_attribute_calls() {
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  return g_attribute_calls;
+}
 
 // A handle's workspace goes back to the pool of the cached plan it belongs to (the handle leaves the plan, or is destroyed):
 // the next handle of this structure takes it over instead of allocating. The caller has drained the handle's stream.

@@ -48,7 +48,11 @@ inline bool env_is(const char* name, const char* value) {
   return e && std::strcmp(e, value) == 0;
 }
 
-constexpr int kRowsPerItem = 128;   // LDS rows staged per work item (64 camera obs × 2)
+// LDS a workgroup may have on this part, static and dynamic together, and what the runtime needs of it: every "does it fit"
+// of the plan, the solve's route and the analyses is  bytes (+ the kernel's static LDS) + kLdsSlack <= kLdsBudget.
+constexpr size_t kLdsBudget = 160 * 1024;
+constexpr size_t kLdsSlack = 1024;
+constexpr int kRowsPerItem = 128;  // LDS rows staged per work item (64 camera obs × 2)
 constexpr int kRowPad = 129;        // largest row stride (doubles) of a staged Jacobian column
 // eval_cells_kernel: the dynamic LDS its launch may ask for. ONE constant for the plan's decision (cell workgroups or
 // not), the kernel's attribute and the launch: cells_launch_lds_bytes() is what a launch asks for.
@@ -410,6 +414,14 @@ constexpr int kBcrCps = 5;        // control points per superblock
 constexpr int kBcrBP = 32;        // padded superblock size
 constexpr int kBcrMaxChain = 8;   // longest chain a node eliminates
 constexpr int kBcrFS = 16;        // border columns per workgroup of a node
+// A level launch's (node, role) workgroups, laid out by XCD: the nodes padded to a multiple of eight, `per` workgroups each.
+// For launch_bcr_level and the plan's chain-length cost; bcr_level_kernel spells the same expression out ("Workgroup ->
+// (node, role)") -- called from there, the function left the compiler with one s_mul_i32's operands the other way round in all
+// five instantiations, and the kernels' code is held byte for byte (profiles/EXPERIMENTS.md).
+// One workgroup of that kernel fills a CU (its LDS) and the part has kNumCUs of them: the launch keeps its separators'
+// workgroups inside that room, the plan charges a level 0 that overflows it.
+constexpr int kNumCUs = 256;
+CAL_HD inline int bcr_level_main_span(int n_nodes, int per) { return 8 * ((n_nodes + 7) / 8) * per; }
 
 struct BcrNodeDev {
   int q;                     // chain length: superblocks blk0, blk0 + 1, ..., eliminated left to right (q > 1 only at level 0)

@@ -22,7 +22,6 @@
 #pragma GCC visibility push(hidden)
 namespace cal {
 
-constexpr size_t kMaxLds = 160 * 1024;
 constexpr int kLogCap = 4096;
 constexpr int kPlanInfoWords = 21;    // words calico_debug_plan_info reports (calico_hip_testing.h)
 constexpr int kNumPhases = 7;   // 5 = calibration: the same event bracket around a trivial kernel; 6 = the reduced-system launch inside phase 2

@@ -88,8 +88,7 @@ LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa) {
   // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
   r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
   const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
-  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) &&
-            std::max(dense_block_solve_lds_bytes(), bcr_back_lds_bytes(lf.q_max, p->bcr_m1p)) + 1024 <= kMaxLds;
+  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) && dense_back_fits(lf.q_max, p->bcr_m1p);
   return r;
 }
 

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 
 #include "kernels.hpp"
 #include "problem_dev.hpp"
@@ -1612,24 +1613,28 @@ size_t reduced_solve_lds_bytes(const SolveArgs& a) {
   return (size_t(m1) * (m1 | 1) + m1) * sizeof(double);
 }
 size_t band_backsolve_lds_bytes(const SolveArgs&) { return 0; }
-hipError_t configure_solve_kernels(size_t band_lds, size_t reduced_lds, size_t back_lds) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&band_cholesky_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(band_lds));
-  if (e != hipSuccess) return e;
-  if (reduced_lds) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_solve_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, int(reduced_lds));
-    if (e != hipSuccess) return e;
-  }
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&reduced_solve_panel_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  for (const void* f : {reinterpret_cast<const void*>(&band_backsolve_kernel<2>), reinterpret_cast<const void*>(&band_backsolve_kernel<3>),
-                        reinterpret_cast<const void*>(&band_backsolve_kernel<4>), reinterpret_cast<const void*>(&band_backsolve_kernel<5>),
-                        reinterpret_cast<const void*>(&band_backsolve_kernel<6>), reinterpret_cast<const void*>(&band_backsolve_kernel<7>),
-                        reinterpret_cast<const void*>(&band_backsolve_kernel<8>)}) {
-    e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(back_lds));
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// reduced_solve_panel_kernel<1>: its one instantiation, and a limit that covers every size launch_reduced_solve gives it
+constexpr auto kPanelSolveFn = reduced_solve_panel_kernel<1>;
+constexpr size_t kPanelSolveMaxLds = 150 * 1024;
+// band_backsolve_kernel<K>: one instantiation per spline order the library takes
+using BandBackFn = decltype(&band_backsolve_kernel<2>);
+struct BandBackVariant { int k; BandBackFn fn; };
+template <int K>
+constexpr BandBackVariant band_back_variant = {K, band_backsolve_kernel<K>};
+constexpr BandBackVariant kBandBackVariants[] = {band_back_variant<2>, band_back_variant<3>, band_back_variant<4>, band_back_variant<5>,
+                                                 band_back_variant<6>, band_back_variant<7>, band_back_variant<8>};
+static const BandBackVariant* select_band_back(int k) {
+  for (const BandBackVariant& v : kBandBackVariants)
+    if (v.k == k) return &v;
+  return nullptr;
+}
+hipError_t configure_solve_kernels(int device, size_t band_lds, size_t reduced_lds, size_t back_lds) {
+  hipError_t e = raise_lds_limit(device, band_cholesky_kernel, band_lds);
+  if (e == hipSuccess) e = raise_lds_limit(device, reduced_solve_kernel, reduced_lds);      // (0 unless it works in LDS)
+  if (e == hipSuccess) e = raise_lds_limit(device, kPanelSolveFn, kPanelSolveMaxLds);
+  for (const BandBackVariant& v : kBandBackVariants)
+    if (e == hipSuccess) e = raise_lds_limit(device, v.fn, back_lds);
+  return e;
 }
 static bool reduced_is_blocked(const SolveArgs& a) { return a.m + 1 > 128 && a.m <= kBlockedMaxM; }
 // K-slices of the Schur complement the reduced solve adds up on load
@@ -1668,7 +1673,7 @@ void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipSt
   } else if (route == kReducedPanel) {
     // a.m == 0 (nothing to calibrate): only the right-hand side's row, which the panel kernel takes
     const size_t lds = (size_t(m1) * ((16 * ((m1 + 15) / 16)) | 1) + m1 + 32 + 128 + 256) * sizeof(double);
-    hipLaunchKernelGGL(reduced_solve_panel_kernel<1>, dim3(1), dim3(256), lds, s, a, 0, ks);
+    hipLaunchKernelGGL(kPanelSolveFn, dim3(1), dim3(256), lds, s, a, 0, ks);
   } else if (route == kReducedBlocked) {
     // panels are eliminated over all CUs until what is left (97..128 unknowns) fits the in-LDS solver, which finishes the
     // factorisation, solves for its unknowns and runs the backward sweep over the panels
@@ -1704,18 +1709,9 @@ void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, do
   const int ks = reduced_schur_slices(a);
   launch_reduced_solve(a, reduced_in_lds, ks, s);
   hipLaunchKernelGGL(border_matvec_kernel, dim3((a.n_s() + 3) / 4), dim3(256), 0, s, a);
-  {
-    const size_t bl = band_backsolve_lds_bytes(a);
-    switch (a.k) {
-      case 2: hipLaunchKernelGGL(band_backsolve_kernel<2>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      case 3: hipLaunchKernelGGL(band_backsolve_kernel<3>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      case 4: hipLaunchKernelGGL(band_backsolve_kernel<4>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      case 5: hipLaunchKernelGGL(band_backsolve_kernel<5>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      case 6: hipLaunchKernelGGL(band_backsolve_kernel<6>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      case 7: hipLaunchKernelGGL(band_backsolve_kernel<7>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-      default: hipLaunchKernelGGL(band_backsolve_kernel<8>, dim3(a.n_seg()), dim3(256), bl, s, a, x, x_cand, blocks, n_blocks); break;
-    }
-  }
+  const BandBackVariant* v = select_band_back(a.k);
+  assert(v && "finalize takes spline orders 2 to 8");
+  hipLaunchKernelGGL(v->fn, dim3(a.n_seg()), dim3(256), band_backsolve_lds_bytes(a), s, a, x, x_cand, blocks, n_blocks);
 }
 void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s) {
   hipLaunchKernelGGL(cost_reduce_kernel, dim3(1), dim3(256), 0, s, item_cost, n_items, R2, st);

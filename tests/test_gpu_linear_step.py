@@ -79,9 +79,12 @@ def _options(api, budget, mu, jacobi, lm_diag):
     return o
 
 
-def check_steps(hip, scene, expect, mu=1.0, jacobi=True, iters=(1,), lm_diag=None, label="", rejected_before=None):
-    """Build, assert the route, and check the step of every iteration in `iters` (see the module's docstring)."""
+def check_steps(hip, scene, expect, mu=1.0, jacobi=True, iters=(1,), lm_diag=None, label="", rejected_before=None, keep=None):
+    """Build, assert the route, and check the step of every iteration in `iters` (see the module's docstring). `keep`: a
+    list that takes the built problem, for a caller that wants the handle to outlive the call."""
     built = syn.build_problem(hip, scene)
+    if keep is not None:
+        keep.append(built)
     P = built.problem
     info = P.plan_info()
     route = {k: info[k] for k in ("tree_solver", "m", "superblocks", "chain", "levels", "root", "schur_rides", "top_seps",
@@ -231,6 +234,20 @@ for _name, _v in (("CALICO_ROLL", "0"), ("CALICO_DENSE_ROLL", "0"), ("CALICO_FUS
                   ("CALICO_BACK_PRE", "1"), ("CALICO_ELIM", "panel"), ("CALICO_SPECULATIVE", "0"), ("CALICO_INLINE_NODES", "0")):
     CASES["two levels, %s=%s" % (_name, _v)] = dict(env={"CALICO_BCR_LEAF": "4", _name: _v}, scene=dict(n_cp=70), iters=(1, 2),
                                                     expect=dict(levels=2, fused_back=0 if _name == "CALICO_FUSE_BACK" else 1))
+
+# Every entry of the kernels' variant tables (dense_back_kernel<QM, MODE, PRE>, bcr_back_kernel<QM, MODE>, band_backsolve_kernel<K>)
+# that no case above reaches. A one-level tree of chains of q has q + 1 superblocks; a two-level one whose top separator is
+# back-substituted in level 0's launch (MODE 2) has 3 q + 2; five control points to a superblock.
+for _q, _n_cp, _levels, _switch in (
+        (1, 10, 1, "CALICO_BACK_PRE=1"), (2, 15, 1, "CALICO_BACK_PRE=1"), (4, 25, 1, "CALICO_BACK_PRE=1"),      # dense_back_kernel<QM, 1, true>
+        (1, 25, 2, "CALICO_BACK_PRE=1"), (2, 40, 2, "CALICO_BACK_PRE=1"),                                        # <QM, 2, true>
+        (2, 15, 1, None), (1, 25, 2, None), (2, 40, 2, None),                                                    # <2, 1, false>, <QM, 2, false>
+        (2, 15, 1, "CALICO_FUSE_BACK=0"), (4, 25, 1, "CALICO_FUSE_BACK=0"), (2, 40, 2, "CALICO_FUSE_BACK=0")):   # bcr_back_kernel<QM, 1>, <2, 2>
+    CASES["chains of %d, %d level(s), %s" % (_q, _levels, _switch or "fused")] = dict(
+        env=dict([("CALICO_BCR_LEAF", str(_q))] + ([_switch.split("=")] if _switch else [])), scene=dict(n_cp=_n_cp),
+        expect=dict(levels=_levels, chain=_q, root=1, top_seps=_levels - 1, fused_back=0 if _switch == "CALICO_FUSE_BACK=0" else 1))
+for _k in (2, 3, 4, 5):
+    CASES["order %d banded" % _k] = dict(env=dict(CALICO_SOLVER="band"), scene=dict(n_cp=25, order=_k), expect=dict(tree_solver=0))
 
 
 @pytest.mark.parametrize("name", list(CASES))
