@@ -584,7 +584,9 @@ class Problem:
                       "all_control_points_observed",
                       # what a linear solve does (calico_hip_testing.h): tree shape, launch fusions, reduced-solve route
                       "superblocks", "chain", "levels", "root", "schur_rides", "top_seps", "fused_back", "reduced_route",
-                      "reduced_in_lds", "schur_slices", "reduced_m", "sep_n")
+                      "reduced_in_lds", "schur_slices", "reduced_m", "sep_n",
+                      # the rest of the route (LinearRoute): what the solve's switches select, the first back-substitution's table entry
+                      "elim", "level0_roll", "dense_mode", "back_pre", "inline_nodes", "first_back_qm", "first_back_mode")
     REDUCED_ROUTES = ("panel", "block", "blocked", "kernel")     # plan_info()["reduced_route"] indexes this
 
     def plan_info(self):

@@ -27,6 +27,7 @@ namespace {
 // (calico_problem::pass): nothing of the LM's is touched.
 struct ReducedPass {
   SolveArgs sa;
+  LinearRoute rt;             // of the pass's one linear solve (the solve's switches as set when the pass opens)
   LmOptionsDev o = {};
   int m = 0, mc = 0;          // rows of the reduced system, calibration columns among them
   CpCovArgs ca = {};          // the control points' band (filled by begin_reduced_pass(band = true))
@@ -40,6 +41,7 @@ int open_reduced_pass(calico_problem* p, ReducedPass& rp) {
   if (rc != CALICO_OK) return rc;
   HIP_TRY(p, hipSetDevice(p->device));
   rp.sa = make_solve_args(p);
+  rp.rt = linear_route(p, rp.sa, SolveSwitches{});
   rp.mc = p->m; rp.m = rp.sa.m;
   return CALICO_OK;
 }
@@ -89,7 +91,7 @@ int begin_reduced_pass(calico_problem* p, ReducedPass& rp, bool band) {
 // the reduction, stopped once the reduced system is formed (nothing to reduce onto without calibration columns)
 int reduce_pass(calico_problem* p, const ReducedPass& rp) {
   if (rp.mc == 0) return CALICO_OK;
-  enqueue_linear_solve(p, rp.sa, rp.o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
+  enqueue_linear_solve(p, rp.sa, rp.rt, rp.o, /*with_post_eval=*/0, /*jacobi=*/0, /*reduce_only=*/true);
   HIP_TRY(p, hipGetLastError());
   return CALICO_OK;
 }

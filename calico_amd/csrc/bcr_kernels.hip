@@ -34,9 +34,6 @@
 
 namespace cal {
 
-bool block_elim_enabled();
-static int dense_elim_mode();
-
 namespace {
 constexpr int BP = kBcrBP;              // 32
 constexpr int BB = BP * BP;             // 1024
@@ -302,7 +299,7 @@ DEVI void schur_root_rows(const SolveArgs& a, const BcrArgs& b, int ks, int w0, 
 // the bookkeeping of the step just accepted when `with_post` is set (post_eval_body: it only reads R(x) and x).
 // ELIM (round 4): the block is eliminated by block_elim.hpp -- a chief wave on the spine, waves 1..3 as followers with the
 // identity rows (role 0: L⁻ᵀ) and the rows of Xᵀ, so that Z comes out of the factorisation -- instead of panel | tile |
-// panel | Z = MᵀX (CALICO_ELIM=panel keeps those).
+// panel | Z = MᵀX (the panel form, elim == false, keeps those).
 // A thread's share of a block's entries on the way from memory to LDS (bcr_level_kernel's fetch / commit): NL threads
 // take NU entries of D / B / A and NF of the F slice each, thread lt the entries lt, lt + NL, ...
 // Level 0 (round 5): the entries are dealt so that the lanes of a load run ALONG the six contiguous doubles of the band's
@@ -3004,8 +3001,8 @@ __global__ __launch_bounds__(kDenseThreads) void dense_back_kernel(SolveArgs a, 
 }
 size_t dense_block_solve_lds_bytes() { return size_t(128 * DNL + 128 + kDenseChan + 128 * 3 + 32 + 128 + kDenseThreads) * sizeof(double); }
 hipError_t configure_dense_block_solve(int device) { return raise_lds_limit(device, dense_block_solve_kernel, dense_block_solve_lds_bytes()); }
-void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0, int outer_back) {
-  hipLaunchKernelGGL(dense_block_solve_kernel, dim3(1), dim3(kDenseThreads), dense_block_solve_lds_bytes(), s, a, ks, t0, outer_back, dense_elim_mode());
+void launch_dense_block_solve(const SolveArgs& a, int ks, int dense_mode, hipStream_t s, int t0, int outer_back) {
+  hipLaunchKernelGGL(dense_block_solve_kernel, dim3(1), dim3(kDenseThreads), dense_block_solve_lds_bytes(), s, a, ks, t0, outer_back, dense_mode);
 }
 // ---------------------------------------------------------------------------
 // Large reduced systems (m + 1 > 128): one step of the blocked right-looking factorisation, 32 columns, over several
@@ -3157,21 +3154,18 @@ void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hip
 size_t bcr_back_lds_bytes(int q_max, int m1p);
 // Can the first back-substitution launch ride in the dense solve's launch? Only the shapes the in-LDS solve takes, no
 // border-row sweep workgroups (those would sit on every CU with the dense solve's LDS footprint), chains of at most four.
-// CALICO_FUSE_BACK=0: two launches (read per solve; the tests' reference for the hand-off).
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows) {
-  return env_flag("CALICO_FUSE_BACK", true) && a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
+  return a.m + 1 <= 128 && a.m >= 1 && ks <= 2 && q_max <= 4 && !border_rows;
 }
 // PRE: the nodes form their solution as an affine map of the reduced solve's output while they wait (back_node_pre);
 // needs mc + 33 <= 128 columns (one 16-column tile per wave) and a reduced solve long enough to hide the recursion behind:
 // it takes ~50k clocks (requests 15k, staging 15k, recursion 20k; dev-timing dump), a reduced solve 11k + 16k per
 // 32-column block -- four blocks (m + 1 > 96: configs[3]) cover it, two (configs[1]: 9450 with, 10200 it/s without) do
-// not. CALICO_BACK_PRE=0 / 1: never / whenever the columns fit (A/B switch).
-static bool dense_back_pre(const SolveArgs& a) {
-  if (a.mc + BP + 1 > 128) return false;
-  return env_flag("CALICO_BACK_PRE", a.m + 1 > 96);
-}
+// not. Two rules: whether it fits, and whether it pays (the default of the solve's back_pre switch: linear_route).
+bool dense_back_pre_fits(const SolveArgs& a) { return a.mc + BP + 1 <= 128; }
+bool dense_back_pre_pays(const SolveArgs& a) { return a.m + 1 > 96; }
 // chains share instantiations by length: QM is the next of 1, 2, 4, 8
-static int chain_variant(int q_max) { return q_max <= 1 ? 1 : (q_max <= 2 ? 2 : (q_max <= 4 ? 4 : 8)); }
+int chain_variant(int q_max) { return q_max <= 1 ? 1 : (q_max <= 2 ? 2 : (q_max <= 4 ? 4 : 8)); }
 // (the solve's own LDS exceeds back_node_pre's at every QM of this launch, so the third term never decides the maximum)
 static size_t dense_back_lds(int q_max, int m1p) {
   const int qm = std::min(chain_variant(q_max), 4);
@@ -3204,26 +3198,18 @@ hipError_t configure_dense_back(int device, int q_max, int m1p) {
   return hipSuccess;
 }
 void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
-                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s) {
-  const DenseBackVariant* v = select_dense_back(q_max, ts.n > 0, dense_back_pre(a));
+                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s, bool pre, int dense_mode) {
+  const DenseBackVariant* v = select_dense_back(q_max, ts.n > 0, pre);
   assert(v && "dense_back_fusable keeps chains longer than four out of the fused launch");
   const dim3 grid(1 + n_nodes + 1), block(kDenseThreads);       // dense solve, the nodes, the calibration / root update
   hipLaunchKernelGGL(v->fn, grid, block, dense_back_lds(q_max, b.m1p), s, a, b, ks, node0, n_nodes, q_max, x, x_cand, blocks, n_blocks, ts,
-                     word, seq, dense_elim_mode());
+                     word, seq, dense_mode);
 }
 
 // ---- launch helpers ---------------------------------------------------------
-// CALICO_ELIM=panel: the block factorisation of rounds 1-3 (two in-wave panels + tile update + Z phase); read per solve (A/B switch)
-bool block_elim_enabled() { return !env_is("CALICO_ELIM", "panel"); }
-// The dense reduced solve with rolling owners (dense_block_solve_body, elim == 2), the default; CALICO_DENSE_ROLL=0: the barrier
-// form (A/B switch, read per solve)
-static int dense_elim_mode() {
-  if (!block_elim_enabled()) return 0;
-  return env_flag("CALICO_DENSE_ROLL", true) ? 2 : 1;
-}
 // Level 0's chains with the rolling chief (bcr_level_kernel<true, true, true>: no workgroup barrier between the blocks of
-// a chain), the default; CALICO_ROLL=0: the barrier form (A/B switch, read per solve)
-static bool level_roll_enabled() { return env_flag("CALICO_ROLL", true); }
+// a chain) exist for the spline orders whose band is block tridiagonal in superblocks (g_roll_tab)
+bool level0_roll_fits(const SolveArgs& a) { return a.k >= 1 && a.k <= 6; }
 // (4 · BP · XLD: the barrier form uses three -- X twice, Z --; the rolling form's layout needs the fourth, see its static_assert)
 size_t bcr_level_lds_bytes() { return size_t(2 * 64 * DLD + 4 * BP * XLD + 80 + 128 + kLevelThreads + kElimBufDoubles) * sizeof(double); }
 size_t bcr_back_lds_bytes(int q_max, int m1p) {
@@ -3259,9 +3245,10 @@ hipError_t configure_bcr_kernels(int device, int q_max, int m1p) {
 
 // `schur_ks` > 0 (the LAST level of a tree of at least two): the Schur complement's tiles and the root's rows ride behind
 // this level's workgroups and take its results over the fan-in word; level 0 (`fan_word` given) resets the word.
+// `elim`, `roll` (level 0 only): the elimination's form, LinearRoute::elim and ::level0_roll.
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
-                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl) {
+                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl, bool elim, bool roll) {
   const int nfs = (a.mc + 1 + kBcrFS - 1) / kBcrFS;
   int n_apply = n_keep > 0 ? std::min(64, std::max(1, n_keep * 4)) : 0;
   const int main_span = bcr_level_main_span(n_nodes, 1 + nfs);
@@ -3271,9 +3258,8 @@ void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nod
   // 224 + 64 + 1 workgroups, level 0 21.5 us with the chains done at 13 us).
   const int room = kNumCUs - main_span - (level == 0 && with_post_eval ? 1 : 0);
   if (room >= 8 && n_apply > room) n_apply = room;
-  const bool elim = block_elim_enabled();
   if (level == 0) {
-    const bool roll = elim && a.k >= 1 && a.k <= 6 && level_roll_enabled();
+    assert((!roll || (elim && level0_roll_fits(a))) && "the rolling chief is a form of the block elimination (linear_route)");
     hipLaunchKernelGGL((roll ? bcr_level_kernel<true, true, true> : elim ? bcr_level_kernel<true, true> : bcr_level_kernel<true, false>), dim3(main_span + n_apply + (with_post_eval ? 1 : 0)), dim3(kLevelThreads),
                        bcr_level_lds_bytes(), s, a, b, node0, n_nodes, nfs, level, keep0, n_keep, o, with_post_eval, x, blocks, n_blocks,
                        log, log_cap, jacobi, 0, 0, 1, fan_word, 0, inl);

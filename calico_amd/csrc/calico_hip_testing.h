@@ -23,21 +23,26 @@ int32_t calico_debug_lm_control_replay(int32_t device, int32_t n, const double* 
                                        double* cost_column_out);
 
 /* What calico_problem_finalize decided for the handle's structure (finalizes the handle if it has not been yet), so
- * that a test can assert WHICH evaluation route it is comparing with the oracle. out[0..n) (n <= 21) receives:
+ * that a test can assert WHICH evaluation route it is comparing with the oracle. out[0..n) (n <= 28) receives:
  *   [0] fuse_expand (1: eval_cells_kernel -- cell workgroups; 0: eval_jacobian_kernel + expand_cells_kernel + row cells),
  *   [1] camera frames on the frame path, [2] work items of the generic / IMU path, [3] cells,
  *   [4] most frames in one camera cell, [5] most work items in one (layout, segment) of the item path,
  *   [6] 1: tree solver, 0: sequential banded solver, [7] m (tangent size of the calibration blocks). */
 int32_t calico_debug_plan_info(calico_problem* problem, int32_t* out, int32_t n);
 /* (out[8], n = 9: 1 if every control point is observed.)
- * What a linear solve of the plan does (n up to 21; the per-solve switches CALICO_FUSE_BACK etc. as set at the call):
+ * What a linear solve of the plan does (n up to 28; the solve's switches -- SolveSwitches, problem_host.hpp -- as set at the call):
  *   [9] superblocks N of the tree solver (0: banded solver), [10] level 0's chain length q, [11] levels, [12] 1: a root exists,
  *   [13] 1: the Schur complement rides in the last level's launch, [14] top separators back-substituted in the level below,
  *   [15] 1: the dense solve is fused with the first back-substitution,
  *   [16] reduced-solve route (0: 16-column panel kernel, 1: in-LDS block solve, 2: blocked panels, 3: reduced_solve_kernel),
  *   [17] 1: reduced_solve_kernel works in LDS (0: in its global workspace), [18] K-slices of the Schur complement,
  *   [19] width of the reduced system a.m (calibration + root or separator rows), [20] sep_n (separator control points of the
- *   banded solver's split). */
+ *   banded solver's split),
+ *   [21] 1: elimination by blocks (0: the panel factorisation), [22] 1: level 0's chains with the rolling chief,
+ *   [23] the dense reduced solve's mode (0: panel form, 1: blocks with barriers, 2: rolling owners),
+ *   [24] 1: the fused launch's nodes in affine form (PRE), [25] 1: node descriptors in the launch arguments,
+ *   [26], [27] (QM, MODE) of the table entry of the first back-substitution behind the reduced solve (dense_back_kernel
+ *   where [15] is 1, else bcr_back_kernel; 0, 0: banded solver). */
 
 /* The last linear solve of the last calico_solve: step delta (what the candidate update applied to the parameters), the
  * damping d added to the diagonal of J^T J, and the Jacobi scale in use. n: calico_num_effective_parameters (calico_evaluate's

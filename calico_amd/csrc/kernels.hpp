@@ -57,7 +57,7 @@ size_t frame_lds_doubles(int Ps, int P1e, int n1);
 size_t band_backsolve_lds_bytes(const SolveArgs& a);
 hipError_t configure_solve_kernels(int device, size_t band_lds, size_t reduced_lds, size_t back_lds);
 void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
-                  int n_blocks, bool dense_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi);
+                  int n_blocks, bool dense_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi, int dense_mode);
 void launch_cost_reduce(const double* item_cost, int n_items, double* R2, const LmState* st, hipStream_t s);
 void launch_control(LmState* st, const LmOptionsDev& o, double* R2, double* x, const double* x_cand, int n_amb,
                     IterLog* log, int log_cap, const double* item_cost, int n_items, const double* Rbase, size_t r_stride,
@@ -80,18 +80,23 @@ hipError_t configure_reduced_block_step(int device);
 size_t dense_block_solve_lds_bytes();
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
-                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl);
+                      hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl, bool elim, bool roll);
 void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
 void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
 
-void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s);
+void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, int dense_mode, hipStream_t s);
 int reduced_solve_route(const SolveArgs& a);
+// shape rules of the tree solver's routes (pure functions of their arguments; the switches are linear_route's, solve.cpp)
 bool dense_back_fusable(const SolveArgs& a, int ks, int q_max, bool border_rows);
+bool dense_back_pre_fits(const SolveArgs& a);
+bool dense_back_pre_pays(const SolveArgs& a);
+bool level0_roll_fits(const SolveArgs& a);
+int chain_variant(int q_max);      // QM of the back-substitution kernels' table entry for chains of up to q_max
 bool dense_back_fits(int q_max, int m1p);
 hipError_t configure_dense_back(int device, int q_max, int m1p);
 void launch_dense_back(const SolveArgs& a, const BcrArgs& b, int ks, int node0, int n_nodes, int q_max, const double* x, double* x_cand,
-                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s);
+                       const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, int* word, int seq, hipStream_t s, bool pre, int dense_mode);
 int reduced_schur_slices(const SolveArgs& a);
 void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const double* x, const BlockDev* blocks, int n_blocks, hipStream_t s,
                            bool with_post_eval, IterLog* log, int log_cap, int jacobi);

@@ -1003,7 +1003,7 @@ int prepare_workspace(calico_problem* p) {
   HIP_TRY(p, p->d_m0.alloc(size_t(n_obs))); HIP_TRY(p, p->d_m1.alloc(size_t(n_obs))); HIP_TRY(p, p->d_m2.alloc(size_t(n_obs)));
   HIP_TRY(p, p->d_partials.alloc(p->partials_alloc));
   HIP_TRY(p, hipMemsetAsync(p->d_partials.p + (p->partials_alloc - 2), 0, 2 * sizeof(double), s));      // the word the lists point to for "nothing"
-  if (env_int("CALICO_KERNEL_TIMING", 0, 0) >= 3) HIP_TRY(p, p->d_wave_log.alloc(2 * size_t(p->n_jac_items + p->n_fitems) + 8));
+  if (kernel_timing_level() >= 3) HIP_TRY(p, p->d_wave_log.alloc(2 * size_t(p->n_jac_items + p->n_fitems) + 8));
   // Behind the second reduce buffer: what the tree solver's rolling chief (bcr_level_kernel, ROLL) reads and masks past the
   // band of the last superblock I = N - 1. Its lanes load at I·strideB + (g_roll_tab offset) and select afterwards; the offsets
   // reach (6k - 1)·36 + 11 doubles into a superblock's storage (rows 30 and 31 of the 32-row tiles count as control point 5,

@@ -42,7 +42,7 @@ inline int env_int(const char* name, int def, int lo, int hi = INT_MAX) {
   const int v = std::atoi(e);
   return v < lo ? lo : (v > hi ? hi : v);
 }
-// A switch that names a variant (CALICO_SOLVER=band, CALICO_ELIM=panel).
+// A switch that names a variant (CALICO_SOLVER=band).
 inline bool env_is(const char* name, const char* value) {
   const char* e = std::getenv(name);
   return e && std::strcmp(e, value) == 0;

@@ -23,7 +23,7 @@
 namespace cal {
 
 constexpr int kLogCap = 4096;
-constexpr int kPlanInfoWords = 21;    // words calico_debug_plan_info reports (calico_hip_testing.h)
+constexpr int kPlanInfoWords = 28;    // words calico_debug_plan_info reports (calico_hip_testing.h)
 constexpr int kNumPhases = 7;   // 5 = calibration: the same event bracket around a trivial kernel; 6 = the reduced-system launch inside phase 2
 
 struct HBlock {
@@ -462,11 +462,48 @@ void release_measurement_staging(calico_problem* p);
 void plan_cache_stats(int64_t* hits, int64_t* misses, int64_t* entries);
 void plan_cache_clear();
 // solve.cpp
+// The switches that shape a solve, read when one is constructed -- at the start of a solve (SolveRun::begin), of
+// the analyses' reduce-only pass and of calico_debug_plan_info -- and handed down: the per-solve counterpart of plan.cpp's
+// PlanSwitches. Each is an A/B switch whose other value is the reference of a test.
+struct SolveSwitches {
+  int stream_depth = env_int("CALICO_STREAM_DEPTH", 2, 0);          // iterations the polled loop keeps ahead of the device (0: the batched loop)
+  bool predict_end = env_flag("CALICO_PREDICT_END", true);          // 0: always one iteration ahead, no end hint (rounds 2-3)
+  bool multirank_async = env_flag("CALICO_MULTIRANK_ASYNC", true);  // 0: one host round trip per iteration with several ranks
+  bool inline_nodes = env_flag("CALICO_INLINE_NODES", true);        // 0: every level reads its node descriptors from the table
+  bool fuse_back = env_flag("CALICO_FUSE_BACK", true);              // 0: the dense solve and the first back-substitution in two launches
+  // the fused launch's nodes in affine form (PRE): unset (-1) where the reduced solve is long enough to hide it behind
+  // (dense_back_pre_pays), 0 never, any other value (1) wherever the columns fit
+  int back_pre = env_flag("CALICO_BACK_PRE", true) ? (env_flag("CALICO_BACK_PRE", false) ? 1 : -1) : 0;
+  bool block_elim = !env_is("CALICO_ELIM", "panel");                // panel: the block factorisation of rounds 1-3 (two in-wave panels + tile update + Z phase)
+  bool dense_roll = env_flag("CALICO_DENSE_ROLL", true);            // 0: the dense reduced solve's barrier form instead of rolling owners
+  bool level_roll = env_flag("CALICO_ROLL", true);                  // 0: level 0's chains in the barrier form instead of the rolling chief
+};
+// What one linear solve does, from the plan and the solve's switches: decided once per solve (linear_route), followed by
+// enqueue_linear_solve and the launch helpers it hands the fields to, reported by calico_debug_plan_info (one decision, so
+// the hook cannot drift from what runs).
+struct LinearRoute {
+  int ks = 1;                 // K-slices of the Schur complement (reduced_schur_slices)
+  int reduced = 0;            // ReducedRoute of the reduced solve
+  bool reduced_in_lds = true; // kReducedKernel: works in LDS (else in Swork)
+  bool elim = true;           // the elimination by blocks (else the panel factorisation), in the tree's levels and the dense solve
+  int dense_mode = 2;         // dense_block_solve_body's `elim`: 0 the panel form, 1 blocks with barriers, 2 rolling owners
+  // tree solver only:
+  bool schur_rides = false;   // the Schur complement rides in the last level's launch
+  BcrTopSeps ts = {};         // top separators back-substituted in the launch of the level below (ts.n of them)
+  int l_first = 0;            // level of the first back-substitution launch behind the reduced solve
+  bool fused = false;         // the dense solve and that back-substitution share one launch (dense_back_kernel)
+  bool back_pre = false;      // ... whose nodes form their solution as an affine map while they wait (dense_back_kernel<.., PRE>)
+  bool level0_roll = false;   // level 0's chains with the rolling chief (bcr_level_kernel<true, true, true>)
+  bool inline_nodes = false;  // the levels' node descriptors travel in the launch arguments
+};
+LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa, const SolveSwitches& sw);
+int kernel_timing_level();    // CALICO_KERNEL_TIMING, read once per process (development diagnostics of a CALICO_DEV_TIMING build)
 SolveArgs make_solve_args(calico_problem* p);
 EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res);
 int upload_x(calico_problem* p, bool seed = true);
 int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, const double* x_at = nullptr, bool spec = false,
                           const ControlTail* tail = nullptr, bool end_hint = false);
-void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only = false);
+void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LinearRoute& rt, const LmOptionsDev& o, int with_post_eval, int jacobi,
+                          bool reduce_only = false);
 }  // namespace cal
 #pragma GCC visibility pop

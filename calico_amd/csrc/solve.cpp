@@ -45,53 +45,6 @@ int do_allreduce(calico_problem* p, double* buf, int64_t n) {
 
 static bool end_hint_available(const calico_problem* p) { return p->order == 6 && p->n_fitems > 0; }
 
-// What one linear solve does, from the plan and the switches read per solve: enqueue_linear_solve follows it,
-// calico_debug_plan_info reports it (one decision, so the hook cannot drift from what runs).
-struct LinearRoute {
-  int ks = 1;                 // K-slices of the Schur complement (reduced_schur_slices)
-  int reduced = 0;            // ReducedRoute of the reduced solve
-  bool reduced_in_lds = true; // kReducedKernel: works in LDS (else in Swork)
-  // tree solver only:
-  bool schur_rides = false;   // the Schur complement rides in the last level's launch
-  BcrTopSeps ts = {};         // top separators back-substituted in the launch of the level below (ts.n of them)
-  int l_first = 0;            // level of the first back-substitution launch behind the reduced solve
-  bool fused = false;         // the dense solve and that back-substitution share one launch (dense_back_kernel)
-};
-LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa) {
-  LinearRoute r;
-  r.ks = reduced_schur_slices(sa);
-  r.reduced = reduced_solve_route(sa);
-  r.reduced_in_lds = p->dense_in_lds;
-  if (!p->use_bcr || p->bcr_levels.empty()) return r;
-  const int L = int(p->bcr_levels.size());
-  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
-  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
-  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
-  // launch bcr_schur_kernel on its own.
-  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
-  r.schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
-  for (int i = 0; r.schur_rides && i < last.n_nodes; ++i) r.schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
-  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
-  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
-  // the ones it waits for anyway) instead of costing a launch of its own.
-  if (L >= 2) {
-    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
-    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
-    for (int i = 0; ok && i < tl.n_nodes; ++i) {
-      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
-      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
-      r.ts.blk[i] = nd.blk0; r.ts.left[i] = nd.left; r.ts.right[i] = nd.right;
-    }
-    r.ts.n = ok ? tl.n_nodes : 0;
-  }
-  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
-  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
-  r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
-  const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
-  r.fused = r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) && dense_back_fits(lf.q_max, p->bcr_m1p);
-  return r;
-}
-
 int read_state(calico_problem* p) {
   HIP_TRY(p, hipMemcpyAsync(p->h_state, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(p, hipStreamSynchronize(p->stream));
@@ -163,12 +116,49 @@ void check_finite_after_tree_solve(calico_problem* p, const SolveArgs& sa, const
 // ---- one LM iteration (declared in problem_host.hpp: analysis.cpp and plan.cpp call these as well) ----
 namespace cal {
 
-SolveArgs make_solve_args(calico_problem* p) {
-  SolveArgs a;
-  a.R = p->d_R.p; a.r_stride = p->speculative ? p->r_size : 0; a.Lb = p->d_Lb.p; a.Linv = p->d_Linv.p; a.Y = p->d_Y.p; a.S = p->d_S.p; a.Spart = p->d_Spart.p;
-  a.Swork = p->d_Swork.p; a.y = p->d_y.p; a.zbuf = p->d_zbuf.p; a.dadd = p->d_dadd.p;
-  a.scale = p->d_scale.p; a.cp_active = p->d_cp_active.p; a.st = p->d_state.p; a.n_cp = p->n_cp; a.k = p->order; a.mc = p->m; a.sep_s = p->sep_s; a.sep_n = p->sep_n; a.m = p->m + p->border_extra();
-  static const int dbg = [] {
+// The route of a solve's linear solves: the plan's shapes, the kernels' shape rules (kernels.hpp) and the solve's switches.
+LinearRoute linear_route(const calico_problem* p, const SolveArgs& sa, const SolveSwitches& sw) {
+  LinearRoute r;
+  r.ks = reduced_schur_slices(sa);
+  r.reduced = reduced_solve_route(sa);
+  r.reduced_in_lds = p->dense_in_lds;
+  r.elim = sw.block_elim;
+  r.dense_mode = !r.elim ? 0 : (sw.dense_roll ? 2 : 1);
+  if (!p->use_bcr || p->bcr_levels.empty()) return r;
+  const int L = int(p->bcr_levels.size());
+  // The Schur complement rides in the last level's launch (its tiles over the rows eliminated below that level run beside
+  // the level's chains; the level's own rows and the root's rows follow an in-launch fan-in): one launch less. Trees of at
+  // least two levels, whose last level has one or two single-superblock nodes by construction of the plan; one-level trees
+  // launch bcr_schur_kernel on its own.
+  const BcrLevel& last = p->bcr_levels[size_t(L - 1)];
+  r.schur_rides = L >= 2 && last.n_nodes >= 1 && last.n_nodes <= 2 && p->bcr_root >= 0;
+  for (int i = 0; r.schur_rides && i < last.n_nodes; ++i) r.schur_rides = p->h_bcr_nodes[size_t(last.node0 + i)].q == 1;
+  // The top level of the tree is one or two single superblocks next to the root: their back-substitution rides in the
+  // launch of the level below (every node there solves the top separators beside it itself -- a few more loads next to
+  // the ones it waits for anyway) instead of costing a launch of its own.
+  if (L >= 2) {
+    const BcrLevel& tl = p->bcr_levels[size_t(L - 1)];
+    bool ok = tl.n_nodes <= 2 && p->bcr_levels[size_t(L - 2)].q_max <= 4;
+    for (int i = 0; ok && i < tl.n_nodes; ++i) {
+      const BcrNodeDev& nd = p->h_bcr_nodes[size_t(tl.node0 + i)];
+      ok = nd.q == 1 && (nd.left < 0 || nd.left == p->bcr_root) && (nd.right < 0 || nd.right == p->bcr_root);
+      r.ts.blk[i] = nd.blk0; r.ts.left[i] = nd.left; r.ts.right[i] = nd.right;
+    }
+    r.ts.n = ok ? tl.n_nodes : 0;
+  }
+  // The first back-substitution launch rides in the launch of the dense reduced solve where the shapes allow it (the
+  // nodes fetch what they need while the solve runs and take its solution over a hand-off word: dense_back_kernel).
+  r.l_first = r.ts.n > 0 ? L - 2 : L - 1;
+  const BcrLevel& lf = p->bcr_levels[size_t(r.l_first)];
+  r.fused = sw.fuse_back && r.l_first == 0 && dense_back_fusable(sa, r.ks, lf.q_max, /*border_rows=*/r.l_first > 0) && dense_back_fits(lf.q_max, p->bcr_m1p);
+  r.back_pre = r.fused && dense_back_pre_fits(sa) && (sw.back_pre < 0 ? dense_back_pre_pays(sa) : sw.back_pre != 0);
+  r.level0_roll = sw.level_roll && r.elim && level0_roll_fits(sa);
+  r.inline_nodes = sw.inline_nodes;
+  return r;
+}
+
+int kernel_timing_level() {
+  static const int level = [] {
     const int v = env_int("CALICO_KERNEL_TIMING", 0, 0);
 #ifndef CALICO_DEV_TIMING
     if (v) std::fprintf(stderr, "[calico] CALICO_KERNEL_TIMING is set, but this library was built without the kernels' development "
@@ -176,15 +166,22 @@ SolveArgs make_solve_args(calico_problem* p) {
 #endif
     return v;
   }();
-  a.debug = dbg;
+  return level;
+}
+
+SolveArgs make_solve_args(calico_problem* p) {
+  SolveArgs a;
+  a.R = p->d_R.p; a.r_stride = p->speculative ? p->r_size : 0; a.Lb = p->d_Lb.p; a.Linv = p->d_Linv.p; a.Y = p->d_Y.p; a.S = p->d_S.p; a.Spart = p->d_Spart.p;
+  a.Swork = p->d_Swork.p; a.y = p->d_y.p; a.zbuf = p->d_zbuf.p; a.dadd = p->d_dadd.p;
+  a.scale = p->d_scale.p; a.cp_active = p->d_cp_active.p; a.st = p->d_state.p; a.n_cp = p->n_cp; a.k = p->order; a.mc = p->m; a.sep_s = p->sep_s; a.sep_n = p->sep_n; a.m = p->m + p->border_extra();
+  a.debug = kernel_timing_level();
   a.progress = nullptr;
   return a;
 }
 
 EvalArgs make_eval_args(calico_problem* p, const double* x, int apply_loss, bool want_res) {
   EvalArgs a;
-  static const int dbg = env_int("CALICO_KERNEL_TIMING", 0, 0);
-  a.debug = dbg;
+  a.debug = kernel_timing_level();
   a.x = x; a.sensors = p->d_sensors.p; a.layouts = p->d_layouts.p; a.items = p->d_items.p;
   a.knots = p->d_knots.p; a.basis = p->d_basis.p; a.ctrl_off = p->d_ctrl_off.p;
   a.m0 = p->d_m0.p; a.m1 = p->d_m1.p; a.m2 = p->d_m2.p; a.stamp = p->d_stamp.p; a.point_off = p->d_point_off.p;
@@ -276,7 +273,8 @@ int enqueue_jacobian_eval(calico_problem* p, const LmState* st, int need_flag, c
 // with_post_eval: 0 none, 1 the bookkeeping of the step just accepted rides in the first launch, 2 the bookkeeping of the
 // solve's FIRST evaluation does (tree solver only: level 0 then forms the Jacobi scale of its diagonal entries itself)
 // reduce_only (the covariance pass): stop once the reduced system is in sa.Spart -- no reduced solve, no back-substitution.
-void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOptionsDev& o, int with_post_eval, int jacobi, bool reduce_only) {
+void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LinearRoute& rt, const LmOptionsDev& o, int with_post_eval, int jacobi,
+                          bool reduce_only) {
   hipStream_t s = p->stream;
   const int n_blocks = int(p->h_blocks.size());
   if (reduce_only && !p->use_bcr) {
@@ -284,26 +282,23 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
     return;
   }
   if (!p->use_bcr) {
-    launch_solve(sa, o, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, p->dense_in_lds, s, with_post_eval == 1, p->d_log.p, kLogCap, jacobi);
+    launch_solve(sa, o, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, p->dense_in_lds, s, with_post_eval == 1, p->d_log.p, kLogCap, jacobi, rt.dense_mode);
     return;
   }
   const BcrArgs b = make_bcr_args(p);
   const int L = int(p->bcr_levels.size());
-  const LinearRoute rt = linear_route(p, sa);
   const int ks = rt.ks;
   const bool schur_rides = rt.schur_rides;
   int* const fan_word = p->d_handoff.p + 4;
-  // (A/B switch, read per solve: 0 = every level reads its node descriptors from the table)
-  const bool inline_nodes = env_flag("CALICO_INLINE_NODES", true);
   for (int l = 0; l < L; ++l) {
     const BcrLevel& lv = p->bcr_levels[size_t(l)];
     BcrInlineNodes inl = {};
-    if (inline_nodes) {
+    if (rt.inline_nodes) {
       if (l == 0) inl.q_regular = p->bcr_q0;
       else if (lv.n_nodes <= 4) { inl.n = lv.n_nodes; for (int i = 0; i < lv.n_nodes; ++i) inl.nd[i] = p->h_bcr_nodes[size_t(lv.node0 + i)]; }
     }
     launch_bcr_level(sa, b, lv.node0, lv.n_nodes, l, lv.keep0, lv.n_keep, o, p->d_x.p, p->d_blocks.p, n_blocks, l == 0 ? with_post_eval : 0,
-                     p->d_log.p, kLogCap, jacobi, s, schur_rides && l == L - 1 ? ks : 0, schur_rides ? fan_word : nullptr, inl);
+                     p->d_log.p, kLogCap, jacobi, s, schur_rides && l == L - 1 ? ks : 0, schur_rides ? fan_word : nullptr, inl, rt.elim, l == 0 && rt.level0_roll);
   }
   if (!schur_rides) launch_bcr_schur(sa, b, ks, o, s);
   if (reduce_only) return;
@@ -313,9 +308,10 @@ void enqueue_linear_solve(calico_problem* p, const SolveArgs& sa, const LmOption
   p->timer.begin(6, s);       // the launch that solves the reduced system: the longest kernel of an iteration at configs[3]
   if (fused) {
     p->handoff_seq = p->handoff_seq % 0x3fffffff + 1;
-    launch_dense_back(sa, b, ks, lf.node0, lf.n_nodes, lf.q_max, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, ts, p->d_handoff.p, p->handoff_seq, s);
+    launch_dense_back(sa, b, ks, lf.node0, lf.n_nodes, lf.q_max, p->d_x.p, p->d_xc.p, p->d_blocks.p, n_blocks, ts, p->d_handoff.p, p->handoff_seq, s,
+                      rt.back_pre, rt.dense_mode);
   } else {
-    launch_reduced_solve(sa, p->dense_in_lds, ks, s);
+    launch_reduced_solve(sa, p->dense_in_lds, ks, rt.dense_mode, s);
   }
   p->timer.end(s);
   for (int l = L - 1; l >= 0; --l) {
@@ -344,11 +340,12 @@ struct SolveRun {
   std::chrono::steady_clock::time_point t_loop;
   LmOptionsDev o;
   SolveArgs sa;
+  LinearRoute rt;      // what every linear solve of this call does
   hipStream_t s = nullptr;
   int n_blocks = 0, log_rows = 0;
   ResultSink sink = {};
   // the mode, decided once in begin(): the polled ("streaming") loop with its options, or the batched one
-  bool streaming = false, fold_first = false, predict_end = false;
+  bool streaming = false, fold_first = false, predict_end = false, multirank_async = true;
   int stream_depth = 0;
   // CALICO_SOLVE_TIMING=1: host time of the sections of this call and since the previous call returned (development aid)
   bool timing = false;
@@ -398,7 +395,8 @@ int SolveRun::begin() {
   // stream and leaves at most `depth` iterations of early-exit kernels behind a terminated solve. The stage that
   // terminates the solve writes the results (state, log, parameters) into pinned host memory itself, so the call
   // returns as soon as the flag is up: the early-exit kernels drain while the caller prepares its next call.
-  stream_depth = env_int("CALICO_STREAM_DEPTH", 2, 0);
+  const SolveSwitches sw;
+  stream_depth = sw.stream_depth; multirank_async = sw.multirank_async;
   // (the progress word carries the iteration count in 20 bits: budgets beyond that take the batched loop)
   streaming = p->speculative && !p->has_exchange() && stream_depth > 0 && p->h_progress != nullptr && opt->max_num_iterations <= 0xfffff;
   log_rows = std::min(kLogCap, std::max(0, opt->max_num_iterations) + 2);
@@ -422,6 +420,7 @@ int SolveRun::begin() {
   p->xc_stale = false;
   mark(1);
   sa = make_solve_args(p);
+  rt = linear_route(p, sa, sw);
   n_blocks = int(p->h_blocks.size());
   if (streaming) sa.progress = p->d_progress;
   // iteration 0
@@ -439,8 +438,8 @@ int SolveRun::begin() {
   // 40 us at configs[3], in front of the caller's next solve). With the end hint the Jacobian launch of iteration i says, from
   // what the linear solve left, whether iteration i's control stage will end the solve; iteration i + 1 is enqueued on its
   // "go" (progress word 2) -- the evaluation chain is still running then, so the device does not wait -- or, without one,
-  // once iteration i has ended without terminating (CALICO_PREDICT_END=0: always one iteration ahead, rounds 2-3).
-  predict_end = streaming && end_hint_available(p) && env_flag("CALICO_PREDICT_END", true);
+  // once iteration i has ended without terminating (SolveSwitches::predict_end off: always one iteration ahead).
+  predict_end = streaming && end_hint_available(p) && sw.predict_end;
   mark(2);
   return CALICO_OK;
 }
@@ -490,7 +489,7 @@ int SolveRun::polled_loop() {
       continue;
     }
     p->timer.begin(2, s);
-    enqueue_linear_solve(p, sa, o, /*with_post_eval=*/enq > 0 ? 1 : (fold_first ? 2 : 0), opt->jacobi_scaling);
+    enqueue_linear_solve(p, sa, rt, o, /*with_post_eval=*/enq > 0 ? 1 : (fold_first ? 2 : 0), opt->jacobi_scaling);
     p->timer.end(s);
     // the control stage rides in the last workgroup of the gather kernel
     ControlTail tail;
@@ -510,7 +509,7 @@ int SolveRun::polled_loop() {
 // batch rides in the prepare kernel of this one; `last` of a batch: it gets a stand-alone post_eval.
 int SolveRun::speculative_iteration(bool async, bool ride, bool last) {
   p->timer.begin(2, s);
-  enqueue_linear_solve(p, sa, o, ride, opt->jacobi_scaling);
+  enqueue_linear_solve(p, sa, rt, o, ride, opt->jacobi_scaling);
   p->timer.end(s);
   if (int rc = enqueue_jacobian_eval(p, p->d_state.p, 0, p->d_xc.p, true)) return rc;
   p->timer.begin(4, s);
@@ -524,7 +523,7 @@ int SolveRun::speculative_iteration(bool async, bool ride, bool last) {
 // (not async: the host reads the state back in between and decides; else the kernels do).
 int SolveRun::cost_first_iteration(bool async) {
   p->timer.begin(2, s);
-  enqueue_linear_solve(p, sa, o, 0, opt->jacobi_scaling);
+  enqueue_linear_solve(p, sa, rt, o, 0, opt->jacobi_scaling);
   p->timer.end(s);
   p->timer.begin(3, s);
   EvalArgs ea = make_eval_args(p, p->d_xc.p, 1, false);
@@ -558,7 +557,7 @@ int SolveRun::cost_first_iteration(bool async) {
 int SolveRun::batched_loop() {
   if (int rc = read_state(p)) return rc;
   const bool spec = p->speculative;
-  const bool async = !p->has_exchange() || (spec && env_flag("CALICO_MULTIRANK_ASYNC", true));
+  const bool async = !p->has_exchange() || (spec && multirank_async);
   const int batch = async ? std::max(1, opt->sync_every) : 1;
   while (!p->h_state->terminated) {
     // The iterations enqueued behind a terminated solve are wasted (with several ranks each still carries a real
@@ -683,13 +682,18 @@ int32_t calico_debug_plan_info(calico_problem* p, int32_t* out, int32_t n) {
   int rc = finalize(p);
   if (rc != CALICO_OK) return rc;
   const SolveArgs sa = make_solve_args(p);
-  const LinearRoute rt = linear_route(p, sa);
+  const LinearRoute rt = linear_route(p, sa, SolveSwitches{});
   const bool tree = p->use_bcr;
+  // the table entry of the first back-substitution behind the reduced solve, from what select_back / select_dense_back get
+  const bool back = tree && !p->bcr_levels.empty();
+  const int first_back_qm = back ? chain_variant(p->bcr_levels[size_t(rt.l_first)].q_max) : 0;
   const int v[kPlanInfoWords] = {p->fuse_expand ? 1 : 0, p->n_fitems, p->n_jac_items, p->n_cells, p->max_cell_frames, p->max_item_run,
                                  tree ? 1 : 0, p->m, p->bcr_all_active ? 1 : 0,
                                  tree ? p->bcr_N : 0, tree ? p->bcr_q0 : 0, tree ? int(p->bcr_levels.size()) : 0,
                                  tree && p->bcr_root >= 0 ? 1 : 0, rt.schur_rides ? 1 : 0, rt.ts.n, rt.fused ? 1 : 0,
-                                 rt.reduced, rt.reduced_in_lds ? 1 : 0, rt.ks, sa.m, p->sep_n};
+                                 rt.reduced, rt.reduced_in_lds ? 1 : 0, rt.ks, sa.m, p->sep_n,
+                                 rt.elim ? 1 : 0, rt.level0_roll ? 1 : 0, rt.dense_mode, rt.back_pre ? 1 : 0, rt.inline_nodes ? 1 : 0,
+                                 first_back_qm, back ? (rt.ts.n > 0 ? 2 : 1) : 0};
   for (int i = 0; i < n; ++i) out[i] = v[i];
   return CALICO_OK;
 }

@@ -1658,18 +1658,18 @@ int reduced_schur_slices(const SolveArgs& a) {
   return kSchurSlices;
 }
 // Dense solve of the (m+1)x(m+1) augmented reduced system in a.Spart (ks K-slices) -> a.y[n_s ...]
-void launch_dense_block_solve(const SolveArgs& a, int ks, hipStream_t s, int t0 = 0, int outer_back = 0);     // bcr_kernels.hip
+void launch_dense_block_solve(const SolveArgs& a, int ks, int dense_mode, hipStream_t s, int t0 = 0, int outer_back = 0);     // bcr_kernels.hip
 void launch_reduced_block_step(const SolveArgs& a, int j, int nsl, int n_wg, hipStream_t s);     // bcr_kernels.hip
 // Which kernel solves the reduced system (launch_reduced_solve; calico_debug_plan_info reports it)
 int reduced_solve_route(const SolveArgs& a) {
   if (a.m + 1 <= 128) return a.m >= 1 ? kReducedBlock : kReducedPanel;
   return reduced_is_blocked(a) ? kReducedBlocked : kReducedKernel;
 }
-void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipStream_t s) {
+void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, int dense_mode, hipStream_t s) {
   const int m1 = a.m + 1;
   const int route = reduced_solve_route(a);
   if (route == kReducedBlock) {
-    launch_dense_block_solve(a, ks, s);      // (ks <= 8, what the solver adds up on load: see reduced_schur_slices)
+    launch_dense_block_solve(a, ks, dense_mode, s);      // (ks <= 8, what the solver adds up on load: see reduced_schur_slices)
   } else if (route == kReducedPanel) {
     // a.m == 0 (nothing to calibrate): only the right-hand side's row, which the panel kernel takes
     const size_t lds = (size_t(m1) * ((16 * ((m1 + 15) / 16)) | 1) + m1 + 32 + 128 + 256) * sizeof(double);
@@ -1682,7 +1682,7 @@ void launch_reduced_solve(const SolveArgs& a, bool reduced_in_lds, int ks, hipSt
       const int rows = m1 - kRB * (j + 1), T = rows > 0 ? (rows + 63) / 64 : 0;
       launch_reduced_block_step(a, j, j == 0 ? ks : 1, T > 0 ? T * (T + 1) / 2 : 1, s);
     }
-    launch_dense_block_solve(a, 1, s, t0, 1);
+    launch_dense_block_solve(a, 1, dense_mode, s, t0, 1);
   } else {
     hipLaunchKernelGGL(reduced_solve_kernel, dim3(1), dim3(256), reduced_in_lds ? reduced_solve_lds_bytes(a) : 0, s, a,
                        reduced_in_lds ? 1 : 0);
@@ -1704,10 +1704,10 @@ void launch_band_reduction(const SolveArgs& a, const LmOptionsDev& o, const doub
   hipLaunchKernelGGL(schur_kernel, dim3(nt * (nt + 1) / 2 * ks), dim3(256), 0, s, a, ks);
 }
 void launch_solve(const SolveArgs& a, const LmOptionsDev& o, const double* x, double* x_cand, const BlockDev* blocks,
-                  int n_blocks, bool reduced_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi) {
+                  int n_blocks, bool reduced_in_lds, hipStream_t s, bool with_post_eval, IterLog* log, int log_cap, int jacobi, int dense_mode) {
   launch_band_reduction(a, o, x, blocks, n_blocks, s, with_post_eval, log, log_cap, jacobi);
   const int ks = reduced_schur_slices(a);
-  launch_reduced_solve(a, reduced_in_lds, ks, s);
+  launch_reduced_solve(a, reduced_in_lds, ks, dense_mode, s);
   hipLaunchKernelGGL(border_matvec_kernel, dim3((a.n_s() + 3) / 4), dim3(256), 0, s, a);
   const BandBackVariant* v = select_band_back(a.k);
   assert(v && "finalize takes spline orders 2 to 8");

@@ -3,7 +3,8 @@
 Every case builds a scene whose shape sends the solve down one route (tree solver: superblocks, chain length, levels, root,
 where the Schur complement and the top separators' back-substitution ride, the fused dense solve; banded solver with or
 without its separator; the reduced solve's kernel; Schur K-slices; ragged last superblocks; unobserved control points),
-asserts through plan_info() that it does, runs one LM iteration (or k of them) and holds the step the candidate update applied
+asserts through plan_info() that it does (the whole route: LinearRoute as calico_debug_plan_info reports it, down to the
+(QM, MODE, PRE) of the back-substitution's table entry and the forms the solve's switches select), runs one LM iteration (or k of them) and holds the step the candidate update applied
 (calico_debug_last_step) against tests/lm_step.py:
 
 - the Jacobi scale and the damping, restated from Ceres, to 1e-13;
@@ -89,7 +90,8 @@ def check_steps(hip, scene, expect, mu=1.0, jacobi=True, iters=(1,), lm_diag=Non
     info = P.plan_info()
     route = {k: info[k] for k in ("tree_solver", "m", "superblocks", "chain", "levels", "root", "schur_rides", "top_seps",
                                   "fused_back", "reduced_route", "reduced_in_lds", "schur_slices", "reduced_m", "sep_n",
-                                  "all_control_points_observed")}
+                                  "all_control_points_observed", "elim", "level0_roll", "dense_mode", "back_pre", "inline_nodes",
+                                  "first_back_qm", "first_back_mode")}
     for k, v in expect.items():
         assert info[k] == v, (label, k, info[k], v, route)
     cols = lm_step.column_blocks(built, scene)
@@ -204,9 +206,10 @@ CASES = {
     "order 3": dict(scene=dict(order=3), expect=dict(tree_solver=1)),
     "order 4": dict(scene=dict(order=4), expect=dict(tree_solver=1)),
     "order 5": dict(scene=dict(order=5), expect=dict(tree_solver=1)),
-    "order 7 (banded, split)": dict(scene=dict(n_cp=60, order=7), expect=dict(tree_solver=0, sep_n=6)),
-    "order 8 (banded, split)": dict(scene=dict(n_cp=60, order=8), expect=dict(tree_solver=0, sep_n=7)),
-    "order 7 (banded, no split)": dict(env=dict(CALICO_BAND_SPLIT="0"), scene=dict(n_cp=60, order=7), expect=dict(tree_solver=0, sep_n=0)),
+    "order 7 (banded, split)": dict(scene=dict(n_cp=60, order=7), expect=dict(tree_solver=0, sep_n=6, level0_roll=0)),
+    "order 8 (banded, split)": dict(scene=dict(n_cp=60, order=8), expect=dict(tree_solver=0, sep_n=7, level0_roll=0)),
+    "order 7 (banded, no split)": dict(env=dict(CALICO_BAND_SPLIT="0"), scene=dict(n_cp=60, order=7),
+                                       expect=dict(tree_solver=0, sep_n=0, level0_roll=0)),
     "order 6 banded, split": dict(env=dict(CALICO_SOLVER="band", CALICO_BAND_SPLIT="1"), scene=dict(), expect=dict(tree_solver=0, sep_n=5)),
     "order 6 banded, no split": dict(env=dict(CALICO_SOLVER="band", CALICO_BAND_SPLIT="0"), scene=dict(), expect=dict(tree_solver=0, sep_n=0)),
     # length: Schur K-slices
@@ -229,11 +232,19 @@ for _n in range(40, 45):       # ragged ends: n_cp mod 5 = 0 .. 4, orders 6 and 
 for _q in range(1, 9):         # chain lengths on 185 control points
     CASES["185 control points, chains of %d" % _q] = dict(env=dict(CALICO_BCR_LEAF=str(_q)), scene=dict(n_cp=185),
                                                           expect=dict(superblocks=37, chain=_q))
-# A/B switches of the tree solver on one two-level scene
-for _name, _v in (("CALICO_ROLL", "0"), ("CALICO_DENSE_ROLL", "0"), ("CALICO_FUSE_BACK", "0"), ("CALICO_BACK_PRE", "0"),
-                  ("CALICO_BACK_PRE", "1"), ("CALICO_ELIM", "panel"), ("CALICO_SPECULATIVE", "0"), ("CALICO_INLINE_NODES", "0")):
+# A/B switches of the tree solver on one two-level scene (14 superblocks = 3 * 4 + 2: chains of four, the top separator folded into
+# level 0's back-substitution, 61 reduced unknowns -- too few for the affine form to pay), each with the route words that prove its form
+for (_name, _v), _route in {
+        ("CALICO_ROLL", "0"): dict(level0_roll=0, elim=1, dense_mode=2),                      # bcr_level_kernel<true, true>
+        ("CALICO_DENSE_ROLL", "0"): dict(dense_mode=1, elim=1, level0_roll=1),
+        ("CALICO_FUSE_BACK", "0"): dict(fused_back=0, back_pre=0, first_back_qm=4, first_back_mode=2),      # bcr_back_kernel<4, 2>
+        ("CALICO_BACK_PRE", "0"): dict(fused_back=1, back_pre=0, first_back_qm=4, first_back_mode=2),       # dense_back_kernel<4, 2, false>
+        ("CALICO_BACK_PRE", "1"): dict(fused_back=1, back_pre=1, first_back_qm=4, first_back_mode=2),       # dense_back_kernel<4, 2, true>
+        ("CALICO_ELIM", "panel"): dict(elim=0, dense_mode=0, level0_roll=0),                  # bcr_level_kernel<.., false>
+        ("CALICO_SPECULATIVE", "0"): dict(elim=1, level0_roll=1, dense_mode=2, back_pre=0),
+        ("CALICO_INLINE_NODES", "0"): dict(inline_nodes=0)}.items():
     CASES["two levels, %s=%s" % (_name, _v)] = dict(env={"CALICO_BCR_LEAF": "4", _name: _v}, scene=dict(n_cp=70), iters=(1, 2),
-                                                    expect=dict(levels=2, fused_back=0 if _name == "CALICO_FUSE_BACK" else 1))
+                                                    expect=dict(dict(levels=2, top_seps=1, fused_back=1), **_route))
 
 # Every entry of the kernels' variant tables (dense_back_kernel<QM, MODE, PRE>, bcr_back_kernel<QM, MODE>, band_backsolve_kernel<K>)
 # that no case above reaches. A one-level tree of chains of q has q + 1 superblocks; a two-level one whose top separator is
@@ -245,7 +256,8 @@ for _q, _n_cp, _levels, _switch in (
         (2, 15, 1, "CALICO_FUSE_BACK=0"), (4, 25, 1, "CALICO_FUSE_BACK=0"), (2, 40, 2, "CALICO_FUSE_BACK=0")):   # bcr_back_kernel<QM, 1>, <2, 2>
     CASES["chains of %d, %d level(s), %s" % (_q, _levels, _switch or "fused")] = dict(
         env=dict([("CALICO_BCR_LEAF", str(_q))] + ([_switch.split("=")] if _switch else [])), scene=dict(n_cp=_n_cp),
-        expect=dict(levels=_levels, chain=_q, root=1, top_seps=_levels - 1, fused_back=0 if _switch == "CALICO_FUSE_BACK=0" else 1))
+        expect=dict(levels=_levels, chain=_q, root=1, top_seps=_levels - 1, fused_back=0 if _switch == "CALICO_FUSE_BACK=0" else 1,
+                    back_pre=1 if _switch == "CALICO_BACK_PRE=1" else 0, first_back_qm=_q, first_back_mode=_levels))
 for _k in (2, 3, 4, 5):
     CASES["order %d banded" % _k] = dict(env=dict(CALICO_SOLVER="band"), scene=dict(n_cp=25, order=_k), expect=dict(tree_solver=0))
 
@@ -256,7 +268,13 @@ def test_linear_step_matches_dense_solve(name, hip, monkeypatch):
     for k, v in c.get("env", {}).items():
         monkeypatch.setenv(k, v)
     scene = make_case_scene(**c.get("scene", {}))
-    check_steps(hip, scene, c.get("expect", {}), mu=c.get("mu", 1.0), jacobi=c.get("jacobi", True), iters=c.get("iters", (1,)),
+    # what a case does not say otherwise is the default route: elimination by blocks, rolling owners in the dense solve, and on
+    # the tree solver (every case that does not expect the banded one) level 0's rolling chief and inline node descriptors
+    expect = dict(c.get("expect", {}))
+    tree = expect.get("tree_solver", 1)
+    for k, v in dict(tree_solver=tree, elim=1, dense_mode=2, level0_roll=tree, inline_nodes=tree).items():
+        expect.setdefault(k, v)
+    check_steps(hip, scene, expect, mu=c.get("mu", 1.0), jacobi=c.get("jacobi", True), iters=c.get("iters", (1,)),
                 label=name, rejected_before=c.get("rejected_before"))
 
 

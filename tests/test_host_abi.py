@@ -62,6 +62,32 @@ def test_product_never_links_the_oracle(hiplib):
             assert "oracle/" not in src and "oracle_" not in src, f
 
 
+SOLVE_SWITCHES = {"CALICO_STREAM_DEPTH", "CALICO_PREDICT_END", "CALICO_MULTIRANK_ASYNC", "CALICO_INLINE_NODES", "CALICO_FUSE_BACK",
+                  "CALICO_BACK_PRE", "CALICO_ELIM", "CALICO_DENSE_ROLL", "CALICO_ROLL"}
+
+
+def test_switches_are_read_where_design_says():
+    """the switches the library reads are the rows of its table; the nine that shape a solve are read in one
+    place (SolveSwitches) and named nowhere else in the sources; no .hip file reads the environment."""
+    csrc = os.path.join(helpers.ROOT, "calico_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".cpp", ".hip", ".hpp", ".h"))}
+    read = set()
+    for src in sources.values():
+        read |= set(re.findall(r'\b(?:env_flag|env_int|env_is|getenv)\(\s*"(CALICO_[A-Z_]+)"', src))
+    design = open(os.path.join(helpers.ROOT, "DESIGN.md")).read()
+    rows = design[design.index("| Switch | Selects | Stays as |"):].split("\n\n")[0].splitlines()[2:]
+    cells = [r.split("|")[1] for r in rows]
+    table = set(n for c in cells for n in re.findall(r"`(CALICO_[A-Z_]+)", c))
+    assert len(table) >= 23
+    assert read == table, (sorted(read - table), sorted(table - read))
+    assert set(n for c in cells if "(solve)" in c for n in re.findall(r"`(CALICO_[A-Z_]+)", c)) == SOLVE_SWITCHES
+    for f, src in sources.items():
+        if f.endswith(".hip"):
+            assert not re.search(r"\b(env_flag|env_int|env_is|getenv)\b", src), f
+    for name in sorted(SOLVE_SWITCHES):
+        assert [f for f, src in sources.items() if re.search(r"\b%s\b" % name, src)] == ["problem_host.hpp"], name
+
+
 def test_shard_windows_partition_rule():
     """calico_amd/csrc/shard.hpp through the oracle's multi-rank emulation: every residual block is
     owned by exactly one rank, windows are contiguous in time and balanced."""
