@@ -435,6 +435,7 @@ class SensorSpec:
     stamps: Optional[np.ndarray] = None
     point_idx: Optional[np.ndarray] = None
     is_outlier: Optional[np.ndarray] = None   # ground-truth gross-outlier flags (synthetic)
+    body_idx: Optional[np.ndarray] = None     # cameras: rigid body of every observation (None: all body 0); point_idx counts inside it
 
     @property
     def dim(self):
@@ -443,6 +444,30 @@ class SensorSpec:
     @property
     def n(self):
         return 0 if self.stamps is None else len(self.stamps)
+
+
+@dataclass
+class BodySpec:
+    """One rigid body of the world model: its model points and T_world_rigidbody, start values and truth.
+    `seen_by` / `window` tell make_scene which cameras observe it (None: all) and in which time window (None: always)."""
+    points: np.ndarray
+    q: np.ndarray            # x,y,z,w
+    t: np.ndarray
+    pose_constant: bool = True
+    points_constant: object = True   # bool, or one flag per model point
+    q_true: Optional[np.ndarray] = None
+    t_true: Optional[np.ndarray] = None
+    points_true: Optional[np.ndarray] = None
+    seen_by: Optional[List[int]] = None
+    window: Optional[tuple] = None
+
+
+def rigid_body(points, t=(0.0, 0.0, 0.0), rotvec=(0.0, 0.0, 0.0), free_pose=False, free_points=False, seen_by=None, window=None):
+    """A further body for make_scene(extra_bodies=[...]) at its true pose. free_pose: the pose is estimated (it starts up to
+    1 cm off when the scene is perturbed); free_points: so are its model points, except three anchors."""
+    points = np.array(points, float)
+    q, t = quat_from_axis_angle(np.asarray(rotvec, float)), np.array(t, float)
+    return BodySpec(points.copy(), q.copy(), t.copy(), not free_pose, not free_points, q, t, points, seen_by, window)
 
 
 @dataclass
@@ -459,10 +484,19 @@ class Scene:
     sensors: List[SensorSpec] = field(default_factory=list)
     body_pose_constant: bool = True
     points_constant: object = True   # bool, or one flag per model point
+    extra_bodies: List[BodySpec] = field(default_factory=list)   # bodies 1, 2, ... (body 0 is the fields above)
+    # registration schedule: [(sensor index, first, last + 1)] -- one add_*_residuals call each, in this order, over the
+    # sensors' arrays as they stand (reorder() permutes those). None: one call per sensor, right behind its parameters.
+    calls: Optional[List[tuple]] = None
 
     @property
     def num_blocks(self):
         return sum(s.n for s in self.sensors)
+
+    @property
+    def bodies(self):
+        """Every rigid body, body 0 first, in one form."""
+        return [BodySpec(self.points, self.body_q, self.body_t, self.body_pose_constant, self.points_constant)] + list(self.extra_bodies)
 
 
 @dataclass
@@ -475,25 +509,50 @@ class BuiltProblem:
     gravity_block: int
     sensor_ids: List[int]
     sensor_blocks: List[dict]
+    bodies: List[dict] = field(default_factory=list)   # per body: id, point_blocks, q, t (body 0's are also the fields above)
+
+
+def body_indices(s):
+    """Rigid body of every observation of a camera sensor."""
+    return np.zeros(s.n, np.int32) if s.body_idx is None else np.asarray(s.body_idx, np.int32)
 
 
 def build_problem(api, scene, device=0, obs_slices=None):
     """Flatten a Scene through the C ABI, in BatchOptimizer::Optimize's order
     (batch_optimizer.cpp:57-70): world model, trajectory, then per sensor its
     parameters and residuals. `obs_slices[i]` optionally restricts sensor i to
-    a slice of its observations (multi-GPU sharding)."""
+    a slice of its observations (multi-GPU sharding). With `scene.calls` every
+    sensor's parameters come first and the residuals follow in that schedule."""
     P = _capi.Problem(api, device)
-    # WorldModel::AddParametersToProblem (world_model.cpp:40-77)
-    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (len(scene.points),))
-    point_blocks = P.add_param_blocks(np.asarray(scene.points, float), constant=pc)
-    bt = P.add_param_block(scene.body_t, constant=scene.body_pose_constant)
-    bq = P.add_param_block(scene.body_q, _capi.MANIFOLD_EIGEN_QUATERNION, scene.body_pose_constant)
+    # WorldModel::AddParametersToProblem (world_model.cpp:40-77): per rigid body its model points, then its pose; gravity last
+    bodies = []
+    for b in scene.bodies:
+        pc = np.broadcast_to(np.asarray(b.points_constant, bool), (len(b.points),))
+        pb = P.add_param_blocks(np.asarray(b.points, float), constant=pc)
+        bt = P.add_param_block(b.t, constant=b.pose_constant)
+        bq = P.add_param_block(b.q, _capi.MANIFOLD_EIGEN_QUATERNION, b.pose_constant)
+        bodies.append(dict(point_blocks=pb, q=bq, t=bt))
     grav = P.add_param_block(scene.gravity, constant=True)  # Q6: gravity can never be enabled
-    body = P.add_rigid_body(bq, bt)
+    for b in bodies:
+        b["id"] = P.add_rigid_body(b["q"], b["t"])
+    body_ids = np.array([b["id"] for b in bodies], np.int32)
+    point_base = np.cumsum([0] + [len(b["point_blocks"]) for b in bodies])
+    all_points = np.concatenate([np.asarray(b["point_blocks"], np.int32) for b in bodies])
     # Trajectory::AddParametersToProblem (bspline.hpp:10-17)
     ctrl_blocks = P.add_param_blocks(np.asarray(scene.ctrl, float))
     P.set_spline(scene.order, scene.knots, scene.basis, ctrl_blocks)
     sids, sblocks = [], []
+
+    def add_residuals(i, sl):
+        s, sid = scene.sensors[i], sids[i]
+        if s.kind == _capi.SENSOR_CAMERA:
+            bi = body_indices(s)[sl]
+            P.add_camera_residuals(sid, s.meas[sl], s.stamps[sl], body_ids[bi], all_points[point_base[bi] + s.point_idx[sl]])
+        else:
+            P.add_imu_residuals(sid, s.meas[sl], s.stamps[sl])
+
+    if scene.calls is not None and obs_slices is not None:
+        raise ValueError("obs_slices and a registration schedule (scene.calls) exclude each other")
     for i, s in enumerate(scene.sensors):
         # Sensor::AddParametersToProblem (camera.cpp:92-113)
         bi = P.add_param_block(s.intrinsics, constant=not s.enable_intrinsics)
@@ -502,16 +561,45 @@ def build_problem(api, scene, device=0, obs_slices=None):
         bl = P.add_param_block([s.latency], constant=not s.enable_latency)
         sid = P.add_sensor(s.kind, s.model, bi, bQ, bT, bl,
                            grav if s.kind == _capi.SENSOR_ACCELEROMETER else -1, s.sigma, s.loss, s.loss_scale)
-        sl = slice(None) if obs_slices is None else obs_slices[i]
-        if s.n:
-            if s.kind == _capi.SENSOR_CAMERA:
-                P.add_camera_residuals(sid, s.meas[sl], s.stamps[sl], np.full(len(s.stamps[sl]), body, np.int32),
-                                       point_blocks[s.point_idx[sl]])
-            else:
-                P.add_imu_residuals(sid, s.meas[sl], s.stamps[sl])
         sids.append(sid)
         sblocks.append(dict(intrinsics=bi, t=bT, q=bQ, latency=bl))
-    return BuiltProblem(P, ctrl_blocks, point_blocks, bq, bt, grav, sids, sblocks)
+        if s.n and scene.calls is None:
+            add_residuals(i, slice(None) if obs_slices is None else obs_slices[i])
+    for i, lo, hi in scene.calls or []:
+        if hi > lo:
+            add_residuals(i, slice(lo, hi))
+    return BuiltProblem(P, ctrl_blocks, bodies[0]["point_blocks"], bodies[0]["q"], bodies[0]["t"], grav, sids, sblocks, bodies)
+
+
+def reorder(scene, perms=None, calls=None):
+    """A copy of the scene whose sensors' observations are registered in another order: `perms[i]` (None: as is) permutes
+    sensor i's arrays -- residuals, masks and Jacobian rows of the built problem then follow that order --, `calls` is the
+    registration schedule (Scene.calls) over the permuted arrays."""
+    import copy
+    out = copy.deepcopy(scene)
+    for s, perm in zip(out.sensors, perms or []):
+        if perm is None:
+            continue
+        perm = np.asarray(perm)
+        assert np.array_equal(np.sort(perm), np.arange(s.n))
+        for name in ("meas", "stamps", "point_idx", "body_idx", "is_outlier"):
+            a = getattr(s, name)
+            if a is not None:
+                setattr(s, name, np.ascontiguousarray(a[perm]))
+    if calls is not None:
+        n_in = [0] * len(out.sensors)
+        for i, lo, hi in calls:
+            assert lo == n_in[i] and hi >= lo, "a sensor's calls must walk its observations front to back"
+            n_in[i] = hi
+        assert n_in == [s.n for s in out.sensors], "the schedule must register every observation once"
+        out.calls = [tuple(int(v) for v in c) for c in calls]
+    return out
+
+
+def interleaved_calls(scene, parts=3):
+    """A schedule of `parts` calls per sensor, round robin across the sensors."""
+    cuts = [np.linspace(0, s.n, parts + 1).astype(int) for s in scene.sensors]
+    return [(i, int(c[k]), int(c[k + 1])) for k in range(parts) for i, c in enumerate(cuts)]
 
 
 def read_back(built, scene):
@@ -524,6 +612,14 @@ def read_back(built, scene):
                         latency=P.get_param_block(b["latency"], 1)[0]))
     ctrl = P.get_param_blocks(np.asarray(built.ctrl_blocks, np.int32), 6).reshape(-1, 6)
     return out, ctrl
+
+
+def read_back_bodies(built, scene):
+    """Current estimates of every rigid body: its pose and its model points."""
+    P = built.problem
+    return [dict(q=P.get_param_block(b["q"], 4), t=P.get_param_block(b["t"], 3),
+                 points=P.get_param_blocks(np.asarray(b["point_blocks"], np.int32), 3).reshape(-1, 3))
+            for b in built.bodies]
 
 
 # ----------------------------------------------------------------------------
@@ -563,12 +659,17 @@ def _initial_intrinsics(kind, model, truth):
 def make_scene(n_cameras=1, camera_model=1, imu=False, imu_model=2, duration=None, cam_rate=None, imu_rate=None,
                knot_frequency=10.0, order=6, chart="plane", pixel_noise=0.0, gyro_noise=0.0, accel_noise=0.0,
                seed=0xCA11C0, robust=False, outlier_fraction=0.0, perturb=True, estimate_spline_from_truth=True,
-               max_cam_obs=None, segment_duration=0.75, repeats=1, free_chart_pose=False, free_points=False, n_imus=1):
+               max_cam_obs=None, segment_duration=0.75, repeats=1, free_chart_pose=False, free_points=False, n_imus=1,
+               extra_bodies=None):
     """Synthetic rig problem in the style of ToyStereoCameraAndImuCalibration
     (batch_optimizer_test.cpp:32-213): camera 0 is the rig frame with free
     intrinsics; further cameras also estimate extrinsics + latency; the IMU
     sensors estimate intrinsics, rotation (+ lever arm for the accelerometer)
-    and latency. Measurements come from the fitted spline (the truth)."""
+    and latency. Measurements come from the fitted spline (the truth).
+    `camera_model`: one model for every camera, or one per camera. `extra_bodies`: further rigid bodies (rigid_body());
+    every camera registers body 0's observations first, then body 1's, ... (each in time order). Their noise comes from a
+    generator of its own, so the rest of the scene is what it is without them."""
+    models = [int(m) for m in np.broadcast_to(np.asarray(camera_model), (n_cameras,))]
     rng = np.random.default_rng(seed)
     stamps, quats, trans = default_synthetic_poses(segment_duration=segment_duration, repeats=repeats)
     knots, basis, ctrl_true = fit_trajectory(stamps, quats, trans, knot_frequency, order)
@@ -593,6 +694,7 @@ def make_scene(n_cameras=1, camera_model=1, imu=False, imu_model=2, duration=Non
         cam_times = np.arange(0.0, t_end + 1e-12, 1.0 / cam_rate)
     cam_times = cam_times[cam_times + max_lat <= last_valid]
     for c in range(n_cameras):
+        camera_model = models[c]
         truth = _TRUE_INTRINSICS[camera_model].copy()
         if c == 0:
             q_true, t_true, lat_true = np.array([0.0, 0, 0, 1.0]), np.zeros(3), 0.0
@@ -652,18 +754,53 @@ def make_scene(n_cameras=1, camera_model=1, imu=False, imu_model=2, duration=Non
     points_constant = True
     points_init = points
     if free_points:
-        # model_definition_is_constant = false (world_model.cpp:52-61). Three non-collinear anchor points stay fixed
-        # so that the chart keeps its gauge; the others start a few millimetres off.
-        p0 = points[0]
-        i1 = int(np.argmax(np.linalg.norm(points - p0, axis=1)))
-        d = (points[i1] - p0) / np.linalg.norm(points[i1] - p0)
-        off = (points - p0) - np.outer((points - p0) @ d, d)
-        i2 = int(np.argmax(np.linalg.norm(off, axis=1)))
-        points_constant = np.zeros(len(points), bool)
-        points_constant[[0, i1, i2]] = True
-        points_init = points + np.where(points_constant[:, None], 0.0, 2e-3 * rng.standard_normal(points.shape))
+        points_constant, points_init = _free_model_points(points, rng)
+    # ---- further rigid bodies: appended to every camera that sees them, body by body ----
+    bodies = []
+    rng_b = np.random.default_rng([int(seed), 0xB0D1E5])
+    for bi, b in enumerate(extra_bodies or [], start=1):
+        import copy
+        b = copy.deepcopy(b)
+        for c, s in enumerate(sensors[:n_cameras]):
+            if s.body_idx is None:
+                s.body_idx = np.zeros(s.n, np.int32)
+            if b.seen_by is not None and c not in b.seen_by:
+                continue
+            tt = cam_times if b.window is None else cam_times[(cam_times >= b.window[0]) & (cam_times <= b.window[1])]
+            px, valid, st, frame, pidx = project_camera(spl, s.model, s.intrinsics_true, s.q_true, s.t_true, s.latency_true, tt,
+                                                        b.points_true, b.q_true, b.t_true)
+            px, st, pidx = px[valid], st[valid], pidx[valid]
+            is_out = np.zeros(len(st), bool)
+            if pixel_noise > 0:
+                px = px + pixel_noise * rng_b.standard_normal(px.shape)
+            if outlier_fraction > 0:
+                is_out = rng_b.random(len(st)) < outlier_fraction
+                mag = rng_b.uniform(5.0, 50.0, (len(st), 1)) * np.sign(rng_b.standard_normal((len(st), 2)))
+                px = np.where(is_out[:, None], px + mag, px)
+            s.meas, s.stamps = np.concatenate([s.meas, px]), np.concatenate([s.stamps, st])
+            s.point_idx = np.concatenate([s.point_idx, pidx.astype(np.int32)])
+            s.body_idx = np.concatenate([s.body_idx, np.full(len(st), bi, np.int32)])
+            s.is_outlier = np.concatenate([s.is_outlier, is_out])
+        if perturb and not b.pose_constant:
+            b.t = b.t_true + 0.01 * rng_b.uniform(-1, 1, 3)
+        if np.ndim(b.points_constant) == 0 and not b.points_constant:
+            b.points_constant, b.points = _free_model_points(b.points_true, rng_b)
+        bodies.append(b)
     return Scene(order, knots, basis, ctrl_true.copy(), ctrl_true, points_init, body_q, body_t, gravity, sensors,
-                 body_pose_constant=not free_chart_pose, points_constant=points_constant)
+                 body_pose_constant=not free_chart_pose, points_constant=points_constant, extra_bodies=bodies)
+
+
+def _free_model_points(points, rng):
+    """model_definition_is_constant = false (world_model.cpp:52-61). Three non-collinear anchor points stay fixed
+    so that the chart keeps its gauge; the others start a few millimetres off. Returns (constant flags, start values)."""
+    p0 = points[0]
+    i1 = int(np.argmax(np.linalg.norm(points - p0, axis=1)))
+    d = (points[i1] - p0) / np.linalg.norm(points[i1] - p0)
+    off = (points - p0) - np.outer((points - p0) @ d, d)
+    i2 = int(np.argmax(np.linalg.norm(off, axis=1)))
+    points_constant = np.zeros(len(points), bool)
+    points_constant[[0, i1, i2]] = True
+    return points_constant, points + np.where(points_constant[:, None], 0.0, 2e-3 * rng.standard_normal(points.shape))
 
 
 def config_scene(index, seed=None):

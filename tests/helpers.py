@@ -96,12 +96,15 @@ def border_layout(built, scene):
     free blocks a residual uses, control points excluded, in block-id order (the order calico_num_effective_parameters
     documents)."""
     import numpy as np
+    from calico_amd import synthetic as syn
     free, used = {}, set()
-    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (len(scene.points),))
-    for b, c in zip(built.point_blocks, pc):
-        free[int(b)] = (not c, 3)
-    free[built.body_t_block] = (not scene.body_pose_constant, 3)
-    free[built.body_q_block] = (not scene.body_pose_constant, 3)
+    bodies = built.bodies      # (body 0 first; a scene without further bodies has just that one)
+    for spec, b in zip(scene.bodies, bodies):
+        pc = np.broadcast_to(np.asarray(spec.points_constant, bool), (len(spec.points),))
+        for blk, c in zip(b["point_blocks"], pc):
+            free[int(blk)] = (not c, 3)
+        free[b["t"]] = (not spec.pose_constant, 3)
+        free[b["q"]] = (not spec.pose_constant, 3)
     free[built.gravity_block] = (False, 3)
     for s, b in zip(scene.sensors, built.sensor_blocks):
         free[b["intrinsics"]] = (s.enable_intrinsics, len(s.intrinsics))
@@ -111,8 +114,10 @@ def border_layout(built, scene):
         if s.n:
             used.update([b["intrinsics"], b["t"], b["q"], b["latency"]])
             if s.kind == _capi.SENSOR_CAMERA:
-                used.update(int(built.point_blocks[i]) for i in np.unique(s.point_idx))
-                used.update([built.body_t_block, built.body_q_block])
+                which = syn.body_indices(s)
+                for k in np.unique(which):
+                    used.update(int(bodies[k]["point_blocks"][i]) for i in np.unique(s.point_idx[which == k]))
+                    used.update([bodies[k]["t"], bodies[k]["q"]])
     out, off = {}, 0
     for b in sorted(free):
         if free[b][0] and b in used:

@@ -148,19 +148,23 @@ def control_points_observed(scene):
 def column_blocks(built, scene):
     """[(block id, manifold)] in calico_evaluate's column order: the observed control points, then the free blocks that
     some residual uses, in the order they were added (Problem's tangent order)."""
+    from calico_amd import synthetic as syn
     quat = MANIFOLD_EIGEN_QUATERNION
     cols = [(int(b), MANIFOLD_EUCLIDEAN) for b, a in zip(built.ctrl_blocks, control_points_observed(scene)) if a]
-    n_pts = len(scene.points)
-    pc = np.broadcast_to(np.asarray(scene.points_constant, bool), (n_pts,))
-    seen = np.zeros(n_pts, bool)
-    cams = False
-    for s in scene.sensors:
-        if s.kind == 0 and s.n:
-            seen[np.asarray(s.point_idx)] = True
-            cams = True
-    calib = [(int(built.point_blocks[i]), MANIFOLD_EUCLIDEAN) for i in range(n_pts) if seen[i] and not pc[i]]
-    if cams and not scene.body_pose_constant:
-        calib += [(built.body_t_block, MANIFOLD_EUCLIDEAN), (built.body_q_block, quat)]
+    calib = []
+    for k, (spec, b) in enumerate(zip(scene.bodies, built.bodies)):      # (body 0 first; most scenes have just that one)
+        n_pts = len(spec.points)
+        pc = np.broadcast_to(np.asarray(spec.points_constant, bool), (n_pts,))
+        seen = np.zeros(n_pts, bool)
+        cams = False
+        for s in scene.sensors:
+            if s.kind == 0 and s.n:
+                mine = syn.body_indices(s) == k
+                seen[np.asarray(s.point_idx)[mine]] = True
+                cams = cams or bool(mine.any())
+        calib += [(int(b["point_blocks"][i]), MANIFOLD_EUCLIDEAN) for i in range(n_pts) if seen[i] and not pc[i]]
+        if cams and not spec.pose_constant:
+            calib += [(b["t"], MANIFOLD_EUCLIDEAN), (b["q"], quat)]
     for s, b in zip(scene.sensors, built.sensor_blocks):
         if not s.n:
             continue
