@@ -6,6 +6,9 @@
 // contiguous segment ranges balanced by block count. A rank then touches only
 // the control points of its window (+ k-1 halo points), so its contribution
 // to the banded part of the normal equations is local.
+// A window may be EMPTY (the rank then evaluates nothing and adds zeros to
+// every exchange): cuts fall on segment boundaries, so several coincide when
+// one segment holds more than 1/world of the blocks or ranks outnumber segments.
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -79,6 +79,7 @@ struct Sensor {
   std::vector<double> meas;    // n×dim
   std::vector<double> stamps;  // n
   std::vector<int> body, point, seg;
+  std::vector<uint8_t> tagged;  // per observation: tagged as an outlier, left out of the problem (empty: none)
   int dim() const { return kind == CALICO_SENSOR_CAMERA ? 2 : 3; }
   int64_t n() const { return int64_t(stamps.size()); }
 };
@@ -221,6 +222,9 @@ static void BuildReduced(Problem& P) {
     for (size_t b = 0; b < P.rblocks.size(); ++b) {
       const int sg = P.sensors[P.rblocks[b].sensor].seg[P.rblocks[b].obs];
       P.own[b] = (sg >= win[size_t(P.rank)] && sg < win[size_t(P.rank) + 1]) ? 1 : 0;
+      // a tagged outlier keeps its place in the windows' counts and in the column layout; it contributes nothing
+      const std::vector<uint8_t>& tg = P.sensors[P.rblocks[b].sensor].tagged;
+      if (size_t(P.rblocks[b].obs) < tg.size() && tg[size_t(P.rblocks[b].obs)]) P.own[b] = 0;   // (observations added after the mask: in)
     }
   }
   P.reduced_blocks.clear();
@@ -934,6 +938,13 @@ int32_t oracle_get_solve_timing(Problem* p, double* out3) {
 int32_t oracle_problem_set_shard(Problem* p, int32_t rank, int32_t world) {
   if (world < 1 || rank < 0 || rank >= world) return p->set_error(CALICO_INVALID_ARGUMENT, "bad rank / world size");
   p->rank = rank; p->world = world; return CALICO_OK;
+}
+// MarkOutliersById / ClearOutliers for evaluate and solve: one byte per observation of the sensor, nullptr clears
+int32_t oracle_problem_set_outlier_mask(Problem* p, int32_t sid, const uint8_t* is_outlier) {
+  if (sid < 0 || sid >= int(p->sensors.size())) return p->set_error(CALICO_INVALID_ARGUMENT, "bad sensor id");
+  oracle::Sensor& s = p->sensors[sid];
+  if (is_outlier) s.tagged.assign(is_outlier, is_outlier + s.n()); else s.tagged.clear();
+  return CALICO_OK;
 }
 // host-buffer all-reduce (sum) callback: fn(ctx, buf, n)
 int32_t oracle_problem_set_allreduce(Problem* p, int32_t (*fn)(void*, double*, int64_t), void* ctx) {

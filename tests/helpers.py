@@ -132,12 +132,59 @@ class _DevArray:
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2}
 
 
-def run_two_ranks(api, scene, values, per_rank, world=2):
-    """Two ranks on one device: each a handle built from `scene` with the parameter values `values` ({block id: values})
-    installed, sharded to its time window (calico_problem_set_shard) with a host exchange (sum in rank order).
-    per_rank(built) runs in a thread per rank; returns the list of its results, rank by rank. Fails with the errors
-    collected from the exchange and the threads."""
+def _run_rank_threads(ranks, per_rank, install, read, write):
+    """The harness of run_ranks and run_oracle_ranks: one thread per handle of `ranks` runs per_rank(built); their exchange
+    callbacks (made here, installed with install(built, callback)) meet at a barrier, sum what read(*args) gives in rank
+    order and hand the total to write(*args, total). Every wait has a limit, and an error in one rank aborts the barrier so
+    that the others fail at once. Returns (results rank by rank, exchanges of every rank)."""
     import threading
+    world = len(ranks)
+    meet = threading.Barrier(world, timeout=120)
+    staged = [None] * world
+    results, errors = [None] * world, []
+    n_calls = [0] * world
+
+    def make_allreduce(rank):
+        def allreduce(ctx, *args):
+            try:
+                n_calls[rank] += 1
+                staged[rank] = read(*args)
+                meet.wait()
+                total = staged[0].copy()
+                for k in range(1, world):
+                    total += staged[k]
+                meet.wait()
+                write(*args, total)
+                return 0
+            except Exception as e:      # noqa: BLE001 (an exception must not unwind through the C frames)
+                errors.append(repr(e))
+                meet.abort()
+                return 1
+        return allreduce
+
+    for r, b in enumerate(ranks):
+        install(b, make_allreduce(r))
+
+    def run(r):
+        try:
+            results[r] = per_rank(ranks[r])
+        except Exception as e:      # noqa: BLE001
+            errors.append(repr(e))
+            meet.abort()
+    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=180)
+    assert not errors, errors
+    assert not any(t.is_alive() for t in th), "a rank did not finish in time"
+    return results, n_calls
+
+
+def run_ranks_counting(api, scene, values, per_rank, world=2):
+    """`world` ranks on one device: each a handle built from `scene` with the parameter values `values` ({block id: values})
+    installed, sharded to its time window (calico_problem_set_shard) with a host exchange (sum in rank order).
+    per_rank(built) runs in a thread per rank. Returns (its results rank by rank, the number of exchanges of every rank)."""
     import torch
     from calico_amd import synthetic as syn
     ranks = []
@@ -147,45 +194,47 @@ def run_two_ranks(api, scene, values, per_rank, world=2):
             b.problem.set_param_block(blk, v)
         b.problem.set_shard(r, world)
         ranks.append(b)
-    meet = threading.Barrier(world, timeout=120)
-    staged = [None] * world
-    results, errors = [None] * world, []
 
-    def make_allreduce(rank):
-        def allreduce(ctx, buf, n, strm):
-            try:
-                torch.cuda.ExternalStream(strm).synchronize()
-                t = torch.as_tensor(_DevArray(buf, n), device="cuda")
-                staged[rank] = t.cpu().numpy().copy()
-                meet.wait()
-                total = staged[0].copy()
-                for k in range(1, world):
-                    total += staged[k]
-                meet.wait()
-                t.copy_(torch.from_numpy(total).cuda())
-                torch.cuda.synchronize()
-                return 0
-            except Exception as e:      # noqa: BLE001
-                errors.append(repr(e))
-                meet.abort()
-                return 1
-        return allreduce
+    def read(buf, n, strm):
+        torch.cuda.ExternalStream(strm).synchronize()
+        return torch.as_tensor(_DevArray(buf, n), device="cuda").cpu().numpy().copy()
 
-    for r, b in enumerate(ranks):
-        b.problem.set_allreduce(make_allreduce(r))
+    def write(buf, n, strm, total):
+        torch.as_tensor(_DevArray(buf, n), device="cuda").copy_(torch.from_numpy(total).cuda())
+        torch.cuda.synchronize()
+    return _run_rank_threads(ranks, per_rank, lambda b, cb: b.problem.set_allreduce(cb), read, write)
 
-    def run(r):
-        try:
-            results[r] = per_rank(ranks[r])
-        except Exception as e:      # noqa: BLE001
-            errors.append(repr(e))
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=180)
-    assert not errors, errors
-    return results
+
+def run_ranks(api, scene, values, per_rank, world=2):
+    """run_ranks_counting's results alone."""
+    return run_ranks_counting(api, scene, values, per_rank, world)[0]
+
+
+run_two_ranks = run_ranks      # (the name the two-rank tests use)
+
+
+def run_oracle_ranks(scene, per_rank, world):
+    """run_ranks on the CPU oracle: `world` handles of `scene`, each sharded to its window (oracle_problem_set_shard), with the
+    oracle's host all-reduce summing in rank order; per_rank(built) runs in a thread per rank. Returns its results rank by rank."""
+    import numpy as np
+    from calico_amd import synthetic as syn
+    oracle = oracle_api()
+    fn_t = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
+    set_allreduce = oracle.lib.oracle_problem_set_allreduce
+    set_allreduce.argtypes, set_allreduce.restype = [C.c_void_p, fn_t, C.c_void_p], C.c_int32
+    ranks, keep = [], []
+    for r in range(world):
+        b = syn.build_problem(oracle, scene)
+        assert oracle.lib.oracle_problem_set_shard(b.problem.h, r, world) == 0
+        ranks.append(b)
+
+    def install(b, callback):
+        keep.append(fn_t(callback))
+        assert set_allreduce(b.problem.h, keep[-1], None) == 0
+
+    def write(buf, n, total):
+        np.ctypeslib.as_array(buf, shape=(n,))[:] = total
+    return _run_rank_threads(ranks, per_rank, install, lambda buf, n: np.ctypeslib.as_array(buf, shape=(n,)).copy(), write)[0]
 
 
 def kernel_resources(source):

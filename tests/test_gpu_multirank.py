@@ -21,10 +21,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _scene():
+def _scene(**more):
     from calico_amd import synthetic as syn
     return syn.make_scene(2, 1, True, 2, cam_rate=10.0, imu_rate=50.0, duration=3.0, segment_duration=3.0 / 23.9,
-                          pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=True, seed=3)
+                          pixel_noise=0.1, gyro_noise=1e-3, accel_noise=1e-2, robust=True, seed=3, **more)
 
 
 def _solve(P, api, sync_every):
