@@ -15,6 +15,8 @@ OK, INVALID_ARGUMENT, FAILED_PRECONDITION, UNIMPLEMENTED, INTERNAL = 0, 3, 9, 12
 MANIFOLD_EUCLIDEAN, MANIFOLD_EIGEN_QUATERNION = 0, 1
 SENSOR_CAMERA, SENSOR_GYROSCOPE, SENSOR_ACCELEROMETER = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
+FRAME_CAMERA, FRAME_RIG = 0, 1
+CAMERA_NUM_PARAMS = {1: 8, 2: 11, 3: 7, 4: 5, 5: 4, 6: 4, 7: 5}      # sensors::CameraIntrinsicsModel -> intrinsics count
 
 
 class SolverOptions(C.Structure):
@@ -142,10 +144,11 @@ ABI_SYMBOLS = [
     "default_prediction_options", "prediction_covariance",
     "default_observability_options", "observability_compute", "observability_info", "observability_get_spectrum",
     "observability_get_directions", "observability_get_block", "observability_get_matrix",
+    "camera_unproject", "camera_project_points", "sensor_unproject", "projection_uncertainty",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
-                "debug_lds_attribute_calls"]
+                "debug_lds_attribute_calls", "debug_camera_unproject_chunked"]
 
 
 class CApi:
@@ -217,6 +220,13 @@ class CApi:
             g("observability_get_directions", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D])
             g("observability_get_block", C.c_int32, [P, C.c_int32, C.c_int32, C.c_int32, D, D])
             g("observability_get_matrix", C.c_int32, [P, D])
+            U8 = C.POINTER(C.c_uint8)
+            if hasattr(self.lib, self.prefix + "camera_unproject"):      # (as the debug hooks below: not in a library of an older round)
+                g("camera_unproject", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, C.c_int64, D, D, U8])
+                g("camera_project_points", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, C.c_int64, D, D, U8, D, D])
+                g("sensor_unproject", C.c_int32, [P, C.c_int32, C.c_int64, D, D, U8])
+                g("projection_uncertainty", C.c_int32, [P, C.c_int32, C.c_int32, C.c_double, C.c_int64, D, D, U8])
+                g("debug_camera_unproject_chunked", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, C.c_int64, D, D, U8, C.c_int64])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -254,6 +264,45 @@ def comm_unique_id(api):
     if st != OK:
         raise CalicoError(st, "calico_comm_get_unique_id failed")
     return bytes(buf)
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _check_free(api, st):
+    """Status of a call without a handle: its message is the calling thread's (calico_last_error(NULL))."""
+    if st != OK:
+        raise CalicoError(st, api.last_error(None).decode())
+
+
+def camera_unproject(api, model, intrinsics, pixels, device=0, chunk=None):
+    """calico_camera_unproject: pixels (n, 2) -> (unit-norm points (n, 3), valid (n,) bool) under the model's projection at
+    `intrinsics`, on the device. Invalid pixels come back as zeros. chunk: test hook (pixels per host-side pass)."""
+    k, px = _f64(intrinsics).ravel(), _f64(pixels).reshape(-1, 2)
+    n = len(px)
+    out, valid = np.zeros((n, 3)), np.zeros(max(n, 1), dtype=np.uint8)
+    if chunk is None:
+        st = api.camera_unproject(int(device), int(model), _dp(k), k.size, n, _dp(px), _dp(out), _u8p(valid))
+    else:
+        st = api.debug_camera_unproject_chunked(int(device), int(model), _dp(k), k.size, n, _dp(px), _dp(out), _u8p(valid), int(chunk))
+    _check_free(api, st)
+    return out, valid[:n].astype(bool)
+
+
+def camera_project_points(api, model, intrinsics, points, jacobians=False, device=0):
+    """calico_camera_project_points: camera-frame points (n, 3) -> (pixels (n, 2), valid (n,) bool), and with jacobians=True
+    also d pixel / d point (n, 2, 3) and d pixel / d intrinsics (n, 2, K)."""
+    k, pt = _f64(intrinsics).ravel(), _f64(points).reshape(-1, 3)
+    n = len(pt)
+    px, valid = np.zeros((n, 2)), np.zeros(max(n, 1), dtype=np.uint8)
+    dp = np.zeros((n, 2, 3)) if jacobians else None
+    dk = np.zeros((n, 2, k.size)) if jacobians else None
+    _check_free(api, api.camera_project_points(int(device), int(model), _dp(k), k.size, n, _dp(pt), _dp(px), _u8p(valid),
+                                               _dp(dp) if jacobians else None, _dp(dk) if jacobians else None))
+    if jacobians:
+        return px, valid[:n].astype(bool), dp, dk
+    return px, valid[:n].astype(bool)
 
 
 class Problem:
@@ -497,6 +546,24 @@ class Problem:
         self._check(self.api.prediction_covariance(self.h, int(sensor), C.byref(o), _dp(cov), _dp(lev),
                                                    valid.ctypes.data_as(C.POINTER(C.c_uint8))))
         return cov, lev, valid[:n].astype(bool)
+
+    def sensor_unproject(self, sensor, pixels):
+        """calico_sensor_unproject: camera_unproject at the camera's current intrinsics, on the handle's stream."""
+        px = _f64(pixels).reshape(-1, 2)
+        n = len(px)
+        out, valid = np.zeros((n, 3)), np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.api.sensor_unproject(self.h, int(sensor), n, _dp(px), _dp(out), _u8p(valid)))
+        return out, valid[:n].astype(bool)
+
+    def projection_uncertainty(self, sensor, pixels, range=1.0, frame=FRAME_RIG):
+        """calico_projection_uncertainty: ([s_uu, s_uv, s_vv] (n, 3) in pixels^2, valid (n,) bool) of a point `range` metres
+        along each pixel's ray, fixed in the camera frame (FRAME_CAMERA: intrinsics only) or in the sensor-rig frame
+        (FRAME_RIG: intrinsics and extrinsics). Needs covariance_compute."""
+        px = _f64(pixels).reshape(-1, 2)
+        n = len(px)
+        out, valid = np.zeros((n, 3)), np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.api.projection_uncertainty(self.h, int(sensor), int(frame), float(range), n, _dp(px), _dp(out), _u8p(valid)))
+        return out, valid[:n].astype(bool)
 
     def covariance_block(self, block_a, block_b, tangent=False, sizes=None):
         """Block (block_a, block_b) of the last computed Σ. `sizes`: (rows, cols) of the requested form; by default taken

@@ -194,7 +194,10 @@ void calico_problem_destroy(calico_problem* p) {
 int32_t calico_plan_cache_stats(int64_t* hits, int64_t* misses, int64_t* entries) { plan_cache_stats(hits, misses, entries); return CALICO_OK; }
 int32_t calico_plan_cache_clear(void) { plan_cache_clear(); return CALICO_OK; }
 
-const char* calico_last_error(const calico_problem* p) { return p ? p->error.c_str() : "null problem"; }
+const char* calico_last_error(const calico_problem* p) {
+  if (p) return p->error.c_str();
+  return handle_free_error().empty() ? "null problem" : handle_free_error().c_str();
+}
 
 void calico_default_solver_options(calico_solver_options* o) {
   // DefaultSolverOptions() (batch_optimizer.cpp:10-17) over Ceres' Solver::Options defaults.

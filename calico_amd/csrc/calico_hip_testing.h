@@ -65,6 +65,11 @@ int32_t calico_debug_observability_info(calico_problem* problem, double* out, in
  * grows only when a handle or an analysis needs more than its device already allows some kernel. */
 int64_t calico_debug_lds_attribute_calls(void);
 
+/* calico_camera_unproject with the host-side chunk -- pixels uploaded, unprojected and downloaded per pass -- given by the
+ * caller (chunk >= 1) instead of the library's default, so that a test reaches the chunk boundary with a few hundred pixels. */
+int32_t calico_debug_camera_unproject_chunked(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n,
+                                              const double* pixels, double* bearings_out, uint8_t* valid_out, int64_t chunk);
+
 #ifdef __cplusplus
 }
 #endif

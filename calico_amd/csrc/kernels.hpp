@@ -120,4 +120,27 @@ hipError_t configure_observability_kernel(int device);
 void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
                       double* out, hipStream_t s);
 
+// ---- camera model maps (camera_kernels.hip): free pixels and points, no residual blocks -----------------------------------
+// All pointers are device memory; `k` (the intrinsics) and, in the rig frame, q_rc are read through wave-uniform addresses. The
+// launches return the launch's own status; n == 0 launches nothing.
+int camera_model_num_params(int model);      // -1: no such model
+hipError_t launch_camera_unproject(int model, const double* k, long long n, const double* pixels /* n x 2 */, double* bearings /* n x 3 */,
+                                   uint8_t* valid, hipStream_t s);
+// d_point (n x 2 x 3) and d_intr (n x 2 x K) may be nullptr (both: the instantiation without derivatives); valid may be nullptr
+hipError_t launch_camera_project_points(int model, const double* k, long long n, const double* points /* n x 3 */, double* pixels /* n x 2 */,
+                                        uint8_t* valid, double* d_point, double* d_intr, hipStream_t s);
+// projection_uncertainty_kernel: theta = [intrinsics K | q 3 | t 3] of one camera, sigma its (K + 6) x (K + 6) covariance
+// (row-major, tangent form, zero rows and columns for what is constant or does not enter the frame)
+struct UncertaintyArgs {
+  const double* k; const double* q;                       // the camera's intrinsics and q_rc (x, y, z, w); t_rc does not enter: p_r - t_rc = R_rc p_c
+  const double* sigma;
+  const double* pixels;                                   // n x 2
+  double* cov;                                            // n x 3: s_uu, s_uv, s_vv
+  uint8_t* valid;
+  long long n;
+  double range;
+  int frame;
+};
+hipError_t launch_projection_uncertainty(int model, const UncertaintyArgs& a, hipStream_t s);
+
 }  // namespace cal

@@ -69,6 +69,28 @@ VectorXd to_vector(const py::object& o) {
   return VectorXd(arr.data(), arr.data() + arr.size());
 }
 
+// (n, 2) pixels of a numpy array
+std::vector<Vector2d> to_pixels(const py::object& o) {
+  auto arr = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(o);
+  if (!arr || !((arr.ndim() == 2 && arr.shape(1) == 2) || (arr.ndim() == 1 && arr.size() == 2)))
+    throw py::type_error("expected an (n, 2) array of pixels (or one pixel of length 2)");
+  std::vector<Vector2d> px(size_t(arr.size() / 2));
+  for (size_t i = 0; i < px.size(); ++i) px[i] = Vector2d(arr.data()[2 * i], arr.data()[2 * i + 1]);
+  return px;
+}
+py::array_t<bool> to_bool_array(const std::vector<uint8_t>& v) {
+  py::array_t<bool> ok{py::ssize_t(v.size())};
+  for (size_t i = 0; i < v.size(); ++i) ok.mutable_at(py::ssize_t(i)) = v[i] != 0;
+  return ok;
+}
+// (bearings (n, 3), valid (n,) bool)
+py::tuple bearings_tuple(const std::vector<Vector3d>& b, const std::vector<uint8_t>& valid) {
+  py::array_t<double> a({py::ssize_t(b.size()), py::ssize_t(3)});
+  for (size_t i = 0; i < b.size(); ++i)
+    for (int c = 0; c < 3; ++c) a.mutable_at(py::ssize_t(i), c) = b[i][c];
+  return py::make_tuple(a, to_bool_array(valid));
+}
+
 // the part of the sensor interface the three sensors share (calico.cpp:77-103 and its two repetitions)
 template <class S, class PyClass>
 void bind_sensor_common(PyClass& c) {
@@ -183,6 +205,28 @@ PYBIND11_MODULE(_calico, m) {
       .value("kUnifiedCamera", CameraIntrinsicsModel::kUnifiedCamera)
       .value("kExtendedUnifiedCamera", CameraIntrinsicsModel::kExtendedUnifiedCamera);
 
+  // sensors::CameraModel::UnprojectPixel (camera_models.h): not bound by the reference's module; named as the C++. On the
+  // device (calico_camera_unproject): the unit-norm point that projects to the pixel.
+  py::class_<CameraModel>(m, "CameraModel")
+      .def_static("UnprojectPixel",
+                  [](CameraIntrinsicsModel model, const py::object& intrinsics, const Vector2d& pixel, int device) {
+                    auto b = CameraModel::UnprojectPixel(model, to_vector(intrinsics), pixel, device);
+                    raise_if_error(b.status());
+                    return b.value();
+                  },
+                  py::arg("model"), py::arg("intrinsics"), py::arg("pixel"), py::arg("device") = 0)
+      .def_static("UnprojectPixels",
+                  [](CameraIntrinsicsModel model, const py::object& intrinsics, const py::object& pixels, int device) {
+                    std::vector<Vector3d> b;
+                    std::vector<uint8_t> valid;
+                    raise_if_error(CameraModel::UnprojectPixels(model, to_vector(intrinsics), to_pixels(pixels), &b, &valid, device));
+                    return bearings_tuple(b, valid);
+                  },
+                  py::arg("model"), py::arg("intrinsics"), py::arg("pixels"), py::arg("device") = 0);
+  py::enum_<ProjectionFrame>(m, "ProjectionFrame")
+      .value("kCamera", ProjectionFrame::kCamera)
+      .value("kRig", ProjectionFrame::kRig);
+
   py::class_<CameraObservationId>(m, "CameraObservationId")
       .def(py::init([] { return CameraObservationId{0.0, 0, 0, 0}; }))
       .def(py::init<const CameraObservationId&>())
@@ -224,7 +268,15 @@ PYBIND11_MODULE(_calico, m) {
       .def("MarkOutlierById", [](Camera& self, const CameraObservationId& id) { raise_if_error(self.MarkOutlierById(id)); })
       .def("MarkOutliersById",
            [](Camera& self, const std::vector<CameraObservationId>& ids) { raise_if_error(self.MarkOutliersById(ids)); })
-      .def("ClearOutliersList", &Camera::ClearOutliersList);
+      .def("ClearOutliersList", &Camera::ClearOutliersList)
+      .def("UnprojectPixels",
+           [](const Camera& self, const py::object& pixels, int device) {
+             std::vector<Vector3d> b;
+             std::vector<uint8_t> valid;
+             raise_if_error(self.UnprojectPixels(to_pixels(pixels), &b, &valid, device));
+             return bearings_tuple(b, valid);
+           },
+           py::arg("pixels"), py::arg("device") = 0);
 
   // ---- trajectory, world model ----
   py::class_<Trajectory, std::shared_ptr<Trajectory>>(m, "Trajectory")
@@ -393,7 +445,19 @@ PYBIND11_MODULE(_calico, m) {
              for (py::ssize_t i = 0; i < n; ++i) ok.mutable_at(i) = valid[size_t(i)] != 0;
              return py::make_tuple(py::array_t<double>({n, d, d}, cov.data()), py::array_t<double>(n, lev.data()), ok);
            },
-           py::arg("sensor"), py::arg("apply_loss") = true);
+           py::arg("sensor"), py::arg("apply_loss") = true)
+      // projection uncertainty map of a camera: ([s_uu, s_uv, s_vv] (n, 3) in pixels^2, valid (n,) bool)
+      .def("ProjectionUncertainty",
+           [](const Covariance& c, std::shared_ptr<Camera> camera, const py::object& pixels, double range, ProjectionFrame frame) {
+             std::vector<std::array<double, 3>> cov;
+             std::vector<uint8_t> valid;
+             raise_if_error(c.ProjectionUncertainty(*camera, to_pixels(pixels), range, frame, &cov, &valid));
+             py::array_t<double> a({py::ssize_t(cov.size()), py::ssize_t(3)});
+             for (size_t i = 0; i < cov.size(); ++i)
+               for (int k = 0; k < 3; ++k) a.mutable_at(py::ssize_t(i), k) = cov[i][size_t(k)];
+             return py::make_tuple(a, to_bool_array(valid));
+           },
+           py::arg("camera"), py::arg("pixels"), py::arg("range") = 1.0, py::arg("frame") = ProjectionFrame::kRig);
 
   py::class_<BatchOptimizer>(m, "BatchOptimizer")
       .def(py::init<>())

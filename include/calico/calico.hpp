@@ -184,6 +184,9 @@ inline SolverOptions DefaultSolverOptions() { SolverOptions o; calico_default_so
 // ---------------------------------------------------------------------------
 class Covariance;
 class Observability;
+namespace sensors { class Camera; }
+/// Frame the 3-D point of a projection uncertainty map is fixed in (CALICO_FRAME_*)
+enum class ProjectionFrame : int { kCamera = CALICO_FRAME_CAMERA, kRig = CALICO_FRAME_RIG };
 class Problem {
  public:
   Problem() = default;
@@ -360,6 +363,28 @@ class Covariance {
     if (valid) valid->swap(v);
     return OkStatus();
   }
+  /// Projection uncertainty map of a camera (calico_projection_uncertainty): for every pixel [s_uu, s_uv, s_vv] (pixels^2) of
+  /// the projection of a point `range` metres along the pixel's ray, fixed in the camera frame (intrinsics only) or in the
+  /// sensor-rig frame (intrinsics and extrinsics); valid = 0 with zeros where the pixel does not unproject. `sensor` as for
+  /// Predictions; the overload below takes a camera of the optimizer the covariance came from.
+  Status ProjectionUncertainty(int sensor, const std::vector<Vector2d>& pixels, double range, ProjectionFrame frame,
+                               std::vector<std::array<double, 3>>* cov, std::vector<uint8_t>* valid) const {
+    if (!h_) return FailedPreconditionError("covariance has not been computed");
+    if (sensor < 0 || sensor >= NumSensors()) return InvalidArgumentError("covariance: sensor not in the problem");
+    const size_t n = pixels.size();
+    std::vector<double> px(2 * n);
+    for (size_t i = 0; i < n; ++i) { px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y(); }
+    std::vector<std::array<double, 3>> c(n);
+    std::vector<uint8_t> v(n, 0);
+    const int st = calico_projection_uncertainty(h_.get(), sensor_ids_[size_t(sensor)], int(frame), range, int64_t(n), px.data(),
+                                                 n ? c[0].data() : nullptr, v.data());
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(h_.get()));
+    if (cov) cov->swap(c);
+    if (valid) valid->swap(v);
+    return OkStatus();
+  }
+  inline Status ProjectionUncertainty(const sensors::Camera& camera, const std::vector<Vector2d>& pixels, double range, ProjectionFrame frame,
+                                      std::vector<std::array<double, 3>>* cov, std::vector<uint8_t>* valid) const;
 
  private:
   friend class Problem;
@@ -813,6 +838,38 @@ struct CameraObservationIdHash {
 };
 struct CameraMeasurement { Vector2d pixel; CameraObservationId id; };
 
+/// sensors::CameraModel (camera_models.h): the inverse model, on the device (calico_camera_unproject). The result is the
+/// UNIT-NORM point that projects to the pixel under the library's projection -- the usual bearing for every model but
+/// ExtendedUnified, whose projection is not scale invariant (include/calico_hip.h). A model is named by its enum value:
+/// there are no model objects here.
+class CameraModel {
+ public:
+  /// UnprojectPixels for n pixels: bearings[i] and valid[i] (0 with a zero vector where the pixel does not unproject)
+  static Status UnprojectPixels(CameraIntrinsicsModel model, const VectorXd& intrinsics, const std::vector<Vector2d>& pixels,
+                                std::vector<Vector3d>* bearings, std::vector<uint8_t>* valid, int device = 0) {
+    const size_t n = pixels.size();
+    std::vector<double> px(2 * n), b(3 * n);
+    for (size_t i = 0; i < n; ++i) { px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y(); }
+    std::vector<uint8_t> v(n, 0);
+    const int st = calico_camera_unproject(device, int(model), intrinsics.data(), int(intrinsics.size()), int64_t(n), px.data(), b.data(), v.data());
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+    if (bearings) {
+      bearings->resize(n);
+      for (size_t i = 0; i < n; ++i) (*bearings)[i] = Vector3d(b[3 * i], b[3 * i + 1], b[3 * i + 2]);
+    }
+    if (valid) valid->swap(v);
+    return OkStatus();
+  }
+  /// CameraModel::UnprojectPixel(intrinsics, pixel): kInvalidArgument for a pixel no point of the model's domain projects to
+  static StatusOr<Vector3d> UnprojectPixel(CameraIntrinsicsModel model, const VectorXd& intrinsics, const Vector2d& pixel, int device = 0) {
+    std::vector<Vector3d> b;
+    std::vector<uint8_t> v;
+    if (Status st = UnprojectPixels(model, intrinsics, {pixel}, &b, &v, device); !st.ok()) return st;
+    if (!v[0]) return InvalidArgumentError("pixel (" + std::to_string(pixel.x()) + ", " + std::to_string(pixel.y()) + ") does not unproject");
+    return b[0];
+  }
+};
+
 inline bool ProjectPointHost(CameraIntrinsicsModel model, const double* k, const cal::V3& p, double pix[2]) {
   double D[2][3], dK[2][cal::kMaxIntr];
   switch (int(model)) {
@@ -844,6 +901,13 @@ class Camera : public SensorCommon {
     model_ = m; intrinsics_.assign(size_t(NumberOfParameters(m)), 0.0); return OkStatus();
   }
   CameraIntrinsicsModel GetModel() const { return model_; }
+  /// CameraModel::UnprojectPixels at this camera's current intrinsics (after Optimize: the estimates, written back in place).
+  /// The handle-free call with the host's copy of the intrinsics: the facade keeps no handle between calls; a caller that
+  /// holds one uses calico_sensor_unproject, which gives the same bits.
+  Status UnprojectPixels(const std::vector<Vector2d>& pixels, std::vector<Vector3d>* bearings, std::vector<uint8_t>* valid, int device = 0) const {
+    if (model_ == CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
+    return CameraModel::UnprojectPixels(model_, intrinsics_, pixels, bearings, valid, device);
+  }
   StatusOr<int> AddParametersToProblem(Problem& problem) final {
     return AddCommonParameters(problem, model_ != CameraIntrinsicsModel::kNone, "camera");
   }
@@ -1058,6 +1122,12 @@ class Accelerometer : public ImuSensor<CALICO_SENSOR_ACCELEROMETER> {
 };
 
 }  // namespace sensors
+
+inline Status Covariance::ProjectionUncertainty(const sensors::Camera& camera, const std::vector<Vector2d>& pixels, double range,
+                                                ProjectionFrame frame, std::vector<std::array<double, 3>>* cov,
+                                                std::vector<uint8_t>* valid) const {
+  return ProjectionUncertainty(camera.ProblemSensor(), pixels, range, frame, cov, valid);
+}
 
 // ---------------------------------------------------------------------------
 // BatchOptimizer (batch_optimizer.{h,cpp})

@@ -135,7 +135,9 @@ typedef struct calico_iteration {
  * no CPU fallback behind this ABI. */
 int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
-/* Message of the last non-OK status on this handle ("" if none). */
+/* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
+ * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points); like a handle's message it
+ * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
 
@@ -485,6 +487,57 @@ int32_t calico_observability_get_block(calico_problem* p, int32_t index, int32_t
                                        double* share);
 /* S̃ itself, dim x dim row-major, zeros in dropped rows / columns. */
 int32_t calico_observability_get_matrix(calico_problem* p, double* out);
+
+/* ---- camera model maps: unprojection, free points, projection uncertainty ---- */
+/* The camera model over arbitrary pixels and points -- no residual blocks, no trajectory, no latency: what a user does
+ * with a calibration once it is solved (rays for triangulation and PnP, rectification look-ups) and the map a person reads
+ * to judge it (how uncertain the projection is across the image, corners included).
+ *
+ * calico_camera_unproject replaces sensors::CameraModel::UnprojectPixel (camera_models.h: Newton for OpenCv5/8 and
+ * KannalaBrandt, closed forms for the rest) for n pixels at once, on the device. bearings_out[i] (n x 3) is the UNIT-NORM
+ * point b with project(intrinsics, b) == pixels[i] under this library's projection (calico_project, the residuals). For six
+ * models that is the usual bearing. For ExtendedUnified the projection the reference and this library evaluate is not scale
+ * invariant (beta * |p_xy|, not its square), so "unit-norm point" is the definition; the reference's own closed form (which its
+ * header calls rather imprecise) is not reproduced. DoubleSphere, FieldOfView, Unified: closed forms; OpenCv5/8: Newton on
+ * the normalised point, at most 30 steps; KannalaBrandt, ExtendedUnified: Newton on the polar angle, at most 100 steps; stop
+ * rule 1e-14 in normalised units. valid_out[i] = 0 and bearings_out[i] = 0 where Newton did not reach the stop rule, a closed
+ * form's radicand is negative, the result is not finite, the projection rejects the point or does not return the pixel.
+ * Needs no problem handle (like calico_fit_spline): allocates and frees its own device memory, n is processed in chunks.
+ * CALICO_INVALID_ARGUMENT -- checked before the device is touched, message in calico_last_error(NULL), which is kept per
+ * thread for the calls without a handle -- for an unknown model, n_intrinsics other than the model's count, n < 0, a NULL
+ * pointer with n > 0; n == 0 is CALICO_OK and touches nothing. */
+int32_t calico_camera_unproject(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n,
+                                const double* pixels, double* bearings_out, uint8_t* valid_out);
+/* The forward model for n free camera-frame points (n x 3): pixels_out n x 2, valid_out n (0 and zeros where the model
+ * rejects the point, e.g. z <= 0 for the pinhole-type models), d_point_out n x 2 x 3 = d pixel / d point, d_intrinsics_out
+ * n x 2 x n_intrinsics = d pixel / d intrinsics. The last three pointers may be NULL. It is the projection of the residuals
+ * itself: ideal pixel -> calico_camera_unproject -> rotate -> this call is a rectification look-up table. Errors as above. */
+int32_t calico_camera_project_points(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n,
+                                     const double* points, double* pixels_out, uint8_t* valid_out, double* d_point_out,
+                                     double* d_intrinsics_out);
+/* calico_camera_unproject at the CURRENT intrinsics of a camera of the problem, read on the device from the handle's
+ * parameter vector, on the handle's stream (ordered behind a solve). Bit-identical to calico_camera_unproject at the values
+ * calico_get_param_block returns. CALICO_INVALID_ARGUMENT for an unknown sensor or one that is not a camera. */
+int32_t calico_sensor_unproject(calico_problem* p, int32_t sensor, int64_t n, const double* pixels, double* bearings_out,
+                                uint8_t* valid_out);
+/* Projection uncertainty map: for each of n pixels the covariance of the pixel a fixed 3-D point projects to, under the
+ * covariance of the camera's estimates: the pixel is unprojected at the current intrinsics, the ray scaled to `range`
+ * metres, and S_pix = G S_tt G^T with G = d pixel / d theta there; cov_out is n x 3 = [s_uu, s_uv, s_vv], in pixels^2
+ * (no a-posteriori variance factor, as the covariance).
+ *   CALICO_FRAME_CAMERA: the point is fixed in the camera frame; theta = the intrinsics block, G = d pixel / d intrinsics
+ *     (`range` only matters for ExtendedUnified, whose projection is not scale invariant).
+ *   CALICO_FRAME_RIG: the point is fixed in the sensor-rig frame, p_c = R_rc^T (p_r - t_rc); theta = intrinsics, q_rc and
+ *     t_rc with all cross-covariances, the quaternion in the EigenQuaternion tangent the covariance uses.
+ * Constant blocks contribute nothing. Latency and the trajectory do NOT enter: the map is about the camera, not about
+ * where the rig was. Needs a successful calico_covariance_compute on the handle (either value of control_points: only the
+ * border is read); otherwise, and after a structural change, CALICO_FAILED_PRECONDITION. S_tt is taken at the values of
+ * that compute, G at the current values. CALICO_INVALID_ARGUMENT for an unknown or non-camera sensor, frame outside {0, 1},
+ * range not finite or <= 0, n < 0, a NULL pointer with n > 0. valid_out[i] = 0 with zeros as for the unprojection.
+ * Leaves the parameters, the LM state, the iteration log and the stored covariance alone. */
+#define CALICO_FRAME_CAMERA 0
+#define CALICO_FRAME_RIG 1
+int32_t calico_projection_uncertainty(calico_problem* p, int32_t sensor, int32_t frame, double range, int64_t n,
+                                      const double* pixels, double* cov_out, uint8_t* valid_out);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
