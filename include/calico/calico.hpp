@@ -52,6 +52,7 @@ class Status {
 inline Status OkStatus() { return Status(); }
 inline Status InvalidArgumentError(const std::string& m) { return Status(StatusCode::kInvalidArgument, m); }
 inline Status FailedPreconditionError(const std::string& m) { return Status(StatusCode::kFailedPrecondition, m); }
+inline Status UnimplementedError(const std::string& m) { return Status(StatusCode::kUnimplemented, m); }
 inline Status InternalError(const std::string& m) { return Status(StatusCode::kInternal, m); }
 template <class T> class StatusOr {
  public:
@@ -562,10 +563,11 @@ class BSpline6 {
       std::copy(M.begin(), M.end(), basis_.begin() + size_t(s) * order * order);
     }
     // least-squares control points on the device (calico_fit_spline: banded normal equations + banded Cholesky; the
-    // reference factors the dense design matrix by column-pivoted QR, bspline.hpp:287-293)
-    const int ncp = nk - order, nd = int(time.size());
+    // reference factors the dense normal equations by column-pivoted QR, bspline.hpp:287-293)
+    const int ncp = nk - order;
+    const int64_t nd = int64_t(time.size());
     std::vector<double> flat(size_t(nd) * 6), ctrl(size_t(ncp) * 6);
-    for (int j = 0; j < nd; ++j) for (int c = 0; c < 6; ++c) flat[size_t(j) * 6 + c] = data[size_t(j)][size_t(c)];
+    for (int64_t j = 0; j < nd; ++j) for (int c = 0; c < 6; ++c) flat[size_t(j) * 6 + c] = data[size_t(j)][size_t(c)];
 #ifdef CALICO_TEST_HOOKS
     const int32_t rc = fit_solver() ? fit_solver()(order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), ctrl.data())
                                     : calico_fit_spline(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), ctrl.data());
@@ -573,6 +575,9 @@ class BSpline6 {
     const int32_t rc = calico_fit_spline(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), ctrl.data());
 #endif
     if (rc == CALICO_INVALID_ARGUMENT) return InvalidArgumentError("spline fit: stamps must be sorted and inside the knot range");
+    if (rc == CALICO_UNIMPLEMENTED)      // calico_fit_spline's on-chip solve holds [band | rhs]: n_ctrl (order + 6) doubles in 156 KiB
+      return UnimplementedError("spline fit: " + std::to_string(ncp) + " control points are too many for the on-device solve; order " +
+                                std::to_string(order) + " fits at most " + std::to_string(156 * 1024 / ((order + 6) * 8)));
     if (rc != CALICO_OK) return InternalError("spline fit failed on the device");
     ctrl_.assign(size_t(ncp), {});
     for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];

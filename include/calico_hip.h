@@ -257,11 +257,25 @@ int32_t calico_get_residuals(calico_problem* p, int32_t sensor_id, double* out,
 /* Spline initialisation on the device: BSpline::FitToData / FitSpline (bspline.hpp:19-37, 246-297), behind
  * Trajectory::FitSpline (trajectory.cpp:14-49). Least-squares control points (n_knots - order rows of 6) of the
  * spline on the given knot vector / basis matrices (as for calico_problem_set_spline) through n sorted samples
- * `data6` (n x 6: axis-angle, position) at `stamps`. The reference factors the dense n x n_ctrl design matrix by
- * column-pivoted QR; here the banded normal equations are assembled in a fixed order and solved by a banded Cholesky
- * (control points the samples do not determine, e.g. at an under-sampled trajectory end, are decoupled). kInvalidArgument for unsorted stamps,
- * stamps outside the valid knots or bad sizes; kUnimplemented when the band does not fit the on-chip solve. Needs no
- * problem handle. */
+ * `data6` (n x 6: axis-angle, position) at `stamps`. The reference factors the dense normal equations X^T X by
+ * column-pivoted QR; here the banded normal equations are assembled in a fixed order (the result is bit-reproducible)
+ * and solved by a banded Cholesky with a ridge of 1e-15 mean_diag (mean_diag = trace(X^T X) / n_ctrl).
+ * Accuracy (profiles/EXPERIMENTS.md, "spline fit accuracy"): the control points lie within ~1e-15 cond2(X)^2 max|C| of
+ * exact least squares -- 2e-9 at order 6 with the last segment covered (cond2 1.8e3), 1e-6 with the last sample half-way
+ * into it (cond2 4.3e4) -- and the fitted values at the samples never further, up to 6 decades closer as cond2 grows
+ * (4e-11 in the latter case).
+ * Control points the samples do not determine are decoupled: a Cholesky pivot <= 1e-13 mean_diag is replaced by
+ * mean_diag and the control point comes back ~0 (exactly 0 where no sample touches it; sqrt(pivot / mean_diag) times
+ * the samples' noise otherwise). This is a cliff, not a rank test: at order 6 with 100 Hz samples on 10 Hz knots, a
+ * last sample 10 % into the last segment leaves the last control point an exact pivot of 3e-16 mean_diag and it is
+ * dropped, although X has full rank (cond2 9.4e7); at 30 % the pivot is 1.7e-11 (cond2 4.1e5) and it is kept; at 20 %
+ * (3.3e-13) it lies within a decade of the threshold, where roundoff decides. With fewer distinct samples than the
+ * control points they touch (one sample per segment, n <= 3) the ridge decides which are kept: the values at the samples
+ * are fitted, the largest control point measures 1.2 to 14.5 times the minimum-norm solution's (the latter for a single
+ * sample at mid-segment). kInvalidArgument for unsorted stamps, stamps outside the valid
+ * knots or bad sizes; kUnimplemented when the band does not fit the on-chip solve (n_ctrl (order + 6) 8 bytes > 156 KiB:
+ * more than 1664 control points at order 6, 1426 at order 8; ctrl_out is then left untouched) or n exceeds INT32_MAX.
+ * Needs no problem handle. */
 int32_t calico_fit_spline(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
                           int64_t n, const double* stamps, const double* data6, double* ctrl_out);
 

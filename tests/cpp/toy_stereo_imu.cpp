@@ -37,6 +37,11 @@ static int32_t oracle_fit(int32_t order, int32_t n_knots, const double* knots, c
   return rc == 0 ? CALICO_OK : CALICO_INTERNAL;
 }
 
+// a trajectory too long for the device's on-chip solve, as calico_fit_spline reports it
+static int32_t too_long_fit(int32_t, int32_t, const double*, const double*, int64_t, const double*, const double*, double*) {
+  return CALICO_UNIMPLEMENTED;
+}
+
 static int failures = 0;
 #define CHECK(cond)                                                         \
   do {                                                                      \
@@ -103,6 +108,14 @@ int main(int argc, char** argv) {
     }
     CHECK(worst < 1e-3); }
   CHECK(!trajectory->Interpolate({-1.0}).ok() && trajectory->Interpolate({-1.0}).status().code() == StatusCode::kInvalidArgument);
+  if (host_only) {  // kUnimplemented from the fit passes through, naming the order's control-point ceiling (156 KiB / ((6 + 6) 8))
+    BSpline6::fit_solver() = &too_long_fit;
+    Trajectory long_trajectory;
+    const Status st = long_trajectory.FitSpline(fixture.trajectory);
+    CHECK(st.code() == StatusCode::kUnimplemented);
+    CHECK(st.message().find("185 control points") != std::string::npos && st.message().find("at most 1664") != std::string::npos);
+    BSpline6::fit_solver() = &oracle_fit;
+  }
 
   RigidBody planar_target; planar_target.world_pose_is_constant = true; planar_target.model_definition_is_constant = true;
   for (size_t i = 0; i < fixture.points.size(); ++i) planar_target.model_definition[int(i)] = fixture.points[i];
