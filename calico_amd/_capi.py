@@ -148,7 +148,7 @@ ABI_SYMBOLS = [
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
-                "debug_lds_attribute_calls", "debug_camera_unproject_chunked"]
+                "debug_lds_attribute_calls", "debug_camera_unproject_chunked", "debug_panel_product", "debug_block_elim"]
 
 
 class CApi:
@@ -237,6 +237,9 @@ class CApi:
                 g("debug_last_step", C.c_int32, [P, C.c_int32, D, D, D])
             if hasattr(self.lib, self.prefix + "debug_lds_attribute_calls"):
                 g("debug_lds_attribute_calls", C.c_int64, [])
+            if hasattr(self.lib, self.prefix + "debug_panel_product"):
+                g("debug_panel_product", C.c_int32, [C.c_int32, C.c_int32, D, D, D])
+                g("debug_block_elim", C.c_int32, [C.c_int32, C.c_int32, D, D, D, D, D])
 
     def _get(self, name, restype, argtypes):
         fn = getattr(self.lib, self.prefix + name)

@@ -3290,4 +3290,65 @@ void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_node
                      blocks, n_blocks, ts);
 }
 
+// ---- test hooks (calico_hip_testing.h): block_elim.hpp on its own -----------------------------------------------------------
+// One wave, one panel product: form 0 = register 0 of the 16x16x4 product (the panel up to round 6; rows 4..15 of its A operand
+// only reach result registers 1..3), form 1 = CAL_PANEL. w, x, out: one double per lane.
+__global__ __launch_bounds__(64) void debug_panel_product_kernel(int form, const double* w, const double* x, double* out) {
+  const int lane = threadIdx.x;
+  if (form == 0) {
+    const f64x4 p = CAL_MFMA(w[lane], x[lane], (f64x4{0.0, 0.0, 0.0, 0.0}));
+    out[lane] = p[0];
+  } else {
+    out[lane] = CAL_PANEL(w[lane], x[lane]);
+  }
+}
+// One 32x32 block the way the solver kernels eliminate it: the chief on wave 0, the identity rows (-> L⁻ᵀ) with a two-tile follower on
+// wave 1, the nt row tiles of X (-> Z = X L⁻ᵀ) with an nt-tile follower on wave 2. D, L, Minv: [32][32]; X, Z: [16 nt][32], row-major.
+constexpr int kDebugElimThreads = 192, kDebugElimMaxTiles = 3;
+__global__ __launch_bounds__(kDebugElimThreads) void debug_block_elim_kernel(int nt, const double* D, const double* X, double* L, double* Z, double* Minv) {
+  __shared__ double A[64 * DLD], Xs[16 * kDebugElimMaxTiles * DLD], Zs[16 * kDebugElimMaxTiles * DLD], chbuf[kElimBufDoubles];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int e = tid; e < BB; e += kDebugElimThreads) {
+    A[(e >> 5) * DLD + (e & 31)] = D[e];
+    A[(32 + (e >> 5)) * DLD + (e & 31)] = 0.0;
+  }
+  for (int e = tid; e < 16 * nt * BP; e += kDebugElimThreads) { Xs[(e >> 5) * DLD + (e & 31)] = X[e]; Zs[(e >> 5) * DLD + (e & 31)] = 0.0; }
+  const ElimChannel ch = elim_channel(chbuf);
+  elim_reset(ch, tid, kDebugElimThreads);
+  __syncthreads();
+  if (wave == 0) {
+    elim_chief<1>(A, DLD, ch, lane);
+  } else if (wave == 1) {
+    const ElimTile t[2] = {{Xs, 0, 0, A + 32 * DLD, DLD, 1, 1, nullptr}, {Xs, 0, 0, A + 48 * DLD, DLD, 1, 2, nullptr}};
+    elim_follow<2>(t, ch, lane);
+  } else if (nt == 1) {
+    const ElimTile t[1] = {{Xs, DLD, 1, Zs, DLD, 1, 0, nullptr}};
+    elim_follow<1>(t, ch, lane);
+  } else if (nt == 2) {
+    const ElimTile t[2] = {{Xs, DLD, 1, Zs, DLD, 1, 0, nullptr}, {Xs + 16 * DLD, DLD, 1, Zs + 16 * DLD, DLD, 1, 0, nullptr}};
+    elim_follow<2>(t, ch, lane);
+  } else {
+    const ElimTile t[3] = {{Xs, DLD, 1, Zs, DLD, 1, 0, nullptr}, {Xs + 16 * DLD, DLD, 1, Zs + 16 * DLD, DLD, 1, 0, nullptr},
+                           {Xs + 32 * DLD, DLD, 1, Zs + 32 * DLD, DLD, 1, 0, nullptr}};
+    elim_follow<3>(t, ch, lane);
+  }
+  __syncthreads();
+  for (int e = tid; e < BB; e += kDebugElimThreads) {
+    const int r = e >> 5, c = e & 31;
+    L[e] = c <= r ? A[r * DLD + c] : 0.0;        // (the chief leaves what lies above the diagonal undefined)
+    Minv[e] = A[(32 + r) * DLD + c];
+  }
+  for (int e = tid; e < 16 * nt * BP; e += kDebugElimThreads) Z[e] = Zs[(e >> 5) * DLD + (e & 31)];
+}
+hipError_t launch_debug_panel_product(int form, const double* w, const double* x, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(debug_panel_product_kernel, dim3(1), dim3(64), 0, s, form, w, x, out);
+  return hipGetLastError();
+}
+int debug_block_elim_max_tiles() { return kDebugElimMaxTiles; }
+hipError_t launch_debug_block_elim(int n_row_tiles, const double* D, const double* X, double* L, double* Z, double* Minv, hipStream_t s) {
+  assert(n_row_tiles >= 1 && n_row_tiles <= kDebugElimMaxTiles);
+  hipLaunchKernelGGL(debug_block_elim_kernel, dim3(1), dim3(kDebugElimThreads), 0, s, n_row_tiles, D, X, L, Z, Minv);
+  return hipGetLastError();
+}
+
 }  // namespace cal

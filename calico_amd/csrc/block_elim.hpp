@@ -13,14 +13,20 @@
 //   * register u of a tile IS the operand "sixteen rows x the four columns of step u" of v_mfma_f64_16x16x4_f64 (lane
 //     (l16, lk) holds entry (l16, k = lk)) -- as A operand and as B operand alike;
 //   * the step's four columns of the factor for row tile T, L_T = Aug_T,step · L44⁻ᵀ, are ONE MFMA with -L44⁻¹ (the
-//     inverse of the 4x4 pivot block's Cholesky factor, rows 0..3 of a 16x4 A operand) against register u; result
-//     register 0 of lane (l16, lk) is L[16T + l16][step column lk] -- the operand layout again -- so the trailing update
-//     tile(J', T) += L_J' L_Tᵀ takes both operands straight from result registers. No LDS, no lane movement;
+//     inverse of the 4x4 pivot block's Cholesky factor) against register u: v_mfma_f64_4x4x4_4b_f64, four independent
+//     4x4x4 products -- the tile's sixteen rows are four blocks of four rows against the same 4x4 factor (CAL_PANEL). Its
+//     operands: A entry (i, k) of block b in lane 16k + 4b + i, B entry (k, j) in lane 16k + 4b + j, D entry (i, j) in lane
+//     16i + 4b + j (profiles/microbench/mfma_f64_4x4x4.hip), so register u of the tile IS the B operand, unchanged, `w`
+//     carries entry (l16 & 3, lk) of -L44⁻¹ in every lane, and the result of lane (l16, lk) is L[16T + l16][step column
+//     lk] -- the operand layout again -- so the trailing update tile(J', T) += L_J' L_Tᵀ takes both operands straight from
+//     results. No LDS, no lane movement. (Up to round 6 the panel was a 16x16x4 product whose A operand had twelve zero
+//     rows and whose result registers 1..3 nobody read: 64 clocks of the matrix pipe and sixteen passes before a dependent
+//     use, against 16 and four for this form -- a panel -> update -> panel round 161 -> 109 clocks.)
 //   * the only cross-lane traffic is the 4x4 pivot block (ten v_readlane pairs out of register u of the diagonal tile),
 //     factored redundantly by every lane: 4 x [v_rsq_f64 + one Newton step] on the chain; the lane's entry of -L44⁻¹ is
 //     the forward substitution of its own unit vector e_lk, selected by l16.
 // One wave cannot go faster than its chain (eight steps of ~75 VALU instructions + two dependent MFMAs) OR than its
-// flops (FP64 MFMA: 64 clocks per 16x16x4 on this part -- the whole augmented block is ~50 of them), so the work is split:
+// flops (FP64 MFMA: 64 clocks per 16x16x4 trailing update on this part, 16 per panel -- the whole augmented block is ~50 products), so the work is split:
 //   * the CHIEF wave owns the spine (the block itself: tiles (0,0), (0,1), (1,1)) and nothing else -- five MFMAs per
 //     step -- and publishes per step, write-once in LDS: w (the pivot operand), l0 / l1 (the step's columns of L for
 //     rows 0..15 / 16..31), then a progress word;
@@ -107,7 +113,7 @@ struct PivotChain {
     pre = __builtin_fma(m2, x2, __builtin_fma(m1, x1, m0 * x0));
     q3 = (m3 * x3a) * rs3;
   }
-  DEVI double s6() {    // the lane's entry of -L44⁻¹ in the A-operand layout (row l16 < 4, k = lk; zero elsewhere)
+  DEVI double s6() {    // the lane's entry of -L44⁻¹ in the panel's A-operand layout (row l16 & 3, k = lk: the same in each block of four rows)
     return __builtin_fma(q3, e3n, pre);
   }
   // The lane's row is picked by arithmetic on lane constants, not by a chain of selects on l16: the compiler turns that chain into a
@@ -117,16 +123,18 @@ struct PivotChain {
   double m0, m1, m2, m3, pre, q3, rs3, e3n;
   DEVI void set_lane(int l16_) {
     l16 = l16_;
-    m0 = l16_ == 0 ? 1.0 : 0.0; m1 = l16_ == 1 ? 1.0 : 0.0; m2 = l16_ == 2 ? 1.0 : 0.0; m3 = l16_ == 3 ? 1.0 : 0.0;
+    const int row = l16_ & 3;        // (of -L44⁻¹: CAL_PANEL's A operand repeats it in every block of four lanes)
+    m0 = row == 0 ? 1.0 : 0.0; m1 = row == 1 ? 1.0 : 0.0; m2 = row == 2 ? 1.0 : 0.0; m3 = row == 3 ? 1.0 : 0.0;
     asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3));
   }
 };
 
 #define CAL_SB() __builtin_amdgcn_sched_barrier(0)
 #define CAL_MFMA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0)
-// keeps all four result registers of a panel product allocated until here: only register 0 is used, and a dead register
-// the compiler hands to the next VALU instruction costs that instruction the MFMA's whole latency in hazard wait states
-#define CAL_KEEP(v) asm volatile("" : : "v"(v))
+// The panel product: sixteen rows of a tile (reg: register u, lane (l16, lk) = entry (row l16, step column lk)) against the 4x4
+// pivot factor (w: entry (l16 & 3, lk) of -L44⁻¹) -> lane (l16, lk): entry (row l16, step column lk) of the step's columns of L.
+// One result register, and it is used: nothing dead is left for the compiler to hand to the next VALU instruction.
+#define CAL_PANEL(w, reg) __builtin_amdgcn_mfma_f64_4x4x4f64(w, reg, 0.0, 0, 0, 0)
 
 // The chief. In: rows 0..31 of A (LDS, row stride LD): the block, lower triangle (the upper one is not read).
 // Out (WRITE_L = 1): rows 0..31: L, lower triangle (above the diagonal undefined); WRITE_L = 2: the lower triangle only --
@@ -157,12 +165,10 @@ DEVI void elim_chief(double* A, int LD, const ElimChannel ch, int lane, long lon
 template <int WRITE_L, bool TS, bool CC>
 DEVI void elim_chief_reg(f64x4 t00, f64x4 t01, f64x4 t11, double* A, int LD, const ElimChannel ch, int lane, long long* ts) {
   const int l16 = lane & 15, lk = lane >> 4;
-  const f64x4 zero4 = {0.0, 0.0, 0.0, 0.0};
   PivotChain pc;
   pc.set_lane(l16);
   pc.e0 = lk == 0 ? -1.0 : 0.0; pc.e1 = lk == 1 ? -1.0 : 0.0; pc.e2 = lk == 2 ? -1.0 : 0.0; pc.e3 = lk == 3 ? -1.0 : 0.0;
   double* const pub = ch.buf + lane;
-  f64x4 p0 = zero4, p1 = zero4;       // panel products (register 0: the step's columns of L for rows 0..15 / 16..31)
   // ---- columns 0..15. Per step: pivot chain -> w; p0 = P(t00), p1 = P(t01) back to back (both only need w); then the
   //      trailing updates t00 (what the next pivot block waits for), t01, t11. FP64 MFMAs and FP64 VALU work of one wave
   //      do not overlap on this part (the matrix instruction runs on the SIMD's FP64 lanes: 64 clocks each), so there is
@@ -175,19 +181,18 @@ DEVI void elim_chief_reg(f64x4 t00, f64x4 t01, f64x4 t11, double* A, int LD, con
     const double w = pc.s6();
     CAL_SB();
     elim_store(pub + elim_slot_w<CC>(u), w);
-    p0 = CAL_MFMA(w, t00[u], zero4);
-    p1 = CAL_MFMA(w, t01[u], zero4);
-    if (u < 3) t00 = CAL_MFMA(p0[0], p0[0], t00);
-    if (u < 3) t01 = CAL_MFMA(p0[0], p1[0], t01);
-    t11 = CAL_MFMA(p1[0], p1[0], t11);
-    if (!CC || u < 3) elim_store(pub + elim_slot_l0<CC>(u), p0[0]);      // (nobody reads l0 of step 3: the compact layout has no place for it)
-    elim_store(pub + elim_slot_l1<CC>(u), p1[0]);
+    const double p0 = CAL_PANEL(w, t00[u]);       // the step's columns of L for rows 0..15 / 16..31
+    const double p1 = CAL_PANEL(w, t01[u]);
+    if (u < 3) t00 = CAL_MFMA(p0, p0, t00);
+    if (u < 3) t01 = CAL_MFMA(p0, p1, t01);
+    t11 = CAL_MFMA(p1, p1, t11);
+    if (!CC || u < 3) elim_store(pub + elim_slot_l0<CC>(u), p0);      // (nobody reads l0 of step 3: the compact layout has no place for it)
+    elim_store(pub + elim_slot_l1<CC>(u), p1);
     if (WRITE_L) {
-      if (WRITE_L == 1 || l16 >= 4 * u + lk) A[l16 * LD + 4 * u + lk] = p0[0];
-      A[(16 + l16) * LD + 4 * u + lk] = p1[0];
+      if (WRITE_L == 1 || l16 >= 4 * u + lk) A[l16 * LD + 4 * u + lk] = p0;
+      A[(16 + l16) * LD + 4 * u + lk] = p1;
     }
     CAL_SB();
-    CAL_KEEP(p0); CAL_KEEP(p1);
   }
   // ---- columns 16..31: the spine is t11 alone. Followers need w and l1 (slot 2) of these steps. ----
 #pragma unroll
@@ -199,14 +204,12 @@ DEVI void elim_chief_reg(f64x4 t00, f64x4 t01, f64x4 t11, double* A, int LD, con
     CAL_SB();
     elim_store(pub + elim_slot_w<CC>(4 + u), w);
     if (u == 3 && !WRITE_L) break;                // (the last step: the followers only need w)
-    p1 = CAL_MFMA(w, t11[u], zero4);
-    if (u < 3) t11 = CAL_MFMA(p1[0], p1[0], t11);
-    if (u < 3) elim_store(pub + elim_slot_l1<CC>(4 + u), p1[0]);
-    if (WRITE_L == 1 || (WRITE_L == 2 && l16 >= 4 * u + lk)) A[(16 + l16) * LD + 16 + 4 * u + lk] = p1[0];
+    const double p1 = CAL_PANEL(w, t11[u]);
+    if (u < 3) t11 = CAL_MFMA(p1, p1, t11);
+    if (u < 3) elim_store(pub + elim_slot_l1<CC>(4 + u), p1);
+    if (WRITE_L == 1 || (WRITE_L == 2 && l16 >= 4 * u + lk)) A[(16 + l16) * LD + 16 + 4 * u + lk] = p1;
     CAL_SB();
-    CAL_KEEP(p1);
   }
-  CAL_KEEP(p0); CAL_KEEP(p1);
   if (TS) ts[8] = __builtin_readcyclecounter();
 }
 
@@ -231,7 +234,6 @@ struct ElimTile {
 template <int NT, bool CC = false>
 DEVI void elim_follow(const ElimTile (&t)[NT], const ElimChannel ch, int lane, bool use_pre = false, const f64x4* pre0 = nullptr, const f64x4* pre1 = nullptr) {
   const int l16 = lane & 15, lk = lane >> 4;
-  const f64x4 zero4 = {0.0, 0.0, 0.0, 0.0};
   f64x4 x0[NT], x1[NT];
 #pragma unroll
   for (int q = 0; q < NT; ++q) {
@@ -271,8 +273,7 @@ DEVI void elim_follow(const ElimTile (&t)[NT], const ElimChannel ch, int lane, b
     double lp[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
-      const f64x4 p = CAL_MFMA(w, (J == 0 ? x0[q][u] : x1[q][u]), zero4);
-      lp[q] = p[0];
+      lp[q] = CAL_PANEL(w, (J == 0 ? x0[q][u] : x1[q][u]));
     }
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
@@ -315,7 +316,6 @@ template <bool CC = false>
 DEVI void elim_follow_d(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double* out1, int out_row, int out_col, const ElimChannel ch, int lane,
                         f64x4& n00, f64x4& n01, f64x4& n11) {
   const int l16 = lane & 15, lk = lane >> 4;
-  const f64x4 zero4 = {0.0, 0.0, 0.0, 0.0};
   const unsigned long long* const sub = reinterpret_cast<const unsigned long long*>(ch.buf) + lane;
   unsigned long long v[3] = {0, 0, 0}, nv[3] = {0, 0, 0};
   auto request = [&](int s, unsigned long long (&d)[3]) {
@@ -336,9 +336,8 @@ DEVI void elim_follow_d(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double* ou
     const double l0 = need_l0 ? __longlong_as_double((long long)v[1]) : 0.0;
     const double l1 = need_l1 ? __longlong_as_double((long long)v[2]) : 0.0;
     if (s < 7) request(s + 1, nv);
-    const f64x4 pa = CAL_MFMA(w, (J == 0 ? x0[0][u] : x1[0][u]), zero4);
-    const f64x4 pb = CAL_MFMA(w, (J == 0 ? x0[1][u] : x1[1][u]), zero4);
-    const double la = pa[0], lb = pb[0];
+    const double la = CAL_PANEL(w, (J == 0 ? x0[0][u] : x1[0][u]));
+    const double lb = CAL_PANEL(w, (J == 0 ? x0[1][u] : x1[1][u]));
     // what the NEXT step's panel products wait for first, then the next block's diagonal (its tile (0,0) first: the pivot chain of
     // the block this wave is about to be the chief of starts there)
     if (need_l0) { x0[0] = CAL_MFMA(l0, la, x0[0]); x0[1] = CAL_MFMA(l0, lb, x0[1]); }
@@ -351,7 +350,6 @@ DEVI void elim_follow_d(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double* ou
       out0[l16 * out_row + col * out_col] = la;
       out1[l16 * out_row + col * out_col] = lb;
     }
-    CAL_KEEP(pa); CAL_KEEP(pb);
     v[0] = nv[0]; v[1] = nv[1]; v[2] = nv[2];
   }
 }
@@ -371,7 +369,6 @@ DEVI void elim_follow_owner(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double
                             f64x4& n00, f64x4& n01, f64x4& n11, bool cross, f64x4 (&nx0)[2], f64x4 (&nx1)[2],
                             const double* c0p, const double* c1p, bool dwave, int* prog, int prog_base) {
   const int l16 = lane & 15, lk = lane >> 4;
-  const f64x4 zero4 = {0.0, 0.0, 0.0, 0.0};
   const unsigned long long* const sub = reinterpret_cast<const unsigned long long*>(ch.buf) + lane;
   unsigned long long v[3] = {0, 0, 0}, nv[3] = {0, 0, 0};
   auto request = [&](int s, unsigned long long (&d)[3]) {
@@ -402,9 +399,8 @@ DEVI void elim_follow_owner(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double
       asm volatile("" ::: "memory");
     };
     if (cross) ask_cross();
-    const f64x4 pa = CAL_MFMA(w, (J == 0 ? x0[0][u] : x1[0][u]), zero4);
-    const f64x4 pb = CAL_MFMA(w, (J == 0 ? x0[1][u] : x1[1][u]), zero4);
-    const double la = pa[0], lb = pb[0];
+    const double la = CAL_PANEL(w, (J == 0 ? x0[0][u] : x1[0][u]));
+    const double lb = CAL_PANEL(w, (J == 0 ? x0[1][u] : x1[1][u]));
     if (need_l0) { x0[0] = CAL_MFMA(l0, la, x0[0]); x0[1] = CAL_MFMA(l0, lb, x0[1]); }
     if (need_l1 && !(J == 1 && u == 3)) { x1[0] = CAL_MFMA(l1, la, x1[0]); x1[1] = CAL_MFMA(l1, lb, x1[1]); }
     n00 = CAL_MFMA(la, la, n00);
@@ -428,7 +424,6 @@ DEVI void elim_follow_owner(f64x4 (&x0)[2], f64x4 (&x1)[2], double* out0, double
       nx0[0] = CAL_MFMA(ca, la, nx0[0]); nx1[0] = CAL_MFMA(cb, la, nx1[0]);
       nx0[1] = CAL_MFMA(ca, lb, nx0[1]); nx1[1] = CAL_MFMA(cb, lb, nx1[1]);
     }
-    CAL_KEEP(pa); CAL_KEEP(pb);
     v[0] = nv[0]; v[1] = nv[1]; v[2] = nv[2];
   }
 }

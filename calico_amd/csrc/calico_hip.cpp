@@ -397,6 +397,36 @@ int32_t calico_debug_roll_table(int32_t spline_order, int32_t lane, uint32_t* ou
 
 int64_t calico_debug_lds_attribute_calls(void) { return cal::lds_attribute_calls(); }
 
+int32_t calico_debug_panel_product(int32_t device, int32_t form, const double* w, const double* x, double* out) {
+  if ((form != 0 && form != 1) || !w || !x || !out) return CALICO_INVALID_ARGUMENT;
+  if (hipSetDevice(device) != hipSuccess) return CALICO_INTERNAL;
+  cal::DevBuf<double> d_w, d_x, d_out;
+  if (d_w.upload(std::vector<double>(w, w + 64), nullptr) != hipSuccess || d_x.upload(std::vector<double>(x, x + 64), nullptr) != hipSuccess ||
+      d_out.alloc(64) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)      // (the uploads' sources are temporaries)
+    return CALICO_INTERNAL;
+  if (cal::launch_debug_panel_product(form, d_w.p, d_x.p, d_out.p, nullptr) != hipSuccess ||
+      hipMemcpy(out, d_out.p, 64 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return CALICO_INTERNAL;
+  return CALICO_OK;
+}
+
+int32_t calico_debug_block_elim(int32_t device, int32_t n_row_tiles, const double* D, const double* X, double* L_out, double* Z_out,
+                                double* Minv_out) {
+  if (n_row_tiles < 1 || n_row_tiles > cal::debug_block_elim_max_tiles() || !D || !X || !L_out || !Z_out || !Minv_out) return CALICO_INVALID_ARGUMENT;
+  if (hipSetDevice(device) != hipSuccess) return CALICO_INTERNAL;
+  const size_t nx = size_t(16) * size_t(n_row_tiles) * 32;
+  cal::DevBuf<double> d_D, d_X, d_L, d_Z, d_M;
+  if (d_D.upload(std::vector<double>(D, D + 1024), nullptr) != hipSuccess || d_X.upload(std::vector<double>(X, X + nx), nullptr) != hipSuccess ||
+      d_L.alloc(1024) != hipSuccess || d_Z.alloc(nx) != hipSuccess || d_M.alloc(1024) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess)
+    return CALICO_INTERNAL;
+  if (cal::launch_debug_block_elim(n_row_tiles, d_D.p, d_X.p, d_L.p, d_Z.p, d_M.p, nullptr) != hipSuccess ||
+      hipMemcpy(L_out, d_L.p, 1024 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(Z_out, d_Z.p, nx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(Minv_out, d_M.p, 1024 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+    return CALICO_INTERNAL;
+  return CALICO_OK;
+}
+
 int32_t calico_get_iterations(calico_problem* p, calico_iteration* out, int32_t max_rows, int32_t* n_out) {
   if (!p || !out || !n_out) return CALICO_INVALID_ARGUMENT;
   const int n = std::min<int>(max_rows, int(p->iterations.size()));

@@ -70,6 +70,19 @@ int64_t calico_debug_lds_attribute_calls(void);
 int32_t calico_debug_camera_unproject_chunked(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n,
                                               const double* pixels, double* bearings_out, uint8_t* valid_out, int64_t chunk);
 
+/* One panel product of the block elimination (block_elim.hpp) on one wave: w, x, out hold one double per lane (64). x: register u
+ * of a tile -- lane (l16 = lane & 15, lk = lane >> 4) = entry (row l16, column lk) of a 16x4 tile; w: entry (l16 & 3, lk) of a 4x4
+ * factor W in every lane; out: lane (l16, lk) = (x Wᵀ)(l16, lk). form 0: register 0 of the 16x16x4 product, form 1: CAL_PANEL (the
+ * 4x4x4 form the kernels use). */
+int32_t calico_debug_panel_product(int32_t device, int32_t form, const double* w, const double* x, double* out);
+
+/* One 32x32 block eliminated by the header's own code in a workgroup of its own: elim_chief<1> on wave 0, elim_follow with the
+ * identity tiles on wave 1 and with the n_row_tiles (1..3) loaded tiles of X on wave 2. D: [32][32] symmetric positive definite
+ * (the lower triangle is read), X: [16 n_row_tiles][32]; L_out: the Cholesky factor (zeros above the diagonal), Z_out = X L⁻ᵀ,
+ * Minv_out = L⁻ᵀ, all row-major. A bad pivot is not patched: NaN from its column on, and the call returns CALICO_OK. */
+int32_t calico_debug_block_elim(int32_t device, int32_t n_row_tiles, const double* D, const double* X, double* L_out, double* Z_out,
+                                double* Minv_out);
+
 #ifdef __cplusplus
 }
 #endif

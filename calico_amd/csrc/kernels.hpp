@@ -81,6 +81,11 @@ size_t dense_block_solve_lds_bytes();
 void launch_bcr_level(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, int level, int keep0, int n_keep, const LmOptionsDev& o,
                       const double* x, const BlockDev* blocks, int n_blocks, int with_post_eval, IterLog* log, int log_cap, int jacobi,
                       hipStream_t s, int schur_ks, int* fan_word, const BcrInlineNodes& inl, bool elim, bool roll);
+// test hooks (calico_hip_testing.h): one panel product of block_elim.hpp (form 0: register 0 of the 16x16x4 product, 1: CAL_PANEL), and
+// one 32x32 block eliminated by its chief and followers in a workgroup of their own (n_row_tiles <= debug_block_elim_max_tiles())
+hipError_t launch_debug_panel_product(int form, const double* w, const double* x, double* out, hipStream_t s);
+int debug_block_elim_max_tiles();
+hipError_t launch_debug_block_elim(int n_row_tiles, const double* D, const double* X, double* L, double* Z, double* Minv, hipStream_t s);
 void launch_bcr_schur(const SolveArgs& a, const BcrArgs& b, int ks, const LmOptionsDev& o, hipStream_t s);
 void launch_bcr_back(const SolveArgs& a, const BcrArgs& b, int node0, int n_nodes, bool top, bool extras, bool border_rows, int q_max,
                      const double* x, double* x_cand, const BlockDev* blocks, int n_blocks, const BcrTopSeps& ts, hipStream_t s);
