@@ -87,6 +87,13 @@ class PredictionOptions(C.Structure):
     _fields_ = [("apply_loss", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class ResectionOptions(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("huber_scale", C.c_double), ("min_points", C.c_int32)]
+
+
+RESECT_OK, RESECT_TOO_FEW_POINTS, RESECT_NO_START, RESECT_NOT_CONVERGED, RESECT_DEGENERATE = 0, 1, 2, 3, 4
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -145,10 +152,12 @@ ABI_SYMBOLS = [
     "default_observability_options", "observability_compute", "observability_info", "observability_get_spectrum",
     "observability_get_directions", "observability_get_block", "observability_get_matrix",
     "camera_unproject", "camera_project_points", "sensor_unproject", "projection_uncertainty",
+    "default_resection_options", "camera_resect",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
-                "debug_lds_attribute_calls", "debug_camera_unproject_chunked", "debug_panel_product", "debug_block_elim"]
+                "debug_lds_attribute_calls", "debug_camera_unproject_chunked", "debug_panel_product", "debug_block_elim",
+                "debug_camera_resect_chunked"]
 
 
 class CApi:
@@ -227,6 +236,12 @@ class CApi:
                 g("sensor_unproject", C.c_int32, [P, C.c_int32, C.c_int64, D, D, U8])
                 g("projection_uncertainty", C.c_int32, [P, C.c_int32, C.c_int32, C.c_double, C.c_int64, D, D, U8])
                 g("debug_camera_unproject_chunked", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, C.c_int64, D, D, U8, C.c_int64])
+            if hasattr(self.lib, self.prefix + "camera_resect"):
+                I64, RO = C.POINTER(C.c_int64), C.POINTER(ResectionOptions)
+                resect = [C.c_int32, C.c_int32, D, C.c_int32, C.c_int64, I64, D, D, D, D, RO, D, D, D, I, I, U8, D]
+                g("default_resection_options", None, [RO])
+                g("camera_resect", C.c_int32, resect)
+                g("debug_camera_resect_chunked", C.c_int32, resect + [C.c_int64])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -306,6 +321,53 @@ def camera_project_points(api, model, intrinsics, points, jacobians=False, devic
     if jacobians:
         return px, valid[:n].astype(bool), dp, dk
     return px, valid[:n].astype(bool)
+
+
+class Resection:
+    """What calico_camera_resect returns: per frame q (x, y, z, w) and t of T_camera_chart, rms (pixels), n_used, iterations,
+    status (RESECT_*), and cov (n_frames, 6, 6) or None."""
+
+    def __init__(self, q, t, rms, n_used, iterations, status, cov):
+        self.q, self.t, self.rms, self.n_used, self.iterations, self.status, self.cov = q, t, rms, n_used, iterations, status, cov
+
+
+def resection_options(api, **kw):
+    """The library's default calico_resection_options with the given fields replaced."""
+    o = ResectionOptions()
+    api.default_resection_options(C.byref(o))
+    for name, v in kw.items():
+        if not hasattr(o, name):
+            raise TypeError("no resection option %r" % name)
+        setattr(o, name, v)
+    return o
+
+
+def camera_resect(api, model, intrinsics, frame_offsets, pixels, points, q_init=None, t_init=None, options=None, covariance=False,
+                  device=0, chunk=None):
+    """calico_camera_resect: the pose T_camera_chart of every frame. frame_offsets (n_frames + 1) cuts pixels (N, 2) and chart
+    points (N, 3) into frames; q_init (n_frames, 4) and t_init (n_frames, 3) together, or neither (homography start: planar
+    charts). options: a ResectionOptions (resection_options(api, ...)) or None. chunk: test hook (pairs per host-side pass)."""
+    k = _f64(intrinsics).ravel()
+    off = np.ascontiguousarray(frame_offsets, dtype=np.int64).ravel()
+    nf = len(off) - 1
+    px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
+    if nf < 0 or len(px) != len(pt) or (nf >= 0 and len(off) and off[-1] != len(px)):
+        raise ValueError("frame_offsets must have n_frames + 1 entries and end at the number of pairs")
+    qi = None if q_init is None else _f64(q_init).reshape(nf, 4)
+    ti = None if t_init is None else _f64(t_init).reshape(nf, 3)
+    m = max(nf, 1)
+    q, t, rms = np.zeros((m, 4)), np.zeros((m, 3)), np.zeros(m)
+    used, its, status = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+    cov = np.zeros((m, 6, 6)) if covariance else None
+    args = [int(device), int(model), _dp(k), k.size, nf, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(px), _dp(pt),
+            None if qi is None else _dp(qi), None if ti is None else _dp(ti), None if options is None else C.byref(options),
+            _dp(q), _dp(t), _dp(rms), _ip(used), _ip(its), _u8p(status), _dp(cov) if covariance else None]
+    if chunk is None:
+        st = api.camera_resect(*args)
+    else:
+        st = api.debug_camera_resect_chunked(*(args + [int(chunk)]))
+    _check_free(api, st)
+    return Resection(q[:nf], t[:nf], rms[:nf], used[:nf], its[:nf], status[:nf], cov[:nf] if covariance else None)
 
 
 class Problem:

@@ -129,3 +129,21 @@ def InitializePinholeAndPoses(all_detections: List[Dict[int, np.ndarray]], model
         R_chart_camera.append(R.T)
         t_chart_camera.append(-R.T @ t)
     return intrinsics, R_chart_camera, t_chart_camera
+
+
+def InitializePoses(camera, all_detections: List[Dict[int, np.ndarray]], model_definition: Dict[int, np.ndarray]
+                    ) -> Tuple[List[np.ndarray], List[np.ndarray], np.ndarray]:
+    """The pose half of InitializePinholeAndPoses for ANY camera model, at the camera's own model and current intrinsics, on
+    the device (Camera.EstimateChartPoses: homography start from the unprojected pixels, then Levenberg-Marquardt on the
+    library's projection). Returns ([R_chart_camera per frame], [t_chart_camera per frame], ok (n_frames,) bool) in the
+    conventions of InitializePinholeAndPoses; a frame that is not ok (too few points, no start, not converged, degenerate)
+    carries the identity and must not be handed to FitSpline."""
+    r = camera.EstimateChartPoses(all_detections, model_definition)
+    R_chart_camera, t_chart_camera = [], []
+    for (x, y, z, w), t in zip(r["q"], r["t"]):
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        R_chart_camera.append(R.T)
+        t_chart_camera.append(-R.T @ t)
+    return R_chart_camera, t_chart_camera, np.asarray(r["status"]) == 0

@@ -83,6 +83,14 @@ int32_t calico_debug_panel_product(int32_t device, int32_t form, const double* w
 int32_t calico_debug_block_elim(int32_t device, int32_t n_row_tiles, const double* D, const double* X, double* L_out, double* Z_out,
                                 double* Minv_out);
 
+/* calico_camera_resect with the host-side chunk -- the most pairs uploaded, resected and downloaded per pass; a frame is never
+ * split, one larger than the chunk travels alone -- given by the caller (chunk_pairs >= 1) instead of the library's default. */
+int32_t calico_debug_camera_resect_chunked(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics,
+                                           int64_t n_frames, const int64_t* frame_offsets, const double* pixels, const double* points,
+                                           const double* q_init, const double* t_init, const calico_resection_options* o,
+                                           double* q_out, double* t_out, double* rms_out, int32_t* n_used_out, int32_t* iterations_out,
+                                           uint8_t* status_out, double* cov_out, int64_t chunk_pairs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // camera.cpp — the camera model over free pixels and points (this part of the C ABI of include/calico_hip.h): unprojection,
-// the forward model with its derivatives, and the projection uncertainty map of a solved problem. The kernels are
-// camera_kernels.hip. Everything that can be checked without a device is checked before the first HIP call.
+// the forward model with its derivatives, the projection uncertainty map of a solved problem (kernels: camera_kernels.hip) and
+// the chart resection (resect_kernels.hip). Everything that can be checked without a device is checked before the first HIP call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -95,9 +95,122 @@ int unproject_free(int device, int model, const double* intrinsics, int n_intrin
   return CALICO_OK;
 }
 
+// pairs per pass of calico_camera_resect: upload, kernel, download (2^20 pairs: 40 MB in, 17 MB of workspace). A frame is never
+// split; one with more pairs than this travels alone.
+constexpr int64_t kResectChunkPairs = int64_t(1) << 20;
+
+int resect_free(int device, int model, const double* intrinsics, int n_intrinsics, int64_t n_frames, const int64_t* offsets,
+                const double* pixels, const double* points, const double* q_init, const double* t_init,
+                const calico_resection_options* opt, double* q_out, double* t_out, double* rms_out, int32_t* n_used_out,
+                int32_t* iterations_out, uint8_t* status_out, double* cov_out, int64_t chunk_pairs) {
+  const char* what = "calico_camera_resect";
+  if (int rc = check_model(nullptr, what, model, intrinsics, n_intrinsics)) return rc;
+  if (n_frames < 0) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": n_frames must be >= 0");
+  calico_resection_options o;
+  calico_default_resection_options(&o);
+  if (opt) o = *opt;
+  if (!std::isfinite(o.step_tolerance) || !(o.step_tolerance > 0.0))
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": step_tolerance must be finite and > 0");
+  if (o.max_iterations < 1) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": max_iterations must be >= 1");
+  if (!std::isfinite(o.huber_scale) || o.huber_scale < 0.0)
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": huber_scale must be finite and >= 0");
+  if (o.min_points < 4) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": min_points must be >= 4");
+  if ((q_init == nullptr) != (t_init == nullptr))
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": q_init and t_init are given together or not at all");
+  if (chunk_pairs < 1) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": chunk must be >= 1");
+  if (n_frames == 0) return CALICO_OK;
+  if (!offsets || !q_out || !t_out || !rms_out || !n_used_out || !iterations_out || !status_out)
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": null frame offsets or output buffer");
+  if (offsets[0] != 0) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": frame_offsets must start at 0");
+  for (int64_t f = 0; f < n_frames; ++f)
+    if (offsets[f + 1] < offsets[f])
+      return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": frame_offsets decrease at frame " + std::to_string(f));
+  const int64_t N = offsets[n_frames];
+  if (N > 0 && (!pixels || !points)) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": null pixels or points");
+  if (int rc = select_device(what, device)) return rc;
+  // chunks of whole frames: [f0, f1) with at most chunk_pairs pairs, or one frame
+  std::vector<int64_t> cuts(1, 0);
+  int64_t max_pairs = 0, max_frames = 0;
+  for (int64_t f0 = 0; f0 < n_frames;) {
+    int64_t f1 = f0 + 1;
+    while (f1 < n_frames && offsets[f1 + 1] - offsets[f0] <= chunk_pairs) ++f1;
+    cuts.push_back(f1);
+    max_pairs = std::max(max_pairs, offsets[f1] - offsets[f0]);
+    max_frames = std::max(max_frames, f1 - f0);
+    f0 = f1;
+  }
+  const size_t K = size_t(n_intrinsics), F = size_t(max_frames), P = size_t(max_pairs);
+  Buf<double> d_k, d_px, d_pt, d_ws, d_qi, d_ti, d_q, d_t, d_rms, d_cov;
+  Buf<int64_t> d_off;
+  Buf<int32_t> d_used, d_it;
+  Buf<uint8_t> d_fl, d_st;
+  FREE_TRY(what, d_k.alloc(K)); FREE_TRY(what, d_px.alloc(P * 2)); FREE_TRY(what, d_pt.alloc(P * 3)); FREE_TRY(what, d_ws.alloc(P * 2));
+  FREE_TRY(what, d_fl.alloc(P)); FREE_TRY(what, d_off.alloc(F + 1));
+  if (q_init) { FREE_TRY(what, d_qi.alloc(F * 4)); FREE_TRY(what, d_ti.alloc(F * 3)); }
+  FREE_TRY(what, d_q.alloc(F * 4)); FREE_TRY(what, d_t.alloc(F * 3)); FREE_TRY(what, d_rms.alloc(F)); FREE_TRY(what, d_used.alloc(F));
+  FREE_TRY(what, d_it.alloc(F)); FREE_TRY(what, d_st.alloc(F));
+  if (cov_out) FREE_TRY(what, d_cov.alloc(F * 36));
+  FREE_TRY(what, hipMemcpy(d_k.p, intrinsics, K * sizeof(double), hipMemcpyHostToDevice));
+  ResectArgs a = {};
+  a.k = d_k.p; a.offsets = d_off.p; a.pixels = d_px.p; a.points = d_pt.p; a.ws = d_ws.p; a.flags = d_fl.p;
+  a.q_init = q_init ? d_qi.p : nullptr; a.t_init = q_init ? d_ti.p : nullptr;
+  a.max_iterations = o.max_iterations; a.step_tolerance = o.step_tolerance; a.huber_scale = o.huber_scale; a.min_points = o.min_points;
+  a.q_out = d_q.p; a.t_out = d_t.p; a.rms_out = d_rms.p; a.n_used_out = d_used.p; a.iterations_out = d_it.p; a.status_out = d_st.p;
+  a.cov_out = cov_out ? d_cov.p : nullptr;
+  std::vector<int64_t> local;
+  for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+    const int64_t f0 = cuts[c], f1 = cuts[c + 1], nf = f1 - f0, p0 = offsets[f0], np = offsets[f1] - p0;
+    local.assign(size_t(nf) + 1, 0);
+    for (int64_t f = 0; f <= nf; ++f) local[size_t(f)] = offsets[f0 + f] - p0;
+    FREE_TRY(what, hipMemcpy(d_off.p, local.data(), local.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (np > 0) {
+      FREE_TRY(what, hipMemcpy(d_px.p, pixels + 2 * p0, size_t(np) * 2 * sizeof(double), hipMemcpyHostToDevice));
+      FREE_TRY(what, hipMemcpy(d_pt.p, points + 3 * p0, size_t(np) * 3 * sizeof(double), hipMemcpyHostToDevice));
+      FREE_TRY(what, hipMemset(d_fl.p, 0, size_t(np)));
+    }
+    if (q_init) {
+      FREE_TRY(what, hipMemcpy(d_qi.p, q_init + 4 * f0, size_t(nf) * 4 * sizeof(double), hipMemcpyHostToDevice));
+      FREE_TRY(what, hipMemcpy(d_ti.p, t_init + 3 * f0, size_t(nf) * 3 * sizeof(double), hipMemcpyHostToDevice));
+    }
+    a.n_frames = nf;
+    FREE_TRY(what, launch_camera_resect(model, a, nullptr));
+    FREE_TRY(what, hipMemcpy(q_out + 4 * f0, d_q.p, size_t(nf) * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(t_out + 3 * f0, d_t.p, size_t(nf) * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(rms_out + f0, d_rms.p, size_t(nf) * sizeof(double), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(n_used_out + f0, d_used.p, size_t(nf) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(iterations_out + f0, d_it.p, size_t(nf) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(status_out + f0, d_st.p, size_t(nf), hipMemcpyDeviceToHost));
+    if (cov_out) FREE_TRY(what, hipMemcpy(cov_out + 36 * f0, d_cov.p, size_t(nf) * 36 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return CALICO_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void calico_default_resection_options(calico_resection_options* o) {
+  if (!o) return;
+  o->max_iterations = 30; o->step_tolerance = 1e-11; o->huber_scale = 0.0; o->min_points = 4;
+}
+
+int32_t calico_camera_resect(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n_frames,
+                             const int64_t* frame_offsets, const double* pixels, const double* points, const double* q_init,
+                             const double* t_init, const calico_resection_options* o, double* q_out, double* t_out, double* rms_out,
+                             int32_t* n_used_out, int32_t* iterations_out, uint8_t* status_out, double* cov_out) {
+  return resect_free(device, model, intrinsics, n_intrinsics, n_frames, frame_offsets, pixels, points, q_init, t_init, o, q_out, t_out,
+                     rms_out, n_used_out, iterations_out, status_out, cov_out, kResectChunkPairs);
+}
+
+// test hook (calico_hip_testing.h)
+int32_t calico_debug_camera_resect_chunked(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n_frames,
+                                           const int64_t* frame_offsets, const double* pixels, const double* points, const double* q_init,
+                                           const double* t_init, const calico_resection_options* o, double* q_out, double* t_out,
+                                           double* rms_out, int32_t* n_used_out, int32_t* iterations_out, uint8_t* status_out,
+                                           double* cov_out, int64_t chunk_pairs) {
+  return resect_free(device, model, intrinsics, n_intrinsics, n_frames, frame_offsets, pixels, points, q_init, t_init, o, q_out, t_out,
+                     rms_out, n_used_out, iterations_out, status_out, cov_out, chunk_pairs);
+}
 
 int32_t calico_camera_unproject(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n,
                                 const double* pixels, double* bearings_out, uint8_t* valid_out) {

@@ -148,4 +148,21 @@ struct UncertaintyArgs {
 };
 hipError_t launch_projection_uncertainty(int model, const UncertaintyArgs& a, hipStream_t s);
 
+// ---- chart resection (resect_kernels.hip): one wave per frame of a ragged batch of (pixel, chart point) pairs ----------------
+// All pointers are device memory. offsets (n_frames + 1) start at 0 and index pixels / points / ws / flags; q_init and t_init are
+// both nullptr (the kernel makes its own start) or n_frames x 4 / x 3; cov_out may be nullptr.
+struct ResectArgs {
+  const double* k;                                        // intrinsics, read through wave-uniform addresses
+  int64_t n_frames;
+  const int64_t* offsets;
+  const double* pixels;                                   // N x 2
+  const double* points;                                   // N x 3, chart frame
+  const double* q_init; const double* t_init;
+  double* ws;                                             // N x 2: the start's normalised image points
+  uint8_t* flags;                                         // N: usable for the start, valid at the current / candidate pose
+  int max_iterations; double step_tolerance; double huber_scale; int min_points;
+  double* q_out; double* t_out; double* rms_out; int* n_used_out; int* iterations_out; uint8_t* status_out; double* cov_out;
+};
+hipError_t launch_camera_resect(int model, const ResectArgs& a, hipStream_t s);
+
 }  // namespace cal

@@ -276,7 +276,53 @@ PYBIND11_MODULE(_calico, m) {
              raise_if_error(self.UnprojectPixels(to_pixels(pixels), &b, &valid, device));
              return bearings_tuple(b, valid);
            },
-           py::arg("pixels"), py::arg("device") = 0);
+           py::arg("pixels"), py::arg("device") = 0)
+      // all_detections: a list of {feature id: pixel}; model_definition: {feature id: chart point (x, y[, z])}; options: None or a
+      // dict of calico_resection_options fields. Returns a dict of arrays, one row per frame.
+      .def("EstimateChartPoses",
+           [](const Camera& self, const std::vector<std::map<int, Vector2d>>& all_detections, const py::dict& model_definition,
+              const py::object& options, bool covariance, int device) {
+             std::map<int, Vector3d> model;
+             for (auto kv : model_definition) {
+               auto arr = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(kv.second);
+               if (!arr || (arr.size() != 2 && arr.size() != 3)) throw py::type_error("a chart point is (x, y) or (x, y, z)");
+               model[py::cast<int>(kv.first)] = Vector3d(arr.data()[0], arr.data()[1], arr.size() == 3 ? arr.data()[2] : 0.0);
+             }
+             calico_resection_options o;
+             calico_default_resection_options(&o);
+             if (!options.is_none()) {
+               for (auto kv : py::cast<py::dict>(options)) {
+                 const std::string name = py::cast<std::string>(kv.first);
+                 if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+                 else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+                 else if (name == "huber_scale") o.huber_scale = py::cast<double>(kv.second);
+                 else if (name == "min_points") o.min_points = py::cast<int>(kv.second);
+                 else throw py::type_error("no resection option '" + name + "'");
+               }
+             }
+             CameraModel::ChartResection r;
+             raise_if_error(self.EstimateChartPoses(all_detections, model, &o, &r, covariance, device));
+             const py::ssize_t n = py::ssize_t(r.NumFrames());
+             py::array_t<double> q({n, py::ssize_t(4)}), t({n, py::ssize_t(3)}), rms(n);
+             py::array_t<int32_t> used(n), its(n);
+             py::array_t<uint8_t> status(n);
+             std::copy(r.q.begin(), r.q.end(), q.mutable_data());
+             std::copy(r.t.begin(), r.t.end(), t.mutable_data());
+             std::copy(r.rms.begin(), r.rms.end(), rms.mutable_data());
+             std::copy(r.n_used.begin(), r.n_used.end(), used.mutable_data());
+             std::copy(r.iterations.begin(), r.iterations.end(), its.mutable_data());
+             std::copy(r.status.begin(), r.status.end(), status.mutable_data());
+             py::dict out;
+             out["q"] = q; out["t"] = t; out["rms"] = rms; out["n_used"] = used; out["iterations"] = its; out["status"] = status;
+             if (covariance) {
+               py::array_t<double> cov({n, py::ssize_t(6), py::ssize_t(6)});
+               std::copy(r.cov.begin(), r.cov.end(), cov.mutable_data());
+               out["cov"] = cov;
+             }
+             return out;
+           },
+           py::arg("all_detections"), py::arg("model_definition"), py::arg("options") = py::none(), py::arg("covariance") = false,
+           py::arg("device") = 0);
 
   // ---- trajectory, world model ----
   py::class_<Trajectory, std::shared_ptr<Trajectory>>(m, "Trajectory")

@@ -873,6 +873,46 @@ class CameraModel {
     if (!v[0]) return InvalidArgumentError("pixel (" + std::to_string(pixel.x()) + ", " + std::to_string(pixel.y()) + ") does not unproject");
     return b[0];
   }
+
+  /// What ResectChart leaves, frame by frame (calico_camera_resect): T_camera_chart as q (x, y, z, w) and t, the RMS pixel
+  /// residual, the pairs used, the steps tried, the status (CALICO_RESECT_*) and, on request, (J^T W J)^-1 in [delta_rot, t].
+  struct ChartResection {
+    std::vector<double> q, t, rms, cov;      // 4, 3, 1 and (with covariance) 36 doubles per frame
+    std::vector<int32_t> n_used, iterations;
+    std::vector<uint8_t> status;
+    size_t NumFrames() const { return status.size(); }
+    bool Ok(size_t frame) const { return status[frame] == CALICO_RESECT_OK; }
+  };
+  /// Chart resection over arrays, on the device: frame f owns the pairs [frame_offsets[f], frame_offsets[f + 1]) of pixels and
+  /// chart points. q_init / t_init (4 and 3 doubles per frame): both or neither (neither: the homography start of a planar
+  /// chart). options == nullptr: the library's defaults.
+  static Status ResectChart(CameraIntrinsicsModel model, const VectorXd& intrinsics, const std::vector<int64_t>& frame_offsets,
+                            const std::vector<Vector2d>& pixels, const std::vector<Vector3d>& points, const calico_resection_options* options,
+                            ChartResection* out, bool covariance = false, const std::vector<double>* q_init = nullptr,
+                            const std::vector<double>* t_init = nullptr, int device = 0) {
+    if (!out) return InvalidArgumentError("ResectChart: null output");
+    if (frame_offsets.empty() || pixels.size() != points.size() || frame_offsets.back() != int64_t(pixels.size()))
+      return InvalidArgumentError("ResectChart: frame_offsets must have n_frames + 1 entries and end at the number of pairs");
+    const size_t nf = frame_offsets.size() - 1, n = pixels.size();
+    if ((q_init && q_init->size() != 4 * nf) || (t_init && t_init->size() != 3 * nf))
+      return InvalidArgumentError("ResectChart: q_init / t_init must hold 4 / 3 doubles per frame");
+    std::vector<double> px(2 * n), pt(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+      px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y();
+      pt[3 * i] = points[i][0]; pt[3 * i + 1] = points[i][1]; pt[3 * i + 2] = points[i][2];
+    }
+    ChartResection r;
+    r.q.assign(4 * nf, 0.0); r.t.assign(3 * nf, 0.0); r.rms.assign(nf, 0.0); r.n_used.assign(nf, 0); r.iterations.assign(nf, 0);
+    r.status.assign(nf, 0);
+    if (covariance) r.cov.assign(36 * nf, 0.0);
+    const int st = calico_camera_resect(device, int(model), intrinsics.data(), int(intrinsics.size()), int64_t(nf), frame_offsets.data(), px.data(),
+                                        pt.data(), q_init ? q_init->data() : nullptr, t_init ? t_init->data() : nullptr, options, r.q.data(),
+                                        r.t.data(), r.rms.data(), r.n_used.data(), r.iterations.data(), r.status.data(),
+                                        covariance ? r.cov.data() : nullptr);
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+    *out = std::move(r);
+    return OkStatus();
+  }
 };
 
 inline bool ProjectPointHost(CameraIntrinsicsModel model, const double* k, const cal::V3& p, double pix[2]) {
@@ -912,6 +952,27 @@ class Camera : public SensorCommon {
   Status UnprojectPixels(const std::vector<Vector2d>& pixels, std::vector<Vector3d>* bearings, std::vector<uint8_t>* valid, int device = 0) const {
     if (model_ == CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
     return CameraModel::UnprojectPixels(model_, intrinsics_, pixels, bearings, valid, device);
+  }
+  /// Where this camera was when each frame of a chart was detected: CameraModel::ResectChart with this camera's model and
+  /// current intrinsics. frames[f] maps a feature id to its pixel, model_definition a feature id to its chart point; the
+  /// pairs of a frame are taken in ascending id order. A detected id the model does not define is an argument error.
+  Status EstimateChartPoses(const std::vector<std::map<int, Vector2d>>& frames, const std::map<int, Vector3d>& model_definition,
+                            const calico_resection_options* options, CameraModel::ChartResection* out, bool covariance = false,
+                            int device = 0) const {
+    if (model_ == CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
+    std::vector<int64_t> offsets(1, 0);
+    std::vector<Vector2d> pixels;
+    std::vector<Vector3d> points;
+    for (const auto& frame : frames) {
+      for (const auto& kv : frame) {
+        const auto it = model_definition.find(kv.first);
+        if (it == model_definition.end()) return InvalidArgumentError("EstimateChartPoses: feature " + std::to_string(kv.first) + " is not in the model definition");
+        pixels.push_back(kv.second);
+        points.push_back(it->second);
+      }
+      offsets.push_back(int64_t(pixels.size()));
+    }
+    return CameraModel::ResectChart(model_, intrinsics_, offsets, pixels, points, options, out, covariance, nullptr, nullptr, device);
   }
   StatusOr<int> AddParametersToProblem(Problem& problem) final {
     return AddCommonParameters(problem, model_ != CameraIntrinsicsModel::kNone, "camera");

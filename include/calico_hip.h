@@ -136,7 +136,7 @@ typedef struct calico_iteration {
 int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
- * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points); like a handle's message it
+ * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -552,6 +552,61 @@ int32_t calico_sensor_unproject(calico_problem* p, int32_t sensor, int64_t n, co
 #define CALICO_FRAME_RIG 1
 int32_t calico_projection_uncertainty(calico_problem* p, int32_t sensor, int32_t frame, double range, int64_t n,
                                       const double* pixels, double* cov_out, uint8_t* valid_out);
+
+/* ---- chart resection: per-frame camera poses at given intrinsics, for every camera model ---- */
+/* Where the camera was when each image of a planar chart was taken: for each of n_frames frames -- frame f owns the pairs
+ * [frame_offsets[f], frame_offsets[f + 1]) of pixels (N x 2) and points (N x 3, chart frame) -- the pose T_camera_chart,
+ * p_camera = R(q) p_chart + t, that minimises  Sum rho(|pixel - project(intrinsics, R p + t)|^2)  in pixels, under this
+ * library's own projection (calico_project, the residuals), on the device. It is the step between a detector's output and
+ * calico_fit_spline, for all seven models and at KNOWN intrinsics (a previous calibration, a data sheet, a first pinhole pass);
+ * estimating intrinsics from scratch (Zhang's closed form, utils.InitializePinholeAndPoses) stays on the host.
+ *   start  q_init == t_init == NULL: the pixels are unprojected (calico_camera_unproject's map), the pairs with a valid unit
+ *          bearing of z > 0.1 give the plane-to-normalised-image homography (Hartley normalisation, normal equations), which
+ *          is split into a rotation (its nearest orthonormal matrix of determinant +1) and a translation with the chart in
+ *          front. Needs the frame's points in their z = 0 plane (|z| <= 1e-9 x the extent of the frame's points) and at
+ *          least 4 usable pairs: otherwise CALICO_RESECT_NO_START. Pixels without a valid unprojection are left out of the
+ *          start only. Otherwise q_init (n_frames x 4; x, y, z, w; normalised here) and t_init (n_frames x 3) start every
+ *          frame, and the points need not be planar.
+ *   refine Levenberg-Marquardt on [delta_rot, t] with the left perturbation R <- exp([delta_rot]x) R, over every pair the model
+ *          accepts at the current pose; rho = identity (huber_scale == 0) or Huber with huber_scale in pixels, weights rho',
+ *          no second-order term. A candidate at which the model rejects a pair that is valid at the current pose is a rejected
+ *          step; a candidate whose cost is within the cost's own rounding error of the current one is accepted. Stops after
+ *          an accepted step with |delta_rot|_inf < step_tolerance and |delta_t|_inf < step_tolerance max(1, |t|) taken at a
+ *          damping at or below its initial value (1e-4 of the diagonal: the step is the Gauss-Newton step to 1e-4) -- or a
+ *          rejected step that small: the pose is kept --, and after max_iterations steps (CALICO_RESECT_NOT_CONVERGED: the
+ *          last accepted pose).
+ * Outputs per frame: q_out (n_frames x 4, unit, w >= 0), t_out (x 3), rms_out = sqrt(Sum |residual|^2 / n_used) in pixels (no
+ * loss applied), n_used_out = the pairs the model accepts at the result, iterations_out = steps tried,
+ * status_out, and cov_out (may be NULL) = n_frames x 6 x 6 (J^T W J)^-1 at the result, order [delta_rot, t], pixel^2 units (no
+ * variance factor, as the covariance). CALICO_RESECT_TOO_FEW_POINTS: fewer than min_points pairs in the frame;
+ * CALICO_RESECT_DEGENERATE: J^T W J not positive definite (at the largest damping, or undamped at the result), no pair valid at
+ * the start, or a non-finite result. Every frame whose status is not OK or NOT_CONVERGED has q = (0, 0, 0, 1), t = 0, rms = 0,
+ * n_used = 0 and a zero cov. Frames are independent: a frame's result depends neither on the other frames of the call nor on
+ * its position, and repeated calls are bit-identical.
+ * Needs no problem handle (like calico_camera_unproject): owns its device memory, processes the frames in chunks, message in
+ * calico_last_error(NULL). CALICO_INVALID_ARGUMENT, before the device is touched: unknown model, n_intrinsics other than the
+ * model's count, n_frames < 0, offsets that do not start at 0 or decrease, a NULL required pointer with n_frames > 0, exactly one
+ * of q_init / t_init, step_tolerance not finite or <= 0, max_iterations < 1, huber_scale < 0 or not finite, min_points < 4.
+ * n_frames == 0 is CALICO_OK and touches nothing. */
+#define CALICO_RESECT_OK 0
+#define CALICO_RESECT_TOO_FEW_POINTS 1
+#define CALICO_RESECT_NO_START 2
+#define CALICO_RESECT_NOT_CONVERGED 3
+#define CALICO_RESECT_DEGENERATE 4
+typedef struct {
+  int32_t max_iterations;   /* 30 */
+  double step_tolerance;    /* 1e-11 */
+  double huber_scale;       /* 0 = no loss; pixels */
+  int32_t min_points;       /* 4; values below 4 are an argument error */
+} calico_resection_options;
+void calico_default_resection_options(calico_resection_options* o);
+int32_t calico_camera_resect(int32_t device, int32_t model, const double* intrinsics, int32_t n_intrinsics, int64_t n_frames,
+                             const int64_t* frame_offsets /* n_frames + 1 */, const double* pixels /* N x 2 */,
+                             const double* points /* N x 3, chart frame */, const double* q_init,
+                             const double* t_init /* both NULL, or n_frames x 4 / x 3 */,
+                             const calico_resection_options* o /* NULL = defaults */, double* q_out, double* t_out,
+                             double* rms_out, int32_t* n_used_out, int32_t* iterations_out, uint8_t* status_out,
+                             double* cov_out /* may be NULL */);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
