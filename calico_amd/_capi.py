@@ -92,6 +92,21 @@ class ResectionOptions(C.Structure):
 
 
 RESECT_OK, RESECT_TOO_FEW_POINTS, RESECT_NO_START, RESECT_NOT_CONVERGED, RESECT_DEGENERATE = 0, 1, 2, 3, 4
+RESECT_NOT_POSITIVE_DEFINITE = 5      # (calibration only: the frame dropped out)
+
+
+class CalibrationOptions(C.Structure):
+    """calico_calibration_options."""
+    _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("huber_scale", C.c_double), ("min_points", C.c_int32)]
+
+
+class CalibrationSummary(C.Structure):
+    """calico_calibration_summary."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("rms", C.c_double), ("frames_used", C.c_int32), ("pairs_used", C.c_int64), ("lambda_", C.c_double)]
+
+
+CALIB_OK, CALIB_TOO_FEW_FRAMES, CALIB_NOT_CONVERGED, CALIB_DEGENERATE = 0, 1, 2, 3
 
 
 class Iteration(C.Structure):
@@ -153,6 +168,7 @@ ABI_SYMBOLS = [
     "observability_get_directions", "observability_get_block", "observability_get_matrix",
     "camera_unproject", "camera_project_points", "sensor_unproject", "projection_uncertainty",
     "default_resection_options", "camera_resect",
+    "default_calibration_options", "camera_calibrate",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -242,6 +258,11 @@ class CApi:
                 g("default_resection_options", None, [RO])
                 g("camera_resect", C.c_int32, resect)
                 g("debug_camera_resect_chunked", C.c_int32, resect + [C.c_int64])
+            if hasattr(self.lib, self.prefix + "camera_calibrate"):
+                I64, CO = C.POINTER(C.c_int64), C.POINTER(CalibrationOptions)
+                g("default_calibration_options", None, [CO])
+                g("camera_calibrate", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, U8, C.c_int64, I64, D, D, D, D, CO, D, D, D, D, I, U8, D,
+                                                  C.POINTER(CalibrationSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -368,6 +389,61 @@ def camera_resect(api, model, intrinsics, frame_offsets, pixels, points, q_init=
         st = api.debug_camera_resect_chunked(*(args + [int(chunk)]))
     _check_free(api, st)
     return Resection(q[:nf], t[:nf], rms[:nf], used[:nf], its[:nf], status[:nf], cov[:nf] if covariance else None)
+
+
+class Calibration:
+    """What calico_camera_calibrate returns: intrinsics (K), per frame q (x, y, z, w) and t of T_camera_chart, rms (pixels),
+    n_used and status (RESECT_*), cov (K, K) or None, and the summary's fields: status (CALIB_*), iterations, initial_cost,
+    final_cost, total_rms, frames_used, pairs_used, lambda_."""
+
+    def __init__(self, intrinsics, q, t, rms, n_used, frame_status, cov, summary):
+        self.intrinsics, self.q, self.t, self.rms, self.n_used, self.frame_status, self.cov = intrinsics, q, t, rms, n_used, frame_status, cov
+        self.status, self.iterations = summary.status, summary.iterations
+        self.initial_cost, self.final_cost, self.total_rms = summary.initial_cost, summary.final_cost, summary.rms
+        self.frames_used, self.pairs_used, self.lambda_ = summary.frames_used, summary.pairs_used, summary.lambda_
+
+
+def calibration_options(api, **kw):
+    """The library's default calico_calibration_options with the given fields replaced."""
+    o = CalibrationOptions()
+    api.default_calibration_options(C.byref(o))
+    for name, v in kw.items():
+        if not hasattr(o, name):
+            raise TypeError("no calibration option %r" % name)
+        setattr(o, name, v)
+    return o
+
+
+def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points, q_init=None, t_init=None, free_mask=None, options=None,
+                     covariance=False, device=0):
+    """calico_camera_calibrate: the intrinsics of `model` jointly with the pose T_camera_chart of every frame. frame_offsets
+    (n_frames + 1) cuts pixels (N, 2) and chart points (N, 3) into frames; q_init (n_frames, 4) and t_init (n_frames, 3) together,
+    or neither (every frame is resected at intrinsics_init). free_mask: K flags, 0 = the entry is a constant; None = all free.
+    options: a CalibrationOptions (calibration_options(api, ...)) or None. Returns a Calibration."""
+    k = _f64(intrinsics_init).ravel()
+    off = np.ascontiguousarray(frame_offsets, dtype=np.int64).ravel()
+    nf = len(off) - 1
+    px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
+    if nf < 0 or len(px) != len(pt) or (len(off) and off[-1] != len(px)):
+        raise ValueError("frame_offsets must have n_frames + 1 entries and end at the number of pairs")
+    qi = None if q_init is None else _f64(q_init).reshape(nf, 4)
+    ti = None if t_init is None else _f64(t_init).reshape(nf, 3)
+    mask = None if free_mask is None else np.ascontiguousarray(np.asarray(free_mask) != 0, dtype=np.uint8).ravel()
+    if mask is not None and mask.size != k.size:
+        raise ValueError("free_mask must have one entry per intrinsic")
+    m = max(nf, 1)
+    k_out = k.copy()
+    q, t, rms = np.zeros((m, 4)), np.zeros((m, 3)), np.zeros(m)
+    q[:, 3] = 1.0
+    used, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
+    cov = np.zeros((k.size, k.size)) if covariance else None
+    summary = CalibrationSummary()
+    st = api.camera_calibrate(int(device), int(model), _dp(k), k.size, None if mask is None else _u8p(mask), nf,
+                              off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(px), _dp(pt), None if qi is None else _dp(qi),
+                              None if ti is None else _dp(ti), None if options is None else C.byref(options), _dp(k_out), _dp(q), _dp(t),
+                              _dp(rms), _ip(used), _u8p(status), _dp(cov) if covariance else None, C.byref(summary))
+    _check_free(api, st)
+    return Calibration(k_out, q[:nf], t[:nf], rms[:nf], used[:nf], status[:nf], cov, summary)
 
 
 class Problem:

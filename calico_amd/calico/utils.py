@@ -147,3 +147,69 @@ def InitializePoses(camera, all_detections: List[Dict[int, np.ndarray]], model_d
         R_chart_camera.append(R.T)
         t_chart_camera.append(-R.T @ t)
     return R_chart_camera, t_chart_camera, np.asarray(r["status"]) == 0
+
+
+def _rotation_of(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+# InitialIntrinsics' mid-range values for the parameters that have no neutral value
+_FOV_START = 1.0          # FieldOfView's w (radians): w -> 0 is the pinhole, but the model's derivative in w vanishes there
+_EUCM_ALPHA_START = 0.5   # ExtendedUnifiedCamera's alpha: at its neutral value 0, beta has no effect on the projection
+
+
+def InitialIntrinsics(model, pinhole) -> np.ndarray:
+    """Starting intrinsics of any camera model from Zhang's pinhole [fx, fy, s, cx, cy] (InitializePinholeAndPoses), in the
+    model's own layout [f, cx, cy, distortion...]. The rule: on the optical axis the model's projection agrees with the pinhole
+    of focal length (fx + fy) / 2 and principal point (cx, cy) to first order (these models have one focal length and no skew).
+    Distortion starts at its neutral value where the model has one -- OpenCv5 / OpenCv8: all zero; KannalaBrandt: all zero
+    (equidistant); DoubleSphere: xi = 0, alpha = 0; UnifiedCamera: alpha = 0 -- and at a documented mid-range value otherwise:
+    FieldOfView w = 1 rad, with f = f_pinhole w / (2 tan(w / 2)); ExtendedUnifiedCamera alpha = 0.5, beta = 1 (on the axis its
+    focal length is the pinhole's for every alpha)."""
+    fx, fy, _, cx, cy = [float(v) for v in pinhole]
+    f = 0.5 * (fx + fy)
+    m = int(model)
+    if m == 1:
+        return np.array([f, cx, cy, 0, 0, 0, 0, 0], float)
+    if m == 2:
+        return np.array([f, cx, cy, 0, 0, 0, 0, 0, 0, 0, 0], float)
+    if m == 3:
+        return np.array([f, cx, cy, 0, 0, 0, 0], float)
+    if m == 4:
+        return np.array([f, cx, cy, 0.0, 0.0])
+    if m == 5:
+        w = _FOV_START
+        return np.array([f * w / (2.0 * np.tan(0.5 * w)), cx, cy, w])
+    if m == 6:
+        return np.array([f, cx, cy, 0.0])
+    if m == 7:
+        return np.array([f, cx, cy, _EUCM_ALPHA_START, 1.0])
+    raise ValueError("no camera model %r" % (model,))
+
+
+def InitializeIntrinsicsAndPoses(camera, all_detections: List[Dict[int, np.ndarray]], model_definition: Dict[int, np.ndarray]
+                                 ) -> Tuple[np.ndarray, List[np.ndarray], List[np.ndarray], np.ndarray]:
+    """InitializePinholeAndPoses for ANY camera model: Zhang's closed form gives the pinhole part, InitialIntrinsics maps it to
+    the camera's model, and Camera.CalibrateIntrinsics (on the device) estimates the model's intrinsics jointly with the pose of
+    every frame under the library's own projection, so that Optimize starts at a minimum of its camera term. The camera's
+    intrinsics are set to the estimate. Returns (intrinsics, [R_chart_camera per frame], [t_chart_camera per frame],
+    ok (n_frames,) bool) in the conventions of InitializePoses; a frame that is not ok carries the identity and must not be handed
+    to FitSpline. Raises RuntimeError when the estimation does not end with status OK.
+
+    The start has zero distortion. That does not reach the minimum for strong OpenCV distortion: the numpy reference of the tests,
+    started this way, converged for the KannalaBrandt fixture and did not for the OpenCv5 / OpenCv8 fixtures (k1 = -0.31). For
+    such a lens start from a data sheet or a previous calibration (Camera.SetIntrinsics, then Camera.CalibrateIntrinsics)."""
+    pinhole, _, _ = InitializePinholeAndPoses(all_detections, model_definition)
+    camera.SetIntrinsics(InitialIntrinsics(camera.GetModel(), pinhole))
+    r = camera.CalibrateIntrinsics(all_detections, model_definition)
+    if r["status"] != 0:
+        raise RuntimeError("Error: the intrinsic calibration ended with status %d after %d iterations" % (r["status"], r["iterations"]))
+    R_chart_camera, t_chart_camera = [], []
+    for q, t in zip(r["q"], r["t"]):
+        R = _rotation_of(q)
+        R_chart_camera.append(R.T)
+        t_chart_camera.append(-R.T @ t)
+    return r["intrinsics"], R_chart_camera, t_chart_camera, np.asarray(r["frame_status"]) == 0

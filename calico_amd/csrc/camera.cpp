@@ -1,6 +1,7 @@
 // camera.cpp — the camera model over free pixels and points (this part of the C ABI of include/calico_hip.h): unprojection,
 // the forward model with its derivatives, the projection uncertainty map of a solved problem (kernels: camera_kernels.hip) and
-// the chart resection (resect_kernels.hip). Everything that can be checked without a device is checked before the first HIP call.
+// the chart resection (resect_kernels.hip) and the intrinsic calibration (calib_kernels.hip). Everything that can be checked
+// without a device is checked before the first HIP call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -185,9 +186,189 @@ int resect_free(int device, int model, const double* intrinsics, int n_intrinsic
   return CALICO_OK;
 }
 
+// calico_camera_calibrate. The whole batch lives on the device for the length of the call (every iteration reads every pair:
+// nothing is chunked). LM cycles -- evaluate, decide, eliminate, reduce -- are enqueued kCalibPollCycles at a time; between the
+// groups the host reads the control word's first field, only to stop enqueuing (launches behind the end return at once).
+constexpr int kCalibPollCycles = 6;
+
+int calibrate_free(int device, int model, const double* k_init, int n_intrinsics, const uint8_t* free_mask, int64_t n_frames,
+                   const int64_t* offsets, const double* pixels, const double* points, const double* q_init, const double* t_init,
+                   const calico_calibration_options* opt, double* k_out, double* q_out, double* t_out, double* rms_out,
+                   int32_t* n_used_out, uint8_t* status_out, double* cov_out, calico_calibration_summary* summary) {
+  const char* what = "calico_camera_calibrate";
+  if (int rc = check_model(nullptr, what, model, k_init, n_intrinsics)) return rc;
+  if (n_frames < 0) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": n_frames must be >= 0");
+  calico_calibration_options o;
+  calico_default_calibration_options(&o);
+  if (opt) o = *opt;
+  if (!std::isfinite(o.step_tolerance) || !(o.step_tolerance > 0.0))
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": step_tolerance must be finite and > 0");
+  if (o.max_iterations < 1) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": max_iterations must be >= 1");
+  if (!std::isfinite(o.huber_scale) || o.huber_scale < 0.0)
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": huber_scale must be finite and >= 0");
+  if (o.min_points < 4) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": min_points must be >= 4");
+  if ((q_init == nullptr) != (t_init == nullptr))
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": q_init and t_init are given together or not at all");
+  const int K = n_intrinsics;
+  unsigned free_bits = 0;
+  for (int i = 0; i < K; ++i)
+    if (!free_mask || free_mask[i]) free_bits |= 1u << i;
+  if (free_bits == 0) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": free_mask leaves no intrinsic free");
+  if (n_frames == 0) return CALICO_OK;
+  if (!offsets || !k_out || !q_out || !t_out || !rms_out || !n_used_out || !status_out || !summary)
+    return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": null frame offsets, output buffer or summary");
+  if (offsets[0] != 0) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": frame_offsets must start at 0");
+  for (int64_t f = 0; f < n_frames; ++f)
+    if (offsets[f + 1] < offsets[f])
+      return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": frame_offsets decrease at frame " + std::to_string(f));
+  const int64_t NP = offsets[n_frames];
+  if (NP > 0 && (!pixels || !points)) return fail(nullptr, CALICO_INVALID_ARGUMENT, std::string(what) + ": null pixels or points");
+  if (int rc = select_device(what, device)) return rc;
+
+  const size_t F = size_t(n_frames), P = size_t(NP), N = size_t(K) + 7;
+  Buf<double> d_k, d_px, d_pt, d_ws, d_q, d_t, d_rms, d_frames, d_gram, d_share, d_cov;
+  Buf<int64_t> d_off;
+  Buf<int32_t> d_used, d_it;
+  Buf<uint8_t> d_fl, d_st, d_act;
+  Buf<CalibControl> d_ctrl;
+  FREE_TRY(what, d_k.alloc(size_t(K))); FREE_TRY(what, d_px.alloc(P * 2)); FREE_TRY(what, d_pt.alloc(P * 3)); FREE_TRY(what, d_fl.alloc(P));
+  FREE_TRY(what, d_off.alloc(F + 1)); FREE_TRY(what, d_q.alloc(F * 4)); FREE_TRY(what, d_t.alloc(F * 3)); FREE_TRY(what, d_rms.alloc(F));
+  FREE_TRY(what, d_used.alloc(F)); FREE_TRY(what, d_st.alloc(F)); FREE_TRY(what, d_act.alloc(F)); FREE_TRY(what, d_ctrl.alloc(1));
+  FREE_TRY(what, d_frames.alloc(F * kCalibFrameDoubles)); FREE_TRY(what, d_gram.alloc(F * 2 * N * N));
+  FREE_TRY(what, d_share.alloc(F * kCalibShare)); FREE_TRY(what, d_cov.alloc(size_t(K) * size_t(K)));
+  FREE_TRY(what, hipMemcpy(d_off.p, offsets, (F + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  if (NP > 0) {
+    FREE_TRY(what, hipMemcpy(d_px.p, pixels, P * 2 * sizeof(double), hipMemcpyHostToDevice));
+    FREE_TRY(what, hipMemcpy(d_pt.p, points, P * 3 * sizeof(double), hipMemcpyHostToDevice));
+  }
+  FREE_TRY(what, hipMemset(d_fl.p, 0, P ? P : 1));
+
+  // the start: poses and who takes part
+  std::vector<double> q0(F * 4, 0.0), t0(F * 3, 0.0);
+  std::vector<uint8_t> status(F, uint8_t(CALICO_RESECT_OK));
+  if (q_init) {
+    for (size_t f = 0; f < F; ++f) {
+      if (offsets[f + 1] - offsets[f] < o.min_points) { status[f] = CALICO_RESECT_TOO_FEW_POINTS; continue; }
+      const double* q = q_init + 4 * f;
+      const double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+      const double sg = (q[3] < 0.0 ? -1.0 : 1.0) / nrm;
+      for (int i = 0; i < 4; ++i) q0[4 * f + size_t(i)] = sg * q[i];
+      for (int i = 0; i < 3; ++i) t0[3 * f + size_t(i)] = t_init[3 * f + size_t(i)];
+    }
+  } else {
+    calico_resection_options ro;
+    calico_default_resection_options(&ro);
+    ro.huber_scale = o.huber_scale; ro.min_points = o.min_points;
+    FREE_TRY(what, d_ws.alloc(P * 2)); FREE_TRY(what, d_it.alloc(F));
+    FREE_TRY(what, hipMemcpy(d_k.p, k_init, size_t(K) * sizeof(double), hipMemcpyHostToDevice));
+    ResectArgs ra = {};
+    ra.k = d_k.p; ra.n_frames = n_frames; ra.offsets = d_off.p; ra.pixels = d_px.p; ra.points = d_pt.p; ra.ws = d_ws.p; ra.flags = d_fl.p;
+    ra.max_iterations = ro.max_iterations; ra.step_tolerance = ro.step_tolerance; ra.huber_scale = ro.huber_scale; ra.min_points = ro.min_points;
+    ra.q_out = d_q.p; ra.t_out = d_t.p; ra.rms_out = d_rms.p; ra.n_used_out = d_used.p; ra.iterations_out = d_it.p; ra.status_out = d_st.p;
+    FREE_TRY(what, launch_camera_resect(model, ra, nullptr));
+    FREE_TRY(what, hipMemcpy(q0.data(), d_q.p, F * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(t0.data(), d_t.p, F * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemcpy(status.data(), d_st.p, F, hipMemcpyDeviceToHost));
+    FREE_TRY(what, hipMemset(d_fl.p, 0, P ? P : 1));      // (the validity bits start clean)
+  }
+  std::vector<uint8_t> active(F, 0);
+  int64_t usable = 0;
+  for (size_t f = 0; f < F; ++f) {
+    active[f] = status[f] == CALICO_RESECT_OK ? 1 : 0;
+    usable += active[f];
+    if (!active[f]) { q0[4 * f] = q0[4 * f + 1] = q0[4 * f + 2] = 0.0; q0[4 * f + 3] = 1.0; t0[3 * f] = t0[3 * f + 1] = t0[3 * f + 2] = 0.0; }
+  }
+  // the outputs that are the inputs (too few frames, a degenerate problem)
+  const auto give_inputs = [&](int calib_status, int iterations, double lambda) {
+    std::copy(k_init, k_init + K, k_out);
+    std::copy(q0.begin(), q0.end(), q_out); std::copy(t0.begin(), t0.end(), t_out);
+    if (q_init)      // (as given, not normalised)
+      for (size_t f = 0; f < F; ++f)
+        if (active[f]) { std::copy(q_init + 4 * f, q_init + 4 * f + 4, q_out + 4 * f); std::copy(t_init + 3 * f, t_init + 3 * f + 3, t_out + 3 * f); }
+    std::fill(rms_out, rms_out + F, 0.0); std::fill(n_used_out, n_used_out + F, 0);
+    std::copy(status.begin(), status.end(), status_out);
+    if (cov_out) std::fill(cov_out, cov_out + size_t(K) * size_t(K), 0.0);
+    *summary = calico_calibration_summary{};
+    summary->status = calib_status; summary->iterations = iterations; summary->lambda = lambda;
+    summary->frames_used = int32_t(usable);
+  };
+  if (usable < 3) { give_inputs(CALICO_CALIB_TOO_FEW_FRAMES, 0, kCalibLambda0); return CALICO_OK; }
+
+  std::vector<double> frames(F * kCalibFrameDoubles, 0.0);
+  for (size_t f = 0; f < F; ++f) {      // the start is the candidate of the first evaluation: slot 1
+    double* ns = frames.data() + f * kCalibFrameDoubles + kCalibSlot;
+    for (int i = 0; i < 4; ++i) ns[i] = q0[4 * f + size_t(i)];
+    for (int i = 0; i < 3; ++i) ns[4 + i] = t0[3 * f + size_t(i)];
+  }
+  CalibControl ctrl = {};
+  ctrl.status = CALICO_CALIB_NOT_CONVERGED; ctrl.first = 1; ctrl.lambda = kCalibLambda0;
+  for (int i = 0; i < K; ++i) ctrl.k[0][i] = ctrl.k[1][i] = k_init[i];
+  FREE_TRY(what, hipMemcpy(d_frames.p, frames.data(), frames.size() * sizeof(double), hipMemcpyHostToDevice));
+  FREE_TRY(what, hipMemcpy(d_act.p, active.data(), F, hipMemcpyHostToDevice));
+  FREE_TRY(what, hipMemcpy(d_st.p, status.data(), F, hipMemcpyHostToDevice));
+  FREE_TRY(what, hipMemcpy(d_ctrl.p, &ctrl, sizeof(ctrl), hipMemcpyHostToDevice));
+  FREE_TRY(what, hipMemset(d_gram.p, 0, F * 2 * N * N * sizeof(double)));
+  FREE_TRY(what, hipMemset(d_share.p, 0, F * kCalibShare * sizeof(double)));
+
+  CalibArgs a = {};
+  a.ctrl = d_ctrl.p; a.K = K; a.free_bits = free_bits; a.n_frames = n_frames; a.offsets = d_off.p; a.pixels = d_px.p; a.points = d_pt.p;
+  a.flags = d_fl.p; a.active = d_act.p; a.status = d_st.p; a.frames = d_frames.p; a.gram = d_gram.p; a.share = d_share.p;
+  a.max_iterations = o.max_iterations; a.step_tolerance = o.step_tolerance; a.huber_scale = o.huber_scale;
+  a.q_out = d_q.p; a.t_out = d_t.p; a.rms_out = d_rms.p; a.n_used_out = d_used.p; a.cov_out = d_cov.p;
+  // every cycle tries a step or raises lambda tenfold after a reduced system that was not positive definite (at most 24 times
+  // in a row): the loop ends on its own; the bound only guards the host against a control word that never moves
+  const int64_t max_cycles = 26 * (int64_t(o.max_iterations) + 2);
+  int done = 0;
+  for (int64_t cycle = 0; !done; cycle += kCalibPollCycles) {
+    if (cycle > max_cycles) return fail(nullptr, CALICO_INTERNAL, std::string(what) + ": the device loop did not end");
+    for (int i = 0; i < kCalibPollCycles; ++i) {
+      FREE_TRY(what, launch_calib_evaluate(model, a, nullptr));
+      FREE_TRY(what, launch_calib_decide(a, nullptr));
+      FREE_TRY(what, launch_calib_eliminate(a, false, nullptr));
+      FREE_TRY(what, launch_calib_reduce(a, false, nullptr));
+    }
+    FREE_TRY(what, hipMemcpy(&done, &d_ctrl.p->done, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  FREE_TRY(what, hipMemcpy(&ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost));
+  if (ctrl.status != CALICO_CALIB_DEGENERATE) {
+    FREE_TRY(what, launch_calib_eliminate(a, true, nullptr));
+    FREE_TRY(what, launch_calib_reduce(a, true, nullptr));
+    FREE_TRY(what, hipMemcpy(&ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost));
+  }
+  if (ctrl.status == CALICO_CALIB_DEGENERATE || !ctrl.final_ok) {
+    give_inputs(CALICO_CALIB_DEGENERATE, ctrl.iterations, ctrl.lambda);
+    return CALICO_OK;
+  }
+  for (int i = 0; i < K; ++i) k_out[i] = ((free_bits >> i) & 1u) ? ctrl.k[ctrl.cur][i] : k_init[i];
+  FREE_TRY(what, hipMemcpy(q_out, d_q.p, F * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  FREE_TRY(what, hipMemcpy(t_out, d_t.p, F * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  FREE_TRY(what, hipMemcpy(rms_out, d_rms.p, F * sizeof(double), hipMemcpyDeviceToHost));
+  FREE_TRY(what, hipMemcpy(n_used_out, d_used.p, F * sizeof(int32_t), hipMemcpyDeviceToHost));
+  FREE_TRY(what, hipMemcpy(status_out, d_st.p, F, hipMemcpyDeviceToHost));
+  if (cov_out) FREE_TRY(what, hipMemcpy(cov_out, d_cov.p, size_t(K) * size_t(K) * sizeof(double), hipMemcpyDeviceToHost));
+  summary->status = ctrl.status; summary->iterations = ctrl.iterations; summary->initial_cost = ctrl.initial_cost;
+  summary->final_cost = ctrl.final_cost; summary->rms = ctrl.rms; summary->frames_used = ctrl.frames_used;
+  summary->pairs_used = ctrl.pairs_used; summary->lambda = ctrl.lambda;
+  return CALICO_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void calico_default_calibration_options(calico_calibration_options* o) {
+  if (!o) return;
+  o->max_iterations = 50; o->step_tolerance = 1e-10; o->huber_scale = 0.0; o->min_points = 4;
+}
+
+int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* intrinsics_init, int32_t n_intrinsics, const uint8_t* free_mask,
+                                int64_t n_frames, const int64_t* frame_offsets, const double* pixels, const double* points,
+                                const double* q_init, const double* t_init, const calico_calibration_options* o, double* intrinsics_out,
+                                double* q_out, double* t_out, double* rms_out, int32_t* n_used_out, uint8_t* status_out,
+                                double* intrinsics_cov_out, calico_calibration_summary* summary) {
+  return calibrate_free(device, model, intrinsics_init, n_intrinsics, free_mask, n_frames, frame_offsets, pixels, points, q_init, t_init,
+                        o, intrinsics_out, q_out, t_out, rms_out, n_used_out, status_out, intrinsics_cov_out, summary);
+}
 
 void calico_default_resection_options(calico_resection_options* o) {
   if (!o) return;

@@ -165,4 +165,48 @@ struct ResectArgs {
 };
 hipError_t launch_camera_resect(int model, const ResectArgs& a, hipStream_t s);
 
+// ---- intrinsic calibration (calib_kernels.hip): K intrinsics and the 6-DOF pose of every frame, an arrowhead system ----------
+// The control word of the device's LM loop: every kernel of an iteration reads it, the two single-workgroup kernels write it.
+struct CalibControl {
+  int done;                     // != 0: every later launch returns at once
+  int status;                   // CALICO_CALIB_*
+  int cur;                      // the slot (intrinsics, poses, Gram matrices, validity bit) of the current point
+  int first;                    // the start has not been evaluated yet
+  int redo;                     // the reduced system was not positive definite: eliminate and reduce again at the larger lambda
+  int iterations;
+  int frames_used;
+  int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
+  long long pairs_used;
+  double lambda, step_k;        // step_k: max |dk_i| / max(1, |k_i|) of the step the candidate was made with
+  double initial_cost, final_cost, rms;
+  double k[2][12];              // the intrinsics of the two slots
+  double dk[12];
+};
+// Per frame, kCalibFrameDoubles doubles: two slots of kCalibSlot ([0, 4) q, [4, 7) t, [7] Sum rho, [8] Sum |e|^2, [9] valid
+// pairs, [10] the cost's rounding scale), [24] Sum rho over the pairs valid at both points, [25] pairs lost, [26] the pose step's
+// size, and from [32] Y = A^-1 [B g], column j at 32 + 6 j.
+constexpr int kCalibShare = 128;                         // doubles per frame of `share` (at most 66 + 11 + 11 + 4 are used)
+constexpr double kCalibLambda0 = 1e-4;                    // the first damping (the resection's)
+constexpr int kCalibSlot = 12, kCalibCommon = 24, kCalibLost = 25, kCalibStep = 26, kCalibY = 32, kCalibFrameDoubles = 112;
+struct CalibArgs {
+  CalibControl* ctrl;
+  int K;                                                  // the model's intrinsics; the Gram matrix has N = K + 7 columns
+  unsigned free_bits;                                     // bit i: intrinsic i is estimated
+  int64_t n_frames;
+  const int64_t* offsets;
+  const double* pixels; const double* points;
+  uint8_t* flags;                                         // N pairs: valid at slot 0 / 1 (pose_bit)
+  uint8_t* active;                                        // n_frames: the frame takes part
+  uint8_t* status;                                        // n_frames: CALICO_RESECT_*
+  double* frames;                                         // n_frames x kCalibFrameDoubles
+  double* gram;                                           // n_frames x 2 x N x N: [J_pose J_k e]^T W [J_pose J_k e] at the two slots
+  double* share;                                          // n_frames x kCalibShare: the frame's entries of the reduced system
+  int max_iterations; double step_tolerance; double huber_scale;
+  double* q_out; double* t_out; double* rms_out; int* n_used_out; double* cov_out /* K x K */;
+};
+hipError_t launch_calib_evaluate(int model, const CalibArgs& a, hipStream_t s);      // candidate: back-substitution + one pass over the pairs
+hipError_t launch_calib_decide(const CalibArgs& a, hipStream_t s);                   // accept / reject, the next lambda, termination
+hipError_t launch_calib_eliminate(const CalibArgs& a, bool final, hipStream_t s);    // per frame: Cholesky, Y, B^T Y (final: undamped, outputs)
+hipError_t launch_calib_reduce(const CalibArgs& a, bool final, hipStream_t s);       // fixed-order sum over the frames, the K x K solve, dk
+
 }  // namespace cal

@@ -123,6 +123,61 @@ void bind_sensor_common(PyClass& c) {
            });
 }
 
+// ---- intrinsic calibration (calico_camera_calibrate): what the two bindings share ----
+// options: None or a dict of calico_calibration_options fields
+calico_calibration_options calibration_options(const py::object& options) {
+  calico_calibration_options o;
+  calico_default_calibration_options(&o);
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+      else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+      else if (name == "huber_scale") o.huber_scale = py::cast<double>(kv.second);
+      else if (name == "min_points") o.min_points = py::cast<int>(kv.second);
+      else throw py::type_error("no calibration option '" + name + "'");
+    }
+  }
+  return o;
+}
+std::vector<uint8_t> to_mask(const py::object& o) {
+  std::vector<uint8_t> mask;
+  if (!o.is_none())
+    for (auto v : py::cast<py::sequence>(o)) mask.push_back(py::cast<bool>(v) ? 1 : 0);
+  return mask;
+}
+// None, or n doubles per frame as a flat vector
+bool to_rows(const py::object& o, std::vector<double>* out) {
+  if (o.is_none()) return false;
+  const VectorXd v = to_vector(o);
+  out->assign(v.begin(), v.end());
+  return true;
+}
+// a dict of arrays, one row per frame, the intrinsics, and the summary's fields
+py::dict calibration_dict(const CameraModel::ChartCalibration& r, bool covariance) {
+  const py::ssize_t n = py::ssize_t(r.NumFrames()), K = py::ssize_t(r.intrinsics.size());
+  py::array_t<double> q({n, py::ssize_t(4)}), t({n, py::ssize_t(3)}), rms(n);
+  py::array_t<int32_t> used(n);
+  py::array_t<uint8_t> status(n);
+  std::copy(r.q.begin(), r.q.end(), q.mutable_data());
+  std::copy(r.t.begin(), r.t.end(), t.mutable_data());
+  std::copy(r.rms.begin(), r.rms.end(), rms.mutable_data());
+  std::copy(r.n_used.begin(), r.n_used.end(), used.mutable_data());
+  std::copy(r.status.begin(), r.status.end(), status.mutable_data());
+  py::dict out;
+  out["intrinsics"] = to_array(r.intrinsics);
+  out["q"] = q; out["t"] = t; out["rms"] = rms; out["n_used"] = used; out["frame_status"] = status;
+  out["status"] = r.summary.status; out["iterations"] = r.summary.iterations; out["initial_cost"] = r.summary.initial_cost;
+  out["final_cost"] = r.summary.final_cost; out["total_rms"] = r.summary.rms; out["frames_used"] = r.summary.frames_used;
+  out["pairs_used"] = r.summary.pairs_used; out["lambda"] = r.summary.lambda;
+  if (covariance) {
+    py::array_t<double> cov({K, K});
+    std::copy(r.cov.begin(), r.cov.end(), cov.mutable_data());
+    out["cov"] = cov;
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_calico, m) {
@@ -222,7 +277,28 @@ PYBIND11_MODULE(_calico, m) {
                     raise_if_error(CameraModel::UnprojectPixels(model, to_vector(intrinsics), to_pixels(pixels), &b, &valid, device));
                     return bearings_tuple(b, valid);
                   },
-                  py::arg("model"), py::arg("intrinsics"), py::arg("pixels"), py::arg("device") = 0);
+                  py::arg("model"), py::arg("intrinsics"), py::arg("pixels"), py::arg("device") = 0)
+      // frame_offsets (n_frames + 1) cuts pixels (N, 2) and points (N, 3) into frames; free_mask: None or K flags; q_init / t_init:
+      // None or (n_frames, 4) / (n_frames, 3); options: None or a dict of calico_calibration_options fields
+      .def_static("CalibrateFromChart",
+                  [](CameraIntrinsicsModel model, const py::object& intrinsics_init, const std::vector<int64_t>& frame_offsets,
+                     const py::object& pixels, const py::object& points, const py::object& options, bool covariance,
+                     const py::object& free_mask, const py::object& q_init, const py::object& t_init, int device) {
+                    const VectorXd flat = to_vector(points);
+                    if (flat.size() % 3 != 0) throw py::type_error("expected an (n, 3) array of chart points");
+                    std::vector<Vector3d> pts(flat.size() / 3);
+                    for (size_t i = 0; i < pts.size(); ++i) pts[i] = Vector3d(flat[3 * i], flat[3 * i + 1], flat[3 * i + 2]);
+                    const calico_calibration_options o = calibration_options(options);
+                    std::vector<double> q0, t0;
+                    const bool hq = to_rows(q_init, &q0), ht = to_rows(t_init, &t0);
+                    CameraModel::ChartCalibration r;
+                    raise_if_error(CameraModel::CalibrateFromChart(model, to_vector(intrinsics_init), frame_offsets, to_pixels(pixels), pts, &o, &r,
+                                                                   covariance, to_mask(free_mask), hq ? &q0 : nullptr, ht ? &t0 : nullptr, device));
+                    return calibration_dict(r, covariance);
+                  },
+                  py::arg("model"), py::arg("intrinsics_init"), py::arg("frame_offsets"), py::arg("pixels"), py::arg("points"),
+                  py::arg("options") = py::none(), py::arg("covariance") = false, py::arg("free_mask") = py::none(),
+                  py::arg("q_init") = py::none(), py::arg("t_init") = py::none(), py::arg("device") = 0);
   py::enum_<ProjectionFrame>(m, "ProjectionFrame")
       .value("kCamera", ProjectionFrame::kCamera)
       .value("kRig", ProjectionFrame::kRig);
@@ -322,7 +398,29 @@ PYBIND11_MODULE(_calico, m) {
              return out;
            },
            py::arg("all_detections"), py::arg("model_definition"), py::arg("options") = py::none(), py::arg("covariance") = false,
-           py::arg("device") = 0);
+           py::arg("device") = 0)
+      // all_detections and model_definition as EstimateChartPoses; the camera's intrinsics are the start and, after a run that ends
+      // OK or NOT_CONVERGED, the estimate. Returns CalibrateFromChart's dict.
+      .def("CalibrateIntrinsics",
+           [](Camera& self, const std::vector<std::map<int, Vector2d>>& all_detections, const py::dict& model_definition,
+              const py::object& options, bool covariance, const py::object& free_mask, const py::object& q_init, const py::object& t_init,
+              int device) {
+             std::map<int, Vector3d> model;
+             for (auto kv : model_definition) {
+               auto arr = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(kv.second);
+               if (!arr || (arr.size() != 2 && arr.size() != 3)) throw py::type_error("a chart point is (x, y) or (x, y, z)");
+               model[py::cast<int>(kv.first)] = Vector3d(arr.data()[0], arr.data()[1], arr.size() == 3 ? arr.data()[2] : 0.0);
+             }
+             const calico_calibration_options o = calibration_options(options);
+             std::vector<double> q0, t0;
+             const bool hq = to_rows(q_init, &q0), ht = to_rows(t_init, &t0);
+             CameraModel::ChartCalibration r;
+             raise_if_error(self.CalibrateIntrinsics(all_detections, model, &o, &r, covariance, to_mask(free_mask), hq ? &q0 : nullptr,
+                                                     ht ? &t0 : nullptr, device));
+             return calibration_dict(r, covariance);
+           },
+           py::arg("all_detections"), py::arg("model_definition"), py::arg("options") = py::none(), py::arg("covariance") = false,
+           py::arg("free_mask") = py::none(), py::arg("q_init") = py::none(), py::arg("t_init") = py::none(), py::arg("device") = 0);
 
   // ---- trajectory, world model ----
   py::class_<Trajectory, std::shared_ptr<Trajectory>>(m, "Trajectory")

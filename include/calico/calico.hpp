@@ -913,6 +913,53 @@ class CameraModel {
     *out = std::move(r);
     return OkStatus();
   }
+
+  /// What CalibrateFromChart leaves (calico_camera_calibrate): the intrinsics, per frame T_camera_chart as q (x, y, z, w) and t,
+  /// the RMS pixel residual, the pairs used and the status (CALICO_RESECT_*), on request the K x K covariance of the intrinsics,
+  /// and the summary (status: CALICO_CALIB_*).
+  struct ChartCalibration {
+    VectorXd intrinsics;
+    std::vector<double> q, t, rms, cov;      // 4, 3 and 1 doubles per frame; (with covariance) K x K
+    std::vector<int32_t> n_used;
+    std::vector<uint8_t> status;
+    calico_calibration_summary summary{};
+    size_t NumFrames() const { return status.size(); }
+    bool Ok() const { return summary.status == CALICO_CALIB_OK; }
+    bool Used(size_t frame) const { return status[frame] == CALICO_RESECT_OK; }
+  };
+  /// Intrinsic calibration over arrays, on the device: the intrinsics of `model` from `intrinsics_init`, jointly with the pose of
+  /// every frame. Frames as in ResectChart. free_mask (K entries, 0 = constant) may be empty: all free. q_init / t_init: both or
+  /// neither (neither: every frame is resected at intrinsics_init). options == nullptr: the library's defaults.
+  static Status CalibrateFromChart(CameraIntrinsicsModel model, const VectorXd& intrinsics_init, const std::vector<int64_t>& frame_offsets,
+                                   const std::vector<Vector2d>& pixels, const std::vector<Vector3d>& points,
+                                   const calico_calibration_options* options, ChartCalibration* out, bool covariance = false,
+                                   const std::vector<uint8_t>& free_mask = {}, const std::vector<double>* q_init = nullptr,
+                                   const std::vector<double>* t_init = nullptr, int device = 0) {
+    if (!out) return InvalidArgumentError("CalibrateFromChart: null output");
+    if (frame_offsets.empty() || pixels.size() != points.size() || frame_offsets.back() != int64_t(pixels.size()))
+      return InvalidArgumentError("CalibrateFromChart: frame_offsets must have n_frames + 1 entries and end at the number of pairs");
+    const size_t nf = frame_offsets.size() - 1, n = pixels.size(), K = size_t(intrinsics_init.size());
+    if ((q_init && q_init->size() != 4 * nf) || (t_init && t_init->size() != 3 * nf))
+      return InvalidArgumentError("CalibrateFromChart: q_init / t_init must hold 4 / 3 doubles per frame");
+    if (!free_mask.empty() && free_mask.size() != K) return InvalidArgumentError("CalibrateFromChart: free_mask must have one entry per intrinsic");
+    std::vector<double> px(2 * n), pt(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+      px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y();
+      pt[3 * i] = points[i][0]; pt[3 * i + 1] = points[i][1]; pt[3 * i + 2] = points[i][2];
+    }
+    ChartCalibration r;
+    r.intrinsics = intrinsics_init;
+    r.q.assign(4 * nf, 0.0); r.t.assign(3 * nf, 0.0); r.rms.assign(nf, 0.0); r.n_used.assign(nf, 0); r.status.assign(nf, 0);
+    for (size_t f = 0; f < nf; ++f) r.q[4 * f + 3] = 1.0;
+    if (covariance) r.cov.assign(K * K, 0.0);
+    const int st = calico_camera_calibrate(device, int(model), intrinsics_init.data(), int(K), free_mask.empty() ? nullptr : free_mask.data(),
+                                           int64_t(nf), frame_offsets.data(), px.data(), pt.data(), q_init ? q_init->data() : nullptr,
+                                           t_init ? t_init->data() : nullptr, options, r.intrinsics.data(), r.q.data(), r.t.data(),
+                                           r.rms.data(), r.n_used.data(), r.status.data(), covariance ? r.cov.data() : nullptr, &r.summary);
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+    *out = std::move(r);
+    return OkStatus();
+  }
 };
 
 inline bool ProjectPointHost(CameraIntrinsicsModel model, const double* k, const cal::V3& p, double pix[2]) {
@@ -973,6 +1020,34 @@ class Camera : public SensorCommon {
       offsets.push_back(int64_t(pixels.size()));
     }
     return CameraModel::ResectChart(model_, intrinsics_, offsets, pixels, points, options, out, covariance, nullptr, nullptr, device);
+  }
+  /// Static intrinsic calibration of this camera from chart detections: CameraModel::CalibrateFromChart with this camera's model,
+  /// started at its current intrinsics (a rough start: utils.InitialIntrinsics) and, unless q_init / t_init are given, at the
+  /// resection of every frame there. Frames and model_definition as in EstimateChartPoses. When the estimation ends with
+  /// CALICO_CALIB_OK or CALICO_CALIB_NOT_CONVERGED the camera's intrinsics are set to the estimate; `out` holds the poses and the
+  /// per-frame statuses either way.
+  Status CalibrateIntrinsics(const std::vector<std::map<int, Vector2d>>& frames, const std::map<int, Vector3d>& model_definition,
+                             const calico_calibration_options* options, CameraModel::ChartCalibration* out, bool covariance = false,
+                             const std::vector<uint8_t>& free_mask = {}, const std::vector<double>* q_init = nullptr,
+                             const std::vector<double>* t_init = nullptr, int device = 0) {
+    if (model_ == CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
+    if (!out) return InvalidArgumentError("CalibrateIntrinsics: null output");
+    std::vector<int64_t> offsets(1, 0);
+    std::vector<Vector2d> pixels;
+    std::vector<Vector3d> points;
+    for (const auto& frame : frames) {
+      for (const auto& kv : frame) {
+        const auto it = model_definition.find(kv.first);
+        if (it == model_definition.end()) return InvalidArgumentError("CalibrateIntrinsics: feature " + std::to_string(kv.first) + " is not in the model definition");
+        pixels.push_back(kv.second);
+        points.push_back(it->second);
+      }
+      offsets.push_back(int64_t(pixels.size()));
+    }
+    if (Status st = CameraModel::CalibrateFromChart(model_, intrinsics_, offsets, pixels, points, options, out, covariance, free_mask, q_init,
+                                                    t_init, device); !st.ok()) return st;
+    if (!frames.empty() && (out->summary.status == CALICO_CALIB_OK || out->summary.status == CALICO_CALIB_NOT_CONVERGED)) intrinsics_ = out->intrinsics;
+    return OkStatus();
   }
   StatusOr<int> AddParametersToProblem(Problem& problem) final {
     return AddCommonParameters(problem, model_ != CameraIntrinsicsModel::kNone, "camera");

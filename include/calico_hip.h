@@ -136,7 +136,8 @@ typedef struct calico_iteration {
 int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
- * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect); like a handle's message it
+ * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
+ * calico_camera_calibrate); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -559,7 +560,8 @@ int32_t calico_projection_uncertainty(calico_problem* p, int32_t sensor, int32_t
  * p_camera = R(q) p_chart + t, that minimises  Sum rho(|pixel - project(intrinsics, R p + t)|^2)  in pixels, under this
  * library's own projection (calico_project, the residuals), on the device. It is the step between a detector's output and
  * calico_fit_spline, for all seven models and at KNOWN intrinsics (a previous calibration, a data sheet, a first pinhole pass);
- * estimating intrinsics from scratch (Zhang's closed form, utils.InitializePinholeAndPoses) stays on the host.
+ * calico_camera_calibrate (below) estimates the intrinsics of any model together with these poses, from a rough start such as
+ * Zhang's closed form for the pinhole part (utils.InitializePinholeAndPoses, on the host) mapped by utils.InitialIntrinsics.
  *   start  q_init == t_init == NULL: the pixels are unprojected (calico_camera_unproject's map), the pairs with a valid unit
  *          bearing of z > 0.1 give the plane-to-normalised-image homography (Hartley normalisation, normal equations), which
  *          is split into a rotation (its nearest orthonormal matrix of determinant +1) and a translation with the chart in
@@ -607,6 +609,71 @@ int32_t calico_camera_resect(int32_t device, int32_t model, const double* intrin
                              const calico_resection_options* o /* NULL = defaults */, double* q_out, double* t_out,
                              double* rms_out, int32_t* n_used_out, int32_t* iterations_out, uint8_t* status_out,
                              double* cov_out /* may be NULL */);
+
+/* ---- intrinsic calibration: the intrinsics of any camera model jointly with the pose of every frame ---- */
+/* Static calibration from the same ragged batch of (pixel, chart point) pairs calico_camera_resect takes: the K intrinsics of
+ * `model` and the pose T_camera_chart of every usable frame that minimise  Sum rho(|pixel - project(k, R_f p + t_f)|^2)  over the
+ * usable frames, under this library's own projection, on the device -- so that calico_solve starts at a minimum of its own
+ * camera term. rho = identity or Huber (huber_scale in pixels, weights rho', no second-order term).
+ *   unknowns  the pose of a frame moves as in the resection, R <- exp([delta_rot]x) R and t <- t + delta_t; the intrinsics move
+ *          additively. free_mask (K bytes; NULL = all free): an entry with free_mask[i] == 0 is a constant, copied bit for bit to
+ *          intrinsics_out, with zero rows and columns in intrinsics_cov_out.
+ *   start  intrinsics_init, and per frame q_init / t_init (n_frames x 4 / x 3) for every frame with at least min_points pairs
+ *          (the others: CALICO_RESECT_TOO_FEW_POINTS). With q_init == t_init == NULL every frame is resected at intrinsics_init
+ *          (calico_camera_resect's kernel, the same huber_scale and min_points, its defaults otherwise); a frame whose resection
+ *          is not CALICO_RESECT_OK is left out and carries the resection's status. Fewer than 3 usable frames:
+ *          CALICO_CALIB_TOO_FEW_FRAMES.
+ *   refine Levenberg-Marquardt on the arrowhead system (6 x 6 pose blocks A_f, couplings B_f, one K x K block C) with Marquardt
+ *          damping lambda diag on the pose blocks and on C, lambda from 1e-4 within [1e-12, 1e12]: each frame eliminates its
+ *          pose, the reduced K x K system gives the step of the intrinsics, the frames back-substitute. The decision is one for
+ *          all frames. A candidate at which the model rejects a pair that is valid at the current point is rejected; one whose
+ *          cost is within the cost's own rounding error of the current one is accepted. Step size
+ *          s = max(|dk_i| / max(1, |k_i|), |delta_rot|_inf, |delta_t|_inf / max(1, |t|)) over all unknowns. Stops after an
+ *          accepted step with s < step_tolerance taken at lambda <= 1e-4 -- or a rejected step that small: the point is kept --
+ *          (CALICO_CALIB_OK), after max_iterations steps (CALICO_CALIB_NOT_CONVERGED: the last accepted point), and when the
+ *          reduced system is not positive definite at the largest damping or the result is not finite
+ *          (CALICO_CALIB_DEGENERATE). A frame whose damped 6 x 6 block is not positive definite drops out for good
+ *          (CALICO_RESECT_NOT_POSITIVE_DEFINITE).
+ * Outputs: intrinsics_out (K), per frame q_out (unit, w >= 0), t_out, rms_out (pixels, no loss), n_used_out, status_out
+ * (CALICO_RESECT_*: OK for a frame that took part to the end); a frame that did not has q = (0, 0, 0, 1), t = 0, rms = 0,
+ * n_used = 0. intrinsics_cov_out (K x K, may be NULL) = (C - Sum_f B_f^T A_f^-1 B_f)^-1, undamped, at the result, in pixel^2
+ * units (no variance factor, as every covariance here). With CALICO_CALIB_TOO_FEW_FRAMES or CALICO_CALIB_DEGENERATE the outputs
+ * are the inputs: intrinsics_init, the start poses of the usable frames, zero rms, n_used and covariance.
+ * The call returns CALICO_OK whenever `summary` is meaningful; how the estimation ended is summary->status. Repeated calls
+ * are bit-identical. Needs no problem handle: owns its device memory, message in calico_last_error(NULL).
+ * CALICO_INVALID_ARGUMENT, before the device is touched: calico_camera_resect's list, a free_mask without a free entry, a NULL
+ * intrinsics_out or summary, step_tolerance not finite or <= 0, max_iterations < 1, min_points < 4. n_frames == 0 is CALICO_OK
+ * and touches nothing. */
+#define CALICO_RESECT_NOT_POSITIVE_DEFINITE 5
+#define CALICO_CALIB_OK 0
+#define CALICO_CALIB_TOO_FEW_FRAMES 1
+#define CALICO_CALIB_NOT_CONVERGED 2
+#define CALICO_CALIB_DEGENERATE 3
+typedef struct {
+  int32_t max_iterations;   /* 50 */
+  double step_tolerance;    /* 1e-10 */
+  double huber_scale;       /* 0 = no loss; pixels */
+  int32_t min_points;       /* 4; values below 4 are an argument error */
+} calico_calibration_options;
+typedef struct {
+  int32_t status;           /* CALICO_CALIB_* */
+  int32_t iterations;       /* steps tried */
+  double initial_cost;      /* Sum rho at the start, over the usable frames */
+  double final_cost;
+  double rms;               /* sqrt(Sum |residual|^2 / pairs_used) in pixels, no loss applied */
+  int32_t frames_used;
+  int64_t pairs_used;
+  double lambda;            /* the damping at the end */
+} calico_calibration_summary;
+void calico_default_calibration_options(calico_calibration_options* o);
+int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* intrinsics_init, int32_t n_intrinsics,
+                                const uint8_t* free_mask /* K, or NULL */, int64_t n_frames,
+                                const int64_t* frame_offsets /* n_frames + 1 */, const double* pixels /* N x 2 */,
+                                const double* points /* N x 3, chart frame */, const double* q_init,
+                                const double* t_init /* both NULL, or n_frames x 4 / x 3 */,
+                                const calico_calibration_options* o /* NULL = defaults */, double* intrinsics_out, double* q_out,
+                                double* t_out, double* rms_out, int32_t* n_used_out, uint8_t* status_out,
+                                double* intrinsics_cov_out /* K x K, may be NULL */, calico_calibration_summary* summary);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
