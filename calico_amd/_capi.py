@@ -109,6 +109,26 @@ class CalibrationSummary(C.Structure):
 CALIB_OK, CALIB_TOO_FEW_FRAMES, CALIB_NOT_CONVERGED, CALIB_DEGENERATE = 0, 1, 2, 3
 
 
+class ImuAlignmentOptions(C.Structure):
+    """calico_imu_alignment_options."""
+    _fields_ = [("max_lag", C.c_double), ("lag_step", C.c_double), ("max_iterations", C.c_int32), ("step_tolerance", C.c_double),
+                ("estimate_latency", C.c_int32), ("estimate_gyro_bias", C.c_int32), ("estimate_accel_bias", C.c_int32),
+                ("min_samples", C.c_int32), ("sigma_gyro", C.c_double)]
+
+
+class ImuAlignmentSummary(C.Structure):
+    """calico_imu_alignment_summary."""
+    _fields_ = [("gyro_status", C.c_int32), ("accel_status", C.c_int32), ("gyro_samples", C.c_int64), ("accel_samples", C.c_int64),
+                ("first_sample", C.c_int64), ("iterations", C.c_int32), ("n_lags", C.c_int32), ("peak_index", C.c_int32),
+                ("coarse_latency", C.c_double), ("peak_correlation", C.c_double), ("gyro_rms", C.c_double), ("accel_rms", C.c_double),
+                ("gravity_norm", C.c_double), ("scatter_pivot", C.c_double), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("lambda_", C.c_double)]
+
+
+ALIGN_OK, ALIGN_TOO_FEW_SAMPLES, ALIGN_NO_PEAK, ALIGN_DEGENERATE, ALIGN_NOT_CONVERGED, ALIGN_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3, 4, 5
+ALIGN_MAX_LAGS = 4096
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -169,6 +189,7 @@ ABI_SYMBOLS = [
     "camera_unproject", "camera_project_points", "sensor_unproject", "projection_uncertainty",
     "default_resection_options", "camera_resect",
     "default_calibration_options", "camera_calibrate",
+    "default_imu_alignment_options", "imu_align",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -263,6 +284,11 @@ class CApi:
                 g("default_calibration_options", None, [CO])
                 g("camera_calibrate", C.c_int32, [C.c_int32, C.c_int32, D, C.c_int32, U8, C.c_int64, I64, D, D, D, D, CO, D, D, D, D, I, U8, D,
                                                   C.POINTER(CalibrationSummary)])
+            if hasattr(self.lib, self.prefix + "imu_align"):
+                AO = C.POINTER(ImuAlignmentOptions)
+                g("default_imu_alignment_options", None, [AO])
+                g("imu_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int64, D, D, C.c_int64, D, D, D, D, D, AO,
+                                           D, D, D, D, D, D, D, C.POINTER(ImuAlignmentSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -444,6 +470,61 @@ def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points,
                               _dp(rms), _ip(used), _u8p(status), _dp(cov) if covariance else None, C.byref(summary))
     _check_free(api, st)
     return Calibration(k_out, q[:nf], t[:nf], rms[:nf], used[:nf], status[:nf], cov, summary)
+
+
+def imu_alignment_options(api, **kw):
+    """The library's default calico_imu_alignment_options with the given fields replaced."""
+    o = ImuAlignmentOptions()
+    api.default_imu_alignment_options(C.byref(o))
+    for name, v in kw.items():
+        if not hasattr(o, name):
+            raise TypeError("no IMU alignment option %r" % name)
+        setattr(o, name, v)
+    return o
+
+
+def imu_align(api, order, knots, basis, ctrl, gyro_stamps, gyro, accel_stamps=None, accel=None, t_rig_accel=None, q_init=None,
+              latency_init=None, options=None, covariance=False, curve=False, device=0):
+    """calico_imu_align: the rotation rig <- gyroscope, the gyroscope's bias, the IMU's latency and, with accelerometer samples,
+    the world's gravity and the accelerometer's bias, against the spline (order, knots, basis, ctrl (n_knots - order, 6)).
+    gyro (n, 3) at gyro_stamps (n, sorted); accel (m, 3) at accel_stamps or neither; q_init (x, y, z, w) and latency_init
+    together or neither. options: an ImuAlignmentOptions (imu_alignment_options(api, ...)) or None. Returns a dict: q_rig_gyro,
+    gyro_bias, latency, gravity_world and accel_bias (None unless the accelerometer part is ALIGN_OK), cov (7, 7) or None,
+    curve (n_lags,) or None, and every field of the summary."""
+    knots, basis, ctrl = _f64(knots).ravel(), _f64(basis), _f64(ctrl).reshape(-1, 6)
+    order = int(order)
+    if len(ctrl) != len(knots) - order or basis.size != (len(knots) - 2 * order + 1) * order * order:
+        raise ValueError("ctrl must be (n_knots - order, 6) and basis (n_knots - 2 order + 1, order, order)")
+    gs, g = _f64(gyro_stamps).ravel(), _f64(gyro).reshape(-1, 3)
+    if len(gs) != len(g):
+        raise ValueError("one gyroscope stamp per sample")
+    if (accel_stamps is None) != (accel is None):
+        raise ValueError("accel_stamps and accel are given together or not at all")
+    as_ = np.zeros(0) if accel is None else _f64(accel_stamps).ravel()
+    am = np.zeros((0, 3)) if accel is None else _f64(accel).reshape(-1, 3)
+    if len(as_) != len(am):
+        raise ValueError("one accelerometer stamp per sample")
+    tra = None if t_rig_accel is None else _f64(t_rig_accel).reshape(3)
+    qi = None if q_init is None else _f64(q_init).reshape(4)
+    li = None if latency_init is None else _f64([latency_init]).reshape(1)
+    q, bias, lat = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3), np.zeros(1)
+    grav, abias = np.full(3, np.nan), np.full(3, np.nan)
+    cov = np.zeros((7, 7)) if covariance else None
+    cur = np.full(ALIGN_MAX_LAGS, np.nan) if curve else None
+    summary = ImuAlignmentSummary()
+    st = api.imu_align(int(device), order, len(knots), _dp(knots), _dp(basis), _dp(ctrl), len(g), _dp(gs) if len(g) else None,
+                       _dp(g) if len(g) else None, len(am), _dp(as_) if len(am) else None, _dp(am) if len(am) else None,
+                       None if tra is None else _dp(tra), None if qi is None else _dp(qi), None if li is None else _dp(li),
+                       None if options is None else C.byref(options), _dp(q), _dp(bias), _dp(lat), _dp(grav), _dp(abias),
+                       _dp(cov) if covariance else None, _dp(cur) if curve else None, C.byref(summary))
+    _check_free(api, st)
+    out = {name: getattr(summary, name) for name, _ in ImuAlignmentSummary._fields_}
+    solved = len(am) > 0 and summary.accel_status == ALIGN_OK
+    out.update(q_rig_gyro=q, gyro_bias=bias, latency=float(lat[0]), gravity_world=grav if solved else None,
+               accel_bias=abias if solved else None, cov=cov, curve=cur[:summary.n_lags] if curve else None)
+    if curve:
+        out["curve_tail"] = cur[summary.n_lags:]      # (never written by the library)
+    return out
 
 
 class Problem:

@@ -213,3 +213,45 @@ def InitializeIntrinsicsAndPoses(camera, all_detections: List[Dict[int, np.ndarr
         R_chart_camera.append(R.T)
         t_chart_camera.append(-R.T @ t)
     return r["intrinsics"], R_chart_camera, t_chart_camera, np.asarray(r["frame_status"]) == 0
+
+
+# where the three bias entries start in the intrinsics of the IMU models (gyroscope and accelerometer models share their layouts):
+# ScaleOnly [s]: none; ScaleAndBias [s, b 3]; VectorNav [scale 3, misalignment 6, bias 3]
+_IMU_BIAS_AT = {1: None, 2: 1, 3: 9}
+
+
+def InitializeImu(trajectory, gyroscope, accelerometer=None, world_model=None, options=None) -> dict:
+    """The IMU side of the start of Optimize, from the trajectory of the camera side (Trajectory.FitSpline over the poses of
+    InitializePoses / InitializeIntrinsicsAndPoses) and the sensors' registered measurements: Trajectory.AlignImu (on the device)
+    estimates the rotation rig <- gyroscope, the gyroscope's bias and the IMU's latency as a minimum of Optimize's own gyroscope
+    term and, with an accelerometer, the world's gravity and the accelerometer's bias. Sets the rotation of the extrinsics, the
+    latency and the bias intrinsics of the gyroscope and of the accelerometer (which shares rotation and latency; the scale and
+    every other intrinsic are left as they are, and a scale-only model has no bias to set) and, given a world model and an
+    accelerometer, its gravity. options: None or a dict of calico_imu_alignment_options fields. Returns AlignImu's dict.
+    Raises RuntimeError when a part does not end with status OK, or for a sensor whose model has not been set (before anything
+    is changed)."""
+    for sensor in (gyroscope, accelerometer):
+        if sensor is not None and int(sensor.GetModel()) not in _IMU_BIAS_AT:
+            raise RuntimeError("Error: InitializeImu does not know where IMU model %d keeps its bias" % int(sensor.GetModel()))
+    r = trajectory.AlignImu(gyroscope, accelerometer, options)
+    if r["gyro_status"] != 0:
+        raise RuntimeError("Error: the gyroscope alignment ended with status %d after %d iterations (%d samples)"
+                           % (r["gyro_status"], r["iterations"], r["gyro_samples"]))
+    if accelerometer is not None and r["accel_status"] != 0:
+        raise RuntimeError("Error: the accelerometer alignment ended with status %d (%d samples)" % (r["accel_status"], r["accel_samples"]))
+    x, y, z, w = r["q_rig_gyro"]
+    for sensor, bias in ((gyroscope, r["gyro_bias"]), (accelerometer, r["accel_bias"])):
+        if sensor is None:
+            continue
+        T = sensor.GetExtrinsics()
+        T.rotation = [w, x, y, z]
+        sensor.SetExtrinsics(T)
+        sensor.SetLatency(float(r["latency"]))
+        at = _IMU_BIAS_AT[int(sensor.GetModel())]
+        if at is not None:
+            k = np.array(sensor.GetIntrinsics(), float)
+            k[at:at + 3] = bias
+            sensor.SetIntrinsics(k)
+    if world_model is not None and accelerometer is not None:
+        world_model.SetGravity([float(v) for v in r["gravity_world"]])
+    return r

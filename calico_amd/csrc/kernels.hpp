@@ -209,4 +209,61 @@ hipError_t launch_calib_decide(const CalibArgs& a, hipStream_t s);              
 hipError_t launch_calib_eliminate(const CalibArgs& a, bool final, hipStream_t s);    // per frame: Cholesky, Y, B^T Y (final: undamped, outputs)
 hipError_t launch_calib_reduce(const CalibArgs& a, bool final, hipStream_t s);       // fixed-order sum over the frames, the K x K solve, dk
 
+// ---- camera-IMU alignment (align_kernels.hip): rotation, gyroscope bias, latency, gravity from a fitted trajectory ------------
+// The control word of the whole call: every kernel reads it, the single-workgroup kernels write it. The stages follow one
+// another on the stream without the host reading anything back; a stage that ends the call sets `done`.
+constexpr int kAlignGram = 36;                           // the upper triangle of the 8 x 8 Gram matrix of [J r], row-major
+constexpr int kAlignCostAt = kAlignGram - 1;             // its last entry, (7, 7): Sum |r|^2
+constexpr int kAlignBadAt = kAlignGram;                  // residuals that are not finite
+constexpr int kAlignNoiseAt = kAlignGram + 1;            // the cost's rounding scale
+constexpr int kAlignSums = kAlignGram + 2;               // what a workgroup of the evaluation sums
+constexpr int kAlignPart = 40;                           // doubles per workgroup of a stage's partials (>= kAlignSums, the largest)
+constexpr int kAlignThreads = 256;                       // samples per workgroup of every per-sample kernel
+constexpr int kAlignLagTile = 8;                         // lags per workgroup of the correlation
+constexpr int kAlignMaxLags = 4096;                      // CALICO_ALIGN_MAX_LAGS (imu_align.cpp asserts it)
+constexpr double kAlignLambda0 = 1e-4;                   // the first damping (the calibration's)
+constexpr int kAlignHornSums = 21;                       // Sum u (3), Sum v (3), Sum v u^T (9), Sum u u^T (6): u = -omega_rig, v = measured
+constexpr int kAlignAccelSums = 16;                      // samples (1), Sum M (9), Sum M^T y (3), Sum y (3)
+constexpr int kAlignAccelResidual = 8;                   // Sum |r|^2, samples, A^T r (6)
+struct AlignControl {
+  int done;                     // != 0: every later launch of the gyroscope part returns at once
+  int gyro_status, accel_status;      // CALICO_ALIGN_*
+  int cur;                      // the slot of the current point
+  int first;                    // the start has not been evaluated yet
+  int iterations;
+  int peak_index;               // of the correlation curve (-1: no search)
+  int cov_ok;
+  long long accel_samples;
+  double lambda, step;          // step: the size of the step the candidate was made with
+  double initial_cost, final_cost;
+  double coarse_latency, peak_correlation, scatter_pivot, gyro_rms, accel_rms;
+  double q[2][4], bias[2][3], latency[2];      // the two slots
+  double G[2][kAlignPart];      // the summed partials of the two slots
+  double cov[49];
+  double gravity[3], accel_bias[3];
+  double accel_sums[kAlignAccelSums];
+};
+struct AlignArgs {
+  AlignControl* ctrl;
+  int order, n_valid;
+  const double* knots; const double* basis; const double* spline_ctrl;
+  const double* stamps; const double* meas;               // the gyroscope samples that take part: n of them (the host's range)
+  int n;
+  const double* lags; int n_lags; double lag_step;        // the latencies of the grid
+  double* corr_part;                                      // chunks x n_lags x 3: Sum a, Sum a^2, Sum a m per (chunk, lag)
+  double* corr_m;                                         // chunks x 2: Sum m, Sum m^2
+  double* curve;                                          // n_lags
+  double* part;                                           // chunks x kAlignPart: the partials of the stage that runs
+  unsigned free_bits;                                     // bit i: parameter i of (rotation 3, bias 3, latency 1) is estimated
+  int max_iterations; double step_tolerance; double inv_sigma;
+  const double* accel_stamps; const double* accel; int n_accel;
+  double t_ra[3]; int estimate_accel_bias; int min_samples;
+};
+int align_chunks(int n);                                                            // workgroups of a per-sample kernel
+hipError_t launch_align_correlate(const AlignArgs& a, hipStream_t s);              // stage A: partial sums, then the curve and its peak
+hipError_t launch_align_horn(const AlignArgs& a, hipStream_t s);                   // stage B: the sums, then rotation and bias into slot 1
+hipError_t launch_align_iteration(const AlignArgs& a, hipStream_t s);              // stage C: evaluate the candidate, decide and step
+hipError_t launch_align_finish(const AlignArgs& a, hipStream_t s);                 // the covariance and the RMS at the result
+hipError_t launch_align_gravity(const AlignArgs& a, hipStream_t s);                // stage D: the sums, the solve, the residual pass
+
 }  // namespace cal

@@ -140,6 +140,27 @@ calico_calibration_options calibration_options(const py::object& options) {
   }
   return o;
 }
+// options: None or a dict of calico_imu_alignment_options fields
+calico_imu_alignment_options imu_alignment_options(const py::object& options) {
+  calico_imu_alignment_options o;
+  calico_default_imu_alignment_options(&o);
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "max_lag") o.max_lag = py::cast<double>(kv.second);
+      else if (name == "lag_step") o.lag_step = py::cast<double>(kv.second);
+      else if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+      else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+      else if (name == "estimate_latency") o.estimate_latency = py::cast<int>(kv.second);
+      else if (name == "estimate_gyro_bias") o.estimate_gyro_bias = py::cast<int>(kv.second);
+      else if (name == "estimate_accel_bias") o.estimate_accel_bias = py::cast<int>(kv.second);
+      else if (name == "min_samples") o.min_samples = py::cast<int>(kv.second);
+      else if (name == "sigma_gyro") o.sigma_gyro = py::cast<double>(kv.second);
+      else throw py::type_error("no IMU alignment option '" + name + "'");
+    }
+  }
+  return o;
+}
 std::vector<uint8_t> to_mask(const py::object& o) {
   std::vector<uint8_t> mask;
   if (!o.is_none())
@@ -436,7 +457,41 @@ PYBIND11_MODULE(_calico, m) {
         auto poses = self.Interpolate(stamps);
         raise_if_error(poses.status());
         return poses.value();
-      });
+      })
+      // Camera-IMU alignment against this trajectory from the sensors' registered measurements (calico_imu_align). options: None
+      // or a dict of calico_imu_alignment_options fields. Returns a dict: q_rig_gyro (x, y, z, w), gyro_bias, latency,
+      // gravity_world, accel_bias, cov and curve (each on request) and the summary's fields. The sensors are not changed.
+      .def("AlignImu",
+           [](const Trajectory& self, const Gyroscope& gyroscope, const py::object& accelerometer, const py::object& options,
+              bool covariance, bool curve, int device) {
+             const calico_imu_alignment_options o = imu_alignment_options(options);
+             const Accelerometer* accel = accelerometer.is_none() ? nullptr : py::cast<const Accelerometer*>(accelerometer);
+             auto res = self.AlignImu(gyroscope, accel, &o, covariance, curve, device);
+             raise_if_error(res.status());
+             const Trajectory::ImuAlignment& r = res.value();
+             py::dict out;
+             out["q_rig_gyro"] = to_array(VectorXd{r.q_rig_gyro.x(), r.q_rig_gyro.y(), r.q_rig_gyro.z(), r.q_rig_gyro.w()});
+             out["gyro_bias"] = to_array(VectorXd{r.gyro_bias[0], r.gyro_bias[1], r.gyro_bias[2]});
+             out["latency"] = r.latency;
+             out["gravity_world"] = to_array(VectorXd{r.gravity_world[0], r.gravity_world[1], r.gravity_world[2]});
+             out["accel_bias"] = to_array(VectorXd{r.accel_bias[0], r.accel_bias[1], r.accel_bias[2]});
+             if (curve) out["curve"] = to_array(r.curve);
+             if (covariance) {
+               py::array_t<double> cov({py::ssize_t(7), py::ssize_t(7)});
+               std::copy(r.cov.begin(), r.cov.end(), cov.mutable_data());
+               out["cov"] = cov;
+             }
+             const calico_imu_alignment_summary& sm = r.summary;
+             out["gyro_status"] = sm.gyro_status; out["accel_status"] = sm.accel_status; out["gyro_samples"] = sm.gyro_samples;
+             out["accel_samples"] = sm.accel_samples; out["first_sample"] = sm.first_sample; out["iterations"] = sm.iterations;
+             out["n_lags"] = sm.n_lags; out["peak_index"] = sm.peak_index; out["coarse_latency"] = sm.coarse_latency;
+             out["peak_correlation"] = sm.peak_correlation; out["gyro_rms"] = sm.gyro_rms; out["accel_rms"] = sm.accel_rms;
+             out["gravity_norm"] = sm.gravity_norm; out["scatter_pivot"] = sm.scatter_pivot; out["initial_cost"] = sm.initial_cost;
+             out["final_cost"] = sm.final_cost; out["lambda"] = sm.lambda;
+             return out;
+           },
+           py::arg("gyroscope"), py::arg("accelerometer") = py::none(), py::arg("options") = py::none(), py::arg("covariance") = false,
+           py::arg("curve") = false, py::arg("device") = 0);
 
   py::class_<Landmark, std::shared_ptr<Landmark>>(m, "Landmark")
       .def(py::init<>())

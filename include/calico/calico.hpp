@@ -624,6 +624,8 @@ class BSpline6 {
   std::vector<std::array<double, 6>> ctrl_;
 };
 
+namespace sensors { class Gyroscope; class Accelerometer; }
+
 class Trajectory {
  public:
   static constexpr int kDefaultSplineOrder = 6;       // trajectory.h:28
@@ -682,6 +684,24 @@ class Trajectory {
     return out;
   }
   const std::map<double, Pose3d>& trajectory() const { return poses_; }
+  /// What AlignImu returns: calico_imu_align's outputs. gravity_world and accel_bias are meaningful when
+  /// summary.accel_status == CALICO_ALIGN_OK; cov (7 x 7, row-major: rotation 3, bias 3, latency 1) and curve (summary.n_lags
+  /// correlations) are filled on request.
+  struct ImuAlignment {
+    Quaterniond q_rig_gyro{1, 0, 0, 0};
+    Vector3d gyro_bias{0, 0, 0}, gravity_world{0, 0, 0}, accel_bias{0, 0, 0};
+    double latency = 0.0;
+    std::vector<double> cov, curve;
+    calico_imu_alignment_summary summary{};
+  };
+  /// Camera-IMU alignment against this trajectory (calico_imu_align, on the device): the rotation rig <- gyroscope, the
+  /// gyroscope's bias, the IMU's latency and, with an accelerometer, the world's gravity and the accelerometer's bias, from the
+  /// sensors' registered measurements (AddMeasurement), in time order. The sensors are read, not changed
+  /// (utils.InitializeImu / the caller sets them). A Status that is not OK is an argument error or a device error; how the
+  /// estimation ended is summary.gyro_status / accel_status.
+  StatusOr<ImuAlignment> AlignImu(const sensors::Gyroscope& gyroscope, const sensors::Accelerometer* accelerometer = nullptr,
+                                  const calico_imu_alignment_options* options = nullptr, bool covariance = false, bool curve = false,
+                                  int device = 0) const;
  private:
   std::map<double, Pose3d> poses_;
   BSpline6 spline_;
@@ -1201,6 +1221,20 @@ class ImuSensor : public SensorCommon {
   }
   void ClearMeasurements() { id_to_measurement_.clear(); }
   int NumberOfMeasurements() const { return int(id_to_measurement_.size()); }
+  /// The registered measurements in time order (stamp, then sequence): stamps (n) and values (n x 3).
+  void SortedMeasurements(std::vector<double>* stamps, std::vector<double>* values) const {
+    std::vector<const ImuMeasurement*> order;
+    order.reserve(id_to_measurement_.size());
+    for (const auto& kv : id_to_measurement_) order.push_back(&kv.second);
+    std::sort(order.begin(), order.end(), [](const ImuMeasurement* a, const ImuMeasurement* b) {
+      return a->id.stamp != b->id.stamp ? a->id.stamp < b->id.stamp : a->id.sequence < b->id.sequence;
+    });
+    stamps->clear(); values->clear();
+    for (const ImuMeasurement* m : order) {
+      stamps->push_back(m->id.stamp);
+      for (int i = 0; i < 3; ++i) values->push_back(m->measurement[i]);
+    }
+  }
   const std::unordered_map<ImuObservationId, Vector3d, ImuObservationIdHash>& residuals() const { return id_to_residual_; }
   /// gyroscope.cpp:56-82 / accelerometer.cpp:76-123
   StatusOr<std::vector<ImuMeasurement>> Project(const std::vector<double>& interp_times, const Trajectory& traj, const WorldModel& world_model) const {
@@ -1263,6 +1297,30 @@ class Accelerometer : public ImuSensor<CALICO_SENSOR_ACCELEROMETER> {
 };
 
 }  // namespace sensors
+
+inline StatusOr<Trajectory::ImuAlignment> Trajectory::AlignImu(const sensors::Gyroscope& gyroscope, const sensors::Accelerometer* accelerometer,
+                                                               const calico_imu_alignment_options* options, bool covariance, bool curve,
+                                                               int device) const {
+  std::vector<double> gs, g, as, a, ctrl;
+  gyroscope.SortedMeasurements(&gs, &g);
+  if (accelerometer) accelerometer->SortedMeasurements(&as, &a);
+  for (const auto& c : spline_.control_points()) ctrl.insert(ctrl.end(), c.begin(), c.end());
+  double t_ra[3] = {0.0, 0.0, 0.0};
+  if (accelerometer)
+    for (int i = 0; i < 3; ++i) t_ra[i] = accelerometer->GetExtrinsics().translation()[i];
+  ImuAlignment r;
+  double q[4] = {0.0, 0.0, 0.0, 1.0};
+  if (covariance) r.cov.assign(49, 0.0);
+  if (curve) r.curve.assign(CALICO_ALIGN_MAX_LAGS, 0.0);
+  const int st = calico_imu_align(device, spline_.GetSplineOrder(), int(spline_.knots().size()), spline_.knots().data(),
+                                  spline_.basis_matrices().data(), ctrl.data(), int64_t(gs.size()), gs.data(), g.data(), int64_t(as.size()),
+                                  as.data(), a.data(), t_ra, nullptr, nullptr, options, q, r.gyro_bias.data(), &r.latency,
+                                  r.gravity_world.data(), r.accel_bias.data(), covariance ? r.cov.data() : nullptr, curve ? r.curve.data() : nullptr, &r.summary);
+  if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+  r.q_rig_gyro = Quaterniond(q[3], q[0], q[1], q[2]);
+  if (curve) r.curve.resize(size_t(r.summary.n_lags));
+  return r;
+}
 
 inline Status Covariance::ProjectionUncertainty(const sensors::Camera& camera, const std::vector<Vector2d>& pixels, double range,
                                                 ProjectionFrame frame, std::vector<std::array<double, 3>>* cov,

@@ -137,7 +137,7 @@ int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
  * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
- * calico_camera_calibrate); like a handle's message it
+ * calico_camera_calibrate, calico_imu_align); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -674,6 +674,104 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* int
                                 const calico_calibration_options* o /* NULL = defaults */, double* intrinsics_out, double* q_out,
                                 double* t_out, double* rms_out, int32_t* n_used_out, uint8_t* status_out,
                                 double* intrinsics_cov_out /* K x K, may be NULL */, calico_calibration_summary* summary);
+
+/* ---- camera-IMU alignment: rotation, gyroscope bias, latency and gravity from a fitted trajectory ---- */
+/* The start calico_solve needs for the IMU side, from the trajectory of the camera side (calico_fit_spline over the poses of
+ * calico_camera_resect / calico_camera_calibrate) and the raw IMU samples, on the device. The model is the optimiser's own
+ * gyroscope term with the scale-and-bias model at scale 1:
+ *   t = stamp - latency,  phi = -pose[0:3](t),  omega_rig = J(phi) phi',  prediction = -R(q_rig_gyro)^T omega_rig + bias,
+ *   residual = (measured - prediction) / sigma_gyro,
+ * so the result is a minimum of calico_solve's gyroscope cost over (rotation, bias, latency) at the given trajectory, and its
+ * numbers are the gyroscope's extrinsic rotation, intrinsics [1, bias] and latency as they stand. As there (and in the
+ * reference's Trajectory::GetEvaluationParams) the spline segment of a sample is the STAMP's; its polynomial is evaluated at t,
+ * beyond its own knots where the latency carries t there.
+ *   spline  order, n_knots, knots, basis as calico_fit_spline / calico_problem_set_spline take them; ctrl ((n_knots - order) x 6).
+ *   samples the gyroscope samples that take part are those whose stamp and whose time stamp - latency lie inside the valid knots
+ *          for EVERY latency of the grid  latency_init (or 0) + l lag_step, |l lag_step| <= max_lag (1e-9 relative slack on l)
+ *          -- when stage A does not run (a start is given, or estimate_latency == 0): at latency_init (or 0) alone. The stamps are sorted, so they are one range
+ *          [first_sample, first_sample + gyro_samples). Fewer than min_samples: CALICO_ALIGN_TOO_FEW_SAMPLES.
+ *   A      (no start given, estimate_latency != 0) per latency of the grid the normalised, centred cross-correlation of
+ *          |omega_rig(stamp - latency)| with |measured| over those samples; the maximum, refined by the parabola through its
+ *          two neighbours, is the coarse latency. CALICO_ALIGN_NO_PEAK: the maximum lies on the first or the last latency of the
+ *          grid, or a variance is below 1e-12 of its raw second moment (constant measurements, a trajectory at rest).
+ *   B      (no start given) at the coarse latency (0 without A) Horn's quaternion of the cross-covariance of -omega_rig and
+ *          measured (both centred when estimate_gyro_bias != 0); the bias is the mean residual. CALICO_ALIGN_DEGENERATE: the
+ *          second eigenvalue of the (centred) scatter of omega_rig is below 1e-6 of the first -- the rig turned about one axis
+ *          only and the rotation about it is undetermined; their ratio is summary->scatter_pivot.
+ *   C      Levenberg-Marquardt on (rotation 3: R <- exp([d]x) R, bias 3, latency 1) with analytic Jacobians, Marquardt damping
+ *          lambda diag from 1e-4 within [1e-12, 1e12]; what is not estimated is held. calico_camera_calibrate's rules: a
+ *          candidate whose cost is within the cost's own rounding error of the current one is accepted, one with a residual
+ *          that is not finite is rejected; step size s = max(|d_rot|_inf, |d_bias|_inf / max(1, |bias|_inf),
+ *          |d_latency| / max(1, |latency|)); stops after a step with s < step_tolerance taken at lambda <= 1e-4
+ *          (CALICO_ALIGN_OK), after max_iterations steps (CALICO_ALIGN_NOT_CONVERGED: the last accepted point), when the
+ *          normal matrix is not positive definite at the largest damping or, undamped, at the result
+ *          (CALICO_ALIGN_NOT_POSITIVE_DEFINITE), when the start is not finite (CALICO_ALIGN_DEGENERATE).
+ *          With q_init and latency_init the loop starts there, at zero bias.
+ *   D      (n_accel > 0, gyroscope part OK or NOT_CONVERGED) AccelerometerResidual's kinematics with q_rig_accel = q_rig_gyro,
+ *          the gyroscope's latency, the lever arm t_rig_accel (NULL = 0) and scale 1 are linear in (gravity_world, accel_bias):
+ *          one pass forms the 6 x 6 normal equations (3 x 3 with estimate_accel_bias == 0) over the samples whose stamp lies
+ *          inside the valid knots, a Cholesky solves them and one step of iterative refinement follows. CALICO_ALIGN_NOT_POSITIVE_DEFINITE (a trajectory that does not
+ *          turn cannot separate gravity from the bias) leaves gravity_world_out and accel_bias_out untouched, as every other
+ *          status but OK does; when the gyroscope part did not get that far, accel_status is its status.
+ * Outputs: q_rig_gyro_out (4: x y z w, unit, w >= 0), gyro_bias_out (3), latency_out -- the start (q_init normalised or the
+ * identity, zero bias, latency_init or 0) with TOO_FEW_SAMPLES, NO_PEAK and DEGENERATE; cov_out (7 x 7, may be NULL): the
+ * undamped inverse normal matrix (J^T J)^-1 of (rotation, bias, latency) at the result, zero rows and columns for what is not
+ * estimated, all zero unless the status is OK or NOT_CONVERGED; curve_out (may be NULL): the first summary->n_lags entries
+ * are the correlation curve when stage A ran, the others are never written.
+ * The call returns CALICO_OK whenever `summary` is meaningful. Repeated calls are bit-identical: every sum has a fixed order.
+ * Needs no problem handle: owns its device memory, message in calico_last_error(NULL).
+ * CALICO_INVALID_ARGUMENT, before the device is touched: order outside [2, 8], n_knots < 2 order, a NULL knots, basis, ctrl,
+ * output or summary, a negative count, NULL samples with a positive count (gravity_world_out and accel_bias_out may be NULL
+ * with n_accel == 0), stamps that decrease, lag_step <= 0, max_lag < 0, more than CALICO_ALIGN_MAX_LAGS latencies in the grid, an option that
+ * is not finite, step_tolerance <= 0, sigma_gyro <= 0, max_iterations < 1, min_samples < 3, q_init without latency_init or
+ * the reverse, a q_init or latency_init that is not finite or a q_init of zero length. n_gyro == 0 is CALICO_OK with
+ * CALICO_ALIGN_TOO_FEW_SAMPLES and touches no device. */
+#define CALICO_ALIGN_OK 0
+#define CALICO_ALIGN_TOO_FEW_SAMPLES 1
+#define CALICO_ALIGN_NO_PEAK 2
+#define CALICO_ALIGN_DEGENERATE 3
+#define CALICO_ALIGN_NOT_CONVERGED 4
+#define CALICO_ALIGN_NOT_POSITIVE_DEFINITE 5
+#define CALICO_ALIGN_MAX_LAGS 4096      /* the most latencies a grid may hold: what curve_out must have room for */
+typedef struct {
+  double max_lag;               /* 0.1 s */
+  double lag_step;              /* 1e-3 s */
+  int32_t max_iterations;       /* 50 */
+  double step_tolerance;        /* 1e-10 */
+  int32_t estimate_latency;     /* 1 */
+  int32_t estimate_gyro_bias;   /* 1 */
+  int32_t estimate_accel_bias;  /* 1 */
+  int32_t min_samples;          /* 16; values below 3 are an argument error */
+  double sigma_gyro;            /* 1: the gyroscope's sigma in calico_problem_add_sensor (scales the covariance and the RMS) */
+} calico_imu_alignment_options;
+typedef struct {
+  int32_t gyro_status;          /* CALICO_ALIGN_* */
+  int32_t accel_status;
+  int64_t gyro_samples;         /* samples that took part */
+  int64_t accel_samples;
+  int64_t first_sample;         /* index of the first gyroscope sample that took part */
+  int32_t iterations;           /* steps tried */
+  int32_t n_lags;               /* latencies of the grid (0: stage A did not run) */
+  int32_t peak_index;           /* of the curve's maximum (-1: stage A did not run) */
+  double coarse_latency;        /* the parabola's (the start's latency without stage A) */
+  double peak_correlation;
+  double gyro_rms;              /* sqrt(Sum |residual|^2 / (3 gyro_samples)), residuals divided by sigma_gyro */
+  double accel_rms;             /* m/s^2 */
+  double gravity_norm;
+  double scatter_pivot;         /* stage B: second / first eigenvalue of the scatter of omega_rig (0: stage B did not run) */
+  double initial_cost;          /* 1/2 Sum |residual|^2 at the start of stage C and at the result */
+  double final_cost;
+  double lambda;                /* the damping at the end */
+} calico_imu_alignment_summary;
+void calico_default_imu_alignment_options(calico_imu_alignment_options* o);
+int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                         const double* ctrl /* (n_knots - order) x 6 */, int64_t n_gyro, const double* gyro_stamps,
+                         const double* gyro /* n_gyro x 3 */, int64_t n_accel, const double* accel_stamps,
+                         const double* accel /* n_accel x 3 */, const double* t_rig_accel /* 3, or NULL */,
+                         const double* q_init /* 4 */, const double* latency_init /* 1; both NULL or both given */,
+                         const calico_imu_alignment_options* o /* NULL = defaults */, double* q_rig_gyro_out, double* gyro_bias_out,
+                         double* latency_out, double* gravity_world_out, double* accel_bias_out, double* cov_out /* 49, may be NULL */,
+                         double* curve_out /* n_lags, may be NULL */, calico_imu_alignment_summary* summary);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
