@@ -378,15 +378,36 @@ class Resection:
         self.q, self.t, self.rms, self.n_used, self.iterations, self.status, self.cov = q, t, rms, n_used, iterations, status, cov
 
 
-def resection_options(api, **kw):
-    """The library's default calico_resection_options with the given fields replaced."""
-    o = ResectionOptions()
-    api.default_resection_options(C.byref(o))
+def _options(struct_cls, default_fn, what, kw):
+    """The library's defaults of an options struct with the given fields replaced."""
+    o = struct_cls()
+    default_fn(C.byref(o))
     for name, v in kw.items():
         if not hasattr(o, name):
-            raise TypeError("no resection option %r" % name)
+            raise TypeError("no %s option %r" % (what, name))
         setattr(o, name, v)
     return o
+
+
+def resection_options(api, **kw):
+    """The library's default calico_resection_options with the given fields replaced."""
+    return _options(ResectionOptions, api.default_resection_options, "resection", kw)
+
+
+class _ChartBatch:
+    """The frames of calico_camera_resect / calico_camera_calibrate as contiguous arrays, which it holds for the length of the
+    call: nf, and `args`, their pointers in the order the calls take them (q_init and t_init may be None)."""
+
+    def __init__(self, frame_offsets, pixels, points, q_init, t_init):
+        off = np.ascontiguousarray(frame_offsets, dtype=np.int64).ravel()
+        self.nf = nf = len(off) - 1
+        px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
+        if nf < 0 or len(px) != len(pt) or off[-1] != len(px):
+            raise ValueError("frame_offsets must have n_frames + 1 entries and end at the number of pairs")
+        qi = None if q_init is None else _f64(q_init).reshape(nf, 4)
+        ti = None if t_init is None else _f64(t_init).reshape(nf, 3)
+        self.arrays = (off, px, pt, qi, ti)
+        self.args = [nf, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(px), _dp(pt), None if qi is None else _dp(qi), None if ti is None else _dp(ti)]
 
 
 def camera_resect(api, model, intrinsics, frame_offsets, pixels, points, q_init=None, t_init=None, options=None, covariance=False,
@@ -395,20 +416,14 @@ def camera_resect(api, model, intrinsics, frame_offsets, pixels, points, q_init=
     points (N, 3) into frames; q_init (n_frames, 4) and t_init (n_frames, 3) together, or neither (homography start: planar
     charts). options: a ResectionOptions (resection_options(api, ...)) or None. chunk: test hook (pairs per host-side pass)."""
     k = _f64(intrinsics).ravel()
-    off = np.ascontiguousarray(frame_offsets, dtype=np.int64).ravel()
-    nf = len(off) - 1
-    px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
-    if nf < 0 or len(px) != len(pt) or (nf >= 0 and len(off) and off[-1] != len(px)):
-        raise ValueError("frame_offsets must have n_frames + 1 entries and end at the number of pairs")
-    qi = None if q_init is None else _f64(q_init).reshape(nf, 4)
-    ti = None if t_init is None else _f64(t_init).reshape(nf, 3)
+    batch = _ChartBatch(frame_offsets, pixels, points, q_init, t_init)
+    nf = batch.nf
     m = max(nf, 1)
     q, t, rms = np.zeros((m, 4)), np.zeros((m, 3)), np.zeros(m)
     used, its, status = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.uint8)
     cov = np.zeros((m, 6, 6)) if covariance else None
-    args = [int(device), int(model), _dp(k), k.size, nf, off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(px), _dp(pt),
-            None if qi is None else _dp(qi), None if ti is None else _dp(ti), None if options is None else C.byref(options),
-            _dp(q), _dp(t), _dp(rms), _ip(used), _ip(its), _u8p(status), _dp(cov) if covariance else None]
+    args = [int(device), int(model), _dp(k), k.size] + batch.args + [None if options is None else C.byref(options), _dp(q), _dp(t), _dp(rms),
+                                                                 _ip(used), _ip(its), _u8p(status), _dp(cov) if covariance else None]
     if chunk is None:
         st = api.camera_resect(*args)
     else:
@@ -431,13 +446,7 @@ class Calibration:
 
 def calibration_options(api, **kw):
     """The library's default calico_calibration_options with the given fields replaced."""
-    o = CalibrationOptions()
-    api.default_calibration_options(C.byref(o))
-    for name, v in kw.items():
-        if not hasattr(o, name):
-            raise TypeError("no calibration option %r" % name)
-        setattr(o, name, v)
-    return o
+    return _options(CalibrationOptions, api.default_calibration_options, "calibration", kw)
 
 
 def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points, q_init=None, t_init=None, free_mask=None, options=None,
@@ -447,13 +456,8 @@ def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points,
     or neither (every frame is resected at intrinsics_init). free_mask: K flags, 0 = the entry is a constant; None = all free.
     options: a CalibrationOptions (calibration_options(api, ...)) or None. Returns a Calibration."""
     k = _f64(intrinsics_init).ravel()
-    off = np.ascontiguousarray(frame_offsets, dtype=np.int64).ravel()
-    nf = len(off) - 1
-    px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
-    if nf < 0 or len(px) != len(pt) or (len(off) and off[-1] != len(px)):
-        raise ValueError("frame_offsets must have n_frames + 1 entries and end at the number of pairs")
-    qi = None if q_init is None else _f64(q_init).reshape(nf, 4)
-    ti = None if t_init is None else _f64(t_init).reshape(nf, 3)
+    batch = _ChartBatch(frame_offsets, pixels, points, q_init, t_init)
+    nf = batch.nf
     mask = None if free_mask is None else np.ascontiguousarray(np.asarray(free_mask) != 0, dtype=np.uint8).ravel()
     if mask is not None and mask.size != k.size:
         raise ValueError("free_mask must have one entry per intrinsic")
@@ -464,23 +468,16 @@ def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points,
     used, status = np.zeros(m, np.int32), np.zeros(m, np.uint8)
     cov = np.zeros((k.size, k.size)) if covariance else None
     summary = CalibrationSummary()
-    st = api.camera_calibrate(int(device), int(model), _dp(k), k.size, None if mask is None else _u8p(mask), nf,
-                              off.ctypes.data_as(C.POINTER(C.c_int64)), _dp(px), _dp(pt), None if qi is None else _dp(qi),
-                              None if ti is None else _dp(ti), None if options is None else C.byref(options), _dp(k_out), _dp(q), _dp(t),
-                              _dp(rms), _ip(used), _u8p(status), _dp(cov) if covariance else None, C.byref(summary))
+    st = api.camera_calibrate(*([int(device), int(model), _dp(k), k.size, None if mask is None else _u8p(mask)] + batch.args +
+                                [None if options is None else C.byref(options), _dp(k_out), _dp(q), _dp(t), _dp(rms), _ip(used), _u8p(status),
+                                 _dp(cov) if covariance else None, C.byref(summary)]))
     _check_free(api, st)
     return Calibration(k_out, q[:nf], t[:nf], rms[:nf], used[:nf], status[:nf], cov, summary)
 
 
 def imu_alignment_options(api, **kw):
     """The library's default calico_imu_alignment_options with the given fields replaced."""
-    o = ImuAlignmentOptions()
-    api.default_imu_alignment_options(C.byref(o))
-    for name, v in kw.items():
-        if not hasattr(o, name):
-            raise TypeError("no IMU alignment option %r" % name)
-        setattr(o, name, v)
-    return o
+    return _options(ImuAlignmentOptions, api.default_imu_alignment_options, "IMU alignment", kw)
 
 
 def imu_align(api, order, knots, basis, ctrl, gyro_stamps, gyro, accel_stamps=None, accel=None, t_rig_accel=None, q_init=None,

@@ -359,7 +359,7 @@ DEV void normal_of(const double* g, unsigned free_bits, double diag_scale, doubl
 }
 }  // namespace
 
-// One wave: the candidate's partials added in workgroup order, the decision (the calibration's rules: a candidate within the
+// One wave: the candidate's partials added in workgroup order, the decision (lm_rule.hpp: a candidate within the
 // cost's rounding error is accepted, a small step ends the loop only at low damping), the damped step from the point that is
 // current afterwards, and the next candidate.
 __global__ __launch_bounds__(64) void align_decide_kernel(AlignArgs a, int n_chunks) {
@@ -392,15 +392,10 @@ __global__ __launch_bounds__(64) void align_decide_kernel(AlignArgs a, int n_chu
     new_cur = nxt; initial = cand;
   } else {
     const bool small = c->step < a.step_tolerance;
-    const bool gauss_newton = lambda <= kAlignLambda0;      // (the damped step is the undamped one to 1e-4: a small one means converged)
-    if (kept && cand <= current + kCostSlack * noise) {
-      new_cur = nxt;
-      lambda = fmax(lambda * 0.1, kResectLambdaMin);
-      if (small && gauss_newton) { status = CALICO_ALIGN_OK; done = 1; }
-    } else {
-      if (small && kept && gauss_newton) { status = CALICO_ALIGN_OK; done = 1; }
-      else lambda = fmin(lambda * 10.0, kResectLambdaMax);
-    }
+    const LmVerdict v = lm_rule(kept, cand, current, noise, small, lambda);
+    if (v.accept) new_cur = nxt;
+    lambda = v.lambda;
+    if (v.converged) { status = CALICO_ALIGN_OK; done = 1; }
   }
   if (done == 0 && iterations >= a.max_iterations) { status = CALICO_ALIGN_NOT_CONVERGED; done = 1; }
   if (done == 0) ++iterations;
@@ -414,8 +409,8 @@ __global__ __launch_bounds__(64) void align_decide_kernel(AlignArgs a, int n_chu
       normal_of(s_g, a.free_bits, 1.0 + lambda, s_h, s_b, lane);
       pd = lds_chol(s_h, 7, lane);
       if (!pd) {
-        if (lambda >= kResectLambdaMax) break;
-        lambda = fmin(lambda * 10.0, kResectLambdaMax);
+        if (lambda >= kLmLambdaMax) break;
+        lambda = fmin(lambda * 10.0, kLmLambdaMax);
       }
     }
     if (!pd) {

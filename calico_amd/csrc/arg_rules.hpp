@@ -1,0 +1,81 @@
+// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp), free of HIP:
+// the standard library and the C header only, so a plain host program can test them (tests/cpp/arg_rules_check.cpp). A rule
+// returns an empty string for "fine", or the message without the call's name (FreeCall, free_call.hpp, puts that in front).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/calico_hip.h"
+
+namespace cal {
+
+// ---- a camera model with its intrinsics (num_params: camera_model_num_params(model), -1: no such model), a count with its buffers ----
+inline std::string camera_model_error(int model, int num_params, const double* intrinsics, int n_intrinsics) {
+  if (num_params < 0) return "unknown camera model " + std::to_string(model);
+  if (n_intrinsics != num_params)
+    return "camera model " + std::to_string(model) + " has " + std::to_string(num_params) + " intrinsics, got " + std::to_string(n_intrinsics);
+  if (!intrinsics) return "null intrinsics";
+  return "";
+}
+inline std::string count_error(int64_t n, bool pointers_ok) {
+  if (n < 0) return "n must be >= 0";
+  if (n > 0 && !pointers_ok) return "null input or output buffer";
+  return "";
+}
+
+// ---- the chart batch of calico_camera_resect / calico_camera_calibrate: what holds whatever n_frames is (Options: either call's) ----
+template <class Options>
+std::string chart_options_error(int64_t n_frames, const Options& o, const double* q_init, const double* t_init) {
+  if (n_frames < 0) return "n_frames must be >= 0";
+  if (!std::isfinite(o.step_tolerance) || !(o.step_tolerance > 0.0)) return "step_tolerance must be finite and > 0";
+  if (o.max_iterations < 1) return "max_iterations must be >= 1";
+  if (!std::isfinite(o.huber_scale) || o.huber_scale < 0.0) return "huber_scale must be finite and >= 0";
+  if (o.min_points < 4) return "min_points must be >= 4";
+  if ((q_init == nullptr) != (t_init == nullptr)) return "q_init and t_init are given together or not at all";
+  return "";
+}
+// The frames of a batch with n_frames > 0 (n_frames + 1 offsets). outputs: the call has all its output buffers (`null_text` names them).
+inline std::string chart_frames_error(int64_t n_frames, const int64_t* offsets, bool outputs, const char* null_text, const double* pixels,
+                                      const double* points) {
+  if (!offsets || !outputs) return null_text;
+  if (offsets[0] != 0) return "frame_offsets must start at 0";
+  for (int64_t f = 0; f < n_frames; ++f)
+    if (offsets[f + 1] < offsets[f]) return "frame_offsets decrease at frame " + std::to_string(f);
+  if (offsets[n_frames] > 0 && (!pixels || !points)) return "null pixels or points";
+  return "";
+}
+
+// ---- a spline given as (order, knots) ----
+inline int spline_valid_knots(int order, int n_knots) { return n_knots - 2 * (order - 1); }      // segments: one fewer
+inline std::string spline_shape_error(int order, int n_knots, int max_order) {
+  if (order < 2 || order > max_order) return "order must be in [2, " + std::to_string(max_order) + "]";
+  if (n_knots < 2 * order) return "n_knots must be >= 2 order";
+  if (spline_valid_knots(order, n_knots) < 2) return "the knots hold no segment";
+  return "";
+}
+// GetSplineIndex (bspline.hpp:138-150): upper_bound(valid_knots, t) - 1, the last valid knot belongs to the last segment.
+// -1 where t lies outside the valid knots (or is not a number). valid_knots = knots + order - 1, n_valid of them.
+inline int spline_segment(const double* valid_knots, int n_valid, double t) {
+  if (!(t >= valid_knots[0]) || !(t <= valid_knots[n_valid - 1])) return -1;
+  return std::min(int(std::upper_bound(valid_knots, valid_knots + n_valid, t) - valid_knots) - 1, n_valid - 2);
+}
+
+// ---- sample stamps: finite and sorted (equal neighbours are fine) ----
+inline std::string stamps_error(const char* name, int64_t n, const double* stamps) {
+  for (int64_t i = 0; i < n; ++i) {
+    if (!std::isfinite(stamps[i])) return std::string(name) + " stamp " + std::to_string(i) + " is not finite";
+    if (i > 0 && stamps[i] < stamps[i - 1]) return std::string(name) + " stamps are not sorted: they decrease at sample " + std::to_string(i);
+  }
+  return "";
+}
+
+// ---- a caller's quaternion (x, y, z, w) as the unit quaternion with w >= 0; which lengths are an error is the caller's rule ----
+inline double quat_norm(const double* q) { return std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); }
+inline void canonical_unit_quat(const double* q, double norm, double* out) {
+  const double sg = (q[3] < 0.0 ? -1.0 : 1.0) / norm;
+  for (int i = 0; i < 4; ++i) out[i] = sg * q[i];
+}
+
+}  // namespace cal

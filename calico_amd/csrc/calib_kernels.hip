@@ -245,15 +245,10 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
     new_cur = nxt; initial = cand;
   } else {
     const bool small = fmax(step, c->step_k) < a.step_tolerance;
-    const bool gauss_newton = lambda <= kCalibLambda0;      // (the damped step is the undamped one to 1e-4: a small one means converged)
-    if (kept && common <= current + kCostSlack * noise) {
-      new_cur = nxt;
-      lambda = fmax(lambda * 0.1, kResectLambdaMin);
-      if (small && gauss_newton) { status = CALICO_CALIB_OK; done = 1; }
-    } else {
-      if (small && kept && gauss_newton) { status = CALICO_CALIB_OK; done = 1; }
-      else lambda = fmin(lambda * 10.0, kResectLambdaMax);
-    }
+    const LmVerdict v = lm_rule(kept, common, current, noise, small, lambda);
+    if (v.accept) new_cur = nxt;
+    lambda = v.lambda;
+    if (v.converged) { status = CALICO_CALIB_OK; done = 1; }
   }
   if (done == 0 && iterations >= a.max_iterations) { status = CALICO_CALIB_NOT_CONVERGED; done = 1; }
   if (done == 0) ++iterations;
@@ -383,8 +378,8 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
   if (!final) {
     if (!pd) {
       if (lane == 0) {
-        if (lambda >= kResectLambdaMax) { c->status = CALICO_CALIB_DEGENERATE; c->done = 1; }
-        else { c->lambda = fmin(lambda * 10.0, kResectLambdaMax); c->redo = 1; }
+        if (lambda >= kLmLambdaMax) { c->status = CALICO_CALIB_DEGENERATE; c->done = 1; }
+        else { c->lambda = fmin(lambda * 10.0, kLmLambdaMax); c->redo = 1; }
       }
       return;
     }
@@ -435,17 +430,7 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
 hipError_t launch_calib_evaluate(int model, const CalibArgs& a, hipStream_t s) {
   if (a.n_frames <= 0) return hipSuccess;
   const dim3 grid(unsigned((a.n_frames + kCalibWaves - 1) / kCalibWaves)), block(kCalibThreads);
-  switch (model) {
-    case 1: hipLaunchKernelGGL(calib_evaluate_kernel<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(calib_evaluate_kernel<2>, grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(calib_evaluate_kernel<3>, grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(calib_evaluate_kernel<4>, grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL(calib_evaluate_kernel<5>, grid, block, 0, s, a); break;
-    case 6: hipLaunchKernelGGL(calib_evaluate_kernel<6>, grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL(calib_evaluate_kernel<7>, grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_camera_model(model, [&](auto m) { hipLaunchKernelGGL(calib_evaluate_kernel<decltype(m)::value>, grid, block, 0, s, a); });
 }
 hipError_t launch_calib_decide(const CalibArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(calib_decide_kernel, dim3(1), dim3(64), 0, s, a);

@@ -138,6 +138,7 @@ int spline_index(const calico_problem* p, double t) {
   while (i + 1 < n && !(t < vk[size_t(i) + 1])) ++i;
   return i;
 }
+std::string& handle_free_error() { static thread_local std::string e; return e; }      // (free_call.hpp: its writers)
 
 }  // namespace cal
 

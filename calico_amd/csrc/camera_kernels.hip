@@ -130,43 +130,28 @@ int camera_model_num_params(int model) {
   }
 }
 
-#define CAMERA_MODEL_SWITCH(model, CALL)                                                                            \
-  switch (model) {                                                                                                  \
-    case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break;                 \
-    case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: return hipErrorInvalidValue;   \
-  }
-
 hipError_t launch_camera_unproject(int model, const double* k, long long n, const double* pixels, double* bearings, uint8_t* valid,
                                    hipStream_t s) {
   if (n <= 0) return hipSuccess;
-#define CALL(M) hipLaunchKernelGGL(camera_unproject_kernel<M>, dim3(camera_grid(n)), dim3(kCameraThreads), 0, s, k, n, pixels, bearings, valid)
-  CAMERA_MODEL_SWITCH(model, CALL)
-#undef CALL
-  return hipGetLastError();
+  const dim3 grid(camera_grid(n)), block(kCameraThreads);
+  return with_camera_model(model, [&](auto m) { hipLaunchKernelGGL(camera_unproject_kernel<decltype(m)::value>, grid, block, 0, s, k, n, pixels, bearings, valid); });
 }
 
 hipError_t launch_camera_project_points(int model, const double* k, long long n, const double* points, double* pixels, uint8_t* valid,
                                         double* d_point, double* d_intr, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   const dim3 grid(camera_grid(n)), block(kCameraThreads);
-  if (d_point || d_intr) {
-#define CALL(M) hipLaunchKernelGGL((camera_project_points_kernel<M, true>), grid, block, 0, s, k, n, points, pixels, valid, d_point, d_intr)
-    CAMERA_MODEL_SWITCH(model, CALL)
-#undef CALL
-  } else {
-#define CALL(M) hipLaunchKernelGGL((camera_project_points_kernel<M, false>), grid, block, 0, s, k, n, points, pixels, valid, d_point, d_intr)
-    CAMERA_MODEL_SWITCH(model, CALL)
-#undef CALL
-  }
-  return hipGetLastError();
+  return with_camera_model(model, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if (d_point || d_intr) hipLaunchKernelGGL((camera_project_points_kernel<M, true>), grid, block, 0, s, k, n, points, pixels, valid, d_point, d_intr);
+    else hipLaunchKernelGGL((camera_project_points_kernel<M, false>), grid, block, 0, s, k, n, points, pixels, valid, d_point, d_intr);
+  });
 }
 
 hipError_t launch_projection_uncertainty(int model, const UncertaintyArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-#define CALL(M) hipLaunchKernelGGL(projection_uncertainty_kernel<M>, dim3(camera_grid(a.n)), dim3(kCameraThreads), 0, s, a)
-  CAMERA_MODEL_SWITCH(model, CALL)
-#undef CALL
-  return hipGetLastError();
+  const dim3 grid(camera_grid(a.n)), block(kCameraThreads);
+  return with_camera_model(model, [&](auto m) { hipLaunchKernelGGL(projection_uncertainty_kernel<decltype(m)::value>, grid, block, 0, s, a); });
 }
 
 }  // namespace cal

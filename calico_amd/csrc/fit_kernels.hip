@@ -1,4 +1,4 @@
-// fit_kernels.hip — spline initialisation on the device.
+// fit_kernels.hip — spline initialisation on the device: the kernels of calico_fit_spline (host: fit.cpp).
 //
 // BSpline::FitToData / FitSpline (bspline.hpp:19-37, 246-297) solves the least-squares problem
 //   min_C || X C - data ||²,  X(j, si_j + a) = w_a(t_j)  (k non-zeros per row, si = GetSplineIndex(t)),
@@ -19,13 +19,10 @@
 // mean_diag, cond₂(X) 9.4e7, dropped; 20 %: 3.3e-13, roundoff decides; 30 %: 1.7e-11, cond₂ 4.1e5, kept).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdint>
-#include <vector>
 
-#include "../../include/calico_hip.h"
 #include "device_math.hpp"
+#include "kernels.hpp"
 
 namespace cal {
 
@@ -121,64 +118,17 @@ __global__ __launch_bounds__(64) void fit_solve_kernel(int n, int k, const doubl
   if (lane == 0) *status = bad ? 1 : 0;
 }
 
-}  // namespace cal
+size_t fit_solve_lds_bytes(int n_ctrl, int k) { return (size_t(n_ctrl) * k + size_t(n_ctrl) * 6) * sizeof(double); }
 
-namespace {
-template <class T> struct Buf {
-  T* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
-};
-}  // namespace
-
-extern "C" int32_t calico_fit_spline(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
-                                     int64_t n, const double* stamps, const double* data6, double* ctrl_out) {
-  using namespace cal;
-  if (order < 2 || order > kMaxOrder || !knots || !basis || !stamps || !data6 || !ctrl_out || n <= 0 || n_knots < 2 * order)
-    return CALICO_INVALID_ARGUMENT;
-  if (n > INT32_MAX) return CALICO_UNIMPLEMENTED;      // the kernels and seg_ptr index the samples with int
-  const int k = order, deg = k - 1, n_ctrl = n_knots - k, n_valid = n_knots - 2 * deg, n_seg = n_valid - 1;
-  if (n_seg < 1) return CALICO_INVALID_ARGUMENT;
-  // GetSplineIndex (bspline.hpp:138-150): upper_bound(valid_knots, t) - 1; the last valid knot belongs to the last segment
-  std::vector<int> seg(static_cast<size_t>(n)), seg_ptr(static_cast<size_t>(n_seg) + 1, 0);
-  const double* vk = knots + deg;
-  for (int64_t j = 0; j < n; ++j) {
-    const double t = stamps[j];
-    if (j > 0 && !(t >= stamps[j - 1])) return CALICO_INVALID_ARGUMENT;      // samples must be sorted (trajectory.cpp:24)
-    if (!(t >= vk[0]) || !(t <= vk[n_valid - 1])) return CALICO_INVALID_ARGUMENT;
-    int s = int(std::upper_bound(vk, vk + n_valid, t) - vk) - 1;
-    if (s > n_seg - 1) s = n_seg - 1;
-    seg[size_t(j)] = s;
-    seg_ptr[size_t(s) + 1] += 1;
-  }
-  for (int s = 0; s < n_seg; ++s) seg_ptr[size_t(s) + 1] += seg_ptr[size_t(s)];
-  const size_t lds = (size_t(n_ctrl) * k + size_t(n_ctrl) * 6) * sizeof(double);
-  if (lds > 156 * 1024) return CALICO_UNIMPLEMENTED;   // trajectory too long for the in-LDS banded solve
-  int dev_count = 0;
-  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count <= 0 || hipSetDevice(device) != hipSuccess) return CALICO_INTERNAL;
-  Buf<double> d_stamps, d_data, d_knots, d_basis, d_W, d_band, d_rhs, d_ctrl;
-  Buf<int> d_seg, d_ptr, d_status;
-#define TRY(x) do { if ((x) != hipSuccess) return CALICO_INTERNAL; } while (0)
-  TRY(d_stamps.alloc(size_t(n))); TRY(d_data.alloc(size_t(n) * 6)); TRY(d_knots.alloc(size_t(n_knots)));
-  TRY(d_basis.alloc(size_t(n_seg) * k * k)); TRY(d_W.alloc(size_t(n) * k)); TRY(d_band.alloc(size_t(n_ctrl) * k));
-  TRY(d_rhs.alloc(size_t(n_ctrl) * 6)); TRY(d_ctrl.alloc(size_t(n_ctrl) * 6)); TRY(d_seg.alloc(size_t(n)));
-  TRY(d_ptr.alloc(size_t(n_seg) + 1)); TRY(d_status.alloc(1));
-  TRY(hipMemcpy(d_stamps.p, stamps, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
-  TRY(hipMemcpy(d_data.p, data6, size_t(n) * 6 * sizeof(double), hipMemcpyHostToDevice));
-  TRY(hipMemcpy(d_knots.p, knots, size_t(n_knots) * sizeof(double), hipMemcpyHostToDevice));
-  TRY(hipMemcpy(d_basis.p, basis, size_t(n_seg) * k * k * sizeof(double), hipMemcpyHostToDevice));
-  TRY(hipMemcpy(d_seg.p, seg.data(), size_t(n) * sizeof(int), hipMemcpyHostToDevice));
-  TRY(hipMemcpy(d_ptr.p, seg_ptr.data(), (size_t(n_seg) + 1) * sizeof(int), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(fit_weights_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, 0, int(n), k, d_stamps.p, d_seg.p, d_knots.p,
-                     d_basis.p, d_W.p);
-  const int n_entries = n_ctrl * (k + 6);
-  hipLaunchKernelGGL(fit_normal_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, 0, n_ctrl, n_seg, k, d_W.p, d_data.p, d_ptr.p,
-                     d_band.p, d_rhs.p);
-  TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  hipLaunchKernelGGL(fit_solve_kernel, dim3(1), dim3(64), lds, 0, n_ctrl, k, d_band.p, d_rhs.p, d_ctrl.p, d_status.p);
-  int status = 0;
-  TRY(hipMemcpy(&status, d_status.p, sizeof(int), hipMemcpyDeviceToHost));
-  TRY(hipMemcpy(ctrl_out, d_ctrl.p, size_t(n_ctrl) * 6 * sizeof(double), hipMemcpyDeviceToHost));
-#undef TRY
-  return status == 0 ? CALICO_OK : CALICO_INTERNAL;
+hipError_t launch_fit_spline(int device, const FitArgs& a, hipStream_t s) {
+  const hipError_t e = raise_lds_limit(device, fit_solve_kernel, fit_solve_lds_bytes(a.n_ctrl, a.k));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fit_weights_kernel, dim3(unsigned((a.n + 255) / 256)), dim3(256), 0, s, a.n, a.k, a.stamps, a.seg, a.knots, a.basis, a.W);
+  const int n_entries = a.n_ctrl * (a.k + 6);
+  hipLaunchKernelGGL(fit_normal_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.seg_ptr, a.band,
+                     a.rhs);
+  hipLaunchKernelGGL(fit_solve_kernel, dim3(1), dim3(64), fit_solve_lds_bytes(a.n_ctrl, a.k), s, a.n_ctrl, a.k, a.band, a.rhs, a.ctrl, a.status);
+  return hipGetLastError();
 }
+
+}  // namespace cal

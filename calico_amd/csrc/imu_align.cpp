@@ -12,50 +12,23 @@
 #include <vector>
 
 #include "../../include/calico_hip.h"
+#include "arg_rules.hpp"
 #include "device_math.hpp"
+#include "free_call.hpp"
 #include "kernels.hpp"
-#include "problem_host.hpp"
+#include "lm_rule.hpp"
 
 namespace {
-
 using namespace cal;
-
-const char* const kWhat = "calico_imu_align";
+const FreeCall call{"calico_imu_align"};
 static_assert(kAlignMaxLags == CALICO_ALIGN_MAX_LAGS, "the peak kernel's curve holds what the header promises");
-
-int fail(int code, const std::string& msg) {
-  handle_free_error() = std::string(kWhat) + ": " + msg;
-  return code;
-}
-int invalid(const std::string& msg) { return fail(CALICO_INVALID_ARGUMENT, msg); }
-
-template <class T> struct Buf {      // the call's own device memory (as calico_fit_spline's)
-  T* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), (n ? n : 1) * sizeof(T)); }
-  hipError_t upload(const T* src, size_t n) {
-    const hipError_t e = alloc(n);
-    return e != hipSuccess || n == 0 ? e : hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice);
-  }
-};
-#define ALIGN_TRY(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return fail(CALICO_INTERNAL, hipGetErrorString(e_)); } while (0)
-
-int check_stamps(const char* name, int64_t n, const double* stamps) {
-  for (int64_t i = 0; i < n; ++i) {
-    if (!std::isfinite(stamps[i])) return invalid(std::string(name) + " stamp " + std::to_string(i) + " is not finite");
-    if (i > 0 && stamps[i] < stamps[i - 1]) return invalid(std::string(name) + " stamps are not sorted: they decrease at sample " + std::to_string(i));
-  }
-  return CALICO_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 void calico_default_imu_alignment_options(calico_imu_alignment_options* o) {
-  if (!o) return;
-  o->max_lag = 0.1; o->lag_step = 1e-3; o->max_iterations = 50; o->step_tolerance = 1e-10;
-  o->estimate_latency = 1; o->estimate_gyro_bias = 1; o->estimate_accel_bias = 1; o->min_samples = 16; o->sigma_gyro = 1.0;
+  // max_lag, lag_step, max_iterations, step_tolerance, estimate_latency / _gyro_bias / _accel_bias, min_samples, sigma_gyro
+  if (o) *o = {0.1, 1e-3, 50, 1e-10, 1, 1, 1, 16, 1.0};
 }
 
 int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis, const double* ctrl,
@@ -64,42 +37,40 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
                          const calico_imu_alignment_options* opt, double* q_out, double* bias_out, double* latency_out,
                          double* gravity_out, double* accel_bias_out, double* cov_out, double* curve_out,
                          calico_imu_alignment_summary* summary) {
-  if (order < 2 || order > kMaxOrder) return invalid("order must be in [2, " + std::to_string(kMaxOrder) + "]");
-  if (n_knots < 2 * order) return invalid("n_knots must be >= 2 order");
-  if (!knots || !basis || !ctrl) return invalid("null knots, basis or ctrl");
-  if (n_gyro < 0 || n_accel < 0) return invalid("n_gyro and n_accel must be >= 0");
-  if (n_gyro > INT32_MAX || n_accel > INT32_MAX) return fail(CALICO_UNIMPLEMENTED, "more than 2^31 - 1 samples");
-  if (n_gyro > 0 && (!gyro_stamps || !gyro)) return invalid("null gyro_stamps or gyro");
-  if (n_accel > 0 && (!accel_stamps || !accel)) return invalid("null accel_stamps or accel");
-  if (!q_out || !bias_out || !latency_out || !summary) return invalid("null q_rig_gyro_out, gyro_bias_out, latency_out or summary");
-  if (n_accel > 0 && (!gravity_out || !accel_bias_out)) return invalid("null gravity_world_out or accel_bias_out");
+  std::string error = spline_shape_error(order, n_knots, kMaxOrder);
+  if (!error.empty()) return call.invalid(error);
+  if (!knots || !basis || !ctrl) return call.invalid("null knots, basis or ctrl");
+  if (n_gyro < 0 || n_accel < 0) return call.invalid("n_gyro and n_accel must be >= 0");
+  if (n_gyro > INT32_MAX || n_accel > INT32_MAX) return call.fail(CALICO_UNIMPLEMENTED, "more than 2^31 - 1 samples");
+  if (n_gyro > 0 && (!gyro_stamps || !gyro)) return call.invalid("null gyro_stamps or gyro");
+  if (n_accel > 0 && (!accel_stamps || !accel)) return call.invalid("null accel_stamps or accel");
+  if (!q_out || !bias_out || !latency_out || !summary) return call.invalid("null q_rig_gyro_out, gyro_bias_out, latency_out or summary");
+  if (n_accel > 0 && (!gravity_out || !accel_bias_out)) return call.invalid("null gravity_world_out or accel_bias_out");
   calico_imu_alignment_options o;
   calico_default_imu_alignment_options(&o);
   if (opt) o = *opt;
-  if (!std::isfinite(o.lag_step) || !(o.lag_step > 0.0)) return invalid("lag_step must be finite and > 0");
-  if (!std::isfinite(o.max_lag) || o.max_lag < 0.0) return invalid("max_lag must be finite and >= 0");
+  if (!std::isfinite(o.lag_step) || !(o.lag_step > 0.0)) return call.invalid("lag_step must be finite and > 0");
+  if (!std::isfinite(o.max_lag) || o.max_lag < 0.0) return call.invalid("max_lag must be finite and >= 0");
   const double half = std::floor(o.max_lag / o.lag_step * (1.0 + 1e-9));
-  if (!(2.0 * half + 1.0 <= double(kAlignMaxLags))) return invalid("max_lag / lag_step gives more than " + std::to_string(kAlignMaxLags) + " lags");
-  if (!std::isfinite(o.step_tolerance) || !(o.step_tolerance > 0.0)) return invalid("step_tolerance must be finite and > 0");
-  if (!std::isfinite(o.sigma_gyro) || !(o.sigma_gyro > 0.0)) return invalid("sigma_gyro must be finite and > 0");
-  if (o.max_iterations < 1) return invalid("max_iterations must be >= 1");
-  if (o.min_samples < 3) return invalid("min_samples must be >= 3");
-  if ((q_init == nullptr) != (latency_init == nullptr)) return invalid("q_init and latency_init are given together or not at all");
+  if (!(2.0 * half + 1.0 <= double(kAlignMaxLags))) return call.invalid("max_lag / lag_step gives more than " + std::to_string(kAlignMaxLags) + " lags");
+  if (!std::isfinite(o.step_tolerance) || !(o.step_tolerance > 0.0)) return call.invalid("step_tolerance must be finite and > 0");
+  if (!std::isfinite(o.sigma_gyro) || !(o.sigma_gyro > 0.0)) return call.invalid("sigma_gyro must be finite and > 0");
+  if (o.max_iterations < 1) return call.invalid("max_iterations must be >= 1");
+  if (o.min_samples < 3) return call.invalid("min_samples must be >= 3");
+  if ((q_init == nullptr) != (latency_init == nullptr)) return call.invalid("q_init and latency_init are given together or not at all");
   double q0[4] = {0.0, 0.0, 0.0, 1.0};
   double lat0 = 0.0;
   if (q_init) {
-    const double nrm = std::sqrt(q_init[0] * q_init[0] + q_init[1] * q_init[1] + q_init[2] * q_init[2] + q_init[3] * q_init[3]);
-    if (!std::isfinite(nrm) || !(nrm > 0.0)) return invalid("q_init must be finite and of non-zero length");
-    if (!std::isfinite(*latency_init)) return invalid("latency_init must be finite");
-    const double sg = (q_init[3] < 0.0 ? -1.0 : 1.0) / nrm;
-    for (int i = 0; i < 4; ++i) q0[i] = sg * q_init[i];
+    const double nrm = quat_norm(q_init);
+    if (!std::isfinite(nrm) || !(nrm > 0.0)) return call.invalid("q_init must be finite and of non-zero length");
+    if (!std::isfinite(*latency_init)) return call.invalid("latency_init must be finite");
+    canonical_unit_quat(q_init, nrm, q0);
     lat0 = *latency_init;
   }
-  if (int rc = check_stamps("gyro", n_gyro, gyro_stamps)) return rc;
-  if (int rc = check_stamps("accel", n_accel, accel_stamps)) return rc;
+  if (!(error = stamps_error("gyro", n_gyro, gyro_stamps)).empty()) return call.invalid(error);
+  if (!(error = stamps_error("accel", n_accel, accel_stamps)).empty()) return call.invalid(error);
 
-  const int k = order, n_valid = n_knots - 2 * (k - 1), n_seg = n_valid - 1, n_ctrl = n_knots - k;
-  if (n_seg < 1) return invalid("the knots hold no segment");
+  const int k = order, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1, n_ctrl = n_knots - k;
   const double* const vk = knots + (k - 1);
   // the grid, and the samples every latency of it keeps on the valid knots
   const int L = int(half), n_lags = 2 * L + 1;
@@ -116,7 +87,7 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   *summary = calico_imu_alignment_summary{};
   summary->gyro_status = CALICO_ALIGN_TOO_FEW_SAMPLES; summary->accel_status = CALICO_ALIGN_TOO_FEW_SAMPLES;
   summary->gyro_samples = n_used; summary->first_sample = first; summary->peak_index = -1; summary->coarse_latency = lat0;
-  summary->lambda = kAlignLambda0;
+  summary->lambda = kLmLambda0;
   const auto give_start = [&]() {
     std::copy(q0, q0 + 4, q_out);
     bias_out[0] = bias_out[1] = bias_out[2] = 0.0;
@@ -125,36 +96,27 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   };
   if (n_used < o.min_samples) { give_start(); return CALICO_OK; }
 
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count || hipSetDevice(device) != hipSuccess)
-    return fail(CALICO_INTERNAL, "no usable HIP device " + std::to_string(device));
+  if (int rc = call.select_device(device)) return rc;
 
   const int n = int(n_used), chunks = align_chunks(n), accel_chunks = align_chunks(int(n_accel));
-  Buf<double> d_knots, d_basis, d_ctrl, d_stamps, d_meas, d_lags, d_corr, d_corr_m, d_curve, d_part, d_as, d_am;
-  Buf<AlignControl> d_c;
-  ALIGN_TRY(d_knots.upload(knots, size_t(n_knots)));
-  ALIGN_TRY(d_basis.upload(basis, size_t(n_seg) * k * k));
-  ALIGN_TRY(d_ctrl.upload(ctrl, size_t(n_ctrl) * 6));
-  ALIGN_TRY(d_stamps.upload(gyro_stamps + first, size_t(n)));
-  ALIGN_TRY(d_meas.upload(gyro + 3 * first, size_t(n) * 3));
-  ALIGN_TRY(d_lags.upload(lags.data(), lags.size()));
-  ALIGN_TRY(d_corr.alloc(search ? size_t(chunks) * n_lags * 3 : 0));
-  ALIGN_TRY(d_corr_m.alloc(size_t(chunks) * 2));
-  ALIGN_TRY(d_curve.alloc(size_t(n_lags)));
-  ALIGN_TRY(d_part.alloc(size_t(std::max(chunks, accel_chunks)) * kAlignPart));
-  ALIGN_TRY(d_as.upload(accel_stamps, size_t(n_accel)));
-  ALIGN_TRY(d_am.upload(accel, size_t(n_accel) * 3));
+  FreeBuf<double> d_knots, d_basis, d_ctrl, d_stamps, d_meas, d_lags, d_corr, d_corr_m, d_curve, d_part, d_as, d_am;
+  FreeBuf<AlignControl> d_c;
+  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
+  FREE_TRY(call, d_ctrl.upload(ctrl, size_t(n_ctrl) * 6)); FREE_TRY(call, d_stamps.upload(gyro_stamps + first, size_t(n)));
+  FREE_TRY(call, d_meas.upload(gyro + 3 * first, size_t(n) * 3)); FREE_TRY(call, d_lags.upload(lags.data(), lags.size()));
+  FREE_TRY(call, d_corr.alloc(search ? size_t(chunks) * n_lags * 3 : 0)); FREE_TRY(call, d_corr_m.alloc(size_t(chunks) * 2));
+  FREE_TRY(call, d_curve.alloc(size_t(n_lags))); FREE_TRY(call, d_part.alloc(size_t(std::max(chunks, accel_chunks)) * kAlignPart));
+  FREE_TRY(call, d_as.upload(accel_stamps, size_t(n_accel))); FREE_TRY(call, d_am.upload(accel, size_t(n_accel) * 3));
 
   AlignControl c;
   std::memset(&c, 0, sizeof(c));
   c.gyro_status = CALICO_ALIGN_NOT_CONVERGED; c.accel_status = CALICO_ALIGN_TOO_FEW_SAMPLES; c.first = 1; c.peak_index = -1;
-  c.lambda = kAlignLambda0; c.coarse_latency = lat0;
+  c.lambda = kLmLambda0; c.coarse_latency = lat0;
   for (int s = 0; s < 2; ++s) {
     for (int i = 0; i < 4; ++i) c.q[s][i] = q0[i];
     c.latency[s] = lat0;
   }
-  ALIGN_TRY(d_c.alloc(1));
-  ALIGN_TRY(hipMemcpy(d_c.p, &c, sizeof(c), hipMemcpyHostToDevice));
+  FREE_TRY(call, d_c.upload(&c, 1));
 
   AlignArgs a = {};
   a.ctrl = d_c.p; a.order = k; a.n_valid = n_valid; a.knots = d_knots.p; a.basis = d_basis.p; a.spline_ctrl = d_ctrl.p;
@@ -166,16 +128,16 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   for (int i = 0; i < 3; ++i) a.t_ra[i] = t_rig_accel ? t_rig_accel[i] : 0.0;
   a.estimate_accel_bias = o.estimate_accel_bias; a.min_samples = o.min_samples;
 
-  if (search) ALIGN_TRY(launch_align_correlate(a, nullptr));
-  if (!q_init) ALIGN_TRY(launch_align_horn(a, nullptr));
+  if (search) FREE_TRY(call, launch_align_correlate(a, nullptr));
+  if (!q_init) FREE_TRY(call, launch_align_horn(a, nullptr));
   // the first launch evaluates the start, every later one a candidate; launches behind the end return at once
-  for (int it = 0; it < o.max_iterations + 2; ++it) ALIGN_TRY(launch_align_iteration(a, nullptr));
-  ALIGN_TRY(launch_align_finish(a, nullptr));
-  ALIGN_TRY(launch_align_gravity(a, nullptr));
-  ALIGN_TRY(hipMemcpy(&c, d_c.p, sizeof(c), hipMemcpyDeviceToHost));
+  for (int it = 0; it < o.max_iterations + 2; ++it) FREE_TRY(call, launch_align_iteration(a, nullptr));
+  FREE_TRY(call, launch_align_finish(a, nullptr));
+  FREE_TRY(call, launch_align_gravity(a, nullptr));
+  FREE_TRY(call, d_c.download(&c, 1));
   if (search) {
     summary->n_lags = n_lags;
-    if (curve_out) ALIGN_TRY(hipMemcpy(curve_out, d_curve.p, size_t(n_lags) * sizeof(double), hipMemcpyDeviceToHost));
+    if (curve_out) FREE_TRY(call, d_curve.download(curve_out, size_t(n_lags)));
   }
 
   summary->gyro_status = c.gyro_status; summary->iterations = c.iterations; summary->peak_index = c.peak_index;

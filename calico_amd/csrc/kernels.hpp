@@ -6,6 +6,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "problem_dev.hpp"
 
@@ -125,10 +126,30 @@ hipError_t configure_observability_kernel(int device);
 void launch_cp_stamps(int n, int k, const double* stamps, const int* seg, const double* knots, const double* basis, const double* band,
                       double* out, hipStream_t s);
 
+// ---- spline fit (fit_kernels.hip; device pointers: seg_ptr is the CSR of the sorted samples over the segments) ----------------
+struct FitArgs {
+  int n, k, n_ctrl, n_seg;
+  const double* stamps; const int* seg; const int* seg_ptr; const double* knots; const double* basis; const double* data;
+  double* W; double* band; double* rhs; double* ctrl; int* status;
+};
+size_t fit_solve_lds_bytes(int n_ctrl, int k);      // the solve works in LDS: the caller refuses what does not fit
+hipError_t launch_fit_spline(int device, const FitArgs& a, hipStream_t s);
+
 // ---- camera model maps (camera_kernels.hip): free pixels and points, no residual blocks -----------------------------------
 // All pointers are device memory; `k` (the intrinsics) and, in the rig frame, q_rc are read through wave-uniform addresses. The
 // launches return the launch's own status; n == 0 launches nothing.
 int camera_model_num_params(int model);      // -1: no such model
+// The one dispatch on the camera model: f(std::integral_constant<int, MODEL>{}) launches; hipErrorInvalidValue: no such model
+template <class F>
+hipError_t with_camera_model(int model, F&& f) {
+  using std::integral_constant;
+  switch (model) {
+    case 1: f(integral_constant<int, 1>{}); break; case 2: f(integral_constant<int, 2>{}); break; case 3: f(integral_constant<int, 3>{}); break;
+    case 4: f(integral_constant<int, 4>{}); break; case 5: f(integral_constant<int, 5>{}); break; case 6: f(integral_constant<int, 6>{}); break;
+    case 7: f(integral_constant<int, 7>{}); break; default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
 hipError_t launch_camera_unproject(int model, const double* k, long long n, const double* pixels /* n x 2 */, double* bearings /* n x 3 */,
                                    uint8_t* valid, hipStream_t s);
 // d_point (n x 2 x 3) and d_intr (n x 2 x K) may be nullptr (both: the instantiation without derivatives); valid may be nullptr
@@ -186,7 +207,6 @@ struct CalibControl {
 // pairs, [10] the cost's rounding scale), [24] Sum rho over the pairs valid at both points, [25] pairs lost, [26] the pose step's
 // size, and from [32] Y = A^-1 [B g], column j at 32 + 6 j.
 constexpr int kCalibShare = 128;                         // doubles per frame of `share` (at most 66 + 11 + 11 + 4 are used)
-constexpr double kCalibLambda0 = 1e-4;                    // the first damping (the resection's)
 constexpr int kCalibSlot = 12, kCalibCommon = 24, kCalibLost = 25, kCalibStep = 26, kCalibY = 32, kCalibFrameDoubles = 112;
 struct CalibArgs {
   CalibControl* ctrl;
@@ -221,7 +241,6 @@ constexpr int kAlignPart = 40;                           // doubles per workgrou
 constexpr int kAlignThreads = 256;                       // samples per workgroup of every per-sample kernel
 constexpr int kAlignLagTile = 8;                         // lags per workgroup of the correlation
 constexpr int kAlignMaxLags = 4096;                      // CALICO_ALIGN_MAX_LAGS (imu_align.cpp asserts it)
-constexpr double kAlignLambda0 = 1e-4;                   // the first damping (the calibration's)
 constexpr int kAlignHornSums = 21;                       // Sum u (3), Sum v (3), Sum v u^T (9), Sum u u^T (6): u = -omega_rig, v = measured
 constexpr int kAlignAccelSums = 16;                      // samples (1), Sum M (9), Sum M^T y (3), Sum y (3)
 constexpr int kAlignAccelResidual = 8;                   // Sum |r|^2, samples, A^T r (6)

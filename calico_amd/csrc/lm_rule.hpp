@@ -1,0 +1,29 @@
+// lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip,
+// calib_kernels.hip, align_kernels.hip): accept or reject a candidate, the next damping, and whether the loop has converged.
+// What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
+// a damped system is not positive definite. Host and device code (the host sets the control word's first damping).
+#pragma once
+#include "device_math.hpp"
+
+namespace cal {
+
+constexpr double kLmLambda0 = 1e-4, kLmLambdaMin = 1e-12, kLmLambdaMax = 1e12;
+// A cost cannot tell two points apart whose costs differ by less than its own rounding error: a residual of e pixels at a pixel
+// coordinate u carries an error of about eps |u|, its square one of 2 |e| eps |u|. A candidate within kCostSlack eps Sum |e| |u|
+// of the current cost is accepted on the model's word (its gradient is known far better than its cost). `noise` is that sum.
+constexpr double kCostSlack = 8.0 * 2.220446049250313e-16;
+
+// accept: the candidate becomes the current point; converged: the loop ends, there or at the point kept; lambda: the next damping
+struct LmVerdict { bool accept, converged; double lambda; };
+
+// kept: the candidate is finite and lost no observation; small: the step that made it was below the tolerance. At
+// lambda <= kLmLambda0 the damped step is the Gauss-Newton step to 1e-4, so a small one means converged -- accepted or not.
+DEV LmVerdict lm_rule(bool kept, double candidate, double current, double noise, bool small, double lambda) {
+  LmVerdict v;
+  v.accept = kept && candidate <= current + kCostSlack * noise;
+  v.converged = small && kept && lambda <= kLmLambda0;
+  v.lambda = v.accept ? fmax(lambda * 0.1, kLmLambdaMin) : v.converged ? lambda : fmin(lambda * 10.0, kLmLambdaMax);
+  return v;
+}
+
+}  // namespace cal

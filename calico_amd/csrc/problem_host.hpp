@@ -453,8 +453,6 @@ struct RcclApi {
 };
 RcclApi& rccl();
 int spline_index(const calico_problem* p, double t);
-// camera.cpp: the message of the calling thread's last non-OK call without a handle (calico_last_error(NULL))
-std::string& handle_free_error();
 // a sharded handle (calico_problem_set_shard, world > 1) evaluates only with an exchange: CALICO_OK, or the error set
 int require_exchange(calico_problem* p);
 // plan.cpp

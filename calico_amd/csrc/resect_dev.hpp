@@ -1,25 +1,21 @@
 // resect_dev.hpp — what the per-frame Levenberg-Marquardt kernels share (resect_kernels.hip: the pose of a frame at given
 // intrinsics; calib_kernels.hip: the intrinsics and the poses of all frames): one wave per frame, wave-uniform small dense systems
-// in the wave's LDS area, quaternion helpers, the damping's constants and the cost's rounding slack. Device code only.
+// in the wave's LDS area, quaternion helpers. The step rule itself is lm_rule.hpp's. Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "camera_inverse.hpp"
+#include "lm_rule.hpp"
 #include "problem_dev.hpp"
 
 namespace cal {
 
-constexpr double kResectLambda0 = 1e-4, kResectLambdaMin = 1e-12, kResectLambdaMax = 1e12;
-// A cost cannot tell two poses apart whose costs differ by less than its own rounding error: a residual of e pixels at a pixel
-// coordinate u carries an error of about eps |u|, its square one of 2 |e| eps |u|. A candidate within kCostSlack eps Sum |e| |u|
-// of the current cost is accepted on the model's word (its gradient is known far better than its cost).
-constexpr double kCostSlack = 8.0 * 2.220446049250313e-16;
-
 namespace {
 
 DEV bool uniform_flag(bool v) { return __builtin_amdgcn_readfirstlane(int(v)) != 0; }
+DEV double uniform_value(double v) { return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v))); }
 
 DEV double wave_max(double v) {
 #pragma unroll

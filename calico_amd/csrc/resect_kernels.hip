@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
     wave_fence();
   }
   if (run) {
-    double lambda = kResectLambda0;
+    double lambda = kLmLambda0;
     bool first = true, small = false;
 #pragma unroll 1
     for (;;) {
@@ -284,14 +284,11 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
         if (!kept || uniform_flag(cand[kValid] < 1.0)) { status = CALICO_RESECT_DEGENERATE; break; }
         cur ^= 1;
         first = false;
-      } else if (kept && uniform_flag(cost_common <= slots[kSlot * cur + kCost] + kCostSlack * slots[kSlot * cur + kNoise])) {
-        cur ^= 1;
-        const bool gauss_newton = lambda <= kResectLambda0;      // (the damped step is the undamped one to 1e-4: a small one means converged)
-        lambda = fmax(lambda * 0.1, kResectLambdaMin);
-        if (small && gauss_newton) { status = CALICO_RESECT_OK; break; }
       } else {
-        if (small && kept && lambda <= kResectLambda0) { status = CALICO_RESECT_OK; break; }
-        lambda = fmin(lambda * 10.0, kResectLambdaMax);
+        const LmVerdict v = lm_rule(kept, cost_common, slots[kSlot * cur + kCost], slots[kSlot * cur + kNoise], small, lambda);
+        if (uniform_flag(v.accept)) cur ^= 1;
+        lambda = uniform_value(v.lambda);      // (the verdict is wave-uniform; said so, lambda stays in scalar registers)
+        if (uniform_flag(v.converged)) { status = CALICO_RESECT_OK; break; }
       }
       if (iterations >= a.max_iterations) break;
       ++iterations;
@@ -308,8 +305,8 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
         }
         wave_fence();
         pd = lds_chol(W, 6, lane);
-        if (pd || lambda >= kResectLambdaMax) break;
-        lambda = fmin(lambda * 10.0, kResectLambdaMax);
+        if (pd || lambda >= kLmLambdaMax) break;
+        lambda = fmin(lambda * 10.0, kLmLambdaMax);
       }
       if (!pd) { status = CALICO_RESECT_DEGENERATE; break; }
       lds_chol_solve(W, rhs, 6, lane);
@@ -367,17 +364,7 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
 hipError_t launch_camera_resect(int model, const ResectArgs& a, hipStream_t s) {
   if (a.n_frames <= 0) return hipSuccess;
   const dim3 grid(unsigned((a.n_frames + kResectWaves - 1) / kResectWaves)), block(kResectThreads);
-  switch (model) {
-    case 1: hipLaunchKernelGGL(resect_kernel<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(resect_kernel<2>, grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL(resect_kernel<3>, grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(resect_kernel<4>, grid, block, 0, s, a); break;
-    case 5: hipLaunchKernelGGL(resect_kernel<5>, grid, block, 0, s, a); break;
-    case 6: hipLaunchKernelGGL(resect_kernel<6>, grid, block, 0, s, a); break;
-    case 7: hipLaunchKernelGGL(resect_kernel<7>, grid, block, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_camera_model(model, [&](auto m) { hipLaunchKernelGGL(resect_kernel<decltype(m)::value>, grid, block, 0, s, a); });
 }
 
 }  // namespace cal

@@ -863,6 +863,25 @@ struct CameraObservationIdHash {
 };
 struct CameraMeasurement { Vector2d pixel; CameraObservationId id; };
 
+namespace detail {
+/// What ResectChart and CalibrateFromChart check and pack alike (px, pt: 2 and 3 doubles per pair; a free_mask has K entries).
+inline Status PackChartBatch(const std::string& what, const std::vector<int64_t>& frame_offsets, const std::vector<Vector2d>& pixels,
+                             const std::vector<Vector3d>& points, const std::vector<double>* q_init, const std::vector<double>* t_init,
+                             size_t mask_size, size_t K, std::vector<double>* px, std::vector<double>* pt) {
+  const size_t nf = frame_offsets.size() - 1, n = pixels.size();
+  if (frame_offsets.empty() || n != points.size() || frame_offsets.back() != int64_t(n))
+    return InvalidArgumentError(what + ": frame_offsets must have n_frames + 1 entries and end at the number of pairs");
+  if ((q_init && q_init->size() != 4 * nf) || (t_init && t_init->size() != 3 * nf))
+    return InvalidArgumentError(what + ": q_init / t_init must hold 4 / 3 doubles per frame");
+  if (mask_size != 0 && mask_size != K) return InvalidArgumentError(what + ": free_mask must have one entry per intrinsic");
+  for (size_t i = 0; i < n; ++i) {
+    px->insert(px->end(), {pixels[i].x(), pixels[i].y()});
+    pt->insert(pt->end(), {points[i][0], points[i][1], points[i][2]});
+  }
+  return OkStatus();
+}
+}  // namespace detail
+
 /// sensors::CameraModel (camera_models.h): the inverse model, on the device (calico_camera_unproject). The result is the
 /// UNIT-NORM point that projects to the pixel under the library's projection -- the usual bearing for every model but
 /// ExtendedUnified, whose projection is not scale invariant (include/calico_hip.h). A model is named by its enum value:
@@ -911,16 +930,9 @@ class CameraModel {
                             ChartResection* out, bool covariance = false, const std::vector<double>* q_init = nullptr,
                             const std::vector<double>* t_init = nullptr, int device = 0) {
     if (!out) return InvalidArgumentError("ResectChart: null output");
-    if (frame_offsets.empty() || pixels.size() != points.size() || frame_offsets.back() != int64_t(pixels.size()))
-      return InvalidArgumentError("ResectChart: frame_offsets must have n_frames + 1 entries and end at the number of pairs");
-    const size_t nf = frame_offsets.size() - 1, n = pixels.size();
-    if ((q_init && q_init->size() != 4 * nf) || (t_init && t_init->size() != 3 * nf))
-      return InvalidArgumentError("ResectChart: q_init / t_init must hold 4 / 3 doubles per frame");
-    std::vector<double> px(2 * n), pt(3 * n);
-    for (size_t i = 0; i < n; ++i) {
-      px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y();
-      pt[3 * i] = points[i][0]; pt[3 * i + 1] = points[i][1]; pt[3 * i + 2] = points[i][2];
-    }
+    std::vector<double> px, pt;
+    if (Status st = detail::PackChartBatch("ResectChart", frame_offsets, pixels, points, q_init, t_init, 0, 0, &px, &pt); !st.ok()) return st;
+    const size_t nf = frame_offsets.size() - 1;
     ChartResection r;
     r.q.assign(4 * nf, 0.0); r.t.assign(3 * nf, 0.0); r.rms.assign(nf, 0.0); r.n_used.assign(nf, 0); r.iterations.assign(nf, 0);
     r.status.assign(nf, 0);
@@ -956,17 +968,10 @@ class CameraModel {
                                    const std::vector<uint8_t>& free_mask = {}, const std::vector<double>* q_init = nullptr,
                                    const std::vector<double>* t_init = nullptr, int device = 0) {
     if (!out) return InvalidArgumentError("CalibrateFromChart: null output");
-    if (frame_offsets.empty() || pixels.size() != points.size() || frame_offsets.back() != int64_t(pixels.size()))
-      return InvalidArgumentError("CalibrateFromChart: frame_offsets must have n_frames + 1 entries and end at the number of pairs");
-    const size_t nf = frame_offsets.size() - 1, n = pixels.size(), K = size_t(intrinsics_init.size());
-    if ((q_init && q_init->size() != 4 * nf) || (t_init && t_init->size() != 3 * nf))
-      return InvalidArgumentError("CalibrateFromChart: q_init / t_init must hold 4 / 3 doubles per frame");
-    if (!free_mask.empty() && free_mask.size() != K) return InvalidArgumentError("CalibrateFromChart: free_mask must have one entry per intrinsic");
-    std::vector<double> px(2 * n), pt(3 * n);
-    for (size_t i = 0; i < n; ++i) {
-      px[2 * i] = pixels[i].x(); px[2 * i + 1] = pixels[i].y();
-      pt[3 * i] = points[i][0]; pt[3 * i + 1] = points[i][1]; pt[3 * i + 2] = points[i][2];
-    }
+    const size_t nf = frame_offsets.size() - 1, K = size_t(intrinsics_init.size());
+    std::vector<double> px, pt;
+    if (Status st = detail::PackChartBatch("CalibrateFromChart", frame_offsets, pixels, points, q_init, t_init, free_mask.size(), K, &px, &pt); !st.ok())
+      return st;
     ChartCalibration r;
     r.intrinsics = intrinsics_init;
     r.q.assign(4 * nf, 0.0); r.t.assign(3 * nf, 0.0); r.rms.assign(nf, 0.0); r.n_used.assign(nf, 0); r.status.assign(nf, 0);

@@ -276,7 +276,8 @@ int32_t calico_get_residuals(calico_problem* p, int32_t sensor_id, double* out,
  * sample at mid-segment). kInvalidArgument for unsorted stamps, stamps outside the valid
  * knots or bad sizes; kUnimplemented when the band does not fit the on-chip solve (n_ctrl (order + 6) 8 bytes > 156 KiB:
  * more than 1664 control points at order 6, 1426 at order 8; ctrl_out is then left untouched) or n exceeds INT32_MAX.
- * Needs no problem handle. */
+ * Needs no problem handle: owns its device memory, the argument rules are checked before the device is touched, message in
+ * calico_last_error(NULL). */
 int32_t calico_fit_spline(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
                           int64_t n, const double* stamps, const double* data6, double* ctrl_out);
 

@@ -80,7 +80,7 @@ def test_entry_points_are_declared_listed_and_exported(api):
     assert callable(_capi.camera_resect) and callable(_capi.resection_options)
     assert "debug_camera_resect_chunked" in _capi.TEST_SYMBOLS and hasattr(api.lib, "calico_debug_camera_resect_chunked")
     # no new environment switches
-    for f in ("resect_kernels.hip", "camera.cpp"):
+    for f in ("resect_kernels.hip", "chart.cpp", "arg_rules.hpp", "free_call.hpp"):
         assert "getenv" not in open(os.path.join(entry.CSRC, f)).read()
 
 
