@@ -109,6 +109,25 @@ class CalibrationSummary(C.Structure):
 CALIB_OK, CALIB_TOO_FEW_FRAMES, CALIB_NOT_CONVERGED, CALIB_DEGENERATE = 0, 1, 2, 3
 
 
+class RigOptions(C.Structure):
+    """calico_rig_options."""
+    _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("huber_scale", C.c_double), ("min_points", C.c_int32),
+                ("min_shared_frames", C.c_int32), ("reference_camera", C.c_int32)]
+
+
+class RigSummary(C.Structure):
+    """calico_rig_summary."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("rms", C.c_double), ("cameras_used", C.c_int32), ("frames_used", C.c_int32), ("views_used", C.c_int64),
+                ("pairs_used", C.c_int64), ("lambda_", C.c_double)]
+
+
+RIG_MAX_CAMERAS = 8
+RIG_OK, RIG_TOO_FEW_VIEWS, RIG_NOT_CONVERGED, RIG_DEGENERATE = 0, 1, 2, 3
+RIG_CAMERA_OK, RIG_CAMERA_REFERENCE, RIG_CAMERA_UNCONNECTED = 0, 1, 2
+RIG_FRAME_OK, RIG_FRAME_NO_VIEW, RIG_FRAME_NOT_POSITIVE_DEFINITE = 0, 1, 2
+
+
 class ImuAlignmentOptions(C.Structure):
     """calico_imu_alignment_options."""
     _fields_ = [("max_lag", C.c_double), ("lag_step", C.c_double), ("max_iterations", C.c_int32), ("step_tolerance", C.c_double),
@@ -190,6 +209,7 @@ ABI_SYMBOLS = [
     "default_resection_options", "camera_resect",
     "default_calibration_options", "camera_calibrate",
     "default_imu_alignment_options", "imu_align",
+    "default_rig_options", "rig_calibrate",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -289,6 +309,11 @@ class CApi:
                 g("default_imu_alignment_options", None, [AO])
                 g("imu_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int64, D, D, C.c_int64, D, D, D, D, D, AO,
                                            D, D, D, D, D, D, D, C.POINTER(ImuAlignmentSummary)])
+            if hasattr(self.lib, self.prefix + "rig_calibrate"):
+                I64, RGO = C.POINTER(C.c_int64), C.POINTER(RigOptions)
+                g("default_rig_options", None, [RGO])
+                g("rig_calibrate", C.c_int32, [C.c_int32, C.c_int32, I, I64, D, C.c_int64, C.c_int64, I, I64, I64, D, D, D, D, D, D, RGO,
+                                               D, D, U8, D, D, U8, D, I, U8, D, C.POINTER(RigSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -473,6 +498,70 @@ def camera_calibrate(api, model, intrinsics_init, frame_offsets, pixels, points,
                                  _dp(cov) if covariance else None, C.byref(summary)]))
     _check_free(api, st)
     return Calibration(k_out, q[:nf], t[:nf], rms[:nf], used[:nf], status[:nf], cov, summary)
+
+
+class RigCalibration:
+    """What calico_rig_calibrate returns: per camera q_rig_camera (C, 4; x, y, z, w), t_rig_camera (C, 3) and camera_status
+    (RIG_CAMERA_*); per rig frame q_frame, t_frame (T_rig_chart) and frame_status (RIG_FRAME_*); per view, in the caller's order,
+    view_rms (pixels), view_n_used and view_status (RESECT_*); cov (6 C, 6 C) or None; and the summary's fields: status (RIG_*),
+    iterations, initial_cost, final_cost, total_rms, cameras_used, frames_used, views_used, pairs_used, lambda_."""
+
+    def __init__(self, q_cam, t_cam, camera_status, q_frame, t_frame, frame_status, view_rms, view_n_used, view_status, cov, summary):
+        self.q_rig_camera, self.t_rig_camera, self.camera_status = q_cam, t_cam, camera_status
+        self.q_frame, self.t_frame, self.frame_status = q_frame, t_frame, frame_status
+        self.view_rms, self.view_n_used, self.view_status, self.cov = view_rms, view_n_used, view_status, cov
+        self.status, self.iterations = summary.status, summary.iterations
+        self.initial_cost, self.final_cost, self.total_rms = summary.initial_cost, summary.final_cost, summary.rms
+        self.cameras_used, self.frames_used, self.views_used = summary.cameras_used, summary.frames_used, summary.views_used
+        self.pairs_used, self.lambda_ = summary.pairs_used, summary.lambda_
+
+
+def rig_options(api, **kw):
+    """The library's default calico_rig_options with the given fields replaced."""
+    return _options(RigOptions, api.default_rig_options, "rig", kw)
+
+
+def rig_calibrate(api, models, intrinsics, n_frames, view_camera, view_frame, view_offsets, pixels, points, q_rig_camera_init=None,
+                  t_rig_camera_init=None, q_frame_init=None, t_frame_init=None, options=None, covariance=False, device=0):
+    """calico_rig_calibrate: the extrinsics T_rig_camera of the cameras of a rig and the pose T_rig_chart of every rig frame.
+    models: one camera model per camera; intrinsics: one array per camera. View v is camera view_camera[v] in rig frame
+    view_frame[v] and owns the pairs [view_offsets[v], view_offsets[v + 1]) of pixels (N, 2) and chart points (N, 3). The
+    starts come in pairs (q, t), the frames' only with the cameras'. options: a RigOptions (rig_options(api, ...)) or None.
+    Returns a RigCalibration."""
+    md = _i32(models).ravel()
+    nc = len(md)
+    ks = [_f64(k).ravel() for k in intrinsics]
+    if len(ks) != nc:
+        raise ValueError("one intrinsics array per camera")
+    koff = np.zeros(nc + 1, dtype=np.int64)
+    koff[1:] = np.cumsum([k.size for k in ks])
+    kk = _f64(np.concatenate(ks)) if nc else np.zeros(1)
+    vc = _i32(view_camera).ravel()
+    vf = np.ascontiguousarray(view_frame, dtype=np.int64).ravel()
+    off = np.ascontiguousarray(view_offsets, dtype=np.int64).ravel()
+    nv, nf = len(vc), int(n_frames)
+    px, pt = _f64(pixels).reshape(-1, 2), _f64(points).reshape(-1, 3)
+    if len(vf) != nv or len(off) != nv + 1 or len(px) != len(pt) or off[-1] != len(px):
+        raise ValueError("view_camera and view_frame have one entry per view, view_offsets one more, ending at the number of pairs")
+
+    def start(a, rows, cols):
+        return None if a is None else _f64(a).reshape(rows, cols)
+    qc, tc, qf, tf = start(q_rig_camera_init, nc, 4), start(t_rig_camera_init, nc, 3), start(q_frame_init, nf, 4), start(t_frame_init, nf, 3)
+    mc, mf, mv = max(nc, 1), max(nf, 1), max(nv, 1)
+    q_cam, t_cam, cam_status = np.zeros((mc, 4)), np.zeros((mc, 3)), np.zeros(mc, np.uint8)
+    q_fr, t_fr, fr_status = np.zeros((mf, 4)), np.zeros((mf, 3)), np.zeros(mf, np.uint8)
+    v_rms, v_used, v_status = np.zeros(mv), np.zeros(mv, np.int32), np.zeros(mv, np.uint8)
+    cov = np.zeros((6 * nc, 6 * nc)) if covariance else None
+    summary = RigSummary()
+    I64 = C.POINTER(C.c_int64)
+    opt = lambda a: None if a is None else _dp(a)      # noqa: E731
+    st = api.rig_calibrate(int(device), nc, _ip(md), koff.ctypes.data_as(I64), _dp(kk), nf, nv, _ip(vc), vf.ctypes.data_as(I64),
+                           off.ctypes.data_as(I64), _dp(px), _dp(pt), opt(qc), opt(tc), opt(qf), opt(tf),
+                           None if options is None else C.byref(options), _dp(q_cam), _dp(t_cam), _u8p(cam_status), _dp(q_fr), _dp(t_fr),
+                           _u8p(fr_status), _dp(v_rms), _ip(v_used), _u8p(v_status), _dp(cov) if covariance else None, C.byref(summary))
+    _check_free(api, st)
+    return RigCalibration(q_cam[:nc], t_cam[:nc], cam_status[:nc], q_fr[:nf], t_fr[:nf], fr_status[:nf], v_rms[:nv], v_used[:nv],
+                          v_status[:nv], cov, summary)
 
 
 def imu_alignment_options(api, **kw):

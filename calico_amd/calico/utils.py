@@ -215,6 +215,29 @@ def InitializeIntrinsicsAndPoses(camera, all_detections: List[Dict[int, np.ndarr
     return r["intrinsics"], R_chart_camera, t_chart_camera, np.asarray(r["frame_status"]) == 0
 
 
+def InitializeRig(cameras, rig_frames: List[Dict[int, Dict[int, np.ndarray]]], model_definition: Dict[int, np.ndarray], options=None
+                  ) -> Tuple[List[np.ndarray], List[np.ndarray], np.ndarray]:
+    """The second and every further camera of the start of Optimize: calico.CalibrateRig (on the device) estimates the extrinsics
+    of every camera but the reference camera (cameras[0] unless options says otherwise), whose frame is the rig's, jointly with
+    the pose of every rig frame, from the chart detections of all cameras at their current intrinsics. rig_frames[f] maps a
+    camera's index in `cameras` to its detections {feature id: pixel} at an instant the rig stood still relative to the chart.
+    Sets the extrinsics of the cameras that took part. Returns ([R_chart_rig per rig frame], [t_chart_rig per rig frame],
+    ok (n_frames,) bool) in the conventions of InitializePoses -- what Trajectory.FitSpline takes, now also for the frames the
+    reference camera never saw; a frame that is not ok carries the identity and must not be handed to FitSpline. options: None or
+    a dict of calico_rig_options fields. Raises RuntimeError when the estimation does not end with status OK (before anything is
+    changed)."""
+    r = _calico.CalibrateRig(list(cameras), rig_frames, model_definition, options)
+    if r["status"] != 0:
+        raise RuntimeError("Error: the rig calibration ended with status %d after %d iterations (%d cameras, %d views used)"
+                           % (r["status"], r["iterations"], r["cameras_used"], r["views_used"]))
+    R_chart_rig, t_chart_rig = [], []
+    for q, t in zip(r["q_frame"], r["t_frame"]):
+        R = _rotation_of(q)
+        R_chart_rig.append(R.T)
+        t_chart_rig.append(-R.T @ t)
+    return R_chart_rig, t_chart_rig, np.asarray(r["frame_status"]) == 0
+
+
 # where the three bias entries start in the intrinsics of the IMU models (gyroscope and accelerometer models share their layouts):
 # ScaleOnly [s]: none; ScaleAndBias [s, b 3]; VectorNav [scale 3, misalignment 6, bias 3]
 _IMU_BIAS_AT = {1: None, 2: 1, 3: 9}

@@ -1,4 +1,4 @@
-// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp), free of HIP:
+// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp), free of HIP:
 // the standard library and the C header only, so a plain host program can test them (tests/cpp/arg_rules_check.cpp). A rule
 // returns an empty string for "fine", or the message without the call's name (FreeCall, free_call.hpp, puts that in front).
 #pragma once
@@ -44,6 +44,53 @@ inline std::string chart_frames_error(int64_t n_frames, const int64_t* offsets, 
   for (int64_t f = 0; f < n_frames; ++f)
     if (offsets[f + 1] < offsets[f]) return "frame_offsets decrease at frame " + std::to_string(f);
   if (offsets[n_frames] > 0 && (!pixels || !points)) return "null pixels or points";
+  return "";
+}
+
+// ---- the rig of calico_rig_calibrate: cameras with their models and intrinsics (num_params[c]: camera_model_num_params of
+// models[c]), and what its options and starts must satisfy whatever the views are ----
+inline std::string rig_cameras_error(int n_cameras, int max_cameras, const int32_t* models, const int* num_params, const int64_t* intrinsics_offsets,
+                                     const double* intrinsics) {
+  if (n_cameras < 1 || n_cameras > max_cameras) return "n_cameras must be in [1, " + std::to_string(max_cameras) + "]";
+  if (!models || !intrinsics_offsets || !intrinsics) return "null models, intrinsics_offsets or intrinsics";
+  if (intrinsics_offsets[0] != 0) return "intrinsics_offsets must start at 0";
+  for (int c = 0; c < n_cameras; ++c) {
+    if (num_params[c] < 0) return "unknown camera model " + std::to_string(models[c]) + " of camera " + std::to_string(c);
+    if (intrinsics_offsets[c + 1] - intrinsics_offsets[c] != num_params[c])
+      return "camera " + std::to_string(c) + " of model " + std::to_string(models[c]) + " has " + std::to_string(num_params[c]) +
+             " intrinsics, its offsets give " + std::to_string(intrinsics_offsets[c + 1] - intrinsics_offsets[c]);
+  }
+  return "";
+}
+inline std::string rig_options_error(int n_cameras, int64_t n_frames, int64_t n_views, const calico_rig_options& o, const double* q_camera_init,
+                                     const double* t_camera_init, const double* q_frame_init, const double* t_frame_init) {
+  if (n_views < 0) return "n_views must be >= 0";
+  std::string error = chart_options_error(n_frames, o, q_camera_init, t_camera_init);
+  if (!error.empty()) return error;
+  if ((q_frame_init == nullptr) != (t_frame_init == nullptr)) return "q_frame_init and t_frame_init are given together or not at all";
+  if (q_frame_init && !q_camera_init) return "a start of the frames needs a start of the cameras";
+  if (o.reference_camera < 0 || o.reference_camera >= n_cameras) return "reference_camera must be in [0, n_cameras)";
+  if (o.min_shared_frames < 1) return "min_shared_frames must be >= 1";
+  return "";
+}
+// The views of a rig with n_views > 0: `order` (n_views) receives them sorted by (frame, camera).
+inline std::string rig_views_error(int n_cameras, int64_t n_frames, int64_t n_views, const int32_t* view_camera, const int64_t* view_frame,
+                                   const int64_t* view_offsets, const double* pixels, const double* points, int64_t* order) {
+  if (!view_camera || !view_frame || !view_offsets) return "null view_camera, view_frame or view_offsets";
+  if (view_offsets[0] != 0) return "view_offsets must start at 0";
+  for (int64_t v = 0; v < n_views; ++v) {
+    if (view_offsets[v + 1] < view_offsets[v]) return "view_offsets decrease at view " + std::to_string(v);
+    if (view_camera[v] < 0 || view_camera[v] >= n_cameras) return "view " + std::to_string(v) + " names camera " + std::to_string(view_camera[v]);
+    if (view_frame[v] < 0 || view_frame[v] >= n_frames) return "view " + std::to_string(v) + " names frame " + std::to_string(view_frame[v]);
+  }
+  if (view_offsets[n_views] > 0 && (!pixels || !points)) return "null pixels or points";
+  for (int64_t v = 0; v < n_views; ++v) order[v] = v;
+  std::sort(order, order + n_views, [&](int64_t x, int64_t y) {
+    return view_frame[x] != view_frame[y] ? view_frame[x] < view_frame[y] : view_camera[x] < view_camera[y];
+  });
+  for (int64_t s = 1; s < n_views; ++s)
+    if (view_frame[order[s]] == view_frame[order[s - 1]] && view_camera[order[s]] == view_camera[order[s - 1]])
+      return "camera " + std::to_string(view_camera[order[s]]) + " has two views of frame " + std::to_string(view_frame[order[s]]);
   return "";
 }
 

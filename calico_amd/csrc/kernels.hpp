@@ -229,6 +229,64 @@ hipError_t launch_calib_decide(const CalibArgs& a, hipStream_t s);              
 hipError_t launch_calib_eliminate(const CalibArgs& a, bool final, hipStream_t s);    // per frame: Cholesky, Y, B^T Y (final: undamped, outputs)
 hipError_t launch_calib_reduce(const CalibArgs& a, bool final, hipStream_t s);       // fixed-order sum over the frames, the K x K solve, dk
 
+// ---- rig calibration (rig_kernels.hip): the extrinsics of C <= 8 cameras and the pose T_rig_chart of every rig frame ----------
+// An arrowhead system again: 6 x 6 frame blocks, bordered by the M x M block of the extrinsics (M = 6 C). A view is one camera's
+// pairs in one rig frame; the views are sorted by (frame, camera) -- frame_views (n_frames + 1) cuts them into frames -- and so
+// are their pairs. The control word of the device's LM loop, as CalibControl:
+constexpr int kRigMaxCameras = 8;                        // CALICO_RIG_MAX_CAMERAS (rig.cpp asserts it)
+constexpr int kRigMaxDim = 6 * kRigMaxCameras;
+constexpr int kRigN = 13;                                // columns of a view's rows: [J_frame 6 | J_extrinsics 6 | e]
+struct RigControl {
+  int done;                     // != 0: every later launch returns at once
+  int status;                   // CALICO_RIG_*
+  int cur;                      // the slot (extrinsics, frame poses, Gram matrices, validity bit) of the current point
+  int first;                    // the start has not been evaluated yet
+  int redo;                     // the reduced system was not positive definite: eliminate and reduce again at the larger lambda
+  int iterations;
+  int frames_used;
+  int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
+  long long views_used, pairs_used;
+  double lambda, step_x;        // step_x: the size of the extrinsics' step the candidate was made with
+  double initial_cost, final_cost, rms;
+  double cam[2][kRigMaxCameras][8];      // T_rig_camera of the two slots: [0, 4) q, [4, 7) t
+  double dx[kRigMaxDim];
+};
+// Per frame, kRigFrameDoubles doubles: two slots of 8 ([0, 4) q, [4, 7) t of T_rig_chart), [16] the pose step's size, and from
+// [24] Y = A^-1 [B g], column j (the M columns of the extrinsics, then g) at 24 + 6 j; a camera without a view in the frame
+// has zero columns. Per view, kRigViewDoubles: two slots of 4 (Sum rho, Sum |e|^2, valid pairs, the cost's rounding scale),
+// [8] Sum rho over the pairs valid at both points, [9] pairs lost.
+constexpr int kRigStep = 16, kRigY = 24, kRigFrameDoubles = kRigY + 6 * (kRigMaxDim + 1) + 2;
+constexpr int kRigViewDoubles = 16, kRigCommon = 8, kRigLost = 9;
+constexpr int kRigShare = kRigMaxDim * kRigMaxDim + 2 * kRigMaxDim + 8;      // doubles per frame of `share`: M M + 2 M + 5 are used
+struct RigArgs {
+  RigControl* ctrl;
+  int n_cameras;
+  unsigned held_bits;                                     // bit c: camera c is held (the reference, an unconnected camera)
+  int intr_at[kRigMaxCameras];                            // where camera c's intrinsics start in `intrinsics`
+  const double* intrinsics;
+  int64_t n_frames, n_views;
+  const int* view_camera; const int64_t* view_frame;      // n_views
+  const int64_t* view_offsets;                            // n_views + 1: the view's pairs
+  const int64_t* frame_views;                             // n_frames + 1: the frame's views, in camera order
+  const double* pixels; const double* points;
+  uint8_t* flags;                                         // N pairs: valid at slot 0 / 1 (pose_bit)
+  const uint8_t* view_active;                             // n_views: usable, of a connected camera
+  const uint8_t* view_writer;                             // n_views: the frame's first active view writes the frame's candidate pose
+  uint8_t* frame_active;                                  // n_frames: the frame takes part
+  uint8_t* frame_status;                                  // n_frames: CALICO_RIG_FRAME_*
+  double* frames;                                         // n_frames x kRigFrameDoubles
+  double* views;                                          // n_views x kRigViewDoubles
+  double* gram;                                           // n_views x 2 x 13 x 13: [J_f J_x e]^T W [J_f J_x e] at the two slots
+  double* share;                                          // n_frames x kRigShare: the frame's entries of the reduced system
+  int max_iterations; double step_tolerance; double huber_scale;
+  double* q_frame_out; double* t_frame_out; double* view_rms_out; int* view_n_used_out; double* cov_out /* M x M */;
+};
+// list: the views (indices) of cameras of `model`, in order
+hipError_t launch_rig_evaluate(int model, const RigArgs& a, const int* list, int n_list, hipStream_t s);
+hipError_t launch_rig_decide(const RigArgs& a, hipStream_t s);                     // accept / reject, the next lambda, termination
+hipError_t launch_rig_eliminate(const RigArgs& a, bool final, hipStream_t s);      // per frame: Cholesky, Y, its share (final: undamped, outputs)
+hipError_t launch_rig_reduce(const RigArgs& a, bool final, hipStream_t s);         // fixed-order sum over the frames, the M x M solve, the step
+
 // ---- camera-IMU alignment (align_kernels.hip): rotation, gyroscope bias, latency, gravity from a fitted trajectory ------------
 // The control word of the whole call: every kernel reads it, the single-workgroup kernels write it. The stages follow one
 // another on the stream without the host reading anything back; a stage that ends the call sets `done`.

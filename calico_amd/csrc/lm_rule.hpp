@@ -1,5 +1,5 @@
 // lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip,
-// calib_kernels.hip, align_kernels.hip): accept or reject a candidate, the next damping, and whether the loop has converged.
+// calib_kernels.hip, align_kernels.hip, rig_kernels.hip): accept or reject a candidate, the next damping, and whether the loop has converged.
 // What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
 // a damped system is not positive definite. Host and device code (the host sets the control word's first damping).
 #pragma once
@@ -24,6 +24,28 @@ DEV LmVerdict lm_rule(bool kept, double candidate, double current, double noise,
   v.converged = small && kept && lambda <= kLmLambda0;
   v.lambda = v.accept ? fmax(lambda * 0.1, kLmLambdaMin) : v.converged ? lambda : fmin(lambda * 10.0, kLmLambdaMax);
   return v;
+}
+
+// One decision of a loop whose control word lives in device memory and whose candidate is judged for all blocks at once (the
+// arrowhead estimators; rig_kernels.hip calls it): the first evaluation only installs the start -- a start that is not kept, or
+// that has no valid observation, ends the loop --, every later one asks lm_rule, and the iteration cap ends the loop at the
+// point kept. The status codes stay with the caller: it maps `outcome`.
+enum LmOutcome { kLmRunning = 0, kLmConverged = 1, kLmBadStart = 2, kLmOutOfIterations = 3 };
+struct LmLoopStep { bool accept; int outcome; double lambda; int iterations; };
+DEV LmLoopStep lm_loop_decision(bool first, bool kept, bool any_valid, double candidate, double current, double noise, bool small, double lambda,
+                                int iterations, int max_iterations) {
+  LmLoopStep s;
+  s.accept = first; s.outcome = kLmRunning; s.lambda = lambda; s.iterations = iterations;
+  if (first) {
+    if (!kept || !any_valid) s.outcome = kLmBadStart;
+  } else {
+    const LmVerdict v = lm_rule(kept, candidate, current, noise, small, lambda);
+    s.accept = v.accept; s.lambda = v.lambda;
+    if (v.converged) s.outcome = kLmConverged;
+  }
+  if (s.outcome == kLmRunning && iterations >= max_iterations) s.outcome = kLmOutOfIterations;
+  if (s.outcome == kLmRunning) ++s.iterations;
+  return s;
 }
 
 }  // namespace cal

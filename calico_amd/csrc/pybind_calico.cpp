@@ -199,6 +199,62 @@ py::dict calibration_dict(const CameraModel::ChartCalibration& r, bool covarianc
   return out;
 }
 
+// ---- rig calibration (calico_rig_calibrate): what the two bindings share ----
+// options: None or a dict of calico_rig_options fields
+calico_rig_options rig_options(const py::object& options) {
+  calico_rig_options o;
+  calico_default_rig_options(&o);
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+      else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+      else if (name == "huber_scale") o.huber_scale = py::cast<double>(kv.second);
+      else if (name == "min_points") o.min_points = py::cast<int>(kv.second);
+      else if (name == "min_shared_frames") o.min_shared_frames = py::cast<int>(kv.second);
+      else if (name == "reference_camera") o.reference_camera = py::cast<int>(kv.second);
+      else throw py::type_error("no rig option '" + name + "'");
+    }
+  }
+  return o;
+}
+template <class T> py::array_t<T> rows_of(const std::vector<T>& v, py::ssize_t rows, py::ssize_t cols) {
+  py::array_t<T> a = cols == 1 ? py::array_t<T>(rows) : py::array_t<T>({rows, cols});
+  std::copy(v.begin(), v.end(), a.mutable_data());
+  return a;
+}
+// a dict of arrays, one row per camera, per rig frame and per view, and the summary's fields
+py::dict rig_dict(const RigCalibration& r, bool covariance) {
+  const py::ssize_t nc = py::ssize_t(r.NumCameras()), nf = py::ssize_t(r.NumFrames()), nv = py::ssize_t(r.NumViews());
+  py::dict out;
+  out["q_rig_camera"] = rows_of(r.q_rig_camera, nc, 4); out["t_rig_camera"] = rows_of(r.t_rig_camera, nc, 3);
+  out["camera_status"] = rows_of(r.camera_status, nc, 1);
+  out["q_frame"] = rows_of(r.q_frame, nf, 4); out["t_frame"] = rows_of(r.t_frame, nf, 3); out["frame_status"] = rows_of(r.frame_status, nf, 1);
+  out["view_rms"] = rows_of(r.view_rms, nv, 1); out["view_n_used"] = rows_of(r.view_n_used, nv, 1); out["view_status"] = rows_of(r.view_status, nv, 1);
+  out["status"] = r.summary.status; out["iterations"] = r.summary.iterations; out["initial_cost"] = r.summary.initial_cost;
+  out["final_cost"] = r.summary.final_cost; out["total_rms"] = r.summary.rms; out["cameras_used"] = r.summary.cameras_used;
+  out["frames_used"] = r.summary.frames_used; out["views_used"] = r.summary.views_used; out["pairs_used"] = r.summary.pairs_used;
+  out["lambda"] = r.summary.lambda;
+  if (covariance) out["cov"] = rows_of(r.cov, 6 * nc, 6 * nc);
+  return out;
+}
+std::vector<Vector3d> to_points(const py::object& points) {
+  const VectorXd flat = to_vector(points);
+  if (flat.size() % 3 != 0) throw py::type_error("expected an (n, 3) array of chart points");
+  std::vector<Vector3d> pts(flat.size() / 3);
+  for (size_t i = 0; i < pts.size(); ++i) pts[i] = Vector3d(flat[3 * i], flat[3 * i + 1], flat[3 * i + 2]);
+  return pts;
+}
+std::map<int, Vector3d> to_model_definition(const py::dict& model_definition) {
+  std::map<int, Vector3d> model;
+  for (auto kv : model_definition) {
+    auto arr = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(kv.second);
+    if (!arr || (arr.size() != 2 && arr.size() != 3)) throw py::type_error("a chart point is (x, y) or (x, y, z)");
+    model[py::cast<int>(kv.first)] = Vector3d(arr.data()[0], arr.data()[1], arr.size() == 3 ? arr.data()[2] : 0.0);
+  }
+  return model;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_calico, m) {
@@ -319,7 +375,32 @@ PYBIND11_MODULE(_calico, m) {
                   },
                   py::arg("model"), py::arg("intrinsics_init"), py::arg("frame_offsets"), py::arg("pixels"), py::arg("points"),
                   py::arg("options") = py::none(), py::arg("covariance") = false, py::arg("free_mask") = py::none(),
-                  py::arg("q_init") = py::none(), py::arg("t_init") = py::none(), py::arg("device") = 0);
+                  py::arg("q_init") = py::none(), py::arg("t_init") = py::none(), py::arg("device") = 0)
+      // models and intrinsics: one entry per camera; view v is camera view_camera[v] in rig frame view_frame[v] with the pairs
+      // [view_offsets[v], view_offsets[v + 1]) of pixels (N, 2) and points (N, 3); the starts: None or (C, 4) / (C, 3) and
+      // (n_frames, 4) / (n_frames, 3); options: None or a dict of calico_rig_options fields
+      .def_static("CalibrateRigFromChart",
+                  [](const std::vector<CameraIntrinsicsModel>& models, const std::vector<py::object>& intrinsics, int64_t n_frames,
+                     const std::vector<int32_t>& view_camera, const std::vector<int64_t>& view_frame, const std::vector<int64_t>& view_offsets,
+                     const py::object& pixels, const py::object& points, const py::object& options, bool covariance,
+                     const py::object& q_rig_camera_init, const py::object& t_rig_camera_init, const py::object& q_frame_init,
+                     const py::object& t_frame_init, int device) {
+                    std::vector<VectorXd> ks;
+                    for (const py::object& k : intrinsics) ks.push_back(to_vector(k));
+                    const calico_rig_options o = rig_options(options);
+                    std::vector<double> qc, tc, qf, tf;
+                    const bool hqc = to_rows(q_rig_camera_init, &qc), htc = to_rows(t_rig_camera_init, &tc);
+                    const bool hqf = to_rows(q_frame_init, &qf), htf = to_rows(t_frame_init, &tf);
+                    RigCalibration r;
+                    raise_if_error(CameraModel::CalibrateRigFromChart(models, ks, n_frames, view_camera, view_frame, view_offsets, to_pixels(pixels),
+                                                                      to_points(points), &o, &r, covariance, hqc ? &qc : nullptr, htc ? &tc : nullptr,
+                                                                      hqf ? &qf : nullptr, htf ? &tf : nullptr, device));
+                    return rig_dict(r, covariance);
+                  },
+                  py::arg("models"), py::arg("intrinsics"), py::arg("n_frames"), py::arg("view_camera"), py::arg("view_frame"),
+                  py::arg("view_offsets"), py::arg("pixels"), py::arg("points"), py::arg("options") = py::none(), py::arg("covariance") = false,
+                  py::arg("q_rig_camera_init") = py::none(), py::arg("t_rig_camera_init") = py::none(), py::arg("q_frame_init") = py::none(),
+                  py::arg("t_frame_init") = py::none(), py::arg("device") = 0);
   py::enum_<ProjectionFrame>(m, "ProjectionFrame")
       .value("kCamera", ProjectionFrame::kCamera)
       .value("kRig", ProjectionFrame::kRig);
@@ -562,6 +643,23 @@ PYBIND11_MODULE(_calico, m) {
       .def_readwrite("initial_trust_region_radius", &SolverOptions::initial_trust_region_radius)
       .def_readwrite("max_trust_region_radius", &SolverOptions::max_trust_region_radius);
   m.def("DefaultSolverOptions", &DefaultSolverOptions);
+
+  // Rig calibration (calico_rig_calibrate): rig_frames[f] maps a camera's index in `cameras` to its detections {feature id:
+  // pixel} in rig frame f; options: None or a dict of calico_rig_options fields. Sets the extrinsics of the cameras whose
+  // status is OK when the estimation ends with status OK. Returns CalibrateRigFromChart's dict.
+  m.def(
+      "CalibrateRig",
+      [](const std::vector<std::shared_ptr<Camera>>& cameras, const std::vector<std::map<int, std::map<int, Vector2d>>>& rig_frames,
+         const py::dict& model_definition, const py::object& options, bool covariance, int device) {
+        std::vector<Camera*> cams;
+        for (const auto& c : cameras) cams.push_back(c.get());
+        const calico_rig_options o = rig_options(options);
+        RigCalibration r;
+        raise_if_error(CalibrateRig(cams, rig_frames, to_model_definition(model_definition), &o, &r, covariance, device).status());
+        return rig_dict(r, covariance);
+      },
+      py::arg("cameras"), py::arg("rig_frames"), py::arg("model_definition"), py::arg("options") = py::none(), py::arg("covariance") = false,
+      py::arg("device") = 0);
 
   // the observability report: spectrum, directions and where they live, as numpy arrays / lists of (name, part, share)
   py::class_<Observability>(m, "Observability")

@@ -882,6 +882,33 @@ inline Status PackChartBatch(const std::string& what, const std::vector<int64_t>
 }
 }  // namespace detail
 
+/// What CalibrateRigFromChart and CalibrateRig leave (calico_rig_calibrate): per camera T_rig_camera as q (x, y, z, w) and t with
+/// its status (CALICO_RIG_CAMERA_*), per rig frame T_rig_chart with its status (CALICO_RIG_FRAME_*), per view -- in the order
+/// the views were given -- the RMS pixel residual, the pairs used and the status (CALICO_RESECT_*), on request the 6 C x 6 C
+/// covariance of the extrinsics, and the summary (status: CALICO_RIG_*).
+struct RigCalibration {
+  std::vector<double> q_rig_camera, t_rig_camera;      // 4 and 3 doubles per camera
+  std::vector<uint8_t> camera_status;
+  std::vector<double> q_frame, t_frame;                // 4 and 3 doubles per rig frame
+  std::vector<uint8_t> frame_status;
+  std::vector<double> view_rms, cov;
+  std::vector<int32_t> view_n_used;
+  std::vector<uint8_t> view_status;
+  calico_rig_summary summary{};
+  size_t NumCameras() const { return camera_status.size(); }
+  size_t NumFrames() const { return frame_status.size(); }
+  size_t NumViews() const { return view_status.size(); }
+  bool Ok() const { return summary.status == CALICO_RIG_OK; }
+  Pose3d CameraPose(size_t c) const {
+    return Pose3d(Quaterniond(q_rig_camera[4 * c + 3], q_rig_camera[4 * c], q_rig_camera[4 * c + 1], q_rig_camera[4 * c + 2]),
+                  Vector3d(t_rig_camera[3 * c], t_rig_camera[3 * c + 1], t_rig_camera[3 * c + 2]));
+  }
+  Pose3d FramePose(size_t f) const {
+    return Pose3d(Quaterniond(q_frame[4 * f + 3], q_frame[4 * f], q_frame[4 * f + 1], q_frame[4 * f + 2]),
+                  Vector3d(t_frame[3 * f], t_frame[3 * f + 1], t_frame[3 * f + 2]));
+  }
+};
+
 /// sensors::CameraModel (camera_models.h): the inverse model, on the device (calico_camera_unproject). The result is the
 /// UNIT-NORM point that projects to the pixel under the library's projection -- the usual bearing for every model but
 /// ExtendedUnified, whose projection is not scale invariant (include/calico_hip.h). A model is named by its enum value:
@@ -981,6 +1008,56 @@ class CameraModel {
                                            int64_t(nf), frame_offsets.data(), px.data(), pt.data(), q_init ? q_init->data() : nullptr,
                                            t_init ? t_init->data() : nullptr, options, r.intrinsics.data(), r.q.data(), r.t.data(),
                                            r.rms.data(), r.n_used.data(), r.status.data(), covariance ? r.cov.data() : nullptr, &r.summary);
+    if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+    *out = std::move(r);
+    return OkStatus();
+  }
+
+  /// Rig calibration over arrays, on the device (calico_rig_calibrate): the extrinsics T_rig_camera of cameras of the given
+  /// models and intrinsics and the pose T_rig_chart of each of n_frames rig frames. View v is camera view_camera[v] in rig frame
+  /// view_frame[v] and owns the pairs [view_offsets[v], view_offsets[v + 1]) of pixels and chart points. The starts (4 and 3
+  /// doubles per camera / per frame) come in pairs, the frames' only with the cameras'; none: every view is resected and the
+  /// cameras are chained through the frames they share. options == nullptr: the library's defaults.
+  static Status CalibrateRigFromChart(const std::vector<CameraIntrinsicsModel>& models, const std::vector<VectorXd>& intrinsics, int64_t n_frames,
+                                      const std::vector<int32_t>& view_camera, const std::vector<int64_t>& view_frame,
+                                      const std::vector<int64_t>& view_offsets, const std::vector<Vector2d>& pixels,
+                                      const std::vector<Vector3d>& points, const calico_rig_options* options, RigCalibration* out,
+                                      bool covariance = false, const std::vector<double>* q_rig_camera_init = nullptr,
+                                      const std::vector<double>* t_rig_camera_init = nullptr, const std::vector<double>* q_frame_init = nullptr,
+                                      const std::vector<double>* t_frame_init = nullptr, int device = 0) {
+    const std::string what = "CalibrateRigFromChart";
+    if (!out) return InvalidArgumentError(what + ": null output");
+    const size_t nc = models.size(), nv = view_camera.size(), nf = size_t(std::max<int64_t>(n_frames, 0));
+    if (intrinsics.size() != nc) return InvalidArgumentError(what + ": one intrinsics vector per camera");
+    if (view_frame.size() != nv || view_offsets.size() != nv + 1)
+      return InvalidArgumentError(what + ": view_camera and view_frame have one entry per view, view_offsets one more");
+    if ((q_rig_camera_init && q_rig_camera_init->size() != 4 * nc) || (t_rig_camera_init && t_rig_camera_init->size() != 3 * nc))
+      return InvalidArgumentError(what + ": q_rig_camera_init / t_rig_camera_init must hold 4 / 3 doubles per camera");
+    // (the views' offsets as frame offsets: the same rule, that they end at the number of pairs)
+    std::vector<double> px, pt;
+    if (Status st = detail::PackChartBatch(what, view_offsets, pixels, points, nullptr, nullptr, 0, 0, &px, &pt); !st.ok()) return st;
+    if ((q_frame_init && q_frame_init->size() != 4 * nf) || (t_frame_init && t_frame_init->size() != 3 * nf))
+      return InvalidArgumentError(what + ": q_frame_init / t_frame_init must hold 4 / 3 doubles per frame");
+    std::vector<int32_t> md(nc);
+    std::vector<int64_t> koff(nc + 1, 0);
+    std::vector<double> k;
+    for (size_t c = 0; c < nc; ++c) {
+      md[c] = int32_t(models[c]);
+      k.insert(k.end(), intrinsics[c].begin(), intrinsics[c].end());
+      koff[c + 1] = int64_t(k.size());
+    }
+    RigCalibration r;
+    r.q_rig_camera.assign(4 * nc, 0.0); r.t_rig_camera.assign(3 * nc, 0.0); r.camera_status.assign(nc, 0);
+    r.q_frame.assign(4 * nf, 0.0); r.t_frame.assign(3 * nf, 0.0); r.frame_status.assign(nf, 0);
+    r.view_rms.assign(nv, 0.0); r.view_n_used.assign(nv, 0); r.view_status.assign(nv, 0);
+    if (covariance) r.cov.assign(36 * nc * nc, 0.0);
+    const auto ptr = [](const std::vector<double>* v) { return v ? v->data() : nullptr; };
+    const int st = calico_rig_calibrate(device, int32_t(nc), md.data(), koff.data(), k.data(), n_frames, int64_t(nv), view_camera.data(),
+                                        view_frame.data(), view_offsets.data(), px.data(), pt.data(), ptr(q_rig_camera_init),
+                                        ptr(t_rig_camera_init), ptr(q_frame_init), ptr(t_frame_init), options, r.q_rig_camera.data(),
+                                        r.t_rig_camera.data(), r.camera_status.data(), r.q_frame.data(), r.t_frame.data(),
+                                        r.frame_status.data(), r.view_rms.data(), r.view_n_used.data(), r.view_status.data(),
+                                        covariance ? r.cov.data() : nullptr, &r.summary);
     if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
     *out = std::move(r);
     return OkStatus();
@@ -1302,6 +1379,56 @@ class Accelerometer : public ImuSensor<CALICO_SENSOR_ACCELEROMETER> {
 };
 
 }  // namespace sensors
+
+using RigCalibration = sensors::RigCalibration;
+
+/// Rig calibration from chart detections (sensors::CameraModel::CalibrateRigFromChart with the cameras' models and current
+/// intrinsics, no start given): rig_frames[f] maps a camera's index in `cameras` to its detections in rig frame f (feature id ->
+/// pixel), model_definition a feature id to its chart point; the views are taken frame by frame in ascending camera index, a
+/// view's pairs in ascending id. The rig's frame is that of the reference camera (options->reference_camera, 0 by default). The
+/// extrinsics of every camera whose status is CALICO_RIG_CAMERA_OK are set (SetExtrinsics), and only when the estimation ended
+/// with CALICO_RIG_OK; `out` (may be null) holds everything the call left either way. Returns T_rig_chart per rig frame (the
+/// identity for a frame whose status is not CALICO_RIG_FRAME_OK).
+inline StatusOr<std::vector<Pose3d>> CalibrateRig(const std::vector<sensors::Camera*>& cameras,
+                                                  const std::vector<std::map<int, std::map<int, Vector2d>>>& rig_frames,
+                                                  const std::map<int, Vector3d>& model_definition, const calico_rig_options* options = nullptr,
+                                                  RigCalibration* out = nullptr, bool covariance = false, int device = 0) {
+  std::vector<sensors::CameraIntrinsicsModel> models;
+  std::vector<VectorXd> intrinsics;
+  for (const sensors::Camera* camera : cameras) {
+    if (!camera) return InvalidArgumentError("CalibrateRig: null camera");
+    if (camera->GetModel() == sensors::CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
+    models.push_back(camera->GetModel());
+    intrinsics.push_back(camera->GetIntrinsics());
+  }
+  std::vector<int32_t> view_camera;
+  std::vector<int64_t> view_frame, view_offsets(1, 0);
+  std::vector<Vector2d> pixels;
+  std::vector<Vector3d> points;
+  for (size_t f = 0; f < rig_frames.size(); ++f)
+    for (const auto& [camera, detections] : rig_frames[f]) {
+      if (camera < 0 || size_t(camera) >= cameras.size())
+        return InvalidArgumentError("CalibrateRig: rig frame " + std::to_string(f) + " names camera " + std::to_string(camera));
+      for (const auto& kv : detections) {
+        const auto it = model_definition.find(kv.first);
+        if (it == model_definition.end()) return InvalidArgumentError("CalibrateRig: feature " + std::to_string(kv.first) + " is not in the model definition");
+        pixels.push_back(kv.second);
+        points.push_back(it->second);
+      }
+      view_camera.push_back(camera); view_frame.push_back(int64_t(f)); view_offsets.push_back(int64_t(pixels.size()));
+    }
+  RigCalibration r;
+  if (Status st = sensors::CameraModel::CalibrateRigFromChart(models, intrinsics, int64_t(rig_frames.size()), view_camera, view_frame, view_offsets,
+                                                              pixels, points, options, &r, covariance, nullptr, nullptr, nullptr, nullptr, device);
+      !st.ok()) return st;
+  if (r.Ok())
+    for (size_t c = 0; c < cameras.size(); ++c)
+      if (r.camera_status[c] == CALICO_RIG_CAMERA_OK) cameras[c]->SetExtrinsics(r.CameraPose(c));
+  std::vector<Pose3d> T_rig_chart(r.NumFrames());
+  for (size_t f = 0; f < r.NumFrames(); ++f) T_rig_chart[f] = r.FramePose(f);
+  if (out) *out = std::move(r);
+  return T_rig_chart;
+}
 
 inline StatusOr<Trajectory::ImuAlignment> Trajectory::AlignImu(const sensors::Gyroscope& gyroscope, const sensors::Accelerometer* accelerometer,
                                                                const calico_imu_alignment_options* options, bool covariance, bool curve,

@@ -137,7 +137,7 @@ int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
  * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
- * calico_camera_calibrate, calico_imu_align); like a handle's message it
+ * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -675,6 +675,104 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* int
                                 const calico_calibration_options* o /* NULL = defaults */, double* intrinsics_out, double* q_out,
                                 double* t_out, double* rms_out, int32_t* n_used_out, uint8_t* status_out,
                                 double* intrinsics_cov_out /* K x K, may be NULL */, calico_calibration_summary* summary);
+
+/* ---- rig calibration: camera-to-camera extrinsics and the pose of every rig frame from shared chart views ---- */
+/* The second and every further camera of a rig: from the chart detections of n_cameras <= CALICO_RIG_MAX_CAMERAS cameras at
+ * KNOWN intrinsics (each camera its own model: models[c], intrinsics[intrinsics_offsets[c] .. intrinsics_offsets[c + 1])), grouped
+ * into rig frames -- instants at which the rig stood still relative to the chart --, the extrinsics T_rig_camera_c of every
+ * camera but the reference camera and the pose T_rig_chart_f of every rig frame that minimise
+ *   Sum_views rho(|pixel - project(k_c, R_c^T (R_f p_chart + t_f - t_c))|^2)
+ * in pixels, on the device: a minimum of calico_solve's own camera term restricted to a static chart. T_rig_camera is the
+ * library's extrinsics convention, p_rig = R_c p_camera + t_c. Quaternions are x, y, z, w; outputs are unit with w >= 0.
+ *   views  a view is the ragged set of (pixel, chart point) pairs of one camera in one rig frame: view v of camera
+ *          view_camera[v] in frame view_frame[v] owns the pairs [view_offsets[v], view_offsets[v + 1]) of pixels (N x 2) and
+ *          points (N x 3, chart frame). Views may come in any order; a (camera, frame) pair may appear at most once. Every sum
+ *          the call forms is ordered by (frame, then camera): the result is bit-identical under any permutation of the views,
+ *          and repeated calls are bit-identical.
+ *   gauge  the reference camera (options: reference_camera) is held at its start, bit for bit -- the identity when no start
+ *          is given --; its status is CALICO_RIG_CAMERA_REFERENCE.
+ *   start  (q_rig_camera_init == NULL) every view is resected (calico_camera_resect's kernel at its camera's model and
+ *          intrinsics, the same huber_scale and min_points, its defaults otherwise); a view that is not CALICO_RESECT_OK is left
+ *          out and keeps that status. Two cameras are connected when at least min_shared_frames frames hold an OK view of both;
+ *          a breadth-first tree from the reference camera visits neighbours in index order; each tree edge gives
+ *          T_a_b = T_a_chart,f T_b_chart,f^-1 per shared frame, whose rotations are averaged by the chordal mean (the dominant
+ *          eigenvector of Sum q q^T after sign alignment, in frame order) and whose translations by the mean. A camera the
+ *          tree does not reach is CALICO_RIG_CAMERA_UNCONNECTED: its views are left out, its output is its start or the
+ *          identity. A frame starts at T_rig_camera_c T_camera_c_chart,f of its usable view of lowest camera index; a frame
+ *          without a usable view is CALICO_RIG_FRAME_NO_VIEW. No camera other than the reference connected:
+ *          CALICO_RIG_TOO_FEW_VIEWS, the outputs are the starts. The tree and the averages run on the host, the resections
+ *          and everything after them on the device. With q_rig_camera_init / t_rig_camera_init (n_cameras x 4 / x 3, normalised
+ *          here) the cameras start there; the same connection rule decides which cameras take part. With q_frame_init /
+ *          t_frame_init (n_frames x 4 / x 3; only together with the camera start) nothing is resected: a view with at least
+ *          min_points pairs is usable, the others are CALICO_RESECT_TOO_FEW_POINTS.
+ *   refine Levenberg-Marquardt on the arrowhead system (6 x 6 frame blocks, one 6 x 6 coupling per view, the 6 C x 6 C block of
+ *          the extrinsics) with R_f <- exp([d]x) R_f, t_f <- t_f + dt for a frame and R_c <- exp([d]x) R_c, t_c <- t_c + dt for
+ *          a camera; rho = identity or Huber (huber_scale in pixels, weights rho', no second-order term); Marquardt damping
+ *          lambda diag on the frame blocks and on the extrinsics block, lambda from 1e-4 within [1e-12, 1e12]; the decision is
+ *          one for all frames and cameras; a candidate at which the model rejects a pair that is valid at the current point is
+ *          rejected, one whose cost is within the cost's own rounding error of the current one is accepted. Step size
+ *          s = max(|d_rot|_inf, |dt|_inf / max(1, |t|_2)) over frames and cameras. Stops after a step with s < step_tolerance
+ *          taken at lambda <= 1e-4 (CALICO_RIG_OK), after max_iterations steps (CALICO_RIG_NOT_CONVERGED: the last accepted
+ *          point), and when the reduced system is not positive definite at the largest damping or the result is not finite
+ *          (CALICO_RIG_DEGENERATE: the outputs are the starts). A frame whose damped 6 x 6 block is not positive definite drops
+ *          out for good, with its views (CALICO_RIG_FRAME_NOT_POSITIVE_DEFINITE).
+ * Outputs: q_rig_camera_out / t_rig_camera_out (n_cameras x 4 / x 3) and camera_status_out (CALICO_RIG_CAMERA_*); q_frame_out /
+ * t_frame_out (n_frames x 4 / x 3: T_rig_chart; the identity for a frame that took no part) and frame_status_out
+ * (CALICO_RIG_FRAME_*); per view, in the caller's order, view_rms_out (pixels, no loss), view_n_used_out and view_status_out
+ * (CALICO_RESECT_*; a view that took no part has rms = 0 and n_used = 0). extrinsics_cov_out (6 C x 6 C, may be NULL) is the
+ * undamped inverse reduced system (C - Sum_f B_f^T A_f^-1 B_f)^-1 at the result, in camera order, 6 entries [d_rot, dt] per
+ * camera, zero rows and columns for the reference and unconnected cameras, in pixel^2 units (no variance factor, as every
+ * covariance here).
+ * The call returns CALICO_OK whenever `summary` is meaningful; how the estimation ended is summary->status. Needs no problem
+ * handle: owns its device memory, message in calico_last_error(NULL). CALICO_INVALID_ARGUMENT, before the device is touched:
+ * n_cameras outside [1, 8], an unknown model, intrinsics offsets that do not match the models' counts, negative counts, a view's
+ * camera or frame out of range, a duplicate (camera, frame) pair, offsets that do not start at 0 or decrease, a NULL required
+ * pointer, exactly one of a q / t pair, a frame start without a camera start, reference_camera out of range,
+ * min_shared_frames < 1, min_points < 4, step_tolerance not finite or <= 0, max_iterations < 1, huber_scale < 0 or not finite.
+ * n_views == 0 is CALICO_OK with CALICO_RIG_TOO_FEW_VIEWS and touches no device. */
+#define CALICO_RIG_MAX_CAMERAS 8
+#define CALICO_RIG_OK 0
+#define CALICO_RIG_TOO_FEW_VIEWS 1
+#define CALICO_RIG_NOT_CONVERGED 2
+#define CALICO_RIG_DEGENERATE 3
+#define CALICO_RIG_CAMERA_OK 0
+#define CALICO_RIG_CAMERA_REFERENCE 1
+#define CALICO_RIG_CAMERA_UNCONNECTED 2
+#define CALICO_RIG_FRAME_OK 0
+#define CALICO_RIG_FRAME_NO_VIEW 1
+#define CALICO_RIG_FRAME_NOT_POSITIVE_DEFINITE 2
+typedef struct {
+  int32_t max_iterations;     /* 50 */
+  double step_tolerance;      /* 1e-10 */
+  double huber_scale;         /* 0 = no loss; pixels */
+  int32_t min_points;         /* 4; values below 4 are an argument error */
+  int32_t min_shared_frames;  /* 3 */
+  int32_t reference_camera;   /* 0 */
+} calico_rig_options;
+typedef struct {
+  int32_t status;             /* CALICO_RIG_* */
+  int32_t iterations;         /* steps tried */
+  double initial_cost;        /* Sum rho at the start, over the views that take part */
+  double final_cost;
+  double rms;                 /* sqrt(Sum |residual|^2 / pairs_used) in pixels, no loss applied */
+  int32_t cameras_used;       /* the reference camera and the cameras connected to it */
+  int32_t frames_used;
+  int64_t views_used;
+  int64_t pairs_used;
+  double lambda;              /* the damping at the end */
+} calico_rig_summary;
+void calico_default_rig_options(calico_rig_options* o);
+int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* models /* C */,
+                             const int64_t* intrinsics_offsets /* C + 1 */, const double* intrinsics, int64_t n_frames,
+                             int64_t n_views, const int32_t* view_camera, const int64_t* view_frame,
+                             const int64_t* view_offsets /* n_views + 1 */, const double* pixels /* N x 2 */,
+                             const double* points /* N x 3, chart frame */, const double* q_rig_camera_init,
+                             const double* t_rig_camera_init /* both NULL, or C x 4 / C x 3 */, const double* q_frame_init,
+                             const double* t_frame_init /* both NULL, or n_frames x 4 / x 3; only with the camera start */,
+                             const calico_rig_options* o /* NULL = defaults */, double* q_rig_camera_out, double* t_rig_camera_out,
+                             uint8_t* camera_status_out, double* q_frame_out, double* t_frame_out, uint8_t* frame_status_out,
+                             double* view_rms_out, int32_t* view_n_used_out, uint8_t* view_status_out /* CALICO_RESECT_* */,
+                             double* extrinsics_cov_out /* 6 C x 6 C, may be NULL */, calico_rig_summary* summary);
 
 /* ---- camera-IMU alignment: rotation, gyroscope bias, latency and gravity from a fitted trajectory ---- */
 /* The start calico_solve needs for the IMU side, from the trajectory of the camera side (calico_fit_spline over the poses of

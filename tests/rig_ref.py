@@ -1,0 +1,311 @@
+"""What the rig-calibration tests share: fixtures and a plain numpy reference. No code under test in here.
+
+The reference estimates the extrinsics T_rig_camera of the cameras that are not held and the pose T_rig_chart of every rig
+frame jointly over the ORACLE's forward model (resect_ref.project at T_camera_chart = T_rig_camera^-1 T_rig_chart).
+Derivatives are central differences with h = 1e-6 in the library's perturbations -- a frame moves by R_f <- exp([d]x) R_f,
+t_f <- t_f + dt, a camera by R_c <- exp([d]x) R_c, t_c <- t_c + dt --, weights are rho' of Huber's loss, no second-order term.
+The normal equations are DENSE (6 F + 6 C <= 168 unknowns, frames first, then cameras; what is held or takes no part gets an
+identity row and a zero right-hand side), Marquardt damping lambda diag on all of them.
+
+Step size (the library's definition):  s = max(|d_rot|_inf, |dt|_inf / max(1, |t|_2))  over frames and cameras. The optimality
+criterion the tests hold the device to: the reference's UNDAMPED Gauss-Newton step at the DEVICE's estimate has
+s <= step_tolerance + 10 FLOOR[fixture].
+"""
+import collections
+import functools
+
+import numpy as np
+
+import resect_ref as rr
+from calico_amd import synthetic as syn
+
+H = 1e-6
+# FLOOR[fixture]: the largest s of six undamped Gauss-Newton steps of the reference at and after the point where refine() stops
+# (0.1 px noise, from the truth perturbed by 0.02 N(0, 1)); REF_FREE[fixture]: the reference's own distance to the truth on
+# noise-free data from the same start. tests/test_rig_host.py::test_reference_floor_and_noise_free_distance re-measures both on
+# every run and prints them; the figures below are its output (python -m pytest tests/test_rig_host.py -s -k floor).
+#   FLOOR     standard: 1.2e-13   chain: 1.8e-13   wide: 1.1e-13   long: 5.2e-13      (6 to 8 accepted steps)
+#   REF_FREE  standard: 4.5e-16   chain: 5.3e-16   wide: 1.4e-15   long: 5.8e-16
+FLOOR = {"standard": 1.2e-13, "chain": 1.8e-13, "wide": 1.1e-13, "long": 5.2e-13}
+REF_FREE = {"standard": 4.5e-16, "chain": 5.3e-16, "wide": 1.4e-15, "long": 5.8e-16}
+
+Rig = collections.namedtuple("Rig", "models ks n_frames view_camera view_frame view_offsets pixels points cams frames")
+
+
+def camera_from_chart(cam, frame):
+    """T_camera_chart (R, t) of a camera (R_c, t_c) = T_rig_camera and a rig frame (R_f, t_f) = T_rig_chart."""
+    (Rc, tc), (Rf, tf) = cam, frame
+    return Rc.T @ Rf, Rc.T @ (np.asarray(tf, float) - np.asarray(tc, float))
+
+
+def project(rig, v, cam, frame):
+    c = rig.view_camera[v]
+    R, t = camera_from_chart(cam, frame)
+    return rr.project(rig.models[c], rig.ks[c], R, t, rig.points[rig.view_offsets[v]:rig.view_offsets[v + 1]])
+
+
+def moved(pose, d):
+    R, t = pose
+    return rr.exp_so3(d[:3]) @ R, np.asarray(t, float) + d[3:]
+
+
+def view_system(rig, v, cam, frame, huber=0.0, h=H, held=False):
+    """(M 12 x 12, g 12, e, ok) of one view in [frame 6 | camera 6]; the camera's columns are zero where it is held."""
+    px, ok = project(rig, v, cam, frame)
+    cols = []
+    for i in range(12):
+        if i >= 6 and held:
+            cols.append(np.zeros_like(px))
+            continue
+        d = np.zeros(6)
+        d[i % 6] = h
+        if i < 6:
+            a, oka = project(rig, v, cam, moved(frame, d))
+            b, okb = project(rig, v, cam, moved(frame, -d))
+        else:
+            a, oka = project(rig, v, moved(cam, d), frame)
+            b, okb = project(rig, v, moved(cam, -d), frame)
+        ok = ok & oka & okb
+        cols.append((a - b) / (2 * h))
+    pix = rig.pixels[rig.view_offsets[v]:rig.view_offsets[v + 1]]
+    e = (px - pix)[ok]
+    J = np.stack([c[ok] for c in cols], axis=2)
+    w = rr.weights(e, huber)
+    return np.einsum("n,nri,nrj->ij", w, J, J), np.einsum("n,nri,nr->i", w, J, e), e, ok
+
+
+def all_views(rig):
+    return np.ones(len(rig.view_camera), bool)
+
+
+def held_of(rig, held=None):
+    return {0} if held is None else set(held)
+
+
+def normal(rig, cams, frames, use=None, held=None, huber=0.0, h=H):
+    """(Hm, g, cost, valid pairs per view) over the views use[v]: dense, unknowns [frames 6 F | cameras 6 C]."""
+    F, Cn = rig.n_frames, len(rig.models)
+    use = all_views(rig) if use is None else use
+    held = held_of(rig, held)
+    n = 6 * (F + Cn)
+    Hm, g, cost = np.zeros((n, n)), np.zeros(n), 0.0
+    valid = np.zeros(len(use), int)
+    for v in np.flatnonzero(use):
+        c, f = rig.view_camera[v], rig.view_frame[v]
+        M, gv, e, ok = view_system(rig, v, cams[c], frames[f], huber, h, c in held)
+        idx = np.r_[6 * f:6 * f + 6, 6 * (F + c):6 * (F + c) + 6]
+        Hm[np.ix_(idx, idx)] += M
+        g[idx] += gv
+        sq = (e ** 2).sum(1)
+        if huber > 0:
+            r = np.sqrt(sq)
+            sq = np.where(r > huber, 2 * huber * r - huber ** 2, sq)
+        cost += float(sq.sum())
+        valid[v] = int(ok.sum())
+    return Hm, g, cost, valid
+
+
+def free_unknowns(rig, use=None, held=None):
+    """The unknowns that are estimated: frames with a view in use, cameras that are not held."""
+    F, Cn = rig.n_frames, len(rig.models)
+    use = all_views(rig) if use is None else use
+    held = held_of(rig, held)
+    free = np.zeros(6 * (F + Cn), bool)
+    for v in np.flatnonzero(use):
+        f = rig.view_frame[v]
+        free[6 * f:6 * f + 6] = True
+    for c in range(Cn):
+        if c not in held:
+            free[6 * (F + c):6 * (F + c) + 6] = True
+    return free
+
+
+def solve(Hm, g, free, lam=0.0):
+    A = Hm + lam * np.diag(np.diag(Hm))
+    d = np.zeros(len(g))
+    d[free] = -np.linalg.solve(A[np.ix_(free, free)], g[free])
+    return d
+
+
+def step_size(rig, cams, frames, d):
+    F = rig.n_frames
+    s = 0.0
+    for i, (_, t) in enumerate(list(frames) + list(cams)):
+        di = d[6 * i:6 * i + 6]
+        s = max(s, float(np.abs(di[:3]).max()), float(np.abs(di[3:]).max() / max(1.0, np.linalg.norm(t))))
+    return s
+
+
+def apply(rig, cams, frames, d):
+    F = rig.n_frames
+    return ([moved(p, d[6 * (F + c):6 * (F + c) + 6]) for c, p in enumerate(cams)], [moved(p, d[6 * f:6 * f + 6]) for f, p in enumerate(frames)])
+
+
+def gn(rig, cams, frames, use=None, held=None, huber=0.0, h=H):
+    """The undamped Gauss-Newton step at (cams, frames): (d, s)."""
+    Hm, g, _, _ = normal(rig, cams, frames, use, held, huber, h)
+    d = solve(Hm, g, free_unknowns(rig, use, held))
+    return d, step_size(rig, cams, frames, d)
+
+
+def refine(rig, cams, frames, use=None, held=None, huber=0.0, max_steps=40):
+    """Levenberg-Marquardt as calib_ref.refine (lambda from 1e-4, / 10 on an accepted step, x 10 on a rejected one) until the step
+    stops shrinking at lambda <= 1e-4. Returns (cams, frames, s of the last step, accepted steps, converged)."""
+    cams = [(R.copy(), np.asarray(t, float).copy()) for R, t in cams]
+    frames = [(R.copy(), np.asarray(t, float).copy()) for R, t in frames]
+    free = free_unknowns(rig, use, held)
+    lam, last, accepted = 1e-4, np.inf, 0
+    Hm, g, c0, n0 = normal(rig, cams, frames, use, held, huber)
+    for _ in range(max_steps):
+        d = solve(Hm, g, free, lam)
+        s = step_size(rig, cams, frames, d)
+        c1_, f1_ = apply(rig, cams, frames, d)
+        H1, g1, c1, n1 = normal(rig, c1_, f1_, use, held, huber)
+        if np.array_equal(n0, n1) and np.isfinite(c1) and c1 <= c0 * (1 + 1e-14):
+            small = lam <= 1e-4 and last < 1e-7 and (s >= last or s < 1e-15)      # (quadratic convergence has hit the floor)
+            if small and s >= last:
+                return cams, frames, last, accepted, True
+            cams, frames, Hm, g, c0, n0, last = c1_, f1_, H1, g1, c1, n1, s
+            accepted += 1
+            if small:
+                return cams, frames, last, accepted, True
+            lam = max(lam * 0.1, 1e-12)
+        else:
+            if lam <= 1e-4 and s < 1e-9:      # below what the cost resolves: the point is kept
+                return cams, frames, s, accepted, True
+            lam = min(lam * 10.0, 1e12)
+    return cams, frames, last, accepted, False
+
+
+def poses_of(q, t):
+    return [(rr.rot(qi), np.asarray(ti, float)) for qi, ti in zip(q, t)]
+
+
+def criterion(rig, q_cam, t_cam, q_frame, t_frame, use=None, held=None, huber=0.0):
+    """s of the reference's undamped Gauss-Newton step at the device's estimate ((q, t) rows per camera and per frame)."""
+    return gn(rig, poses_of(q_cam, t_cam), poses_of(q_frame, t_frame), use, held, huber)[1]
+
+
+def rms_at(rig, q_cam, t_cam, q_frame, t_frame, use=None):
+    """(rms over the views in use, pairs, [rms per view])."""
+    cams, frames = poses_of(q_cam, t_cam), poses_of(q_frame, t_frame)
+    use = all_views(rig) if use is None else use
+    ss, n, per = 0.0, 0, np.zeros(len(use))
+    for v in np.flatnonzero(use):
+        px, ok = project(rig, v, cams[rig.view_camera[v]], frames[rig.view_frame[v]])
+        e = (px - rig.pixels[rig.view_offsets[v]:rig.view_offsets[v + 1]])[ok]
+        ss += float((e * e).sum())
+        n += int(ok.sum())
+        per[v] = np.sqrt((e * e).sum() / ok.sum())
+    return float(np.sqrt(ss / n)), n, per
+
+
+def reduced_covariance(rig, q_cam, t_cam, q_frame, t_frame, use=None, held=None, huber=0.0, h=H):
+    """(C - Sum B^T A^-1 B)^-1 at the estimate (6 C x 6 C), zero rows and columns for the held cameras."""
+    F, Cn = rig.n_frames, len(rig.models)
+    Hm, _, _, _ = normal(rig, poses_of(q_cam, t_cam), poses_of(q_frame, t_frame), use, held, huber, h)
+    free = free_unknowns(rig, use, held)
+    ff, fc = free[:6 * F], free[6 * F:]
+    A = Hm[:6 * F, :6 * F][np.ix_(ff, ff)]
+    B = Hm[:6 * F, 6 * F:][np.ix_(ff, fc)]
+    Cm = Hm[6 * F:, 6 * F:][np.ix_(fc, fc)]
+    cov = np.zeros((6 * Cn, 6 * Cn))
+    cov[np.ix_(fc, fc)] = np.linalg.inv(Cm - B.T @ np.linalg.solve(A, B))
+    return cov
+
+
+def distance(cams, frames, rig, use=None, held=None):
+    """The largest pose_distance to the truth over the cameras that are not held and the frames with a view in use."""
+    free = free_unknowns(rig, use, held)
+    F = rig.n_frames
+    d = 0.0
+    for f in range(F):
+        if free[6 * f]:
+            d = max(d, rr.pose_distance(*frames[f], *rig.frames[f]))
+    for c in range(len(rig.models)):
+        if free[6 * (F + c)]:
+            d = max(d, rr.pose_distance(*cams[c], *rig.cams[c]))
+    return d
+
+
+def perturbed_start(rig, seed=4321, scale=0.02):
+    """(q_cam, t_cam, q_frame, t_frame): the truth perturbed by scale N(0, 1); camera 0 stays at the truth."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for poses, keep in ((rig.cams, 1), (rig.frames, 0)):
+        q, t = [], []
+        for i, (R, tt) in enumerate(poses):
+            p = scale * rng.standard_normal(6)
+            if i < keep:
+                p[:] = 0.0
+            qq = rr.quat_of(rr.exp_so3(p[:3]) @ R)
+            q.append(qq if qq[3] >= 0 else -qq)
+            t.append(np.asarray(tt, float) + p[3:])
+        out += [np.array(q), np.array(t)]
+    return tuple(out)
+
+
+def _make(models, cams, frames, pts, noise, seed, keep=None):
+    ks = [np.array(syn._TRUE_INTRINSICS[m], float) for m in models]
+    rng = np.random.default_rng(seed)
+    vc, vf, off, pix, pnt = [], [], [0], [], []
+    for f, frame in enumerate(frames):
+        for c, cam in enumerate(cams):
+            R, t = camera_from_chart(cam, frame)
+            px, ok = rr.project(models[c], ks[c], R, t, pts)
+            assert ok.all(), (c, f)
+            px = px + noise * rng.standard_normal(px.shape)      # (drawn for every view: a fixture that drops views keeps the others' pixels)
+            if keep is not None and not keep(c, f):
+                continue
+            vc.append(c)
+            vf.append(f)
+            off.append(off[-1] + len(pts))
+            pix.append(px)
+            pnt.append(pts)
+    arrays = (np.array(vc, np.int32), np.array(vf, np.int64), np.array(off, np.int64), np.concatenate(pix), np.concatenate(pnt))
+    for a in arrays:
+        a.setflags(write=False)
+    return Rig(tuple(models), ks, len(frames), *arrays, cams, frames)
+
+
+STANDARD_CAMS = (((0.0, 0.0, 0.0), (0.0, 0.0, 0.0)), ((0.02, -0.03, 0.05), (0.12, 0.0, 0.01)), ((-0.04, 0.10, 0.03), (-0.10, 0.05, -0.02)))
+
+
+def _cams(rows):
+    return [(rr.exp_so3(np.array(r, float)), np.array(t, float)) for r, t in rows]
+
+
+@functools.lru_cache(maxsize=None)
+def standard(noise, models=(1, 3, 6)):
+    """The 20 frames x 36 planar points of resect_ref.fixture taken as T_rig_chart, three cameras: 60 views, 2160 pairs."""
+    return _make(models, _cams(STANDARD_CAMS), rr.true_poses(), syn.planar_points(), noise, 2468)
+
+
+@functools.lru_cache(maxsize=None)
+def chain(noise):
+    """The standard rig where camera 0 sees frames 0-9, camera 1 all frames and camera 2 frames 8-19: cameras 0 and 2 share two
+    frames, fewer than min_shared_frames, and frames 10-19 have no view of the reference camera."""
+    return _make((1, 3, 6), _cams(STANDARD_CAMS), rr.true_poses(), syn.planar_points(), noise, 2468,
+                 keep=lambda c, f: (c == 0 and f <= 9) or c == 1 or (c == 2 and f >= 8))
+
+
+@functools.lru_cache(maxsize=None)
+def wide(noise):
+    """Eight cameras (models 1..7, then 1) within 0.15 m and 0.1 rad of the rig's origin, six frames; the last view is dropped:
+    47 views, no multiple of the evaluation's four waves. The smallest shape that runs M = 48 and every model in one call."""
+    rng = np.random.default_rng(97531)
+    rows = [((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))]
+    for _ in range(7):
+        r, t = rng.uniform(-1, 1, 3), rng.uniform(-1, 1, 3)
+        rows.append((tuple(0.1 * r / max(1.0, np.linalg.norm(r))), tuple(0.15 * t / max(1.0, np.linalg.norm(t)))))
+    return _make((1, 2, 3, 4, 5, 6, 7, 1), _cams(rows), rr.true_poses()[::3][:6], syn.planar_points(), noise, 8642,
+                 keep=lambda c, f: not (c == 7 and f == 5))
+
+
+@functools.lru_cache(maxsize=None)
+def long_views(noise):
+    """Two cameras, six frames, the 144 points of the AprilGrid: three trips of 64 pairs per view, the last one partial."""
+    return _make((1, 3), _cams(STANDARD_CAMS[:2]), rr.true_poses()[::3][:6], syn.aprilgrid_points(), noise, 1357)
+
+
+FIXTURES = {"standard": standard, "chain": chain, "wide": wide, "long": long_views}
