@@ -147,6 +147,26 @@ class ImuAlignmentSummary(C.Structure):
 ALIGN_OK, ALIGN_TOO_FEW_SAMPLES, ALIGN_NO_PEAK, ALIGN_DEGENERATE, ALIGN_NOT_CONVERGED, ALIGN_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3, 4, 5
 ALIGN_MAX_LAGS = 4096
 
+FIT_MAX_LAMBDAS = 32
+FIT_OK, FIT_NOT_POSITIVE_DEFINITE, FIT_TARGET_NOT_MET = 0, 1, 2
+
+
+class SplineFitOptions(C.Structure):
+    """calico_spline_fit_options."""
+    _fields_ = [("derivative", C.c_int32), ("relative", C.c_int32), ("n_lambda", C.c_int32), ("lambda_rot", C.c_double * FIT_MAX_LAMBDAS),
+                ("lambda_pos", C.c_double * FIT_MAX_LAMBDAS), ("target_rms_rot", C.c_double), ("target_rms_pos", C.c_double)]
+
+
+class SplineFitRow(C.Structure):
+    """calico_spline_fit_row."""
+    _fields_ = [("status", C.c_int32), ("replaced_pivots", C.c_int32), ("lambda_", C.c_double), ("rss", C.c_double), ("penalty", C.c_double),
+                ("rms", C.c_double)]
+
+
+class SplineFitSummary(C.Structure):
+    """calico_spline_fit_summary."""
+    _fields_ = [("status", C.c_int32 * 2), ("chosen", C.c_int32 * 2), ("n_used", C.c_int64 * 2)]
+
 
 class Iteration(C.Structure):
     _fields_ = [
@@ -210,6 +230,7 @@ ABI_SYMBOLS = [
     "default_calibration_options", "camera_calibrate",
     "default_imu_alignment_options", "imu_align",
     "default_rig_options", "rig_calibrate",
+    "default_spline_fit_options", "fit_spline_smooth",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -314,6 +335,11 @@ class CApi:
                 g("default_rig_options", None, [RGO])
                 g("rig_calibrate", C.c_int32, [C.c_int32, C.c_int32, I, I64, D, C.c_int64, C.c_int64, I, I64, I64, D, D, D, D, D, D, RGO,
                                                D, D, U8, D, D, U8, D, I, U8, D, C.POINTER(RigSummary)])
+            if hasattr(self.lib, self.prefix + "fit_spline_smooth"):
+                FO = C.POINTER(SplineFitOptions)
+                g("default_spline_fit_options", None, [FO])
+                g("fit_spline_smooth", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, D, D, C.POINTER(SplineFitRow),
+                                                   C.POINTER(SplineFitSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -611,6 +637,53 @@ def imu_align(api, order, knots, basis, ctrl, gyro_stamps, gyro, accel_stamps=No
     if curve:
         out["curve_tail"] = cur[summary.n_lags:]      # (never written by the library)
     return out
+
+
+def default_spline_fit_options(api, lambda_rot=None, lambda_pos=None, **kw):
+    """The library's default calico_spline_fit_options with the given fields replaced. lambda_rot / lambda_pos: a number or a
+    sequence (the grid); n_lambda follows their length unless given."""
+    o = _options(SplineFitOptions, api.default_spline_fit_options, "spline fit", kw)
+    for name, grid in (("lambda_rot", lambda_rot), ("lambda_pos", lambda_pos)):
+        if grid is None:
+            continue
+        grid = np.atleast_1d(np.asarray(grid, dtype=np.float64))
+        if not 1 <= len(grid) <= FIT_MAX_LAMBDAS:
+            raise ValueError("%s must have 1 to %d entries" % (name, FIT_MAX_LAMBDAS))
+        field = getattr(o, name)
+        for i in range(FIT_MAX_LAMBDAS):
+            field[i] = grid[i] if i < len(grid) else 0.0
+        if "n_lambda" not in kw:
+            o.n_lambda = len(grid)
+    return o
+
+
+def fit_spline_smooth(api, order, knots, basis, stamps, data6, weights=None, options=None, device=0):
+    """calico_fit_spline_smooth: the penalised spline fit through sorted samples data6 (n, 6) at stamps, per channel group (rotation:
+    channels 0..2, position: 3..5) and for every lambda of the options' grid. weights: (n, 2) [rotation, position] or None (all 1).
+    options: a SplineFitOptions (default_spline_fit_options(api, ...)) or None. Returns a dict: ctrl (n_ctrl, 6; each group's chosen
+    lambda), ctrl_all (n_lambda, n_ctrl, 6), rows ([group][lambda] dicts: status, replaced_pivots, lambda, rss, penalty, rms) and
+    summary (status, chosen, n_used: one entry per group)."""
+    knots, basis, order = _f64(knots).ravel(), _f64(basis), int(order)
+    t, d = _f64(stamps).ravel(), _f64(data6).reshape(-1, 6)
+    if len(t) != len(d):
+        raise ValueError("one stamp per sample")
+    if basis.size != max(len(knots) - 2 * order + 1, 0) * order * order:
+        raise ValueError("basis must be (n_knots - 2 order + 1, order, order)")
+    w = None if weights is None else _f64(weights).reshape(-1, 2)
+    if w is not None and len(w) != len(t):
+        raise ValueError("weights must be (n, 2)")
+    nl = options.n_lambda if options is not None else 1
+    n_ctrl = max(len(knots) - order, 1)
+    ctrl = np.full((n_ctrl, 6), np.nan)
+    ctrl_all = np.full((max(min(nl, FIT_MAX_LAMBDAS), 1), n_ctrl, 6), np.nan)
+    rows = (SplineFitRow * (2 * len(ctrl_all)))()
+    summary = SplineFitSummary()
+    st = api.fit_spline_smooth(int(device), order, len(knots), _dp(knots), _dp(basis), len(t), _dp(t), _dp(d), None if w is None else _dp(w),
+                               None if options is None else C.byref(options), _dp(ctrl), _dp(ctrl_all), rows, C.byref(summary))
+    _check_free(api, st)
+    names = [("status", "status"), ("replaced_pivots", "replaced_pivots"), ("lambda", "lambda_"), ("rss", "rss"), ("penalty", "penalty"), ("rms", "rms")]
+    return dict(ctrl=ctrl, ctrl_all=ctrl_all, rows=[[{k: getattr(rows[g * nl + l], f) for k, f in names} for l in range(nl)] for g in range(2)],
+                summary=dict(status=list(summary.status), chosen=list(summary.chosen), n_used=list(summary.n_used)))
 
 
 class Problem:

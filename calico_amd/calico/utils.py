@@ -137,7 +137,9 @@ def InitializePoses(camera, all_detections: List[Dict[int, np.ndarray]], model_d
     the device (Camera.EstimateChartPoses: homography start from the unprojected pixels, then Levenberg-Marquardt on the
     library's projection). Returns ([R_chart_camera per frame], [t_chart_camera per frame], ok (n_frames,) bool) in the
     conventions of InitializePinholeAndPoses; a frame that is not ok (too few points, no start, not converged, degenerate)
-    carries the identity and must not be handed to FitSpline."""
+    carries the identity and must not be handed to FitSpline. With the smoothing fit (Trajectory.FitSplineSmooth) such frames
+    are simply left out: its roughness penalty carries the spline across the gap they leave, where FitSpline would drop the
+    control points of a gap longer than the spline's support to zero."""
     r = camera.EstimateChartPoses(all_detections, model_definition)
     R_chart_camera, t_chart_camera = [], []
     for (x, y, z, w), t in zip(r["q"], r["t"]):
@@ -223,7 +225,8 @@ def InitializeRig(cameras, rig_frames: List[Dict[int, Dict[int, np.ndarray]]], m
     camera's index in `cameras` to its detections {feature id: pixel} at an instant the rig stood still relative to the chart.
     Sets the extrinsics of the cameras that took part. Returns ([R_chart_rig per rig frame], [t_chart_rig per rig frame],
     ok (n_frames,) bool) in the conventions of InitializePoses -- what Trajectory.FitSpline takes, now also for the frames the
-    reference camera never saw; a frame that is not ok carries the identity and must not be handed to FitSpline. options: None or
+    reference camera never saw; a frame that is not ok carries the identity and must not be handed to FitSpline (with
+    Trajectory.FitSplineSmooth such frames are simply left out: the penalty carries the spline across the gap). options: None or
     a dict of calico_rig_options fields. Raises RuntimeError when the estimation does not end with status OK (before anything is
     changed)."""
     r = _calico.CalibrateRig(list(cameras), rig_frames, model_definition, options)

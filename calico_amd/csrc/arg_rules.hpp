@@ -118,6 +118,37 @@ inline std::string stamps_error(const char* name, int64_t n, const double* stamp
   return "";
 }
 
+// ---- the smoothing fit of calico_fit_spline_smooth: its options, and the sample weights (n x 2; n_used[g]: weights > 0 of column g) ----
+inline std::string spline_fit_options_error(int order, const calico_spline_fit_options& o) {
+  const int m_max = std::min(3, order - 1);
+  if (o.derivative < 1 || o.derivative > m_max) return "derivative must be in [1, " + std::to_string(m_max) + "] at order " + std::to_string(order);
+  if (o.n_lambda < 1 || o.n_lambda > CALICO_FIT_MAX_LAMBDAS) return "n_lambda must be in [1, " + std::to_string(CALICO_FIT_MAX_LAMBDAS) + "]";
+  for (int g = 0; g < 2; ++g) {
+    const double* grid = g == 0 ? o.lambda_rot : o.lambda_pos;
+    const char* name = g == 0 ? "lambda_rot" : "lambda_pos";
+    for (int l = 0; l < o.n_lambda; ++l) {
+      if (!std::isfinite(grid[l]) || grid[l] < 0.0) return std::string(name) + "[" + std::to_string(l) + "] must be finite and >= 0";
+      if (l > 0 && !(grid[l] > grid[l - 1])) return std::string(name) + " must be strictly ascending: entry " + std::to_string(l) + " is not";
+    }
+    const double target = g == 0 ? o.target_rms_rot : o.target_rms_pos;
+    if (!std::isfinite(target) || target < 0.0) return std::string(g == 0 ? "target_rms_rot" : "target_rms_pos") + " must be finite and >= 0";
+  }
+  return "";
+}
+inline std::string sample_weights_error(int64_t n, const double* weights, int64_t n_used[2]) {
+  n_used[0] = n_used[1] = weights ? 0 : n;
+  if (!weights) return "";
+  for (int64_t j = 0; j < n; ++j)
+    for (int g = 0; g < 2; ++g) {
+      const double w = weights[j * 2 + g];
+      if (!std::isfinite(w) || w < 0.0) return "weight " + std::to_string(g) + " of sample " + std::to_string(j) + " must be finite and >= 0";
+      n_used[g] += w > 0.0;
+    }
+  for (int g = 0; g < 2; ++g)
+    if (n_used[g] == 0) return std::string(g == 0 ? "rotation" : "position") + " weights: no sample has a weight > 0";
+  return "";
+}
+
 // ---- a caller's quaternion (x, y, z, w) as the unit quaternion with w >= 0; which lengths are an error is the caller's rule ----
 inline double quat_norm(const double* q) { return std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); }
 inline void canonical_unit_quat(const double* q, double norm, double* out) {

@@ -11,7 +11,8 @@
 //   fit_solve_kernel     one wave: banded Cholesky (tiny ridge; pivots the samples do not determine -- the trajectory end
 //                        can have fewer samples than control points, where the reference's QR result is
 //                        roundoff-defined -- are decoupled),
-//                        forward and backward substitution of the six right-hand sides, all in LDS
+//                        forward and backward substitution of the six right-hand sides, all in LDS (fit_band_solve, shared
+//                        with the smoothing fit below: calico_fit_spline_smooth, its kernels after fit_solve_kernel)
 // Accuracy (profiles/EXPERIMENTS.md, "spline fit accuracy"; tests/fit_ref.py is the reference): backward error of the normal
 // equations ~5e-16 on every shape; control points within 0.2-0.7 x 1e-15 cond₂² max|C| of exact least squares on the kept
 // columns (cond₂ theirs), fitted values never further and up to 6 decades closer as cond₂ grows. The pivot rule is a cliff: a control point whose pivot is <= 1e-13 mean_diag comes back ~0 even where
@@ -58,15 +59,12 @@ __global__ void fit_normal_kernel(int n_ctrl, int n_seg, int k, const double* __
   if (e < k) band[size_t(a) * k + e] = acc; else rhs[size_t(a) * 6 + (e - k)] = acc;
 }
 
-__global__ __launch_bounds__(64) void fit_solve_kernel(int n, int k, const double* __restrict__ band_g, const double* __restrict__ rhs_g,
-                                                       double* __restrict__ ctrl, int* status) {
-  extern __shared__ double lds[];
-  double* B = lds;                   // [n][k]  B[a][d] = L(a, a - d) after the factorisation
-  double* Y = lds + size_t(n) * k;   // [n][6]
-  const int lane = threadIdx.x;
-  for (int i = lane; i < n * k; i += 64) B[i] = band_g[i];
-  for (int i = lane; i < n * 6; i += 64) Y[i] = rhs_g[i];
-  __syncthreads();
+// The solve every fit shares, one wave on [B | Y] in LDS: B [n][k] is the lower band of the matrix (B[a][d] = A(a, a - d); L(a, a - d)
+// afterwards), Y [n][NRHS] the right-hand sides (the solution afterwards). Ridge of 1e-15 mean_diag of B, right-looking banded
+// Cholesky with the pivot rule, forward and backward substitution. Returns through `bad` whether a pivot was not finite and
+// through `replaced` how many pivots the rule replaced (both wave-uniform). The caller has synchronised after filling B and Y.
+template <int NRHS>
+DEV void fit_band_solve(int n, int k, double* B, double* Y, int lane, bool* bad_out, int* replaced_out) {
   double tr = 0.0;
   for (int i = lane; i < n; i += 64) tr += B[i * k];
 #pragma unroll
@@ -86,12 +84,13 @@ __global__ __launch_bounds__(64) void fit_solve_kernel(int n, int k, const doubl
     if (i < k) { ui = i; uc = t + 1; }
   }
   bool bad = false;
+  int replaced = 0;
   for (int j = 0; j < n; ++j) {
     double d = B[j * k];
     bad = bad || !isfinite(d);
     // a control point the samples do not determine (fewer samples than control points at the trajectory end: the
     // reference's pivoted QR returns roundoff there) is decoupled instead of dividing by noise
-    if (!(d > 1e-13 * mean_diag)) d = mean_diag;
+    if (!(d > 1e-13 * mean_diag)) { d = mean_diag; ++replaced; }
     const double inv = 1.0 / sqrt(d);
     __syncthreads();
     if (lane == 0) B[j * k] = d * inv;
@@ -100,22 +99,177 @@ __global__ __launch_bounds__(64) void fit_solve_kernel(int n, int k, const doubl
     if (ui > 0 && j + ui < n) B[(j + ui) * k + (ui - uc)] -= B[(j + ui) * k + ui] * B[(j + uc) * k + uc];
     __syncthreads();
   }
-  // forward then backward substitution, lane c < 6 per right-hand side
-  if (lane < 6) {
+  // forward then backward substitution, lane c < NRHS per right-hand side
+  if (lane < NRHS) {
     for (int a = 0; a < n; ++a) {
-      double s = Y[a * 6 + lane];
-      for (int d = 1; d < k && d <= a; ++d) s -= B[a * k + d] * Y[(a - d) * 6 + lane];
-      Y[a * 6 + lane] = s / B[a * k];
+      double s = Y[a * NRHS + lane];
+      for (int d = 1; d < k && d <= a; ++d) s -= B[a * k + d] * Y[(a - d) * NRHS + lane];
+      Y[a * NRHS + lane] = s / B[a * k];
     }
     for (int a = n - 1; a >= 0; --a) {
-      double s = Y[a * 6 + lane];
-      for (int d = 1; d < k && a + d < n; ++d) s -= B[(a + d) * k + d] * Y[(a + d) * 6 + lane];
+      double s = Y[a * NRHS + lane];
+      for (int d = 1; d < k && a + d < n; ++d) s -= B[(a + d) * k + d] * Y[(a + d) * NRHS + lane];
       s /= B[a * k];
-      Y[a * 6 + lane] = s;
-      ctrl[size_t(a) * 6 + lane] = s;
+      Y[a * NRHS + lane] = s;
     }
   }
+  __syncthreads();
+  *bad_out = bad;
+  *replaced_out = replaced;
+}
+
+__global__ __launch_bounds__(64) void fit_solve_kernel(int n, int k, const double* __restrict__ band_g, const double* __restrict__ rhs_g,
+                                                       double* __restrict__ ctrl, int* status) {
+  extern __shared__ double lds[];
+  double* B = lds;                   // [n][k]
+  double* Y = lds + size_t(n) * k;   // [n][6]
+  const int lane = threadIdx.x;
+  for (int i = lane; i < n * k; i += 64) B[i] = band_g[i];
+  for (int i = lane; i < n * 6; i += 64) Y[i] = rhs_g[i];
+  __syncthreads();
+  bool bad;
+  int replaced;
+  fit_band_solve<6>(n, k, B, Y, lane, &bad, &replaced);
+  for (int i = lane; i < n * 6; i += 64) ctrl[i] = Y[i];
   if (lane == 0) *status = bad ? 1 : 0;
+}
+
+// ---- the smoothing fit (calico_fit_spline_smooth):  min_C sum_j w_j |X_j C - d_j|² + lambda ∫ |s^(m)(t)|² dt  per channel group
+// (0: axis-angle, channels 0..2; 1: position, channels 3..5), for a whole grid of lambda in one launch.
+//   fit_penalty_kernel          one thread per band entry of P (n_ctrl x k), the Gram matrix of the m-th derivatives of the basis
+//                               functions: per segment of length D with basis matrix M (row = power of u),
+//                               P_seg = D^(1-2m) Mᵀ H M,  H_ij = c_i c_j / (i + j - 2m + 1),  c_i = i! / (i - m)!  (i, j >= m)
+//   fit_normal_weighted_kernel  one thread per entry of [band | 3 rhs] per group: fit_normal_kernel's sum with w_{j,g} applied; a
+//                               sample of weight 0 is skipped (its data are not read). Without weights the sum is fit_normal_kernel's.
+//   fit_solve_smooth_kernel     one wave per (group, lambda): A = N_g + lambda P in LDS, fit_band_solve, c'Pc, the weighted rss, the row
+
+// entry e of row a: P(a, a - e), summed over the segments that hold both control points, in segment order
+__global__ void fit_penalty_kernel(int n_ctrl, int n_seg, int k, int m, const double* __restrict__ knots, const double* __restrict__ basis,
+                                   double* __restrict__ P) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_ctrl * k) return;
+  const int a = t / k, e = t - a * k;
+  double acc = 0.0;
+  const int s_lo = max(0, a - (k - 1)), s_hi = min(a, n_seg - 1);
+  for (int s = s_lo; s <= s_hi; ++s) {
+    const int ia = a - s, ib = ia - e;
+    if (ib < 0) continue;
+    const double* M = basis + size_t(s) * k * k;
+    const double delta = knots[s + k] - knots[s + k - 1];
+    double scale = delta;                                     // D^(1 - 2m)
+    for (int q = 0; q < 2 * m; ++q) scale /= delta;
+    double seg = 0.0;
+    for (int i = m; i < k; ++i) {
+      double ci = 1.0;
+      for (int q = 0; q < m; ++q) ci *= double(i - q);
+      double row = 0.0;
+      for (int j = m; j < k; ++j) {
+        double cj = 1.0;
+        for (int q = 0; q < m; ++q) cj *= double(j - q);
+        row += (ci * cj / double(i + j - 2 * m + 1)) * M[j * k + ib];
+      }
+      seg += M[i * k + ia] * row;
+    }
+    acc += scale * seg;
+  }
+  P[size_t(a) * k + e] = acc;
+}
+
+// entry e of row a of group g: e < k -> N_g(a, a - e), e >= k -> rhs_g(a, e - k); weights [n][2] (WEIGHTED) or none
+template <bool WEIGHTED>
+__global__ void fit_normal_weighted_kernel(int n_ctrl, int n_seg, int k, const double* __restrict__ W, const double* __restrict__ data,
+                                           const double* __restrict__ weights, const int* __restrict__ seg_ptr, double* __restrict__ band,
+                                           double* __restrict__ rhs) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int per = k + 3, g = blockIdx.y;
+  if (t >= n_ctrl * per) return;
+  const int a = t / per, e = t - a * per;
+  double acc = 0.0;
+  const int s_lo = max(0, a - (k - 1)), s_hi = min(a, n_seg - 1);
+  for (int s = s_lo; s <= s_hi; ++s) {
+    const int ia = a - s;                       // local index of control point a in segment s
+    const int ib = e < k ? ia - e : 0;          // local index of control point a - e
+    if (e < k && ib < 0) continue;
+    for (int q = seg_ptr[s]; q < seg_ptr[s + 1]; ++q) {
+      const double wa = W[size_t(q) * k + ia];
+      if (WEIGHTED) {
+        const double w = weights[size_t(q) * 2 + g];
+        if (w == 0.0) continue;
+        acc += e < k ? wa * (W[size_t(q) * k + ib] * w) : wa * (data[size_t(q) * 6 + 3 * g + (e - k)] * w);
+      } else {
+        acc += e < k ? wa * W[size_t(q) * k + ib] : wa * data[size_t(q) * 6 + 3 * g + (e - k)];
+      }
+    }
+  }
+  if (e < k) band[(size_t(g) * n_ctrl + a) * k + e] = acc; else rhs[(size_t(g) * n_ctrl + a) * 3 + (e - k)] = acc;
+}
+
+DEV double fit_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void fit_solve_smooth_kernel(FitSmoothArgs a) {
+  extern __shared__ double lds[];
+  const int n = a.n_ctrl, k = a.k, g = blockIdx.x, l = blockIdx.y, lane = threadIdx.x;
+  double* B = lds;                   // [n][k]
+  double* Y = lds + size_t(n) * k;   // [n][3]
+  const double* N = a.band + size_t(g) * n * k;
+  const double* rhs = a.rhs + size_t(g) * n * 3;
+  double lambda = g == 0 ? a.lambda_rot[l] : a.lambda_pos[l];
+  if (a.relative) {      // in units of trace(N_g) / trace(P)
+    double tn = 0.0, tp = 0.0;
+    for (int i = lane; i < n; i += 64) { tn += N[i * k]; tp += a.P[i * k]; }
+    lambda *= fit_wave_sum(tn) / fit_wave_sum(tp);
+  }
+  if (lambda == 0.0) {
+    for (int i = lane; i < n * k; i += 64) B[i] = N[i];
+  } else {
+    for (int i = lane; i < n * k; i += 64) B[i] = N[i] + lambda * a.P[i];
+  }
+  for (int i = lane; i < n * 3; i += 64) Y[i] = rhs[i];
+  __syncthreads();
+  bool bad;
+  int replaced;
+  fit_band_solve<3>(n, k, B, Y, lane, &bad, &replaced);
+  FitSmoothRow row;
+  row.status = bad ? 1 : 0; row.replaced_pivots = replaced; row.lambda = lambda;
+  if (bad) {      // this lambda's control points are not written; its sums are not numbers
+    row.rss = row.penalty = row.rms = __longlong_as_double(0x7ff8000000000000ll);
+  } else {
+    double* out = a.ctrl_all + size_t(l) * n * 6 + 3 * g;
+    for (int i = lane; i < n * 3; i += 64) out[(i / 3) * 6 + i % 3] = Y[i];
+    // c' P c over the three channels: row a of P times c, then c_a times that
+    double pen = 0.0;
+    for (int r = lane; r < n; r += 64) {
+      double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+      for (int b = max(0, r - (k - 1)); b <= min(n - 1, r + (k - 1)); ++b) {
+        const double p = b <= r ? a.P[size_t(r) * k + (r - b)] : a.P[size_t(b) * k + (b - r)];
+        p0 += p * Y[b * 3]; p1 += p * Y[b * 3 + 1]; p2 += p * Y[b * 3 + 2];
+      }
+      pen += Y[r * 3] * p0 + Y[r * 3 + 1] * p1 + Y[r * 3 + 2] * p2;
+    }
+    row.penalty = fit_wave_sum(pen);
+    // the weighted residual sum of squares: lanes stride over the samples, then one fixed shuffle tree
+    double rss = 0.0;
+    for (int j = lane; j < a.n; j += 64) {
+      const double w = a.weights ? a.weights[size_t(j) * 2 + g] : 1.0;
+      if (w == 0.0) continue;
+      const int s = a.seg[j];
+      double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+      for (int i = 0; i < k; ++i) {
+        const double wi = a.W[size_t(j) * k + i];
+        r0 += wi * Y[(s + i) * 3]; r1 += wi * Y[(s + i) * 3 + 1]; r2 += wi * Y[(s + i) * 3 + 2];
+      }
+      const double* d = a.data + size_t(j) * 6 + 3 * g;
+      r0 -= d[0]; r1 -= d[1]; r2 -= d[2];
+      rss += w * (r0 * r0 + r1 * r1 + r2 * r2);
+    }
+    row.rss = fit_wave_sum(rss);
+    row.rms = sqrt(row.rss / (3.0 * double(g == 0 ? a.n_used_rot : a.n_used_pos)));
+  }
+  if (lane == 0) a.rows[size_t(g) * a.n_lambda + l] = row;
 }
 
 size_t fit_solve_lds_bytes(int n_ctrl, int k) { return (size_t(n_ctrl) * k + size_t(n_ctrl) * 6) * sizeof(double); }
@@ -128,6 +282,24 @@ hipError_t launch_fit_spline(int device, const FitArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(fit_normal_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.seg_ptr, a.band,
                      a.rhs);
   hipLaunchKernelGGL(fit_solve_kernel, dim3(1), dim3(64), fit_solve_lds_bytes(a.n_ctrl, a.k), s, a.n_ctrl, a.k, a.band, a.rhs, a.ctrl, a.status);
+  return hipGetLastError();
+}
+
+size_t fit_solve_smooth_lds_bytes(int n_ctrl, int k) { return (size_t(n_ctrl) * k + size_t(n_ctrl) * 3) * sizeof(double); }
+
+hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s) {
+  const size_t lds = fit_solve_smooth_lds_bytes(a.n_ctrl, a.k);
+  const hipError_t e = raise_lds_limit(device, fit_solve_smooth_kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fit_weights_kernel, dim3(unsigned((a.n + 255) / 256)), dim3(256), 0, s, a.n, a.k, a.stamps, a.seg, a.knots, a.basis, a.W);
+  hipLaunchKernelGGL(fit_penalty_kernel, dim3((a.n_ctrl * a.k + 255) / 256), dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.derivative, a.knots, a.basis,
+                     a.P);
+  const dim3 grid((a.n_ctrl * (a.k + 3) + 255) / 256, 2);
+  if (a.weights)
+    hipLaunchKernelGGL(fit_normal_weighted_kernel<true>, grid, dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.weights, a.seg_ptr, a.band, a.rhs);
+  else
+    hipLaunchKernelGGL(fit_normal_weighted_kernel<false>, grid, dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.weights, a.seg_ptr, a.band, a.rhs);
+  hipLaunchKernelGGL(fit_solve_smooth_kernel, dim3(2, a.n_lambda), dim3(64), lds, s, a);
   return hipGetLastError();
 }
 

@@ -134,6 +134,19 @@ struct FitArgs {
 };
 size_t fit_solve_lds_bytes(int n_ctrl, int k);      // the solve works in LDS: the caller refuses what does not fit
 hipError_t launch_fit_spline(int device, const FitArgs& a, hipStream_t s);
+// The smoothing fit: two channel groups (0: axis-angle, 1: position), each with its own weights column, normal matrix and
+// lambda grid; P is the roughness penalty's band (shared). band [2][n_ctrl][k], rhs [2][n_ctrl][3], ctrl_all [n_lambda][n_ctrl][6],
+// rows [2][n_lambda] (the layout of calico_spline_fit_row). weights: [n][2] or null (all 1).
+constexpr int kFitMaxLambdas = 32;
+struct FitSmoothRow { int status, replaced_pivots; double lambda, rss, penalty, rms; };
+struct FitSmoothArgs {
+  int n, k, n_ctrl, n_seg, derivative, relative, n_lambda, n_used_rot, n_used_pos;
+  double lambda_rot[kFitMaxLambdas], lambda_pos[kFitMaxLambdas];
+  const double* stamps; const int* seg; const int* seg_ptr; const double* knots; const double* basis; const double* data; const double* weights;
+  double* W; double* P; double* band; double* rhs; double* ctrl_all; FitSmoothRow* rows;
+};
+size_t fit_solve_smooth_lds_bytes(int n_ctrl, int k);      // [band | 3 rhs] of one group
+hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s);
 
 // ---- camera model maps (camera_kernels.hip): free pixels and points, no residual blocks -----------------------------------
 // All pointers are device memory; `k` (the intrinsics) and, in the rig frame, q_rc are read through wave-uniform addresses. The

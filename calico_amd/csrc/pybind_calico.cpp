@@ -161,6 +161,31 @@ calico_imu_alignment_options imu_alignment_options(const py::object& options) {
   }
   return o;
 }
+// None, or a dict of calico_spline_fit_options fields; lambda_rot / lambda_pos: a number or a sequence (n_lambda follows its length)
+calico_spline_fit_options spline_fit_options(const py::object& options) {
+  calico_spline_fit_options o;
+  calico_default_spline_fit_options(&o);
+  if (options.is_none()) return o;
+  bool n_given = false;
+  for (auto kv : py::cast<py::dict>(options)) {
+    const std::string name = py::cast<std::string>(kv.first);
+    if (name == "derivative") o.derivative = py::cast<int>(kv.second);
+    else if (name == "relative") o.relative = py::cast<int>(kv.second);
+    else if (name == "n_lambda") { o.n_lambda = py::cast<int>(kv.second); n_given = true; }
+    else if (name == "target_rms_rot") o.target_rms_rot = py::cast<double>(kv.second);
+    else if (name == "target_rms_pos") o.target_rms_pos = py::cast<double>(kv.second);
+    else if (name == "lambda_rot" || name == "lambda_pos") {
+      std::vector<double> grid;
+      if (py::isinstance<py::float_>(kv.second) || py::isinstance<py::int_>(kv.second)) grid.push_back(py::cast<double>(kv.second));
+      else for (auto v : py::cast<py::sequence>(kv.second)) grid.push_back(py::cast<double>(v));
+      if (grid.empty() || grid.size() > CALICO_FIT_MAX_LAMBDAS) throw py::value_error(name + " must have 1 to 32 entries");
+      double* dst = name == "lambda_rot" ? o.lambda_rot : o.lambda_pos;
+      for (size_t i = 0; i < CALICO_FIT_MAX_LAMBDAS; ++i) dst[i] = i < grid.size() ? grid[i] : 0.0;
+      if (!n_given) o.n_lambda = int(grid.size());
+    } else throw py::type_error("no spline fit option '" + name + "'");
+  }
+  return o;
+}
 std::vector<uint8_t> to_mask(const py::object& o) {
   std::vector<uint8_t> mask;
   if (!o.is_none())
@@ -534,6 +559,46 @@ PYBIND11_MODULE(_calico, m) {
           },
           py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
           py::arg("spline_order") = Trajectory::kDefaultSplineOrder)
+      // The smoothing fit (calico_fit_spline_smooth). options: None or a dict of calico_spline_fit_options fields; weights: None or
+      // one [rotation, position] pair per pose in time order. Returns a dict: status, chosen, n_used (one entry per group) and
+      // rows ([group][lambda] dicts: status, replaced_pivots, lambda, rss, penalty, rms).
+      .def(
+          "FitSplineSmooth",
+          [](Trajectory& self, const std::map<double, Pose3d>& poses, double knot_frequency, int spline_order, const py::object& options,
+             const py::object& weights) {
+            const calico_spline_fit_options o = spline_fit_options(options);
+            std::vector<std::array<double, 2>> w;
+            if (!weights.is_none())
+              for (auto row : py::cast<py::sequence>(weights)) {
+                const auto pair = py::cast<std::vector<double>>(row);
+                if (pair.size() != 2) throw py::value_error("weights: one [rotation, position] pair per pose");
+                w.push_back({pair[0], pair[1]});
+              }
+            auto res = self.FitSplineSmooth(poses, knot_frequency, spline_order, o, w);
+            raise_if_error(res.status());
+            const calico_spline_fit_summary& sm = res.value().summary;
+            py::dict out;
+            out["status"] = py::make_tuple(sm.status[0], sm.status[1]);
+            out["chosen"] = py::make_tuple(sm.chosen[0], sm.chosen[1]);
+            out["n_used"] = py::make_tuple(sm.n_used[0], sm.n_used[1]);
+            py::list groups;
+            const size_t nl = res.value().rows.size() / 2;
+            for (size_t g = 0; g < 2; ++g) {
+              py::list rows;
+              for (size_t l = 0; l < nl; ++l) {
+                const calico_spline_fit_row& r = res.value().rows[g * nl + l];
+                py::dict d;
+                d["status"] = r.status; d["replaced_pivots"] = r.replaced_pivots; d["lambda"] = r.lambda; d["rss"] = r.rss;
+                d["penalty"] = r.penalty; d["rms"] = r.rms;
+                rows.append(d);
+              }
+              groups.append(rows);
+            }
+            out["rows"] = groups;
+            return out;
+          },
+          py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
+          py::arg("spline_order") = Trajectory::kDefaultSplineOrder, py::arg("options") = py::none(), py::arg("weights") = py::none())
       .def("Interpolate", [](const Trajectory& self, const std::vector<double>& stamps) {
         auto poses = self.Interpolate(stamps);
         raise_if_error(poses.status());

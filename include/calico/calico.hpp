@@ -547,21 +547,7 @@ class BSpline6 {
     if (time.size() != data.size()) return InvalidArgumentError("Data and time vectors are not the same size.");
     if (order < 2) return InvalidArgumentError("Spline order must be greater than 2. Got " + std::to_string(order));
     if (knot_frequency <= 0) return InvalidArgumentError("Knot frequency must be greater than 0.");
-    order_ = order;
-    const int deg = order - 1;
-    const double duration = time.back() - time.front(), dt = 1.0 / knot_frequency;
-    const int nvalid = 1 + int(std::ceil(duration * knot_frequency)), nk = nvalid + 2 * deg;
-    knots_.assign(size_t(nk), 0.0); valid_knots_.assign(size_t(nvalid), 0.0);
-    for (int i = -deg; i < nk - deg; ++i) {
-      knots_[size_t(i + deg)] = time.front() + dt * i;
-      if (i > -1 && i < nvalid) valid_knots_[size_t(i)] = knots_[size_t(i + deg)];
-    }
-    const int nseg = nvalid - 1;
-    basis_.assign(size_t(nseg) * order * order, 0.0);
-    for (int s = 0; s < nseg; ++s) {
-      const std::vector<double> M = Basis(order, s + deg);
-      std::copy(M.begin(), M.end(), basis_.begin() + size_t(s) * order * order);
-    }
+    const int nk = BuildKnots(time, order, knot_frequency);
     // least-squares control points on the device (calico_fit_spline: banded normal equations + banded Cholesky; the
     // reference factors the dense normal equations by column-pivoted QR, bspline.hpp:287-293)
     const int ncp = nk - order;
@@ -579,6 +565,58 @@ class BSpline6 {
       return UnimplementedError("spline fit: " + std::to_string(ncp) + " control points are too many for the on-device solve; order " +
                                 std::to_string(order) + " fits at most " + std::to_string(156 * 1024 / ((order + 6) * 8)));
     if (rc != CALICO_OK) return InternalError("spline fit failed on the device");
+    ctrl_.assign(size_t(ncp), {});
+    for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
+    return OkStatus();
+  }
+  /// What a smoothing fit found: the summary (per group status, chosen lambda, samples used) and the row of every (group, lambda).
+  struct SmoothFit {
+    calico_spline_fit_summary summary{};
+    std::vector<calico_spline_fit_row> rows;      // 2 x n_lambda, group-major
+  };
+#ifdef CALICO_TEST_HOOKS
+  /// Test builds only, as fit_solver(): the solve behind FitToDataSmooth (calico_fit_spline_smooth without its device argument).
+  using SmoothFitSolver = int32_t (*)(int32_t order, int32_t n_knots, const double* knots, const double* basis, int64_t n, const double* stamps,
+                                      const double* data6, const double* weights, const calico_spline_fit_options* options, double* ctrl_out,
+                                      double* ctrl_all_out, calico_spline_fit_row* rows_out, calico_spline_fit_summary* summary);
+  static SmoothFitSolver& smooth_fit_solver() {
+    static SmoothFitSolver solver = nullptr;
+    return solver;
+  }
+#endif
+  /// The smoothing (penalised) fit on the knot vector and basis of FitToData: calico_fit_spline_smooth on device 0. weights: one
+  /// [rotation, position] pair per sample, or empty (all 1). The control points are each group's chosen lambda's.
+  Status FitToDataSmooth(const std::vector<double>& time, const std::vector<std::array<double, 6>>& data, int order, double knot_frequency,
+                         const calico_spline_fit_options& options, const std::vector<std::array<double, 2>>& weights, SmoothFit* fit = nullptr) {
+    if (time.empty()) return InvalidArgumentError("Attempted to fit data on empty time vector.");
+    if (data.empty()) return InvalidArgumentError("Attempted to fit on empty data.");
+    if (time.size() != data.size()) return InvalidArgumentError("Data and time vectors are not the same size.");
+    if (!weights.empty() && weights.size() != time.size()) return InvalidArgumentError("Weights and time vectors are not the same size.");
+    if (order < 2) return InvalidArgumentError("Spline order must be greater than 2. Got " + std::to_string(order));
+    if (knot_frequency <= 0) return InvalidArgumentError("Knot frequency must be greater than 0.");
+    const int nk = BuildKnots(time, order, knot_frequency), ncp = nk - order;
+    const int64_t nd = int64_t(time.size());
+    std::vector<double> flat(size_t(nd) * 6), w(weights.size() * 2), ctrl(size_t(ncp) * 6);
+    for (int64_t j = 0; j < nd; ++j) for (int c = 0; c < 6; ++c) flat[size_t(j) * 6 + c] = data[size_t(j)][size_t(c)];
+    for (size_t j = 0; j < weights.size(); ++j) { w[j * 2] = weights[j][0]; w[j * 2 + 1] = weights[j][1]; }
+    SmoothFit found;
+    found.rows.assign(size_t(2) * size_t(std::min(std::max(options.n_lambda, 1), CALICO_FIT_MAX_LAMBDAS)), calico_spline_fit_row{});
+    const double* wp = w.empty() ? nullptr : w.data();
+#ifdef CALICO_TEST_HOOKS
+    const int32_t rc = smooth_fit_solver()
+        ? smooth_fit_solver()(order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, ctrl.data(), nullptr, found.rows.data(), &found.summary)
+        : calico_fit_spline_smooth(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, ctrl.data(), nullptr, found.rows.data(), &found.summary);
+#else
+    const int32_t rc = calico_fit_spline_smooth(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, ctrl.data(),
+                                                nullptr, found.rows.data(), &found.summary);
+#endif
+    if (fit) *fit = found;
+    const char* why = calico_last_error(nullptr);
+    if (rc == CALICO_INVALID_ARGUMENT) return InvalidArgumentError(std::string("smoothing spline fit: ") + (why ? why : "invalid argument"));
+    if (rc == CALICO_UNIMPLEMENTED)      // the on-chip solve holds one group's [band | 3 rhs]: n_ctrl (order + 3) doubles in 156 KiB
+      return UnimplementedError("smoothing spline fit: " + std::to_string(ncp) + " control points are too many for the on-device solve; order " +
+                                std::to_string(order) + " fits at most " + std::to_string(156 * 1024 / ((order + 3) * 8)));
+    if (rc != CALICO_OK) return InternalError("smoothing spline fit failed on the device");
     ctrl_.assign(size_t(ncp), {});
     for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
     return OkStatus();
@@ -601,6 +639,25 @@ class BSpline6 {
     return OkStatus();
   }
  private:
+  /// bspline.hpp:163-189: the knot vector over [time.front(), time.back()] and the basis matrix of every segment. Returns n_knots.
+  int BuildKnots(const std::vector<double>& time, int order, double knot_frequency) {
+    order_ = order;
+    const int deg = order - 1;
+    const double duration = time.back() - time.front(), dt = 1.0 / knot_frequency;
+    const int nvalid = 1 + int(std::ceil(duration * knot_frequency)), nk = nvalid + 2 * deg;
+    knots_.assign(size_t(nk), 0.0); valid_knots_.assign(size_t(nvalid), 0.0);
+    for (int i = -deg; i < nk - deg; ++i) {
+      knots_[size_t(i + deg)] = time.front() + dt * i;
+      if (i > -1 && i < nvalid) valid_knots_[size_t(i)] = knots_[size_t(i + deg)];
+    }
+    const int nseg = nvalid - 1;
+    basis_.assign(size_t(nseg) * order * order, 0.0);
+    for (int s = 0; s < nseg; ++s) {
+      const std::vector<double> M = Basis(order, s + deg);
+      std::copy(M.begin(), M.end(), basis_.begin() + size_t(s) * order * order);
+    }
+    return nk;
+  }
   std::vector<double> Basis(int k, int i) const {  // bspline.hpp:191-244
     if (k == 1) return {1.0};
     const std::vector<double> P = Basis(k - 1, i);
@@ -636,6 +693,36 @@ class Trajectory {
     poses_ = poses_world_sensorrig;
     std::vector<double> stamps;
     std::vector<std::array<double, 6>> data;
+    PosesToData(&stamps, &data);
+    return spline_.FitToData(stamps, data, spline_order, knot_frequency);
+  }
+  /// FitSpline with the smoothing fit (calico_fit_spline_smooth): the same axis-angle conversion and phase unwrapping, then the
+  /// penalised fit with `options` (calico_default_spline_fit_options for the defaults) and one [rotation, position] weight pair
+  /// per pose in time order, or none (all 1). Poses that are unknown are simply left out: the penalty carries the spline across.
+  StatusOr<BSpline6::SmoothFit> FitSplineSmooth(const std::map<double, Pose3d>& poses_world_sensorrig, double knot_frequency,
+                                                int spline_order, const calico_spline_fit_options& options,
+                                                const std::vector<std::array<double, 2>>& weights = {}) {
+    poses_ = poses_world_sensorrig;
+    std::vector<double> stamps;
+    std::vector<std::array<double, 6>> data;
+    PosesToData(&stamps, &data);
+    BSpline6::SmoothFit fit;
+    const Status st = spline_.FitToDataSmooth(stamps, data, spline_order, knot_frequency, options, weights, &fit);
+    if (!st.ok()) return st;
+    return fit;
+  }
+  int AddParametersToProblem(Problem& problem) {  // trajectory.cpp:51 (+ the evaluation tables of :63-79)
+    const int n = spline_.AddParametersToProblem(problem);
+    std::vector<double*> ctrl;
+    for (auto& c : spline_.control_points()) ctrl.push_back(c.data());
+    problem.SetSpline(spline_.GetSplineOrder(), spline_.knots(), spline_.basis_matrices(), ctrl);
+    return n;
+  }
+  const BSpline6& spline() const { return spline_; }
+  BSpline6& spline() { return spline_; }
+ private:
+  /// trajectory.cpp:24-46: poses_ in time order as [unwrapped axis-angle; position]
+  void PosesToData(std::vector<double>* stamps, std::vector<std::array<double, 6>>* data) const {
     std::array<double, 3> prev{};
     bool first = true;
     for (const auto& [stamp, T] : poses_) {  // std::map iterates sorted (trajectory.cpp:24 sorts)
@@ -654,20 +741,11 @@ class Trajectory {
         }
       }
       prev = phi; first = false;
-      stamps.push_back(stamp);
-      data.push_back({phi[0], phi[1], phi[2], T.translation()[0], T.translation()[1], T.translation()[2]});
+      stamps->push_back(stamp);
+      data->push_back({phi[0], phi[1], phi[2], T.translation()[0], T.translation()[1], T.translation()[2]});
     }
-    return spline_.FitToData(stamps, data, spline_order, knot_frequency);
   }
-  int AddParametersToProblem(Problem& problem) {  // trajectory.cpp:51 (+ the evaluation tables of :63-79)
-    const int n = spline_.AddParametersToProblem(problem);
-    std::vector<double*> ctrl;
-    for (auto& c : spline_.control_points()) ctrl.push_back(c.data());
-    problem.SetSpline(spline_.GetSplineOrder(), spline_.knots(), spline_.basis_matrices(), ctrl);
-    return n;
-  }
-  const BSpline6& spline() const { return spline_; }
-  BSpline6& spline() { return spline_; }
+ public:
   /// trajectory.h:93-101
   static Pose3d VectorToPose3(const double v[6]) {
     const cal::Q4 q = cal::angle_axis_to_quat(cal::mk(v[0], v[1], v[2]));

@@ -281,6 +281,65 @@ int32_t calico_get_residuals(calico_problem* p, int32_t sensor_id, double* out,
 int32_t calico_fit_spline(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
                           int64_t n, const double* stamps, const double* data6, double* ctrl_out);
 
+/* The smoothing (penalised) spline fit: per channel group g (0: axis-angle, channels 0..2; 1: position, channels 3..5)
+ *   min_C  sum_j w_jg |X_j C - d_j|^2  +  lambda_g  integral |s^(m)(t)|^2 dt   over the valid knots,
+ * for a whole grid of lambda in one launch (one workgroup per group and lambda). The penalty matrix P -- the Gram matrix of the
+ * m-th derivatives of the basis functions, closed form per segment -- has the band of X^T W X, so each candidate is the banded
+ * Cholesky of calico_fit_spline on A = X^T W X + lambda P, with the same ridge (1e-15 mean_diag of A) and the same pivot rule.
+ * What the samples leave open (a gap longer than the spline's support, one sample per segment, a ragged end) the penalty
+ * decides: with lambda > 0 and m <= the number of distinct samples, A is positive definite and no pivot is replaced.
+ *   weights  n x 2 [rotation, position], >= 0 and finite, or NULL (all 1). A sample of weight 0 in a group is skipped for that
+ *            group: its data are not read. Each group needs one sample of positive weight.
+ *   lambda   n_lambda values per group, >= 0 and strictly ascending; with `relative` in units of trace(X^T W X) / trace(P) of
+ *            the group (taken on the device), so that 1e-3 means the same on every trajectory; otherwise absolute (data
+ *            units^2 s^(2m-1)). lambda = 0 is the plain weighted fit; with weights NULL, n_lambda 1 and both lambda 0, ctrl_out
+ *            has calico_fit_spline's bits.
+ *   choice   target_rms 0: the first lambda of the grid. target_rms > 0: the largest lambda whose weighted RMS is <= the
+ *            target (discrepancy principle); if none is, CALICO_FIT_TARGET_NOT_MET and the smallest lambda. A lambda whose
+ *            factorisation met a pivot that is not finite is never chosen and its control points are not written (its
+ *            row's rss, penalty and rms are NaN); if a group has no other, the call returns kInternal.
+ * ctrl_out (n_ctrl x 6) receives each group's chosen lambda; ctrl_all_out (n_lambda x n_ctrl x 6, may be NULL) every lambda's;
+ * rows_out (2 x n_lambda, group-major, may be NULL) and summary what was found. Bit-reproducible: fixed-order sums, no atomics.
+ * kInvalidArgument as for calico_fit_spline, and for a weight, lambda or target that is negative or not finite, a grid that is
+ * not strictly ascending, n_lambda outside [1, CALICO_FIT_MAX_LAMBDAS], derivative outside [1, min(3, order - 1)], a NULL
+ * summary or ctrl_out. kUnimplemented, outputs untouched, when one group's [band | 3 rhs] does not fit the on-chip solve
+ * (n_ctrl (order + 3) 8 bytes > 156 KiB: more than 2218 control points at order 6) or n exceeds INT32_MAX. Needs no problem handle. */
+#define CALICO_FIT_MAX_LAMBDAS 32
+#define CALICO_FIT_OK 0
+#define CALICO_FIT_NOT_POSITIVE_DEFINITE 1   /* a pivot was not finite: this lambda's control points are not written and never chosen */
+#define CALICO_FIT_TARGET_NOT_MET 2          /* group status only: no lambda of the grid reached target_rms; the smallest lambda was taken */
+typedef struct {
+  int32_t derivative;       /* 2: m, the penalised derivative; 1 <= m <= min(3, order - 1) */
+  int32_t relative;         /* 1: lambdas are multiples of trace(X^T W X) / trace(P) of their group; 0: absolute */
+  int32_t n_lambda;         /* 1; at most CALICO_FIT_MAX_LAMBDAS */
+  double lambda_rot[CALICO_FIT_MAX_LAMBDAS];   /* {1e-3}; >= 0, strictly ascending */
+  double lambda_pos[CALICO_FIT_MAX_LAMBDAS];   /* {1e-3} */
+  double target_rms_rot;    /* 0: take lambda_rot[0]. > 0: the largest lambda of the grid whose weighted RMS <= target */
+  double target_rms_pos;
+} calico_spline_fit_options;
+typedef struct {            /* one per (group, lambda) */
+  int32_t status;           /* CALICO_FIT_OK or CALICO_FIT_NOT_POSITIVE_DEFINITE */
+  int32_t replaced_pivots;  /* pivots the 1e-13 rule replaced (0 on a well-posed penalised fit) */
+  double lambda;            /* the absolute lambda that was used */
+  double rss;               /* sum_j w_j |X_j C - d_j|^2 over the group's three channels */
+  double penalty;           /* sum over the channels of c^T P c */
+  double rms;               /* sqrt(rss / (3 n_used)), n_used = samples of weight > 0 */
+} calico_spline_fit_row;
+typedef struct {
+  int32_t status[2];        /* per group: CALICO_FIT_OK, CALICO_FIT_NOT_POSITIVE_DEFINITE (no usable lambda) or CALICO_FIT_TARGET_NOT_MET */
+  int32_t chosen[2];        /* index into the grid, -1: none */
+  int64_t n_used[2];
+} calico_spline_fit_summary;
+void calico_default_spline_fit_options(calico_spline_fit_options* o);
+int32_t calico_fit_spline_smooth(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                                 int64_t n, const double* stamps, const double* data6,
+                                 const double* weights /* n x 2: [rotation, position], or NULL = 1 */,
+                                 const calico_spline_fit_options* o /* NULL = defaults */,
+                                 double* ctrl_out /* n_ctrl x 6: the chosen lambda of each group */,
+                                 double* ctrl_all_out /* n_lambda x n_ctrl x 6, may be NULL */,
+                                 calico_spline_fit_row* rows_out /* 2 x n_lambda, may be NULL */,
+                                 calico_spline_fit_summary* summary);
+
 /* Outlier tags (Camera::MarkOutliersById / ClearOutliers, camera.cpp:281-301; outlier_ids_, camera.h:185): tagged
  * observations stay registered but are left out of the problem, as AddResidualsToProblem does (camera.cpp:121-124) --
  * no residual block, no residual, not counted in the summary. `is_outlier` has one byte per observation of the
