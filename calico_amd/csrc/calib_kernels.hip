@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
 #pragma unroll 1
   for (int i = 0; i < a.K; ++i) finite = finite && __builtin_isfinite(c->k[nxt][i]);
   const bool kept = lost == 0.0 && finite && __builtin_isfinite(cand);
-  int done = 0, status = c->status, new_cur = cur, iterations = c->iterations;
+  int done = 0, status = c->status, new_cur = cur, iterations = c->iterations, accepted = c->accepted;
   double lambda = c->lambda, initial = c->initial_cost;
   if (c->first != 0) {
     if (!kept || valid < 1.0) { status = CALICO_CALIB_DEGENERATE; done = 1; }
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
   } else {
     const bool small = fmax(step, c->step_k) < a.step_tolerance;
     const LmVerdict v = lm_rule(kept, common, current, noise, small, lambda);
-    if (v.accept) new_cur = nxt;
+    if (v.accept) { new_cur = nxt; accepted = 1; }
     lambda = v.lambda;
     if (v.converged) { status = CALICO_CALIB_OK; done = 1; }
   }
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
   if (done == 0) ++iterations;
   if (lane == 0) {
     c->done = done; c->status = status; c->cur = new_cur; c->first = 0; c->iterations = iterations; c->lambda = lambda;
-    c->initial_cost = initial;
+    c->initial_cost = initial; c->accepted = accepted;
   }
 }
 
@@ -424,6 +424,9 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
   ok = __all(ok) != 0;
   if (lane == 0) {
     c->final_ok = ok ? 1 : 0; c->final_cost = cost; c->rms = rms; c->frames_used = int(frames); c->pairs_used = (long long)valid;
+    // no step was accepted: the point kept is the start, and its cost is ONE number -- this sum, not the decision's sum of the
+    // same terms in another order, which can differ from it in the last bit and would read as a decrease
+    if (c->accepted == 0) c->initial_cost = cost;
   }
 }
 

@@ -210,6 +210,7 @@ struct CalibControl {
   int iterations;
   int frames_used;
   int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
+  int accepted;                 // a step has been accepted: the point kept is not the start
   long long pairs_used;
   double lambda, step_k;        // step_k: max |dk_i| / max(1, |k_i|) of the step the candidate was made with
   double initial_cost, final_cost, rms;
@@ -258,6 +259,7 @@ struct RigControl {
   int iterations;
   int frames_used;
   int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
+  int accepted;                 // a step has been accepted: the point kept is not the start
   long long views_used, pairs_used;
   double lambda, step_x;        // step_x: the size of the extrinsics' step the candidate was made with
   double initial_cost, final_cost, rms;

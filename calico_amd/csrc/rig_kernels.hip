@@ -254,6 +254,7 @@ __global__ __launch_bounds__(64) void rig_decide_kernel(RigArgs a) {
     c->done = s.outcome != kLmRunning ? 1 : 0; c->status = status; c->cur = s.accept ? nxt : cur; c->first = 0;
     c->iterations = s.iterations; c->lambda = s.lambda;
     if (first) c->initial_cost = cand;
+    else if (s.accept) c->accepted = 1;
   }
 }
 
@@ -488,6 +489,9 @@ __global__ __launch_bounds__(kRigParts * kRigChunk) void rig_reduce_kernel(RigAr
   if (lane == 0) {
     c->final_ok = ok ? 1 : 0; c->final_cost = cost; c->rms = rms; c->frames_used = int(frames); c->views_used = (long long)views;
     c->pairs_used = (long long)valid;
+    // no step was accepted: the point kept is the start, and its cost is ONE number -- this sum, not the decision's sum of the
+    // same terms in another order, which can differ from it in the last bit and would read as a decrease
+    if (c->accepted == 0) c->initial_cost = cost;
   }
 }
 

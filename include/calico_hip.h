@@ -719,7 +719,7 @@ typedef struct {
   int32_t status;           /* CALICO_CALIB_* */
   int32_t iterations;       /* steps tried */
   double initial_cost;      /* Sum rho at the start, over the usable frames */
-  double final_cost;
+  double final_cost;        /* == initial_cost, bit for bit, where no step was accepted (the start is returned) */
   double rms;               /* sqrt(Sum |residual|^2 / pairs_used) in pixels, no loss applied */
   int32_t frames_used;
   int64_t pairs_used;
@@ -812,7 +812,7 @@ typedef struct {
   int32_t status;             /* CALICO_RIG_* */
   int32_t iterations;         /* steps tried */
   double initial_cost;        /* Sum rho at the start, over the views that take part */
-  double final_cost;
+  double final_cost;          /* == initial_cost, bit for bit, where no step was accepted (the start is returned) */
   double rms;                 /* sqrt(Sum |residual|^2 / pairs_used) in pixels, no loss applied */
   int32_t cameras_used;       /* the reference camera and the cameras connected to it */
   int32_t frames_used;

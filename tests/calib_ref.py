@@ -31,6 +31,11 @@ FLOOR = {1: 2.4e-12, 2: 3.3e-11, 3: 1.5e-10, 4: 1.9e-10, 5: 8.1e-12, 6: 2.7e-12,
 #   model 1: 3.4e-15   2: 3.2e-15   3: 2.0e-15   4: 3.6e-15   5: 2.4e-15   6: 4.0e-16   7: 1.4e-15
 REF_FREE = {1: 3.4e-15, 2: 3.2e-15, 3: 2.0e-15, 4: 3.6e-15, 5: 2.4e-15, 6: 4.0e-16, 7: 1.4e-15}
 
+# FLOOR_LONG[model]: FLOOR, measured the same way on resect_ref.long_fixture (137 frames of 12 pairs, 0.1 px noise) from
+# long_start (tests/test_calib_host.py::test_reference_floor_of_the_long_batch re-measures it). Measured:
+#   model 1: 6.2e-10   6: 5.9e-12      (6 and 5 accepted steps)
+FLOOR_LONG = {1: 6.2e-10, 6: 5.9e-12}
+
 
 def frame_system(model, k, R, t, pts, pix, huber=0.0, h=H, free=None):
     """(A 6x6, B 6xK, C KxK, g_pose, g_k, e, ok) of one frame: J by central differences in [d_rot, t | k]; the columns of an
@@ -213,7 +218,17 @@ def start_intrinsics(model):
 def standard_start(model, noise):
     """(k0, q0 (20, 4), t0 (20, 3)) of the standard start for resect_ref.fixture(model, noise): k0 as above, the poses from
     resect_ref.refine at k0, started from the truth perturbed by 0.02 N(0, 1). Read-only arrays."""
-    _, off, px, pt, poses = rr.fixture(model, noise)
+    return start_of(rr.fixture(model, noise), model)
+
+
+@functools.lru_cache(maxsize=None)
+def long_start(model, noise):
+    """The standard start of resect_ref.long_fixture(model, noise): (k0, q0 (137, 4), t0 (137, 3))."""
+    return start_of(rr.long_fixture(model, noise), model)
+
+
+def start_of(fixture, model):
+    _, off, px, pt, poses = fixture
     k0 = start_intrinsics(model)
     rng = np.random.default_rng(4321 + model)
     q0, t0 = [], []
@@ -232,3 +247,84 @@ def standard_start(model, noise):
 
 def start_poses(q0, t0):
     return [(rr.rot(q), np.asarray(t, float)) for q, t in zip(q0, t0)]
+
+
+FOV_W = 1e-3      # FieldOfView (model 5) below its w^2 < 1e-5 branch: the pixel does not depend on w there
+
+
+@functools.lru_cache(maxsize=None)
+def fov_fixture(noise=0.1):
+    """resect_ref.fixture's 20 frames for FieldOfView at w = FOV_W: (intrinsics, offsets, pixels, points, true poses)."""
+    model = 5
+    k = np.array(syn._TRUE_INTRINSICS[model], float)
+    k[3] = FOV_W
+    pts = syn.planar_points()
+    rng = np.random.default_rng(1234 + 50)
+    poses = rr.true_poses()
+    pix = []
+    for R, t in poses:
+        px, ok = rr.project(model, k, R, t, pts)
+        assert ok.all()
+        pix.append(px + noise * rng.standard_normal(px.shape))
+    off = np.arange(len(poses) + 1, dtype=np.int64) * len(pts)
+    px, pt = np.concatenate(pix), np.tile(pts, (len(poses), 1))
+    for a in (k, off, px, pt):
+        a.setflags(write=False)
+    return k, off, px, pt, poses
+
+
+@functools.lru_cache(maxsize=None)
+def fov_start():
+    """The standard start of fov_fixture() with w left at FOV_W: (k0, q0, t0)."""
+    k, off, px, pt, poses = fov_fixture()
+    k0 = np.array([k[0] * 1.01, k[1] + 3.0, k[2] - 2.0, FOV_W])
+    rng = np.random.default_rng(4321 + 50)
+    q0, t0 = [], []
+    for f, (R, t) in enumerate(poses):
+        s = slice(off[f], off[f + 1])
+        p = 0.02 * rng.standard_normal(6)
+        Rs, ts, _, _ = rr.refine(5, k0, rr.exp_so3(p[:3]) @ R, t + p[3:], pt[s], px[s])
+        q = rr.quat_of(Rs)
+        q0.append(q if q[3] >= 0 else -q)
+        t0.append(ts)
+    q0, t0 = np.array(q0), np.array(t0)
+    for a in (k0, q0, t0):
+        a.setflags(write=False)
+    return k0, q0, t0
+
+
+BOUNDARY_FRAME = 5
+BOUNDARY_FREE = (1, 1, 1, 0)      # alpha is held: the validity boundary z = -w d of the unified model stays where the case put it
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_fixture(kind):
+    """resect_ref.fixture's 20 frames under the unified model at alpha = 0.7, frame BOUNDARY_FRAME replaced by
+    resect_ref.boundary_case(kind) (37 pairs, the last one near the validity boundary). The start: k0 = the truth with
+    f x 1.01, cx + 3, cy - 2 and alpha as it is (constant: BOUNDARY_FREE); the frames as standard_start makes them, the boundary
+    frame at the case's start. Returns (k, off, px, pt, k0, q0, t0). Read-only arrays."""
+    k = rr.unified_intrinsics()
+    k0 = np.array([k[0] * 1.01, k[1] + 3.0, k[2] - 2.0, k[3]])
+    case = rr.boundary_case(kind, BOUNDARY_FRAME, 0.1, tuple(k0))
+    plane = syn.planar_points()
+    rng, rng_start = np.random.default_rng(1234 + 60), np.random.default_rng(4321 + 60)
+    px, pt, q0, t0 = [], [], [], []
+    for f, (R, t) in enumerate(rr.true_poses()):
+        if f == BOUNDARY_FRAME:
+            pix, pts, (Rs, ts) = case.pixels, case.points, case.start
+        else:
+            pix, ok = rr.project(6, k, R, t, plane)
+            assert ok.all()
+            pix, pts = pix + 0.1 * rng.standard_normal(pix.shape), plane
+            p = 0.02 * rng_start.standard_normal(6)
+            Rs, ts, _, _ = rr.refine(6, k0, rr.exp_so3(p[:3]) @ R, t + p[3:], pts, pix)
+        px.append(pix)
+        pt.append(pts)
+        q = rr.quat_of(Rs)
+        q0.append(q if q[3] >= 0 else -q)
+        t0.append(ts)
+    off = np.concatenate([[0], np.cumsum([len(a) for a in px])]).astype(np.int64)
+    out = (k, off, np.concatenate(px), np.concatenate(pt), k0, np.array(q0), np.array(t0))
+    for a in out:
+        a.setflags(write=False)
+    return out

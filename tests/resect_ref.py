@@ -7,6 +7,7 @@ camera-from-chart rotations), weights are rho' of Huber's loss (1, or scale / |e
 own last step -- the FLOOR -- bounds what its difference quotients can resolve; the optimality criterion the tests hold the
 device to is that the reference's weighted Gauss-Newton step AT THE DEVICE'S POSE is at most step_tolerance + 10 FLOOR.
 """
+import collections
 import functools
 
 import numpy as np
@@ -140,6 +141,110 @@ def fixture(model, noise, points="planar"):
     for a in (k, off, px, pt):
         a.setflags(write=False)
     return k, off, px, pt, poses
+
+
+LONG_FRAMES = 137      # more than 8 x 16 (the calibration's unrolled reduction) and 2 x 64 + 9 (its decision's strided sums)
+
+
+@functools.lru_cache(maxsize=None)
+def long_poses(n_frames, seed):
+    """n_frames seeded draws around true_poses(): pose f is true_poses()[f % 20] turned by 0.05 N(0, 1) rad and moved by
+    0.03 N(0, 1) m."""
+    base = true_poses()
+    rng = np.random.default_rng(seed)
+    out = []
+    for f in range(n_frames):
+        R, t = base[f % len(base)]
+        p = rng.standard_normal(6)
+        out.append((exp_so3(0.05 * p[:3]) @ R, t + 0.03 * p[3:]))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def long_fixture(model, noise, n_frames=LONG_FRAMES):
+    """As fixture(), for n_frames poses of long_poses() and the 12 chart points planar_points()[::3] per frame: every pair is
+    valid (asserted from the oracle). Read-only arrays."""
+    k = np.array(syn._TRUE_INTRINSICS[model], float)
+    pts = syn.planar_points()[::3]
+    rng = np.random.default_rng(5678 + model)
+    poses = long_poses(n_frames, 8765)
+    pix = []
+    for R, t in poses:
+        px, ok = project(model, k, R, t, pts)
+        assert ok.all()
+        pix.append(px + noise * rng.standard_normal(px.shape))
+    off = np.arange(len(poses) + 1, dtype=np.int64) * len(pts)
+    px, pt = np.concatenate(pix), np.tile(pts, (len(poses), 1))
+    for a in (k, off, px, pt):
+        a.setflags(write=False)
+    return k, off, px, pt, poses
+
+
+UNIFIED_ALPHA = 0.7      # the unified model (6) of the boundary cases: valid for z > -w d, w = (1 - alpha) / alpha; the pixel is finite there
+
+
+def unified_intrinsics():
+    k = np.array(syn._TRUE_INTRINSICS[6], float)
+    k[3] = UNIFIED_ALPHA
+    return k
+
+
+def axis_angle(P):
+    """The angle between a point in the camera frame and the optical axis."""
+    P = np.asarray(P, float)
+    return float(np.arccos(P[2] / np.linalg.norm(P)))
+
+
+def unified_boundary_angle():
+    return float(np.arccos(-(1 - UNIFIED_ALPHA) / UNIFIED_ALPHA))
+
+
+BoundaryCase = collections.namedtuple("BoundaryCase", "k points pixels start truth")
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_case(kind, frame=5, noise=0.1, k_start=None, displaced=100.0):
+    """One frame of the chart under the unified model at alpha = 0.7 with ONE extra chart point off the plane (the last pair),
+    near the model's validity boundary. truth: the pose the 36 planar pixels were made at (0.1 px noise); start: the truth
+    turned by 0.02 rad about the camera's y axis, which moves the extra point across the boundary.
+      "lost":    valid at the start, 0.3 degrees inside, pixel = its projection at the start; beyond the boundary at the truth
+      "invalid": 2 degrees beyond the boundary at the start and farther at the truth; its pixel is never read
+      "joins":   0.3 degrees beyond at the start, inside at the truth; pixel = its projection at the truth moved by `displaced` px
+    k_start (a tuple): the intrinsics the "lost" pixel is projected with, where the start's are not the truth's (the
+    calibration; alpha must be the truth's). Returns BoundaryCase(k, points (37, 3), pixels (37, 2), start (R, t), truth (R, t)).
+    Read-only arrays."""
+    k = unified_intrinsics()
+    Rt, tt = true_poses()[frame]
+    plane = syn.planar_points()
+    rng = np.random.default_rng(606 + frame)
+    px, ok = project(6, k, Rt, tt, plane)
+    assert ok.all()
+    px = px + noise * rng.standard_normal(px.shape)
+    off_deg, sign = {"lost": (-0.3, -1.0), "invalid": (2.0, -1.0), "joins": (0.3, 1.0)}[kind]
+    Rs = exp_so3([0.0, sign * 0.02, 0.0]) @ Rt
+    th = unified_boundary_angle() + np.deg2rad(off_deg)
+    Pc = 1.0 * np.array([np.sin(th), 0.0, np.cos(th)])      # in the camera frame at the start, 1 m away
+    extra = Rs.T @ (Pc - tt)
+    pts = np.vstack([plane, extra])
+    if kind == "joins":
+        e_px, e_ok = project(6, k, Rt, tt, extra[None])
+        e_px = e_px + [[displaced, 0.0]]
+    else:
+        e_px, e_ok = project(6, k if k_start is None else np.array(k_start, float), Rs, tt, extra[None])
+        if kind == "invalid":
+            e_px, e_ok = np.zeros((1, 2)), np.ones(1, bool)
+    assert e_ok.all()
+    pix = np.vstack([px, e_px])
+    for a in (k, pts, pix):
+        a.setflags(write=False)
+    return BoundaryCase(k, pts, pix, (Rs, np.array(tt, float)), (Rt, np.array(tt, float)))
+
+
+def behind(pose):
+    """The pose moved along the optical axis so that the chart (within 1 m of its origin) is behind the camera: no pair of a
+    pinhole model (1) projects from there."""
+    R, t = pose
+    return R, np.array([t[0], t[1], -abs(t[2]) - 1.0])
 
 
 def wide_angle(model):

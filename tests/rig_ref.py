@@ -24,10 +24,10 @@ H = 1e-6
 # (0.1 px noise, from the truth perturbed by 0.02 N(0, 1)); REF_FREE[fixture]: the reference's own distance to the truth on
 # noise-free data from the same start. tests/test_rig_host.py::test_reference_floor_and_noise_free_distance re-measures both on
 # every run and prints them; the figures below are its output (python -m pytest tests/test_rig_host.py -s -k floor).
-#   FLOOR     standard: 1.2e-13   chain: 1.8e-13   wide: 1.1e-13   long: 5.2e-13      (6 to 8 accepted steps)
-#   REF_FREE  standard: 4.5e-16   chain: 5.3e-16   wide: 1.4e-15   long: 5.8e-16
-FLOOR = {"standard": 1.2e-13, "chain": 1.8e-13, "wide": 1.1e-13, "long": 5.2e-13}
-REF_FREE = {"standard": 4.5e-16, "chain": 5.3e-16, "wide": 1.4e-15, "long": 5.8e-16}
+#   FLOOR     standard: 1.2e-13   chain: 1.8e-13   wide: 1.1e-13   long: 5.2e-13   many: 3.3e-13      (6 to 8 accepted steps)
+#   REF_FREE  standard: 4.5e-16   chain: 5.3e-16   wide: 1.4e-15   long: 5.8e-16   many: 7.0e-16
+FLOOR = {"standard": 1.2e-13, "chain": 1.8e-13, "wide": 1.1e-13, "long": 5.2e-13, "many": 3.3e-13}
+REF_FREE = {"standard": 4.5e-16, "chain": 5.3e-16, "wide": 1.4e-15, "long": 5.8e-16, "many": 7.0e-16}
 
 Rig = collections.namedtuple("Rig", "models ks n_frames view_camera view_frame view_offsets pixels points cams frames")
 
@@ -308,4 +308,47 @@ def long_views(noise):
     return _make((1, 3), _cams(STANDARD_CAMS[:2]), rr.true_poses()[::3][:6], syn.aprilgrid_points(), noise, 1357)
 
 
-FIXTURES = {"standard": standard, "chain": chain, "wide": wide, "long": long_views}
+@functools.lru_cache(maxsize=None)
+def many(noise):
+    """Two cameras (models 1 and 3), 70 frames of resect_ref.long_poses(), the 12 chart points planar_points()[::3]: 140 views,
+    more than two trips of the decision's sums over the views and more than one over the frames, and past the unrolled body of
+    the reduction (4 parts x 4)."""
+    return _make((1, 3), _cams(STANDARD_CAMS[:2]), rr.long_poses(70, 24680), syn.planar_points()[::3], noise, 97)
+
+
+FIXTURES = {"standard": standard, "chain": chain, "wide": wide, "long": long_views, "many": many}
+
+
+BOUNDARY_FRAME = 5
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_rig(kind):
+    """The standard rig with camera 0 (the reference camera, at the rig's origin) under the unified model at alpha = 0.7 and its
+    view of frame BOUNDARY_FRAME replaced by resect_ref.boundary_case(kind): 37 pairs, the last one near the validity boundary.
+    Returns (rig, start, the view's index): the start is perturbed_start at a quarter of its scale (from there the first step of the standard
+    fixture is accepted), the boundary frame at the case's start."""
+    case = rr.boundary_case(kind, BOUNDARY_FRAME, displaced=300.0)      # (300 px: rho above the drop of the 2160 pairs in common)
+    base = standard(0.1, models=(6, 3, 1))
+    v = int(np.flatnonzero((base.view_camera == 0) & (base.view_frame == BOUNDARY_FRAME))[0])
+    ks = [case.k] + list(base.ks[1:])
+    off, pix, pnt = [0], [], []
+    for u in range(len(base.view_camera)):
+        s = slice(base.view_offsets[u], base.view_offsets[u + 1])
+        px, pts = (case.pixels, case.points) if u == v else (base.pixels[s], base.points[s])
+        if base.view_camera[u] == 0 and u != v:      # (camera 0's other views: the same noise, alpha = 0.7)
+            clean, ok = rr.project(6, base.ks[0], *camera_from_chart(base.cams[0], base.frames[base.view_frame[u]]), pts)
+            mine, ok2 = rr.project(6, case.k, *camera_from_chart(base.cams[0], base.frames[base.view_frame[u]]), pts)
+            assert ok.all() and ok2.all()
+            px = mine + (px - clean)
+        off.append(off[-1] + len(px))
+        pix.append(px)
+        pnt.append(pts)
+    arrays = (np.array(off, np.int64), np.concatenate(pix), np.concatenate(pnt))
+    for a in arrays:
+        a.setflags(write=False)
+    rig = Rig(base.models, ks, base.n_frames, base.view_camera, base.view_frame, *arrays, base.cams, base.frames)
+    start = [a.copy() for a in perturbed_start(rig, scale=0.005)]
+    q = rr.quat_of(case.start[0])
+    start[2][BOUNDARY_FRAME], start[3][BOUNDARY_FRAME] = (q if q[3] >= 0 else -q), case.start[1]
+    return rig, tuple(start), v

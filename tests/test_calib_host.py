@@ -10,6 +10,9 @@ Measured here (seven models, resect_ref.fixture: 20 frames x 36 points, the stan
   the reference's own distance to the truth on noise-free data (s-scaled for the intrinsics, pose_distance for the poses):
     model 1: 3.4e-15   2: 3.2e-15   3: 2.0e-15   4: 3.6e-15   5: 2.4e-15   6: 4.0e-16   7: 1.4e-15
   accepted steps of the reference from the standard start: 5 to 12; rms at 0.1 px noise 0.132 to 0.138 px.
+  FLOOR_LONG (resect_ref.long_fixture: 137 frames x 12 points, long_start) -- model 1: 6.2e-10   6: 5.9e-12
+  the reference's first LM step from h = 2e-6 against h = 1e-6 differences, and the same step without lambda diag C:
+    model 1: 1.1e-11 / 9.8e-3   2: 4.9e-10 / 5.6e-2   4: 2.7e-11 / 3.2e-2
 The committed figures are this machine's. The floor is rounding noise, so another CPU's libm and BLAS move it: the test holds the
 re-measured values to twice the committed ones and prints them."""
 import ctypes as C
@@ -250,3 +253,74 @@ def test_reference_converges_from_initial_intrinsics_for_kannala_brandt():
     print("accepted steps", accepted, "last s", last, "distance between the two results", cr.intrinsics_distance(ka, kb), cr.poses_distance(pa, pb))
     assert converged
     assert max(cr.intrinsics_distance(ka, kb), cr.poses_distance(pa, pb)) <= 10 * cr.FLOOR[model]
+
+
+@pytest.mark.parametrize("model", (1, 6))
+def test_reference_floor_of_the_long_batch(model):
+    """calib_ref.FLOOR_LONG, re-measured as FLOOR is: the reference converges from long_start on the 137 frames of
+    resect_ref.long_fixture (every pair valid: the fixture asserts it) and six more undamped Gauss-Newton steps stay within
+    twice the committed figure."""
+    k, off, px, pt, poses = rr.long_fixture(model, 0.1)
+    assert len(poses) == 137 and len(px) == 1644
+    k0, q0, t0 = cr.long_start(model, 0.1)
+    kr, pr, last, accepted, converged = cr.refine(model, k0, cr.start_poses(q0, t0), off, pt, px)
+    assert converged and accepted <= 12, (accepted, last)
+    floor = 0.0
+    for _ in range(6):
+        dk, d, s = cr.gn(model, kr, pr, off, pt, px)
+        floor = max(floor, s)
+        kr, pr = cr.apply(kr, pr, dk, d)
+    print("model", model, "FLOOR_LONG", floor, "accepted steps", accepted)
+    assert floor <= 2 * cr.FLOOR_LONG[model]
+
+
+@pytest.mark.parametrize("model", (1, 2, 4))
+def test_a_step_without_lambda_diag_c_is_far_from_the_true_step(model):
+    """What keeps the step tests' bound (10 floors, tests/test_gpu_chart_steps.py) from hiding what they are for: from the
+    standard start the reference's first step is accepted, and the same step with the lambda diag C term left out of the reduced
+    system ends at least 1000 floors away (floor: the first step from h = 2e-6 against h = 1e-6 differences)."""
+    import lm_rule_ref as lm
+    k, off, px, pt, poses = rr.fixture(model, 0.1)
+    k0, q0, t0 = cr.standard_start(model, 0.1)
+    start = cr.start_poses(q0, t0)
+    true = lm.calib_loop(model, k0, start, off, pt, px, 1)
+    other = lm.calib_loop(model, k0, start, off, pt, px, 1, h=2e-6)
+    mutant = lm.calib_loop(model, k0, start, off, pt, px, 1, drop_diag_c=True)
+
+    def dist(a, b):
+        return max(cr.intrinsics_distance(a.point[0], b.point[0]), cr.poses_distance(a.point[1], b.point[1]))
+    floor, moved = dist(true, other), dist(true, mutant)
+    print("model", model, "floor", floor, "the mutant's distance", moved)
+    assert true.log == other.log == [True] and true.lam == 1e-5
+    assert floor > 0 and moved >= 1000 * floor
+
+
+def test_field_of_view_column_of_w_is_exactly_zero_below_its_branch():
+    """FieldOfView at w = 1e-3 (w^2 < 1e-5): the oracle's pixel does not depend on w, the reference's central difference for that
+    column is exactly zero, its reduced system is never positive definite with w free, and its loop climbs the ladder to the
+    cap: degenerate at lambda = 1e12 within the first iteration."""
+    import lm_rule_ref as lm
+    k, off, px, pt, poses = cr.fov_fixture()
+    k0, q0, t0 = cr.fov_start()
+    assert k0[3] == cr.FOV_W and k[3] == cr.FOV_W and cr.FOV_W ** 2 < 1e-5
+    sys = cr.systems(5, k0, cr.start_poses(q0, t0), off, pt, px)
+    for A, B, Cm, _, gk, _, ok in sys:
+        assert ok.all() and not B[:, 3].any() and not Cm[3, :].any() and not Cm[:, 3].any() and gk[3] == 0.0
+        np.linalg.cholesky(A)
+    ref = lm.calib_loop(5, k0, cr.start_poses(q0, t0), off, pt, px, 50)
+    assert ref.status == "degenerate" and ref.lam == 1e12 and ref.iterations == 1 and ref.log == []
+    held = lm.calib_loop(5, k0, cr.start_poses(q0, t0), off, pt, px, 1, free=(1, 1, 1, 0))
+    assert held.status == "out_of_iterations" and held.log == [True]
+
+
+def test_boundary_fixtures_have_the_properties_the_gpu_tests_rely_on():
+    """calib_ref.boundary_fixture, from the reference alone (lm_rule_ref's checks say what is held), with alpha held."""
+    import lm_rule_ref as lm
+    f = cr.BOUNDARY_FRAME
+    pose = lambda p: p[1][f]      # noqa: E731
+    for kind, check, steps in (("lost", lm.check_lost, 8), ("joins", lm.check_joins, 1), ("invalid", lm.check_invalid, 50)):
+        k, off, px, pt, k0, q0, t0 = cr.boundary_fixture(kind)
+        assert len(px) == 721 and off[f + 1] - off[f] == 37
+        start = (k0, cr.start_poses(q0, t0))
+        loop = lm.calib_loop(6, k0, start[1], off, pt, px, steps, free=cr.BOUNDARY_FREE)
+        print(kind, "accepted", loop.log, "lambda", loop.lam, "first accepted step", check(loop, pose, start, pt[off[f + 1] - 1], off[f + 1] - 1))

@@ -191,3 +191,23 @@ def test_reference_reaches_its_floor():
     print("reference floor", worst)
     assert worst <= rr.FLOOR
 
+
+
+def test_boundary_cases_have_the_properties_the_gpu_tests_rely_on():
+    """resect_ref.boundary_case, from the reference alone (lm_rule_ref's checks say what is held): `lost` is rejected until the
+    damping keeps the extra point inside the validity boundary, `invalid` never has it, `joins` gains it at the first candidate,
+    which only the comparison over the pairs in common accepts. And a start that puts the chart behind a pinhole camera has no
+    valid pair."""
+    import lm_rule_ref as lm
+    same = lambda p: p      # noqa: E731  (the point of the resection's loop is the frame's pose)
+    c = rr.boundary_case("lost")
+    first = lm.check_lost(lm.resect_loop(6, c.k, *c.start, c.points, c.pixels, 8), same, c.start, c.points[-1], -1)
+    c = rr.boundary_case("joins")
+    lm.check_joins(lm.resect_loop(6, c.k, *c.start, c.points, c.pixels, 1), same, c.start, c.points[-1], -1)
+    c = rr.boundary_case("invalid")
+    lm.check_invalid(lm.resect_loop(6, c.k, *c.start, c.points, c.pixels, 30), same, c.start, c.points[-1], -1)
+    print("lost: the first accepted step is step", first)
+    k, off, px, pt, poses = rr.fixture(1, 0.1)
+    for f in (0, 7, 19):
+        _, ok = rr.project(1, k, *rr.behind(poses[f]), pt[off[f]:off[f + 1]])
+        assert not ok.any()

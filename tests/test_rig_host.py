@@ -3,7 +3,9 @@ every argument rule of calico_rig_calibrate is checked before the device is touc
 CALICO_RIG_TOO_FEW_VIEWS, and the shared numpy reference (rig_ref.py) is measured on every fixture the GPU tests use: its FLOOR
 and its noise-free distance to the truth. The committed figures (rig_ref.FLOOR, rig_ref.REF_FREE) are this machine's; the floor
 is rounding noise, so another CPU's libm and BLAS move it: the test holds the re-measured values to twice the committed ones
-(calib_ref's rule) and prints them."""
+(calib_ref's rule) and prints them.
+Measured: the reference's first LM step from h = 2e-6 against h = 1e-6 differences, and the same step without the fill between
+the cameras: standard (a quarter of the perturbation) 4.1e-12 / 3.4e-3, wide 1.7e-11 / 7.5e-2."""
 import ctypes as C
 import os
 import re
@@ -206,3 +208,44 @@ def test_reference_floor_and_noise_free_distance(name):
     free = gr.distance(cams, frames, rig)
     print("fixture", name, "noise-free distance to the truth", free, "accepted steps", accepted)
     assert converged and free <= 2 * gr.REF_FREE[name]
+
+
+@pytest.mark.parametrize("name", ("standard", "wide"))
+def test_a_step_without_the_fill_between_cameras_is_far_from_the_true_step(name):
+    """What keeps the step tests' bound (10 floors, tests/test_gpu_chart_steps.py) from hiding what they are for: the
+    reference's first step is accepted, and the same step with the camera-to-camera blocks of the Schur complement zeroed ends at
+    least 1000 floors away (floor: the first step from h = 2e-6 against h = 1e-6 differences). From perturbed_start the
+    standard fixture's first step is REJECTED (the step tests pin that as well); the condition is held on the start the step
+    tests call `standard-near`, a quarter of the perturbation."""
+    import lm_rule_ref as lm
+    import resect_ref as rr
+    rig = gr.FIXTURES[name](0.1)
+    if name == "standard":
+        far = gr.perturbed_start(rig)
+        assert lm.rig_loop(rig, gr.poses_of(*far[:2]), gr.poses_of(*far[2:]), 1).log == [False]
+    start = gr.perturbed_start(rig, scale=0.005) if name == "standard" else gr.perturbed_start(rig)
+    c0, f0 = gr.poses_of(*start[:2]), gr.poses_of(*start[2:])
+    true, other, mutant = lm.rig_loop(rig, c0, f0, 1), lm.rig_loop(rig, c0, f0, 1, h=2e-6), lm.rig_loop(rig, c0, f0, 1, drop_fill=True)
+
+    def dist(a, b):
+        return max(rr.pose_distance(*p, *q) for p, q in zip(a.point[0] + a.point[1], b.point[0] + b.point[1]))
+    floor, moved = dist(true, other), dist(true, mutant)
+    print("fixture", name, "floor", floor, "the mutant's distance", moved, "the mutant's step accepted:", mutant.log)
+    assert true.log == other.log == [True] and true.lam == 1e-5
+    assert floor > 0 and moved >= 1000 * floor
+
+
+def test_boundary_rigs_have_the_properties_the_gpu_tests_rely_on():
+    """rig_ref.boundary_rig, from the reference alone (lm_rule_ref's checks say what is held). Camera 0 is the reference camera
+    at the rig's origin: its T_camera_chart is the rig frame's pose."""
+    import lm_rule_ref as lm
+    f = gr.BOUNDARY_FRAME
+    pose = lambda p: p[1][f]      # noqa: E731
+    for kind, check, steps in (("lost", lm.check_lost, 8), ("joins", lm.check_joins, 1), ("invalid", lm.check_invalid, 50)):
+        rig, start, v = gr.boundary_rig(kind)
+        assert rig.view_camera[v] == 0 and rig.view_frame[v] == f and rig.view_offsets[v + 1] - rig.view_offsets[v] == 37
+        assert np.array_equal(rig.cams[0][0], np.eye(3)) and not rig.cams[0][1].any()
+        at = rig.view_offsets[v + 1] - 1
+        point = (gr.poses_of(*start[:2]), gr.poses_of(*start[2:]))
+        loop = lm.rig_loop(rig, *point, steps)
+        print(kind, "accepted", loop.log, "lambda", loop.lam, "first accepted step", check(loop, pose, point, rig.points[at], at))
