@@ -1,39 +1,20 @@
 // calib_kernels.hip — static intrinsic calibration (calico_camera_calibrate): the K intrinsics of a camera model jointly with
 // the pose T_camera_chart of every frame of a ragged batch of (pixel, chart point) pairs, by Levenberg-Marquardt on the device.
 //
-// The normal equations are an arrowhead: n_frames independent 6x6 pose blocks A_f, bordered by one dense K x K block C through
-// the 6 x K couplings B_f. Unknowns of a frame: [delta_rot, delta_t] with R <- exp([delta_rot]x) R (the resection's); the
-// intrinsics move additively. Marquardt damping lambda diag on the pose blocks and on C. One LM iteration is four launches, and
-// the host enqueues them without reading anything back (the control word, CalibControl, lives in device memory):
-//   evaluate  (one wave per frame, kCalibWaves frames per workgroup) makes the frame's candidate pose from the step of the
-//             intrinsics (back-substitution delta_f = -(Y_g + Y_B dk), Y_f = (A_f + lambda diag A_f)^-1 [B_f g_f]) and evaluates the
-//             candidate in ONE pass over the frame's pairs: costs and counts as wave sums of per-lane partial sums (4 doubles), and
-//             the Gram matrix of the rows sqrt(w) [J_pose (6) | J_k (K) | e] -- N = K + 7 <= 18 columns, two rows per pair -- on the
-//             matrix cores: the 64 lanes stage 64 rows (first the u rows, then the v rows) in the wave's LDS area, and sixteen
-//             v_mfma_f64_16x16x4_f64 steps per tile add them to the 16 x 16 accumulator tiles (one tile for N <= 16, the three
-//             tiles of the lower triangle for OpenCv8's N = 18). The Gram matrix holds A_f, B_f, g_f and the frame's share of C and
-//             g_k; 171 per-lane partial sums would not fit the register file, 4 or 12 accumulator registers do. The order of
-//             accumulation is fixed: pairs in trips of 64, rows in groups of four.
-//   decide    (one wave) sums the frames' costs in a fixed order (lane l takes frames l, l + 64, ...; then the wave sum), accepts
-//             or rejects the candidate FOR ALL frames (the intrinsics are shared), sets the next lambda and ends the loop.
-//   eliminate (one wave per frame) Cholesky of A_f + lambda diag A_f in LDS, Y_f, and the frame's share B_f^T Y_f of the reduced
-//             system, with its share of C, into the frame's slab, entry by entry in the order the reduction reads. A frame whose damped block is not positive definite drops out for good.
-//   reduce    (one workgroup) sums C_f - B_f^T Y_f over the frames: thread (part, entry) adds the frames part, part + 8, ... in
-//             order, the eight parts are added in order -- nothing depends on a grid size, and there are no atomics --, solves
-//             the damped K x K system by Cholesky in LDS and writes dk, the candidate intrinsics and their step size.
-// Launches behind the end of the loop return at once. The same eliminate and reduce kernels, undamped at the result, give the
-// outputs per frame, the summary's sums and the covariance of the intrinsics (C - Sum B_f^T A_f^-1 B_f)^-1.
+// The arrowhead loop of arrowhead_dev.hpp, which describes the four launches of an iteration. What is this file's own: the border
+// is the K x K block C of the intrinsics, which move additively (a held one has an identity row); a block of pairs is a frame, one
+// wave per frame, kCalibWaves frames per workgroup; the rows are sqrt(w) [J_pose (6) | J_k (K) | e], N = K + 7 <= 18 columns (one
+// accumulator tile, three for OpenCv8); the frame's share of the reduced system is C_f - B_f^T Y_f, its entries in calib_entry's
+// order, summed in eight parts. The control word is CalibControl.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../../include/calico_hip.h"
+#include "arrowhead_dev.hpp"
 #include "kernels.hpp"
-#include "resect_dev.hpp"
 
 namespace cal {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kCalibWaves = 4;
 constexpr int kCalibThreads = 64 * kCalibWaves;
@@ -44,9 +25,7 @@ constexpr int kSlotCost = 7, kSlotSs = 8, kSlotValid = 9, kSlotNoise = 10;
 
 namespace {
 
-DEV Q4 frame_q(const double* st) { Q4 q; q.x = st[0]; q.y = st[1]; q.z = st[2]; q.w = st[3]; return q; }
-DEV V3 frame_t(const double* st) { return mk(st[4], st[5], st[6]); }
-DEV double max3(V3 v) { return fmax(fmax(dabs(v.x), dabs(v.y)), dabs(v.z)); }
+constexpr LmStatusCodes kCalibStatus = {CALICO_CALIB_OK, CALICO_CALIB_DEGENERATE, CALICO_CALIB_NOT_CONVERGED};
 
 // The entries of a frame's share of the reduced system, in the order the reduction adds them up: the lower triangle of
 // C_f - B_f^T Y_B by rows, then g_k - B_f^T Y_g (K), the diagonal of C_f (K: the damping's scale), then Sum rho, Sum |e|^2, the
@@ -82,9 +61,9 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
   const int64_t f = int64_t(blockIdx.x) * kCalibWaves + wave;
   if (f >= a.n_frames) return;      // (the whole wave: no barrier follows)
   const CalibControl* const c = a.ctrl;
-  if (c->done != 0 || c->redo != 0 || a.active[f] == 0) return;
-  const int cur = c->cur, nxt = cur ^ 1;
-  const bool first = c->first != 0;
+  if (c->lm.done != 0 || c->lm.redo != 0 || a.active[f] == 0) return;
+  const int cur = c->lm.cur, nxt = cur ^ 1;
+  const bool first = c->lm.first != 0;
   double* const fr = a.frames + f * kCalibFrameDoubles;
   double* const ns = fr + kCalibSlot * nxt;
   const double* const k = c->k[nxt];
@@ -93,7 +72,7 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
   V3 t;
   double step = 0.0;
   if (first) {
-    q = frame_q(ns); t = frame_t(ns);
+    q = slot_q(ns); t = slot_t(ns);
   } else {
     const double* const cs = fr + kCalibSlot * cur;
     double d[6];
@@ -104,11 +83,7 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
       for (int j = 0; j < K; ++j) v += fr[kCalibY + 6 * j + r] * c->dk[j];
       d[r] = -v;
     }
-    const V3 dr = mk(d[0], d[1], d[2]), dt = mk(d[3], d[4], d[5]), t0 = frame_t(cs);
-    q = canonical(quat_mul(angle_axis_to_quat(dr), frame_q(cs)));
-    t = t0 + dt;
-    step = fmax(max3(dr), max3(dt) / fmax(1.0, sqrt(dot(t0, t0))));
-    if (!__builtin_isfinite(step)) step = 1e300;
+    step = retract_pose(slot_q(cs), slot_t(cs), mk(d[0], d[1], d[2]), mk(d[3], d[4], d[5]), &q, &t);
   }
   const M3 R = rotmat(q);
   const int64_t base = a.offsets[f], n = a.offsets[f + 1] - base;
@@ -140,8 +115,8 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
       a.flags[i] = uint8_t((fl & ~pose_bit(nxt)) | (ok ? pose_bit(nxt) : 0));
       if (ok) {
         const double e[2] = {pix[0] - u, pix[1] - v}, sq = e[0] * e[0] + e[1] * e[1];
-        double w = 1.0, rho = sq;
-        if (hs > 0.0 && sq > hs2) { const double r = sqrt(sq); w = hs / r; rho = 2.0 * hs * r - hs2; }
+        double w, rho;
+        huber(sq, hs, hs2, &w, &rho);
         const double sw = sqrt(w);
         // d Pc / d delta = -[R P]x: row r of J_pose is [(R P) x D_r, D_r]
 #pragma unroll
@@ -190,20 +165,10 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
       }
     }
   }
-  // the Gram matrix, full and symmetric (C/D layout: col = lane & 15, row = (lane >> 4) + 4 reg)
-  double* const G = a.gram + (f * 2 + nxt) * (N * N);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = lk + 4 * r;
-    if (row < N && lc < N) G[row * N + lc] = acc00[r];
-    if (kTwo) {
-      if (16 + row < N && lc < N) { G[(16 + row) * N + lc] = acc10[r]; G[lc * N + 16 + row] = acc10[r]; }
-      if (16 + row < N && 16 + lc < N) G[(16 + row) * N + 16 + lc] = acc11[r];
-    }
-  }
+  gram_store<N>(a.gram + (f * 2 + nxt) * (N * N), lane, acc00, acc10, acc11);
   s_cost = wave_sum(s_cost); s_common = wave_sum(s_common); s_ss = wave_sum(s_ss); s_noise = wave_sum(s_noise);
   if (lane == 0) {
-    ns[0] = q.x; ns[1] = q.y; ns[2] = q.z; ns[3] = q.w; ns[4] = t.x; ns[5] = t.y; ns[6] = t.z;
+    put_slot_pose(ns, q, t);
     ns[kSlotCost] = s_cost; ns[kSlotSs] = s_ss; ns[kSlotValid] = double(n_valid); ns[kSlotNoise] = s_noise;
     fr[kCalibCommon] = s_common; fr[kCalibLost] = double(lost); fr[kCalibStep] = step;
   }
@@ -213,9 +178,9 @@ __global__ __launch_bounds__(kCalibThreads, kCalibWavesPerSimd) void calib_evalu
 __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
   CalibControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
-  if (c->redo != 0) { if (lane == 0) c->redo = 0; return; }
-  const int cur = c->cur, nxt = cur ^ 1;
+  if (c->lm.done != 0) return;
+  if (c->lm.redo != 0) { if (lane == 0) c->lm.redo = 0; return; }
+  const int cur = c->lm.cur, nxt = cur ^ 1;
   double cand = 0.0, common = 0.0, current = 0.0, noise = 0.0, lost = 0.0, valid = 0.0, step = 0.0;
   bool finite = true;
   // (no branch on the frame's flag: a frame that takes no part adds zero; its slots are finite, the host cleared them)
@@ -227,7 +192,7 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
     const double* const ns = fr + kCalibSlot * nxt;
     const double v_cand = ns[kSlotCost], v_valid = ns[kSlotValid], v_common = fr[kCalibCommon], v_lost = fr[kCalibLost];
     const double v_current = cs[kSlotCost], v_noise = cs[kSlotNoise], v_step = fr[kCalibStep];
-    const bool v_finite = finite_pose(frame_q(ns), frame_t(ns));
+    const bool v_finite = finite_pose(slot_q(ns), slot_t(ns));
     cand += act ? v_cand : 0.0; valid += act ? v_valid : 0.0; common += act ? v_common : 0.0; lost += act ? v_lost : 0.0;
     current += act ? v_current : 0.0; noise += act ? v_noise : 0.0; step = fmax(step, act ? v_step : 0.0);
     finite = finite && (v_finite || !act);
@@ -238,24 +203,8 @@ __global__ __launch_bounds__(64) void calib_decide_kernel(CalibArgs a) {
 #pragma unroll 1
   for (int i = 0; i < a.K; ++i) finite = finite && __builtin_isfinite(c->k[nxt][i]);
   const bool kept = lost == 0.0 && finite && __builtin_isfinite(cand);
-  int done = 0, status = c->status, new_cur = cur, iterations = c->iterations, accepted = c->accepted;
-  double lambda = c->lambda, initial = c->initial_cost;
-  if (c->first != 0) {
-    if (!kept || valid < 1.0) { status = CALICO_CALIB_DEGENERATE; done = 1; }
-    new_cur = nxt; initial = cand;
-  } else {
-    const bool small = fmax(step, c->step_k) < a.step_tolerance;
-    const LmVerdict v = lm_rule(kept, common, current, noise, small, lambda);
-    if (v.accept) { new_cur = nxt; accepted = 1; }
-    lambda = v.lambda;
-    if (v.converged) { status = CALICO_CALIB_OK; done = 1; }
-  }
-  if (done == 0 && iterations >= a.max_iterations) { status = CALICO_CALIB_NOT_CONVERGED; done = 1; }
-  if (done == 0) ++iterations;
-  if (lane == 0) {
-    c->done = done; c->status = status; c->cur = new_cur; c->first = 0; c->iterations = iterations; c->lambda = lambda;
-    c->initial_cost = initial; c->accepted = accepted;
-  }
+  const bool small = fmax(step, c->lm.step) < a.step_tolerance;
+  lm_control_decide(&c->lm, lane, kept, valid >= 1.0, cand, common, current, noise, small, a.max_iterations, kCalibStatus);
 }
 
 // final: undamped, at the result, for every frame (the loop is over): the frame's outputs, Y and the share for the covariance.
@@ -265,38 +214,23 @@ __global__ __launch_bounds__(kCalibThreads) void calib_eliminate_kernel(CalibArg
   const int64_t f = int64_t(blockIdx.x) * kCalibWaves + wave;
   if (f >= a.n_frames) return;
   const CalibControl* const c = a.ctrl;
-  if (!final && c->done != 0) return;
-  const int K = a.K, N = K + 7, cur = c->cur;
+  if (!final && c->lm.done != 0) return;
+  const int K = a.K, N = K + 7, cur = c->lm.cur;
   double* const fr = a.frames + f * kCalibFrameDoubles;
   const double* const cs = fr + kCalibSlot * cur;
   bool active = a.active[f] != 0;
   if (active) {
-    const double lambda = final ? 0.0 : c->lambda;
+    const double lambda = final ? 0.0 : c->lm.lambda;
     const double* const G = a.gram + (f * 2 + cur) * (N * N);
     double* const W = s_w[wave];
     double* const Y = W + 36;      // column j (K columns of B, then g) at 6 j
     if (lane < 36) { const int r = lane / 6, col = lane - 6 * r; W[lane] = G[r * N + col] * (r == col ? 1.0 + lambda : 1.0); }
     for (int e = lane; e < 6 * (K + 1); e += 64) { const int j = e / 6, r = e - 6 * j; Y[e] = G[r * N + 6 + j]; }
     wave_fence();
-    const bool pd = lds_chol(W, 6, lane);
-    if (!pd) {
+    if (!eliminate_frame_block(W, Y, K + 1, lane)) {
       active = false;
       if (lane == 0) { a.active[f] = 0; a.status[f] = uint8_t(final ? CALICO_RESECT_DEGENERATE : CALICO_RESECT_NOT_POSITIVE_DEFINITE); }
     } else {
-      if (lane <= K) {      // lane j solves column j: nobody else reads or writes it
-        double* const b = Y + 6 * lane;
-        for (int i = 0; i < 6; ++i) {
-          double v = b[i];
-          for (int kk = 0; kk < i; ++kk) v -= W[6 * i + kk] * b[kk];
-          b[i] = v / W[6 * i + i];
-        }
-        for (int i = 5; i >= 0; --i) {
-          double v = b[i];
-          for (int kk = i + 1; kk < 6; ++kk) v -= W[6 * kk + i] * b[kk];
-          b[i] = v / W[6 * i + i];
-        }
-      }
-      wave_fence();
       for (int e = lane; e < 6 * (K + 1); e += 64) fr[kCalibY + e] = Y[e];
       // the frame's share, entry by entry in the reduction's order: contiguous, so that the reduction's loads are whole lines
       double* const sh = a.share + f * kCalibEntries;
@@ -307,11 +241,7 @@ __global__ __launch_bounds__(kCalibThreads) void calib_eliminate_kernel(CalibArg
         double v = 1.0;
         if (g_at >= 0) {
           v = G[g_at];
-          if (s_row >= 0) {      // (B^T Y)[s_row][s_col]
-            double by = 0.0;
-            for (int r = 0; r < 6; ++r) by += G[r * N + 6 + s_row] * Y[6 * s_col + r];
-            v -= by;
-          }
+          if (s_row >= 0) v -= bty(G + 6 + s_row, N, Y + 6 * s_col);      // (B^T Y)[s_row][s_col]
         } else if (slot_at >= 0) {
           v = cs[slot_at];
         }
@@ -320,47 +250,27 @@ __global__ __launch_bounds__(kCalibThreads) void calib_eliminate_kernel(CalibArg
     }
   }
   if (final && lane == 0) {
-    a.q_out[4 * f] = active ? cs[0] : 0.0; a.q_out[4 * f + 1] = active ? cs[1] : 0.0; a.q_out[4 * f + 2] = active ? cs[2] : 0.0;
-    a.q_out[4 * f + 3] = active ? cs[3] : 1.0;
-    a.t_out[3 * f] = active ? cs[4] : 0.0; a.t_out[3 * f + 1] = active ? cs[5] : 0.0; a.t_out[3 * f + 2] = active ? cs[6] : 0.0;
+    put_pose_out(a.q_out + 4 * f, a.t_out + 3 * f, cs, active);
     a.rms_out[f] = active ? sqrt(cs[kSlotSs] / cs[kSlotValid]) : 0.0;
     a.n_used_out[f] = active ? int(cs[kSlotValid]) : 0;
   }
 }
 
-// One workgroup of kCalibParts x kCalibEntries threads: thread (part, entry) adds the entry (calib_entry) of the frames' shares.
+// One workgroup of kCalibParts x kCalibEntries threads: thread (part, entry) adds the entry (calib_entry) of the frames' shares,
+// the loads of sixteen frames in flight at once.
 __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kernel(CalibArgs a, int final) {
   __shared__ double s_part[kCalibParts][kCalibEntries];
   __shared__ double s_tot[kCalibEntries];
   __shared__ double s_S[kMaxIntr * kMaxIntr], s_Li[kMaxIntr * kMaxIntr], s_rhs[kMaxIntr];
   CalibControl* const c = a.ctrl;
-  if (!final && c->done != 0) return;      // (the whole workgroup)
-  const int K = a.K, cur = c->cur, nxt = cur ^ 1;
-  const int part = threadIdx.x / kCalibEntries, el = threadIdx.x % kCalibEntries;
+  if (!final && c->lm.done != 0) return;      // (the whole workgroup)
+  const int K = a.K, cur = c->lm.cur, nxt = cur ^ 1;
   const int n_tri = K * (K + 1) / 2, n_el = n_tri + 2 * K + 4;
-  double sum = 0.0;
-  if (el < n_el) {
-    // (no branch on the frame's flag: the loads of sixteen frames are in flight at once, a frame that takes no part adds zero; a
-    // wave reads 64 consecutive entries of a frame's share)
-#pragma unroll 16
-    for (int64_t f = part; f < a.n_frames; f += kCalibParts) {
-      const bool act = a.active[f] != 0;
-      const double v = a.share[f * kCalibEntries + el];
-      sum += act ? v : 0.0;
-    }
-  }
-  s_part[part][el] = sum;
-  __syncthreads();
-  if (part == 0) {
-    double v = 0.0;
-#pragma unroll
-    for (int p = 0; p < kCalibParts; ++p) v += s_part[p][el];
-    s_tot[el] = v;
-  }
-  __syncthreads();
+  __builtin_assume(n_el <= kCalibEntries);      // (one trip)
+  sum_shares<kCalibParts, kCalibEntries, 16>(a.share, kCalibEntries, a.active, a.n_frames, n_el, [](int) { return true; }, s_part, s_tot);
   if (threadIdx.x >= 64) return;      // the small system: wave 0
   const int lane = threadIdx.x;
-  const double lambda = final ? 0.0 : c->lambda;
+  const double lambda = final ? 0.0 : c->lm.lambda;
   if (lane == 0) {
     for (int i = 0; i < K; ++i) {
       const bool fi = ((a.free_bits >> i) & 1u) != 0;
@@ -376,13 +286,7 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
   wave_fence();
   const bool pd = lds_chol(s_S, K, lane);
   if (!final) {
-    if (!pd) {
-      if (lane == 0) {
-        if (lambda >= kLmLambdaMax) { c->status = CALICO_CALIB_DEGENERATE; c->done = 1; }
-        else { c->lambda = fmin(lambda * 10.0, kLmLambdaMax); c->redo = 1; }
-      }
-      return;
-    }
+    if (!pd) { lm_control_not_pd(&c->lm, lane, lambda, CALICO_CALIB_DEGENERATE); return; }
     lds_chol_solve(s_S, s_rhs, K, lane);
     double step = 0.0;
 #pragma unroll 1
@@ -394,7 +298,7 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
       step = fmax(step, sz);
       if (lane == 0) { c->dk[i] = d; c->k[nxt][i] = fi ? k0 + d : k0; }
     }
-    if (lane == 0) c->step_k = step;
+    if (lane == 0) c->lm.step = step;
     return;
   }
   // the result: sums for the summary, and the covariance of the intrinsics, the inverse of the undamped reduced system
@@ -403,31 +307,14 @@ __global__ __launch_bounds__(kCalibParts * kCalibEntries) void calib_reduce_kern
   bool ok = pd && __builtin_isfinite(cost) && __builtin_isfinite(rms);
 #pragma unroll 1
   for (int i = 0; i < K; ++i) ok = ok && __builtin_isfinite(c->k[cur][i]);
-  // L^-1 column by column (lane col < K owns column col), then L^-T L^-1
-  if (lane < K) {
-    for (int r = 0; r < K; ++r) {
-      double v = r == lane ? 1.0 : 0.0;
-      for (int kk = lane; kk < r; ++kk) v -= s_S[K * r + kk] * s_Li[K * kk + lane];
-      s_Li[K * r + lane] = r < lane ? 0.0 : v / s_S[K * r + r];
-    }
-  }
-  wave_fence();
-  for (int e = lane; e < K * K; e += 64) {
-    const int r = e / K, col = e - K * r;
-    double v = 0.0;
-    for (int kk = 0; kk < K; ++kk) v += s_Li[K * kk + r] * s_Li[K * kk + col];
+  chol_inverse_gram(s_S, s_Li, K, lane, [&](int e, int r, int col, double v) {
     const bool free_rc = ((a.free_bits >> r) & 1u) != 0 && ((a.free_bits >> col) & 1u) != 0;
     v = free_rc ? v : 0.0;
     ok = ok && __builtin_isfinite(v);
     if (a.cov_out) a.cov_out[e] = pd ? v : 0.0;
-  }
+  });
   ok = __all(ok) != 0;
-  if (lane == 0) {
-    c->final_ok = ok ? 1 : 0; c->final_cost = cost; c->rms = rms; c->frames_used = int(frames); c->pairs_used = (long long)valid;
-    // no step was accepted: the point kept is the start, and its cost is ONE number -- this sum, not the decision's sum of the
-    // same terms in another order, which can differ from it in the last bit and would read as a decrease
-    if (c->accepted == 0) c->initial_cost = cost;
-  }
+  lm_control_finish(&c->lm, lane, ok, cost, rms, frames, valid);
 }
 
 hipError_t launch_calib_evaluate(int model, const CalibArgs& a, hipStream_t s) {

@@ -13,25 +13,18 @@
 #include "calico_hip_testing.h"
 #include "free_call.hpp"
 #include "kernels.hpp"
+#include "lm_host.hpp"
 #include "lm_rule.hpp"
 
 namespace {
 
 using namespace cal;
 
-ResectArgs resect_args(const calico_resection_options& o) {
-  ResectArgs a = {};
-  a.max_iterations = o.max_iterations; a.step_tolerance = o.step_tolerance; a.huber_scale = o.huber_scale; a.min_points = o.min_points;
-  return a;
-}
-
 // pairs per pass of calico_camera_resect: upload, kernel, download (2^20 pairs: 40 MB in, 17 MB of workspace). A frame is never
 // split; one with more pairs than this travels alone.
 constexpr int64_t kResectChunkPairs = int64_t(1) << 20;
-// calico_camera_calibrate. The whole batch lives on the device for the length of the call (every iteration reads every pair:
-// nothing is chunked). LM cycles -- evaluate, decide, eliminate, reduce -- are enqueued kCalibPollCycles at a time; between the
-// groups the host reads the control word's first field, only to stop enqueuing (launches behind the end return at once).
-constexpr int kCalibPollCycles = 6;
+// calico_camera_calibrate: the whole batch lives on the device for the length of the call (every iteration reads every pair:
+// nothing is chunked).
 
 }  // namespace
 
@@ -68,21 +61,14 @@ int32_t calico_debug_camera_resect_chunked(int32_t device, int32_t model, const 
     f0 = f1;
   }
   const size_t K = size_t(n_intrinsics), F = size_t(max_frames), P = size_t(max_pairs);
-  FreeBuf<double> d_k, d_px, d_pt, d_ws, d_qi, d_ti, d_q, d_t, d_rms, d_cov;
+  FreeBuf<double> d_k, d_px, d_pt, d_qi, d_ti;
   FreeBuf<int64_t> d_off;
-  FreeBuf<int32_t> d_used, d_it;
-  FreeBuf<uint8_t> d_fl, d_st;
-  FREE_TRY(call, d_k.upload(intrinsics, K)); FREE_TRY(call, d_px.alloc(P * 2)); FREE_TRY(call, d_pt.alloc(P * 3)); FREE_TRY(call, d_ws.alloc(P * 2));
+  FreeBuf<uint8_t> d_fl;
+  ResectRun run;
+  FREE_TRY(call, d_k.upload(intrinsics, K)); FREE_TRY(call, d_px.alloc(P * 2)); FREE_TRY(call, d_pt.alloc(P * 3));
   FREE_TRY(call, d_fl.alloc(P)); FREE_TRY(call, d_off.alloc(F + 1));
   if (q_init) { FREE_TRY(call, d_qi.alloc(F * 4)); FREE_TRY(call, d_ti.alloc(F * 3)); }
-  FREE_TRY(call, d_q.alloc(F * 4)); FREE_TRY(call, d_t.alloc(F * 3)); FREE_TRY(call, d_rms.alloc(F)); FREE_TRY(call, d_used.alloc(F));
-  FREE_TRY(call, d_it.alloc(F)); FREE_TRY(call, d_st.alloc(F));
-  if (cov_out) FREE_TRY(call, d_cov.alloc(F * 36));
-  ResectArgs a = resect_args(o);
-  a.k = d_k.p; a.offsets = d_off.p; a.pixels = d_px.p; a.points = d_pt.p; a.ws = d_ws.p; a.flags = d_fl.p;
-  a.q_init = q_init ? d_qi.p : nullptr; a.t_init = q_init ? d_ti.p : nullptr;
-  a.q_out = d_q.p; a.t_out = d_t.p; a.rms_out = d_rms.p; a.n_used_out = d_used.p; a.iterations_out = d_it.p; a.status_out = d_st.p;
-  a.cov_out = cov_out ? d_cov.p : nullptr;
+  FREE_TRY(call, run.alloc(F, P, cov_out != nullptr));
   std::vector<int64_t> local;
   for (size_t c = 0; c + 1 < cuts.size(); ++c) {
     const int64_t f0 = cuts[c], f1 = cuts[c + 1], p0 = offsets[f0];
@@ -93,12 +79,11 @@ int32_t calico_debug_camera_resect_chunked(int32_t device, int32_t model, const 
     FREE_TRY(call, d_px.put(pixels + 2 * p0, np * 2)); FREE_TRY(call, d_pt.put(points + 3 * p0, np * 3));
     if (np > 0) FREE_TRY(call, d_fl.zero(np));
     if (q_init) { FREE_TRY(call, d_qi.put(q_init + 4 * f0, nf * 4)); FREE_TRY(call, d_ti.put(t_init + 3 * f0, nf * 3)); }
-    a.n_frames = int64_t(nf);
-    FREE_TRY(call, launch_camera_resect(model, a, nullptr));
-    FREE_TRY(call, d_q.download(q_out + 4 * f0, nf * 4)); FREE_TRY(call, d_t.download(t_out + 3 * f0, nf * 3));
-    FREE_TRY(call, d_rms.download(rms_out + f0, nf)); FREE_TRY(call, d_used.download(n_used_out + f0, nf));
-    FREE_TRY(call, d_it.download(iterations_out + f0, nf)); FREE_TRY(call, d_st.download(status_out + f0, nf));
-    if (cov_out) FREE_TRY(call, d_cov.download(cov_out + 36 * f0, nf * 36));
+    FREE_TRY(call, launch_camera_resect(model, run.args(o, d_k.p, int64_t(nf), d_off.p, d_px.p, d_pt.p, d_fl.p, d_qi.p, d_ti.p), nullptr));
+    FREE_TRY(call, run.q.download(q_out + 4 * f0, nf * 4)); FREE_TRY(call, run.t.download(t_out + 3 * f0, nf * 3));
+    FREE_TRY(call, run.rms.download(rms_out + f0, nf)); FREE_TRY(call, run.used.download(n_used_out + f0, nf));
+    FREE_TRY(call, run.iterations.download(iterations_out + f0, nf)); FREE_TRY(call, run.status.download(status_out + f0, nf));
+    if (cov_out) FREE_TRY(call, run.cov.download(cov_out + 36 * f0, nf * 36));
   }
   return CALICO_OK;
 }
@@ -126,12 +111,12 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* k_i
   if (!error.empty()) return call.invalid(error);
   if (int rc = call.select_device(device)) return rc;
   const size_t F = size_t(n_frames), P = size_t(offsets[n_frames]), N = size_t(K) + 7;
-  FreeBuf<double> d_k, d_px, d_pt, d_ws, d_q, d_t, d_rms, d_frames, d_gram, d_share, d_cov;
+  FreeBuf<double> d_px, d_pt, d_q, d_t, d_rms, d_frames, d_gram, d_share, d_cov;
   FreeBuf<int64_t> d_off;
-  FreeBuf<int32_t> d_used, d_it;
+  FreeBuf<int32_t> d_used;
   FreeBuf<uint8_t> d_fl, d_st, d_act;
   FreeBuf<CalibControl> d_ctrl;
-  FREE_TRY(call, d_k.alloc(size_t(K))); FREE_TRY(call, d_px.upload(pixels, P * 2)); FREE_TRY(call, d_pt.upload(points, P * 3));
+  FREE_TRY(call, d_px.upload(pixels, P * 2)); FREE_TRY(call, d_pt.upload(points, P * 3));
   FREE_TRY(call, d_fl.alloc(P)); FREE_TRY(call, d_off.upload(offsets, F + 1)); FREE_TRY(call, d_q.alloc(F * 4)); FREE_TRY(call, d_t.alloc(F * 3));
   FREE_TRY(call, d_rms.alloc(F)); FREE_TRY(call, d_used.alloc(F)); FREE_TRY(call, d_st.alloc(F)); FREE_TRY(call, d_act.alloc(F)); FREE_TRY(call, d_ctrl.alloc(1));
   FREE_TRY(call, d_frames.alloc(F * kCalibFrameDoubles)); FREE_TRY(call, d_gram.alloc(F * 2 * N * N));
@@ -151,14 +136,10 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* k_i
     calico_resection_options ro;
     calico_default_resection_options(&ro);
     ro.huber_scale = o.huber_scale; ro.min_points = o.min_points;
-    FREE_TRY(call, d_ws.alloc(P * 2)); FREE_TRY(call, d_it.alloc(F));
-    FREE_TRY(call, d_k.put(k_init, size_t(K)));
-    ResectArgs ra = resect_args(ro);
-    ra.k = d_k.p; ra.n_frames = n_frames; ra.offsets = d_off.p; ra.pixels = d_px.p; ra.points = d_pt.p; ra.ws = d_ws.p; ra.flags = d_fl.p;
-    ra.q_out = d_q.p; ra.t_out = d_t.p; ra.rms_out = d_rms.p; ra.n_used_out = d_used.p; ra.iterations_out = d_it.p; ra.status_out = d_st.p;
-    FREE_TRY(call, launch_camera_resect(model, ra, nullptr));
-    FREE_TRY(call, d_q.download(q0.data(), F * 4)); FREE_TRY(call, d_t.download(t0.data(), F * 3));
-    FREE_TRY(call, d_st.download(status.data(), F));
+    FreeBuf<double> d_k;
+    ResectRun run;
+    FREE_TRY(call, d_k.upload(k_init, size_t(K))); FREE_TRY(call, run.alloc(F, P, false));
+    FREE_TRY(call, run.start(model, ro, d_k.p, F, d_off.p, d_px.p, d_pt.p, d_fl.p, q0.data(), t0.data(), status.data()));
     FREE_TRY(call, d_fl.zero(P));      // (the validity bits start clean)
   }
   std::vector<uint8_t> active(F, 0);
@@ -191,7 +172,7 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* k_i
     std::copy(&t0[3 * f], &t0[3 * f] + 3, ns + 4);
   }
   CalibControl ctrl = {};
-  ctrl.status = CALICO_CALIB_NOT_CONVERGED; ctrl.first = 1; ctrl.lambda = kLmLambda0;
+  ctrl.lm.status = CALICO_CALIB_NOT_CONVERGED; ctrl.lm.first = 1; ctrl.lm.lambda = kLmLambda0;
   for (int i = 0; i < K; ++i) ctrl.k[0][i] = ctrl.k[1][i] = k_init[i];
   FREE_TRY(call, d_frames.put(frames.data(), frames.size())); FREE_TRY(call, d_act.put(active.data(), F));
   FREE_TRY(call, d_st.put(status.data(), F)); FREE_TRY(call, d_ctrl.put(&ctrl, 1));
@@ -202,35 +183,31 @@ int32_t calico_camera_calibrate(int32_t device, int32_t model, const double* k_i
   a.flags = d_fl.p; a.active = d_act.p; a.status = d_st.p; a.frames = d_frames.p; a.gram = d_gram.p; a.share = d_share.p;
   a.max_iterations = o.max_iterations; a.step_tolerance = o.step_tolerance; a.huber_scale = o.huber_scale;
   a.q_out = d_q.p; a.t_out = d_t.p; a.rms_out = d_rms.p; a.n_used_out = d_used.p; a.cov_out = d_cov.p;
-  // every cycle tries a step or raises lambda tenfold after a reduced system that was not positive definite (at most 24 times
-  // in a row): the loop ends on its own; the bound only guards the host against a control word that never moves
-  const int64_t max_cycles = 26 * (int64_t(o.max_iterations) + 2);
-  int done = 0;
-  for (int64_t cycle = 0; !done; cycle += kCalibPollCycles) {
-    if (cycle > max_cycles) return call.fail(CALICO_INTERNAL, "the device loop did not end");
-    for (int i = 0; i < kCalibPollCycles; ++i) {
-      FREE_TRY(call, launch_calib_evaluate(model, a, nullptr)); FREE_TRY(call, launch_calib_decide(a, nullptr));
-      FREE_TRY(call, launch_calib_eliminate(a, false, nullptr)); FREE_TRY(call, launch_calib_reduce(a, false, nullptr));
-    }
-    FREE_TRY(call, hipMemcpy(&done, &d_ctrl.p->done, sizeof(int), hipMemcpyDeviceToHost));
-  }
+  const int rc = run_device_lm(call, &d_ctrl.p->lm.done, o.max_iterations, [&] {
+    hipError_t e = launch_calib_evaluate(model, a, nullptr);
+    if (e == hipSuccess) e = launch_calib_decide(a, nullptr);
+    if (e == hipSuccess) e = launch_calib_eliminate(a, false, nullptr);
+    return e != hipSuccess ? e : launch_calib_reduce(a, false, nullptr);
+  });
+  if (rc != CALICO_OK) return rc;
   FREE_TRY(call, d_ctrl.download(&ctrl, 1));
-  if (ctrl.status != CALICO_CALIB_DEGENERATE) {
+  const LmControl& lm = ctrl.lm;
+  if (lm.status != CALICO_CALIB_DEGENERATE) {
     FREE_TRY(call, launch_calib_eliminate(a, true, nullptr)); FREE_TRY(call, launch_calib_reduce(a, true, nullptr));
     FREE_TRY(call, d_ctrl.download(&ctrl, 1));
   }
-  if (ctrl.status == CALICO_CALIB_DEGENERATE || !ctrl.final_ok) {
-    give_inputs(CALICO_CALIB_DEGENERATE, ctrl.iterations, ctrl.lambda);
+  if (lm.status == CALICO_CALIB_DEGENERATE || !lm.final_ok) {
+    give_inputs(CALICO_CALIB_DEGENERATE, lm.iterations, lm.lambda);
     return CALICO_OK;
   }
-  for (int i = 0; i < K; ++i) k_out[i] = ((free_bits >> i) & 1u) ? ctrl.k[ctrl.cur][i] : k_init[i];
+  for (int i = 0; i < K; ++i) k_out[i] = ((free_bits >> i) & 1u) ? ctrl.k[lm.cur][i] : k_init[i];
   FREE_TRY(call, d_q.download(q_out, F * 4)); FREE_TRY(call, d_t.download(t_out, F * 3));
   FREE_TRY(call, d_rms.download(rms_out, F)); FREE_TRY(call, d_used.download(n_used_out, F));
   FREE_TRY(call, d_st.download(status_out, F));
   if (cov_out) FREE_TRY(call, d_cov.download(cov_out, size_t(K) * size_t(K)));
-  summary->status = ctrl.status; summary->iterations = ctrl.iterations; summary->initial_cost = ctrl.initial_cost;
-  summary->final_cost = ctrl.final_cost; summary->rms = ctrl.rms; summary->frames_used = ctrl.frames_used;
-  summary->pairs_used = ctrl.pairs_used; summary->lambda = ctrl.lambda;
+  summary->status = lm.status; summary->iterations = lm.iterations; summary->initial_cost = lm.initial_cost;
+  summary->final_cost = lm.final_cost; summary->rms = lm.rms; summary->frames_used = lm.frames_used;
+  summary->pairs_used = lm.pairs_used; summary->lambda = lm.lambda;
   return CALICO_OK;
 }
 

@@ -201,22 +201,27 @@ hipError_t launch_camera_resect(int model, const ResectArgs& a, hipStream_t s);
 
 // ---- intrinsic calibration (calib_kernels.hip): K intrinsics and the 6-DOF pose of every frame, an arrowhead system ----------
 // The control word of the device's LM loop: every kernel of an iteration reads it, the two single-workgroup kernels write it.
-struct CalibControl {
+// Its head is the same for every arrowhead estimator (arrowhead_dev.hpp writes it; lm_host.hpp polls its first field):
+struct LmControl {
   int done;                     // != 0: every later launch returns at once
-  int status;                   // CALICO_CALIB_*
-  int cur;                      // the slot (intrinsics, poses, Gram matrices, validity bit) of the current point
+  int status;                   // the estimator's own codes (CALICO_CALIB_*, CALICO_RIG_*)
+  int cur;                      // the slot (border unknowns, poses, Gram matrices, validity bit) of the current point
   int first;                    // the start has not been evaluated yet
   int redo;                     // the reduced system was not positive definite: eliminate and reduce again at the larger lambda
   int iterations;
-  int frames_used;
-  int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
   int accepted;                 // a step has been accepted: the point kept is not the start
+  int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
+  int frames_used;
   long long pairs_used;
-  double lambda, step_k;        // step_k: max |dk_i| / max(1, |k_i|) of the step the candidate was made with
+  double lambda, step;          // step: the size of the border's step the candidate was made with
   double initial_cost, final_cost, rms;
+};
+struct CalibControl {
+  LmControl lm;                 // lm.step: max |dk_i| / max(1, |k_i|)
   double k[2][12];              // the intrinsics of the two slots
   double dk[12];
 };
+static_assert(offsetof(CalibControl, lm.done) == 0, "the host polls the control word's first field");
 // Per frame, kCalibFrameDoubles doubles: two slots of kCalibSlot ([0, 4) q, [4, 7) t, [7] Sum rho, [8] Sum |e|^2, [9] valid
 // pairs, [10] the cost's rounding scale), [24] Sum rho over the pairs valid at both points, [25] pairs lost, [26] the pose step's
 // size, and from [32] Y = A^-1 [B g], column j at 32 + 6 j.
@@ -251,21 +256,12 @@ constexpr int kRigMaxCameras = 8;                        // CALICO_RIG_MAX_CAMER
 constexpr int kRigMaxDim = 6 * kRigMaxCameras;
 constexpr int kRigN = 13;                                // columns of a view's rows: [J_frame 6 | J_extrinsics 6 | e]
 struct RigControl {
-  int done;                     // != 0: every later launch returns at once
-  int status;                   // CALICO_RIG_*
-  int cur;                      // the slot (extrinsics, frame poses, Gram matrices, validity bit) of the current point
-  int first;                    // the start has not been evaluated yet
-  int redo;                     // the reduced system was not positive definite: eliminate and reduce again at the larger lambda
-  int iterations;
-  int frames_used;
-  int final_ok;                 // the undamped reduced system at the result was positive definite (covariance written)
-  int accepted;                 // a step has been accepted: the point kept is not the start
-  long long views_used, pairs_used;
-  double lambda, step_x;        // step_x: the size of the extrinsics' step the candidate was made with
-  double initial_cost, final_cost, rms;
+  LmControl lm;
+  long long views_used;
   double cam[2][kRigMaxCameras][8];      // T_rig_camera of the two slots: [0, 4) q, [4, 7) t
   double dx[kRigMaxDim];
 };
+static_assert(offsetof(RigControl, lm.done) == 0, "the host polls the control word's first field");
 // Per frame, kRigFrameDoubles doubles: two slots of 8 ([0, 4) q, [4, 7) t of T_rig_chart), [16] the pose step's size, and from
 // [24] Y = A^-1 [B g], column j (the M columns of the extrinsics, then g) at 24 + 6 j; a camera without a view in the frame
 // has zero columns. Per view, kRigViewDoubles: two slots of 4 (Sum rho, Sum |e|^2, valid pairs, the cost's rounding scale),

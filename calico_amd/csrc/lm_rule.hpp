@@ -1,5 +1,6 @@
-// lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip,
-// calib_kernels.hip, align_kernels.hip, rig_kernels.hip): accept or reject a candidate, the next damping, and whether the loop has converged.
+// lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip and
+// align_kernels.hip call it themselves, calib_kernels.hip and rig_kernels.hip through arrowhead_dev.hpp): accept or reject a
+// candidate, the next damping, and whether the loop has converged.
 // What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
 // a damped system is not positive definite. Host and device code (the host sets the control word's first damping).
 #pragma once
@@ -27,9 +28,9 @@ DEV LmVerdict lm_rule(bool kept, double candidate, double current, double noise,
 }
 
 // One decision of a loop whose control word lives in device memory and whose candidate is judged for all blocks at once (the
-// arrowhead estimators; rig_kernels.hip calls it): the first evaluation only installs the start -- a start that is not kept, or
-// that has no valid observation, ends the loop --, every later one asks lm_rule, and the iteration cap ends the loop at the
-// point kept. The status codes stay with the caller: it maps `outcome`.
+// arrowhead estimators: arrowhead_dev.hpp's lm_control_decide calls it): the first evaluation only installs the start -- a start
+// that is not kept, or that has no valid observation, ends the loop --, every later one asks lm_rule, and the iteration cap ends
+// the loop at the point kept. The status codes stay with the caller: it maps `outcome`.
 enum LmOutcome { kLmRunning = 0, kLmConverged = 1, kLmBadStart = 2, kLmOutOfIterations = 3 };
 struct LmLoopStep { bool accept; int outcome; double lambda; int iterations; };
 DEV LmLoopStep lm_loop_decision(bool first, bool kept, bool any_valid, double candidate, double current, double noise, bool small, double lambda,

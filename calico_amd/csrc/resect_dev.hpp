@@ -1,6 +1,7 @@
 // resect_dev.hpp — what the per-frame Levenberg-Marquardt kernels share (resect_kernels.hip: the pose of a frame at given
-// intrinsics; calib_kernels.hip: the intrinsics and the poses of all frames; rig_kernels.hip: a rig: views and rig frames): one wave per frame, wave-uniform small dense systems
-// in the wave's LDS area, quaternion helpers. The step rule itself is lm_rule.hpp's. Device code only.
+// intrinsics; calib_kernels.hip: the intrinsics and the poses of all frames; rig_kernels.hip: a rig: views and rig frames; all
+// three through arrowhead_dev.hpp): one wave per frame, wave-uniform small dense systems in the wave's LDS area, quaternion
+// helpers. The step rule itself is lm_rule.hpp's. Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -33,8 +33,8 @@
 #include <cstdint>
 
 #include "../../include/calico_hip.h"
+#include "arrowhead_dev.hpp"
 #include "kernels.hpp"
-#include "resect_dev.hpp"
 
 namespace cal {
 
@@ -91,8 +91,8 @@ DEV void resect_evaluate(const ResectArgs& a, int64_t base, int64_t n, int lane,
       a.flags[i] = uint8_t((fl & ~pose_bit(nxt)) | (ok ? pose_bit(nxt) : 0));
       if (ok) {
         const double e0 = pix[0] - u, e1 = pix[1] - v, sq = e0 * e0 + e1 * e1;
-        double w = 1.0, rho = sq;
-        if (hs > 0.0 && sq > hs2) { const double r = sqrt(sq); w = hs / r; rho = 2.0 * hs * r - hs2; }
+        double w, rho;
+        huber(sq, hs, hs2, &w, &rho);
         // d Pc / d delta = -[R P]x: row r of J is [(R P) x D_r, D_r]
         double J[2][6];
 #pragma unroll
@@ -314,7 +314,10 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
       const double tol = a.step_tolerance;
       small = uniform_flag(fmax(fmax(dabs(dr.x), dabs(dr.y)), dabs(dr.z)) < tol &&
                            fmax(fmax(dabs(dt.x), dabs(dt.y)), dabs(dt.z)) < tol * fmax(1.0, sqrt(dot(t, t))));
-      put_pose(slots + kSlot * (cur ^ 1), canonical(quat_mul(angle_axis_to_quat(dr), pose_q(cs))), t + dt, lane);
+      Q4 qn;
+      V3 tn;
+      (void)retract_pose(pose_q(cs), t, dr, dt, &qn, &tn);      // (this kernel's test of the step is the two comparisons above)
+      put_pose(slots + kSlot * (cur ^ 1), qn, tn, lane);
       wave_fence();
     }
   }
@@ -329,19 +332,7 @@ __global__ __launch_bounds__(kResectThreads, kResectWavesPerSimd) void resect_ke
         for (int c = 0; c <= r; ++c) W[6 * r + c] = cs[r * (r + 1) / 2 + c];
     wave_fence();
     bool ok = lds_chol(W, 6, lane);
-    // L^-1 column by column (lane c < 6 owns column c), then C = L^-T L^-1
-    if (lane < 6) {
-      for (int r = 0; r < 6; ++r) {
-        double v = r == lane ? 1.0 : 0.0;
-        for (int k = lane; k < r; ++k) v -= W[6 * r + k] * Li[6 * k + lane];
-        Li[6 * r + lane] = r < lane ? 0.0 : v / W[6 * r + r];
-      }
-    }
-    wave_fence();
-    if (lane < 36) {
-      const int r = lane / 6, c = lane - 6 * r;
-      for (int k = 0; k < 6; ++k) cov += Li[6 * k + r] * Li[6 * k + c];
-    }
+    chol_inverse_gram(W, Li, 6, lane, [&](int, int, int, double v) { cov = v; });      // (36 entries: one per lane)
     ok = ok && __all(__builtin_isfinite(cov)) && __builtin_isfinite(sqrt(cs[kSs] / cs[kValid]));
     if (uniform_flag(!ok)) { status = CALICO_RESECT_DEGENERATE; has_pose = false; }
   }

@@ -15,6 +15,7 @@
 #include "arg_rules.hpp"
 #include "free_call.hpp"
 #include "kernels.hpp"
+#include "lm_host.hpp"
 #include "lm_rule.hpp"
 
 namespace {
@@ -22,9 +23,6 @@ namespace {
 using namespace cal;
 
 static_assert(kRigMaxCameras == CALICO_RIG_MAX_CAMERAS, "the kernels' table of cameras is the header's");
-
-// LM cycles are enqueued kRigPollCycles at a time (chart.cpp's rule: between the groups the host reads the control word's first field)
-constexpr int kRigPollCycles = 6;
 
 // a rigid transform: unit quaternion (x, y, z, w) and translation
 struct Pose { double q[4] = {0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0}; };
@@ -185,6 +183,7 @@ int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* m
   } else {
     calico_resection_options ro;
     calico_default_resection_options(&ro);
+    ro.huber_scale = o.huber_scale; ro.min_points = o.min_points;
     for (int c = 0; c < C; ++c) {      // camera c's views: one batch of the resection, in frame order
       std::vector<size_t> mine;
       std::vector<int64_t> off(1, 0);
@@ -199,21 +198,15 @@ int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* m
         std::copy(s_px.begin() + 2 * s_off[s], s_px.begin() + 2 * s_off[s + 1], px.begin() + 2 * off[i]);
         std::copy(s_pt.begin() + 3 * s_off[s], s_pt.begin() + 3 * s_off[s + 1], pt.begin() + 3 * off[i]);
       }
-      FreeBuf<double> d_k, d_px, d_pt, d_ws, d_q, d_t, d_rms;
+      FreeBuf<double> d_k, d_px, d_pt;
       FreeBuf<int64_t> d_off;
-      FreeBuf<int32_t> d_used, d_it;
-      FreeBuf<uint8_t> d_fl, d_st;
+      FreeBuf<uint8_t> d_fl;
+      ResectRun run;
       FREE_TRY(call, d_k.upload(intrinsics + intrinsics_offsets[c], size_t(num_params[c])));
-      FREE_TRY(call, d_px.upload(px.data(), np * 2)); FREE_TRY(call, d_pt.upload(pt.data(), np * 3)); FREE_TRY(call, d_ws.alloc(np * 2));
+      FREE_TRY(call, d_px.upload(px.data(), np * 2)); FREE_TRY(call, d_pt.upload(pt.data(), np * 3));
       FREE_TRY(call, d_fl.alloc(np)); FREE_TRY(call, d_fl.zero(np)); FREE_TRY(call, d_off.upload(off.data(), nf + 1));
-      FREE_TRY(call, d_q.alloc(nf * 4)); FREE_TRY(call, d_t.alloc(nf * 3)); FREE_TRY(call, d_rms.alloc(nf)); FREE_TRY(call, d_used.alloc(nf));
-      FREE_TRY(call, d_it.alloc(nf)); FREE_TRY(call, d_st.alloc(nf));
-      ResectArgs ra = {};
-      ra.max_iterations = ro.max_iterations; ra.step_tolerance = ro.step_tolerance; ra.huber_scale = o.huber_scale; ra.min_points = o.min_points;
-      ra.k = d_k.p; ra.n_frames = int64_t(nf); ra.offsets = d_off.p; ra.pixels = d_px.p; ra.points = d_pt.p; ra.ws = d_ws.p; ra.flags = d_fl.p;
-      ra.q_out = d_q.p; ra.t_out = d_t.p; ra.rms_out = d_rms.p; ra.n_used_out = d_used.p; ra.iterations_out = d_it.p; ra.status_out = d_st.p;
-      FREE_TRY(call, launch_camera_resect(models[c], ra, nullptr));
-      FREE_TRY(call, d_q.download(q.data(), nf * 4)); FREE_TRY(call, d_t.download(t.data(), nf * 3)); FREE_TRY(call, d_st.download(st.data(), nf));
+      FREE_TRY(call, run.alloc(nf, np, false));
+      FREE_TRY(call, run.start(models[c], ro, d_k.p, nf, d_off.p, d_px.p, d_pt.p, d_fl.p, q.data(), t.data(), st.data()));
       for (size_t i = 0; i < nf; ++i) {
         vstat[mine[i]] = st[i];
         std::copy(&q[4 * i], &q[4 * i] + 4, view_pose[mine[i]].q); std::copy(&t[3 * i], &t[3 * i] + 3, view_pose[mine[i]].t);
@@ -289,7 +282,7 @@ int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* m
       std::copy(frame[f].q, frame[f].q + 4, ns); std::copy(frame[f].t, frame[f].t + 3, ns + 4);
     }
   RigControl ctrl = {};
-  ctrl.status = CALICO_RIG_NOT_CONVERGED; ctrl.first = 1; ctrl.lambda = kLmLambda0;
+  ctrl.lm.status = CALICO_RIG_NOT_CONVERGED; ctrl.lm.first = 1; ctrl.lm.lambda = kLmLambda0;
   for (int slot = 0; slot < 2; ++slot)
     for (int c = 0; c < C; ++c) {
       std::copy(cam[size_t(c)].q, cam[size_t(c)].q + 4, ctrl.cam[slot][c]); std::copy(cam[size_t(c)].t, cam[size_t(c)].t + 3, ctrl.cam[slot][c] + 4);
@@ -309,33 +302,29 @@ int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* m
   a.frames = d_frames.p; a.views = d_views.p; a.gram = d_gram.p; a.share = d_share.p;
   a.max_iterations = o.max_iterations; a.step_tolerance = o.step_tolerance; a.huber_scale = o.huber_scale;
   a.q_frame_out = d_q.p; a.t_frame_out = d_t.p; a.view_rms_out = d_rms.p; a.view_n_used_out = d_used.p; a.cov_out = d_cov.p;
-  // every cycle tries a step or raises lambda tenfold after a reduced system that was not positive definite (at most 24 times
-  // in a row): the loop ends on its own; the bound only guards the host against a control word that never moves
-  const int64_t max_cycles = 26 * (int64_t(o.max_iterations) + 2);
-  int done = 0;
-  for (int64_t cycle = 0; !done; cycle += kRigPollCycles) {
-    if (cycle > max_cycles) return call.fail(CALICO_INTERNAL, "the device loop did not end");
-    for (int i = 0; i < kRigPollCycles; ++i) {
-      for (int m = 1; m < 8; ++m) FREE_TRY(call, launch_rig_evaluate(m, a, d_lists[m].p, int(lists[size_t(m)].size()), nullptr));
-      FREE_TRY(call, launch_rig_decide(a, nullptr));
-      FREE_TRY(call, launch_rig_eliminate(a, false, nullptr)); FREE_TRY(call, launch_rig_reduce(a, false, nullptr));
-    }
-    FREE_TRY(call, hipMemcpy(&done, &d_ctrl.p->done, sizeof(int), hipMemcpyDeviceToHost));
-  }
+  const int rc = run_device_lm(call, &d_ctrl.p->lm.done, o.max_iterations, [&] {
+    hipError_t e = hipSuccess;
+    for (int m = 1; m < 8 && e == hipSuccess; ++m) e = launch_rig_evaluate(m, a, d_lists[m].p, int(lists[size_t(m)].size()), nullptr);
+    if (e == hipSuccess) e = launch_rig_decide(a, nullptr);
+    if (e == hipSuccess) e = launch_rig_eliminate(a, false, nullptr);
+    return e != hipSuccess ? e : launch_rig_reduce(a, false, nullptr);
+  });
+  if (rc != CALICO_OK) return rc;
   FREE_TRY(call, d_ctrl.download(&ctrl, 1));
-  if (ctrl.status != CALICO_RIG_DEGENERATE) {
+  const LmControl& lm = ctrl.lm;
+  if (lm.status != CALICO_RIG_DEGENERATE) {
     FREE_TRY(call, launch_rig_eliminate(a, true, nullptr)); FREE_TRY(call, launch_rig_reduce(a, true, nullptr));
     FREE_TRY(call, d_ctrl.download(&ctrl, 1));
   }
-  if (ctrl.status == CALICO_RIG_DEGENERATE || !ctrl.final_ok) {
-    give_starts(CALICO_RIG_DEGENERATE, ctrl.iterations, ctrl.lambda, false);
+  if (lm.status == CALICO_RIG_DEGENERATE || !lm.final_ok) {
+    give_starts(CALICO_RIG_DEGENERATE, lm.iterations, lm.lambda, false);
     return CALICO_OK;
   }
-  give_starts(ctrl.status, 0, 0.0, true);      // the held cameras, every camera's status
+  give_starts(lm.status, 0, 0.0, true);      // the held cameras, every camera's status
   for (int c = 0; c < C; ++c) {
     if (cam_status[size_t(c)] != CALICO_RIG_CAMERA_OK) continue;
-    std::copy(ctrl.cam[ctrl.cur][c], ctrl.cam[ctrl.cur][c] + 4, q_rig_camera_out + 4 * c);
-    std::copy(ctrl.cam[ctrl.cur][c] + 4, ctrl.cam[ctrl.cur][c] + 7, t_rig_camera_out + 3 * c);
+    std::copy(ctrl.cam[lm.cur][c], ctrl.cam[lm.cur][c] + 4, q_rig_camera_out + 4 * c);
+    std::copy(ctrl.cam[lm.cur][c] + 4, ctrl.cam[lm.cur][c] + 7, t_rig_camera_out + 3 * c);
   }
   FREE_TRY(call, d_q.download(q_frame_out, F * 4)); FREE_TRY(call, d_t.download(t_frame_out, F * 3));
   FREE_TRY(call, d_fst.download(frame_status_out, F));
@@ -348,10 +337,10 @@ int32_t calico_rig_calibrate(int32_t device, int32_t n_cameras, const int32_t* m
   }
   if (extrinsics_cov_out) FREE_TRY(call, d_cov.download(extrinsics_cov_out, size_t(M) * size_t(M)));
   *summary = calico_rig_summary{};
-  summary->status = ctrl.status; summary->iterations = ctrl.iterations; summary->initial_cost = ctrl.initial_cost;
-  summary->final_cost = ctrl.final_cost; summary->rms = ctrl.rms; summary->cameras_used = connected + 1;
-  summary->frames_used = ctrl.frames_used; summary->views_used = ctrl.views_used; summary->pairs_used = ctrl.pairs_used;
-  summary->lambda = ctrl.lambda;
+  summary->status = lm.status; summary->iterations = lm.iterations; summary->initial_cost = lm.initial_cost;
+  summary->final_cost = lm.final_cost; summary->rms = lm.rms; summary->cameras_used = connected + 1;
+  summary->frames_used = lm.frames_used; summary->views_used = ctrl.views_used; summary->pairs_used = lm.pairs_used;
+  summary->lambda = lm.lambda;
   return CALICO_OK;
 }
 

@@ -90,10 +90,11 @@ def test_entry_points_are_declared_listed_and_exported(api):
     assert callable(_capi.camera_calibrate) and callable(_capi.calibration_options)
     for f in ("calib_kernels.hip", "resect_dev.hpp"):      # no new environment switches
         assert "getenv" not in open(os.path.join(entry.CSRC, f)).read()
-    # the helpers the two per-frame LM kernels share are in one header, not copied
-    for f in ("calib_kernels.hip", "resect_kernels.hip"):
+    # the helpers the per-frame LM kernels share are in one header, not copied: resect_dev.hpp, which all three include through the
+    # arrowhead header
+    for f, header in (("calib_kernels.hip", "arrowhead_dev.hpp"), ("resect_kernels.hip", "arrowhead_dev.hpp"), ("arrowhead_dev.hpp", "resect_dev.hpp")):
         src = open(os.path.join(entry.CSRC, f)).read()
-        assert '#include "resect_dev.hpp"' in src and "lds_chol(double*" not in src, f
+        assert '#include "%s"' % header in src and "lds_chol(double*" not in src and "getenv" not in src, f
 
 
 def test_default_options(api):

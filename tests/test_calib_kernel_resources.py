@@ -2,7 +2,7 @@
 
 Budget: the per-frame evaluation kernel asks for two waves per SIMD (kCalibWavesPerSimd), that is at most 256 VGPRs, with no
 scratch and no spills -- 171 per-lane partial sums in FP64 (342 VGPRs) would not fit, the Gram matrix on the matrix cores does.
-As compiled: calib_evaluate_kernel<1..7> 190, 232, 222, 168, 225, 160, 168 VGPRs; LDS per workgroup of four waves
+As compiled: calib_evaluate_kernel<1..7> 191, 233, 223, 168, 226, 161, 168 VGPRs; LDS per workgroup of four waves
 4 x 64 x (K + 7) x 8 bytes = 30720, 36864, 28672, 24576, 22528, 22528, 24576 (9216 per wave at most); calib_eliminate_kernel 73
 VGPRs and 3456 bytes; calib_reduce_kernel 59 VGPRs and 11616 bytes; calib_decide_kernel 67 VGPRs, no LDS. ScratchSize 0 in all."""
 import os

@@ -151,10 +151,12 @@ def test_the_scaffold_is_defined_once():
     assert [f for f, src in sources.items() if re.search(r"#define\s+FREE_TRY\b", src)] == ["free_call.hpp"]
     assert [f for f, src in sources.items() if "no usable HIP device" in src] == ["free_call.hpp"]
     assert [f for f, src in sources.items() if re.search(r"handle_free_error\(\)\s*\{", src)] == ["calico_hip.cpp"]
-    # the step rule and its constants: one definition, three kernels that call it
+    # the step rule and its constants: one definition, two kernels that call it themselves; the two arrowhead estimators reach
+    # it through the one loop decision that the arrowhead header calls
     assert [f for f, src in sources.items() if "kCostSlack =" in src] == ["lm_rule.hpp"]
-    assert sorted(f for f, src in sources.items() if "lm_rule(" in src and f != "lm_rule.hpp") == ["align_kernels.hip", "calib_kernels.hip",
-                                                                                                   "resect_kernels.hip"]
+    assert sorted(f for f, src in sources.items() if "lm_rule(" in src and f != "lm_rule.hpp") == ["align_kernels.hip", "resect_kernels.hip"]
+    assert [f for f, src in sources.items() if "lm_loop_decision(" in src and f != "lm_rule.hpp"] == ["arrowhead_dev.hpp"]
+    assert sorted(f for f, src in sources.items() if "lm_control_decide(" in src) == ["arrowhead_dev.hpp", "calib_kernels.hip", "rig_kernels.hip"]
     # the camera-model dispatch: defined in kernels.hpp, used by the three launch files
     assert "with_camera_model(int model" in sources["kernels.hpp"]
     for f in ("camera_kernels.hip", "resect_kernels.hip", "calib_kernels.hip"):

@@ -96,11 +96,16 @@ def test_entry_points_are_declared_listed_and_exported(api):
         src = open(os.path.join(entry.CSRC, f)).read()
         assert "getenv" not in src and "hipMalloc(" not in src, f
     src = open(os.path.join(entry.CSRC, "rig_kernels.hip")).read()
-    # the step rule is lm_rule.hpp's: the decide kernel asks its loop decision, which asks lm_rule; no constants of its own
+    # the step rule is lm_rule.hpp's: the decide kernel asks the arrowhead header's decision, which asks the loop decision, which
+    # asks lm_rule; no constants of its own. The shared device code is one header, not a copy.
     rule = open(os.path.join(entry.CSRC, "lm_rule.hpp")).read()
-    assert '#include "resect_dev.hpp"' in src and "lds_chol(double*" not in src and "lm_loop_decision(" in src
+    shared = open(os.path.join(entry.CSRC, "arrowhead_dev.hpp")).read()
+    assert '#include "arrowhead_dev.hpp"' in src and '#include "resect_dev.hpp"' in shared
+    assert "lds_chol(double*" not in src and "lds_chol(double*" not in shared and "lm_control_decide(" in src
+    assert "= lm_loop_decision(" in shared
     assert 0 <= rule.find("LmLoopStep lm_loop_decision(") < rule.rfind("= lm_rule(") and "1e-4" not in src and "kCostSlack" not in src
-    assert "mfma_f64_16x16x4f64" in src and not re.search(r"\batomic[A-Z_a-z]*\(", src)
+    assert "1e-4" not in shared and "kCostSlack" not in shared
+    assert "mfma_f64_16x16x4f64" in src and not re.search(r"\batomic[A-Z_a-z]*\(", src + shared)
 
 
 def test_default_options(api):
