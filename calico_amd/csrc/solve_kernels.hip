@@ -1390,7 +1390,6 @@ DEVI void control_body(LmState* st_g, const LmOptionsDev& o, double* R2, double*
     s_accept = 0;
     finish_update(st, 0);
     const double cand_norm = st->cand_norm;
-    st->n_cost_evals += 1;
     st->iteration += 1;
     st->step_successful = 0; st->relative_decrease = 0.0; st->cost_change = 0.0;
     if (!st->step_valid) {
@@ -1405,6 +1404,7 @@ DEVI void control_body(LmState* st_g, const LmOptionsDev& o, double* R2, double*
       }
     } else {
       st->num_consecutive_invalid = 0;
+      st->n_cost_evals += 1;      // (Ceres counts no cost evaluation for an invalid step: the candidate is never looked at)
       const double ev_cost = pf.c01 ? pf.c01[0] : R2[0], ev_invalid = pf.c01 ? pf.c01[1] : R2[1];
       const double candidate_cost = (ev_invalid > 0.0) ? 1.7976931348623157e308 : ev_cost;
       st->candidate_cost = candidate_cost;

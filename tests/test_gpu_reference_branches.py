@@ -15,26 +15,10 @@ import pytest
 
 import helpers
 from calico_amd import _capi, synthetic as syn
+from solve_endings import (crafted_scene as _scene, ladder_scene, observe_all_points as _obs_all_points,
+                           static_points as _static_points)
 
 pytestmark = pytest.mark.gpu
-
-
-def _camera(model, intr, meas, stamps, pidx, latency=0.0, free_latency=False, free_extrinsics=False):
-    return syn.SensorSpec(_capi.SENSOR_CAMERA, model, "cam", np.asarray(intr, float), np.array([0.0, 0, 0, 1.0]), np.zeros(3),
-                          latency, np.asarray(intr, float), np.array([0.0, 0, 0, 1.0]), np.zeros(3), latency, True,
-                          free_extrinsics, free_latency, sigma=1.0, loss=0, loss_scale=1.0, meas=np.asarray(meas, float),
-                          stamps=np.asarray(stamps, float), point_idx=np.asarray(pidx, np.int32))
-
-
-def _scene(ctrl_fn, points, sensors_fn, t1=1.0, knot_frequency=10.0, order=6):
-    knots = syn.knot_vector(0.0, t1, order, knot_frequency)
-    basis = syn.basis_matrices(knots, order)
-    n_ctrl = len(knots) - order
-    ctrl = np.array([ctrl_fn(i) for i in range(n_ctrl)], float)
-    sc = syn.Scene(order, knots, basis, ctrl.copy(), ctrl.copy(), np.asarray(points, float), np.array([0.0, 0, 0, 1.0]), np.zeros(3),
-                   np.array([0.0, 0.0, -9.80665]), [])
-    sc.sensors = sensors_fn(sc)
-    return sc
 
 
 def _compare_evaluation(hip, oracle, scene, rtol=1e-9):
@@ -54,23 +38,6 @@ def _compare_evaluation(hip, oracle, scene, rtol=1e-9):
         assert np.array_equal(vg, vr)
         assert np.abs(rg - rr).max() <= rtol * max(1.0, np.abs(rr).max())
     return g, r
-
-
-def _static_points():
-    # camera at the origin looking down +z (all poses identity): the first point sits 5e-10 off the optical axis, inside
-    # the r < 1e-9 branch. (EXACTLY on the axis the reference's autodiff differentiates sqrt(x^2 + y^2) at 0 and hands
-    # Ceres a NaN Jacobian -- the oracle does the same; that input is a failed evaluation, not a branch to mirror.)
-    return np.array([[5e-10, 0.0, 1.0], [0.1, 0.0, 1.0], [0.0, -0.2, 1.5], [0.3, 0.25, 2.0], [-0.2, 0.1, 0.8], [1e-4, -2e-4, 1.0],
-                     [-0.4, -0.3, 1.2], [0.05, 0.4, 1.1]])
-
-
-def _obs_all_points(scene, stamps, model, intr, noise=0.3, seed=5, **kw):
-    rng = np.random.default_rng(seed)
-    spl = (scene.knots, scene.basis, scene.ctrl_true, scene.order)
-    px, valid, st, _, pidx = syn.project_camera(spl, model, np.asarray(intr, float), np.array([0.0, 0, 0, 1.0]), np.zeros(3), 0.0,
-                                                 np.asarray(stamps, float), scene.points, scene.body_q, scene.body_t)
-    assert valid.all()
-    return [_camera(model, intr, px + noise * rng.standard_normal(px.shape), st, pidx, **kw)]
 
 
 @pytest.mark.parametrize("theta", [0.0, 1e-8])
@@ -139,12 +106,7 @@ def test_candidate_that_cannot_be_evaluated_mid_solve(hip, oracle):
     a step pushes the point behind the camera, the candidate's cost cannot be evaluated, the step is rejected with
     cost 1.797693e+308 and the radius goes down the /2 /4 ladder -- rows 1-4 of the reference's Ceres table, here in the
     middle of a solve (found with the oracle; iterations 4 and 5)."""
-    cv = syn._TRUE_INTRINSICS[1].copy()
-    pts = _static_points().copy()
-    pts[5] = [0.002, -0.001, 0.01]
-    scene = _scene(lambda i: [0.0, 0.0, 0.0, 0.0, 0.0, 0.0], pts,
-                   lambda sc: _obs_all_points(sc, [0.05, 0.31, 0.52, 0.77], 1, cv, noise=0.0))
-    scene.ctrl = scene.ctrl + np.array([0.0, 0.0, 0.0, 0.0, 0.0, -0.03])
+    scene = ladder_scene()
     built = {}
     logs = {}
     for name, api in (("hip", hip), ("oracle", oracle)):
