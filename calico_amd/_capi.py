@@ -144,6 +144,21 @@ class ImuAlignmentSummary(C.Structure):
                 ("lambda_", C.c_double)]
 
 
+class CameraAlignmentOptions(C.Structure):
+    """calico_camera_alignment_options."""
+    _fields_ = [("max_lag", C.c_double), ("lag_step", C.c_double), ("max_iterations", C.c_int32), ("step_tolerance", C.c_double),
+                ("estimate_latency", C.c_int32), ("estimate_translation", C.c_int32), ("huber_scale", C.c_double),
+                ("min_points", C.c_int32), ("min_frames", C.c_int32), ("sigma_pixel", C.c_double)]
+
+
+class CameraAlignmentSummary(C.Structure):
+    """calico_camera_alignment_summary."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("frames_used", C.c_int64), ("pairs_used", C.c_int64),
+                ("n_lags", C.c_int32), ("peak_index", C.c_int32), ("coarse_latency", C.c_double), ("peak_score", C.c_double),
+                ("rms", C.c_double), ("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double)]
+
+
+CAMERA_ALIGN_FRAME_OUTSIDE = 6      # a frame status beside RESECT_*: outside the trajectory
 ALIGN_OK, ALIGN_TOO_FEW_SAMPLES, ALIGN_NO_PEAK, ALIGN_DEGENERATE, ALIGN_NOT_CONVERGED, ALIGN_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3, 4, 5
 ALIGN_MAX_LAGS = 4096
 
@@ -229,6 +244,7 @@ ABI_SYMBOLS = [
     "default_resection_options", "camera_resect",
     "default_calibration_options", "camera_calibrate",
     "default_imu_alignment_options", "imu_align",
+    "default_camera_alignment_options", "camera_align",
     "default_rig_options", "rig_calibrate",
     "default_spline_fit_options", "fit_spline_smooth",
 ]
@@ -330,6 +346,11 @@ class CApi:
                 g("default_imu_alignment_options", None, [AO])
                 g("imu_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int64, D, D, C.c_int64, D, D, D, D, D, AO,
                                            D, D, D, D, D, D, D, C.POINTER(ImuAlignmentSummary)])
+            if hasattr(self.lib, self.prefix + "camera_align"):
+                I64, CAO = C.POINTER(C.c_int64), C.POINTER(CameraAlignmentOptions)
+                g("default_camera_alignment_options", None, [CAO])
+                g("camera_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int32, D, C.c_int32, D, D, C.c_int64, D, I64, D, D,
+                                              D, D, D, CAO, D, D, D, D, I, U8, D, D, C.POINTER(CameraAlignmentSummary)])
             if hasattr(self.lib, self.prefix + "rig_calibrate"):
                 I64, RGO = C.POINTER(C.c_int64), C.POINTER(RigOptions)
                 g("default_rig_options", None, [RGO])
@@ -634,6 +655,55 @@ def imu_align(api, order, knots, basis, ctrl, gyro_stamps, gyro, accel_stamps=No
     solved = len(am) > 0 and summary.accel_status == ALIGN_OK
     out.update(q_rig_gyro=q, gyro_bias=bias, latency=float(lat[0]), gravity_world=grav if solved else None,
                accel_bias=abias if solved else None, cov=cov, curve=cur[:summary.n_lags] if curve else None)
+    if curve:
+        out["curve_tail"] = cur[summary.n_lags:]      # (never written by the library)
+    return out
+
+
+def camera_alignment_options(api, **kw):
+    """The library's default calico_camera_alignment_options with the given fields replaced."""
+    return _options(CameraAlignmentOptions, api.default_camera_alignment_options, "camera alignment", kw)
+
+
+def camera_align(api, order, knots, basis, ctrl, model, intrinsics, frame_stamps, frame_offsets, pixels, points, q_world_chart=None,
+                 t_world_chart=None, q_init=None, t_init=None, latency_init=None, options=None, covariance=False, curve=False, device=0):
+    """calico_camera_align: the extrinsics T_rig_camera and the latency of a camera against the spline (order, knots, basis, ctrl
+    (n_knots - order, 6)) from its chart detections at known intrinsics. frame_offsets (n_frames + 1) cuts pixels (N, 2) and chart
+    points (N, 3) into frames stamped frame_stamps (n_frames, sorted); (q_world_chart, t_world_chart): the chart's pose, None =
+    identity; q_init (x, y, z, w), t_init and latency_init together or none. options: a CameraAlignmentOptions
+    (camera_alignment_options(api, ...)) or None. Returns a dict: q_rig_camera, t_rig_camera, latency, frame_rms, frame_n_used,
+    frame_status, cov (7, 7) or None, curve (n_lags,) or None, and every field of the summary."""
+    knots, basis, ctrl = _f64(knots).ravel(), _f64(basis), _f64(ctrl).reshape(-1, 6)
+    order = int(order)
+    if len(ctrl) != len(knots) - order or basis.size != (len(knots) - 2 * order + 1) * order * order:
+        raise ValueError("ctrl must be (n_knots - order, 6) and basis (n_knots - 2 order + 1, order, order)")
+    k = _f64(intrinsics).ravel()
+    batch = _ChartBatch(frame_offsets, pixels, points, None, None)
+    nf = batch.nf
+    fs = _f64(frame_stamps).ravel()
+    if len(fs) != nf:
+        raise ValueError("one stamp per frame")
+
+    def opt(a, n):
+        return None if a is None else _f64(a).reshape(n)
+    qw, tw, qi, ti = opt(q_world_chart, 4), opt(t_world_chart, 3), opt(q_init, 4), opt(t_init, 3)
+    li = None if latency_init is None else _f64([latency_init]).reshape(1)
+    ptr = lambda a: None if a is None else _dp(a)      # noqa: E731
+    m = max(nf, 1)
+    q, t, lat = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3), np.zeros(1)
+    rms, used, status = np.zeros(m), np.zeros(m, np.int32), np.zeros(m, np.uint8)
+    cov = np.zeros((7, 7)) if covariance else None
+    cur = np.full(ALIGN_MAX_LAGS, np.nan) if curve else None
+    summary = CameraAlignmentSummary()
+    off = batch.arrays[0]
+    st = api.camera_align(int(device), order, len(knots), _dp(knots), _dp(basis), _dp(ctrl), int(model), _dp(k), k.size, ptr(qw), ptr(tw), nf,
+                          _dp(fs) if nf else None, off.ctypes.data_as(C.POINTER(C.c_int64)), batch.args[2], batch.args[3], ptr(qi), ptr(ti),
+                          ptr(li), None if options is None else C.byref(options), _dp(q), _dp(t), _dp(lat), _dp(rms), _ip(used),
+                          _u8p(status), ptr(cov), ptr(cur), C.byref(summary))
+    _check_free(api, st)
+    out = {name: getattr(summary, name) for name, _ in CameraAlignmentSummary._fields_}
+    out.update(q_rig_camera=q, t_rig_camera=t, latency=float(lat[0]), frame_rms=rms[:nf], frame_n_used=used[:nf], frame_status=status[:nf],
+               cov=cov, curve=cur[:summary.n_lags] if curve else None)
     if curve:
         out["curve_tail"] = cur[summary.n_lags:]      # (never written by the library)
     return out

@@ -281,3 +281,23 @@ def InitializeImu(trajectory, gyroscope, accelerometer=None, world_model=None, o
     if world_model is not None and accelerometer is not None:
         world_model.SetGravity([float(v) for v in r["gravity_world"]])
     return r
+
+
+def InitializeCamera(trajectory, camera, world_model, options=None) -> dict:
+    """The start of Optimize for a camera that is not synchronised with the trajectory's camera, from the trajectory
+    (Trajectory.FitSpline over the reference camera's poses) and this camera's registered measurements of rigid body 0:
+    Trajectory.AlignCamera (on the device) estimates the extrinsics T_rig_camera and the latency at the camera's current
+    intrinsics as a minimum of Optimize's own camera term with the trajectory held. Sets the camera's extrinsics and latency.
+    options: None or a dict of calico_camera_alignment_options fields. Returns AlignCamera's dict. Raises RuntimeError when the
+    alignment does not end with status OK, before anything is changed."""
+    r = trajectory.AlignCamera(camera, world_model, options)
+    if r["status"] != 0:
+        raise RuntimeError("Error: the camera alignment ended with status %d after %d iterations (%d frames)"
+                           % (r["status"], r["iterations"], r["frames_used"]))
+    x, y, z, w = r["q_rig_camera"]
+    T = camera.GetExtrinsics()
+    T.rotation = [w, x, y, z]
+    T.translation = [float(v) for v in r["t_rig_camera"]]
+    camera.SetExtrinsics(T)
+    camera.SetLatency(float(r["latency"]))
+    return r

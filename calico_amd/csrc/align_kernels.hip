@@ -35,7 +35,6 @@ constexpr int kAlignWaves = kAlignThreads / 64;
 constexpr double kAlignZeroVariance = 1e-12;
 // rotation about one axis only: the second eigenvalue of the scatter of omega_rig against the first
 constexpr double kAlignMinPivot = 1e-6;
-constexpr int kAlignJacobiSweeps = 12;
 
 DEV AlignSpline spline_of(const AlignArgs& a) {
   AlignSpline s;
@@ -79,37 +78,6 @@ DEV bool gyro_rates(const AlignSpline& sp, double stamp, double tau, V3* omega, 
   align_rates<false>(p0, p1, mk(0.0, 0.0, 0.0), omega, &unused);
   if constexpr (DOT) *omega_dot = align_omega_dot(p0, p1, mk(p[DOT ? 2 : 0][0], p[DOT ? 2 : 0][1], p[DOT ? 2 : 0][2]));
   return true;
-}
-
-// Eigenvalues (the diagonal of A afterwards) and eigenvectors (the columns of V) of a symmetric matrix by cyclic Jacobi; every
-// index is a compile-time constant.
-template <int N>
-DEV void align_jacobi(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-  for (int sweep = 0; sweep < kAlignJacobiSweeps; ++sweep) {
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
-        const bool turn = fabs(apq) > 1e-300;
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        if (!turn || !__builtin_isfinite(s) || !__builtin_isfinite(c)) { c = 1.0; s = 0.0; }
-#pragma unroll
-        for (int k = 0; k < N; ++k) { const double x = A[k][p], y = A[k][q]; A[k][p] = c * x - s * y; A[k][q] = s * x + c * y; }
-#pragma unroll
-        for (int k = 0; k < N; ++k) { const double x = A[p][k], y = A[q][k]; A[p][k] = c * x - s * y; A[q][k] = s * x + c * y; }
-#pragma unroll
-        for (int k = 0; k < N; ++k) { const double x = V[k][p], y = V[k][q]; V[k][p] = c * x - s * y; V[k][q] = s * x + c * y; }
-      }
-    }
-  }
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp), free of HIP:
+// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp, camera_align.cpp), free of HIP:
 // the standard library and the C header only, so a plain host program can test them (tests/cpp/arg_rules_check.cpp). A rule
 // returns an empty string for "fine", or the message without the call's name (FreeCall, free_call.hpp, puts that in front).
 #pragma once
@@ -115,6 +115,44 @@ inline std::string stamps_error(const char* name, int64_t n, const double* stamp
     if (!std::isfinite(stamps[i])) return std::string(name) + " stamp " + std::to_string(i) + " is not finite";
     if (i > 0 && stamps[i] < stamps[i - 1]) return std::string(name) + " stamps are not sorted: they decrease at sample " + std::to_string(i);
   }
+  return "";
+}
+
+// ---- the latency grid of calico_camera_align (calico_imu_align's rule): latency0 + l lag_step, |l| <= half ----
+// half_out: floor(max_lag / lag_step) with 1e-9 relative slack.
+inline std::string lag_grid_error(double max_lag, double lag_step, int max_lags, int* half_out) {
+  if (!std::isfinite(lag_step) || !(lag_step > 0.0)) return "lag_step must be finite and > 0";
+  if (!std::isfinite(max_lag) || max_lag < 0.0) return "max_lag must be finite and >= 0";
+  const double half = std::floor(max_lag / lag_step * (1.0 + 1e-9));
+  if (!(2.0 * half + 1.0 <= double(max_lags))) return "max_lag / lag_step gives more than " + std::to_string(max_lags) + " lags";
+  *half_out = int(half);
+  return "";
+}
+
+// ---- calico_camera_align: its options (the chart batch's rules hold too), T_world_chart and its start ----
+inline std::string camera_alignment_options_error(const calico_camera_alignment_options& o, int max_lags, int* half_out) {
+  const std::string error = lag_grid_error(o.max_lag, o.lag_step, max_lags, half_out);
+  if (!error.empty()) return error;
+  if (!std::isfinite(o.sigma_pixel) || !(o.sigma_pixel > 0.0)) return "sigma_pixel must be finite and > 0";
+  if (o.min_frames < 3) return "min_frames must be >= 3";
+  return "";
+}
+inline double quat_norm(const double* q);
+inline std::string camera_alignment_start_error(const double* q_world_chart, const double* t_world_chart, const double* q_init,
+                                                const double* t_init, const double* latency_init) {
+  if (q_world_chart) {
+    const double n = quat_norm(q_world_chart);
+    if (!std::isfinite(n) || !(n > 0.0)) return "q_world_chart must be finite and of non-zero length";
+  }
+  if (t_world_chart && !(std::isfinite(t_world_chart[0]) && std::isfinite(t_world_chart[1]) && std::isfinite(t_world_chart[2])))
+    return "t_world_chart must be finite";
+  const int given = (q_init ? 1 : 0) + (t_init ? 1 : 0) + (latency_init ? 1 : 0);
+  if (given != 0 && given != 3) return "q_init, t_init and latency_init are given together or not at all";
+  if (given == 0) return "";
+  const double n = quat_norm(q_init);
+  if (!std::isfinite(n) || !(n > 0.0)) return "q_init must be finite and of non-zero length";
+  if (!(std::isfinite(t_init[0]) && std::isfinite(t_init[1]) && std::isfinite(t_init[2]))) return "t_init must be finite";
+  if (!std::isfinite(*latency_init)) return "latency_init must be finite";
   return "";
 }
 

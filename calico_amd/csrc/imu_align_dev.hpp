@@ -1,4 +1,5 @@
-// imu_align_dev.hpp — what the camera-IMU alignment kernels (align_kernels.hip) need of the IMU items' kinematics, on a spline
+// imu_align_dev.hpp — what the alignment kernels (align_kernels.hip; camalign_kernels.hip takes the spline, the sums and the Jacobi
+// eigen-solver) need of the IMU items' kinematics, on a spline
 // that is not part of a problem: the segment of a time, the pose's derivatives there, and the rig's angular velocity and
 // acceleration as GyroscopeResidual / AccelerometerResidual form them (phi = -pose[0:3], omega = J(phi) phi', alpha = J' phi' +
 // J phi'', gyroscope_cost_functor.h / accelerometer_cost_functor.h through device_math.hpp's Rodrigues pieces). Device code only.
@@ -139,6 +140,38 @@ DEV double align_wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+
+constexpr int kAlignJacobiSweeps = 12;
+// Eigenvalues (the diagonal of A afterwards) and eigenvectors (the columns of V) of a symmetric matrix by cyclic Jacobi; every
+// index is a compile-time constant.
+template <int N>
+DEV void align_jacobi(double (&A)[N][N], double (&V)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int sweep = 0; sweep < kAlignJacobiSweeps; ++sweep) {
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
+        const bool turn = fabs(apq) > 1e-300;
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        if (!turn || !__builtin_isfinite(s) || !__builtin_isfinite(c)) { c = 1.0; s = 0.0; }
+#pragma unroll
+        for (int k = 0; k < N; ++k) { const double x = A[k][p], y = A[k][q]; A[k][p] = c * x - s * y; A[k][q] = s * x + c * y; }
+#pragma unroll
+        for (int k = 0; k < N; ++k) { const double x = A[p][k], y = A[q][k]; A[p][k] = c * x - s * y; A[q][k] = s * x + c * y; }
+#pragma unroll
+        for (int k = 0; k < N; ++k) { const double x = V[k][p], y = V[k][q]; V[k][p] = c * x - s * y; V[k][q] = s * x + c * y; }
+      }
+    }
+  }
 }
 
 }  // namespace cal

@@ -354,4 +354,67 @@ hipError_t launch_align_iteration(const AlignArgs& a, hipStream_t s);           
 hipError_t launch_align_finish(const AlignArgs& a, hipStream_t s);                 // the covariance and the RMS at the result
 hipError_t launch_align_gravity(const AlignArgs& a, hipStream_t s);                // stage D: the sums, the solve, the residual pass
 
+// ---- camera-to-trajectory alignment (camalign_kernels.hip): T_rig_camera and the camera's latency from a fitted trajectory -----
+// The frames are those that take part (the host packs them, in stamp order). The control word of the whole call, as AlignControl:
+// every kernel reads it, the single-workgroup kernels write it, no host read between the stages.
+constexpr int kCamAlignGram = 36;                        // the upper triangle of the 8 x 8 Gram matrix of sqrt(w) [J r], row-major
+constexpr int kCamAlignCostAt = 36;                      // Sum rho / sigma^2 over the valid pairs
+constexpr int kCamAlignSsAt = 37;                        // Sum |e|^2 over them, pixels^2, no loss
+constexpr int kCamAlignValidAt = 38;                     // their number
+constexpr int kCamAlignNoiseAt = 39;                     // the cost's rounding scale
+constexpr int kCamAlignSums = 40;                        // what a frame's slot holds
+constexpr int kCamAlignCommonAt = 2 * kCamAlignSums;     // Sum rho / sigma^2 of the candidate over the pairs valid at the current point
+constexpr int kCamAlignLostAt = kCamAlignCommonAt + 1;   // pairs valid at the current point that the candidate lost
+constexpr int kCamAlignFrameDoubles = 88;                // per frame: two slots, common, lost
+constexpr int kCamAlignPoseSums = 14;                    // Sum q q^T (10: xx xy xz xw yy yz yw zz zw ww), Sum t (3), Sum |t|^2
+constexpr int kCamAlignThreads = 256;                    // frames per workgroup of the pose sums
+constexpr int kCamAlignLagTile = 8;                      // lags per workgroup of the pose sums
+struct CamAlignControl {
+  int done;                     // != 0: every later launch of the loop returns at once
+  int status;                   // CALICO_ALIGN_*
+  int cur;                      // the slot of the current point
+  int first;                    // the start has not been evaluated yet
+  int iterations;
+  int peak_index;               // of the score curve (-1: no search)
+  int cov_ok;
+  int frames_used;              // frames that take part after the resection
+  long long pairs_used;
+  double lambda, step;          // step: the size of the step the candidate was made with
+  double initial_cost, final_cost, rms;
+  double coarse_latency, peak_score;
+  double d2;                    // the mean of |t_camera_chart|^2 over the frames that take part
+  double q[2][4], t[2][3], latency[2];      // the two slots
+  double G[2][kCamAlignSums];   // the summed frames of the two slots
+  double cov[49];
+};
+struct CamAlignArgs {
+  CamAlignControl* ctrl;
+  int order, n_valid;
+  const double* knots; const double* basis; const double* spline_ctrl;
+  const double* k;                                        // the camera's intrinsics
+  double q_wm[4], t_wm[3];                                // T_world_chart
+  int n_frames;                                           // frames that take part
+  const double* stamps;                                   // n_frames
+  const int64_t* offsets;                                 // n_frames + 1
+  const double* pixels; const double* points;
+  uint8_t* flags;                                         // N pairs: valid at slot 0 / 1 (pose_bit)
+  uint8_t* active;                                        // n_frames: the frame still takes part (the resection was OK)
+  uint8_t* frame_status;                                  // n_frames: CALICO_RESECT_*
+  const double* q_cm; const double* t_cm;                 // n_frames x 4 / x 3: T_camera_chart of the resection
+  const uint8_t* resect_status;                           // n_frames
+  const double* lags; int n_lags; double lag_step;        // the latencies of the grid
+  double* pose_part;                                      // chunks x n_lags x kCamAlignPoseSums
+  double* curve;                                          // n_lags
+  double* frames;                                         // n_frames x kCamAlignFrameDoubles
+  unsigned free_bits;                                     // bit i: parameter i of (rotation 3, translation 3, latency 1) is estimated
+  int max_iterations; double step_tolerance; double inv_sigma; double huber_scale; int min_frames;
+  double* frame_rms_out; int* frame_n_used_out;           // n_frames
+};
+int camalign_chunks(int n);                                                          // workgroups of the pose sums
+hipError_t launch_camalign_gate(const CamAlignArgs& a, hipStream_t s);               // after the resection: who takes part, d^2
+hipError_t launch_camalign_search(const CamAlignArgs& a, hipStream_t s);             // stage A: the pose sums per lag, the curve, its minimum
+hipError_t launch_camalign_mean(const CamAlignArgs& a, hipStream_t s);               // stage B: the mean pose at the coarse latency into slot 1
+hipError_t launch_camalign_iteration(int model, const CamAlignArgs& a, hipStream_t s);      // stage C: evaluate the candidate, decide and step
+hipError_t launch_camalign_finish(const CamAlignArgs& a, hipStream_t s);             // covariance, RMS, per-frame outputs
+
 }  // namespace cal

@@ -1,5 +1,5 @@
 // lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip and
-// align_kernels.hip call it themselves, calib_kernels.hip and rig_kernels.hip through arrowhead_dev.hpp): accept or reject a
+// align_kernels.hip call it themselves, calib_kernels.hip, rig_kernels.hip and camalign_kernels.hip through arrowhead_dev.hpp): accept or reject a
 // candidate, the next damping, and whether the loop has converged.
 // What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
 // a damped system is not positive definite. Host and device code (the host sets the control word's first damping).

@@ -161,6 +161,28 @@ calico_imu_alignment_options imu_alignment_options(const py::object& options) {
   }
   return o;
 }
+// options: None or a dict of calico_camera_alignment_options fields
+calico_camera_alignment_options camera_alignment_options(const py::object& options) {
+  calico_camera_alignment_options o;
+  calico_default_camera_alignment_options(&o);
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "max_lag") o.max_lag = py::cast<double>(kv.second);
+      else if (name == "lag_step") o.lag_step = py::cast<double>(kv.second);
+      else if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+      else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+      else if (name == "estimate_latency") o.estimate_latency = py::cast<int>(kv.second);
+      else if (name == "estimate_translation") o.estimate_translation = py::cast<int>(kv.second);
+      else if (name == "huber_scale") o.huber_scale = py::cast<double>(kv.second);
+      else if (name == "min_points") o.min_points = py::cast<int>(kv.second);
+      else if (name == "min_frames") o.min_frames = py::cast<int>(kv.second);
+      else if (name == "sigma_pixel") o.sigma_pixel = py::cast<double>(kv.second);
+      else throw py::type_error("no camera alignment option '" + name + "'");
+    }
+  }
+  return o;
+}
 // None, or a dict of calico_spline_fit_options fields; lambda_rot / lambda_pos: a number or a sequence (n_lambda follows its length)
 calico_spline_fit_options spline_fit_options(const py::object& options) {
   calico_spline_fit_options o;
@@ -637,6 +659,41 @@ PYBIND11_MODULE(_calico, m) {
              return out;
            },
            py::arg("gyroscope"), py::arg("accelerometer") = py::none(), py::arg("options") = py::none(), py::arg("covariance") = false,
+           py::arg("curve") = false, py::arg("device") = 0)
+      // Alignment of a camera that is not synchronised with this trajectory, from its registered measurements of the rigid body
+      // model_id (calico_camera_align). options: None or a dict of calico_camera_alignment_options fields. Returns a dict:
+      // q_rig_camera (x, y, z, w), t_rig_camera, latency, image_ids, stamps, frame_rms, frame_n_used, frame_status, cov and curve
+      // (each on request) and the summary's fields. The camera is not changed.
+      .def("AlignCamera",
+           [](const Trajectory& self, const Camera& camera, const WorldModel& world_model, const py::object& options, int model_id,
+              bool covariance, bool curve, int device) {
+             const calico_camera_alignment_options o = camera_alignment_options(options);
+             auto res = self.AlignCamera(camera, world_model, &o, model_id, covariance, curve, device);
+             raise_if_error(res.status());
+             const Trajectory::CameraAlignment& r = res.value();
+             const Quaterniond& q = r.T_rig_camera.rotation();
+             const Vector3d& t = r.T_rig_camera.translation();
+             py::dict out;
+             out["q_rig_camera"] = to_array(VectorXd{q.x(), q.y(), q.z(), q.w()});
+             out["t_rig_camera"] = to_array(VectorXd{t[0], t[1], t[2]});
+             out["latency"] = r.latency;
+             out["image_ids"] = r.image_ids; out["stamps"] = to_array(r.stamps); out["frame_rms"] = to_array(r.frame_rms);
+             out["frame_n_used"] = std::vector<int>(r.frame_n_used.begin(), r.frame_n_used.end());
+             out["frame_status"] = std::vector<int>(r.frame_status.begin(), r.frame_status.end());
+             if (curve) out["curve"] = to_array(r.curve);
+             if (covariance) {
+               py::array_t<double> cov({py::ssize_t(7), py::ssize_t(7)});
+               std::copy(r.cov.begin(), r.cov.end(), cov.mutable_data());
+               out["cov"] = cov;
+             }
+             const calico_camera_alignment_summary& sm = r.summary;
+             out["status"] = sm.status; out["iterations"] = sm.iterations; out["frames_used"] = sm.frames_used; out["pairs_used"] = sm.pairs_used;
+             out["n_lags"] = sm.n_lags; out["peak_index"] = sm.peak_index; out["coarse_latency"] = sm.coarse_latency;
+             out["peak_score"] = sm.peak_score; out["rms"] = sm.rms; out["initial_cost"] = sm.initial_cost; out["final_cost"] = sm.final_cost;
+             out["lambda"] = sm.lambda;
+             return out;
+           },
+           py::arg("camera"), py::arg("world_model"), py::arg("options") = py::none(), py::arg("model_id") = 0, py::arg("covariance") = false,
            py::arg("curve") = false, py::arg("device") = 0);
 
   py::class_<Landmark, std::shared_ptr<Landmark>>(m, "Landmark")

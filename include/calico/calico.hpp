@@ -682,6 +682,7 @@ class BSpline6 {
 };
 
 namespace sensors { class Gyroscope; class Accelerometer; }
+class WorldModel;
 
 class Trajectory {
  public:
@@ -780,6 +781,29 @@ class Trajectory {
   StatusOr<ImuAlignment> AlignImu(const sensors::Gyroscope& gyroscope, const sensors::Accelerometer* accelerometer = nullptr,
                                   const calico_imu_alignment_options* options = nullptr, bool covariance = false, bool curve = false,
                                   int device = 0) const;
+  /// What AlignCamera returns: calico_camera_align's outputs. The frames are the camera's images of the rigid body, in stamp
+  /// order: image_ids, stamps and, per frame, the RMS pixel residual, the pairs used and the status (CALICO_RESECT_* or
+  /// CALICO_CAMERA_ALIGN_FRAME_OUTSIDE); cov (7 x 7, row-major: rotation 3, translation 3, latency 1) and curve (summary.n_lags
+  /// scores) are filled on request.
+  struct CameraAlignment {
+    Pose3d T_rig_camera;
+    double latency = 0.0;
+    std::vector<int> image_ids;
+    std::vector<double> stamps, frame_rms;
+    std::vector<int32_t> frame_n_used;
+    std::vector<uint8_t> frame_status;
+    std::vector<double> cov, curve;
+    calico_camera_alignment_summary summary{};
+    bool Ok() const { return summary.status == CALICO_ALIGN_OK; }
+  };
+  /// Alignment of a camera that is not synchronised with this trajectory (calico_camera_align, on the device): its extrinsics
+  /// T_rig_camera and its latency at its current intrinsics, from its registered measurements (AddMeasurement) of the rigid body
+  /// model_id that are not marked as outliers, grouped by image_id (a frame's stamp is its measurements'), with the body's
+  /// model definition and pose. The camera is read, not changed (utils.InitializeCamera / the caller sets it). A Status that is
+  /// not OK is an argument error or a device error; how the estimation ended is summary.status.
+  StatusOr<CameraAlignment> AlignCamera(const sensors::Camera& camera, const WorldModel& world_model,
+                                        const calico_camera_alignment_options* options = nullptr, int model_id = 0, bool covariance = false,
+                                        bool curve = false, int device = 0) const;
  private:
   std::map<double, Pose3d> poses_;
   BSpline6 spline_;
@@ -1318,6 +1342,7 @@ class Camera : public SensorCommon {
   }
   Status MarkOutliersById(const std::vector<CameraObservationId>& ids) { for (const auto& id : ids) { const Status st = MarkOutlierById(id); if (!st.ok()) return st; } return OkStatus(); }
   void ClearOutliersList() { outlier_ids_.clear(); }
+  bool IsOutlier(const CameraObservationId& id) const { return outlier_ids_.count(id) != 0; }
   void ClearMeasurements() { id_to_measurement_.clear(); residual_order_.clear(); id_to_residual_.clear(); outlier_ids_.clear(); }
   int NumberOfMeasurements() const { return int(id_to_measurement_.size()); }
  private:
@@ -1528,6 +1553,56 @@ inline StatusOr<Trajectory::ImuAlignment> Trajectory::AlignImu(const sensors::Gy
                                   r.gravity_world.data(), r.accel_bias.data(), covariance ? r.cov.data() : nullptr, curve ? r.curve.data() : nullptr, &r.summary);
   if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
   r.q_rig_gyro = Quaterniond(q[3], q[0], q[1], q[2]);
+  if (curve) r.curve.resize(size_t(r.summary.n_lags));
+  return r;
+}
+
+inline StatusOr<Trajectory::CameraAlignment> Trajectory::AlignCamera(const sensors::Camera& camera, const WorldModel& world_model,
+                                                                     const calico_camera_alignment_options* options, int model_id,
+                                                                     bool covariance, bool curve, int device) const {
+  if (camera.GetModel() == sensors::CameraIntrinsicsModel::kNone) return FailedPreconditionError("Camera model has not been set!");
+  const auto body_it = world_model.rigidbodies().find(model_id);
+  if (body_it == world_model.rigidbodies().end())
+    return InvalidArgumentError("AlignCamera: no rigid body with id " + std::to_string(model_id) + " in the world model");
+  const RigidBody& body = *body_it->second;
+  // the body's images: (stamp, image id) -> feature id -> pixel, so frames come in stamp order and pairs in id order
+  std::map<std::pair<double, int>, std::map<int, Vector2d>> frames;
+  for (const auto& [id, m] : camera.GetMeasurementIdToMeasurement()) {
+    if (id.model_id != model_id || camera.IsOutlier(id)) continue;
+    frames[{id.stamp, id.image_id}][id.feature_id] = m.pixel;
+  }
+  CameraAlignment r;
+  std::vector<int64_t> offsets(1, 0);
+  std::vector<Vector2d> pixels;
+  std::vector<Vector3d> points;
+  for (const auto& [key, frame] : frames) {
+    for (const auto& [feature, pixel] : frame) {
+      const auto it = body.model_definition.find(feature);
+      if (it == body.model_definition.end())
+        return InvalidArgumentError("AlignCamera: feature " + std::to_string(feature) + " is not in the model definition");
+      pixels.push_back(pixel);
+      points.push_back(it->second);
+    }
+    r.stamps.push_back(key.first); r.image_ids.push_back(key.second);
+    offsets.push_back(int64_t(pixels.size()));
+  }
+  const size_t F = r.stamps.size();
+  std::vector<double> ctrl;
+  for (const auto& c : spline_.control_points()) ctrl.insert(ctrl.end(), c.begin(), c.end());
+  r.frame_rms.assign(F, 0.0); r.frame_n_used.assign(F, 0); r.frame_status.assign(F, 0);
+  if (covariance) r.cov.assign(49, 0.0);
+  if (curve) r.curve.assign(CALICO_ALIGN_MAX_LAGS, 0.0);
+  double q[4] = {0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
+  static_assert(sizeof(Vector2d) == 2 * sizeof(double) && sizeof(Vector3d) == 3 * sizeof(double), "pixels and points are packed");
+  const int st = calico_camera_align(device, spline_.GetSplineOrder(), int(spline_.knots().size()), spline_.knots().data(),
+                                     spline_.basis_matrices().data(), ctrl.data(), int(camera.GetModel()), camera.GetIntrinsics().data(),
+                                     int(camera.GetIntrinsics().size()), body.T_world_rigidbody.rotation().data(),
+                                     body.T_world_rigidbody.translation().data(), int64_t(F), r.stamps.data(), offsets.data(),
+                                     pixels.empty() ? nullptr : pixels[0].data(), points.empty() ? nullptr : points[0].data(), nullptr, nullptr,
+                                     nullptr, options, q, t, &r.latency, r.frame_rms.data(), r.frame_n_used.data(), r.frame_status.data(),
+                                     covariance ? r.cov.data() : nullptr, curve ? r.curve.data() : nullptr, &r.summary);
+  if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+  r.T_rig_camera = Pose3d(Quaterniond(q[3], q[0], q[1], q[2]), Vector3d(t[0], t[1], t[2]));
   if (curve) r.curve.resize(size_t(r.summary.n_lags));
   return r;
 }

@@ -137,7 +137,7 @@ int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
  * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
- * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align); like a handle's message it
+ * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align, calico_camera_align); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -930,6 +930,98 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
                          const calico_imu_alignment_options* o /* NULL = defaults */, double* q_rig_gyro_out, double* gyro_bias_out,
                          double* latency_out, double* gravity_world_out, double* accel_bias_out, double* cov_out /* 49, may be NULL */,
                          double* curve_out /* n_lags, may be NULL */, calico_imu_alignment_summary* summary);
+
+/* ---- camera-to-trajectory alignment: extrinsics and latency of a camera that is not synchronised with the trajectory ---- */
+/* The camera-side twin of calico_imu_align: the start calico_solve needs for a camera that shares no instant with the reference
+ * camera (calico_rig_calibrate needs rig frames), from the trajectory fitted to the reference camera's poses and this camera's raw
+ * chart detections at known intrinsics, on the device. The model is the optimiser's own camera term with the trajectory held:
+ *   t = stamp - latency,  p = pose(t),  R_rw = R(quat(-p[0:3])),  t_wr = p[3:6],
+ *   x_camera = R_rc^T (R_rw (R_wm x_chart + t_wm - t_wr) - t_rc),  residual = (pixel - project(intrinsics, x_camera)) / sigma_pixel,
+ * with (q_rc, t_rc) = T_rig_camera and (q_wm, t_wm) = T_world_chart (q_world_chart, t_world_chart; NULL = identity / 0), so the
+ * result is a minimum of calico_solve's camera cost over (extrinsics, latency) at the given trajectory. As there the spline
+ * segment of a frame is the STAMP's; its polynomial is evaluated at t, beyond its own knots where the latency carries t there.
+ *   spline  as calico_imu_align takes it.  frames  frame_offsets (n_frames + 1) cuts pixels (N x 2) and chart points (N x 3) into
+ *          frames, as calico_camera_resect takes them; frame_stamps (n_frames) do not decrease.
+ *   frames that take part: at least min_points pairs (the others: CALICO_RESECT_TOO_FEW_POINTS), and the stamp and the time
+ *          stamp - latency inside the valid knots for EVERY latency of the grid  latency_init (or 0) + l lag_step,
+ *          |l lag_step| <= max_lag (1e-9 relative slack on l) -- when stage A does not run (a start is given, or
+ *          estimate_latency == 0): at latency_init (or 0) alone (the others: CALICO_CAMERA_ALIGN_FRAME_OUTSIDE). Fewer than
+ *          min_frames: CALICO_ALIGN_TOO_FEW_SAMPLES.
+ *   R      (no start given) every frame that takes part is resected at `intrinsics` (calico_camera_resect's kernel with the same
+ *          huber_scale and min_points, its defaults otherwise); a frame whose resection is not CALICO_RESECT_OK drops out with
+ *          the resection's status. Fewer than min_frames are left: CALICO_ALIGN_TOO_FEW_SAMPLES.
+ *   A      (no start given, estimate_latency != 0) per latency tau of the grid and frame i the estimate
+ *          E_i(tau) = T_rig_world(stamp_i - tau) T_world_chart T_chart_camera_i of T_rig_camera, and
+ *          score(tau) = 4 (1 - lambda_max(Sum q q^T) / n) + (Sum |t|^2 / n - |mean t|^2) / d^2 -- the scatter of the rotations
+ *          (rad^2) plus that of the translations under the angle the camera sees it, d^2 the mean of |t_camera_chart_i|^2.
+ *          The minimum, refined by the parabola through its two neighbours, is the coarse latency. CALICO_ALIGN_NO_PEAK: the
+ *          minimum lies on the first or the last latency of the grid, or the curve's range is below 1e-12 of its maximum (or of
+ *          1 rad^2 where the maximum itself is rounding): a rig at rest.
+ *   B      (no start given) at the coarse latency (0 without A) q_rig_camera is the principal eigenvector of Sum q q^T (w >= 0),
+ *          t_rig_camera the mean translation (0 with estimate_translation == 0).
+ *   C      Levenberg-Marquardt on (rotation 3: R <- exp([d]x) R, translation 3, latency 1) with analytic Jacobians -- the
+ *          latency column through the first derivative of the stamp's segment --, Huber's loss on the pixel residual
+ *          (huber_scale, pixels; 0 = none; weights rho', no second-order term), Marquardt damping lambda diag from 1e-4 within
+ *          [1e-12, 1e12]; what is not estimated is held. calico_camera_calibrate's rules: the costs compared are those over
+ *          the pairs valid at the current point, a candidate within the cost's own rounding error of the current one is accepted,
+ *          one at which the model rejects a pair that is valid at the current point is rejected; step size
+ *          s = max(|d_rot|_inf, |d_t|_inf / max(1, |t|_inf), |d_latency| / max(1, |latency|)); endings as calico_imu_align:
+ *          CALICO_ALIGN_OK, _NOT_CONVERGED, _NOT_POSITIVE_DEFINITE, and _DEGENERATE for a start that is not finite or has no
+ *          valid pair.
+ * Outputs: q_rig_camera_out (4: x y z w, unit, w >= 0), t_rig_camera_out (3), latency_out -- the start (q_init normalised or the
+ * identity, t_init or 0, latency_init or 0) with TOO_FEW_SAMPLES, NO_PEAK and DEGENERATE; per frame the RMS pixel residual (no
+ * loss), the valid pairs and the status (CALICO_RESECT_*, or CALICO_CAMERA_ALIGN_FRAME_OUTSIDE; a frame that took no part, and
+ * every frame unless the status is OK or NOT_CONVERGED, has rms = 0 and n_used = 0); cov_out (7 x 7, may be NULL): the undamped
+ * (J^T W J)^-1 of (rotation, translation, latency) at the result, zero rows and columns for what is held, all zero unless the
+ * status is OK or NOT_CONVERGED; curve_out (may be NULL): the first summary->n_lags entries are the score curve when stage A ran,
+ * the others are never written.
+ * The call returns CALICO_OK whenever `summary` is meaningful. Repeated calls are bit-identical: every sum has a fixed order.
+ * Needs no problem handle: owns its device memory, message in calico_last_error(NULL).
+ * CALICO_INVALID_ARGUMENT, before the device is touched: calico_imu_align's rules for the spline and the grid, calico_camera_resect's
+ * for the model, the intrinsics and the frames, frame stamps that decrease or are not finite, a start given in part, not finite
+ * or with a q_init of zero length, a q_world_chart that is not finite or of zero length, step_tolerance <= 0, sigma_pixel <= 0,
+ * huber_scale < 0, max_iterations < 1, min_points < 4, min_frames < 3, a NULL output or summary. n_frames == 0 is CALICO_OK
+ * with CALICO_ALIGN_TOO_FEW_SAMPLES and touches no device. */
+#define CALICO_CAMERA_ALIGN_FRAME_OUTSIDE 6      /* frame status: the stamp, or stamp - latency for a latency of the grid, lies outside the valid knots */
+typedef struct {
+  double max_lag;               /* 0.1 s */
+  double lag_step;              /* 1e-3 s */
+  int32_t max_iterations;       /* 50 */
+  double step_tolerance;        /* 1e-10 */
+  int32_t estimate_latency;     /* 1 */
+  int32_t estimate_translation; /* 1 */
+  double huber_scale;           /* 0 = no loss; pixels */
+  int32_t min_points;           /* 4 */
+  int32_t min_frames;           /* 8; values below 3 are an argument error */
+  double sigma_pixel;           /* 1: the camera's sigma in calico_problem_add_sensor (scales the costs and the covariance) */
+} calico_camera_alignment_options;
+typedef struct {
+  int32_t status;               /* CALICO_ALIGN_* */
+  int32_t iterations;           /* steps tried */
+  int64_t frames_used;          /* frames that took part (after the resection) */
+  int64_t pairs_used;           /* pairs valid at the result */
+  int32_t n_lags;               /* latencies of the grid (0: stage A did not run) */
+  int32_t peak_index;           /* of the curve's minimum (-1: stage A did not run) */
+  double coarse_latency;        /* the parabola's (the start's latency without stage A) */
+  double peak_score;            /* the curve's minimum */
+  double rms;                   /* pixels, no loss: sqrt(Sum |pixel - projection|^2 / pairs_used) */
+  double initial_cost;          /* 1/2 Sum rho(|pixel - projection|^2) / sigma_pixel^2 at the start of stage C and at the result */
+  double final_cost;
+  double lambda;                /* the damping at the end */
+} calico_camera_alignment_summary;
+void calico_default_camera_alignment_options(calico_camera_alignment_options* o);
+int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                            const double* ctrl /* (n_knots - order) x 6 */, int32_t model, const double* intrinsics,
+                            int32_t n_intrinsics, const double* q_world_chart /* 4 xyzw, NULL = identity */,
+                            const double* t_world_chart /* 3, NULL = 0 */, int64_t n_frames,
+                            const double* frame_stamps /* n_frames, non-decreasing */, const int64_t* frame_offsets /* n_frames + 1 */,
+                            const double* pixels /* N x 2 */, const double* points /* N x 3, chart frame */,
+                            const double* q_init /* 4 */, const double* t_init /* 3 */,
+                            const double* latency_init /* 1; all three or none */,
+                            const calico_camera_alignment_options* o /* NULL = defaults */, double* q_rig_camera_out,
+                            double* t_rig_camera_out, double* latency_out, double* frame_rms_out, int32_t* frame_n_used_out,
+                            uint8_t* frame_status_out /* CALICO_RESECT_* */, double* cov_out /* 7 x 7, may be NULL */,
+                            double* curve_out /* n_lags, may be NULL */, calico_camera_alignment_summary* summary);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
