@@ -158,6 +158,20 @@ class CameraAlignmentSummary(C.Structure):
                 ("rms", C.c_double), ("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double)]
 
 
+class AccelAlignmentOptions(C.Structure):
+    """calico_accel_alignment_options."""
+    _fields_ = [("max_iterations", C.c_int32), ("step_tolerance", C.c_double), ("estimate_rotation", C.c_int32),
+                ("estimate_lever_arm", C.c_int32), ("estimate_bias", C.c_int32), ("estimate_gravity", C.c_int32),
+                ("estimate_latency", C.c_int32), ("min_samples", C.c_int32), ("sigma_accel", C.c_double)]
+
+
+class AccelAlignmentSummary(C.Structure):
+    """calico_accel_alignment_summary."""
+    _fields_ = [("status", C.c_int32), ("linear_status", C.c_int32), ("samples", C.c_int64), ("first_sample", C.c_int64),
+                ("iterations", C.c_int32), ("rms", C.c_double), ("linear_rms", C.c_double), ("gravity_norm", C.c_double),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("lambda_", C.c_double)]
+
+
 CAMERA_ALIGN_FRAME_OUTSIDE = 6      # a frame status beside RESECT_*: outside the trajectory
 ALIGN_OK, ALIGN_TOO_FEW_SAMPLES, ALIGN_NO_PEAK, ALIGN_DEGENERATE, ALIGN_NOT_CONVERGED, ALIGN_NOT_POSITIVE_DEFINITE = 0, 1, 2, 3, 4, 5
 ALIGN_MAX_LAGS = 4096
@@ -245,6 +259,7 @@ ABI_SYMBOLS = [
     "default_calibration_options", "camera_calibrate",
     "default_imu_alignment_options", "imu_align",
     "default_camera_alignment_options", "camera_align",
+    "default_accel_alignment_options", "accel_align",
     "default_rig_options", "rig_calibrate",
     "default_spline_fit_options", "fit_spline_smooth",
 ]
@@ -346,6 +361,11 @@ class CApi:
                 g("default_imu_alignment_options", None, [AO])
                 g("imu_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int64, D, D, C.c_int64, D, D, D, D, D, AO,
                                            D, D, D, D, D, D, D, C.POINTER(ImuAlignmentSummary)])
+            if hasattr(self.lib, self.prefix + "accel_align"):
+                XO = C.POINTER(AccelAlignmentOptions)
+                g("default_accel_alignment_options", None, [XO])
+                g("accel_align", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, D, C.c_int64, D, D, D, D, D, D, D, XO,
+                                             D, D, D, D, D, D, C.POINTER(AccelAlignmentSummary)])
             if hasattr(self.lib, self.prefix + "camera_align"):
                 I64, CAO = C.POINTER(C.c_int64), C.POINTER(CameraAlignmentOptions)
                 g("default_camera_alignment_options", None, [CAO])
@@ -657,6 +677,44 @@ def imu_align(api, order, knots, basis, ctrl, gyro_stamps, gyro, accel_stamps=No
                accel_bias=abias if solved else None, cov=cov, curve=cur[:summary.n_lags] if curve else None)
     if curve:
         out["curve_tail"] = cur[summary.n_lags:]      # (never written by the library)
+    return out
+
+
+def accel_alignment_options(api, **kw):
+    """The library's default calico_accel_alignment_options with the given fields replaced."""
+    return _options(AccelAlignmentOptions, api.default_accel_alignment_options, "accelerometer alignment", kw)
+
+
+def accel_align(api, order, knots, basis, ctrl, stamps, accel, q_init, latency_init, t_init=None, bias_init=None, gravity_init=None,
+                options=None, covariance=False, device=0):
+    """calico_accel_align: the rotation rig <- accelerometer, its lever arm, its bias, the world's gravity and its latency against
+    the spline (order, knots, basis, ctrl (n_knots - order, 6)). accel (n, 3) at stamps (n, sorted); q_init (x, y, z, w) and
+    latency_init are required (calico_imu_align's for the gyroscope); t_init, bias_init and gravity_init all three or none.
+    options: an AccelAlignmentOptions (accel_alignment_options(api, ...)) or None. Returns a dict: q_rig_accel, t_rig_accel, bias,
+    gravity_world, latency, cov (13, 13) or None, and every field of the summary."""
+    knots, basis, ctrl = _f64(knots).ravel(), _f64(basis), _f64(ctrl).reshape(-1, 6)
+    order = int(order)
+    if len(ctrl) != len(knots) - order or basis.size != (len(knots) - 2 * order + 1) * order * order:
+        raise ValueError("ctrl must be (n_knots - order, 6) and basis (n_knots - 2 order + 1, order, order)")
+    s, m = _f64(stamps).ravel(), _f64(accel).reshape(-1, 3)
+    if len(s) != len(m):
+        raise ValueError("one stamp per sample")
+
+    def vec(a, n):
+        return None if a is None else _f64(a).reshape(n)
+    qi, ti, bi, gi = vec(q_init, 4), vec(t_init, 3), vec(bias_init, 3), vec(gravity_init, 3)
+    li = None if latency_init is None else _f64([latency_init]).reshape(1)
+    ptr = lambda a: None if a is None else _dp(a)      # noqa: E731
+    q, t, bias, grav, lat = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3), np.zeros(3), np.zeros(3), np.zeros(1)
+    cov = np.zeros((13, 13)) if covariance else None
+    summary = AccelAlignmentSummary()
+    st = api.accel_align(int(device), order, len(knots), _dp(knots), _dp(basis), _dp(ctrl), len(m), _dp(s) if len(m) else None,
+                         _dp(m) if len(m) else None, ptr(qi), ptr(li), ptr(ti), ptr(bi), ptr(gi),
+                         None if options is None else C.byref(options), _dp(q), _dp(t), _dp(bias), _dp(grav), _dp(lat), ptr(cov),
+                         C.byref(summary))
+    _check_free(api, st)
+    out = {name: getattr(summary, name) for name, _ in AccelAlignmentSummary._fields_}
+    out.update(q_rig_accel=q, t_rig_accel=t, bias=bias, gravity_world=grav, latency=float(lat[0]), cov=cov)
     return out
 
 

@@ -4,5 +4,5 @@ the helpers of calico/utils.py) over the MI355X HIP backend. The extension modul
 from .._calico import *  # noqa: F401,F403
 from .._calico import __doc__ as _backend_doc  # noqa: F401
 from .utils import (ComputeRmseHeatmapAndFeatureCount, DetectionsToCameraMeasurements,  # noqa: F401
-                    InitialIntrinsics, InitializeCamera, InitializeImu, InitializeIntrinsicsAndPoses, InitializePinholeAndPoses, InitializePoses,
+                    InitialIntrinsics, InitializeAccelerometer, InitializeCamera, InitializeImu, InitializeIntrinsicsAndPoses, InitializePinholeAndPoses, InitializePoses,
                     InitializeRig)

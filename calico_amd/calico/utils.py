@@ -283,6 +283,37 @@ def InitializeImu(trajectory, gyroscope, accelerometer=None, world_model=None, o
     return r
 
 
+def InitializeAccelerometer(trajectory, accelerometer, world_model=None, options=None) -> dict:
+    """The accelerometer's start of Optimize where no data sheet gives its mounting, after InitializeImu (which leaves it the
+    gyroscope's rotation and latency and does not touch its translation): Trajectory.AlignAccelerometer (on the device) estimates
+    its rotation, its lever arm, its bias, the world's gravity and its latency as a minimum of Optimize's own accelerometer term
+    with the trajectory held, started at the sensor's current rotation and latency. Sets the rotation AND the translation of the
+    extrinsics, the latency, the bias intrinsics (the scale and every other intrinsic are left as they are, and a scale-only
+    model has no bias to set) and, given a world model, its gravity. options: None or a dict of calico_accel_alignment_options
+    fields. Returns AlignAccelerometer's dict. Raises RuntimeError when the alignment does not end with status OK, or for a
+    sensor whose model has not been set, before anything is changed."""
+    if int(accelerometer.GetModel()) not in _IMU_BIAS_AT:
+        raise RuntimeError("Error: InitializeAccelerometer does not know where IMU model %d keeps its bias" % int(accelerometer.GetModel()))
+    r = trajectory.AlignAccelerometer(accelerometer, options)
+    if r["status"] != 0:
+        raise RuntimeError("Error: the accelerometer alignment ended with status %d (linear stage %d) after %d iterations (%d samples)"
+                           % (r["status"], r["linear_status"], r["iterations"], r["samples"]))
+    x, y, z, w = r["q_rig_accel"]
+    T = accelerometer.GetExtrinsics()
+    T.rotation = [w, x, y, z]
+    T.translation = [float(v) for v in r["t_rig_accel"]]
+    accelerometer.SetExtrinsics(T)
+    accelerometer.SetLatency(float(r["latency"]))
+    at = _IMU_BIAS_AT[int(accelerometer.GetModel())]
+    if at is not None:
+        k = np.array(accelerometer.GetIntrinsics(), float)
+        k[at:at + 3] = r["bias"]
+        accelerometer.SetIntrinsics(k)
+    if world_model is not None:
+        world_model.SetGravity([float(v) for v in r["gravity_world"]])
+    return r
+
+
 def InitializeCamera(trajectory, camera, world_model, options=None) -> dict:
     """The start of Optimize for a camera that is not synchronised with the trajectory's camera, from the trajectory
     (Trajectory.FitSpline over the reference camera's poses) and this camera's registered measurements of rigid body 0:

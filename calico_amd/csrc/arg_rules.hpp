@@ -1,4 +1,4 @@
-// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp, camera_align.cpp), free of HIP:
+// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp, camera_align.cpp, accel_align.cpp), free of HIP:
 // the standard library and the C header only, so a plain host program can test them (tests/cpp/arg_rules_check.cpp). A rule
 // returns an empty string for "fine", or the message without the call's name (FreeCall, free_call.hpp, puts that in front).
 #pragma once

@@ -417,4 +417,47 @@ hipError_t launch_camalign_mean(const CamAlignArgs& a, hipStream_t s);          
 hipError_t launch_camalign_iteration(int model, const CamAlignArgs& a, hipStream_t s);      // stage C: evaluate the candidate, decide and step
 hipError_t launch_camalign_finish(const CamAlignArgs& a, hipStream_t s);             // covariance, RMS, per-frame outputs
 
+// ---- accelerometer alignment (accalign_kernels.hip): rotation, lever arm, bias, gravity and latency from a fitted trajectory ----
+// The samples are those that take part (the host's range). The control word of the whole call, as AlignControl: every kernel
+// reads it, the single-wave kernels write it, no host read between the stages.
+constexpr int kAccAlignParams = 13;                      // rotation 3, lever arm 3, bias 3, gravity 3, latency 1
+constexpr int kAccAlignCols = 14;                        // [J | r]: the columns of the Gram matrix (one 16 x 16 accumulator tile)
+constexpr int kAccAlignGram = kAccAlignCols * kAccAlignCols;      // full and symmetric, row-major
+constexpr int kAccAlignCostAt = kAccAlignGram - 1;       // its last entry, (13, 13): Sum |r|^2
+constexpr int kAccAlignBadAt = kAccAlignGram;            // residuals that are not finite
+constexpr int kAccAlignNoiseAt = kAccAlignGram + 1;      // the cost's rounding scale
+constexpr int kAccAlignCountAt = kAccAlignGram + 2;      // samples evaluated
+constexpr int kAccAlignSums = kAccAlignGram + 3;         // what a workgroup of the evaluation sums
+constexpr int kAccAlignPart = 200;                       // doubles per workgroup of the partials (>= kAccAlignSums)
+constexpr int kAccAlignThreads = 256;                    // samples per workgroup of the evaluation
+constexpr int kAccAlignLinear = 9;                       // stage L: lever arm, bias, gravity (parameters 3 .. 11)
+constexpr int kAccAlignStageLinear = 0, kAccAlignStageRefine = 1, kAccAlignStageLoop = 2;
+struct AccAlignControl {
+  int done;                     // != 0: every later launch returns at once
+  int status, linear_status;    // CALICO_ALIGN_* (linear_status -1: stage L did not run)
+  int stage;                    // kAccAlignStage*
+  int cur;                      // the slot of the current point
+  int first;                    // the loop's start has not been evaluated yet
+  int iterations;
+  int cov_ok;
+  double lambda, step;          // step: the size of the step the candidate was made with
+  double initial_cost, final_cost, rms, linear_rms;
+  double q[2][4], t[2][3], bias[2][3], gravity[2][3], latency[2];      // the two slots
+  double G[2][kAccAlignPart];   // the summed partials of the two slots
+  double cov[kAccAlignParams * kAccAlignParams];
+};
+struct AccAlignArgs {
+  AccAlignControl* ctrl;
+  int order, n_valid;
+  const double* knots; const double* basis; const double* spline_ctrl;
+  const double* stamps; const double* meas;               // the samples that take part: n of them
+  int n;
+  double* part;                                           // chunks x kAccAlignPart
+  unsigned free_bits;                                     // bit i: parameter i is estimated
+  int max_iterations; double step_tolerance; double inv_sigma;
+};
+int accalign_chunks(int n);                                                          // workgroups of the evaluation
+hipError_t launch_accalign_iteration(const AccAlignArgs& a, hipStream_t s);          // evaluate the candidate; stage L's solve, or decide and step
+hipError_t launch_accalign_finish(const AccAlignArgs& a, hipStream_t s);             // the covariance and the RMS at the result
+
 }  // namespace cal

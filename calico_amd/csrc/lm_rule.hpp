@@ -1,5 +1,5 @@
 // lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip and
-// align_kernels.hip call it themselves, calib_kernels.hip, rig_kernels.hip and camalign_kernels.hip through arrowhead_dev.hpp): accept or reject a
+// align_kernels.hip call it themselves, calib_kernels.hip, rig_kernels.hip and camalign_kernels.hip through arrowhead_dev.hpp, accalign_kernels.hip through lm_point_decision): accept or reject a
 // candidate, the next damping, and whether the loop has converged.
 // What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
 // a damped system is not positive definite. Host and device code (the host sets the control word's first damping).
@@ -47,6 +47,13 @@ DEV LmLoopStep lm_loop_decision(bool first, bool kept, bool any_valid, double ca
   if (s.outcome == kLmRunning && iterations >= max_iterations) s.outcome = kLmOutOfIterations;
   if (s.outcome == kLmRunning) ++s.iterations;
   return s;
+}
+
+// The same decision for a loop over ONE point (accalign_kernels.hip): there is no block that could be left without a valid
+// observation, the samples that take part are fixed by the host.
+DEV LmLoopStep lm_point_decision(bool first, bool kept, double candidate, double current, double noise, bool small, double lambda, int iterations,
+                                 int max_iterations) {
+  return lm_loop_decision(first, kept, true, candidate, current, noise, small, lambda, iterations, max_iterations);
 }
 
 }  // namespace cal

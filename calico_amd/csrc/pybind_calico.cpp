@@ -161,6 +161,27 @@ calico_imu_alignment_options imu_alignment_options(const py::object& options) {
   }
   return o;
 }
+// options: None or a dict of calico_accel_alignment_options fields
+calico_accel_alignment_options accel_alignment_options(const py::object& options) {
+  calico_accel_alignment_options o;
+  calico_default_accel_alignment_options(&o);
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+      else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+      else if (name == "estimate_rotation") o.estimate_rotation = py::cast<int>(kv.second);
+      else if (name == "estimate_lever_arm") o.estimate_lever_arm = py::cast<int>(kv.second);
+      else if (name == "estimate_bias") o.estimate_bias = py::cast<int>(kv.second);
+      else if (name == "estimate_gravity") o.estimate_gravity = py::cast<int>(kv.second);
+      else if (name == "estimate_latency") o.estimate_latency = py::cast<int>(kv.second);
+      else if (name == "min_samples") o.min_samples = py::cast<int>(kv.second);
+      else if (name == "sigma_accel") o.sigma_accel = py::cast<double>(kv.second);
+      else throw py::type_error("no accelerometer alignment option '" + name + "'");
+    }
+  }
+  return o;
+}
 // options: None or a dict of calico_camera_alignment_options fields
 calico_camera_alignment_options camera_alignment_options(const py::object& options) {
   calico_camera_alignment_options o;
@@ -660,6 +681,37 @@ PYBIND11_MODULE(_calico, m) {
            },
            py::arg("gyroscope"), py::arg("accelerometer") = py::none(), py::arg("options") = py::none(), py::arg("covariance") = false,
            py::arg("curve") = false, py::arg("device") = 0)
+      // Alignment of an accelerometer against this trajectory from its registered measurements, started at its current rotation
+      // and latency (calico_accel_align). options: None or a dict of calico_accel_alignment_options fields. Returns a dict:
+      // q_rig_accel (x, y, z, w), t_rig_accel, bias, gravity_world, latency, cov (on request) and the summary's fields. The sensor
+      // is not changed.
+      .def("AlignAccelerometer",
+           [](const Trajectory& self, const Accelerometer& accelerometer, const py::object& options, bool covariance, int device) {
+             const calico_accel_alignment_options o = accel_alignment_options(options);
+             auto res = self.AlignAccelerometer(accelerometer, &o, covariance, device);
+             raise_if_error(res.status());
+             const Trajectory::AccelerometerAlignment& r = res.value();
+             const Quaterniond& q = r.T_rig_accel.rotation();
+             const Vector3d& t = r.T_rig_accel.translation();
+             py::dict out;
+             out["q_rig_accel"] = to_array(VectorXd{q.x(), q.y(), q.z(), q.w()});
+             out["t_rig_accel"] = to_array(VectorXd{t[0], t[1], t[2]});
+             out["bias"] = to_array(VectorXd{r.bias[0], r.bias[1], r.bias[2]});
+             out["gravity_world"] = to_array(VectorXd{r.gravity_world[0], r.gravity_world[1], r.gravity_world[2]});
+             out["latency"] = r.latency;
+             if (covariance) {
+               py::array_t<double> cov({py::ssize_t(13), py::ssize_t(13)});
+               std::copy(r.cov.begin(), r.cov.end(), cov.mutable_data());
+               out["cov"] = cov;
+             }
+             const calico_accel_alignment_summary& sm = r.summary;
+             out["status"] = sm.status; out["linear_status"] = sm.linear_status; out["samples"] = sm.samples;
+             out["first_sample"] = sm.first_sample; out["iterations"] = sm.iterations; out["rms"] = sm.rms; out["linear_rms"] = sm.linear_rms;
+             out["gravity_norm"] = sm.gravity_norm; out["initial_cost"] = sm.initial_cost; out["final_cost"] = sm.final_cost;
+             out["lambda"] = sm.lambda;
+             return out;
+           },
+           py::arg("accelerometer"), py::arg("options") = py::none(), py::arg("covariance") = false, py::arg("device") = 0)
       // Alignment of a camera that is not synchronised with this trajectory, from its registered measurements of the rigid body
       // model_id (calico_camera_align). options: None or a dict of calico_camera_alignment_options fields. Returns a dict:
       // q_rig_camera (x, y, z, w), t_rig_camera, latency, image_ids, stamps, frame_rms, frame_n_used, frame_status, cov and curve

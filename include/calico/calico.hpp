@@ -781,6 +781,25 @@ class Trajectory {
   StatusOr<ImuAlignment> AlignImu(const sensors::Gyroscope& gyroscope, const sensors::Accelerometer* accelerometer = nullptr,
                                   const calico_imu_alignment_options* options = nullptr, bool covariance = false, bool curve = false,
                                   int device = 0) const;
+  /// What AlignAccelerometer returns: calico_accel_align's outputs; cov (13 x 13, row-major: rotation 3, lever arm 3, bias 3,
+  /// gravity 3, latency 1) is filled on request.
+  struct AccelerometerAlignment {
+    Pose3d T_rig_accel;
+    Vector3d bias{0, 0, 0}, gravity_world{0, 0, 0};
+    double latency = 0.0;
+    std::vector<double> cov;
+    calico_accel_alignment_summary summary{};
+    bool Ok() const { return summary.status == CALICO_ALIGN_OK; }
+  };
+  /// Alignment of an accelerometer against this trajectory (calico_accel_align, on the device): its rotation, its lever arm, its
+  /// bias, the world's gravity and its latency, from its registered measurements (AddMeasurement) in time order. The start is
+  /// the sensor's current rotation and latency (what AlignImu / utils.InitializeImu found for the gyroscope of the same unit);
+  /// lever arm, bias and gravity start from the call's own linear stage, so all three are estimated. The sensor is read, not
+  /// changed (utils.InitializeAccelerometer / the caller sets it). A Status that is not OK is an argument error or a device
+  /// error; how the estimation ended is summary.status.
+  StatusOr<AccelerometerAlignment> AlignAccelerometer(const sensors::Accelerometer& accelerometer,
+                                                      const calico_accel_alignment_options* options = nullptr, bool covariance = false,
+                                                      int device = 0) const;
   /// What AlignCamera returns: calico_camera_align's outputs. The frames are the camera's images of the rigid body, in stamp
   /// order: image_ids, stamps and, per frame, the RMS pixel residual, the pairs used and the status (CALICO_RESECT_* or
   /// CALICO_CAMERA_ALIGN_FRAME_OUTSIDE); cov (7 x 7, row-major: rotation 3, translation 3, latency 1) and curve (summary.n_lags
@@ -1554,6 +1573,26 @@ inline StatusOr<Trajectory::ImuAlignment> Trajectory::AlignImu(const sensors::Gy
   if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
   r.q_rig_gyro = Quaterniond(q[3], q[0], q[1], q[2]);
   if (curve) r.curve.resize(size_t(r.summary.n_lags));
+  return r;
+}
+
+inline StatusOr<Trajectory::AccelerometerAlignment> Trajectory::AlignAccelerometer(const sensors::Accelerometer& accelerometer,
+                                                                                   const calico_accel_alignment_options* options,
+                                                                                   bool covariance, int device) const {
+  std::vector<double> as, a, ctrl;
+  accelerometer.SortedMeasurements(&as, &a);
+  for (const auto& c : spline_.control_points()) ctrl.insert(ctrl.end(), c.begin(), c.end());
+  const Quaterniond& q0 = accelerometer.GetExtrinsics().rotation();
+  const double q_init[4] = {q0.x(), q0.y(), q0.z(), q0.w()}, latency_init = accelerometer.GetLatency();
+  AccelerometerAlignment r;
+  double q[4] = {0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
+  if (covariance) r.cov.assign(169, 0.0);
+  const int st = calico_accel_align(device, spline_.GetSplineOrder(), int(spline_.knots().size()), spline_.knots().data(),
+                                    spline_.basis_matrices().data(), ctrl.data(), int64_t(as.size()), as.data(), a.data(), q_init, &latency_init,
+                                    nullptr, nullptr, nullptr, options, q, t, r.bias.data(), r.gravity_world.data(), &r.latency,
+                                    covariance ? r.cov.data() : nullptr, &r.summary);
+  if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+  r.T_rig_accel = Pose3d(Quaterniond(q[3], q[0], q[1], q[2]), Vector3d(t[0], t[1], t[2]));
   return r;
 }
 

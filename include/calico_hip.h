@@ -137,7 +137,7 @@ int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
  * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
- * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align, calico_camera_align); like a handle's message it
+ * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align, calico_camera_align, calico_accel_align); like a handle's message it
  * is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
@@ -1022,6 +1022,83 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
                             double* t_rig_camera_out, double* latency_out, double* frame_rms_out, int32_t* frame_n_used_out,
                             uint8_t* frame_status_out /* CALICO_RESECT_* */, double* cov_out /* 7 x 7, may be NULL */,
                             double* curve_out /* n_lags, may be NULL */, calico_camera_alignment_summary* summary);
+
+/* ---- accelerometer alignment: rotation, lever arm, bias, gravity and latency from a fitted trajectory ---- */
+/* The third sibling of calico_imu_align and calico_camera_align: the start calico_solve needs for an accelerometer whose
+ * mounting is not known from a data sheet, on the device. calico_imu_align's stage D takes the accelerometer's rotation and
+ * latency from the gyroscope and its lever arm as given; this call estimates all of it. The model is the optimiser's own
+ * accelerometer term with the scale-and-bias model at scale 1 and the trajectory held, exactly as stage D states it:
+ *   t = stamp - latency,  phi = -pose[0:3](t),  omega = J(phi) phi',  alpha = Sum_i (H_i(phi) phi') phi'_i + J(phi) phi''
+ *   (ExpSO3Hessian's closed form, which is not d omega / d t),
+ *   prediction = R(q_rig_accel)^T (R(phi) (pose''[3:6](t) - gravity) + omega x (omega x t_rig_accel) - alpha x t_rig_accel) + bias,
+ *   residual = (measured - prediction) / sigma_accel,
+ * so the result is a minimum of calico_solve's accelerometer cost over (rotation, lever arm, bias, gravity, latency) at the given
+ * trajectory. As there the spline segment of a sample is the STAMP's; its polynomial is evaluated at t, beyond its own knots
+ * where the latency carries t there. The latency column is the derivative of that expression as it stands (through the closed
+ * form of alpha and the pose's third derivative).
+ *   spline  as calico_imu_align takes it.
+ *   samples those whose stamp and whose time stamp - latency_init lie inside the valid knots; the stamps are sorted, so they are
+ *          one range [first_sample, first_sample + samples), fixed for the whole call. Fewer than min_samples:
+ *          CALICO_ALIGN_TOO_FEW_SAMPLES.
+ *   start  q_init and latency_init are required (what calico_imu_align returned for the gyroscope of the same unit). t_init,
+ *          bias_init and gravity_init are given all three or none; with none, all three groups must be estimated and
+ *   L      the model being linear in (lever arm, bias, gravity) at fixed rotation and latency, one evaluation at zero forms the
+ *          Gram matrix whose 9 x 9 block a Cholesky solves, and one step of iterative refinement follows from a second
+ *          evaluation. summary->linear_status and linear_rms are the stage's; CALICO_ALIGN_NOT_POSITIVE_DEFINITE (or
+ *          CALICO_ALIGN_DEGENERATE for a residual that is not finite) there ends the call with the start in the outputs.
+ *   loop   Levenberg-Marquardt on (rotation 3: R <- exp([d]x) R, lever arm 3, bias 3, gravity 3, latency 1) with analytic
+ *          Jacobians and calico_imu_align's rules: damping lambda diag from 1e-4 within [1e-12, 1e12], what is not estimated
+ *          (estimate_* == 0) is held, a candidate within the cost's own rounding error is accepted, one with a residual that is
+ *          not finite is rejected; step size s = the largest over the groups of |d|_inf / max(1, |value|_inf), the rotation
+ *          unscaled; endings CALICO_ALIGN_OK, _NOT_CONVERGED (the last accepted point), _NOT_POSITIVE_DEFINITE (at the largest
+ *          damping or, undamped, at the result), _DEGENERATE (a start that is not finite).
+ * Outputs: q_rig_accel_out (4: x y z w, unit, w >= 0), t_rig_accel_out (3), bias_out (3), gravity_world_out (3), latency_out
+ * -- the start (q_init normalised, latency_init, the three given or zero) with TOO_FEW_SAMPLES, DEGENERATE and a stage L that
+ * is not OK; cov_out (13 x 13, may be NULL): the undamped (J^T J)^-1 in that order of the parameters at the result, zero rows
+ * and columns for what is held, all zero unless the status is OK or NOT_CONVERGED. summary->rms and linear_rms are in m/s^2
+ * (sqrt(Sum |measured - prediction|^2 / (3 samples))), the costs 1/2 Sum |residual|^2.
+ * The call returns CALICO_OK whenever `summary` is meaningful. Repeated calls are bit-identical: every sum has a fixed order.
+ * Needs no problem handle: owns its device memory, message in calico_last_error(NULL).
+ * CALICO_INVALID_ARGUMENT, before the device is touched: calico_imu_align's rules for the spline, the count, the stamps and
+ * the outputs; a NULL q_init or latency_init, one that is not finite, a q_init of zero length; t_init, bias_init and
+ * gravity_init not all three or none, or not finite; none of them with one of their groups held; an option that is not
+ * finite, step_tolerance <= 0, sigma_accel <= 0, max_iterations < 1, min_samples < 5. n == 0 is CALICO_OK with
+ * CALICO_ALIGN_TOO_FEW_SAMPLES and touches no device.
+ * Out of scope: the scale and the misalignment intrinsics of the other IMU models (the scale is 1), a constraint on the norm of
+ * gravity (summary->gravity_norm reports it), and a search over the latency (the gyroscope's alignment supplies the start). */
+typedef struct {
+  int32_t max_iterations;       /* 50 */
+  double step_tolerance;        /* 1e-10 */
+  int32_t estimate_rotation;    /* 1 */
+  int32_t estimate_lever_arm;   /* 1 */
+  int32_t estimate_bias;        /* 1 */
+  int32_t estimate_gravity;     /* 1 */
+  int32_t estimate_latency;     /* 1 */
+  int32_t min_samples;          /* 16; values below 5 are an argument error */
+  double sigma_accel;           /* 1: the accelerometer's sigma in calico_problem_add_sensor (scales the covariance and the costs) */
+} calico_accel_alignment_options;
+typedef struct {
+  int32_t status;               /* CALICO_ALIGN_* */
+  int32_t linear_status;        /* stage L's; -1: it did not run */
+  int64_t samples;              /* samples that took part */
+  int64_t first_sample;         /* index of the first of them */
+  int32_t iterations;           /* steps tried */
+  double rms;                   /* m/s^2, at the result */
+  double linear_rms;            /* m/s^2, at stage L's solution before its refinement step */
+  double gravity_norm;
+  double initial_cost;          /* 1/2 Sum |residual|^2 at the start of the loop and at the result */
+  double final_cost;
+  double lambda;                /* the damping at the end */
+} calico_accel_alignment_summary;
+void calico_default_accel_alignment_options(calico_accel_alignment_options* o);
+int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                           const double* ctrl /* (n_knots - order) x 6 */, int64_t n, const double* stamps /* n, non-decreasing */,
+                           const double* accel /* n x 3 */, const double* q_init /* 4 xyzw */, const double* latency_init /* 1 */,
+                           const double* t_init /* 3 */, const double* bias_init /* 3 */,
+                           const double* gravity_init /* 3; all three or none */,
+                           const calico_accel_alignment_options* o /* NULL = defaults */, double* q_rig_accel_out,
+                           double* t_rig_accel_out, double* bias_out, double* gravity_world_out, double* latency_out,
+                           double* cov_out /* 13 x 13, may be NULL */, calico_accel_alignment_summary* summary);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
