@@ -26,6 +26,7 @@
 #include "../../include/calico_hip.h"
 #include "imu_align_dev.hpp"
 #include "kernels.hpp"
+#include "point_lm_dev.hpp"
 #include "resect_dev.hpp"
 
 namespace cal {
@@ -36,10 +37,6 @@ constexpr int kAccAlignWaves = kAccAlignThreads / 64;
 constexpr int kAccAlignRow = 16;                          // doubles of a staged row: 14 columns and two zeros
 constexpr int kAccAlignArea = 64 * kAccAlignRow;          // a wave's staging area: 8 KB
 typedef double acc_f64x4 __attribute__((ext_vector_type(4)));
-
-DEV bool accalign_runs(int status) { return status == CALICO_ALIGN_OK || status == CALICO_ALIGN_NOT_CONVERGED; }
-DEV bool bit(unsigned bits, int i) { return ((bits >> i) & 1u) != 0u; }
-DEV double amax3(const double* v) { return fmax(fabs(v[0]), fmax(fabs(v[1]), fabs(v[2]))); }
 
 DEV D1 pick(bool c, D1 a, D1 b) { D1 r; r.v = c ? a.v : b.v; r.d = c ? a.d : b.d; return r; }
 DEV D1 dual(double v, double d) { D1 r; r.v = v; r.d = d; return r; }
@@ -87,9 +84,9 @@ __global__ __launch_bounds__(kAccAlignThreads) void accalign_eval_kernel(AccAlig
   __shared__ double s_x[kAccAlignWaves * kAccAlignArea];
   __shared__ double s_w[kAccAlignWaves][4];
   const AccAlignControl* const c = a.ctrl;
-  if (c->done != 0) return;
+  if (c->lm.done != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int slot = c->cur ^ 1;
+  const int slot = c->lm.cur ^ 1;
   Q4 q; q.x = c->q[slot][0]; q.y = c->q[slot][1]; q.z = c->q[slot][2]; q.w = c->q[slot][3];
   const V3 tra = mk(c->t[slot][0], c->t[slot][1], c->t[slot][2]);
   const V3 b = mk(c->bias[slot][0], c->bias[slot][1], c->bias[slot][2]);
@@ -97,8 +94,7 @@ __global__ __launch_bounds__(kAccAlignThreads) void accalign_eval_kernel(AccAlig
   const double tau = c->latency[slot], is = a.inv_sigma;
   const M3 Ra = rotmat(q);
   const int i = blockIdx.x * kAccAlignThreads + threadIdx.x;
-  AlignSpline sp;
-  sp.k = a.order; sp.n_valid = a.n_valid; sp.knots = a.knots; sp.basis = a.basis; sp.ctrl = a.spline_ctrl;
+  const AlignSpline& sp = a.spline;
   double* const area = s_x + wave * kAccAlignArea;
   double* const row = area + lane * kAccAlignRow;
 
@@ -192,34 +188,19 @@ __global__ __launch_bounds__(kAccAlignThreads) void accalign_eval_kernel(AccAlig
   }
 }
 
-namespace {
-// The N x N normal matrix (row-major) and the right-hand side -gradient of the parameters first .. first + N - 1 from the summed
-// Gram matrix g; a parameter that is not estimated has a unit row.
-DEV void accalign_normal(const double* g, int first, int N, unsigned free_bits, double diag_scale, double* H, double* rhs, int lane) {
-  for (int e = lane; e < N * N; e += 64) {
-    const int i = e / N, j = e - N * i;
-    const bool both = bit(free_bits, first + i) && bit(free_bits, first + j);
-    const double v = both ? g[(first + i) * kAccAlignCols + first + j] : (i == j ? 1.0 : 0.0);
-    H[e] = i == j ? v * diag_scale : v;
-  }
-  if (lane < N) rhs[lane] = bit(free_bits, first + lane) ? -g[(first + lane) * kAccAlignCols + (kAccAlignCols - 1)] : 0.0;
-  wave_fence();
-}
-}  // namespace
-
 // One wave: the candidate's partials added in workgroup order, then what the stage asks for. Stage L: the model is linear in
 // (lever arm, bias, gravity) at the given rotation and latency, so the 9 x 9 block of the Gram matrix evaluated at zero solves
 // for them; the normal equations square the condition number, so a second evaluation at that solution gives one step of
-// iterative refinement (align_accel_solve_kernel's reason) before the loop starts there. The loop: the decision (lm_rule.hpp: lm_point_decision),
-// the damped step from the point that is current afterwards, and the next candidate.
+// iterative refinement (align_accel_solve_kernel's reason) before the loop starts there. The loop is point_lm_dev.hpp's: the decision
+// (lm_rule.hpp: lm_point_decision), the damped 13 x 13 step from the point that is current afterwards, and the next candidate.
 __global__ __launch_bounds__(64) void accalign_decide_kernel(AccAlignArgs a, int n_chunks) {
   __shared__ double s_g[kAccAlignPart];
   __shared__ double s_h[kAccAlignParams * kAccAlignParams];
   __shared__ double s_b[16];
   AccAlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
-  const int cur = c->cur, nxt = cur ^ 1, stage = c->stage;
+  if (c->lm.done != 0) return;
+  const int cur = c->lm.cur, nxt = cur ^ 1, stage = c->stage;
   for (int e = lane; e < kAccAlignSums; e += 64) {
     double s = 0.0;
     for (int ch = 0; ch < n_chunks; ++ch) s += a.part[size_t(ch) * kAccAlignPart + e];
@@ -228,26 +209,20 @@ __global__ __launch_bounds__(64) void accalign_decide_kernel(AccAlignArgs a, int
   }
   wave_fence();
   const double cand = 0.5 * s_g[kAccAlignCostAt], lost = s_g[kAccAlignBadAt];
-  bool finite = __builtin_isfinite(cand) && __builtin_isfinite(c->latency[nxt]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) finite = finite && __builtin_isfinite(c->q[nxt][j]);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) finite = finite && __builtin_isfinite(c->t[nxt][j]) && __builtin_isfinite(c->bias[nxt][j]) && __builtin_isfinite(c->gravity[nxt][j]);
-  const bool kept = lost == 0.0 && finite;
+  const bool kept = lost == 0.0 && __builtin_isfinite(cand) && point_lm_finite(c->q[nxt], 4) && point_lm_finite(c->t[nxt], 3) && point_lm_finite(c->bias[nxt], 3) &&
+                    point_lm_finite(c->gravity[nxt], 3) && point_lm_finite(&c->latency[nxt], 1);
 
   if (stage != kAccAlignStageLoop) {
     int linear = CALICO_ALIGN_OK;
     if (!kept) {
       linear = CALICO_ALIGN_DEGENERATE;
     } else {
-      accalign_normal(s_g, 3, kAccAlignLinear, ~0u, 1.0, s_h, s_b, lane);
+      point_lm_normal(GramFull14{s_g}, 3, kAccAlignLinear, ~0u, 1.0, s_h, s_b, lane);
       if (!lds_chol(s_h, kAccAlignLinear, lane)) {
         linear = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
       } else {
         lds_chol_solve(s_h, s_b, kAccAlignLinear, lane);
-        bool ok = true;
-        for (int j = 0; j < kAccAlignLinear; ++j) ok = ok && __builtin_isfinite(s_b[j]);
-        if (!ok) linear = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
+        if (!point_lm_finite(s_b, kAccAlignLinear)) linear = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
         else if (lane == 0) {
 #pragma unroll
           for (int j = 0; j < 3; ++j) { c->t[nxt][j] += s_b[j]; c->bias[nxt][j] += s_b[3 + j]; c->gravity[nxt][j] += s_b[6 + j]; }
@@ -256,7 +231,7 @@ __global__ __launch_bounds__(64) void accalign_decide_kernel(AccAlignArgs a, int
     }
     if (lane == 0) {
       c->linear_status = linear;
-      if (linear != CALICO_ALIGN_OK) { c->status = linear; c->done = 1; }
+      if (linear != CALICO_ALIGN_OK) { c->lm.status = linear; c->lm.done = 1; }
       if (stage == kAccAlignStageRefine) c->linear_rms = sqrt(s_g[kAccAlignCostAt] / (3.0 * s_g[kAccAlignCountAt])) / a.inv_sigma;
       c->stage = stage + 1;
     }
@@ -264,63 +239,19 @@ __global__ __launch_bounds__(64) void accalign_decide_kernel(AccAlignArgs a, int
   }
 
   const double current = 0.5 * c->G[cur][kAccAlignCostAt], noise = c->G[cur][kAccAlignNoiseAt];
-  int done = 0, status = c->status, new_cur = cur, iterations = c->iterations;
-  double lambda = c->lambda, initial = c->initial_cost;
-  {
-    const bool first = c->first != 0;
-    const LmLoopStep v = lm_point_decision(first, kept, cand, current, noise, c->step < a.step_tolerance, lambda, iterations, a.max_iterations);
-    if (v.accept) new_cur = nxt;
-    if (first) initial = cand;
-    lambda = v.lambda; iterations = v.iterations;
-    if (v.outcome != kLmRunning) {
-      done = 1;
-      status = v.outcome == kLmConverged ? CALICO_ALIGN_OK : v.outcome == kLmBadStart ? CALICO_ALIGN_DEGENERATE : CALICO_ALIGN_NOT_CONVERGED;
-    }
-  }
+  PointLmState st = point_lm_state(c->lm, lm_point_decision(c->lm.first != 0, kept, cand, current, noise, c->lm.step < a.step_tolerance, c->lm.lambda,
+                                                            c->lm.iterations, a.max_iterations), cand);
   double step = 0.0;
-  if (done == 0) {
-    if (new_cur != nxt) {      // (rejected: the step starts at the old point again)
-      for (int e = lane; e < kAccAlignSums; e += 64) s_g[e] = c->G[cur][e];
-    }
-    wave_fence();
-    bool pd = false;
-#pragma unroll 1
-    for (int tries = 0; tries < 26 && !pd; ++tries) {
-      accalign_normal(s_g, 0, kAccAlignParams, a.free_bits, 1.0 + lambda, s_h, s_b, lane);
-      pd = lds_chol(s_h, kAccAlignParams, lane);
-      if (!pd) {
-        if (lambda >= kLmLambdaMax) break;
-        lambda = fmin(lambda * 10.0, kLmLambdaMax);
-      }
-    }
-    if (!pd) {
-      status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE; done = 1;
-    } else {
-      lds_chol_solve(s_h, s_b, kAccAlignParams, lane);
-      const double d[13] = {s_b[0], s_b[1], s_b[2], s_b[3], s_b[4], s_b[5], s_b[6], s_b[7], s_b[8], s_b[9], s_b[10], s_b[11], s_b[12]};
-      Q4 q; q.x = c->q[new_cur][0]; q.y = c->q[new_cur][1]; q.z = c->q[new_cur][2]; q.w = c->q[new_cur][3];
-      const double tau = c->latency[new_cur];
-      Q4 qc = canonical(quat_mul(angle_axis_to_quat(mk(d[0], d[1], d[2])), q));
-      if ((a.free_bits & 7u) == 0u) qc = q;      // (held: the same bits, not the product with the identity normalised again)
-      step = fmax(fmax(amax3(d), amax3(d + 3) / fmax(1.0, amax3(c->t[new_cur]))),
-                  fmax(fmax(amax3(d + 6) / fmax(1.0, amax3(c->bias[new_cur])), amax3(d + 9) / fmax(1.0, amax3(c->gravity[new_cur]))),
-                       fabs(d[12]) / fmax(1.0, fabs(tau))));
-      if (lane == 0) {
-        const int to = new_cur ^ 1;
-        c->q[to][0] = qc.x; c->q[to][1] = qc.y; c->q[to][2] = qc.z; c->q[to][3] = qc.w;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          c->t[to][j] = c->t[new_cur][j] + d[3 + j]; c->bias[to][j] = c->bias[new_cur][j] + d[6 + j];
-          c->gravity[to][j] = c->gravity[new_cur][j] + d[9 + j];
-        }
-        c->latency[to] = tau + d[12];
-      }
+  if (st.done == 0) {
+    point_lm_restore(s_g, c->G[cur], kAccAlignSums, st.cur != nxt, lane);
+    if (point_lm_damped_step(GramFull14{s_g}, kAccAlignParams, a.free_bits, &st, s_h, s_b, lane)) {
+      const int at = st.cur, to = at ^ 1;
+      const double rot = point_lm_rotate(c->q[at], s_b, (a.free_bits & 7u) == 0u, c->q[to], lane), lever = point_lm_add3(c->t[at], s_b + 3, c->t[to], lane);
+      const double bias = point_lm_add3(c->bias[at], s_b + 6, c->bias[to], lane), grav = point_lm_add3(c->gravity[at], s_b + 9, c->gravity[to], lane);
+      step = point_lm_step_size(fmax(rot, lever), fmax(bias, grav), point_lm_add1(c->latency[at], s_b[12], &c->latency[to], lane));
     }
   }
-  if (lane == 0) {
-    c->done = done; c->status = status; c->cur = new_cur; c->first = 0; c->iterations = iterations; c->lambda = lambda;
-    c->initial_cost = initial; c->step = step;
-  }
+  point_lm_write(&c->lm, lane, st, step);
 }
 
 // The undamped inverse normal matrix at the result (zero rows and columns for what is not estimated) and the RMS in m/s^2.
@@ -330,28 +261,12 @@ __global__ __launch_bounds__(64) void accalign_final_kernel(AccAlignArgs a) {
   __shared__ double s_b[16];
   AccAlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (!accalign_runs(c->status) || c->first != 0) return;
-  const int cur = c->cur;
+  if (!point_lm_ran(c->lm.status) || c->lm.first != 0) return;
+  const int cur = c->lm.cur;
   for (int e = lane; e < kAccAlignSums; e += 64) s_g[e] = c->G[cur][e];
   wave_fence();
-  accalign_normal(s_g, 0, kAccAlignParams, a.free_bits, 1.0, s_h, s_b, lane);
-  const bool pd = lds_chol(s_h, kAccAlignParams, lane);
-  if (pd) {
-#pragma unroll 1
-    for (int j = 0; j < kAccAlignParams; ++j) {
-      if (lane < kAccAlignParams) s_b[lane] = lane == j ? 1.0 : 0.0;
-      wave_fence();
-      lds_chol_solve(s_h, s_b, kAccAlignParams, lane);
-      if (lane < kAccAlignParams) c->cov[lane * kAccAlignParams + j] = bit(a.free_bits, lane) && bit(a.free_bits, j) ? s_b[lane] : 0.0;
-      wave_fence();
-    }
-  }
-  if (lane == 0) {
-    c->cov_ok = pd ? 1 : 0;
-    if (!pd) c->status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
-    c->final_cost = 0.5 * s_g[kAccAlignCostAt];
-    c->rms = sqrt(s_g[kAccAlignCostAt] / (3.0 * double(a.n))) / a.inv_sigma;
-  }
+  point_lm_finish(&c->lm, GramFull14{s_g}, kAccAlignParams, a.free_bits, 0.5 * s_g[kAccAlignCostAt], s_h, s_b, c->cov, lane);
+  if (lane == 0) c->rms = sqrt(s_g[kAccAlignCostAt] / (3.0 * double(a.n))) / a.inv_sigma;
 }
 
 // ---- launches ------------------------------------------------------------------------------------------------------------------

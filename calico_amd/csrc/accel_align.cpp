@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../../include/calico_hip.h"
+#include "align_host.hpp"
 #include "arg_rules.hpp"
 #include "device_math.hpp"
 #include "free_call.hpp"
@@ -65,12 +66,8 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
   canonical_unit_quat(q_init, nrm, q0);
   const double lat0 = *latency_init;
 
-  const int k = order, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1, n_ctrl = n_knots - k;
-  const double* const vk = knots + (k - 1);
-  int64_t first = 0, end = n_all;
-  // (the stamp itself too: its segment is the one the optimiser evaluates)
-  while (first < n_all && !(stamps[first] - lat0 >= vk[0] && stamps[first] >= vk[0])) ++first;
-  while (end > first && !(stamps[end - 1] - lat0 <= vk[n_valid - 1] && stamps[end - 1] <= vk[n_valid - 1])) --end;
+  int64_t first, end;
+  ValidKnots(order, n_knots, knots, lat0, lat0).trim(stamps, n_all, &first, &end);
   const int64_t n_used = end - first;
 
   *summary = calico_accel_alignment_summary{};
@@ -80,7 +77,7 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
     std::copy(q0, q0 + 4, q_out);
     for (int i = 0; i < 3; ++i) { t_out[i] = linear ? 0.0 : t_init[i]; bias_out[i] = linear ? 0.0 : bias_init[i]; gravity_out[i] = linear ? 0.0 : gravity_init[i]; }
     *latency_out = lat0;
-    if (cov_out) std::fill(cov_out, cov_out + kAccAlignParams * kAccAlignParams, 0.0);
+    give_covariance(cov_out, nullptr, kAccAlignParams, false);
     summary->gravity_norm = std::sqrt(gravity_out[0] * gravity_out[0] + gravity_out[1] * gravity_out[1] + gravity_out[2] * gravity_out[2]);
   };
   if (n_used < o.min_samples) { give_start(); return CALICO_OK; }
@@ -88,15 +85,16 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
   if (int rc = call.select_device(device)) return rc;
 
   const int n = int(n_used), chunks = accalign_chunks(n);
-  FreeBuf<double> d_knots, d_basis, d_ctrl, d_stamps, d_meas, d_part;
+  SplineOnDevice d_spline;
+  FreeBuf<double> d_stamps, d_meas, d_part;
   FreeBuf<AccAlignControl> d_c;
-  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
-  FREE_TRY(call, d_ctrl.upload(ctrl, size_t(n_ctrl) * 6)); FREE_TRY(call, d_stamps.upload(stamps + first, size_t(n)));
+  FREE_TRY(call, d_spline.upload(order, n_knots, knots, basis, ctrl)); FREE_TRY(call, d_stamps.upload(stamps + first, size_t(n)));
   FREE_TRY(call, d_meas.upload(accel + 3 * first, size_t(n) * 3)); FREE_TRY(call, d_part.alloc(size_t(chunks) * kAccAlignPart));
 
   AccAlignControl c;
   std::memset(&c, 0, sizeof(c));
-  c.status = CALICO_ALIGN_NOT_CONVERGED; c.linear_status = -1; c.first = 1; c.lambda = kLmLambda0;
+  start_point_lm(&c.lm);
+  c.linear_status = -1;
   c.stage = linear ? kAccAlignStageLinear : kAccAlignStageLoop;
   for (int s = 0; s < 2; ++s) {
     for (int i = 0; i < 4; ++i) c.q[s][i] = q0[i];
@@ -106,7 +104,7 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
   FREE_TRY(call, d_c.upload(&c, 1));
 
   AccAlignArgs a = {};
-  a.ctrl = d_c.p; a.order = k; a.n_valid = n_valid; a.knots = d_knots.p; a.basis = d_basis.p; a.spline_ctrl = d_ctrl.p;
+  a.ctrl = d_c.p; a.spline = d_spline.spline;
   a.stamps = d_stamps.p; a.meas = d_meas.p; a.n = n; a.part = d_part.p;
   a.free_bits = (o.estimate_rotation != 0 ? 0x7u : 0u) | (o.estimate_lever_arm != 0 ? 0x38u : 0u) | (o.estimate_bias != 0 ? 0x1c0u : 0u) |
                 (o.estimate_gravity != 0 ? 0xe00u : 0u) | (o.estimate_latency != 0 ? 0x1000u : 0u);
@@ -114,26 +112,23 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
 
   // stage L is two launches; the loop's first launch evaluates the start, every later one a candidate; launches behind the end
   // return at once
-  for (int it = 0; it < (linear ? 2 : 0) + o.max_iterations + 2; ++it) FREE_TRY(call, launch_accalign_iteration(a, nullptr));
+  FREE_TRY(call, enqueue_point_lm((linear ? 2 : 0) + o.max_iterations + 2, [&] { return launch_accalign_iteration(a, nullptr); }));
   FREE_TRY(call, launch_accalign_finish(a, nullptr));
   FREE_TRY(call, d_c.download(&c, 1));
 
-  summary->status = c.status; summary->linear_status = c.linear_status; summary->iterations = c.iterations;
-  summary->initial_cost = c.initial_cost; summary->final_cost = c.final_cost; summary->lambda = c.lambda; summary->rms = c.rms;
+  summary->status = c.lm.status; summary->linear_status = c.linear_status; summary->iterations = c.lm.iterations;
+  summary->initial_cost = c.lm.initial_cost; summary->final_cost = c.lm.final_cost; summary->lambda = c.lm.lambda; summary->rms = c.rms;
   summary->linear_rms = c.linear_rms;
-  const bool ran = c.status == CALICO_ALIGN_OK || c.status == CALICO_ALIGN_NOT_CONVERGED;
-  if (c.first != 0 || c.status == CALICO_ALIGN_DEGENERATE) {
+  if (c.lm.first != 0 || c.lm.status == CALICO_ALIGN_DEGENERATE) {
     give_start();
   } else {
-    std::copy(c.q[c.cur], c.q[c.cur] + 4, q_out);
-    std::copy(c.t[c.cur], c.t[c.cur] + 3, t_out);
-    std::copy(c.bias[c.cur], c.bias[c.cur] + 3, bias_out);
-    std::copy(c.gravity[c.cur], c.gravity[c.cur] + 3, gravity_out);
-    *latency_out = c.latency[c.cur];
-    if (cov_out) {
-      if (ran && c.cov_ok) std::copy(c.cov, c.cov + kAccAlignParams * kAccAlignParams, cov_out);
-      else std::fill(cov_out, cov_out + kAccAlignParams * kAccAlignParams, 0.0);
-    }
+    const int cur = c.lm.cur;
+    std::copy(c.q[cur], c.q[cur] + 4, q_out);
+    std::copy(c.t[cur], c.t[cur] + 3, t_out);
+    std::copy(c.bias[cur], c.bias[cur] + 3, bias_out);
+    std::copy(c.gravity[cur], c.gravity[cur] + 3, gravity_out);
+    *latency_out = c.latency[cur];
+    give_covariance(cov_out, c.cov, kAccAlignParams, point_lm_ran(c.lm.status) && c.lm.cov_ok);
   }
   summary->gravity_norm = std::sqrt(gravity_out[0] * gravity_out[0] + gravity_out[1] * gravity_out[1] + gravity_out[2] * gravity_out[2]);
   return CALICO_OK;

@@ -24,6 +24,7 @@
 #include "../../include/calico_hip.h"
 #include "imu_align_dev.hpp"
 #include "kernels.hpp"
+#include "point_lm_dev.hpp"
 #include "resect_dev.hpp"
 
 namespace cal {
@@ -35,14 +36,6 @@ constexpr int kAlignWaves = kAlignThreads / 64;
 constexpr double kAlignZeroVariance = 1e-12;
 // rotation about one axis only: the second eigenvalue of the scatter of omega_rig against the first
 constexpr double kAlignMinPivot = 1e-6;
-
-DEV AlignSpline spline_of(const AlignArgs& a) {
-  AlignSpline s;
-  s.k = a.order; s.n_valid = a.n_valid; s.knots = a.knots; s.basis = a.basis; s.ctrl = a.spline_ctrl;
-  return s;
-}
-DEV int gram_at(int r, int c) { return r * 8 - (r * (r - 1)) / 2 + (c - r); }      // r <= c
-DEV bool align_runs(int status) { return status == CALICO_ALIGN_OK || status == CALICO_ALIGN_NOT_CONVERGED; }
 
 // The workgroup's sums of v[0 .. NV) to out[0 .. NV): the wave's butterfly, then the waves in order. Every thread of the
 // workgroup calls it.
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(kAlignThreads) void align_corr_kernel(AlignArgs a) 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * kAlignThreads + threadIdx.x;
   const bool in = i < a.n;
-  const AlignSpline sp = spline_of(a);
+  const AlignSpline& sp = a.spline;
   const double stamp = in ? a.stamps[i] : 0.0;
   double m = 0.0;
   if (in) { const double x = a.meas[3 * size_t(i)], y = a.meas[3 * size_t(i) + 1], z = a.meas[3 * size_t(i) + 2]; m = sqrt(x * x + y * y + z * z); }
@@ -157,8 +150,8 @@ __global__ __launch_bounds__(kAlignThreads) void align_corr_peak_kernel(AlignArg
   c->peak_correlation = best;
   if (flat || peak == 0 || peak == a.n_lags - 1) {
     c->coarse_latency = a.lags[peak];
-    c->gyro_status = CALICO_ALIGN_NO_PEAK;
-    c->done = 1;
+    c->lm.status = CALICO_ALIGN_NO_PEAK;
+    c->lm.done = 1;
     return;
   }
   const double ym = s_curve[peak - 1], yp = s_curve[peak + 1], den = ym - 2.0 * best + yp;
@@ -172,10 +165,10 @@ __global__ __launch_bounds__(kAlignThreads) void align_corr_peak_kernel(AlignArg
 __global__ __launch_bounds__(kAlignThreads) void align_horn_sums_kernel(AlignArgs a) {
   __shared__ double s_w[kAlignWaves][kAlignPart];
   const AlignControl* const c = a.ctrl;
-  if (c->done != 0) return;
+  if (c->lm.done != 0) return;
   const double tau = c->latency[1];
   const int i = blockIdx.x * kAlignThreads + threadIdx.x;
-  const AlignSpline sp = spline_of(a);
+  const AlignSpline& sp = a.spline;
   double v[kAlignHornSums];
 #pragma unroll
   for (int e = 0; e < kAlignHornSums; ++e) v[e] = 0.0;
@@ -200,7 +193,7 @@ __global__ __launch_bounds__(64) void align_horn_kernel(AlignArgs a, int n_chunk
   __shared__ double s_g[kAlignPart];
   AlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
+  if (c->lm.done != 0) return;
   if (lane < kAlignHornSums) {
     double s = 0.0;
     for (int ch = 0; ch < n_chunks; ++ch) s += a.part[size_t(ch) * kAlignPart + lane];
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(64) void align_horn_kernel(AlignArgs a, int n_chunk
   const double emax = fmax(e0, fmax(e1, e2)), emin = fmin(e0, fmin(e1, e2)), emid = (e0 + e1 + e2) - emax - emin;
   const double pivot = emax > 0.0 ? emid / emax : 0.0;
   if (!(pivot >= kAlignMinPivot)) {
-    if (lane == 0) { c->scatter_pivot = __builtin_isfinite(pivot) ? pivot : 0.0; c->gyro_status = CALICO_ALIGN_DEGENERATE; c->done = 1; }
+    if (lane == 0) { c->scatter_pivot = __builtin_isfinite(pivot) ? pivot : 0.0; c->lm.status = CALICO_ALIGN_DEGENERATE; c->lm.done = 1; }
     return;
   }
   // Horn: the unit quaternion (w, x, y, z) that maximises Sum u . R v is the eigenvector of the largest eigenvalue of N
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(64) void align_horn_kernel(AlignArgs a, int n_chunk
     c->q[1][0] = q.x; c->q[1][1] = q.y; c->q[1][2] = q.z; c->q[1][3] = q.w;
     c->bias[1][0] = b[0]; c->bias[1][1] = b[1]; c->bias[1][2] = b[2];
     if (!(__builtin_isfinite(q.x) && __builtin_isfinite(q.y) && __builtin_isfinite(q.z) && __builtin_isfinite(q.w))) {
-      c->gyro_status = CALICO_ALIGN_DEGENERATE; c->done = 1;
+      c->lm.status = CALICO_ALIGN_DEGENERATE; c->lm.done = 1;
     }
   }
 }
@@ -267,14 +260,14 @@ __global__ __launch_bounds__(64) void align_horn_kernel(AlignArgs a, int n_chunk
 __global__ __launch_bounds__(kAlignThreads) void align_eval_kernel(AlignArgs a) {
   __shared__ double s_w[kAlignWaves][kAlignPart];
   const AlignControl* const c = a.ctrl;
-  if (c->done != 0) return;
-  const int slot = c->cur ^ 1;
+  if (c->lm.done != 0) return;
+  const int slot = c->lm.cur ^ 1;
   Q4 q; q.x = c->q[slot][0]; q.y = c->q[slot][1]; q.z = c->q[slot][2]; q.w = c->q[slot][3];
   const double b[3] = {c->bias[slot][0], c->bias[slot][1], c->bias[slot][2]};
   const double tau = c->latency[slot], is = a.inv_sigma;
   const M3 R = rotmat(q);
   const int i = blockIdx.x * kAlignThreads + threadIdx.x;
-  const AlignSpline sp = spline_of(a);
+  const AlignSpline& sp = a.spline;
   double v[kAlignSums];
 #pragma unroll
   for (int e = 0; e < kAlignSums; ++e) v[e] = 0.0;
@@ -313,31 +306,17 @@ __global__ __launch_bounds__(kAlignThreads) void align_eval_kernel(AlignArgs a) 
   align_block_sum<kAlignSums>(v, s_w, a.part + size_t(blockIdx.x) * kAlignPart);
 }
 
-namespace {
-// the 7 x 7 normal matrix (row-major) and the gradient of the summed triangle g; a parameter that is not estimated has a unit row
-DEV void normal_of(const double* g, unsigned free_bits, double diag_scale, double* H, double* rhs, int lane) {
-  if (lane < 49) {
-    const int i = lane / 7, j = lane - 7 * i, lo = i < j ? i : j, hi = i < j ? j : i;
-    const bool both = ((free_bits >> i) & 1u) != 0u && ((free_bits >> j) & 1u) != 0u;
-    const double v = both ? g[gram_at(lo, hi)] : (i == j ? 1.0 : 0.0);
-    H[lane] = i == j ? v * diag_scale : v;
-  }
-  if (lane < 7) rhs[lane] = ((free_bits >> lane) & 1u) != 0u ? -g[gram_at(lane, 7)] : 0.0;
-  wave_fence();
-}
-}  // namespace
-
-// One wave: the candidate's partials added in workgroup order, the decision (lm_rule.hpp: a candidate within the
-// cost's rounding error is accepted, a small step ends the loop only at low damping), the damped step from the point that is
-// current afterwards, and the next candidate.
+// One wave: the candidate's partials added in workgroup order, then point_lm_dev.hpp's iteration: the decision (lm_rule.hpp: a
+// candidate within the cost's rounding error is accepted, a small step ends the loop only at low damping), the damped 7 x 7 step
+// from the point that is current afterwards, and the next candidate.
 __global__ __launch_bounds__(64) void align_decide_kernel(AlignArgs a, int n_chunks) {
   __shared__ double s_g[kAlignPart];
   __shared__ double s_h[49];
   __shared__ double s_b[8];
   AlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
-  const int cur = c->cur, nxt = cur ^ 1;
+  if (c->lm.done != 0) return;
+  const int cur = c->lm.cur, nxt = cur ^ 1;
   if (lane < kAlignSums) {
     double s = 0.0;
     for (int ch = 0; ch < n_chunks; ++ch) s += a.part[size_t(ch) * kAlignPart + lane];
@@ -347,64 +326,19 @@ __global__ __launch_bounds__(64) void align_decide_kernel(AlignArgs a, int n_chu
   wave_fence();
   const double cand = 0.5 * s_g[kAlignCostAt], lost = s_g[kAlignBadAt];
   const double current = 0.5 * c->G[cur][kAlignCostAt], noise = c->G[cur][kAlignNoiseAt];
-  bool finite = __builtin_isfinite(cand) && __builtin_isfinite(c->latency[nxt]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) finite = finite && __builtin_isfinite(c->q[nxt][j]);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) finite = finite && __builtin_isfinite(c->bias[nxt][j]);
-  const bool kept = lost == 0.0 && finite;
-  int done = 0, status = c->gyro_status, new_cur = cur, iterations = c->iterations;
-  double lambda = c->lambda, initial = c->initial_cost;
-  if (c->first != 0) {
-    if (!kept) { status = CALICO_ALIGN_DEGENERATE; done = 1; }
-    new_cur = nxt; initial = cand;
-  } else {
-    const bool small = c->step < a.step_tolerance;
-    const LmVerdict v = lm_rule(kept, cand, current, noise, small, lambda);
-    if (v.accept) new_cur = nxt;
-    lambda = v.lambda;
-    if (v.converged) { status = CALICO_ALIGN_OK; done = 1; }
-  }
-  if (done == 0 && iterations >= a.max_iterations) { status = CALICO_ALIGN_NOT_CONVERGED; done = 1; }
-  if (done == 0) ++iterations;
+  const bool kept = lost == 0.0 && __builtin_isfinite(cand) && point_lm_finite(c->q[nxt], 4) && point_lm_finite(c->bias[nxt], 3) && point_lm_finite(&c->latency[nxt], 1);
+  PointLmState st = point_lm_state(c->lm, lm_point_decision(c->lm.first != 0, kept, cand, current, noise, c->lm.step < a.step_tolerance, c->lm.lambda,
+                                                            c->lm.iterations, a.max_iterations), cand);
   double step = 0.0;
-  if (done == 0) {
-    if (new_cur != nxt && lane < kAlignSums) s_g[lane] = c->G[cur][lane];      // (rejected: the step starts at the old point again)
-    wave_fence();
-    bool pd = false;
-#pragma unroll 1
-    for (int tries = 0; tries < 26 && !pd; ++tries) {
-      normal_of(s_g, a.free_bits, 1.0 + lambda, s_h, s_b, lane);
-      pd = lds_chol(s_h, 7, lane);
-      if (!pd) {
-        if (lambda >= kLmLambdaMax) break;
-        lambda = fmin(lambda * 10.0, kLmLambdaMax);
-      }
-    }
-    if (!pd) {
-      status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE; done = 1;
-    } else {
-      lds_chol_solve(s_h, s_b, 7, lane);
-      const double d[7] = {s_b[0], s_b[1], s_b[2], s_b[3], s_b[4], s_b[5], s_b[6]};
-      Q4 q; q.x = c->q[new_cur][0]; q.y = c->q[new_cur][1]; q.z = c->q[new_cur][2]; q.w = c->q[new_cur][3];
-      const double b[3] = {c->bias[new_cur][0], c->bias[new_cur][1], c->bias[new_cur][2]};
-      const double tau = c->latency[new_cur];
-      const Q4 qc = canonical(quat_mul(angle_axis_to_quat(mk(d[0], d[1], d[2])), q));
-      const double bs = fmax(1.0, fmax(fabs(b[0]), fmax(fabs(b[1]), fabs(b[2]))));
-      step = fmax(fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2]))),
-                  fmax(fmax(fabs(d[3]), fmax(fabs(d[4]), fabs(d[5]))) / bs, fabs(d[6]) / fmax(1.0, fabs(tau))));
-      if (lane == 0) {
-        const int to = new_cur ^ 1;
-        c->q[to][0] = qc.x; c->q[to][1] = qc.y; c->q[to][2] = qc.z; c->q[to][3] = qc.w;
-        c->bias[to][0] = b[0] + d[3]; c->bias[to][1] = b[1] + d[4]; c->bias[to][2] = b[2] + d[5];
-        c->latency[to] = tau + d[6];
-      }
+  if (st.done == 0) {
+    point_lm_restore(s_g, c->G[cur], kAlignSums, st.cur != nxt, lane);
+    if (point_lm_damped_step(GramTriangle8{s_g}, 7, a.free_bits, &st, s_h, s_b, lane)) {
+      const int at = st.cur, to = at ^ 1;
+      step = point_lm_step_size(point_lm_rotate(c->q[at], s_b, false, c->q[to], lane), point_lm_add3(c->bias[at], s_b + 3, c->bias[to], lane),
+                                point_lm_add1(c->latency[at], s_b[6], &c->latency[to], lane));
     }
   }
-  if (lane == 0) {
-    c->done = done; c->gyro_status = status; c->cur = new_cur; c->first = 0; c->iterations = iterations; c->lambda = lambda;
-    c->initial_cost = initial; c->step = step;
-  }
+  point_lm_write(&c->lm, lane, st, step);
 }
 
 // The undamped inverse normal matrix at the result (zero rows and columns for what is not estimated) and the RMS.
@@ -414,31 +348,12 @@ __global__ __launch_bounds__(64) void align_final_kernel(AlignArgs a) {
   __shared__ double s_b[8];
   AlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (!align_runs(c->gyro_status) || c->first != 0) return;
-  const int cur = c->cur;
+  if (!point_lm_ran(c->lm.status) || c->lm.first != 0) return;
+  const int cur = c->lm.cur;
   if (lane < kAlignSums) s_g[lane] = c->G[cur][lane];
   wave_fence();
-  normal_of(s_g, a.free_bits, 1.0, s_h, s_b, lane);
-  const bool pd = lds_chol(s_h, 7, lane);
-  if (pd) {
-#pragma unroll 1
-    for (int j = 0; j < 7; ++j) {
-      if (lane < 7) s_b[lane] = lane == j ? 1.0 : 0.0;
-      wave_fence();
-      lds_chol_solve(s_h, s_b, 7, lane);
-      if (lane < 7) {
-        const bool both = ((a.free_bits >> lane) & 1u) != 0u && ((a.free_bits >> j) & 1u) != 0u;
-        c->cov[lane * 7 + j] = both ? s_b[lane] : 0.0;
-      }
-      wave_fence();
-    }
-  }
-  if (lane == 0) {
-    c->cov_ok = pd ? 1 : 0;
-    if (!pd) c->gyro_status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
-    c->final_cost = 0.5 * s_g[kAlignCostAt];
-    c->gyro_rms = sqrt(s_g[kAlignCostAt] / (3.0 * double(a.n)));
-  }
+  point_lm_finish(&c->lm, GramTriangle8{s_g}, 7, a.free_bits, 0.5 * s_g[kAlignCostAt], s_h, s_b, c->cov, lane);
+  if (lane == 0) c->gyro_rms = sqrt(s_g[kAlignCostAt] / (3.0 * double(a.n)));
 }
 
 // ---- stage D -------------------------------------------------------------------------------------------------------------------
@@ -449,14 +364,14 @@ template <bool RESIDUAL>
 __global__ __launch_bounds__(kAlignThreads) void align_accel_kernel(AlignArgs a) {
   __shared__ double s_w[kAlignWaves][kAlignPart];
   const AlignControl* const c = a.ctrl;
-  if (!align_runs(c->gyro_status)) return;
+  if (!point_lm_ran(c->lm.status)) return;
   if (RESIDUAL && c->accel_status != CALICO_ALIGN_OK) return;
-  const int cur = c->cur;
+  const int cur = c->lm.cur;
   Q4 q; q.x = c->q[cur][0]; q.y = c->q[cur][1]; q.z = c->q[cur][2]; q.w = c->q[cur][3];
   const double tau = c->latency[cur];
   const M3 Ra = rotmat(q);
   const int i = blockIdx.x * kAlignThreads + threadIdx.x;
-  const AlignSpline sp = spline_of(a);
+  const AlignSpline& sp = a.spline;
   constexpr int NV = RESIDUAL ? kAlignAccelResidual : kAlignAccelSums;
   double v[NV];
 #pragma unroll
@@ -520,7 +435,7 @@ __global__ __launch_bounds__(64) void align_accel_solve_kernel(AlignArgs a, int 
   __shared__ double s_b[8];
   AlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (!align_runs(c->gyro_status)) return;
+  if (!point_lm_ran(c->lm.status)) return;
   if (mode != 0 && c->accel_status != CALICO_ALIGN_OK) return;
   const int NV = mode == 0 ? kAlignAccelSums : kAlignAccelResidual;
   if (lane < NV) {

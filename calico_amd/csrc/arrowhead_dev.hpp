@@ -201,16 +201,6 @@ DEV void lm_control_decide(LmControl* head, int lane, bool kept, bool any_valid,
     else if (s.accept) head->accepted = 1;
   }
 }
-// The same decision for a loop that keeps a control word of its own shape (camalign_kernels.hip): the step, and in *status the
-// code the loop ends with (unchanged while it runs).
-DEV LmLoopStep lm_decide(bool first, bool kept, bool any_valid, double common, double current, double noise, bool small, double lambda,
-                         int iterations, int max_iterations, LmStatusCodes status_of, int* status) {
-  const LmLoopStep s = lm_loop_decision(first, kept, any_valid, common, current, noise, small, lambda, iterations, max_iterations);
-  if (s.outcome == kLmConverged) *status = status_of.converged;
-  else if (s.outcome == kLmBadStart) *status = status_of.bad_start;
-  else if (s.outcome == kLmOutOfIterations) *status = status_of.out_of_iterations;
-  return s;
-}
 // The damped reduced system was not positive definite: eliminate and reduce again at ten times the damping, while there is any.
 DEV void lm_control_not_pd(LmControl* head, int lane, double lambda, int degenerate_status) {
   if (lane != 0) return;

@@ -29,6 +29,7 @@
 #include "arrowhead_dev.hpp"
 #include "imu_align_dev.hpp"
 #include "kernels.hpp"
+#include "point_lm_dev.hpp"
 
 namespace cal {
 
@@ -42,15 +43,6 @@ constexpr double kCamAlignFlat = 1e-12;
 
 namespace {
 
-DEV AlignSpline spline_of(const CamAlignArgs& a) {
-  AlignSpline s;
-  s.k = a.order; s.n_valid = a.n_valid; s.knots = a.knots; s.basis = a.basis; s.ctrl = a.spline_ctrl;
-  return s;
-}
-constexpr LmStatusCodes kCamAlignStatus = {CALICO_ALIGN_OK, CALICO_ALIGN_DEGENERATE, CALICO_ALIGN_NOT_CONVERGED};
-DEV int gram_at(int r, int c) { return r * 8 - (r * (r - 1)) / 2 + (c - r); }      // r <= c
-DEV bool camalign_runs(int status) { return status == CALICO_ALIGN_OK || status == CALICO_ALIGN_NOT_CONVERGED; }
-DEV Q4 q_of(const double* p) { Q4 q; q.x = p[0]; q.y = p[1]; q.z = p[2]; q.w = p[3]; return q; }
 DEV Q4 quat_conj(Q4 q) { q.x = -q.x; q.y = -q.y; q.z = -q.z; return q; }
 
 // The rig's pose at the time t in the segment seg (the STAMP's, align_segment: t = stamp - latency may lie beyond its knots):
@@ -104,8 +96,8 @@ __global__ __launch_bounds__(64) void camalign_gate_kernel(CamAlignArgs a) {
   if (lane == 0) {
     c->frames_used = n;
     c->d2 = n > 0 ? d2 / double(n) : 0.0;
-    if (n < a.min_frames) { c->status = CALICO_ALIGN_TOO_FEW_SAMPLES; c->done = 1; }
-    else if (!(c->d2 > 0.0) || !__builtin_isfinite(c->d2)) { c->status = CALICO_ALIGN_DEGENERATE; c->done = 1; }
+    if (n < a.min_frames) { c->lm.status = CALICO_ALIGN_TOO_FEW_SAMPLES; c->lm.done = 1; }
+    else if (!(c->d2 > 0.0) || !__builtin_isfinite(c->d2)) { c->lm.status = CALICO_ALIGN_DEGENERATE; c->lm.done = 1; }
   }
 }
 
@@ -114,11 +106,11 @@ __global__ __launch_bounds__(64) void camalign_gate_kernel(CamAlignArgs a) {
 __global__ __launch_bounds__(kCamAlignThreads) void camalign_pose_kernel(CamAlignArgs a, int single) {
   __shared__ double s_part[kCamAlignPoseWaves][kCamAlignLagTile][kCamAlignPoseSums];
   const CamAlignControl* const c = a.ctrl;
-  if (c->done != 0) return;      // (the whole workgroup)
+  if (c->lm.done != 0) return;      // (the whole workgroup)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * kCamAlignThreads + threadIdx.x;
   const bool in = i < a.n_frames && a.active[i < a.n_frames ? i : 0] != 0;
-  const AlignSpline sp = spline_of(a);
+  const AlignSpline& sp = a.spline;
   const int n_lags = single ? 1 : a.n_lags;
   const double stamp = in ? a.stamps[i] : 0.0;
   const int seg = in ? align_segment(sp, stamp) : -1;      // (>= 0: the host let no other frame in)
@@ -126,7 +118,7 @@ __global__ __launch_bounds__(kCamAlignThreads) void camalign_pose_kernel(CamAlig
   Q4 q_wc; q_wc.x = q_wc.y = q_wc.z = 0.0; q_wc.w = 1.0;
   V3 c_w = mk(0.0, 0.0, 0.0);
   if (in) {
-    const Q4 q_cm = normalized(q_of(a.q_cm + 4 * size_t(i))), q_wm = q_of(a.q_wm);
+    const Q4 q_cm = normalized(quat_at(a.q_cm + 4 * size_t(i))), q_wm = quat_at(a.q_wm);
     const V3 t_cm = mk(a.t_cm[3 * size_t(i)], a.t_cm[3 * size_t(i) + 1], a.t_cm[3 * size_t(i) + 2]);
     q_wc = quat_mul(q_wm, quat_conj(q_cm));
     c_w = mul(rotmat(q_wm), -mulT(rotmat(q_cm), t_cm)) + mk(a.t_wm[0], a.t_wm[1], a.t_wm[2]);
@@ -170,7 +162,7 @@ __global__ __launch_bounds__(kCamAlignThreads) void camalign_pose_kernel(CamAlig
 __global__ __launch_bounds__(kCamAlignThreads) void camalign_peak_kernel(CamAlignArgs a, int n_chunks) {
   __shared__ double s_curve[kAlignMaxLags];
   CamAlignControl* const c = a.ctrl;
-  if (c->done != 0) return;
+  if (c->lm.done != 0) return;
   const double n = double(c->frames_used), d2 = c->d2;
   for (int l = threadIdx.x; l < a.n_lags; l += kCamAlignThreads) {
     double g[kCamAlignPoseSums];
@@ -206,8 +198,8 @@ __global__ __launch_bounds__(kCamAlignThreads) void camalign_peak_kernel(CamAlig
   const bool flat = !finite || !(worst - best > kCamAlignFlat * fmax(worst, 1.0));
   if (flat || peak == 0 || peak == a.n_lags - 1) {
     c->coarse_latency = a.lags[peak];
-    c->status = CALICO_ALIGN_NO_PEAK;
-    c->done = 1;
+    c->lm.status = CALICO_ALIGN_NO_PEAK;
+    c->lm.done = 1;
     return;
   }
   const double ym = s_curve[peak - 1], yp = s_curve[peak + 1], den = ym - 2.0 * best + yp;
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(64) void camalign_mean_kernel(CamAlignArgs a, int n
   __shared__ double s_g[16];
   CamAlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
+  if (c->lm.done != 0) return;
   if (lane < kCamAlignPoseSums) {
     double s = 0.0;
     for (int ch = 0; ch < n_chunks; ++ch) s += a.pose_part[size_t(ch) * kCamAlignPoseSums + lane];
@@ -248,7 +240,7 @@ __global__ __launch_bounds__(64) void camalign_mean_kernel(CamAlignArgs a, int n
   if (lane == 0) {
     c->q[1][0] = q.x; c->q[1][1] = q.y; c->q[1][2] = q.z; c->q[1][3] = q.w;
     if ((a.free_bits & 0x38u) != 0u) { c->t[1][0] = t.x; c->t[1][1] = t.y; c->t[1][2] = t.z; }
-    if (!finite_pose(q, t)) { c->status = CALICO_ALIGN_DEGENERATE; c->done = 1; }
+    if (!finite_pose(q, t)) { c->lm.status = CALICO_ALIGN_DEGENERATE; c->lm.done = 1; }
   }
 }
 
@@ -265,10 +257,10 @@ __global__ __launch_bounds__(kCamAlignEvalThreads, kCamAlignWavesPerSimd) void c
   const int f = int(blockIdx.x) * kCamAlignWaves + wave;
   if (f >= a.n_frames) return;      // (the whole wave: no barrier follows)
   const CamAlignControl* const c = a.ctrl;
-  if (c->done != 0 || a.active[f] == 0) return;
-  const int cur = c->cur, nxt = cur ^ 1;
-  const bool first = c->first != 0;
-  const AlignSpline sp = spline_of(a);
+  if (c->lm.done != 0 || a.active[f] == 0) return;
+  const int cur = c->lm.cur, nxt = cur ^ 1;
+  const bool first = c->lm.first != 0;
+  const AlignSpline& sp = a.spline;
   // the frame's pose and its time derivative: wave-uniform
   Q4 q_rw;
   V3 t_wr, omega, t_wr_dot;
@@ -276,8 +268,8 @@ __global__ __launch_bounds__(kCamAlignEvalThreads, kCamAlignWavesPerSimd) void c
   const int seg = align_segment(sp, stamp);
   if (seg < 0) return;      // (the host let no such frame in)
   rig_pose<true>(sp, seg, stamp - c->latency[nxt], &q_rw, &t_wr, &omega, &t_wr_dot);
-  const M3 R_rw = rotmat(q_rw), Rc = rotmat(q_of(c->q[nxt]));
-  const M3 R_rm = mul(R_rw, rotmat(q_of(a.q_wm)));
+  const M3 R_rw = rotmat(q_rw), Rc = rotmat(quat_at(c->q[nxt]));
+  const M3 R_rm = mul(R_rw, rotmat(quat_at(a.q_wm)));
   const V3 t_rm = mul(R_rw, mk(a.t_wm[0], a.t_wm[1], a.t_wm[2]) - t_wr), vel = mul(R_rw, t_wr_dot);
   const V3 t_rc = mk(c->t[nxt][0], c->t[nxt][1], c->t[nxt][2]);
   const int64_t base = a.offsets[f], n = a.offsets[f + 1] - base;
@@ -352,7 +344,7 @@ __global__ __launch_bounds__(kCamAlignEvalThreads, kCamAlignWavesPerSimd) void c
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const int row = lk + 4 * r;
-    if (lc < N && row <= lc) ns[gram_at(row, lc)] = acc[r];
+    if (lc < N && row <= lc) ns[GramTriangle8::at(row, lc)] = acc[r];
   }
   s_cost = wave_sum(s_cost); s_common = wave_sum(s_common); s_ss = wave_sum(s_ss); s_noise = wave_sum(s_noise);
   if (lane == 0) {
@@ -361,30 +353,18 @@ __global__ __launch_bounds__(kCamAlignEvalThreads, kCamAlignWavesPerSimd) void c
   }
 }
 
-namespace {
-// the 7 x 7 normal matrix (row-major) and the gradient of the summed triangle g; a parameter that is not estimated has a unit row
-DEV void normal_of(const double* g, unsigned free_bits, double diag_scale, double* H, double* rhs, int lane) {
-  if (lane < 49) {
-    const int i = lane / 7, j = lane - 7 * i, lo = i < j ? i : j, hi = i < j ? j : i;
-    const bool both = ((free_bits >> i) & 1u) != 0u && ((free_bits >> j) & 1u) != 0u;
-    const double v = both ? g[gram_at(lo, hi)] : (i == j ? 1.0 : 0.0);
-    H[lane] = i == j ? v * diag_scale : v;
-  }
-  if (lane < 7) rhs[lane] = ((free_bits >> lane) & 1u) != 0u ? -g[gram_at(lane, 7)] : 0.0;
-  wave_fence();
-}
-}  // namespace
-
-// One wave: the candidate's records added in frame order (lane e adds entry e), the decision (lm_rule.hpp's lm_loop_decision through arrowhead_dev.hpp's lm_decide),
-// the damped step from the point that is current afterwards, and the next candidate.
+// One wave: the candidate's records added in frame order (lane e adds entry e), then point_lm_dev.hpp's iteration: the decision
+// (lm_rule.hpp's lm_loop_decision; the camera's own: the cost over the pairs valid at both points is what is compared, a start
+// without a valid pair is a bad one, and the cost is a sum of rho, not half of it), the damped 7 x 7 step from the point that is
+// current afterwards, and the next candidate.
 __global__ __launch_bounds__(64) void camalign_decide_kernel(CamAlignArgs a) {
   __shared__ double s_g[kCamAlignSums + 2];
   __shared__ double s_h[49];
   __shared__ double s_b[8];
   CamAlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  if (c->done != 0) return;
-  const int cur = c->cur, nxt = cur ^ 1;
+  if (c->lm.done != 0) return;
+  const int cur = c->lm.cur, nxt = cur ^ 1;
   if (lane < kCamAlignSums + 2) {
     const int at = lane < kCamAlignSums ? kCamAlignSums * nxt + lane : kCamAlignCommonAt + (lane - kCamAlignSums);
     double s = 0.0;
@@ -398,59 +378,19 @@ __global__ __launch_bounds__(64) void camalign_decide_kernel(CamAlignArgs a) {
   wave_fence();
   const double cand = s_g[kCamAlignCostAt], common = s_g[kCamAlignSums], lost = s_g[kCamAlignSums + 1];
   const double current = c->G[cur][kCamAlignCostAt], noise = c->G[cur][kCamAlignNoiseAt];
-  bool finite = __builtin_isfinite(cand) && __builtin_isfinite(c->latency[nxt]);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) finite = finite && __builtin_isfinite(c->q[nxt][j]);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) finite = finite && __builtin_isfinite(c->t[nxt][j]);
-  const bool first = c->first != 0;
-  const bool kept = lost == 0.0 && finite;
-  const bool small = c->step < a.step_tolerance;
-  int status = c->status;
-  const LmLoopStep s = lm_decide(first, kept, s_g[kCamAlignValidAt] >= 1.0, common, current, noise, small, c->lambda, c->iterations,
-                                 a.max_iterations, kCamAlignStatus, &status);
-  int done = s.outcome != kLmRunning ? 1 : 0;
-  const int new_cur = s.accept ? nxt : cur;
-  double lambda = s.lambda, step = 0.0;
-  if (done == 0) {
-    if (!s.accept && lane < kCamAlignSums) s_g[lane] = c->G[cur][lane];      // (rejected: the step starts at the old point again)
-    wave_fence();
-    bool pd = false;
-#pragma unroll 1
-    for (int tries = 0; tries < 26 && !pd; ++tries) {
-      normal_of(s_g, a.free_bits, 1.0 + lambda, s_h, s_b, lane);
-      pd = lds_chol(s_h, 7, lane);
-      if (!pd) {
-        if (lambda >= kLmLambdaMax) break;
-        lambda = fmin(lambda * 10.0, kLmLambdaMax);
-      }
-    }
-    if (!pd) {
-      status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE; done = 1;
-    } else {
-      lds_chol_solve(s_h, s_b, 7, lane);
-      const double d[7] = {s_b[0], s_b[1], s_b[2], s_b[3], s_b[4], s_b[5], s_b[6]};
-      const Q4 q = q_of(c->q[new_cur]);
-      const double t[3] = {c->t[new_cur][0], c->t[new_cur][1], c->t[new_cur][2]};
-      const double tau = c->latency[new_cur];
-      const Q4 qc = canonical(quat_mul(angle_axis_to_quat(mk(d[0], d[1], d[2])), q));
-      const double ts = fmax(1.0, fmax(fabs(t[0]), fmax(fabs(t[1]), fabs(t[2]))));
-      step = fmax(fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2]))),
-                  fmax(fmax(fabs(d[3]), fmax(fabs(d[4]), fabs(d[5]))) / ts, fabs(d[6]) / fmax(1.0, fabs(tau))));
-      if (!__builtin_isfinite(step)) step = 1e300;
-      if (lane == 0) {
-        const int to = new_cur ^ 1;
-        c->q[to][0] = qc.x; c->q[to][1] = qc.y; c->q[to][2] = qc.z; c->q[to][3] = qc.w;
-        c->t[to][0] = t[0] + d[3]; c->t[to][1] = t[1] + d[4]; c->t[to][2] = t[2] + d[5];
-        c->latency[to] = tau + d[6];
-      }
+  const bool kept = lost == 0.0 && __builtin_isfinite(cand) && point_lm_finite(c->q[nxt], 4) && point_lm_finite(c->t[nxt], 3) && point_lm_finite(&c->latency[nxt], 1);
+  PointLmState st = point_lm_state(c->lm, lm_loop_decision(c->lm.first != 0, kept, s_g[kCamAlignValidAt] >= 1.0, common, current, noise,
+                                                           c->lm.step < a.step_tolerance, c->lm.lambda, c->lm.iterations, a.max_iterations), 0.5 * cand);
+  double step = 0.0;
+  if (st.done == 0) {
+    point_lm_restore(s_g, c->G[cur], kCamAlignSums, st.cur != nxt, lane);
+    if (point_lm_damped_step(GramTriangle8{s_g}, 7, a.free_bits, &st, s_h, s_b, lane)) {
+      const int at = st.cur, to = at ^ 1;
+      step = point_lm_step_size(point_lm_rotate(c->q[at], s_b, false, c->q[to], lane), point_lm_add3(c->t[at], s_b + 3, c->t[to], lane),
+                                point_lm_add1(c->latency[at], s_b[6], &c->latency[to], lane));
     }
   }
-  if (lane == 0) {
-    c->done = done; c->status = status; c->cur = new_cur; c->first = 0; c->iterations = s.iterations; c->lambda = lambda;
-    if (first) c->initial_cost = 0.5 * cand;
-    c->step = step;
-  }
+  point_lm_write(&c->lm, lane, st, step);
 }
 
 // One wave: the undamped inverse normal matrix at the result (zero rows and columns for what is not estimated), the RMS, and
@@ -461,8 +401,8 @@ __global__ __launch_bounds__(64) void camalign_final_kernel(CamAlignArgs a) {
   __shared__ double s_b[8];
   CamAlignControl* const c = a.ctrl;
   const int lane = threadIdx.x;
-  const bool ran = camalign_runs(c->status) && c->first == 0;
-  const int cur = c->cur;
+  const bool ran = point_lm_ran(c->lm.status) && c->lm.first == 0;
+  const int cur = c->lm.cur;
   for (int f = lane; f < a.n_frames; f += 64) {
     const double* const cs = a.frames + size_t(f) * kCamAlignFrameDoubles + kCamAlignSums * cur;
     const bool act = ran && a.active[f] != 0 && cs[kCamAlignValidAt] >= 1.0;
@@ -472,25 +412,8 @@ __global__ __launch_bounds__(64) void camalign_final_kernel(CamAlignArgs a) {
   if (!ran) return;
   if (lane < kCamAlignSums) s_g[lane] = c->G[cur][lane];
   wave_fence();
-  normal_of(s_g, a.free_bits, 1.0, s_h, s_b, lane);
-  const bool pd = lds_chol(s_h, 7, lane);
-  if (pd) {
-#pragma unroll 1
-    for (int j = 0; j < 7; ++j) {
-      if (lane < 7) s_b[lane] = lane == j ? 1.0 : 0.0;
-      wave_fence();
-      lds_chol_solve(s_h, s_b, 7, lane);
-      if (lane < 7) {
-        const bool both = ((a.free_bits >> lane) & 1u) != 0u && ((a.free_bits >> j) & 1u) != 0u;
-        c->cov[lane * 7 + j] = both ? s_b[lane] : 0.0;
-      }
-      wave_fence();
-    }
-  }
+  point_lm_finish(&c->lm, GramTriangle8{s_g}, 7, a.free_bits, 0.5 * s_g[kCamAlignCostAt], s_h, s_b, c->cov, lane);
   if (lane == 0) {
-    c->cov_ok = pd ? 1 : 0;
-    if (!pd) c->status = CALICO_ALIGN_NOT_POSITIVE_DEFINITE;
-    c->final_cost = 0.5 * s_g[kCamAlignCostAt];
     c->rms = sqrt(s_g[kCamAlignSsAt] / s_g[kCamAlignValidAt]);
     c->pairs_used = (long long)s_g[kCamAlignValidAt];
   }

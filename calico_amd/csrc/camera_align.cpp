@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/calico_hip.h"
+#include "align_host.hpp"
 #include "arg_rules.hpp"
 #include "device_math.hpp"
 #include "free_call.hpp"
@@ -69,14 +70,13 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
   if (q_world_chart) canonical_unit_quat(q_world_chart, quat_norm(q_world_chart), q_wm);
   if (t_world_chart) std::copy(t_world_chart, t_world_chart + 3, t_wm);
 
-  const int k = order, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1, n_ctrl = n_knots - k;
-  const double* const vk = knots + (k - 1);
   // the grid, and the frames every latency of it keeps on the valid knots
   const int n_lags = 2 * half + 1;
   std::vector<double> lags(static_cast<size_t>(n_lags));
   for (int l = 0; l < n_lags; ++l) lags[size_t(l)] = lat0 + double(l - half) * o.lag_step;
   const bool search = !q_init && o.estimate_latency != 0;
   const double lat_lo = search ? lags.front() : lat0, lat_hi = search ? lags.back() : lat0;      // (no search: no grid to keep on the knots)
+  const ValidKnots on_knots(order, n_knots, knots, lat_lo, lat_hi);
   const size_t F = size_t(n_frames);
   std::vector<int64_t> part;      // the frames that take part, in stamp order
   std::vector<int64_t> off(1, 0);
@@ -85,8 +85,7 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
     const int64_t n = frame_offsets[f + 1] - frame_offsets[f];
     uint8_t st = CALICO_RESECT_OK;
     if (n < o.min_points) st = CALICO_RESECT_TOO_FEW_POINTS;
-    // (the stamp itself too: its segment is the one the optimiser evaluates)
-    else if (!(s >= vk[0] && s <= vk[n_valid - 1] && s - lat_hi >= vk[0] && s - lat_lo <= vk[n_valid - 1])) st = CALICO_CAMERA_ALIGN_FRAME_OUTSIDE;
+    else if (!(on_knots.from(s) && on_knots.until(s))) st = CALICO_CAMERA_ALIGN_FRAME_OUTSIDE;
     frame_status_out[f] = st; frame_rms_out[f] = 0.0; frame_n_used_out[f] = 0;
     if (st == CALICO_RESECT_OK) { part.push_back(int64_t(f)); off.push_back(off.back() + n); }
   }
@@ -98,7 +97,7 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
   const auto give_start = [&]() {
     std::copy(q0, q0 + 4, q_out); std::copy(t0, t0 + 3, t_out);
     *latency_out = lat0;
-    if (cov_out) std::fill(cov_out, cov_out + 49, 0.0);
+    give_covariance(cov_out, nullptr, 7, false);
   };
   if (int64_t(nf) < o.min_frames) { give_start(); return CALICO_OK; }
   if (np > size_t(INT32_MAX)) return call.fail(CALICO_UNIMPLEMENTED, "more than 2^31 - 1 pairs");
@@ -115,14 +114,14 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
     std::copy(points + 3 * b, points + 3 * (b + n), pt.begin() + 3 * off[i]);
   }
   const int n = int(nf), chunks = camalign_chunks(n);
-  FreeBuf<double> d_knots, d_basis, d_ctrl, d_k, d_stamps, d_px, d_pt, d_lags, d_pose, d_curve, d_frames, d_rms;
+  SplineOnDevice d_spline;
+  FreeBuf<double> d_k, d_stamps, d_px, d_pt, d_lags, d_pose, d_curve, d_frames, d_rms;
   FreeBuf<int64_t> d_off;
   FreeBuf<int32_t> d_used;
   FreeBuf<uint8_t> d_fl, d_rfl, d_active, d_status;
   FreeBuf<CamAlignControl> d_c;
   ResectRun run;
-  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
-  FREE_TRY(call, d_ctrl.upload(ctrl, size_t(n_ctrl) * 6)); FREE_TRY(call, d_k.upload(intrinsics, size_t(n_intrinsics)));
+  FREE_TRY(call, d_spline.upload(order, n_knots, knots, basis, ctrl)); FREE_TRY(call, d_k.upload(intrinsics, size_t(n_intrinsics)));
   FREE_TRY(call, d_stamps.upload(stamps.data(), nf)); FREE_TRY(call, d_px.upload(px.data(), np * 2)); FREE_TRY(call, d_pt.upload(pt.data(), np * 3));
   FREE_TRY(call, d_off.upload(off.data(), nf + 1)); FREE_TRY(call, d_lags.upload(lags.data(), lags.size()));
   FREE_TRY(call, d_pose.alloc(size_t(chunks) * size_t(n_lags) * kCamAlignPoseSums)); FREE_TRY(call, d_curve.alloc(size_t(n_lags)));
@@ -134,8 +133,8 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
 
   CamAlignControl c;
   std::memset(&c, 0, sizeof(c));
-  c.status = CALICO_ALIGN_NOT_CONVERGED; c.first = 1; c.peak_index = -1; c.frames_used = n;
-  c.lambda = kLmLambda0; c.coarse_latency = lat0;
+  start_point_lm(&c.lm);
+  c.peak_index = -1; c.frames_used = n; c.coarse_latency = lat0;
   for (int s = 0; s < 2; ++s) {
     std::copy(q0, q0 + 4, c.q[s]); std::copy(t0, t0 + 3, c.t[s]);
     c.latency[s] = lat0;
@@ -143,7 +142,7 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
   FREE_TRY(call, d_c.upload(&c, 1));
 
   CamAlignArgs a = {};
-  a.ctrl = d_c.p; a.order = k; a.n_valid = n_valid; a.knots = d_knots.p; a.basis = d_basis.p; a.spline_ctrl = d_ctrl.p; a.k = d_k.p;
+  a.ctrl = d_c.p; a.spline = d_spline.spline; a.k = d_k.p;
   std::copy(q_wm, q_wm + 4, a.q_wm); std::copy(t_wm, t_wm + 3, a.t_wm);
   a.n_frames = n; a.stamps = d_stamps.p; a.offsets = d_off.p; a.pixels = d_px.p; a.points = d_pt.p; a.flags = d_fl.p;
   a.active = d_active.p; a.frame_status = d_status.p;
@@ -166,10 +165,10 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
     FREE_TRY(call, launch_camalign_mean(a, nullptr));
   }
   // the first launch evaluates the start, every later one a candidate; launches behind the end return at once
-  for (int it = 0; it < o.max_iterations + 2; ++it) FREE_TRY(call, launch_camalign_iteration(model, a, nullptr));
+  FREE_TRY(call, enqueue_point_lm(o.max_iterations + 2, [&] { return launch_camalign_iteration(model, a, nullptr); }));
   FREE_TRY(call, launch_camalign_finish(a, nullptr));
   FREE_TRY(call, d_c.download(&c, 1));
-  if (search && c.status != CALICO_ALIGN_TOO_FEW_SAMPLES && (c.peak_index >= 0)) {
+  if (search && c.lm.status != CALICO_ALIGN_TOO_FEW_SAMPLES && (c.peak_index >= 0)) {
     summary->n_lags = n_lags;
     if (curve_out) FREE_TRY(call, d_curve.download(curve_out, size_t(n_lags)));
   }
@@ -182,19 +181,16 @@ int32_t calico_camera_align(int32_t device, int32_t order, int32_t n_knots, cons
     frame_rms_out[f] = rms[i]; frame_n_used_out[f] = used[i]; frame_status_out[f] = st_part[i];
   }
 
-  summary->status = c.status; summary->iterations = c.iterations; summary->frames_used = c.frames_used; summary->pairs_used = c.pairs_used;
+  summary->status = c.lm.status; summary->iterations = c.lm.iterations; summary->frames_used = c.frames_used; summary->pairs_used = c.pairs_used;
   summary->peak_index = c.peak_index; summary->coarse_latency = c.coarse_latency; summary->peak_score = c.peak_score;
-  summary->rms = c.rms; summary->initial_cost = c.initial_cost; summary->final_cost = c.final_cost; summary->lambda = c.lambda;
-  const bool ran = c.status == CALICO_ALIGN_OK || c.status == CALICO_ALIGN_NOT_CONVERGED;
-  if (c.first != 0 || c.status == CALICO_ALIGN_DEGENERATE || c.status == CALICO_ALIGN_NO_PEAK || c.status == CALICO_ALIGN_TOO_FEW_SAMPLES) {
+  summary->rms = c.rms; summary->initial_cost = c.lm.initial_cost; summary->final_cost = c.lm.final_cost; summary->lambda = c.lm.lambda;
+  if (c.lm.first != 0 || c.lm.status == CALICO_ALIGN_DEGENERATE || c.lm.status == CALICO_ALIGN_NO_PEAK || c.lm.status == CALICO_ALIGN_TOO_FEW_SAMPLES) {
     give_start();
   } else {
-    std::copy(c.q[c.cur], c.q[c.cur] + 4, q_out); std::copy(c.t[c.cur], c.t[c.cur] + 3, t_out);
-    *latency_out = c.latency[c.cur];
-    if (cov_out) {
-      if (ran && c.cov_ok) std::copy(c.cov, c.cov + 49, cov_out);
-      else std::fill(cov_out, cov_out + 49, 0.0);
-    }
+    const int cur = c.lm.cur;
+    std::copy(c.q[cur], c.q[cur] + 4, q_out); std::copy(c.t[cur], c.t[cur] + 3, t_out);
+    *latency_out = c.latency[cur];
+    give_covariance(cov_out, c.cov, 7, point_lm_ran(c.lm.status) && c.lm.cov_ok);
   }
   return CALICO_OK;
 }

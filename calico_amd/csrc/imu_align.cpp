@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/calico_hip.h"
+#include "align_host.hpp"
 #include "arg_rules.hpp"
 #include "device_math.hpp"
 #include "free_call.hpp"
@@ -70,18 +71,14 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   if (!(error = stamps_error("gyro", n_gyro, gyro_stamps)).empty()) return call.invalid(error);
   if (!(error = stamps_error("accel", n_accel, accel_stamps)).empty()) return call.invalid(error);
 
-  const int k = order, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1, n_ctrl = n_knots - k;
-  const double* const vk = knots + (k - 1);
   // the grid, and the samples every latency of it keeps on the valid knots
   const int L = int(half), n_lags = 2 * L + 1;
   std::vector<double> lags(static_cast<size_t>(n_lags));
   for (int l = 0; l < n_lags; ++l) lags[size_t(l)] = lat0 + double(l - L) * o.lag_step;
   const bool search = !q_init && o.estimate_latency != 0;
   const double lat_lo = search ? lags.front() : lat0, lat_hi = search ? lags.back() : lat0;      // (no search: no grid to keep on the knots)
-  int64_t first = 0, end = n_gyro;
-  // (the stamp itself too: its segment is the one the optimiser evaluates)
-  while (first < n_gyro && !(gyro_stamps[first] - lat_hi >= vk[0] && gyro_stamps[first] >= vk[0])) ++first;
-  while (end > first && !(gyro_stamps[end - 1] - lat_lo <= vk[n_valid - 1] && gyro_stamps[end - 1] <= vk[n_valid - 1])) --end;
+  int64_t first, end;
+  ValidKnots(order, n_knots, knots, lat_lo, lat_hi).trim(gyro_stamps, n_gyro, &first, &end);
   const int64_t n_used = end - first;
 
   *summary = calico_imu_alignment_summary{};
@@ -92,17 +89,17 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
     std::copy(q0, q0 + 4, q_out);
     bias_out[0] = bias_out[1] = bias_out[2] = 0.0;
     *latency_out = lat0;
-    if (cov_out) std::fill(cov_out, cov_out + 49, 0.0);
+    give_covariance(cov_out, nullptr, 7, false);
   };
   if (n_used < o.min_samples) { give_start(); return CALICO_OK; }
 
   if (int rc = call.select_device(device)) return rc;
 
   const int n = int(n_used), chunks = align_chunks(n), accel_chunks = align_chunks(int(n_accel));
-  FreeBuf<double> d_knots, d_basis, d_ctrl, d_stamps, d_meas, d_lags, d_corr, d_corr_m, d_curve, d_part, d_as, d_am;
+  SplineOnDevice d_spline;
+  FreeBuf<double> d_stamps, d_meas, d_lags, d_corr, d_corr_m, d_curve, d_part, d_as, d_am;
   FreeBuf<AlignControl> d_c;
-  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
-  FREE_TRY(call, d_ctrl.upload(ctrl, size_t(n_ctrl) * 6)); FREE_TRY(call, d_stamps.upload(gyro_stamps + first, size_t(n)));
+  FREE_TRY(call, d_spline.upload(order, n_knots, knots, basis, ctrl)); FREE_TRY(call, d_stamps.upload(gyro_stamps + first, size_t(n)));
   FREE_TRY(call, d_meas.upload(gyro + 3 * first, size_t(n) * 3)); FREE_TRY(call, d_lags.upload(lags.data(), lags.size()));
   FREE_TRY(call, d_corr.alloc(search ? size_t(chunks) * n_lags * 3 : 0)); FREE_TRY(call, d_corr_m.alloc(size_t(chunks) * 2));
   FREE_TRY(call, d_curve.alloc(size_t(n_lags))); FREE_TRY(call, d_part.alloc(size_t(std::max(chunks, accel_chunks)) * kAlignPart));
@@ -110,8 +107,8 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
 
   AlignControl c;
   std::memset(&c, 0, sizeof(c));
-  c.gyro_status = CALICO_ALIGN_NOT_CONVERGED; c.accel_status = CALICO_ALIGN_TOO_FEW_SAMPLES; c.first = 1; c.peak_index = -1;
-  c.lambda = kLmLambda0; c.coarse_latency = lat0;
+  start_point_lm(&c.lm);
+  c.accel_status = CALICO_ALIGN_TOO_FEW_SAMPLES; c.peak_index = -1; c.coarse_latency = lat0;
   for (int s = 0; s < 2; ++s) {
     for (int i = 0; i < 4; ++i) c.q[s][i] = q0[i];
     c.latency[s] = lat0;
@@ -119,7 +116,7 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   FREE_TRY(call, d_c.upload(&c, 1));
 
   AlignArgs a = {};
-  a.ctrl = d_c.p; a.order = k; a.n_valid = n_valid; a.knots = d_knots.p; a.basis = d_basis.p; a.spline_ctrl = d_ctrl.p;
+  a.ctrl = d_c.p; a.spline = d_spline.spline;
   a.stamps = d_stamps.p; a.meas = d_meas.p; a.n = n; a.lags = d_lags.p; a.n_lags = n_lags; a.lag_step = o.lag_step;
   a.corr_part = d_corr.p; a.corr_m = d_corr_m.p; a.curve = d_curve.p; a.part = d_part.p;
   a.free_bits = 7u | (o.estimate_gyro_bias != 0 ? 0x38u : 0u) | (o.estimate_latency != 0 ? 0x40u : 0u);
@@ -131,7 +128,7 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
   if (search) FREE_TRY(call, launch_align_correlate(a, nullptr));
   if (!q_init) FREE_TRY(call, launch_align_horn(a, nullptr));
   // the first launch evaluates the start, every later one a candidate; launches behind the end return at once
-  for (int it = 0; it < o.max_iterations + 2; ++it) FREE_TRY(call, launch_align_iteration(a, nullptr));
+  FREE_TRY(call, enqueue_point_lm(o.max_iterations + 2, [&] { return launch_align_iteration(a, nullptr); }));
   FREE_TRY(call, launch_align_finish(a, nullptr));
   FREE_TRY(call, launch_align_gravity(a, nullptr));
   FREE_TRY(call, d_c.download(&c, 1));
@@ -140,23 +137,21 @@ int32_t calico_imu_align(int32_t device, int32_t order, int32_t n_knots, const d
     if (curve_out) FREE_TRY(call, d_curve.download(curve_out, size_t(n_lags)));
   }
 
-  summary->gyro_status = c.gyro_status; summary->iterations = c.iterations; summary->peak_index = c.peak_index;
+  summary->gyro_status = c.lm.status; summary->iterations = c.lm.iterations; summary->peak_index = c.peak_index;
   summary->coarse_latency = c.coarse_latency; summary->peak_correlation = c.peak_correlation; summary->scatter_pivot = c.scatter_pivot;
-  summary->initial_cost = c.initial_cost; summary->final_cost = c.final_cost; summary->lambda = c.lambda; summary->gyro_rms = c.gyro_rms;
-  const bool ran = c.gyro_status == CALICO_ALIGN_OK || c.gyro_status == CALICO_ALIGN_NOT_CONVERGED;
-  if (c.first != 0 || c.gyro_status == CALICO_ALIGN_DEGENERATE || c.gyro_status == CALICO_ALIGN_NO_PEAK) {
+  summary->initial_cost = c.lm.initial_cost; summary->final_cost = c.lm.final_cost; summary->lambda = c.lm.lambda; summary->gyro_rms = c.gyro_rms;
+  const bool ran = point_lm_ran(c.lm.status);
+  if (c.lm.first != 0 || c.lm.status == CALICO_ALIGN_DEGENERATE || c.lm.status == CALICO_ALIGN_NO_PEAK) {
     give_start();
   } else {
-    std::copy(c.q[c.cur], c.q[c.cur] + 4, q_out);
-    std::copy(c.bias[c.cur], c.bias[c.cur] + 3, bias_out);
-    *latency_out = c.latency[c.cur];
-    if (cov_out) {
-      if (ran && c.cov_ok) std::copy(c.cov, c.cov + 49, cov_out);
-      else std::fill(cov_out, cov_out + 49, 0.0);
-    }
+    const int cur = c.lm.cur;
+    std::copy(c.q[cur], c.q[cur] + 4, q_out);
+    std::copy(c.bias[cur], c.bias[cur] + 3, bias_out);
+    *latency_out = c.latency[cur];
+    give_covariance(cov_out, c.cov, 7, ran && c.lm.cov_ok);
   }
   if (!ran) {
-    summary->accel_status = c.gyro_status;
+    summary->accel_status = c.lm.status;
   } else if (n_accel > 0) {
     summary->accel_status = c.accel_status; summary->accel_samples = c.accel_samples;
     if (c.accel_status == CALICO_ALIGN_OK) {

@@ -9,16 +9,9 @@
 #include <cstddef>
 
 #include "device_math.hpp"
+#include "kernels.hpp"      // AlignSpline
 
 namespace cal {
-
-struct AlignSpline {
-  int k;                      // order
-  int n_valid;                // valid knots: n_knots - 2 (k - 1); segments: n_valid - 1
-  const double* knots;        // n_knots
-  const double* basis;        // (n_valid - 1) x k x k
-  const double* ctrl;         // (n_knots - k) x 6
-};
 
 // GetSplineIndex (bspline.hpp:138-150): upper_bound(valid_knots, t) - 1, the last valid knot belongs to the last segment.
 // -1 where t lies outside the valid knots (or is not a number).

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "../../include/calico_hip.h"
 #include "problem_dev.hpp"
 
 namespace cal {
@@ -298,6 +299,32 @@ hipError_t launch_rig_decide(const RigArgs& a, hipStream_t s);                  
 hipError_t launch_rig_eliminate(const RigArgs& a, bool final, hipStream_t s);      // per frame: Cholesky, Y, its share (final: undamped, outputs)
 hipError_t launch_rig_reduce(const RigArgs& a, bool final, hipStream_t s);         // fixed-order sum over the frames, the M x M solve, the step
 
+// ---- the alignment family (align_kernels.hip, camalign_kernels.hip, accalign_kernels.hip) ---------------------------------------
+// Each runs a Levenberg-Marquardt loop over ONE point with a dense normal matrix (7 or 13 unknowns), two slots (current point and
+// candidate), and its control word in device memory. The head of that word is the same for the three (point_lm_dev.hpp decides
+// and writes it, align_host.hpp sets it up and reads it back), as LmControl is for the arrowhead estimators:
+struct PointLmControl {
+  int done;                     // != 0: every later launch of the loop returns at once
+  int status;                   // CALICO_ALIGN_*
+  int cur;                      // the slot of the current point
+  int first;                    // the start has not been evaluated yet
+  int iterations;
+  int cov_ok;                   // the undamped normal matrix at the result was positive definite (covariance written)
+  double lambda, step;          // step: the size of the step the candidate was made with
+  double initial_cost, final_cost;
+};
+static_assert(offsetof(PointLmControl, done) == 0, "done is the head's first field");
+// the loop ran to a point that is a result
+__host__ __device__ inline bool point_lm_ran(int status) { return status == CALICO_ALIGN_OK || status == CALICO_ALIGN_NOT_CONVERGED; }
+// The fitted trajectory the three align against: a spline that is not part of a problem (imu_align_dev.hpp evaluates it).
+struct AlignSpline {
+  int k;                      // order
+  int n_valid;                // valid knots: n_knots - 2 (k - 1); segments: n_valid - 1
+  const double* knots;        // n_knots
+  const double* basis;        // (n_valid - 1) x k x k
+  const double* ctrl;         // (n_knots - k) x 6
+};
+
 // ---- camera-IMU alignment (align_kernels.hip): rotation, gyroscope bias, latency, gravity from a fitted trajectory ------------
 // The control word of the whole call: every kernel reads it, the single-workgroup kernels write it. The stages follow one
 // another on the stream without the host reading anything back; a stage that ends the call sets `done`.
@@ -314,16 +341,10 @@ constexpr int kAlignHornSums = 21;                       // Sum u (3), Sum v (3)
 constexpr int kAlignAccelSums = 16;                      // samples (1), Sum M (9), Sum M^T y (3), Sum y (3)
 constexpr int kAlignAccelResidual = 8;                   // Sum |r|^2, samples, A^T r (6)
 struct AlignControl {
-  int done;                     // != 0: every later launch of the gyroscope part returns at once
-  int gyro_status, accel_status;      // CALICO_ALIGN_*
-  int cur;                      // the slot of the current point
-  int first;                    // the start has not been evaluated yet
-  int iterations;
+  PointLmControl lm;            // lm.status: the gyroscope part's; lm.done: every later launch of the gyroscope part returns at once
+  int accel_status;             // CALICO_ALIGN_*
   int peak_index;               // of the correlation curve (-1: no search)
-  int cov_ok;
   long long accel_samples;
-  double lambda, step;          // step: the size of the step the candidate was made with
-  double initial_cost, final_cost;
   double coarse_latency, peak_correlation, scatter_pivot, gyro_rms, accel_rms;
   double q[2][4], bias[2][3], latency[2];      // the two slots
   double G[2][kAlignPart];      // the summed partials of the two slots
@@ -331,10 +352,10 @@ struct AlignControl {
   double gravity[3], accel_bias[3];
   double accel_sums[kAlignAccelSums];
 };
+static_assert(offsetof(AlignControl, lm) == 0, "every launch reads the control word's first field");
 struct AlignArgs {
   AlignControl* ctrl;
-  int order, n_valid;
-  const double* knots; const double* basis; const double* spline_ctrl;
+  AlignSpline spline;
   const double* stamps; const double* meas;               // the gyroscope samples that take part: n of them (the host's range)
   int n;
   const double* lags; int n_lags; double lag_step;        // the latencies of the grid
@@ -370,27 +391,21 @@ constexpr int kCamAlignPoseSums = 14;                    // Sum q q^T (10: xx xy
 constexpr int kCamAlignThreads = 256;                    // frames per workgroup of the pose sums
 constexpr int kCamAlignLagTile = 8;                      // lags per workgroup of the pose sums
 struct CamAlignControl {
-  int done;                     // != 0: every later launch of the loop returns at once
-  int status;                   // CALICO_ALIGN_*
-  int cur;                      // the slot of the current point
-  int first;                    // the start has not been evaluated yet
-  int iterations;
+  PointLmControl lm;            // lm.done: every later launch of the loop returns at once
   int peak_index;               // of the score curve (-1: no search)
-  int cov_ok;
   int frames_used;              // frames that take part after the resection
   long long pairs_used;
-  double lambda, step;          // step: the size of the step the candidate was made with
-  double initial_cost, final_cost, rms;
+  double rms;
   double coarse_latency, peak_score;
   double d2;                    // the mean of |t_camera_chart|^2 over the frames that take part
   double q[2][4], t[2][3], latency[2];      // the two slots
   double G[2][kCamAlignSums];   // the summed frames of the two slots
   double cov[49];
 };
+static_assert(offsetof(CamAlignControl, lm) == 0, "every launch reads the control word's first field");
 struct CamAlignArgs {
   CamAlignControl* ctrl;
-  int order, n_valid;
-  const double* knots; const double* basis; const double* spline_ctrl;
+  AlignSpline spline;
   const double* k;                                        // the camera's intrinsics
   double q_wm[4], t_wm[3];                                // T_world_chart
   int n_frames;                                           // frames that take part
@@ -433,23 +448,18 @@ constexpr int kAccAlignThreads = 256;                    // samples per workgrou
 constexpr int kAccAlignLinear = 9;                       // stage L: lever arm, bias, gravity (parameters 3 .. 11)
 constexpr int kAccAlignStageLinear = 0, kAccAlignStageRefine = 1, kAccAlignStageLoop = 2;
 struct AccAlignControl {
-  int done;                     // != 0: every later launch returns at once
-  int status, linear_status;    // CALICO_ALIGN_* (linear_status -1: stage L did not run)
+  PointLmControl lm;            // lm.first: the LOOP's start has not been evaluated yet
+  int linear_status;            // CALICO_ALIGN_* (-1: stage L did not run)
   int stage;                    // kAccAlignStage*
-  int cur;                      // the slot of the current point
-  int first;                    // the loop's start has not been evaluated yet
-  int iterations;
-  int cov_ok;
-  double lambda, step;          // step: the size of the step the candidate was made with
-  double initial_cost, final_cost, rms, linear_rms;
+  double rms, linear_rms;
   double q[2][4], t[2][3], bias[2][3], gravity[2][3], latency[2];      // the two slots
   double G[2][kAccAlignPart];   // the summed partials of the two slots
   double cov[kAccAlignParams * kAccAlignParams];
 };
+static_assert(offsetof(AccAlignControl, lm) == 0, "every launch reads the control word's first field");
 struct AccAlignArgs {
   AccAlignControl* ctrl;
-  int order, n_valid;
-  const double* knots; const double* basis; const double* spline_ctrl;
+  AlignSpline spline;
   const double* stamps; const double* meas;               // the samples that take part: n of them
   int n;
   double* part;                                           // chunks x kAccAlignPart

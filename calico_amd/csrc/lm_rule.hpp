@@ -1,6 +1,7 @@
-// lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip and
-// align_kernels.hip call it themselves, calib_kernels.hip, rig_kernels.hip and camalign_kernels.hip through arrowhead_dev.hpp, accalign_kernels.hip through lm_point_decision): accept or reject a
-// candidate, the next damping, and whether the loop has converged.
+// lm_rule.hpp — the Levenberg-Marquardt step rule of the estimators that run their loop on the device (resect_kernels.hip calls it
+// itself, calib_kernels.hip and rig_kernels.hip through arrowhead_dev.hpp's lm_control_decide, the three alignments --
+// align_kernels.hip, camalign_kernels.hip, accalign_kernels.hip -- with point_lm_dev.hpp's point_lm_state behind it):
+// accept or reject a candidate, the next damping, and whether the loop has converged.
 // What differs between them stays with them: the first evaluation, the iteration cap and the status codes, and the retry while
 // a damped system is not positive definite. Host and device code (the host sets the control word's first damping).
 #pragma once
@@ -49,7 +50,8 @@ DEV LmLoopStep lm_loop_decision(bool first, bool kept, bool any_valid, double ca
   return s;
 }
 
-// The same decision for a loop over ONE point (accalign_kernels.hip): there is no block that could be left without a valid
+// The same decision for a loop over ONE point (point_lm_dev.hpp; tests/cpp/arg_rules_check.cpp holds it to the decision that
+// align_kernels.hip once spelt out): there is no block that could be left without a valid
 // observation, the samples that take part are fixed by the host.
 DEV LmLoopStep lm_point_decision(bool first, bool kept, double candidate, double current, double noise, bool small, double lambda, int iterations,
                                  int max_iterations) {

@@ -73,6 +73,7 @@ DEV void lds_chol_solve(const double* L, double* b, int N, int lane) {
   }
 }
 
+DEV Q4 quat_at(const double* p) { Q4 q; q.x = p[0]; q.y = p[1]; q.z = p[2]; q.w = p[3]; return q; }      // (x, y, z, w) in memory
 DEV Q4 quat_mul(Q4 a, Q4 b) {      // R(a b) = R(a) R(b)
   Q4 r;
   r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;

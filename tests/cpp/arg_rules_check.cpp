@@ -11,11 +11,14 @@
 //  4. on accept the new lambda is max(0.1 lambda, 1e-12);
 //  5. on reject the new lambda is lambda if converged, else min(10 lambda, 1e12) -- so it is unchanged iff converged, except at
 //     the upper clamp itself (lambda = 1e12 is never converged and cannot grow).
+// lm_point_decision (the decision of a loop over one point: the alignments') against the IMU alignment's decision as its kernel
+// once spelt it out: see check_point_decision.
 // Exits 0 and prints "OK <checks>" when all hold; prints the first violation and exits 1 otherwise.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <memory>
 #include <string>
@@ -195,6 +198,52 @@ void check_lm_rule() {
   }
 }
 
+// The decision of the IMU alignment's loop as align_decide_kernel spelt it out before it went through lm_point_decision: the
+// first evaluation installs the start (a start that is not kept ends the loop), every later one asks lm_rule, the iteration cap
+// ends the loop at the point kept, and only a loop that goes on counts the iteration.
+cal::LmLoopStep written_out_decision(bool first, bool kept, double cand, double current, double noise, bool small, double lambda, int iterations,
+                                     int max_iterations) {
+  cal::LmLoopStep s;
+  s.accept = false; s.outcome = cal::kLmRunning; s.lambda = lambda; s.iterations = iterations;
+  if (first) {
+    if (!kept) s.outcome = cal::kLmBadStart;      // (DEGENERATE)
+    s.accept = true;
+  } else {
+    const cal::LmVerdict v = cal::lm_rule(kept, cand, current, noise, small, lambda);
+    if (v.accept) s.accept = true;
+    s.lambda = v.lambda;
+    if (v.converged) s.outcome = cal::kLmConverged;      // (OK)
+  }
+  if (s.outcome == cal::kLmRunning && iterations >= max_iterations) s.outcome = cal::kLmOutOfIterations;      // (NOT_CONVERGED)
+  if (s.outcome == cal::kLmRunning) ++s.iterations;
+  return s;
+}
+
+// lm_point_decision against it over first x kept x small x candidate in {below the current cost, within its noise, above} x
+// lambda in {kLmLambdaMin, kLmLambda0, kLmLambdaMax} x iterations in {below, at, above the cap}: the same accept, outcome,
+// lambda (bit for bit) and iteration count everywhere.
+void check_point_decision() {
+  const double current = 12345.678, noise = 9.0e5, bound = current + cal::kCostSlack * noise;
+  const double candidates[3] = {0.5 * current, 0.5 * (current + bound), 2.0 * current};
+  expect(candidates[1] > current && candidates[1] < bound, "lm_point_decision", "the middle candidate lies within the noise");
+  const int cap = 7;
+  for (int first = 0; first < 2; ++first)
+    for (int kept = 0; kept < 2; ++kept)
+      for (int small = 0; small < 2; ++small)
+        for (double cand : candidates)
+          for (double lambda : {cal::kLmLambdaMin, cal::kLmLambda0, cal::kLmLambdaMax})
+            for (int iterations : {cap - 1, cap, cap + 1}) {
+              const cal::LmLoopStep a = written_out_decision(first != 0, kept != 0, cand, current, noise, small != 0, lambda, iterations, cap);
+              const cal::LmLoopStep b = cal::lm_point_decision(first != 0, kept != 0, cand, current, noise, small != 0, lambda, iterations, cap);
+              const std::string at = "first " + std::to_string(first) + " kept " + std::to_string(kept) + " small " + std::to_string(small) +
+                                     " candidate " + std::to_string(cand) + " lambda " + std::to_string(lambda) + " iterations " + std::to_string(iterations);
+              expect(a.accept == b.accept, "lm_point_decision: accept", at);
+              expect(a.outcome == b.outcome, "lm_point_decision: outcome", at);
+              expect(std::memcmp(&a.lambda, &b.lambda, sizeof(double)) == 0, "lm_point_decision: lambda's bits", at);
+              expect(a.iterations == b.iterations, "lm_point_decision: iterations", at);
+            }
+}
+
 }  // namespace
 
 int main() {
@@ -206,6 +255,7 @@ int main() {
   check_stamps();
   check_quaternion();
   check_lm_rule();
+  check_point_decision();
   std::printf("OK %ld\n", g_checks);
   return 0;
 }

@@ -5,7 +5,7 @@ the one accumulator tile of the evaluation lives in four VGPRs). LDS is static a
 rows of 16 doubles per wave, 4 x 8 KB, and keeps 4 x 4 wave sums (32896 bytes); the one-wave kernels keep the 200 sums, the
 13 x 13 system and its right-hand side of 16 (the decision 3080 bytes, the final kernel 3088 with its alignment padding).
 
-VGPRs: the siblings' bar is four waves per SIMD (128). The one-wave kernels are under it (84 and 18 as compiled). The
+VGPRs: the siblings' bar is four waves per SIMD (128). The one-wave kernels are under it (60 and 20 as compiled). The
 evaluation is not: 176 as compiled. One lane carries a sample's whole forward-mode evaluation -- four derivative rows of spline
 weights unrolled to order 8, the Rodrigues coefficients with their derivative along t (nine dual numbers), omega and alpha as
 duals, and then the 42 entries of its three rows [J | r] live until the last of the three staging passes. Its figure is pinned

@@ -7,7 +7,7 @@ registry): the evaluation stages 64 rows of 8 columns per wave, 4 x 64 x 8 x 8 =
 4 x 8 x 14 partial sums (3584 bytes); the peak kernel keeps the curve (4096 lags, 32768 bytes); the one-wave kernels the 42 sums,
 the 7 x 7 system and its right-hand side. All under the 64 KiB a workgroup may have without asking.
 As compiled: camalign_eval_kernel<1..7> 164, 166, 232, 164, 230, 164, 164 VGPRs, occupancy 3, 3, 2, 3, 2, 3, 3;
-camalign_pose_kernel 142 VGPRs; camalign_peak_kernel 78; camalign_mean_kernel 108; camalign_decide_kernel 64;
+camalign_pose_kernel 142 VGPRs; camalign_peak_kernel 78; camalign_mean_kernel 108; camalign_decide_kernel 52;
 camalign_final_kernel 28; camalign_gate_kernel 20, no LDS. ScratchSize 0 and no spills in all."""
 import os
 import shutil

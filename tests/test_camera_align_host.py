@@ -92,8 +92,12 @@ def test_entry_points_are_declared_listed_and_exported(api):
     src = open(os.path.join(entry.CSRC, "camalign_kernels.hip")).read()
     for word in ("lds_chol(double*", "void align_jacobi", "LmVerdict lm_rule", "void huber("):
         assert word not in src, word
-    for word in ("align_jacobi<4>", "lm_decide(", "lds_chol(", "huber(", "__builtin_amdgcn_mfma_f64_16x16x4f64"):
+    for word in ("align_jacobi<4>", "lm_loop_decision(", "point_lm_state(", "point_lm_damped_step(", "point_lm_finish(", "huber(",
+                 "__builtin_amdgcn_mfma_f64_16x16x4f64"):
         assert word in src, word
+    # (the Cholesky is called by the dense one-point loop's header, which the three alignments share)
+    shared = open(os.path.join(entry.CSRC, "point_lm_dev.hpp")).read()
+    assert "lds_chol(" in shared and "lds_chol(double*" not in shared and "lds_chol(" not in src and "kLmLambdaMax" not in src
     assert "launch_camalign_iteration" in open(os.path.join(entry.CSRC, "kernels.hpp")).read()
     for struct, cls in (("calico_camera_alignment_options", _capi.CameraAlignmentOptions),
                         ("calico_camera_alignment_summary", _capi.CameraAlignmentSummary)):

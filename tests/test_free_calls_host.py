@@ -151,11 +151,24 @@ def test_the_scaffold_is_defined_once():
     assert [f for f, src in sources.items() if re.search(r"#define\s+FREE_TRY\b", src)] == ["free_call.hpp"]
     assert [f for f, src in sources.items() if "no usable HIP device" in src] == ["free_call.hpp"]
     assert [f for f, src in sources.items() if re.search(r"handle_free_error\(\)\s*\{", src)] == ["calico_hip.cpp"]
-    # the step rule and its constants: one definition, two kernels that call it themselves; the two arrowhead estimators reach
-    # it through the one loop decision that the arrowhead header calls
+    # the step rule and its constants: one definition, one kernel that calls it itself (the resection's in-wave loop); the two
+    # arrowhead estimators reach it through the one loop decision that the arrowhead header calls, the three alignments ask it themselves
+    # and hand the outcome to the dense one-point header's one mapping to their status codes
     assert [f for f, src in sources.items() if "kCostSlack =" in src] == ["lm_rule.hpp"]
-    assert sorted(f for f, src in sources.items() if "lm_rule(" in src and f != "lm_rule.hpp") == ["align_kernels.hip", "resect_kernels.hip"]
-    assert [f for f, src in sources.items() if "lm_loop_decision(" in src and f != "lm_rule.hpp"] == ["arrowhead_dev.hpp"]
+    assert sorted(f for f, src in sources.items() if "lm_rule(" in src and f != "lm_rule.hpp") == ["resect_kernels.hip"]
+    assert [f for f, src in sources.items() if "lm_loop_decision(" in src and f != "lm_rule.hpp"] == ["arrowhead_dev.hpp", "camalign_kernels.hip"]
+    assert [f for f, src in sources.items() if "lm_point_decision(" in src and f != "lm_rule.hpp"] == ["accalign_kernels.hip", "align_kernels.hip"]
+    assert [f for f, src in sources.items() if re.search(r"\blm_decide\(", src)] == []
+    assert sorted(f for f, src in sources.items() if "point_lm_state(" in src) == ["accalign_kernels.hip", "align_kernels.hip", "camalign_kernels.hip",
+                                                                                  "point_lm_dev.hpp"]
+    assert [f for f, src in sources.items() if "CALICO_ALIGN_NOT_CONVERGED" in src and f.endswith((".hip", "_dev.hpp"))] == ["point_lm_dev.hpp"]
+    # the dense one-point loop: the normal equations, the damping ladder and the undamped inverse are defined once, and no
+    # alignment kernel file spells the ladder out
+    for word in ("point_lm_normal(", "point_lm_damped_step(", "point_lm_finish("):
+        assert [f for f, src in sources.items() if re.search(r"DEV \w+ " + re.escape(word), src)] == ["point_lm_dev.hpp"], word
+    assert [f for f, src in sources.items() if "tries < 26" in src] == ["point_lm_dev.hpp"]
+    for f in ("align_kernels.hip", "camalign_kernels.hip", "accalign_kernels.hip"):
+        assert "point_lm_damped_step(" in sources[f] and "point_lm_finish(" in sources[f] and "kLmLambdaMax" not in sources[f], f
     assert sorted(f for f, src in sources.items() if "lm_control_decide(" in src) == ["arrowhead_dev.hpp", "calib_kernels.hip", "rig_kernels.hip"]
     # the camera-model dispatch: defined in kernels.hpp, used by the three launch files
     assert "with_camera_model(int model" in sources["kernels.hpp"]

@@ -12,8 +12,9 @@ from calico_amd import synthetic as syn
 from golden_io import scene_from_dict
 
 FIXTURES = sorted(f for f in glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "*.npz"))
-                  # not scenes: the reference's iteration table (tests/test_ceres_log.py), recorded bits (tests/test_gpu_arrowhead_bits.py)
-                  if not os.path.basename(f).startswith(("ceres_log", "arrowhead_parent_bits")))
+                  # not scenes: the reference's iteration table (tests/test_ceres_log.py), recorded bits (tests/test_gpu_arrowhead_bits.py,
+                  # tests/test_gpu_align_bits.py)
+                  if not os.path.basename(f).startswith(("ceres_log", "arrowhead_parent_bits", "align_parent_bits")))
 
 
 def _check(api, path, rtol_eval, rtol_solve):

@@ -6,7 +6,7 @@ of the returned struct in scratch here -- 24 bytes per lane -- which is why imu_
 As compiled, VGPRs and LDS bytes per workgroup:
   align_corr_kernel 110 / 832 (4 waves x 8 lags x 3 sums + 4 x 2)      align_corr_peak_kernel 32 / 33024 (the curve: 4096 doubles)
   align_horn_sums_kernel 74 / 1280 (4 waves x 40 doubles)              align_horn_kernel 114 / 320 (the Jacobi iterations live in registers)
-  align_eval_kernel 88 / 1280                                          align_decide_kernel 64 / 784 (40 + 49 + 8 doubles + the flag)
+  align_eval_kernel 88 / 1280                                          align_decide_kernel 52 / 784 (40 + 49 + 8 doubles + the flag)
   align_final_kernel 20 / 784                                          align_accel_kernel<false / true> 98 / 1280
   align_accel_solve_kernel 14 / 672
 The per-sample kernels run 256 threads per workgroup; at most 128 VGPRs keeps four waves per SIMD. The LDS figures are the
