@@ -178,6 +178,9 @@ ALIGN_MAX_LAGS = 4096
 
 FIT_MAX_LAMBDAS = 32
 FIT_OK, FIT_NOT_POSITIVE_DEFINITE, FIT_TARGET_NOT_MET = 0, 1, 2
+FIT_MAX_ITERATIONS, FIT_SCALE_ZERO = 3, 4      # group statuses of the robust fit
+ROBUST_HUBER, ROBUST_TUKEY = 1, 2
+FIT_ROBUST_ITERATION_LIMIT = 64
 
 
 class SplineFitOptions(C.Structure):
@@ -195,6 +198,20 @@ class SplineFitRow(C.Structure):
 class SplineFitSummary(C.Structure):
     """calico_spline_fit_summary."""
     _fields_ = [("status", C.c_int32 * 2), ("chosen", C.c_int32 * 2), ("n_used", C.c_int64 * 2)]
+
+
+class SplineRobustOptions(C.Structure):
+    """calico_spline_robust_options."""
+    _fields_ = [("loss", C.c_int32), ("max_iterations", C.c_int32), ("tuning_rot", C.c_double), ("tuning_pos", C.c_double),
+                ("scale_rot", C.c_double), ("scale_pos", C.c_double), ("min_scale_rot", C.c_double), ("min_scale_pos", C.c_double),
+                ("step_tolerance", C.c_double)]
+
+
+class SplineRobustSummary(C.Structure):
+    """calico_spline_robust_summary: one entry per group."""
+    _fields_ = [("status", C.c_int32 * 2), ("iterations", C.c_int32 * 2), ("replaced_pivots", C.c_int32 * 2), ("n_used", C.c_int64 * 2),
+                ("n_downweighted", C.c_int64 * 2), ("n_rejected", C.c_int64 * 2), ("lambda_", C.c_double * 2), ("scale", C.c_double * 2),
+                ("median_residual", C.c_double * 2), ("last_step", C.c_double * 2), ("rss", C.c_double * 2)]
 
 
 class Iteration(C.Structure):
@@ -262,6 +279,7 @@ ABI_SYMBOLS = [
     "default_accel_alignment_options", "accel_align",
     "default_rig_options", "rig_calibrate",
     "default_spline_fit_options", "fit_spline_smooth",
+    "default_spline_robust_options", "fit_spline_robust",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -381,6 +399,11 @@ class CApi:
                 g("default_spline_fit_options", None, [FO])
                 g("fit_spline_smooth", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, D, D, C.POINTER(SplineFitRow),
                                                    C.POINTER(SplineFitSummary)])
+            if hasattr(self.lib, self.prefix + "fit_spline_robust"):
+                FO, RO = C.POINTER(SplineFitOptions), C.POINTER(SplineRobustOptions)
+                g("default_spline_robust_options", None, [RO])
+                g("fit_spline_robust", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, RO, D, D, D,
+                                                   C.POINTER(SplineRobustSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -812,6 +835,37 @@ def fit_spline_smooth(api, order, knots, basis, stamps, data6, weights=None, opt
     names = [("status", "status"), ("replaced_pivots", "replaced_pivots"), ("lambda", "lambda_"), ("rss", "rss"), ("penalty", "penalty"), ("rms", "rms")]
     return dict(ctrl=ctrl, ctrl_all=ctrl_all, rows=[[{k: getattr(rows[g * nl + l], f) for k, f in names} for l in range(nl)] for g in range(2)],
                 summary=dict(status=list(summary.status), chosen=list(summary.chosen), n_used=list(summary.n_used)))
+
+
+def default_spline_robust_options(api, **kw):
+    """The library's default calico_spline_robust_options with the given fields replaced."""
+    return _options(SplineRobustOptions, api.default_spline_robust_options, "robust spline fit", kw)
+
+
+def fit_spline_robust(api, order, knots, basis, stamps, data6, weights=None, options=None, robust=None, device=0):
+    """calico_fit_spline_robust: iteratively reweighted least squares (Huber or Tukey, scale from the median residual norm) around
+    the smoothing fit, per channel group. weights: (n, 2) prior weights or None. options: a SplineFitOptions with one lambda and
+    no target, or None; robust: a SplineRobustOptions (default_spline_robust_options(api, ...)) or None. Returns a dict: ctrl
+    (n_ctrl, 6), robust_weights (n, 2: u of the last solve, 0 where the prior weight is 0), residuals (n, 2: the residual norms at
+    ctrl, NaN where the prior weight is 0) and summary (a dict of two-entry lists, one entry per group)."""
+    knots, basis, order = _f64(knots).ravel(), _f64(basis), int(order)
+    t, d = _f64(stamps).ravel(), _f64(data6).reshape(-1, 6)
+    if len(t) != len(d):
+        raise ValueError("one stamp per sample")
+    if basis.size != max(len(knots) - 2 * order + 1, 0) * order * order:
+        raise ValueError("basis must be (n_knots - 2 order + 1, order, order)")
+    w = None if weights is None else _f64(weights).reshape(-1, 2)
+    if w is not None and len(w) != len(t):
+        raise ValueError("weights must be (n, 2)")
+    ctrl = np.full((max(len(knots) - order, 1), 6), np.nan)
+    u, e = np.full((len(t), 2), np.nan), np.full((len(t), 2), np.nan)
+    summary = SplineRobustSummary()
+    st = api.fit_spline_robust(int(device), order, len(knots), _dp(knots), _dp(basis), len(t), _dp(t), _dp(d), None if w is None else _dp(w),
+                               None if options is None else C.byref(options), None if robust is None else C.byref(robust), _dp(ctrl), _dp(u),
+                               _dp(e), C.byref(summary))
+    _check_free(api, st)
+    return dict(ctrl=ctrl, robust_weights=u, residuals=e,
+                summary={name.rstrip("_"): list(getattr(summary, name)) for name, _ in SplineRobustSummary._fields_})
 
 
 class Problem:

@@ -173,6 +173,20 @@ inline std::string spline_fit_options_error(int order, const calico_spline_fit_o
   }
   return "";
 }
+// calico_fit_spline_robust: what it asks of the smoothing fit's options (already valid) and of its own
+inline std::string spline_robust_options_error(const calico_spline_fit_options& fit, const calico_spline_robust_options& o) {
+  if (fit.n_lambda != 1) return "n_lambda must be 1: the robust fit takes one lambda per group";
+  if (fit.target_rms_rot != 0.0 || fit.target_rms_pos != 0.0) return "target_rms_rot and target_rms_pos must be 0: the robust fit chooses no lambda";
+  if (o.loss != CALICO_ROBUST_HUBER && o.loss != CALICO_ROBUST_TUKEY) return "unknown loss " + std::to_string(o.loss);
+  if (o.max_iterations < 0 || o.max_iterations > CALICO_FIT_ROBUST_ITERATION_LIMIT)
+    return "max_iterations must be in [0, " + std::to_string(CALICO_FIT_ROBUST_ITERATION_LIMIT) + "]";
+  const struct { const char* name; double v; } fields[] = {
+      {"tuning_rot", o.tuning_rot}, {"tuning_pos", o.tuning_pos}, {"scale_rot", o.scale_rot}, {"scale_pos", o.scale_pos},
+      {"min_scale_rot", o.min_scale_rot}, {"min_scale_pos", o.min_scale_pos}, {"step_tolerance", o.step_tolerance}};
+  for (const auto& f : fields)
+    if (!std::isfinite(f.v) || f.v < 0.0) return std::string(f.name) + " must be finite and >= 0";
+  return "";
+}
 inline std::string sample_weights_error(int64_t n, const double* weights, int64_t n_used[2]) {
   n_used[0] = n_used[1] = weights ? 0 : n;
   if (!weights) return "";

@@ -2,7 +2,9 @@
 // (kernels: fit_kernels.hip). Everything that can be checked without a device is checked before the first HIP call. The host
 // finds the segment of every sample (the samples are sorted: a CSR over the segments), uploads, launches and reads back.
 // calico_fit_spline_smooth is the same call with sample weights, a roughness penalty and a grid of lambda per channel group: the
-// device solves every (group, lambda), the host applies the selection rule to the rows it downloads.
+// device solves every (group, lambda), the host applies the selection rule to the rows it downloads. calico_fit_spline_robust is
+// the smoothing fit with one lambda followed by reweighted solves (kernels: fit_robust_kernels.hip): the host enqueues every
+// iteration, the device decides which of them still run, and the host reads back once.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -145,5 +147,97 @@ extern "C" int32_t calico_fit_spline_smooth(int32_t device, int32_t order, int32
   for (int g = 0; g < 2; ++g)
     if (summary->status[g] == CALICO_FIT_NOT_POSITIVE_DEFINITE)
       return call.fail(CALICO_INTERNAL, std::string("no lambda of the ") + (g == 0 ? "rotation" : "position") + " grid has a finite factorisation");
+  return CALICO_OK;
+}
+
+extern "C" void calico_default_spline_robust_options(calico_spline_robust_options* o) {
+  if (!o) return;
+  *o = calico_spline_robust_options{};
+  o->loss = CALICO_ROBUST_HUBER; o->max_iterations = 20; o->step_tolerance = 1e-9;
+}
+
+// calico_fit_spline_robust: the smoothing fit's checks, uploads and launch arguments with n_lambda 1; the loop itself is the
+// device's (fit_robust_kernels.hip): iteration 0 plus max_iterations reweighted ones are enqueued, then one readback.
+extern "C" int32_t calico_fit_spline_robust(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis, int64_t n,
+                                            const double* stamps, const double* data6, const double* weights,
+                                            const calico_spline_fit_options* fit, const calico_spline_robust_options* robust, double* ctrl_out,
+                                            double* robust_weights_out, double* residuals_out, calico_spline_robust_summary* summary) {
+  using namespace cal;
+  const FreeCall call{"calico_fit_spline_robust"};
+  calico_spline_fit_options o;
+  calico_spline_robust_options ro;
+  if (fit) o = *fit; else calico_default_spline_fit_options(&o);
+  if (robust) ro = *robust; else calico_default_spline_robust_options(&ro);
+  std::string error = spline_shape_error(order, n_knots, kMaxOrder);
+  if (error.empty() && (!knots || !basis || !stamps || !data6 || !ctrl_out || !summary)) error = "null knots, basis, stamps, data, ctrl_out or summary";
+  if (error.empty() && n <= 0) error = "n must be > 0";
+  if (error.empty()) error = spline_fit_options_error(order, o);
+  if (error.empty()) error = spline_robust_options_error(o, ro);
+  if (!error.empty()) return call.invalid(error);
+  if (n > INT32_MAX) return call.fail(CALICO_UNIMPLEMENTED, "more than 2^31 - 1 samples");      // the kernels and seg_ptr index the samples with int
+  if (!(error = stamps_error("sample", n, stamps)).empty()) return call.invalid(error);
+  int64_t n_used[2];
+  if (!(error = sample_weights_error(n, weights, n_used)).empty()) return call.invalid(error);
+  const int k = order, n_ctrl = n_knots - k, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1;
+  std::vector<int> seg, seg_ptr;
+  if (!(error = bin_samples(k, n_valid, knots, n, stamps, &seg, &seg_ptr)).empty()) return call.invalid(error);
+  if (fit_solve_smooth_lds_bytes(n_ctrl, k) > 156 * 1024) return call.fail(CALICO_UNIMPLEMENTED, "the trajectory is too long for the banded solve in LDS");
+  if (int rc = call.select_device(device)) return rc;
+  FreeBuf<double> d_stamps, d_data, d_weights, d_knots, d_basis, d_W, d_P, d_band, d_rhs, d_ctrl, d_e, d_u, d_wu;
+  FreeBuf<int> d_seg, d_ptr, d_hist;
+  FreeBuf<FitSmoothRow> d_rows;
+  FreeBuf<FitRobustState> d_state;
+  std::vector<double> u(size_t(n) * 2, 1.0);      // the robust weights before any reweighting: 1, and 0 where the prior weight is 0
+  if (weights) for (size_t i = 0; i < u.size(); ++i) u[i] = weights[i] > 0.0 ? 1.0 : 0.0;
+  FREE_TRY(call, d_stamps.upload(stamps, size_t(n))); FREE_TRY(call, d_data.upload(data6, size_t(n) * 6));
+  if (weights) FREE_TRY(call, d_weights.upload(weights, size_t(n) * 2));
+  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
+  FREE_TRY(call, d_seg.upload(seg.data(), seg.size())); FREE_TRY(call, d_ptr.upload(seg_ptr.data(), seg_ptr.size()));
+  FREE_TRY(call, d_W.alloc(size_t(n) * k)); FREE_TRY(call, d_P.alloc(size_t(n_ctrl) * k));
+  FREE_TRY(call, d_band.alloc(size_t(2) * n_ctrl * k)); FREE_TRY(call, d_rhs.alloc(size_t(2) * n_ctrl * 3));
+  FREE_TRY(call, d_ctrl.alloc(size_t(n_ctrl) * 6)); FREE_TRY(call, d_ctrl.zero(size_t(n_ctrl) * 6)); FREE_TRY(call, d_rows.alloc(2));
+  FREE_TRY(call, d_e.alloc(size_t(n) * 2)); FREE_TRY(call, d_u.upload(u.data(), u.size())); FREE_TRY(call, d_wu.alloc(size_t(n) * 2));
+  FREE_TRY(call, d_hist.alloc(size_t(2) * 8 * 256)); FREE_TRY(call, d_state.alloc(2));
+  FitSmoothArgs a = {};
+  a.n = int(n); a.k = k; a.n_ctrl = n_ctrl; a.n_seg = n_seg; a.derivative = o.derivative; a.relative = o.relative != 0; a.n_lambda = 1;
+  a.n_used_rot = int(n_used[0]); a.n_used_pos = int(n_used[1]);
+  a.lambda_rot[0] = o.lambda_rot[0]; a.lambda_pos[0] = o.lambda_pos[0];
+  a.stamps = d_stamps.p; a.seg = d_seg.p; a.seg_ptr = d_ptr.p; a.knots = d_knots.p; a.basis = d_basis.p; a.data = d_data.p; a.weights = d_weights.p;
+  a.W = d_W.p; a.P = d_P.p; a.band = d_band.p; a.rhs = d_rhs.p; a.ctrl_all = d_ctrl.p; a.rows = d_rows.p;
+  FitRobustArgs r = {};
+  r.loss = ro.loss; r.max_iterations = ro.max_iterations; r.step_tolerance = ro.step_tolerance;
+  const double default_tuning = ro.loss == CALICO_ROBUST_HUBER ? 2.7955 : 2.0 * 2.7955;
+  for (int g = 0; g < 2; ++g) {
+    const double tuning = g == 0 ? ro.tuning_rot : ro.tuning_pos;
+    r.rank[g] = int((n_used[g] - 1) / 2);
+    r.tuning[g] = tuning > 0.0 ? tuning : default_tuning;
+    r.fixed_scale[g] = g == 0 ? ro.scale_rot : ro.scale_pos;
+    r.min_scale[g] = g == 0 ? ro.min_scale_rot : ro.min_scale_pos;
+  }
+  r.e = d_e.p; r.u = d_u.p; r.wu = d_wu.p; r.hist = d_hist.p; r.state = d_state.p;
+  FREE_TRY(call, launch_fit_spline_robust(device, a, r, nullptr));
+  FitRobustState state[2];
+  std::vector<double> ctrl(size_t(n_ctrl) * 6);
+  FREE_TRY(call, d_state.download(state, 2)); FREE_TRY(call, d_ctrl.download(ctrl.data(), ctrl.size()));
+  std::vector<double> e;
+  if (robust_weights_out) FREE_TRY(call, d_u.download(u.data(), u.size()));
+  if (residuals_out) { e.resize(size_t(n) * 2); FREE_TRY(call, d_e.download(e.data(), e.size())); }
+  int failed = -1;
+  for (int g = 0; g < 2; ++g) {
+    const FitRobustState& st = state[g];
+    summary->status[g] = st.status; summary->iterations[g] = st.iterations; summary->replaced_pivots[g] = st.replaced_pivots;
+    summary->n_used[g] = n_used[g]; summary->n_downweighted[g] = st.n_downweighted; summary->n_rejected[g] = st.n_rejected;
+    summary->lambda[g] = st.lambda; summary->scale[g] = st.scale; summary->median_residual[g] = st.median; summary->last_step[g] = st.last_step;
+    summary->rss[g] = st.rss;
+    if (st.status == CALICO_FIT_NOT_POSITIVE_DEFINITE && failed < 0) failed = g;
+    if (st.status == CALICO_FIT_NOT_POSITIVE_DEFINITE && st.iterations == 0 && st.done_iter == 1) continue;      // iteration 0 wrote no control points
+    for (int i = 0; i < n_ctrl; ++i) for (int c = 0; c < 3; ++c) ctrl_out[size_t(i) * 6 + 3 * g + c] = ctrl[size_t(i) * 6 + 3 * g + c];
+    for (int64_t j = 0; j < n; ++j) {
+      if (robust_weights_out) robust_weights_out[j * 2 + g] = u[size_t(j) * 2 + g];
+      if (residuals_out) residuals_out[j * 2 + g] = e[size_t(j) * 2 + g];
+    }
+  }
+  if (failed >= 0)
+    return call.fail(CALICO_INTERNAL, std::string("a pivot of the ") + (failed == 0 ? "rotation" : "position") + " group's normal equations was not finite");
   return CALICO_OK;
 }

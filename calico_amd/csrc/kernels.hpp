@@ -148,6 +148,17 @@ struct FitSmoothArgs {
 };
 size_t fit_solve_smooth_lds_bytes(int n_ctrl, int k);      // [band | 3 rhs] of one group
 hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s);
+// The robust fit (fit_robust_kernels.hip): iteratively reweighted least squares around the smoothing fit with n_lambda 1, one loop
+// per group, controlled on the device. state [2]: done_iter is the control word (0: running; 1 + the iteration that finished the
+// group), read first by every kernel of a later iteration. e, u, wu [n][2]: residual norms, robust weights (uploaded as 1, 0 where
+// the prior weight is 0) and prior x robust weights; hist [2][8][256]: the digit counts of the selection.
+struct FitRobustState { int done_iter, status, iterations, replaced_pivots, n_downweighted, n_rejected; double lambda, scale, median, last_step, rss; };
+struct FitRobustArgs {
+  int loss, max_iterations, rank[2];      // rank: (m - 1) / 2 of the m samples of weight > 0
+  double tuning[2], fixed_scale[2], min_scale[2], step_tolerance;
+  double* e; double* u; double* wu; int* hist; FitRobustState* state;
+};
+hipError_t launch_fit_spline_robust(int device, const FitSmoothArgs& a, const FitRobustArgs& r, hipStream_t s);
 
 // ---- camera model maps (camera_kernels.hip): free pixels and points, no residual blocks -----------------------------------
 // All pointers are device memory; `k` (the intrinsics) and, in the rig frame, q_rc are read through wave-uniform addresses. The

@@ -229,6 +229,31 @@ calico_spline_fit_options spline_fit_options(const py::object& options) {
   }
   return o;
 }
+// None, or a dict of calico_spline_robust_options fields; loss: CALICO_ROBUST_HUBER / _TUKEY, or "huber" / "tukey"
+calico_spline_robust_options spline_robust_options(const py::object& options) {
+  calico_spline_robust_options o;
+  calico_default_spline_robust_options(&o);
+  if (options.is_none()) return o;
+  for (auto kv : py::cast<py::dict>(options)) {
+    const std::string name = py::cast<std::string>(kv.first);
+    if (name == "loss") {
+      if (py::isinstance<py::str>(kv.second)) {
+        const std::string loss = py::cast<std::string>(kv.second);
+        if (loss != "huber" && loss != "tukey") throw py::value_error("loss must be 'huber' or 'tukey'");
+        o.loss = loss == "huber" ? CALICO_ROBUST_HUBER : CALICO_ROBUST_TUKEY;
+      } else o.loss = py::cast<int>(kv.second);
+    } else if (name == "max_iterations") o.max_iterations = py::cast<int>(kv.second);
+    else if (name == "tuning_rot") o.tuning_rot = py::cast<double>(kv.second);
+    else if (name == "tuning_pos") o.tuning_pos = py::cast<double>(kv.second);
+    else if (name == "scale_rot") o.scale_rot = py::cast<double>(kv.second);
+    else if (name == "scale_pos") o.scale_pos = py::cast<double>(kv.second);
+    else if (name == "min_scale_rot") o.min_scale_rot = py::cast<double>(kv.second);
+    else if (name == "min_scale_pos") o.min_scale_pos = py::cast<double>(kv.second);
+    else if (name == "step_tolerance") o.step_tolerance = py::cast<double>(kv.second);
+    else throw py::type_error("no robust spline fit option '" + name + "'");
+  }
+  return o;
+}
 std::vector<uint8_t> to_mask(const py::object& o) {
   std::vector<uint8_t> mask;
   if (!o.is_none())
@@ -642,6 +667,47 @@ PYBIND11_MODULE(_calico, m) {
           },
           py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
           py::arg("spline_order") = Trajectory::kDefaultSplineOrder, py::arg("options") = py::none(), py::arg("weights") = py::none())
+      // The robust fit (calico_fit_spline_robust). options: as FitSplineSmooth's, with one lambda per group; robust: None or a dict of
+      // calico_spline_robust_options fields (loss: "huber" or "tukey"); weights: prior weights, as FitSplineSmooth's. Returns a dict: the
+      // summary's fields (one entry per group), and robust_weights and residuals, one [rotation, position] pair per pose in time order.
+      .def(
+          "FitSplineRobust",
+          [](Trajectory& self, const std::map<double, Pose3d>& poses, double knot_frequency, int spline_order, const py::object& options,
+             const py::object& robust, const py::object& weights) {
+            const calico_spline_fit_options o = spline_fit_options(options);
+            const calico_spline_robust_options r = spline_robust_options(robust);
+            std::vector<std::array<double, 2>> w;
+            if (!weights.is_none())
+              for (auto row : py::cast<py::sequence>(weights)) {
+                const auto pair = py::cast<std::vector<double>>(row);
+                if (pair.size() != 2) throw py::value_error("weights: one [rotation, position] pair per pose");
+                w.push_back({pair[0], pair[1]});
+              }
+            auto res = self.FitSplineRobust(poses, knot_frequency, spline_order, o, r, w);
+            raise_if_error(res.status());
+            const calico_spline_robust_summary& sm = res.value().summary;
+            py::dict out;
+            out["status"] = py::make_tuple(sm.status[0], sm.status[1]);
+            out["iterations"] = py::make_tuple(sm.iterations[0], sm.iterations[1]);
+            out["replaced_pivots"] = py::make_tuple(sm.replaced_pivots[0], sm.replaced_pivots[1]);
+            out["n_used"] = py::make_tuple(sm.n_used[0], sm.n_used[1]);
+            out["n_downweighted"] = py::make_tuple(sm.n_downweighted[0], sm.n_downweighted[1]);
+            out["n_rejected"] = py::make_tuple(sm.n_rejected[0], sm.n_rejected[1]);
+            out["lambda"] = py::make_tuple(sm.lambda[0], sm.lambda[1]);
+            out["scale"] = py::make_tuple(sm.scale[0], sm.scale[1]);
+            out["median_residual"] = py::make_tuple(sm.median_residual[0], sm.median_residual[1]);
+            out["last_step"] = py::make_tuple(sm.last_step[0], sm.last_step[1]);
+            out["rss"] = py::make_tuple(sm.rss[0], sm.rss[1]);
+            py::list u, e;
+            for (const auto& pair : res.value().robust_weights) u.append(py::make_tuple(pair[0], pair[1]));
+            for (const auto& pair : res.value().residuals) e.append(py::make_tuple(pair[0], pair[1]));
+            out["robust_weights"] = u;
+            out["residuals"] = e;
+            return out;
+          },
+          py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
+          py::arg("spline_order") = Trajectory::kDefaultSplineOrder, py::arg("options") = py::none(), py::arg("robust") = py::none(),
+          py::arg("weights") = py::none())
       .def("Interpolate", [](const Trajectory& self, const std::vector<double>& stamps) {
         auto poses = self.Interpolate(stamps);
         raise_if_error(poses.status());

@@ -621,6 +621,66 @@ class BSpline6 {
     for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
     return OkStatus();
   }
+  /// What a robust fit found: the summary (per group status, iterations, scale, counts), and per sample in time order the robust
+  /// weight of the last solve (0 where the prior weight is 0) and the residual norm at the result (NaN there), [rotation, position].
+  struct RobustFit {
+    calico_spline_robust_summary summary{};
+    std::vector<std::array<double, 2>> robust_weights, residuals;
+  };
+#ifdef CALICO_TEST_HOOKS
+  /// Test builds only, as fit_solver(): the solve behind FitToDataRobust (calico_fit_spline_robust without its device argument).
+  using RobustFitSolver = int32_t (*)(int32_t order, int32_t n_knots, const double* knots, const double* basis, int64_t n, const double* stamps,
+                                      const double* data6, const double* weights, const calico_spline_fit_options* fit,
+                                      const calico_spline_robust_options* robust, double* ctrl_out, double* robust_weights_out,
+                                      double* residuals_out, calico_spline_robust_summary* summary);
+  static RobustFitSolver& robust_fit_solver() {
+    static RobustFitSolver solver = nullptr;
+    return solver;
+  }
+#endif
+  /// The robust fit on the knot vector and basis of FitToData: calico_fit_spline_robust on device 0 (iteratively reweighted least
+  /// squares around the smoothing fit; `options` takes one lambda per group and no target). weights: prior weights, as FitToDataSmooth's.
+  Status FitToDataRobust(const std::vector<double>& time, const std::vector<std::array<double, 6>>& data, int order, double knot_frequency,
+                         const calico_spline_fit_options& options, const calico_spline_robust_options& robust,
+                         const std::vector<std::array<double, 2>>& weights, RobustFit* fit = nullptr) {
+    if (time.empty()) return InvalidArgumentError("Attempted to fit data on empty time vector.");
+    if (data.empty()) return InvalidArgumentError("Attempted to fit on empty data.");
+    if (time.size() != data.size()) return InvalidArgumentError("Data and time vectors are not the same size.");
+    if (!weights.empty() && weights.size() != time.size()) return InvalidArgumentError("Weights and time vectors are not the same size.");
+    if (order < 2) return InvalidArgumentError("Spline order must be greater than 2. Got " + std::to_string(order));
+    if (knot_frequency <= 0) return InvalidArgumentError("Knot frequency must be greater than 0.");
+    const int nk = BuildKnots(time, order, knot_frequency), ncp = nk - order;
+    const int64_t nd = int64_t(time.size());
+    std::vector<double> flat(size_t(nd) * 6), w(weights.size() * 2), ctrl(size_t(ncp) * 6), u(size_t(nd) * 2), e(size_t(nd) * 2);
+    for (int64_t j = 0; j < nd; ++j) for (int c = 0; c < 6; ++c) flat[size_t(j) * 6 + c] = data[size_t(j)][size_t(c)];
+    for (size_t j = 0; j < weights.size(); ++j) { w[j * 2] = weights[j][0]; w[j * 2 + 1] = weights[j][1]; }
+    RobustFit found;
+    const double* wp = w.empty() ? nullptr : w.data();
+#ifdef CALICO_TEST_HOOKS
+    const int32_t rc = robust_fit_solver()
+        ? robust_fit_solver()(order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &robust, ctrl.data(), u.data(), e.data(), &found.summary)
+        : calico_fit_spline_robust(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &robust, ctrl.data(), u.data(), e.data(), &found.summary);
+#else
+    const int32_t rc = calico_fit_spline_robust(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &robust,
+                                                ctrl.data(), u.data(), e.data(), &found.summary);
+#endif
+    const char* why = calico_last_error(nullptr);
+    if (rc == CALICO_INVALID_ARGUMENT) return InvalidArgumentError(std::string("robust spline fit: ") + (why ? why : "invalid argument"));
+    if (rc == CALICO_UNIMPLEMENTED)      // the smoothing fit's ceiling: one group's [band | 3 rhs], n_ctrl (order + 3) doubles in 156 KiB
+      return UnimplementedError("robust spline fit: " + std::to_string(ncp) + " control points are too many for the on-device solve; order " +
+                                std::to_string(order) + " fits at most " + std::to_string(156 * 1024 / ((order + 3) * 8)));
+    found.robust_weights.resize(size_t(nd));
+    found.residuals.resize(size_t(nd));
+    for (int64_t j = 0; j < nd; ++j) {
+      found.robust_weights[size_t(j)] = {u[size_t(j) * 2], u[size_t(j) * 2 + 1]};
+      found.residuals[size_t(j)] = {e[size_t(j) * 2], e[size_t(j) * 2 + 1]};
+    }
+    if (fit) *fit = found;
+    if (rc != CALICO_OK) return InternalError("robust spline fit failed on the device");
+    ctrl_.assign(size_t(ncp), {});
+    for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
+    return OkStatus();
+  }
   /// bspline.hpp:39-72 at one time; error codes of bspline.hpp:74-85
   Status Evaluate(double t, int derivative, double out[6]) const {
     if (derivative < 0 || derivative > order_ - 1) return InvalidArgumentError("Invalid derivative for interpolation.");
@@ -709,6 +769,23 @@ class Trajectory {
     PosesToData(&stamps, &data);
     BSpline6::SmoothFit fit;
     const Status st = spline_.FitToDataSmooth(stamps, data, spline_order, knot_frequency, options, weights, &fit);
+    if (!st.ok()) return st;
+    return fit;
+  }
+  /// FitSpline with the robust fit (calico_fit_spline_robust): the same axis-angle conversion and phase unwrapping, then
+  /// iteratively reweighted least squares (Huber or Tukey) around the smoothing fit -- for poses that are wrong and not known to
+  /// be (a resection on the other branch of the planar ambiguity reports a small RMS). `fit_options` takes one lambda per group;
+  /// the result's robust_weights single out the poses the fit set aside, in time order.
+  StatusOr<BSpline6::RobustFit> FitSplineRobust(const std::map<double, Pose3d>& poses_world_sensorrig, double knot_frequency,
+                                                int spline_order, const calico_spline_fit_options& fit_options,
+                                                const calico_spline_robust_options& robust_options,
+                                                const std::vector<std::array<double, 2>>& weights = {}) {
+    poses_ = poses_world_sensorrig;
+    std::vector<double> stamps;
+    std::vector<std::array<double, 6>> data;
+    PosesToData(&stamps, &data);
+    BSpline6::RobustFit fit;
+    const Status st = spline_.FitToDataRobust(stamps, data, spline_order, knot_frequency, fit_options, robust_options, weights, &fit);
     if (!st.ok()) return st;
     return fit;
   }

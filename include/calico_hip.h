@@ -340,6 +340,74 @@ int32_t calico_fit_spline_smooth(int32_t device, int32_t order, int32_t n_knots,
                                  calico_spline_fit_row* rows_out /* 2 x n_lambda, may be NULL */,
                                  calico_spline_fit_summary* summary);
 
+/* The robust spline fit: iteratively reweighted least squares around calico_fit_spline_smooth, for samples that are wrong and not
+ * known to be (a resected pose on the other branch of the planar ambiguity reports a small RMS). One independent loop per channel
+ * group g, with prior weights w_j (weights[:, g], NULL = 1); the loop stays on the device, the host reads back once.
+ *   iteration 0      calico_fit_spline_smooth with n_lambda 1 (bit for bit). Its absolute lambda is frozen: a relative lambda is not
+ *                    re-derived from the reweighted trace, so the objective does not move with the weights.
+ *   iteration 1..T   e_j = |X_j C - d_j|_2 (the norm over the group's three channels) over the m samples with w_j > 0;
+ *                    med = the element of rank (m - 1) / 2 of the sorted e (the lower median, an exact order statistic);
+ *                    sigma = max(med / 1.5381722544550522, min_scale) -- the constant is sqrt(median of chi2_3), so sigma is the
+ *                    per-channel standard deviation of Gaussian residuals -- or the caller's scale > 0 (no selection runs then);
+ *                    sigma == 0: the group stops with CALICO_FIT_SCALE_ZERO at the previous control points and all u = 1;
+ *                    z = e / sigma;  Huber: u = min(1, c / z);  Tukey: u = (1 - (z / c)^2)^2 for z < c, else 0;
+ *                    (X^T diag(w u) X + lambda_abs P) C = X^T diag(w u) d with the smoothing fit's sums, ridge and pivot rule (a
+ *                    total weight of 0 is skipped like a prior weight of 0);
+ *                    step = max|C - C_prev| / max|C| (0 where no control point moved). 0 < step_tolerance and step <= it: the
+ *                    group is converged, CALICO_FIT_OK; after T iterations without that CALICO_FIT_MAX_ITERATIONS. A pivot that
+ *                    is not finite: CALICO_FIT_NOT_POSITIVE_DEFINITE, the group keeps the previous control points and the call
+ *                    returns kInternal (at iteration 0: that group's columns of ctrl_out are not written).
+ *   afterwards       one more residual pass gives residuals_out at ctrl_out.
+ * On data without noise the median residual is the spline's own approximation error, and Huber at a vanishing scale is an L1 fit
+ * that the iteration approaches slowly: give the noise floor as min_scale, or the scale itself.
+ * tuning 0 is the loss's default: c = 2.7955 for Huber (sqrt of the 95 % point of chi2_3), twice that for Tukey (conventions).
+ * robust_weights_out (n x 2, may be NULL) holds u of the last solve (1 where no reweighting ran), 0 where w = 0; residuals_out
+ * (n x 2, may be NULL) e at ctrl_out, NaN where w = 0 (those data are not read). The summary's scale and median_residual are the
+ * ones the last reweighting used (NaN: none ran; median_residual NaN with a caller's scale). Bit-reproducible: the selection adds
+ * integers only, every floating-point sum has a fixed order.
+ * kInvalidArgument for everything calico_fit_spline_smooth refuses, and for fit.n_lambda != 1 or a non-zero target, an unknown
+ * loss, max_iterations outside [0, CALICO_FIT_ROBUST_ITERATION_LIMIT], a negative or non-finite tuning, scale, min_scale or
+ * step_tolerance, a NULL summary or ctrl_out. kUnimplemented, outputs untouched, at the smoothing fit's LDS ceiling. */
+#define CALICO_FIT_MAX_ITERATIONS 3          /* group status: max_iterations reweighted solves without step <= step_tolerance */
+#define CALICO_FIT_SCALE_ZERO 4              /* group status: the scale estimate was 0 (set min_scale); previous control points kept */
+#define CALICO_ROBUST_HUBER 1
+#define CALICO_ROBUST_TUKEY 2
+#define CALICO_FIT_ROBUST_ITERATION_LIMIT 64
+typedef struct {
+  int32_t loss;             /* CALICO_ROBUST_HUBER */
+  int32_t max_iterations;   /* 20; 0..CALICO_FIT_ROBUST_ITERATION_LIMIT; 0 = the smoothing fit */
+  double tuning_rot;        /* 0 = the loss's default */
+  double tuning_pos;
+  double scale_rot;         /* 0 = estimate every iteration */
+  double scale_pos;
+  double min_scale_rot;     /* 0 */
+  double min_scale_pos;
+  double step_tolerance;    /* 1e-9; 0 = run every iteration */
+} calico_spline_robust_options;
+typedef struct {            /* per group */
+  int32_t status[2];        /* CALICO_FIT_OK, _NOT_POSITIVE_DEFINITE, _MAX_ITERATIONS or _SCALE_ZERO */
+  int32_t iterations[2];    /* reweighted solves that produced the control points */
+  int32_t replaced_pivots[2];
+  int64_t n_used[2];
+  int64_t n_downweighted[2];   /* 0 < u < 1 */
+  int64_t n_rejected[2];       /* u == 0 */
+  double lambda[2];         /* the absolute lambda of every solve */
+  double scale[2];
+  double median_residual[2];
+  double last_step[2];
+  double rss[2];            /* sum w u e^2 at the result */
+} calico_spline_robust_summary;
+void calico_default_spline_robust_options(calico_spline_robust_options* o);
+int32_t calico_fit_spline_robust(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                                 int64_t n, const double* stamps, const double* data6,
+                                 const double* weights /* n x 2 or NULL */,
+                                 const calico_spline_fit_options* fit /* NULL = defaults; n_lambda must be 1, targets 0 */,
+                                 const calico_spline_robust_options* robust /* NULL = defaults */,
+                                 double* ctrl_out /* n_ctrl x 6 */,
+                                 double* robust_weights_out /* n x 2, may be NULL */,
+                                 double* residuals_out /* n x 2, may be NULL */,
+                                 calico_spline_robust_summary* summary);
+
 /* Outlier tags (Camera::MarkOutliersById / ClearOutliers, camera.cpp:281-301; outlier_ids_, camera.h:185): tagged
  * observations stay registered but are left out of the problem, as AddResidualsToProblem does (camera.cpp:121-124) --
  * no residual block, no residual, not counted in the summary. `is_outlier` has one byte per observation of the
