@@ -181,6 +181,8 @@ FIT_OK, FIT_NOT_POSITIVE_DEFINITE, FIT_TARGET_NOT_MET = 0, 1, 2
 FIT_MAX_ITERATIONS, FIT_SCALE_ZERO = 3, 4      # group statuses of the robust fit
 ROBUST_HUBER, ROBUST_TUKEY = 1, 2
 FIT_ROBUST_ITERATION_LIMIT = 64
+FIT_CV_AT_GRID_END = 5                         # group status of the cross-validated fit
+FIT_CV_GCV, FIT_CV_PRESS = 0, 1
 
 
 class SplineFitOptions(C.Structure):
@@ -212,6 +214,21 @@ class SplineRobustSummary(C.Structure):
     _fields_ = [("status", C.c_int32 * 2), ("iterations", C.c_int32 * 2), ("replaced_pivots", C.c_int32 * 2), ("n_used", C.c_int64 * 2),
                 ("n_downweighted", C.c_int64 * 2), ("n_rejected", C.c_int64 * 2), ("lambda_", C.c_double * 2), ("scale", C.c_double * 2),
                 ("median_residual", C.c_double * 2), ("last_step", C.c_double * 2), ("rss", C.c_double * 2)]
+
+
+class SplineCvOptions(C.Structure):
+    """calico_spline_cv_options."""
+    _fields_ = [("criterion", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SplineCvRow(C.Structure):
+    """calico_spline_cv_row."""
+    _fields_ = [("edf", C.c_double), ("gcv", C.c_double), ("press", C.c_double), ("max_leverage", C.c_double)]
+
+
+class SplineCvSummary(C.Structure):
+    """calico_spline_cv_summary: one entry per group."""
+    _fields_ = [("status", C.c_int32 * 2), ("chosen", C.c_int32 * 2), ("n_used", C.c_int64 * 2), ("edf", C.c_double * 2), ("score", C.c_double * 2)]
 
 
 class Iteration(C.Structure):
@@ -280,6 +297,7 @@ ABI_SYMBOLS = [
     "default_rig_options", "rig_calibrate",
     "default_spline_fit_options", "fit_spline_smooth",
     "default_spline_robust_options", "fit_spline_robust",
+    "default_spline_cv_options", "fit_spline_cv",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -404,6 +422,11 @@ class CApi:
                 g("default_spline_robust_options", None, [RO])
                 g("fit_spline_robust", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, RO, D, D, D,
                                                    C.POINTER(SplineRobustSummary)])
+            if hasattr(self.lib, self.prefix + "fit_spline_cv"):
+                FO, CO = C.POINTER(SplineFitOptions), C.POINTER(SplineCvOptions)
+                g("default_spline_cv_options", None, [CO])
+                g("fit_spline_cv", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, CO, D, D, C.POINTER(SplineFitRow),
+                                               C.POINTER(SplineCvRow), D, D, C.POINTER(SplineCvSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -866,6 +889,46 @@ def fit_spline_robust(api, order, knots, basis, stamps, data6, weights=None, opt
     _check_free(api, st)
     return dict(ctrl=ctrl, robust_weights=u, residuals=e,
                 summary={name.rstrip("_"): list(getattr(summary, name)) for name, _ in SplineRobustSummary._fields_})
+
+
+def default_spline_cv_options(api, **kw):
+    """The library's default calico_spline_cv_options with the given fields replaced."""
+    return _options(SplineCvOptions, api.default_spline_cv_options, "cross-validated spline fit", kw)
+
+
+def fit_spline_cv(api, order, knots, basis, stamps, data6, weights=None, options=None, cv=None, device=0):
+    """calico_fit_spline_cv: the smoothing fit over the options' lambda grid with each group's lambda chosen by generalised
+    cross-validation or the leave-one-out score (cv: a SplineCvOptions, default_spline_cv_options(api, criterion=...), or None).
+    options: a SplineFitOptions without targets, or None. Returns fit_spline_smooth's dict (ctrl at the choice) plus cv_rows
+    ([group][lambda] dicts: edf, gcv, press, max_leverage), leverage (n, 2: h_j at the chosen lambda, 0 where the weight is 0),
+    loo_residuals (n, 2: e_j / (1 - h_j), NaN where the weight is 0), chosen, and a summary with status, chosen, n_used, edf, score."""
+    knots, basis, order = _f64(knots).ravel(), _f64(basis), int(order)
+    t, d = _f64(stamps).ravel(), _f64(data6).reshape(-1, 6)
+    if len(t) != len(d):
+        raise ValueError("one stamp per sample")
+    if basis.size != max(len(knots) - 2 * order + 1, 0) * order * order:
+        raise ValueError("basis must be (n_knots - 2 order + 1, order, order)")
+    w = None if weights is None else _f64(weights).reshape(-1, 2)
+    if w is not None and len(w) != len(t):
+        raise ValueError("weights must be (n, 2)")
+    nl = options.n_lambda if options is not None else 1
+    n_ctrl = max(len(knots) - order, 1)
+    ctrl = np.full((n_ctrl, 6), np.nan)
+    ctrl_all = np.full((max(min(nl, FIT_MAX_LAMBDAS), 1), n_ctrl, 6), np.nan)
+    rows = (SplineFitRow * (2 * len(ctrl_all)))()
+    cv_rows = (SplineCvRow * (2 * len(ctrl_all)))()
+    h, loo = np.full((len(t), 2), np.nan), np.full((len(t), 2), np.nan)
+    summary = SplineCvSummary()
+    st = api.fit_spline_cv(int(device), order, len(knots), _dp(knots), _dp(basis), len(t), _dp(t), _dp(d), None if w is None else _dp(w),
+                           None if options is None else C.byref(options), None if cv is None else C.byref(cv), _dp(ctrl), _dp(ctrl_all), rows,
+                           cv_rows, _dp(h), _dp(loo), C.byref(summary))
+    _check_free(api, st)
+    names = [("status", "status"), ("replaced_pivots", "replaced_pivots"), ("lambda", "lambda_"), ("rss", "rss"), ("penalty", "penalty"), ("rms", "rms")]
+    cv_names = ("edf", "gcv", "press", "max_leverage")
+    return dict(ctrl=ctrl, ctrl_all=ctrl_all, rows=[[{k: getattr(rows[g * nl + l], f) for k, f in names} for l in range(nl)] for g in range(2)],
+                cv_rows=[[{k: getattr(cv_rows[g * nl + l], k) for k in cv_names} for l in range(nl)] for g in range(2)],
+                leverage=h, loo_residuals=loo, chosen=list(summary.chosen),
+                summary={name: list(getattr(summary, name)) for name, _ in SplineCvSummary._fields_})
 
 
 class Problem:

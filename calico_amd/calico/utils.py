@@ -139,7 +139,8 @@ def InitializePoses(camera, all_detections: List[Dict[int, np.ndarray]], model_d
     conventions of InitializePinholeAndPoses; a frame that is not ok (too few points, no start, not converged, degenerate)
     carries the identity and must not be handed to FitSpline. With the smoothing fit (Trajectory.FitSplineSmooth) such frames
     are simply left out: its roughness penalty carries the spline across the gap they leave, where FitSpline would drop the
-    control points of a gap longer than the spline's support to zero. A frame that IS ok can still be wrong (the planar two-fold
+    control points of a gap longer than the spline's support to zero (Trajectory.FitSplineCV is the same fit with the penalty's
+    weight lambda chosen from a grid by cross-validation: no noise level of the poses is needed). A frame that IS ok can still be wrong (the planar two-fold
     ambiguity, few corners, a mis-decoded tag: a small RMS at a pose tenths of a radian off): for frames not known to be bad use
     the robust fit, Trajectory.FitSplineRobust, whose per-pose weights single them out."""
     r = camera.EstimateChartPoses(all_detections, model_definition)
@@ -228,7 +229,8 @@ def InitializeRig(cameras, rig_frames: List[Dict[int, Dict[int, np.ndarray]]], m
     Sets the extrinsics of the cameras that took part. Returns ([R_chart_rig per rig frame], [t_chart_rig per rig frame],
     ok (n_frames,) bool) in the conventions of InitializePoses -- what Trajectory.FitSpline takes, now also for the frames the
     reference camera never saw; a frame that is not ok carries the identity and must not be handed to FitSpline (with
-    Trajectory.FitSplineSmooth such frames are simply left out: the penalty carries the spline across the gap; for frames that are
+    Trajectory.FitSplineSmooth such frames are simply left out: the penalty carries the spline across the gap, and
+    Trajectory.FitSplineCV chooses the penalty's weight by cross-validation; for frames that are
     wrong and not known to be, Trajectory.FitSplineRobust downweights them and says which). options: None or
     a dict of calico_rig_options fields. Raises RuntimeError when the estimation does not end with status OK (before anything is
     changed)."""

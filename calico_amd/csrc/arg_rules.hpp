@@ -187,6 +187,12 @@ inline std::string spline_robust_options_error(const calico_spline_fit_options& 
     if (!std::isfinite(f.v) || f.v < 0.0) return std::string(f.name) + " must be finite and >= 0";
   return "";
 }
+// calico_fit_spline_cv: what it asks of the smoothing fit's options (already valid) and of its own
+inline std::string spline_cv_options_error(const calico_spline_fit_options& fit, const calico_spline_cv_options& o) {
+  if (fit.target_rms_rot != 0.0 || fit.target_rms_pos != 0.0) return "target_rms_rot and target_rms_pos must be 0: the cross-validated fit chooses lambda itself";
+  if (o.criterion != CALICO_FIT_CV_GCV && o.criterion != CALICO_FIT_CV_PRESS) return "unknown criterion " + std::to_string(o.criterion);
+  return "";
+}
 inline std::string sample_weights_error(int64_t n, const double* weights, int64_t n_used[2]) {
   n_used[0] = n_used[1] = weights ? 0 : n;
   if (!weights) return "";

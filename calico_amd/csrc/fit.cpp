@@ -4,7 +4,8 @@
 // calico_fit_spline_smooth is the same call with sample weights, a roughness penalty and a grid of lambda per channel group: the
 // device solves every (group, lambda), the host applies the selection rule to the rows it downloads. calico_fit_spline_robust is
 // the smoothing fit with one lambda followed by reweighted solves (kernels: fit_robust_kernels.hip): the host enqueues every
-// iteration, the device decides which of them still run, and the host reads back once.
+// iteration, the device decides which of them still run, and the host reads back once. calico_fit_spline_cv is the smoothing fit's
+// grid with the choice made on the device by cross-validation (kernels: fit_cv_kernels.hip), and one readback.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -239,5 +240,101 @@ extern "C" int32_t calico_fit_spline_robust(int32_t device, int32_t order, int32
   }
   if (failed >= 0)
     return call.fail(CALICO_INTERNAL, std::string("a pivot of the ") + (failed == 0 ? "rotation" : "position") + " group's normal equations was not finite");
+  return CALICO_OK;
+}
+
+extern "C" void calico_default_spline_cv_options(calico_spline_cv_options* o) {
+  if (!o) return;
+  *o = calico_spline_cv_options{};
+  o->criterion = CALICO_FIT_CV_GCV;
+}
+
+static_assert(sizeof(cal::FitCvRow) == sizeof(calico_spline_cv_row), "the kernels write calico_spline_cv_row");
+
+// calico_fit_spline_cv: the smoothing fit's checks, uploads and launch arguments; the solve kernel also inverts on the band, the
+// scores and the choice are the device's (fit_cv_kernels.hip); one readback.
+extern "C" int32_t calico_fit_spline_cv(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis, int64_t n,
+                                        const double* stamps, const double* data6, const double* weights, const calico_spline_fit_options* fit,
+                                        const calico_spline_cv_options* cv, double* ctrl_out, double* ctrl_all_out, calico_spline_fit_row* rows_out,
+                                        calico_spline_cv_row* cv_rows_out, double* leverage_out, double* loo_residuals_out,
+                                        calico_spline_cv_summary* summary) {
+  using namespace cal;
+  const FreeCall call{"calico_fit_spline_cv"};
+  calico_spline_fit_options o;
+  calico_spline_cv_options co;
+  if (fit) o = *fit; else calico_default_spline_fit_options(&o);
+  if (cv) co = *cv; else calico_default_spline_cv_options(&co);
+  std::string error = spline_shape_error(order, n_knots, kMaxOrder);
+  if (error.empty() && (!knots || !basis || !stamps || !data6 || !ctrl_out || !summary)) error = "null knots, basis, stamps, data, ctrl_out or summary";
+  if (error.empty() && n <= 0) error = "n must be > 0";
+  if (error.empty()) error = spline_fit_options_error(order, o);
+  if (error.empty()) error = spline_cv_options_error(o, co);
+  if (!error.empty()) return call.invalid(error);
+  if (n > INT32_MAX) return call.fail(CALICO_UNIMPLEMENTED, "more than 2^31 - 1 samples");      // the kernels and seg_ptr index the samples with int
+  if (!(error = stamps_error("sample", n, stamps)).empty()) return call.invalid(error);
+  int64_t n_used[2];
+  if (!(error = sample_weights_error(n, weights, n_used)).empty()) return call.invalid(error);
+  const int k = order, n_ctrl = n_knots - k, n_valid = spline_valid_knots(k, n_knots), n_seg = n_valid - 1, nl = o.n_lambda;
+  std::vector<int> seg, seg_ptr;
+  if (!(error = bin_samples(k, n_valid, knots, n, stamps, &seg, &seg_ptr)).empty()) return call.invalid(error);
+  if (fit_solve_smooth_lds_bytes(n_ctrl, k) > 156 * 1024) return call.fail(CALICO_UNIMPLEMENTED, "the trajectory is too long for the banded solve in LDS");
+  if (int rc = call.select_device(device)) return rc;
+  const int n_blocks = int((n + 255) / 256);
+  FreeBuf<double> d_stamps, d_data, d_weights, d_knots, d_basis, d_W, d_P, d_band, d_rhs, d_ctrl, d_zband, d_edf, d_partial, d_leverage, d_loo;
+  FreeBuf<int> d_seg, d_ptr;
+  FreeBuf<FitSmoothRow> d_rows;
+  FreeBuf<FitCvRow> d_cv_rows;
+  FreeBuf<FitCvSummary> d_summary;
+  FREE_TRY(call, d_stamps.upload(stamps, size_t(n))); FREE_TRY(call, d_data.upload(data6, size_t(n) * 6));
+  if (weights) FREE_TRY(call, d_weights.upload(weights, size_t(n) * 2));
+  FREE_TRY(call, d_knots.upload(knots, size_t(n_knots))); FREE_TRY(call, d_basis.upload(basis, size_t(n_seg) * k * k));
+  FREE_TRY(call, d_seg.upload(seg.data(), seg.size())); FREE_TRY(call, d_ptr.upload(seg_ptr.data(), seg_ptr.size()));
+  FREE_TRY(call, d_W.alloc(size_t(n) * k)); FREE_TRY(call, d_P.alloc(size_t(n_ctrl) * k));
+  FREE_TRY(call, d_band.alloc(size_t(2) * n_ctrl * k)); FREE_TRY(call, d_rhs.alloc(size_t(2) * n_ctrl * 3));
+  FREE_TRY(call, d_ctrl.alloc(size_t(nl) * n_ctrl * 6)); FREE_TRY(call, d_rows.alloc(size_t(2) * nl));
+  FREE_TRY(call, d_zband.alloc(size_t(2) * nl * n_ctrl * k)); FREE_TRY(call, d_edf.alloc(size_t(2) * nl));
+  FREE_TRY(call, d_partial.alloc(size_t(2) * nl * n_blocks * 2)); FREE_TRY(call, d_cv_rows.alloc(size_t(2) * nl)); FREE_TRY(call, d_summary.alloc(1));
+  FREE_TRY(call, d_leverage.alloc(size_t(n) * 2)); FREE_TRY(call, d_loo.alloc(size_t(n) * 2));
+  FitSmoothArgs a = {};
+  a.n = int(n); a.k = k; a.n_ctrl = n_ctrl; a.n_seg = n_seg; a.derivative = o.derivative; a.relative = o.relative != 0; a.n_lambda = nl;
+  a.n_used_rot = int(n_used[0]); a.n_used_pos = int(n_used[1]);
+  for (int l = 0; l < nl; ++l) { a.lambda_rot[l] = o.lambda_rot[l]; a.lambda_pos[l] = o.lambda_pos[l]; }
+  a.stamps = d_stamps.p; a.seg = d_seg.p; a.seg_ptr = d_ptr.p; a.knots = d_knots.p; a.basis = d_basis.p; a.data = d_data.p; a.weights = d_weights.p;
+  a.W = d_W.p; a.P = d_P.p; a.band = d_band.p; a.rhs = d_rhs.p; a.ctrl_all = d_ctrl.p; a.rows = d_rows.p;
+  FitCvArgs c = {};
+  c.criterion = co.criterion; c.n_blocks = n_blocks;
+  c.zband = d_zband.p; c.edf = d_edf.p; c.partial = d_partial.p; c.cv_rows = d_cv_rows.p; c.summary = d_summary.p; c.leverage = d_leverage.p; c.loo = d_loo.p;
+  FREE_TRY(call, launch_fit_spline_cv(device, a, c, nullptr));
+  std::vector<FitSmoothRow> rows(size_t(2) * nl);
+  std::vector<FitCvRow> cv_rows(size_t(2) * nl);
+  std::vector<double> ctrl(size_t(nl) * n_ctrl * 6), leverage, loo;
+  FitCvSummary sm;
+  FREE_TRY(call, d_summary.download(&sm, 1)); FREE_TRY(call, d_rows.download(rows.data(), rows.size()));
+  FREE_TRY(call, d_cv_rows.download(cv_rows.data(), cv_rows.size())); FREE_TRY(call, d_ctrl.download(ctrl.data(), ctrl.size()));
+  if (leverage_out) { leverage.resize(size_t(n) * 2); FREE_TRY(call, d_leverage.download(leverage.data(), leverage.size())); }
+  if (loo_residuals_out) { loo.resize(size_t(n) * 2); FREE_TRY(call, d_loo.download(loo.data(), loo.size())); }
+  // the host's part: the columns of the lambdas that have control points, and the per-sample columns of the groups that chose
+  for (int g = 0; g < 2; ++g) {
+    summary->status[g] = sm.status[g]; summary->chosen[g] = sm.chosen[g]; summary->n_used[g] = n_used[g];
+    summary->edf[g] = sm.edf[g]; summary->score[g] = sm.score[g];
+    for (int l = 0; l < nl; ++l) {
+      if (rows[size_t(g) * nl + l].status != CALICO_FIT_OK) continue;
+      const double* src = ctrl.data() + size_t(l) * n_ctrl * 6 + 3 * g;
+      double* const targets[2] = {ctrl_all_out ? ctrl_all_out + size_t(l) * n_ctrl * 6 + 3 * g : nullptr,
+                                  l == sm.chosen[g] ? ctrl_out + 3 * g : nullptr};
+      for (double* out : targets)
+        if (out) for (int i = 0; i < n_ctrl; ++i) for (int ch = 0; ch < 3; ++ch) out[size_t(i) * 6 + ch] = src[size_t(i) * 6 + ch];
+    }
+    if (sm.chosen[g] < 0) continue;
+    for (int64_t j = 0; j < n; ++j) {
+      if (leverage_out) leverage_out[j * 2 + g] = leverage[size_t(j) * 2 + g];
+      if (loo_residuals_out) loo_residuals_out[j * 2 + g] = loo[size_t(j) * 2 + g];
+    }
+  }
+  if (rows_out) for (size_t i = 0; i < rows.size(); ++i) rows_out[i] = {rows[i].status, rows[i].replaced_pivots, rows[i].lambda, rows[i].rss, rows[i].penalty, rows[i].rms};
+  if (cv_rows_out) for (size_t i = 0; i < cv_rows.size(); ++i) cv_rows_out[i] = {cv_rows[i].edf, cv_rows[i].gcv, cv_rows[i].press, cv_rows[i].max_leverage};
+  for (int g = 0; g < 2; ++g)
+    if (summary->status[g] == CALICO_FIT_NOT_POSITIVE_DEFINITE)
+      return call.fail(CALICO_INTERNAL, std::string("no lambda of the ") + (g == 0 ? "rotation" : "position") + " grid has a factorisation cross-validation can use");
   return CALICO_OK;
 }

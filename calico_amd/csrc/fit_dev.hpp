@@ -1,10 +1,12 @@
 // fit_dev.hpp — the device code the spline fits share (fit_kernels.hip: calico_fit_spline and calico_fit_spline_smooth;
-// fit_robust_kernels.hip: calico_fit_spline_robust): the banded Cholesky solve in LDS, the wave sum, and one entry of the weighted
-// normal equations. One definition each, so that a fit that repeats another's step repeats its bits.
+// fit_robust_kernels.hip: calico_fit_spline_robust; fit_cv_kernels.hip: calico_fit_spline_cv): the banded Cholesky solve in LDS, the
+// wave sum, one entry of the weighted normal equations, and one (group, lambda) of the smoothing fit's grid. One definition each,
+// so that a fit that repeats another's step repeats its bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
+#include "kernels.hpp"
 
 namespace cal {
 
@@ -100,6 +102,71 @@ DEV void fit_normal_weighted_entry(int t, int g, int n_ctrl, int n_seg, int k, c
     }
   }
   if (e < k) band[(size_t(g) * n_ctrl + a) * k + e] = acc; else rhs[(size_t(g) * n_ctrl + a) * 3 + (e - k)] = acc;
+}
+
+// One (group g, grid entry l) of the smoothing fit, one wave: A = N_g + lambda P in LDS ([n_ctrl][k] band | [n_ctrl][3] rhs, the
+// caller's dynamic LDS), fit_band_solve, the control points into ctrl_all, c'Pc, the weighted rss, the row (written to a.rows and
+// returned, wave-uniform). Afterwards the band in LDS holds the Cholesky factor L (of A + ridge) and the rhs the control points.
+DEV FitSmoothRow fit_smooth_solve_wave(const FitSmoothArgs& a, int g, int l, int lane, double* lds) {
+  const int n = a.n_ctrl, k = a.k;
+  double* B = lds;                   // [n][k]
+  double* Y = lds + size_t(n) * k;   // [n][3]
+  const double* N = a.band + size_t(g) * n * k;
+  const double* rhs = a.rhs + size_t(g) * n * 3;
+  double lambda = g == 0 ? a.lambda_rot[l] : a.lambda_pos[l];
+  if (a.relative) {      // in units of trace(N_g) / trace(P)
+    double tn = 0.0, tp = 0.0;
+    for (int i = lane; i < n; i += 64) { tn += N[i * k]; tp += a.P[i * k]; }
+    lambda *= fit_wave_sum(tn) / fit_wave_sum(tp);
+  }
+  if (lambda == 0.0) {
+    for (int i = lane; i < n * k; i += 64) B[i] = N[i];
+  } else {
+    for (int i = lane; i < n * k; i += 64) B[i] = N[i] + lambda * a.P[i];
+  }
+  for (int i = lane; i < n * 3; i += 64) Y[i] = rhs[i];
+  __syncthreads();
+  bool bad;
+  int replaced;
+  fit_band_solve<3>(n, k, B, Y, lane, &bad, &replaced);
+  FitSmoothRow row;
+  row.status = bad ? 1 : 0; row.replaced_pivots = replaced; row.lambda = lambda;
+  if (bad) {      // this lambda's control points are not written; its sums are not numbers
+    row.rss = row.penalty = row.rms = __longlong_as_double(0x7ff8000000000000ll);
+  } else {
+    double* out = a.ctrl_all + size_t(l) * n * 6 + 3 * g;
+    for (int i = lane; i < n * 3; i += 64) out[(i / 3) * 6 + i % 3] = Y[i];
+    // c' P c over the three channels: row a of P times c, then c_a times that
+    double pen = 0.0;
+    for (int r = lane; r < n; r += 64) {
+      double p0 = 0.0, p1 = 0.0, p2 = 0.0;
+      for (int b = max(0, r - (k - 1)); b <= min(n - 1, r + (k - 1)); ++b) {
+        const double p = b <= r ? a.P[size_t(r) * k + (r - b)] : a.P[size_t(b) * k + (b - r)];
+        p0 += p * Y[b * 3]; p1 += p * Y[b * 3 + 1]; p2 += p * Y[b * 3 + 2];
+      }
+      pen += Y[r * 3] * p0 + Y[r * 3 + 1] * p1 + Y[r * 3 + 2] * p2;
+    }
+    row.penalty = fit_wave_sum(pen);
+    // the weighted residual sum of squares: lanes stride over the samples, then one fixed shuffle tree
+    double rss = 0.0;
+    for (int j = lane; j < a.n; j += 64) {
+      const double w = a.weights ? a.weights[size_t(j) * 2 + g] : 1.0;
+      if (w == 0.0) continue;
+      const int s = a.seg[j];
+      double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+      for (int i = 0; i < k; ++i) {
+        const double wi = a.W[size_t(j) * k + i];
+        r0 += wi * Y[(s + i) * 3]; r1 += wi * Y[(s + i) * 3 + 1]; r2 += wi * Y[(s + i) * 3 + 2];
+      }
+      const double* d = a.data + size_t(j) * 6 + 3 * g;
+      r0 -= d[0]; r1 -= d[1]; r2 -= d[2];
+      rss += w * (r0 * r0 + r1 * r1 + r2 * r2);
+    }
+    row.rss = fit_wave_sum(rss);
+    row.rms = sqrt(row.rss / (3.0 * double(g == 0 ? a.n_used_rot : a.n_used_pos)));
+  }
+  if (lane == 0) a.rows[size_t(g) * a.n_lambda + l] = row;
+  return row;
 }
 
 }  // namespace cal

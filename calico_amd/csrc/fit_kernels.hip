@@ -126,66 +126,11 @@ __global__ void fit_normal_weighted_kernel(int n_ctrl, int n_seg, int k, const d
   fit_normal_weighted_entry<WEIGHTED>(blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y, n_ctrl, n_seg, k, W, data, weights, seg_ptr, band, rhs);      // fit_dev.hpp
 }
 
+// (fit_smooth_solve_wave, one (group, lambda) of the grid from A = N + lambda P to its row: fit_dev.hpp, shared with the
+// cross-validated fit, fit_cv_kernels.hip)
 __global__ __launch_bounds__(64) void fit_solve_smooth_kernel(FitSmoothArgs a) {
   extern __shared__ double lds[];
-  const int n = a.n_ctrl, k = a.k, g = blockIdx.x, l = blockIdx.y, lane = threadIdx.x;
-  double* B = lds;                   // [n][k]
-  double* Y = lds + size_t(n) * k;   // [n][3]
-  const double* N = a.band + size_t(g) * n * k;
-  const double* rhs = a.rhs + size_t(g) * n * 3;
-  double lambda = g == 0 ? a.lambda_rot[l] : a.lambda_pos[l];
-  if (a.relative) {      // in units of trace(N_g) / trace(P)
-    double tn = 0.0, tp = 0.0;
-    for (int i = lane; i < n; i += 64) { tn += N[i * k]; tp += a.P[i * k]; }
-    lambda *= fit_wave_sum(tn) / fit_wave_sum(tp);
-  }
-  if (lambda == 0.0) {
-    for (int i = lane; i < n * k; i += 64) B[i] = N[i];
-  } else {
-    for (int i = lane; i < n * k; i += 64) B[i] = N[i] + lambda * a.P[i];
-  }
-  for (int i = lane; i < n * 3; i += 64) Y[i] = rhs[i];
-  __syncthreads();
-  bool bad;
-  int replaced;
-  fit_band_solve<3>(n, k, B, Y, lane, &bad, &replaced);
-  FitSmoothRow row;
-  row.status = bad ? 1 : 0; row.replaced_pivots = replaced; row.lambda = lambda;
-  if (bad) {      // this lambda's control points are not written; its sums are not numbers
-    row.rss = row.penalty = row.rms = __longlong_as_double(0x7ff8000000000000ll);
-  } else {
-    double* out = a.ctrl_all + size_t(l) * n * 6 + 3 * g;
-    for (int i = lane; i < n * 3; i += 64) out[(i / 3) * 6 + i % 3] = Y[i];
-    // c' P c over the three channels: row a of P times c, then c_a times that
-    double pen = 0.0;
-    for (int r = lane; r < n; r += 64) {
-      double p0 = 0.0, p1 = 0.0, p2 = 0.0;
-      for (int b = max(0, r - (k - 1)); b <= min(n - 1, r + (k - 1)); ++b) {
-        const double p = b <= r ? a.P[size_t(r) * k + (r - b)] : a.P[size_t(b) * k + (b - r)];
-        p0 += p * Y[b * 3]; p1 += p * Y[b * 3 + 1]; p2 += p * Y[b * 3 + 2];
-      }
-      pen += Y[r * 3] * p0 + Y[r * 3 + 1] * p1 + Y[r * 3 + 2] * p2;
-    }
-    row.penalty = fit_wave_sum(pen);
-    // the weighted residual sum of squares: lanes stride over the samples, then one fixed shuffle tree
-    double rss = 0.0;
-    for (int j = lane; j < a.n; j += 64) {
-      const double w = a.weights ? a.weights[size_t(j) * 2 + g] : 1.0;
-      if (w == 0.0) continue;
-      const int s = a.seg[j];
-      double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-      for (int i = 0; i < k; ++i) {
-        const double wi = a.W[size_t(j) * k + i];
-        r0 += wi * Y[(s + i) * 3]; r1 += wi * Y[(s + i) * 3 + 1]; r2 += wi * Y[(s + i) * 3 + 2];
-      }
-      const double* d = a.data + size_t(j) * 6 + 3 * g;
-      r0 -= d[0]; r1 -= d[1]; r2 -= d[2];
-      rss += w * (r0 * r0 + r1 * r1 + r2 * r2);
-    }
-    row.rss = fit_wave_sum(rss);
-    row.rms = sqrt(row.rss / (3.0 * double(g == 0 ? a.n_used_rot : a.n_used_pos)));
-  }
-  if (lane == 0) a.rows[size_t(g) * a.n_lambda + l] = row;
+  fit_smooth_solve_wave(a, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 
 size_t fit_solve_lds_bytes(int n_ctrl, int k) { return (size_t(n_ctrl) * k + size_t(n_ctrl) * 6) * sizeof(double); }
@@ -203,10 +148,8 @@ hipError_t launch_fit_spline(int device, const FitArgs& a, hipStream_t s) {
 
 size_t fit_solve_smooth_lds_bytes(int n_ctrl, int k) { return (size_t(n_ctrl) * k + size_t(n_ctrl) * 3) * sizeof(double); }
 
-hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s) {
-  const size_t lds = fit_solve_smooth_lds_bytes(a.n_ctrl, a.k);
-  const hipError_t e = raise_lds_limit(device, fit_solve_smooth_kernel, lds);
-  if (e != hipSuccess) return e;
+// what every (group, lambda) solve reads: the spline weights W, the penalty band P, and [band | 3 rhs] of both groups
+void launch_fit_smooth_prepare(const FitSmoothArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(fit_weights_kernel, dim3(unsigned((a.n + 255) / 256)), dim3(256), 0, s, a.n, a.k, a.stamps, a.seg, a.knots, a.basis, a.W);
   hipLaunchKernelGGL(fit_penalty_kernel, dim3((a.n_ctrl * a.k + 255) / 256), dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.derivative, a.knots, a.basis,
                      a.P);
@@ -215,6 +158,13 @@ hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStrea
     hipLaunchKernelGGL(fit_normal_weighted_kernel<true>, grid, dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.weights, a.seg_ptr, a.band, a.rhs);
   else
     hipLaunchKernelGGL(fit_normal_weighted_kernel<false>, grid, dim3(256), 0, s, a.n_ctrl, a.n_seg, a.k, a.W, a.data, a.weights, a.seg_ptr, a.band, a.rhs);
+}
+
+hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s) {
+  const size_t lds = fit_solve_smooth_lds_bytes(a.n_ctrl, a.k);
+  const hipError_t e = raise_lds_limit(device, fit_solve_smooth_kernel, lds);
+  if (e != hipSuccess) return e;
+  launch_fit_smooth_prepare(a, s);
   hipLaunchKernelGGL(fit_solve_smooth_kernel, dim3(2, a.n_lambda), dim3(64), lds, s, a);
   return hipGetLastError();
 }

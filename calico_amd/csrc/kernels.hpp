@@ -148,6 +148,19 @@ struct FitSmoothArgs {
 };
 size_t fit_solve_smooth_lds_bytes(int n_ctrl, int k);      // [band | 3 rhs] of one group
 hipError_t launch_fit_spline_smooth(int device, const FitSmoothArgs& a, hipStream_t s);
+void launch_fit_smooth_prepare(const FitSmoothArgs& a, hipStream_t s);      // its launches before the solve: W, P, [band | 3 rhs]
+// The cross-validated fit (fit_cv_kernels.hip): the smoothing fit's grid, then per (group, lambda) the band of Z = A^-1 by selected
+// inversion of the factor in LDS, edf = sum Z o N, the leverages h_j and the PRESS sum over the samples, and the choice on the
+// device. zband [2][n_lambda][n_ctrl][k] (the band's layout); edf [2][n_lambda] (NaN: the row is not eligible); partial
+// [2][n_lambda][n_blocks][2]: per block of 256 samples the PRESS terms' sum and the largest h; cv_rows [2][n_lambda] (the layout of
+// calico_spline_cv_row); leverage, loo [n][2] at each group's chosen lambda.
+struct FitCvRow { double edf, gcv, press, max_leverage; };
+struct FitCvSummary { int status[2], chosen[2]; double edf[2], score[2]; };
+struct FitCvArgs {
+  int criterion, n_blocks;
+  double* zband; double* edf; double* partial; FitCvRow* cv_rows; FitCvSummary* summary; double* leverage; double* loo;
+};
+hipError_t launch_fit_spline_cv(int device, const FitSmoothArgs& a, const FitCvArgs& c, hipStream_t s);
 // The robust fit (fit_robust_kernels.hip): iteratively reweighted least squares around the smoothing fit with n_lambda 1, one loop
 // per group, controlled on the device. state [2]: done_iter is the control word (0: running; 1 + the iteration that finished the
 // group), read first by every kernel of a later iteration. e, u, wu [n][2]: residual norms, robust weights (uploaded as 1, 0 where

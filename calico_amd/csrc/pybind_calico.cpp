@@ -254,6 +254,22 @@ calico_spline_robust_options spline_robust_options(const py::object& options) {
   }
   return o;
 }
+calico_spline_cv_options spline_cv_options(const py::object& options) {
+  calico_spline_cv_options o;
+  calico_default_spline_cv_options(&o);
+  if (options.is_none()) return o;
+  for (auto kv : py::cast<py::dict>(options)) {
+    const std::string name = py::cast<std::string>(kv.first);
+    if (name == "criterion") {
+      if (py::isinstance<py::str>(kv.second)) {
+        const std::string criterion = py::cast<std::string>(kv.second);
+        if (criterion != "gcv" && criterion != "press") throw py::value_error("criterion must be 'gcv' or 'press'");
+        o.criterion = criterion == "gcv" ? CALICO_FIT_CV_GCV : CALICO_FIT_CV_PRESS;
+      } else o.criterion = py::cast<int>(kv.second);
+    } else throw py::type_error("no cross-validated spline fit option '" + name + "'");
+  }
+  return o;
+}
 std::vector<uint8_t> to_mask(const py::object& o) {
   std::vector<uint8_t> mask;
   if (!o.is_none())
@@ -707,6 +723,62 @@ PYBIND11_MODULE(_calico, m) {
           },
           py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
           py::arg("spline_order") = Trajectory::kDefaultSplineOrder, py::arg("options") = py::none(), py::arg("robust") = py::none(),
+          py::arg("weights") = py::none())
+      // The cross-validated fit (calico_fit_spline_cv). options: as FitSplineSmooth's, a grid and no target; cv: None or a dict of
+      // calico_spline_cv_options fields (criterion: "gcv" or "press"); weights: as FitSplineSmooth's. Returns FitSplineSmooth's dict
+      // plus edf and score (one entry per group), cv_rows ([group][lambda] dicts: edf, gcv, press, max_leverage), and leverage and
+      // loo_residuals, one [rotation, position] pair per pose in time order.
+      .def(
+          "FitSplineCV",
+          [](Trajectory& self, const std::map<double, Pose3d>& poses, double knot_frequency, int spline_order, const py::object& options,
+             const py::object& cv, const py::object& weights) {
+            const calico_spline_fit_options o = spline_fit_options(options);
+            const calico_spline_cv_options co = spline_cv_options(cv);
+            std::vector<std::array<double, 2>> w;
+            if (!weights.is_none())
+              for (auto row : py::cast<py::sequence>(weights)) {
+                const auto pair = py::cast<std::vector<double>>(row);
+                if (pair.size() != 2) throw py::value_error("weights: one [rotation, position] pair per pose");
+                w.push_back({pair[0], pair[1]});
+              }
+            auto res = self.FitSplineCV(poses, knot_frequency, spline_order, o, co, w);
+            raise_if_error(res.status());
+            const calico_spline_cv_summary& sm = res.value().summary;
+            py::dict out;
+            out["status"] = py::make_tuple(sm.status[0], sm.status[1]);
+            out["chosen"] = py::make_tuple(sm.chosen[0], sm.chosen[1]);
+            out["n_used"] = py::make_tuple(sm.n_used[0], sm.n_used[1]);
+            out["edf"] = py::make_tuple(sm.edf[0], sm.edf[1]);
+            out["score"] = py::make_tuple(sm.score[0], sm.score[1]);
+            py::list groups, cv_groups;
+            const size_t nl = res.value().rows.size() / 2;
+            for (size_t g = 0; g < 2; ++g) {
+              py::list rows, cv_rows;
+              for (size_t l = 0; l < nl; ++l) {
+                const calico_spline_fit_row& r = res.value().rows[g * nl + l];
+                py::dict d;
+                d["status"] = r.status; d["replaced_pivots"] = r.replaced_pivots; d["lambda"] = r.lambda; d["rss"] = r.rss;
+                d["penalty"] = r.penalty; d["rms"] = r.rms;
+                rows.append(d);
+                const calico_spline_cv_row& c = res.value().cv_rows[g * nl + l];
+                py::dict e;
+                e["edf"] = c.edf; e["gcv"] = c.gcv; e["press"] = c.press; e["max_leverage"] = c.max_leverage;
+                cv_rows.append(e);
+              }
+              groups.append(rows);
+              cv_groups.append(cv_rows);
+            }
+            out["rows"] = groups;
+            out["cv_rows"] = cv_groups;
+            py::list h, loo;
+            for (const auto& pair : res.value().leverage) h.append(py::make_tuple(pair[0], pair[1]));
+            for (const auto& pair : res.value().loo_residuals) loo.append(py::make_tuple(pair[0], pair[1]));
+            out["leverage"] = h;
+            out["loo_residuals"] = loo;
+            return out;
+          },
+          py::arg("poses"), py::arg("knot_frequency") = Trajectory::kDefaultKnotFrequency,
+          py::arg("spline_order") = Trajectory::kDefaultSplineOrder, py::arg("options") = py::none(), py::arg("cv") = py::none(),
           py::arg("weights") = py::none())
       .def("Interpolate", [](const Trajectory& self, const std::vector<double>& stamps) {
         auto poses = self.Interpolate(stamps);

@@ -681,6 +681,73 @@ class BSpline6 {
     for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
     return OkStatus();
   }
+  /// What a cross-validated fit found: the summary (per group status, chosen lambda, edf and score there), the smoothing fit's row
+  /// and the cross-validation row of every (group, lambda), and per sample in time order the leverage h_j at the chosen lambda (0
+  /// where the weight is 0) and the leave-one-out residual e_j / (1 - h_j) (NaN there), [rotation, position].
+  struct CvFit {
+    calico_spline_cv_summary summary{};
+    std::vector<calico_spline_fit_row> rows;      // 2 x n_lambda, group-major
+    std::vector<calico_spline_cv_row> cv_rows;    // 2 x n_lambda, group-major
+    std::vector<std::array<double, 2>> leverage, loo_residuals;
+  };
+#ifdef CALICO_TEST_HOOKS
+  /// Test builds only, as fit_solver(): the solve behind FitToDataCV (calico_fit_spline_cv without its device argument).
+  using CvFitSolver = int32_t (*)(int32_t order, int32_t n_knots, const double* knots, const double* basis, int64_t n, const double* stamps,
+                                  const double* data6, const double* weights, const calico_spline_fit_options* fit,
+                                  const calico_spline_cv_options* cv, double* ctrl_out, double* ctrl_all_out, calico_spline_fit_row* rows_out,
+                                  calico_spline_cv_row* cv_rows_out, double* leverage_out, double* loo_residuals_out,
+                                  calico_spline_cv_summary* summary);
+  static CvFitSolver& cv_fit_solver() {
+    static CvFitSolver solver = nullptr;
+    return solver;
+  }
+#endif
+  /// The smoothing fit with each group's lambda chosen from `options`' grid by cross-validation (calico_fit_spline_cv on device 0:
+  /// generalised cross-validation or the leave-one-out score, `cv.criterion`); `options` takes no target. weights: as FitToDataSmooth's.
+  Status FitToDataCV(const std::vector<double>& time, const std::vector<std::array<double, 6>>& data, int order, double knot_frequency,
+                     const calico_spline_fit_options& options, const calico_spline_cv_options& cv,
+                     const std::vector<std::array<double, 2>>& weights, CvFit* fit = nullptr) {
+    if (time.empty()) return InvalidArgumentError("Attempted to fit data on empty time vector.");
+    if (data.empty()) return InvalidArgumentError("Attempted to fit on empty data.");
+    if (time.size() != data.size()) return InvalidArgumentError("Data and time vectors are not the same size.");
+    if (!weights.empty() && weights.size() != time.size()) return InvalidArgumentError("Weights and time vectors are not the same size.");
+    if (order < 2) return InvalidArgumentError("Spline order must be greater than 2. Got " + std::to_string(order));
+    if (knot_frequency <= 0) return InvalidArgumentError("Knot frequency must be greater than 0.");
+    const int nk = BuildKnots(time, order, knot_frequency), ncp = nk - order;
+    const int64_t nd = int64_t(time.size());
+    std::vector<double> flat(size_t(nd) * 6), w(weights.size() * 2), ctrl(size_t(ncp) * 6), h(size_t(nd) * 2), loo(size_t(nd) * 2);
+    for (int64_t j = 0; j < nd; ++j) for (int c = 0; c < 6; ++c) flat[size_t(j) * 6 + c] = data[size_t(j)][size_t(c)];
+    for (size_t j = 0; j < weights.size(); ++j) { w[j * 2] = weights[j][0]; w[j * 2 + 1] = weights[j][1]; }
+    CvFit found;
+    const size_t n_rows = size_t(2) * size_t(std::min(std::max(options.n_lambda, 1), CALICO_FIT_MAX_LAMBDAS));
+    found.rows.assign(n_rows, calico_spline_fit_row{});
+    found.cv_rows.assign(n_rows, calico_spline_cv_row{});
+    const double* wp = w.empty() ? nullptr : w.data();
+#ifdef CALICO_TEST_HOOKS
+    const int32_t rc = cv_fit_solver()
+        ? cv_fit_solver()(order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &cv, ctrl.data(), nullptr, found.rows.data(), found.cv_rows.data(), h.data(), loo.data(), &found.summary)
+        : calico_fit_spline_cv(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &cv, ctrl.data(), nullptr, found.rows.data(), found.cv_rows.data(), h.data(), loo.data(), &found.summary);
+#else
+    const int32_t rc = calico_fit_spline_cv(0, order, nk, knots_.data(), basis_.data(), nd, time.data(), flat.data(), wp, &options, &cv, ctrl.data(),
+                                            nullptr, found.rows.data(), found.cv_rows.data(), h.data(), loo.data(), &found.summary);
+#endif
+    const char* why = calico_last_error(nullptr);
+    if (rc == CALICO_INVALID_ARGUMENT) return InvalidArgumentError(std::string("cross-validated spline fit: ") + (why ? why : "invalid argument"));
+    if (rc == CALICO_UNIMPLEMENTED)      // the smoothing fit's ceiling: one group's [band | 3 rhs], n_ctrl (order + 3) doubles in 156 KiB
+      return UnimplementedError("cross-validated spline fit: " + std::to_string(ncp) + " control points are too many for the on-device solve; order " +
+                                std::to_string(order) + " fits at most " + std::to_string(156 * 1024 / ((order + 3) * 8)));
+    found.leverage.resize(size_t(nd));
+    found.loo_residuals.resize(size_t(nd));
+    for (int64_t j = 0; j < nd; ++j) {
+      found.leverage[size_t(j)] = {h[size_t(j) * 2], h[size_t(j) * 2 + 1]};
+      found.loo_residuals[size_t(j)] = {loo[size_t(j) * 2], loo[size_t(j) * 2 + 1]};
+    }
+    if (fit) *fit = found;
+    if (rc != CALICO_OK) return InternalError("cross-validated spline fit failed on the device");
+    ctrl_.assign(size_t(ncp), {});
+    for (int i = 0; i < ncp; ++i) for (int c = 0; c < 6; ++c) ctrl_[size_t(i)][size_t(c)] = ctrl[size_t(i) * 6 + c];
+    return OkStatus();
+  }
   /// bspline.hpp:39-72 at one time; error codes of bspline.hpp:74-85
   Status Evaluate(double t, int derivative, double out[6]) const {
     if (derivative < 0 || derivative > order_ - 1) return InvalidArgumentError("Invalid derivative for interpolation.");
@@ -786,6 +853,22 @@ class Trajectory {
     PosesToData(&stamps, &data);
     BSpline6::RobustFit fit;
     const Status st = spline_.FitToDataRobust(stamps, data, spline_order, knot_frequency, fit_options, robust_options, weights, &fit);
+    if (!st.ok()) return st;
+    return fit;
+  }
+  /// FitSpline with the smoothing fit's lambda chosen by cross-validation (calico_fit_spline_cv): the same axis-angle conversion
+  /// and phase unwrapping, then every lambda of `fit_options`' grid (no target), and per group the one with the smallest
+  /// generalised cross-validation or leave-one-out score -- no noise level of the poses is needed. The result carries the scores of
+  /// the whole grid, and per pose in time order its leverage and leave-one-out residual at the choice.
+  StatusOr<BSpline6::CvFit> FitSplineCV(const std::map<double, Pose3d>& poses_world_sensorrig, double knot_frequency, int spline_order,
+                                        const calico_spline_fit_options& fit_options, const calico_spline_cv_options& cv_options,
+                                        const std::vector<std::array<double, 2>>& weights = {}) {
+    poses_ = poses_world_sensorrig;
+    std::vector<double> stamps;
+    std::vector<std::array<double, 6>> data;
+    PosesToData(&stamps, &data);
+    BSpline6::CvFit fit;
+    const Status st = spline_.FitToDataCV(stamps, data, spline_order, knot_frequency, fit_options, cv_options, weights, &fit);
     if (!st.ok()) return st;
     return fit;
   }

@@ -408,6 +408,64 @@ int32_t calico_fit_spline_robust(int32_t device, int32_t order, int32_t n_knots,
                                  double* residuals_out /* n x 2, may be NULL */,
                                  calico_spline_robust_summary* summary);
 
+/* The smoothing fit with lambda chosen by cross-validation: calico_fit_spline_smooth's grid, and per (group, lambda) what the fit
+ * says about its own predictive error, without a noise level from the caller (target_rms needs one, and nobody has it before
+ * calibrating). With A = X^T W X + lambda P the hat matrix is H = X A^-1 X^T W; its diagonal and trace need only the entries of
+ * A^-1 inside A's band, which Takahashi's selected inversion takes from the banded Cholesky factor the fit already holds on chip
+ * (O(n_ctrl order^2), in place). A^-1 is the inverse of the matrix that was factored (A plus the fit's ridge, 1e-15 mean_diag).
+ *   h_j      w_j X_j A^-1 X_j^T, the leverage of sample j: the share of its own datum in its fitted value, in [0, 1)
+ *   edf      tr(A^-1 X^T W X) = sum_j h_j, the effective degrees of freedom per channel, from the band alone
+ *   gcv      (rss / (3 n_used)) / (1 - edf / n_used)^2, n_used = samples of weight > 0; +inf when edf >= n_used
+ *   press    sum_j w_j e_j^2 / (1 - h_j)^2 / (3 n_used), e_j = |X_j C - d_j|_2 over the group's three channels: the mean squared
+ *            leave-one-out residual, exactly what n_used refits without sample j give AT THE ROW'S ABSOLUTE LAMBDA -- a relative
+ *            lambda is converted once, from the full data, and not again for each left-out sample; +inf if any h_j >= 1
+ *   choice   per group the smallest score (gcv or press, options.criterion) over the eligible rows; a tie goes to the larger
+ *            lambda. A row whose factorisation was not finite, or replaced a pivot (A^-1 is then not the inverse of the fit's
+ *            matrix), is never eligible and its cv row is NaN. No eligible row: CALICO_FIT_NOT_POSITIVE_DEFINITE, kInternal, and
+ *            that group's columns of ctrl_out, leverage_out and loo_residuals_out are not written. n_lambda >= 2 and the choice
+ *            is the first or last entry: CALICO_FIT_CV_AT_GRID_END -- the call succeeds, the minimum may lie outside: extend the grid.
+ * ctrl_all_out and rows_out are calico_fit_spline_smooth's for the same inputs bit for bit (the solve, the lambda scaling, rss and
+ * penalty are the same code); ctrl_out holds each group's columns of ctrl_all_out at the choice. cv_rows_out (2 x n_lambda,
+ * group-major, may be NULL); leverage_out (n x 2, may be NULL) h_j at each group's chosen lambda, 0 where w_j = 0 (those data are
+ * not read); loo_residuals_out (n x 2, may be NULL) e_j / (1 - h_j), NaN where w_j = 0 and +inf where h_j >= 1. Bit-reproducible:
+ * no atomics, every sum in a fixed order; the choice is made on the device and the host reads back once.
+ * Measured (profiles/EXPERIMENTS.md, "Spline fit cross-validation"): h and edf within a few 1e-16 cond2(A) of a long-double inverse.
+ * kInvalidArgument for everything calico_fit_spline_smooth refuses, and for a non-zero target_rms (choosing is this call's own
+ * job) or an unknown criterion. kUnimplemented, outputs untouched, at the smoothing fit's LDS ceiling. */
+#define CALICO_FIT_CV_AT_GRID_END 5          /* group status: the chosen lambda is the grid's first or last entry */
+#define CALICO_FIT_CV_GCV 0
+#define CALICO_FIT_CV_PRESS 1
+typedef struct {
+  int32_t criterion;        /* CALICO_FIT_CV_GCV */
+  int32_t reserved;         /* 0 */
+} calico_spline_cv_options;
+typedef struct {            /* one per (group, lambda); all NaN where the row is not eligible */
+  double edf;
+  double gcv;
+  double press;
+  double max_leverage;      /* max_j h_j */
+} calico_spline_cv_row;
+typedef struct {            /* per group */
+  int32_t status[2];        /* CALICO_FIT_OK, CALICO_FIT_CV_AT_GRID_END or CALICO_FIT_NOT_POSITIVE_DEFINITE (no eligible lambda) */
+  int32_t chosen[2];        /* index into the grid, -1: none */
+  int64_t n_used[2];
+  double edf[2];            /* at the choice (NaN: none) */
+  double score[2];          /* the criterion's value at the choice */
+} calico_spline_cv_summary;
+void calico_default_spline_cv_options(calico_spline_cv_options* o);
+int32_t calico_fit_spline_cv(int32_t device, int32_t order, int32_t n_knots, const double* knots, const double* basis,
+                             int64_t n, const double* stamps, const double* data6,
+                             const double* weights /* n x 2 or NULL */,
+                             const calico_spline_fit_options* fit /* NULL = defaults; targets must be 0 */,
+                             const calico_spline_cv_options* cv /* NULL = defaults */,
+                             double* ctrl_out /* n_ctrl x 6 */,
+                             double* ctrl_all_out /* n_lambda x n_ctrl x 6, may be NULL */,
+                             calico_spline_fit_row* rows_out /* 2 x n_lambda, may be NULL */,
+                             calico_spline_cv_row* cv_rows_out /* 2 x n_lambda, may be NULL */,
+                             double* leverage_out /* n x 2, may be NULL */,
+                             double* loo_residuals_out /* n x 2, may be NULL */,
+                             calico_spline_cv_summary* summary);
+
 /* Outlier tags (Camera::MarkOutliersById / ClearOutliers, camera.cpp:281-301; outlier_ids_, camera.h:185): tagged
  * observations stay registered but are left out of the problem, as AddResidualsToProblem does (camera.cpp:121-124) --
  * no residual block, no residual, not counted in the summary. `is_outlier` has one byte per observation of the
