@@ -231,6 +231,29 @@ class SplineCvSummary(C.Structure):
     _fields_ = [("status", C.c_int32 * 2), ("chosen", C.c_int32 * 2), ("n_used", C.c_int64 * 2), ("edf", C.c_double * 2), ("score", C.c_double * 2)]
 
 
+class AllanOptions(C.Structure):
+    """calico_allan_options."""
+    _fields_ = [("points_per_decade", C.c_int32), ("terms", C.c_int32), ("max_tau_fraction", C.c_double), ("n_cluster_sizes", C.c_int32),
+                ("reserved", C.c_int32), ("cluster_sizes", C.POINTER(C.c_int64))]
+
+
+class AllanNoise(C.Structure):
+    """calico_allan_noise: one axis."""
+    _fields_ = [("Q", C.c_double), ("N", C.c_double), ("B", C.c_double), ("K", C.c_double), ("R", C.c_double), ("objective", C.c_double),
+                ("terms_used", C.c_int32), ("n_points", C.c_int32), ("status", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+class AllanSummary(C.Structure):
+    """calico_allan_summary."""
+    _fields_ = [("n", C.c_int64), ("sample_rate_hz", C.c_double), ("duration", C.c_double), ("N_pooled", C.c_double),
+                ("sigma_at_rate", C.c_double), ("bias_drift_over_recording", C.c_double)]
+
+
+ALLAN_MAX_CLUSTERS = 256
+ALLAN_TERM_QUANTISATION, ALLAN_TERM_WHITE, ALLAN_TERM_BIAS_INSTABILITY, ALLAN_TERM_RATE_RANDOM_WALK, ALLAN_TERM_RAMP = 1, 2, 4, 8, 16
+ALLAN_OK, ALLAN_NO_WHITE_NOISE, ALLAN_TOO_FEW_POINTS, ALLAN_NONFINITE = 0, 1, 2, 3
+
+
 class Iteration(C.Structure):
     _fields_ = [
         ("iteration", C.c_int32),
@@ -298,6 +321,7 @@ ABI_SYMBOLS = [
     "default_spline_fit_options", "fit_spline_smooth",
     "default_spline_robust_options", "fit_spline_robust",
     "default_spline_cv_options", "fit_spline_cv",
+    "default_allan_options", "imu_allan",
 ]
 # Test hooks (calico_amd/csrc/calico_hip_testing.h): exported, not part of the drop-in surface.
 TEST_SYMBOLS = ["debug_lm_control_replay", "debug_plan_info", "debug_roll_table", "debug_last_step", "debug_observability_info",
@@ -427,6 +451,11 @@ class CApi:
                 g("default_spline_cv_options", None, [CO])
                 g("fit_spline_cv", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, D, D, C.c_int64, D, D, D, FO, CO, D, D, C.POINTER(SplineFitRow),
                                                C.POINTER(SplineCvRow), D, D, C.POINTER(SplineCvSummary)])
+            if hasattr(self.lib, self.prefix + "imu_allan"):
+                I64, NO = C.POINTER(C.c_int64), C.POINTER(AllanOptions)
+                g("default_allan_options", None, [NO])
+                g("imu_allan", C.c_int32, [C.c_int32, C.c_int64, D, C.c_double, D, NO, I, I64, D, D, D, C.POINTER(AllanNoise),
+                                           C.POINTER(AllanSummary)])
             g("debug_observability_info", C.c_int32, [P, D, C.c_int32])
             g("debug_lm_control_replay", C.c_int32,
               [C.c_int32, C.c_int32, D, I, C.POINTER(SolverOptions), D, I, D])
@@ -929,6 +958,45 @@ def fit_spline_cv(api, order, knots, basis, stamps, data6, weights=None, options
                 cv_rows=[[{k: getattr(cv_rows[g * nl + l], k) for k in cv_names} for l in range(nl)] for g in range(2)],
                 leverage=h, loo_residuals=loo, chosen=list(summary.chosen),
                 summary={name: list(getattr(summary, name)) for name, _ in SplineCvSummary._fields_})
+
+
+def default_allan_options(api, cluster_sizes=None, **kw):
+    """The library's default calico_allan_options with the given fields replaced. cluster_sizes: an explicit list of cluster
+    sizes instead of the logarithmic grid (the returned struct keeps the array alive)."""
+    o = _options(AllanOptions, api.default_allan_options, "Allan variance", kw)
+    if cluster_sizes is not None:
+        m = np.ascontiguousarray(cluster_sizes, dtype=np.int64).ravel()
+        o._cluster_sizes = m
+        o.n_cluster_sizes = len(m)
+        o.cluster_sizes = m.ctypes.data_as(C.POINTER(C.c_int64))
+    return o
+
+
+def imu_allan(api, samples, stamps=None, sample_rate_hz=0.0, options=None, device=0):
+    """calico_imu_allan: the overlapping Allan variance of the three axes of a static IMU log (samples (n, 3); stamps (n,) or None
+    with sample_rate_hz) over a grid of cluster sizes, and per axis the IEEE-952 noise coefficients. options: an AllanOptions
+    (default_allan_options(api, ...)) or None. Returns a dict: cluster_sizes (c,), tau (c,), avar (c, 3), rel_err (c,), noise (three
+    dicts: Q, N, B, K, R, objective, terms_used, n_points, status) and summary (n, sample_rate_hz, duration, N_pooled,
+    sigma_at_rate, bias_drift_over_recording)."""
+    y = _f64(samples).reshape(-1, 3)
+    t = None if stamps is None else _f64(stamps).ravel()
+    if t is not None and len(t) != len(y):
+        raise ValueError("one stamp per sample")
+    nc = C.c_int32(0)
+    m = np.zeros(ALLAN_MAX_CLUSTERS, dtype=np.int64)
+    tau, rel = np.full(ALLAN_MAX_CLUSTERS, np.nan), np.full(ALLAN_MAX_CLUSTERS, np.nan)
+    avar = np.full((ALLAN_MAX_CLUSTERS, 3), np.nan)
+    noise = (AllanNoise * 3)()
+    summary = AllanSummary()
+    st = api.imu_allan(int(device), len(y), None if t is None else _dp(t), float(sample_rate_hz), _dp(y) if len(y) else None,
+                       None if options is None else C.byref(options), C.byref(nc), m.ctypes.data_as(C.POINTER(C.c_int64)), _dp(tau), _dp(avar),
+                       _dp(rel), noise, C.byref(summary))
+    _check_free(api, st)
+    c = nc.value
+    names = ("Q", "N", "B", "K", "R", "objective", "terms_used", "n_points", "status")
+    return dict(cluster_sizes=m[:c].copy(), tau=tau[:c].copy(), avar=avar[:c].copy(), rel_err=rel[:c].copy(),
+                noise=[{k: getattr(noise[a], k) for k in names} for a in range(3)],
+                summary={name: getattr(summary, name) for name, _ in AllanSummary._fields_})
 
 
 class Problem:

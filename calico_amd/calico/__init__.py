@@ -3,6 +3,6 @@ the helpers of calico/utils.py) over the MI355X HIP backend. The extension modul
 `__graft_entry__.build()` next to libcalico_hip.so; there is no other backend."""
 from .._calico import *  # noqa: F401,F403
 from .._calico import __doc__ as _backend_doc  # noqa: F401
-from .utils import (ComputeRmseHeatmapAndFeatureCount, DetectionsToCameraMeasurements,  # noqa: F401
+from .utils import (CharacterizeImuNoise, ComputeRmseHeatmapAndFeatureCount, DetectionsToCameraMeasurements,  # noqa: F401
                     InitialIntrinsics, InitializeAccelerometer, InitializeCamera, InitializeImu, InitializeIntrinsicsAndPoses, InitializePinholeAndPoses, InitializePoses,
-                    InitializeRig)
+                    InitializeRig, SetImuNoise)

@@ -337,3 +337,23 @@ def InitializeCamera(trajectory, camera, world_model, options=None) -> dict:
     camera.SetExtrinsics(T)
     camera.SetLatency(float(r["latency"]))
     return r
+
+
+def CharacterizeImuNoise(stamps, samples, options=None) -> dict:
+    """The noise of a gyroscope or an accelerometer from a recording of the sensor at rest (calico_imu_allan, on the device): the
+    overlapping Allan variance of the three axes over a logarithmic grid of cluster sizes and per axis the IEEE-952 coefficients
+    (white noise N, bias instability B, rate random walk K; quantisation and ramp through options["terms"]). stamps (n,) evenly
+    spaced (a gap raises RuntimeError: split the log), samples (n, 3). options: None or a dict of calico_allan_options fields
+    (points_per_decade, max_tau_fraction, terms, cluster_sizes). Returns a dict: cluster_sizes, tau, rel_err, avar (c, 3), noise
+    (one dict per axis) and summary (N_pooled, sigma_at_rate, bias_drift_over_recording, ...)."""
+    return _calico.CharacterizeImuNoise([float(t) for t in np.asarray(stamps, float).ravel()], np.asarray(samples, float).reshape(-1, 3), options)
+
+
+def SetImuNoise(sensor, noise, rate_hz=None) -> float:
+    """SetMeasurementNoise of a gyroscope or an accelerometer from CharacterizeImuNoise's dict: sigma = N_pooled sqrt(rate_hz), the
+    optimiser's one scalar per sensor. rate_hz None: the rate of the sensor's own registered measurements, (n - 1) / (last stamp
+    - first stamp). Returns the sigma that was set. Raises RuntimeError where the characterisation holds no white noise or the
+    sensor has no rate."""
+    rate = float(sensor.MeasurementRate() if rate_hz is None else rate_hz)
+    sensor.ApplyNoise(noise, rate)
+    return sensor.GetMeasurementNoise()

@@ -1,4 +1,4 @@
-// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp, camera_align.cpp, accel_align.cpp), free of HIP:
+// arg_rules.hpp — the argument rules the calls without a problem handle share (chart.cpp, fit.cpp, imu_align.cpp, rig.cpp, camera_align.cpp, accel_align.cpp, allan.cpp), free of HIP:
 // the standard library and the C header only, so a plain host program can test them (tests/cpp/arg_rules_check.cpp). A rule
 // returns an empty string for "fine", or the message without the call's name (FreeCall, free_call.hpp, puts that in front).
 #pragma once
@@ -204,6 +204,63 @@ inline std::string sample_weights_error(int64_t n, const double* weights, int64_
     }
   for (int g = 0; g < 2; ++g)
     if (n_used[g] == 0) return std::string(g == 0 ? "rotation" : "position") + " weights: no sample has a weight > 0";
+  return "";
+}
+
+// ---- calico_imu_allan: its options, the rate of its log, and its grid of cluster sizes ----
+inline std::string allan_options_error(const calico_allan_options& o) {
+  constexpr int all_terms = CALICO_ALLAN_TERM_QUANTISATION | CALICO_ALLAN_TERM_WHITE | CALICO_ALLAN_TERM_BIAS_INSTABILITY |
+                            CALICO_ALLAN_TERM_RATE_RANDOM_WALK | CALICO_ALLAN_TERM_RAMP;
+  if (o.terms == 0 || (o.terms & ~all_terms) != 0) return "terms must be a non-empty mask of CALICO_ALLAN_TERM_* bits";
+  if (o.n_cluster_sizes < 0 || o.n_cluster_sizes > CALICO_ALLAN_MAX_CLUSTERS)
+    return "n_cluster_sizes must be in [0, " + std::to_string(CALICO_ALLAN_MAX_CLUSTERS) + "]";
+  if (o.n_cluster_sizes > 0) return o.cluster_sizes ? "" : "null cluster_sizes";
+  if (o.points_per_decade < 1) return "points_per_decade must be >= 1";
+  if (!std::isfinite(o.max_tau_fraction) || !(o.max_tau_fraction > 0.0) || o.max_tau_fraction > 0.5) return "max_tau_fraction must be in (0, 0.5]";
+  return "";
+}
+// The rate: from the stamps where they are given ((n - 1) / span; they are finite, strictly increasing, and no step leaves
+// [0.5, 1.5] / rate), otherwise the caller's. n >= 3.
+inline std::string allan_rate_error(int64_t n, const double* stamps, double sample_rate_hz, double* rate_out) {
+  if (!stamps) {
+    if (!std::isfinite(sample_rate_hz) || !(sample_rate_hz > 0.0)) return "sample_rate_hz must be finite and > 0 where no stamps are given";
+    *rate_out = sample_rate_hz;
+    return "";
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    if (!std::isfinite(stamps[i])) return "stamp " + std::to_string(i) + " is not finite";
+    if (i > 0 && !(stamps[i] > stamps[i - 1])) return "stamps must be strictly increasing: sample " + std::to_string(i) + " is not later than the one before";
+  }
+  const double rate = double(n - 1) / (stamps[n - 1] - stamps[0]);
+  if (!std::isfinite(rate) || !(rate > 0.0)) return "the stamps give no rate";
+  for (int64_t i = 1; i < n; ++i) {
+    const double steps = (stamps[i] - stamps[i - 1]) * rate;
+    if (!(steps >= 0.5 && steps <= 1.5))
+      return "the step to sample " + std::to_string(i) + " is " + std::to_string(steps) + " of the mean step (a gap: split the log)";
+  }
+  *rate_out = rate;
+  return "";
+}
+// m_out (CALICO_ALLAN_MAX_CLUSTERS): the caller's list, or the distinct floor(10^(i / points_per_decade) + 1/2) up to max_tau_fraction n.
+inline std::string allan_grid_error(int64_t n, const calico_allan_options& o, int64_t* m_out, int* n_out) {
+  int count = 0;
+  if (o.n_cluster_sizes > 0) {
+    for (int j = 0; j < o.n_cluster_sizes; ++j) {
+      const int64_t m = o.cluster_sizes[j];
+      if (m < 1 || m >= n || 2 * m >= n) return "cluster size " + std::to_string(j) + " must satisfy 1 <= m and 2 m < n";
+      if (j > 0 && m <= o.cluster_sizes[j - 1]) return "cluster_sizes must be strictly increasing: entry " + std::to_string(j) + " is not";
+      m_out[count++] = m;
+    }
+  } else {
+    for (int i = 0; count < CALICO_ALLAN_MAX_CLUSTERS; ++i) {
+      const double v = std::floor(std::pow(10.0, double(i) / double(o.points_per_decade)) + 0.5);
+      if (!(v <= o.max_tau_fraction * double(n)) || !(2.0 * v < double(n))) break;
+      const int64_t m = int64_t(v);
+      if (count == 0 || m > m_out[count - 1]) m_out[count++] = m;
+    }
+    if (count == 0) return "the log is too short: no cluster size m has m <= max_tau_fraction n";
+  }
+  *n_out = count;
   return "";
 }
 

@@ -1,5 +1,5 @@
 // free_call.hpp — the scaffold of a call that takes no problem handle and owns its device memory (camera.cpp, chart.cpp, fit.cpp,
-// imu_align.cpp, rig.cpp, camera_align.cpp, accel_align.cpp): where its message goes, how it picks its device, and its buffers. (The three
+// imu_align.cpp, rig.cpp, camera_align.cpp, accel_align.cpp, allan.cpp): where its message goes, how it picks its device, and its buffers. (The three
 // alignment calls share more: align_host.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>

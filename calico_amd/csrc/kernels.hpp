@@ -494,4 +494,23 @@ int accalign_chunks(int n);                                                     
 hipError_t launch_accalign_iteration(const AccAlignArgs& a, hipStream_t s);          // evaluate the candidate; stage L's solve, or decide and step
 hipError_t launch_accalign_finish(const AccAlignArgs& a, hipStream_t s);             // the covariance and the RMS at the result
 
+// ---- IMU noise (allan_kernels.hip): the overlapping Allan variance of the three axes of a static log ----
+// samples [n][3]; theta [3][plane], plane >= n + 1 and even (each axis' plane starts on 16 bytes); block_sum, offsets [3][n_blocks];
+// partial [3][n_clusters][n_chunks]; out [n_clusters][3] variances, then the three axes' flags as doubles: the call's one readback.
+constexpr int kAllanScanBlock = 2048;      // samples per workgroup of the prefix sum
+constexpr int kAllanTermChunk = 4096;      // terms of the variance's sum per workgroup
+constexpr int kAllanMaxClusters = 256;
+struct AllanArgs {
+  int n, n_blocks, n_clusters, n_chunks;
+  double dt;
+  size_t plane;
+  const double* samples;
+  double* block_sum; double* offsets; double* mean; double* theta; double* partial; double* out;
+  int* flags;                              // [3], zero before the launch: the axis holds a sample that is not finite
+  int m[kAllanMaxClusters];                // the cluster sizes, ascending: 1 <= m, 2 m < n
+};
+inline int allan_blocks(int n) { return int((static_cast<long long>(n) + kAllanScanBlock - 1) / kAllanScanBlock); }
+__host__ __device__ inline int allan_chunks(int n, int m) { return int((static_cast<long long>(n) - 2 * m + kAllanTermChunk - 1) / kAllanTermChunk); }      // of n - 2m terms
+hipError_t launch_imu_allan(const AllanArgs& a, hipStream_t s);
+
 }  // namespace cal

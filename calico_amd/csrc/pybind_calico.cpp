@@ -112,6 +112,7 @@ void bind_sensor_common(PyClass& c) {
       .def("AddMeasurement", &S::AddMeasurement)
       .def("AddMeasurements", &S::AddMeasurements)
       .def("SetMeasurementNoise", &S::SetMeasurementNoise)
+      .def("GetMeasurementNoise", &S::GetMeasurementNoise)
       .def("NumberOfMeasurements", &S::NumberOfMeasurements)
       .def("ClearMeasurements", &S::ClearMeasurements)
       .def("Project",
@@ -121,6 +122,57 @@ void bind_sensor_common(PyClass& c) {
              raise_if_error(vals.status());
              return vals.value();
            });
+}
+
+// ---- IMU noise (calico_imu_allan) ----
+// options: None or a dict of calico_allan_options fields; cluster_sizes (a list) travels beside it and is kept alive in `sizes`
+calico_allan_options allan_options(const py::object& options, std::vector<int64_t>* sizes) {
+  calico_allan_options o = DefaultAllanOptions();
+  if (!options.is_none()) {
+    for (auto kv : py::cast<py::dict>(options)) {
+      const std::string name = py::cast<std::string>(kv.first);
+      if (name == "points_per_decade") o.points_per_decade = py::cast<int>(kv.second);
+      else if (name == "max_tau_fraction") o.max_tau_fraction = py::cast<double>(kv.second);
+      else if (name == "terms") o.terms = py::cast<int>(kv.second);
+      else if (name == "cluster_sizes") *sizes = py::cast<std::vector<int64_t>>(kv.second);
+      else throw py::type_error("no Allan variance option '" + name + "'");
+    }
+  }
+  if (!sizes->empty()) { o.n_cluster_sizes = int(sizes->size()); o.cluster_sizes = sizes->data(); }
+  return o;
+}
+py::dict imu_noise_dict(const ImuNoise& r) {
+  const py::ssize_t nc = py::ssize_t(r.cluster_sizes.size());
+  py::array_t<double> avar({nc, py::ssize_t(3)});
+  for (py::ssize_t j = 0; j < nc; ++j)
+    for (int c = 0; c < 3; ++c) avar.mutable_at(j, c) = r.avar[size_t(j)][c];
+  py::list noise;
+  for (const calico_allan_noise& a : r.axes) {
+    py::dict d;
+    d["Q"] = a.Q; d["N"] = a.N; d["B"] = a.B; d["K"] = a.K; d["R"] = a.R; d["objective"] = a.objective;
+    d["terms_used"] = a.terms_used; d["n_points"] = a.n_points; d["status"] = int(a.status);
+    noise.append(d);
+  }
+  py::dict sm;
+  sm["n"] = r.summary.n; sm["sample_rate_hz"] = r.summary.sample_rate_hz; sm["duration"] = r.summary.duration;
+  sm["N_pooled"] = r.summary.N_pooled; sm["sigma_at_rate"] = r.summary.sigma_at_rate;
+  sm["bias_drift_over_recording"] = r.summary.bias_drift_over_recording;
+  py::dict out;
+  out["cluster_sizes"] = py::array_t<int64_t>(nc, r.cluster_sizes.data());
+  out["tau"] = py::array_t<double>(nc, r.tau.data());
+  out["rel_err"] = py::array_t<double>(nc, r.rel_err.data());
+  out["avar"] = avar; out["noise"] = noise; out["summary"] = sm;
+  return out;
+}
+// noise: CharacterizeImuNoise's dict (its summary's N_pooled is what ApplyNoise reads)
+template <class S, class PyClass>
+void bind_imu_noise(PyClass& c) {
+  c.def("MeasurementRate", [](const S& self) { auto r = self.MeasurementRate(); raise_if_error(r.status()); return r.value(); })
+      .def("ApplyNoise", [](S& self, const py::dict& noise, double rate_hz) {
+        ImuNoise n;
+        n.summary.N_pooled = py::cast<double>(py::cast<py::dict>(noise["summary"])["N_pooled"]);
+        raise_if_error(self.ApplyNoise(n, rate_hz));
+      }, py::arg("noise"), py::arg("rate_hz"));
 }
 
 // ---- intrinsic calibration (calico_camera_calibrate): what the two bindings share ----
@@ -426,6 +478,7 @@ PYBIND11_MODULE(_calico, m) {
       .value("kAccelerometerVectorNav", AccelerometerIntrinsicsModel::kAccelerometerVectorNav);
   py::class_<Accelerometer, std::shared_ptr<Accelerometer>, Sensor> accelerometer(m, "Accelerometer");
   bind_sensor_common<Accelerometer>(accelerometer);
+  bind_imu_noise<Accelerometer>(accelerometer);
 
   py::enum_<GyroscopeIntrinsicsModel>(m, "GyroscopeIntrinsicsModel")
       .value("kNone", GyroscopeIntrinsicsModel::kNone)
@@ -434,6 +487,7 @@ PYBIND11_MODULE(_calico, m) {
       .value("kGyroscopeVectorNav", GyroscopeIntrinsicsModel::kGyroscopeVectorNav);
   py::class_<Gyroscope, std::shared_ptr<Gyroscope>, Sensor> gyroscope(m, "Gyroscope");
   bind_sensor_common<Gyroscope>(gyroscope);
+  bind_imu_noise<Gyroscope>(gyroscope);
 
   // ---- camera ----
   py::enum_<CameraIntrinsicsModel>(m, "CameraIntrinsicsModel")
@@ -955,6 +1009,24 @@ PYBIND11_MODULE(_calico, m) {
       .def_readwrite("initial_trust_region_radius", &SolverOptions::initial_trust_region_radius)
       .def_readwrite("max_trust_region_radius", &SolverOptions::max_trust_region_radius);
   m.def("DefaultSolverOptions", &DefaultSolverOptions);
+
+  // IMU noise from a recording at rest (calico_imu_allan): stamps (n), samples (n, 3); options: None or a dict of
+  // calico_allan_options fields (cluster_sizes: a list). Returns a dict: cluster_sizes, tau, rel_err, avar (c, 3), noise (three
+  // dicts: Q, N, B, K, R, objective, terms_used, n_points, status) and summary.
+  m.def(
+      "CharacterizeImuNoise",
+      [](const std::vector<double>& stamps, const py::array_t<double, py::array::c_style | py::array::forcecast>& samples, const py::object& options,
+         int device) {
+        if (samples.ndim() != 2 || samples.shape(1) != 3) throw py::value_error("samples must be (n, 3)");
+        std::vector<Vector3d> y(size_t(samples.shape(0)));
+        for (py::ssize_t i = 0; i < samples.shape(0); ++i) y[size_t(i)] = Vector3d(samples.at(i, 0), samples.at(i, 1), samples.at(i, 2));
+        std::vector<int64_t> sizes;
+        const calico_allan_options o = allan_options(options, &sizes);
+        auto r = CharacterizeImuNoise(stamps, y, o, device);
+        raise_if_error(r.status());
+        return imu_noise_dict(r.value());
+      },
+      py::arg("stamps"), py::arg("samples"), py::arg("options") = py::none(), py::arg("device") = 0);
 
   // Rig calibration (calico_rig_calibrate): rig_frames[f] maps a camera's index in `cameras` to its detections {feature id:
   // pixel} in rig frame f; options: None or a dict of calico_rig_options fields. Sets the extrinsics of the cameras whose

@@ -1105,6 +1105,7 @@ class SensorCommon : public Sensor {
     if (sigma <= 0.0) return InvalidArgumentError("Sigma must be greater than 0.");
     sigma_ = sigma; return OkStatus();
   }
+  double GetMeasurementNoise() const { return sigma_; }
   /// index of this sensor in the Problem it last added its residuals to (-1: none yet): Covariance::Predictions
   int ProblemSensor() const { return problem_sensor_; }
  protected:
@@ -1544,6 +1545,37 @@ using GyroscopeMeasurement = ImuMeasurement;
 using AccelerometerObservationId = ImuObservationId;
 using AccelerometerMeasurement = ImuMeasurement;
 
+/// What CharacterizeImuNoise returns: calico_imu_allan's outputs -- the grid of cluster sizes, the Allan variance of the three
+/// axes at each of them (avar[j][axis]), the IEEE-952 coefficients per axis, and the summary with the pooled white-noise density.
+struct ImuNoise {
+  std::vector<int64_t> cluster_sizes;
+  std::vector<double> tau, rel_err;
+  std::vector<Vector3d> avar;
+  std::array<calico_allan_noise, 3> axes{};
+  calico_allan_summary summary{};
+  /// The sigma SetMeasurementNoise takes for a recording of this sensor at rate_hz: N_pooled sqrt(rate_hz).
+  double MeasurementSigma(double rate_hz) const { return summary.N_pooled * std::sqrt(rate_hz); }
+};
+inline calico_allan_options DefaultAllanOptions() { calico_allan_options o; calico_default_allan_options(&o); return o; }
+/// The noise of a gyroscope or an accelerometer from a recording at rest (calico_imu_allan, on the device): stamps (n, evenly
+/// spaced: a gap is kInvalidArgument) and samples (n). The fit's status per axis is in axes[i].status (CALICO_ALLAN_*).
+inline StatusOr<ImuNoise> CharacterizeImuNoise(const std::vector<double>& stamps, const std::vector<Vector3d>& samples,
+                                               const calico_allan_options& options = DefaultAllanOptions(), int device = 0) {
+  static_assert(sizeof(Vector3d) == 3 * sizeof(double), "samples travel as n x 3 doubles");
+  if (stamps.size() != samples.size()) return InvalidArgumentError("CharacterizeImuNoise: one stamp per sample");
+  ImuNoise r;
+  int32_t nc = 0;
+  r.cluster_sizes.assign(CALICO_ALLAN_MAX_CLUSTERS, 0);
+  r.tau.assign(CALICO_ALLAN_MAX_CLUSTERS, 0.0); r.rel_err.assign(CALICO_ALLAN_MAX_CLUSTERS, 0.0);
+  r.avar.assign(CALICO_ALLAN_MAX_CLUSTERS, Vector3d());
+  const int st = calico_imu_allan(device, int64_t(samples.size()), stamps.empty() ? nullptr : stamps.data(), 0.0,
+                                  samples.empty() ? nullptr : samples[0].data(), &options, &nc, r.cluster_sizes.data(), r.tau.data(),
+                                  r.avar[0].data(), r.rel_err.data(), r.axes.data(), &r.summary);
+  if (st != CALICO_OK) return Status(static_cast<StatusCode>(st), calico_last_error(nullptr));
+  r.cluster_sizes.resize(size_t(nc)); r.tau.resize(size_t(nc)); r.rel_err.resize(size_t(nc)); r.avar.resize(size_t(nc));
+  return r;
+}
+
 template <int KIND>
 class ImuSensor : public SensorCommon {
  public:
@@ -1598,6 +1630,22 @@ class ImuSensor : public SensorCommon {
       stamps->push_back(m->id.stamp);
       for (int i = 0; i < 3; ++i) values->push_back(m->measurement[i]);
     }
+  }
+  /// The rate of the registered measurements: (n - 1) / (last stamp - first stamp).
+  StatusOr<double> MeasurementRate() const {
+    if (id_to_measurement_.size() < 2) return FailedPreconditionError("Sensor " + name_ + " has fewer than two measurements: no rate.");
+    double first = id_to_measurement_.begin()->first.stamp, last = first;
+    for (const auto& kv : id_to_measurement_) { first = std::min(first, kv.first.stamp); last = std::max(last, kv.first.stamp); }
+    if (!(last > first)) return FailedPreconditionError("The measurements of sensor " + name_ + " share one stamp: no rate.");
+    return double(id_to_measurement_.size() - 1) / (last - first);
+  }
+  /// The sensor's sigma from a noise characterisation (CharacterizeImuNoise on a recording at rest) for measurements at rate_hz:
+  /// SetMeasurementNoise(noise.MeasurementSigma(rate_hz)). The optimiser's sigma is one scalar per sensor: the pooled density.
+  Status ApplyNoise(const ImuNoise& noise, double rate_hz) {
+    if (!std::isfinite(rate_hz) || !(rate_hz > 0.0)) return InvalidArgumentError("ApplyNoise: rate_hz must be finite and > 0.");
+    if (!(noise.summary.N_pooled > 0.0) || !std::isfinite(noise.summary.N_pooled))
+      return InvalidArgumentError("ApplyNoise: the characterisation holds no white-noise density (N_pooled is not > 0).");
+    return SetMeasurementNoise(noise.MeasurementSigma(rate_hz));
   }
   const std::unordered_map<ImuObservationId, Vector3d, ImuObservationIdHash>& residuals() const { return id_to_residual_; }
   /// gyroscope.cpp:56-82 / accelerometer.cpp:76-123

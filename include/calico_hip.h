@@ -137,8 +137,8 @@ int32_t calico_problem_create(calico_problem** out, int32_t device);
 void calico_problem_destroy(calico_problem* p);
 /* Message of the last non-OK status on this handle ("" if none). p == NULL: of the calling thread's last non-OK call that
  * takes no handle or was given none (calico_camera_unproject, calico_camera_project_points, calico_camera_resect,
- * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align, calico_camera_align, calico_accel_align); like a handle's message it
- * is not cleared by a later success. */
+ * calico_camera_calibrate, calico_rig_calibrate, calico_imu_align, calico_camera_align, calico_accel_align, calico_imu_allan); like a
+ * handle's message it is not cleared by a later success. */
 const char* calico_last_error(const calico_problem* p);
 void calico_default_solver_options(calico_solver_options* o);
 
@@ -1225,6 +1225,81 @@ int32_t calico_accel_align(int32_t device, int32_t order, int32_t n_knots, const
                            const calico_accel_alignment_options* o /* NULL = defaults */, double* q_rig_accel_out,
                            double* t_rig_accel_out, double* bias_out, double* gravity_world_out, double* latency_out,
                            double* cov_out /* 13 x 13, may be NULL */, calico_accel_alignment_summary* summary);
+
+/* ---- IMU noise from a static log: overlapping Allan variance and the IEEE-952 coefficients ---- */
+/* The sigma that calico_problem_add_sensor takes for a gyroscope or an accelerometer, from a recording of the sensor at rest,
+ * on the device. With dt = 1 / rate, theta_0 = 0, theta_k = dt Sum_{i<k} (y_i - mean(y)) and tau = m dt, per axis
+ *   avar(tau) = 1 / (2 tau^2 (n - 2m)) Sum_{k=0}^{n-2m-1} (theta_{k+2m} - 2 theta_{k+m} + theta_k)^2,
+ * the overlapping Allan variance (the mean is removed for conditioning only: the second difference does not see it), and
+ *   rel_err(m) = 1 / sqrt(2 (n / m - 1)),
+ * IEEE-952's relative error of its square root, the same for the three axes; rel_err^-2 is the fit's weight.
+ *   grid     options->n_cluster_sizes == 0: m = the distinct values of floor(10^(i / points_per_decade) + 1/2), i = 0, 1, ...,
+ *            while m <= max_tau_fraction n and 2m < n. Otherwise the caller's list.
+ *   fit      per axis, in the variance domain, over the enabled terms (options->terms, CALICO_ALLAN_TERM_* bits):
+ *              avar(tau) ~ 3 Q^2 / tau^2 + N^2 / tau + (2 ln 2 / pi) B^2 + K^2 tau / 3 + R^2 tau^2 / 2,
+ *            the non-negative least squares of Sum_i w_i (1 - model_i / avar_i)^2, w_i = 2 (n / m_i - 1), over the squared
+ *            coefficients. With at most five unknowns the NNLS is exact: every non-empty subset of the enabled terms is
+ *            solved (Householder QR of the column-normalised design), and of the subsets whose coefficients are all >= 0 the
+ *            least objective wins; ties (objectives within Sum_i w_i (64 eps)^2, the rounding of their residuals) go to the
+ *            fewer terms, then to the lower mask. Cluster sizes whose variance is 0 or not finite are left out.
+ *   summary  N_pooled = sqrt((N_x^2 + N_y^2 + N_z^2) / 3): the optimiser's sigma is one scalar per sensor; sigma_at_rate =
+ *            N_pooled sqrt(sample_rate_hz). For a calibration recording at another rate, sigma is N_pooled sqrt(that rate).
+ *            duration = n / sample_rate_hz; bias_drift_over_recording = max over the axes of K sqrt(duration): what the rate
+ *            random walk moves the bias by over a recording of that length, to hold against the optimiser's constant bias.
+ * Outputs: n_clusters_out (1), cluster_sizes_out, tau_out and rel_err_out (CALICO_ALLAN_MAX_CLUSTERS each), avar_out
+ * (CALICO_ALLAN_MAX_CLUSTERS x 3; row j holds the three axes at cluster size j, n_clusters rows are written), noise_out (3).
+ * The kernels (allan_kernels.hip) sum in FP64 in orders that n and m alone fix -- a three-phase prefix sum over blocks of
+ * kAllanScanBlock = 2048 samples, then per (cluster size, axis) partial sums over chunks of kAllanTermChunk = 4096 terms -- so
+ * repeated calls are bit-identical, the axes do not see each other, and an explicit list gives what the same grid gives.
+ * Needs no problem handle: owns its device memory, message in calico_last_error(NULL).
+ * CALICO_INVALID_ARGUMENT, before the device is touched: n < 3; a NULL samples or output; stamps that are not finite and
+ * strictly increasing, or with a step outside [0.5, 1.5] / rate, rate = (n - 1) / (t_last - t_first) -- the message names
+ * the first such sample ("a gap: split the log"); without stamps a sample_rate_hz that is not finite and > 0 (with stamps it
+ * is not read); points_per_decade < 1, max_tau_fraction outside (0, 0.5], terms 0 or with unknown bits; a list that is NULL,
+ * longer than CALICO_ALLAN_MAX_CLUSTERS, not strictly increasing, or with an m < 1 or 2m >= n. n > 2^31 - 1: CALICO_UNIMPLEMENTED.
+ * Out of scope: non-uniform sampling and gap filling, the modified, Hadamard and total variances, confidence intervals
+ * beyond rel_err, and a sigma per axis inside the optimiser. */
+#define CALICO_ALLAN_MAX_CLUSTERS 256
+#define CALICO_ALLAN_TERM_QUANTISATION 1          /* Q: 3 Q^2 / tau^2 */
+#define CALICO_ALLAN_TERM_WHITE 2                 /* N: N^2 / tau (angle / velocity random walk) */
+#define CALICO_ALLAN_TERM_BIAS_INSTABILITY 4      /* B: (2 ln 2 / pi) B^2 */
+#define CALICO_ALLAN_TERM_RATE_RANDOM_WALK 8      /* K: K^2 tau / 3 */
+#define CALICO_ALLAN_TERM_RAMP 16                 /* R: R^2 tau^2 / 2 */
+#define CALICO_ALLAN_OK 0
+#define CALICO_ALLAN_NO_WHITE_NOISE 1             /* N came back 0 */
+#define CALICO_ALLAN_TOO_FEW_POINTS 2             /* fewer usable cluster sizes than enabled terms: the coefficients are 0 */
+#define CALICO_ALLAN_NONFINITE 3                  /* the axis holds a NaN or Inf: its variances are NaN, the other axes are unaffected */
+typedef struct {
+  int32_t points_per_decade;      /* 10 */
+  int32_t terms;                  /* WHITE | BIAS_INSTABILITY | RATE_RANDOM_WALK */
+  double max_tau_fraction;        /* 0.1; at most 0.5 */
+  int32_t n_cluster_sizes;        /* 0: the grid above */
+  int32_t reserved;               /* 0 */
+  const int64_t* cluster_sizes;   /* n_cluster_sizes of them, strictly increasing */
+} calico_allan_options;
+typedef struct {                  /* one axis */
+  double Q, N, B, K, R;           /* 0 where the term is not enabled or not in terms_used */
+  double objective;               /* Sum_i w_i (1 - model_i / avar_i)^2 at the result */
+  int32_t terms_used;             /* the winning subset */
+  int32_t n_points;               /* cluster sizes that took part */
+  uint8_t status;                 /* CALICO_ALLAN_* */
+  uint8_t reserved[7];
+} calico_allan_noise;
+typedef struct {
+  int64_t n;
+  double sample_rate_hz;          /* the rate used: from the stamps where they are given */
+  double duration;                /* n / sample_rate_hz */
+  double N_pooled;
+  double sigma_at_rate;
+  double bias_drift_over_recording;
+} calico_allan_summary;
+void calico_default_allan_options(calico_allan_options* o);
+int32_t calico_imu_allan(int32_t device, int64_t n, const double* stamps /* n, or NULL */, double sample_rate_hz,
+                         const double* samples /* n x 3, as calico_problem_add_imu_residuals takes them */,
+                         const calico_allan_options* options /* NULL: defaults */,
+                         int32_t* n_clusters_out, int64_t* cluster_sizes_out, double* tau_out,
+                         double* avar_out /* n_clusters x 3 */, double* rel_err_out /* n_clusters */,
+                         calico_allan_noise* noise_out /* 3, one per axis */, calico_allan_summary* summary);
 
 /* ---- multi-GPU -------------------------------------------------------- */
 /* Observations shard across ranks; the only exchange is the sum of the
